@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — SVGF Mpixels/s (full pipeline) at 1080p on N GPUs of one node, plus the a-trous kernel's HBM roofline.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 A "step" is one svgf_denoise() call = one full SVGF pass (temporal accumulation + 5 edge-avoiding a-trous levels +
@@ -9,8 +9,13 @@ history rotation) over one 1920x1080 frame of the synthetic Cornell-like sequenc
 are resident in HBM before the timed region starts.  N > 1: one process and one SVGF context per GPU, every rank
 denoises its own independent sequence (weak scaling, no data-path collective); value = pixels of all ranks / max time.
 
+A plain run does what the headline figure needs: set-up, warm-up, the trial that picks the way the timed steps run, the K
+timed steps, the outputs (--dump-outputs DIR: the frame the last timed step returned, rank 0, as DIR/denoised.npy in float32)
+and the JSON line.  --full adds everything else below: per-kernel events in the timed steps, the other leg, the latency
+and caller legs, the isolated roofline frames, the cadence leg, telemetry, the PMC record and the CPU baseline.
+
 Rank 0 prints ONE JSON line.  `value` is the pipelined throughput (K calls enqueued back to back, one synchronisation at
-the end); `latency_ms_sync` is the metric as SURVEY.md §8(d)(i) words it — the median wall time of one svgf_denoise +
+the end); `latency_ms_sync` (--full) is the metric as SURVEY.md §8(d)(i) words it — the median wall time of one svgf_denoise +
 svgf_sync pair, what the reference's synchronous denoise() (src/denoise.cu:401) gives its caller.  `roofline` is for the
 dominant kernel (the a-trous level): algorithmic bytes per launch (56 B/pixel) / mean launch duration from
 HIP events attached to the kernel dispatches of the launch stream inside the timed region (hipExtLaunchKernelGGL: the kernel's
@@ -156,6 +161,23 @@ def cpu_baseline(pkg, frames, params, budget_s=25.0, threads=None, what="full-SV
     return res
 
 
+DUMP_LIMIT_BYTES = 64 * 1024 * 1024
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: every array as DIR/<name>.npy in float32.  An array above its share of the 64 MB budget is replaced by a fixed,
+    seeded sample of its pixels (rows of the last axis, in their original order) as DIR/<name>_sample.npy."""
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // max(1, len(arrays)) - 4096      # (room for the .npy header)
+    for name, arr in arrays.items():
+        arr = np.ascontiguousarray(arr, dtype=np.float32)
+        if arr.nbytes > share:
+            rows = arr.reshape(-1, arr.shape[-1])
+            idx = np.sort(np.random.default_rng(12345).choice(rows.shape[0], share // rows[0].nbytes, replace=False))
+            arr, name = rows[idx], name + "_sample"
+        np.save(os.path.join(dirname, name + ".npy"), arr)
+
+
 def pkg_cpu_slice(rank, world):
     """N > 1: each rank's host thread (and its telemetry sampler) is pinned to its own slice of the CPUs this process may use, so
     that eight launch loops on a 16-CPU cgroup do not migrate over each other.  Returns the slice (None: not pinned)."""
@@ -176,7 +198,7 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline leg")
     ap.add_argument("--config", default="1080p-static", choices=["1080p-static", "1080p-moving", "4k-static", "4k-moving", "4k-room", "config1"],
                     help="1080p-static = BASELINE configs[1] (the default, the headline metric); 1080p-moving = configs[2] "
                          "(64-frame moving-camera sequence); 4k-static = configs[3]; 4k-moving = the same at 3840x2160; 4k-room = "
@@ -193,7 +215,7 @@ def main():
     ap.add_argument("--overlap", action="store_true", help="(old name of the default; kept so that old command lines still run)")
     ap.add_argument("--no-overlap", action="store_true", help="same as --no-pipeline")
     ap.add_argument("--latency-calls", type=int, default=60,
-                    help="svgf_denoise + svgf_sync pairs of the latency measurement (SURVEY.md 8(d)(i): median of >= 50 after 10 warm-ups)")
+                    help="svgf_denoise + svgf_sync pairs of the latency measurement (--full; SURVEY.md 8(d)(i): median of >= 50 after 10 warm-ups)")
     ap.add_argument("--host-inputs", action="store_true",
                     help="render the synthetic frames with numpy and upload them (default: the device-side producer, "
                          "svgf_synth_render, SURVEY.md 8f row f1; both give the same frames bit for bit)")
@@ -202,13 +224,19 @@ def main():
                          "svgf_denoise_planar) instead of handing over 52-byte AoS texels; static-camera configs only (the planes of "
                          "both history parities are filled once, before the timed region, like the AoS inputs)")
     ap.add_argument("--cadence-hz", type=float, default=60.0,
-                    help="also measure the state an interactive renderer lives in (N = 1 only): producer + svgf_denoise + display pack once per "
+                    help="--full: also measure the state an interactive renderer lives in (N = 1 only): producer + svgf_denoise + display pack once per "
                          "1/Hz seconds with the GPU idle in between, timed by HIP events around the denoise; 0 = skip the leg")
     ap.add_argument("--cadence-frames", type=int, default=40)
     ap.add_argument("--trial-reps", type=int, default=3, help="pipelined / ordered regions of --steps frames each, alternating, that decide which way the timed steps run")
     ap.add_argument("--min-warmup-seconds", type=float, default=0.6,
                     help="untimed steps continue after --warmup until this much wall time has passed (clock ramp, history "
                          "fill): a --steps 20 run then measures what a --steps 200 run measures")
+    ap.add_argument("--full", action="store_true",
+                    help="also run and report every measurement beside the headline figure: per-kernel events in the timed steps, the other "
+                         "leg, latency, caller, isolated roofline and cadence legs, telemetry, the PMC record, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the frame the last timed step returned (rank 0) as DIR/denoised.npy (float32; "
+                         "above 64 MB a fixed, seeded sample of its pixels, DIR/denoised_sample.npy)")
     a = ap.parse_args()
 
     # the CPU-baseline leg: one OpenMP thread per physical core, pinned (read by libgomp when the oracle library is loaded)
@@ -345,9 +373,10 @@ def main():
     if pipeline:
         den_o = pkg.Denoiser(W, H, device=local_rank)
         op = pkg.SvgfParams.from_buffer_copy(params).set(inputs_ready=0)
-    PROFILE_STRIDE = 10     # an event pair attached to every kernel dispatch of every 10th timed step (a timed frame runs ~25 us longer)
-    den.profile_stride(PROFILE_STRIDE)
-    den.profile_enable(a.steps)
+    PROFILE_STRIDE = 10     # --full: an event pair attached to every kernel dispatch of every 10th timed step (a timed frame runs ~25 us longer)
+    if a.full:
+        den.profile_stride(PROFILE_STRIDE)
+        den.profile_enable(a.steps)
 
     if a.planar_inputs:
         if moving or a.host_inputs:
@@ -382,9 +411,9 @@ def main():
     # (a sysfs walk, a device-property query) takes milliseconds; between the warm-up and the timed region that was enough idle
     # time for the GPU to leave its sustained power state, and the first timed frames paid the ramp back up: 0.266 -> 0.313 ms per
     # step on the driver's 20-step command with identical kernels (profiles/r04_ab_bench_r03_vs_r04_tree.log, r04_bisect*.log).
-    # (SVGF_BENCH_NO_TELEMETRY=1: no sampler thread at all.)
-    tm_all = telemetry.Sampler(local_rank, period_s=float(os.environ.get("SVGF_BENCH_TELEMETRY_PERIOD", "0.005")))
-    if not os.environ.get("SVGF_BENCH_NO_TELEMETRY"):
+    # (SVGF_BENCH_NO_TELEMETRY=1: no sampler thread at all; a plain run, without --full, has none either.)
+    tm_all = telemetry.Sampler(local_rank, period_s=float(os.environ.get("SVGF_BENCH_TELEMETRY_PERIOD", "0.005"))) if a.full else None
+    if tm_all is not None and not os.environ.get("SVGF_BENCH_NO_TELEMETRY"):
         tm_all.start()
     # warm-up is run with profiling slots too, then the frame counter restarts so slots hold the timed steps only
     # the first 12 frames of the process (cold: clocks and socket power not ramped yet): timed, part of the warm-up
@@ -400,7 +429,9 @@ def main():
     cold_ms = (time.perf_counter() - t_c0) / 12 * 1e3
     t_w = time.perf_counter()
     n_w = 13
-    while n_w < a.warmup or time.perf_counter() - t_w < a.min_warmup_seconds:
+    # (every stretch of untimed frames ends on the last frame of the nsrc-frame cycle, and the timed steps start on its first: the
+    # history the timed steps inherit, and so what they compute, is the same from run to run however many frames the clock allowed)
+    while n_w < a.warmup or time.perf_counter() - t_w < a.min_warmup_seconds or n_w % nsrc:
         step(n_w)
         n_w += 1
         if n_w % 32 == 0:
@@ -432,7 +463,7 @@ def main():
 
     def settle(fn, seconds):
         t, k = time.perf_counter(), 0
-        while time.perf_counter() - t < seconds:
+        while time.perf_counter() - t < seconds or k % nsrc:
             fn(k)
             k += 1
             if k % 32 == 0:
@@ -441,15 +472,20 @@ def main():
 
     pipeline_trial = None
     if pipeline:
-        den_o.profile_stride(PROFILE_STRIDE)
-        den_o.profile_enable(a.steps)
+        if a.full:
+            den_o.profile_stride(PROFILE_STRIDE)
+            den_o.profile_enable(a.steps)
         tr_o, tr_p = [], []
         settle(step_ordered, 0.25)
         for _ in range(max(1, a.trial_reps)):
-            den_o.profile_enable(a.steps); tr_o.append(region(step_ordered, a.steps))
+            if a.full:
+                den_o.profile_enable(a.steps)
+            tr_o.append(region(step_ordered, a.steps))
         settle(step_pipe, 0.25)
         for _ in range(max(1, a.trial_reps)):
-            den.profile_enable(a.steps); tr_p.append(region(step_pipe, a.steps))
+            if a.full:
+                den.profile_enable(a.steps)
+            tr_p.append(region(step_pipe, a.steps))
         m_o, m_p = float(np.median(tr_o)), float(np.median(tr_p))
         pipeline_trial = {"pipelined_ms": [round(t, 5) for t in tr_p], "ordered_ms": [round(t, 5) for t in tr_o],
                           "pipelined_median_ms": round(m_p, 5), "ordered_median_ms": round(m_o, 5), "frames_each": a.steps,
@@ -461,13 +497,17 @@ def main():
     den_first, den = den, cur["den"]
     t_warm_end = time.perf_counter()
     untimed_before = calls["n"]
-    den.profile_enable(a.steps)
+    if a.full:
+        den.profile_enable(a.steps)
     t_region0 = time.perf_counter()
     # N > 1: the ranks' warm-ups and trials end at different times; they meet on a host-side (gloo) group while their GPUs keep running
     # untimed frames (farm.timed_region), then the bracketing barrier + synchronisation, then the K timed steps
     dt, pixels = pkg.farm.timed_region(step, a.steps, 0, lambda: torch.cuda.synchronize(dev), dist=dist, device=None if share_device else dev,
                                        busy_group=busy_group)
     t_region1 = time.perf_counter()
+    if a.dump_outputs and rank == 0:
+        # what the last timed step returned: step(i) writes outs[i & 1] and the timed steps are i = 0 .. K-1 (timed_region ends synchronised)
+        dump_outputs(a.dump_outputs, {"denoised": outs[(a.steps - 1) & 1].cpu().numpy()})
     if os.environ.get("SVGF_BENCH_DEBUG"):
         dbg = [region(step, a.steps) for _ in range(4)]
         dbg2 = [pkg.farm.timed_region(step, a.steps, 0, lambda: torch.cuda.synchronize(dev), dist=dist, device=None if share_device else dev)[0] / a.steps * 1e3 for _ in range(3)]
@@ -479,6 +519,43 @@ def main():
     if dist is not None and world > 1:
         per_rank = [None] * world
         dist.all_gather_object(per_rank, mine)
+
+    metric = ("SVGF Mpixels/s (one non-temporal level, BASELINE configs[0]) at 800x800; \u00e0-trous HBM GB/s vs roofline" if a.config == "config1"
+              else "SVGF Mpixels/s (full pipeline) at 4K; \u00e0-trous HBM GB/s vs roofline" if a.config.startswith("4k")
+              else "SVGF Mpixels/s (full pipeline) at 1080p; \u00e0-trous HBM GB/s vs roofline")
+    config = {"workload": (f"cornell-like {W}x{H}, variance fill + ONE a-trous level (temporal off), " if a.config == "config1" else
+                           f"room.txt (primitives + 2 810 triangles, device ray-cast) {W}x{H}, full SVGF (temporal + 5 a-trous levels, history_level 1), " if a.config == "4k-room" else
+                           f"cornell-like {W}x{H}, full SVGF (temporal + 5 a-trous levels, history_level 1), ")
+                          + ("moving camera, 64-frame sequence replayed" if moving else "static camera, steady-state history")
+                          + ("; G-buffer handed over as planes written in place by the producer (svgf_denoise_planar)" if a.planar_inputs else "")
+                          + "; one independent sequence per GPU", "name": a.config,
+              "width": W, "height": H, "atrous_levels": 1 if a.config == "config1" else NLEVEL,
+              "parallelism": f"replicas{world}" + ("-sharing-one-device(test-only)" if share_device else "")}
+
+    def finish():
+        for dd in {id(x): x for x in (den, den_o, den_first)}.values():
+            dd.free()
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+
+    if not a.full:
+        # a plain run: the headline figure and what it rests on; every other measurement is --full's
+        if not (np.isfinite(outs[0].sum().item()) and np.isfinite(outs[1].sum().item())):
+            raise SystemExit("bench: non-finite output")
+        if rank == 0:
+            print(json.dumps({
+                "metric": metric, "value": round(pixels / dt / 1e6, 2), "unit": "Mpixels/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
+                "warmup_steps_run": n_w, "untimed_steps_before_timed_region": untimed_before,
+                "ms_per_step": round(dt / a.steps * 1e3, 5), "higher_is_better": True, "scaling": "weak",
+                "state": "sustained", "sustained_after_s": round(t_warm_end - t_c0, 3), "cold_ms_per_step": round(cold_ms, 5),
+                "cold_is": "frames 2-13 of the process", "first_frame_ms": round(first_frame_ms, 3),
+                "frame_pipeline": pipeline, "frame_pipeline_trial": pipeline_trial,
+                "frame_pipeline_status": pipeline_status, "frame_pipeline_refused": pipeline_refused, "context_create_ms": round(create_ms, 3),
+                "per_rank": per_rank, "idle_before_timed_region_ms": round((t_region0 - t_warm_end) * 1e3, 3),
+                "vs_baseline": None, "dtype": "f32", "data": "synthetic", "config": config, "full": False}), flush=True)
+        finish()
+        return
 
     # per-kernel durations of the timed steps (HIP events attached to the dispatches on the launch stream)
     atrous_ms, temporal_ms, fused_ms = [], [], []
@@ -679,9 +756,7 @@ def main():
         iso_us = float(np.mean(iso_atrous_ms)) * 1e3
         iso_gbs = bytes_px * W * H / (iso_us * 1e-6) / 1e9
         line = {
-            "metric": ("SVGF Mpixels/s (one non-temporal level, BASELINE configs[0]) at 800x800; \u00e0-trous HBM GB/s vs roofline" if a.config == "config1"
-                       else "SVGF Mpixels/s (full pipeline) at 4K; \u00e0-trous HBM GB/s vs roofline" if a.config.startswith("4k")
-                       else "SVGF Mpixels/s (full pipeline) at 1080p; \u00e0-trous HBM GB/s vs roofline"),
+            "metric": metric,
             "value": round(value, 2), "unit": "Mpixels/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
             "warmup_steps_run": n_w,
             # every frame this process ran before the K timed ones: the warm-up (>= --warmup steps and >= --min-warmup-seconds), the trial's
@@ -710,14 +785,7 @@ def main():
             "telemetry": {"timed_region": tm_all.summary(t_region0, t_region1), "latency_calls": tm_all.summary(t_lat0, t_lat1),
                           "isolated_16_frames": tm_all.summary(t_iso0, t_iso1)},
             "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": (f"cornell-like {W}x{H}, variance fill + ONE a-trous level (temporal off), " if a.config == "config1" else
-                                    f"room.txt (primitives + 2 810 triangles, device ray-cast) {W}x{H}, full SVGF (temporal + 5 a-trous levels, history_level 1), " if a.config == "4k-room" else
-                                    f"cornell-like {W}x{H}, full SVGF (temporal + 5 a-trous levels, history_level 1), ")
-                                   + ("moving camera, 64-frame sequence replayed" if moving else "static camera, steady-state history")
-                                   + ("; G-buffer handed over as planes written in place by the producer (svgf_denoise_planar)" if a.planar_inputs else "")
-                                   + "; one independent sequence per GPU", "name": a.config,
-                       "width": W, "height": H, "atrous_levels": 1 if a.config == "config1" else NLEVEL,
-                       "parallelism": f"replicas{world}" + ("-sharing-one-device(test-only)" if share_device else "")},
+            "config": config, "full": True,
             # the dominant kernel's OWN figure: every a-trous launch of 16 consecutive ORDERED frames (one kernel at a time on the GPU),
             # sustained state, the dispatches' own begin / end timestamps — what `rocprofv3 --kernel-trace --stats` of an ordered run
             # reproduces (profiles/).  The same launches as they ran among the timed steps (with the frame pipeline: sharing the GPU with
@@ -771,11 +839,7 @@ def main():
             else:
                 line["cpu_baseline"] = cpu_baseline(pkg, host_frames, params)
         print(json.dumps(line), flush=True)
-    for dd in {id(x): x for x in (den, den_o, den_first)}.values():
-        dd.free()
-    if dist is not None:
-        dist.barrier()
-        dist.destroy_process_group()
+    finish()
 
 
 if __name__ == "__main__":

@@ -12,7 +12,9 @@ Binaries (oracle/ref/Makefile, built only where /root/reference exists; they tra
   python tests/golden/make_ref_scene_goldens.py --gpu  --out gpurun_out/ref_scenes     # on the GPU box
   python tests/golden/make_ref_scene_goldens.py --host --out tests/golden/ref_scenes   # in the build container
 then copy gpurun_out/ref_scenes/*.npz to tests/golden/ref_scenes/ and commit.  The .npz files use the schema of
-tests/golden/ref_gpu/ (make_ref_gpu_goldens.py) plus `pbo` / `pattern` (display-pack golden).
+tests/golden/ref_gpu/ (make_ref_gpu_goldens.py) plus `pbo` / `pattern` (display-pack golden).  --host also writes
+scene_files.tar.gz: a copy of the reference's scene text, OBJ models and textures, and ref_mesh_triangles.npz (the triangle
+list the reference's loader built per scene), so that the parser / loader tests need nothing outside the repository.
 """
 from __future__ import annotations
 
@@ -102,6 +104,32 @@ def host_part(out):
         json.dump(rec, f, indent=0, separators=(",", ":"))
     base = os.path.join(out, "ref_savepng_37x5")
     run([os.path.join(REF, "ref_host_tools"), "png", base])
+    # the triangle lists the reference's own loader builds (tinyobjloader + Scene::loadMesh), corners as position | normal | uv
+    tris = {}
+    for s in ("cornell", "room", "bunny", "diamond"):
+        mesh = os.path.join(out, "_mesh.bin")
+        run([os.path.join(REF, "ref_host_tools"), "mesh", s + ".txt", mesh], cwd=os.path.join(REF, "scenes"))
+        raw = open(mesh, "rb").read()
+        os.remove(mesh)
+        ntri, ng, _ = struct.unpack_from("<3i", raw, 0)
+        tris[s] = np.frombuffer(raw, "<f4", ntri * 24, 12 + ng * 12).reshape(ntri, 24)
+    # that list and the scene files themselves (scene text, OBJ models, textures: data the parser / loader tests read), as one
+    # archive with fixed timestamps and owners, so that the same inputs give the same bytes
+    import gzip
+    import io
+    import tarfile
+    npz = io.BytesIO()
+    np.savez_compressed(npz, **tris)
+    members = [("ref_mesh_triangles.npz", npz.getvalue())]
+    for rel in [s + ".txt" for s in ("cornell", "room", "bunny", "diamond")] + \
+               [sub + "/" + f for sub in ("Models", "Textures") for f in sorted(os.listdir(os.path.join(REF, "scenes", sub)))]:
+        members.append((rel, open(os.path.join(REF, "scenes", rel), "rb").read()))
+    with open(os.path.join(out, "scene_files.tar.gz"), "wb") as fo, gzip.GzipFile(fileobj=fo, mode="wb", mtime=0) as gz, \
+            tarfile.open(fileobj=gz, mode="w", format=tarfile.PAX_FORMAT) as tar:
+        for rel, data in members:
+            ti = tarfile.TarInfo(rel)
+            ti.size, ti.mode = len(data), 0o644
+            tar.addfile(ti, io.BytesIO(data))
     print("wrote", out, {k: (len(v["materials"]), len(v["geoms"])) for k, v in rec.items()})
 
 

@@ -111,7 +111,7 @@ def test_bench_distributed_branch_runs_with_one_rank_on_rccl():
     from conftest import ROOT
     env = dict(os.environ, SVGF_BENCH_FORCE_DIST="1", MASTER_ADDR="127.0.0.1")
     env.pop("MASTER_PORT", None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2", "--no-cpu-baseline",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2", "--full", "--no-cpu-baseline",
                         "--min-warmup-seconds", "0.1", "--cadence-frames", "16"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -157,7 +157,7 @@ def test_bench_launcher_two_ranks_sharing_one_gpu():
     env = dict(os.environ, SVGF_BENCH_SHARE_DEVICE="1")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2", "--no-cpu-baseline",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2", "--full", "--no-cpu-baseline",
                         "--min-warmup-seconds", "0.1", "--latency-calls", "50"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -191,7 +191,7 @@ def test_bench_launcher_eight_ranks_sharing_one_gpu_on_configs4():
     env = dict(os.environ, SVGF_BENCH_SHARE_DEVICE="1")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--config", "4k-room", "--steps", "3", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--config", "4k-room", "--steps", "3", "--warmup", "1", "--full",
                         "--min-warmup-seconds", "0.05", "--latency-calls", "50", "--trial-reps", "1"],
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=1500, env=env)
     assert r.returncode == 0, r.stderr[-3000:]

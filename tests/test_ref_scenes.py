@@ -132,16 +132,26 @@ def test_save_png_matches_reference_png(pkg, tmp_path):
     assert np.array_equal(got[finite], want[finite])
 
 
-REF_SCENES_DIR = "/root/reference/scenes"
+@pytest.fixture(scope="module")
+def ref_scenes_dir(tmp_path_factory):
+    """The reference's scenes/ directory (scene text, OBJ models, textures) and the triangle lists its own loader built from it
+    (oracle/_ref/ref_host_tools mesh), stored as one archive by tests/golden/make_ref_scene_goldens.py --host."""
+    import tarfile
+    d = tmp_path_factory.mktemp("ref_scenes")
+    with tarfile.open(os.path.join(DIR, "scene_files.tar.gz")) as tar:
+        if hasattr(tarfile, "data_filter"):
+            tar.extractall(d, filter="data")
+        else:
+            tar.extractall(d)
+    return str(d)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_SCENES_DIR), reason="the reference's scene files exist in the build container only")
 @pytest.mark.parametrize("scene", ["cornell", "room", "bunny", "diamond"])
-def test_scene_parser_matches_reference_loader(pkg, scene):
+def test_scene_parser_matches_reference_loader(pkg, scene, ref_scenes_dir):
     """scene.parse_scene / geom_array against what the reference's own Scene loader (src/scene.cpp) parsed from its four
     scene files (tests/golden/ref_scenes/scene_records.json, dumped by oracle/_ref/ref_host_tools)."""
     rec = json.load(open(os.path.join(DIR, "scene_records.json")))[scene]
-    sc = pkg.scene.parse_scene(open(os.path.join(REF_SCENES_DIR, scene + ".txt")).read())
+    sc = pkg.scene.parse_scene(open(os.path.join(ref_scenes_dir, scene + ".txt")).read())
     assert tuple(rec["camera"]["resolution"]) == sc.camera["res"]
     assert np.allclose(rec["camera"]["position"], sc.camera["eye"], atol=0) and np.allclose(rec["camera"]["lookAt"], sc.camera["lookat"], atol=0)
     assert np.allclose(rec["camera"]["up"], sc.camera["up"], atol=0) and np.float32(rec["camera"]["fov"][1]) == np.float32(sc.camera["fovy"])
@@ -164,35 +174,25 @@ def test_scene_parser_matches_reference_loader(pkg, scene):
         assert r["material"] == g["materialid"]
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_SCENES_DIR), reason="the reference's scene / model / texture files exist in the build container only")
 @pytest.mark.parametrize("scene", ["cornell", "room", "bunny", "diamond"])
-def test_obj_loader_matches_reference_triangles(pkg, scene, tmp_path):
+def test_obj_loader_matches_reference_triangles(pkg, scene, ref_scenes_dir):
     """mesh.scene_triangles (our OBJ reader + Scene::loadMesh's transforms) against the triangle list the reference's own
     loader built (ref_host_tools mesh, i.e. tinyobjloader + src/scene.cpp:234-311): the same triangles, corner for corner,
     as a set — the reference's loader emits shapes in another order, which only changes triangle ids."""
-    import subprocess
-    tool = os.path.join(ROOT, "oracle", "_ref", "ref_host_tools")
-    if not os.path.exists(tool):
-        pytest.skip("oracle/_ref/ref_host_tools not built")
     from importlib import import_module
     mesh = import_module(pkg.__name__ + ".mesh")
-    out = str(tmp_path / "m.bin")
-    subprocess.run([tool, "mesh", scene + ".txt", out], cwd=os.path.join(ROOT, "oracle", "_ref", "scenes"), check=True,
-                   stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    raw = open(out, "rb").read()
-    ntri, ng, _ = struct.unpack_from("<3i", raw, 0)
-    ref = np.frombuffer(raw, "<f4", ntri * 24, 12 + ng * 12).reshape(ntri, 24)
-    sc = pkg.scene.parse_scene(open(os.path.join(REF_SCENES_DIR, scene + ".txt")).read())
-    tp, tn, tu, tobj = mesh.scene_triangles(sc, os.path.join(REF_SCENES_DIR, "Models"))
+    ref = np.load(os.path.join(ref_scenes_dir, "ref_mesh_triangles.npz"))[scene]
+    ntri = ref.shape[0]
+    sc = pkg.scene.parse_scene(open(os.path.join(ref_scenes_dir, scene + ".txt")).read())
+    tp, tn, tu, tobj = mesh.scene_triangles(sc, os.path.join(ref_scenes_dir, "Models"))
     assert len(tp) == ntri
     ours = np.concatenate([tp, tn, tu], axis=-1).reshape(ntri, 24)
     key = lambda a: a[np.lexsort(np.round(a[:, ::-1].astype(np.float64), 4).T)]          # noqa: E731
     assert np.allclose(key(ours), key(ref), rtol=2e-6, atol=2e-6)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_SCENES_DIR), reason="the reference's scene / model / texture files exist in the build container only")
 @pytest.mark.parametrize("name,scene", [("cornell96_static", "cornell"), ("cornell128x72_moving", "cornell"), ("room128x72_static_sepcolor", "room")])
-def test_first_hit_with_meshes_matches_reference_gbuffer(pkg, name, scene):
+def test_first_hit_with_meshes_matches_reference_gbuffer(pkg, name, scene, ref_scenes_dir):
     """mesh.first_hit_gbuffer — primitives + triangle meshes + textures — against the G-buffer the reference's own path
     tracer wrote for the same camera (src/pathtrace.cu:316-323): geomId per pixel, world position, interpolated mesh
     normal (with the reference's corner weights), material / texture albedo (JPEG decoders differ by <= 2/255)."""
@@ -200,9 +200,9 @@ def test_first_hit_with_meshes_matches_reference_gbuffer(pkg, name, scene):
     mesh = import_module(pkg.__name__ + ".mesh")
     z = np.load(os.path.join(DIR, name + ".npz"))
     W, H = int(z["W"]), int(z["H"])
-    sc = pkg.scene.parse_scene(open(os.path.join(REF_SCENES_DIR, scene + ".txt")).read())
-    tris = mesh.scene_triangles(sc, os.path.join(REF_SCENES_DIR, "Models"))
-    tex = mesh.load_textures(sc, os.path.join(REF_SCENES_DIR, "Textures"))
+    sc = pkg.scene.parse_scene(open(os.path.join(ref_scenes_dir, scene + ".txt")).read())
+    tris = mesh.scene_triangles(sc, os.path.join(ref_scenes_dir, "Models"))
+    tex = mesh.load_textures(sc, os.path.join(ref_scenes_dir, "Textures"))
     for f in (0, z["cams"].shape[0] - 1):
         c = z["cams"][f]
         cam = dict(right=c[0:3].astype(np.float32), up=c[3:6].astype(np.float32), view=c[6:9].astype(np.float32),

@@ -13,17 +13,17 @@ cd $R
 if [ "$2" != "quick" ]; then
 timeout 2400 python -m pytest tests -m gpu -q -rA 2>&1 | grep -E "passed|failed|error|worst|pipelined|PASSED.*(4k|room|1080p)|max rel" | tail -40 > $O/gpu_tests.txt
 fi
-for i in 1 2 3; do python bench.py --gpus 1 --steps 20 --warmup 5 $([ $i != 1 ] && echo --no-cpu-baseline) > $O/bench_line_driver_cmd_$i.json 2>> $O/bench_driver_cmd.err; done
+for i in 1 2 3; do python bench.py --full --gpus 1 --steps 20 --warmup 5 $([ $i != 1 ] && echo --no-cpu-baseline) > $O/bench_line_driver_cmd_$i.json 2>> $O/bench_driver_cmd.err; done
 cp $O/bench_line_driver_cmd_1.json $O/bench_line_driver_cmd.json
-python bench.py --steps 20 --warmup 5 --no-pipeline --no-cpu-baseline > $O/bench_line_driver_cmd_no_pipeline.json 2>> $O/bench_driver_cmd.err
-GPU_MAX_HW_QUEUES=1 python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_line_driver_cmd_one_hw_queue.json 2>> $O/bench_driver_cmd.err
-python bench.py --no-cpu-baseline > $O/bench_line.json 2>/dev/null
-python bench.py --no-cpu-baseline --planar-inputs > $O/bench_line_planar_inputs.json 2>/dev/null
-python bench.py --no-cpu-baseline --config 1080p-moving > $O/bench_line_1080p_moving.json 2>/dev/null
-python bench.py --no-cpu-baseline --config 4k-static > $O/bench_line_4k_static.json 2>/dev/null
-python bench.py --no-cpu-baseline --config 4k-room > $O/bench_line_4k_room.json 2>/dev/null
-python bench.py --config config1 > $O/bench_line_config1.json 2>/dev/null
-python bench.py --steps 20 --warmup 5 --no-cpu-baseline --cadence-hz 144 --cadence-frames 100 > $O/bench_line_cadence_144hz.json 2>/dev/null
+python bench.py --full --steps 20 --warmup 5 --no-pipeline --no-cpu-baseline > $O/bench_line_driver_cmd_no_pipeline.json 2>> $O/bench_driver_cmd.err
+GPU_MAX_HW_QUEUES=1 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_line_driver_cmd_one_hw_queue.json 2>> $O/bench_driver_cmd.err
+python bench.py --full --no-cpu-baseline > $O/bench_line.json 2>/dev/null
+python bench.py --full --no-cpu-baseline --planar-inputs > $O/bench_line_planar_inputs.json 2>/dev/null
+python bench.py --full --no-cpu-baseline --config 1080p-moving > $O/bench_line_1080p_moving.json 2>/dev/null
+python bench.py --full --no-cpu-baseline --config 4k-static > $O/bench_line_4k_static.json 2>/dev/null
+python bench.py --full --no-cpu-baseline --config 4k-room > $O/bench_line_4k_room.json 2>/dev/null
+python bench.py --full --config config1 > $O/bench_line_config1.json 2>/dev/null
+python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --cadence-hz 144 --cadence-frames 100 > $O/bench_line_cadence_144hz.json 2>/dev/null
 python tools/clock_states.py --json $O/clock_states.json > $O/clock_states.txt 2>/dev/null
 python tools/probe.py --variants 0,4,2 --reps 200 --sustain 0.6 > $O/probe_1080p.log 2>&1
 python tools/probe.py --variants 0,2 --size 3840x2160 --frames 8 --reps 60 --sustain 0.6 > $O/probe_4k.log 2>&1
@@ -35,11 +35,11 @@ python tools/soak.py --frames 6000 --random 97 > $O/pipeline_soak.log 2>&1
 python tools/soak.py --frames 1500 --random 97 --size 801x603 >> $O/pipeline_soak.log 2>&1
 cd /tmp && export TMPDIR=/tmp
 # ---- 1080p: kernel trace of the driver's command, SQ pass, HBM passes ----
-rocprofv3 --kernel-trace --stats -d $O/prof -o p --output-format csv -- python $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --cadence-hz 0 > $O/bench_line_under_rocprofv3.json 2>/dev/null
+rocprofv3 --kernel-trace --stats -d $O/prof -o p --output-format csv -- python $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --cadence-hz 0 > $O/bench_line_under_rocprofv3.json 2>/dev/null
 cp $(find $O/prof -name "*kernel_stats.csv" | head -1) $O/rocprofv3_kernel_stats_bench.csv 2>/dev/null
 rm -rf $O/prof
 # the same with every frame ordered on the one stream: one kernel at a time on the GPU, the kernels' own durations
-rocprofv3 --kernel-trace --stats -d $O/prof -o p --output-format csv -- python $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-pipeline --cadence-hz 0 > $O/bench_line_no_pipeline_under_rocprofv3.json 2>/dev/null
+rocprofv3 --kernel-trace --stats -d $O/prof -o p --output-format csv -- python $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-pipeline --cadence-hz 0 > $O/bench_line_no_pipeline_under_rocprofv3.json 2>/dev/null
 cp $(find $O/prof -name "*kernel_stats.csv" | head -1) $O/rocprofv3_kernel_stats_bench_ordered.csv 2>/dev/null
 rm -rf $O/prof
 rocprofv3 -i $R/tools/pmc2.txt -d $O/pmc_sq -o p --output-format csv -- python $R/tools/probe.py --variants 0 --frames 6 > /dev/null 2>&1
@@ -51,7 +51,7 @@ python $R/tools/pmc_summary.py $O/pmc_hbm "atrous" > $O/pmc_hbm.txt
 python $R/tools/pmc_summary.py $O/pmc_hbm "k_temporal" >> $O/pmc_hbm.txt
 rm -rf $O/pmc_hbm
 # ---- 3840x2160 (configs[3]): the same three ----
-rocprofv3 --kernel-trace --stats -d $O/prof4k -o p --output-format csv -- python $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-pipeline --config 4k-static --cadence-hz 0 > $O/bench_line_4k_no_pipeline_under_rocprofv3.json 2>/dev/null
+rocprofv3 --kernel-trace --stats -d $O/prof4k -o p --output-format csv -- python $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-pipeline --config 4k-static --cadence-hz 0 > $O/bench_line_4k_no_pipeline_under_rocprofv3.json 2>/dev/null
 cp $(find $O/prof4k -name "*kernel_stats.csv" | head -1) $O/rocprofv3_kernel_stats_4k_ordered.csv 2>/dev/null
 rm -rf $O/prof4k
 rocprofv3 -i $R/tools/pmc2.txt -d $O/pmc_sq4k -o p --output-format csv -- python $R/tools/probe.py --variants 0 --size 3840x2160 --frames 6 --reps 10 > /dev/null 2>&1
