@@ -24,6 +24,8 @@ SVGF_OK = 0
 STATE_HISTORY_LENGTH, STATE_MOMENTS, STATE_COLOR_HISTORY, STATE_VARIANCE_TEMPORAL, STATE_COLOR_ACC = range(5)
 KERNEL_TEMPORAL, KERNEL_PREPARE, KERNEL_ATROUS, KERNEL_DEBUGVIEW, KERNEL_COPYOUT, KERNEL_FUSED = 1, 2, 3, 4, 5, 6
 MAX_LEVELS = 10
+# svgf_exp_level_kernels (experiments build): the kernel an a-trous level ran
+LEVEL_KERNEL_NAMES = ("fused", "lane", "lane2y", "strip", "lattice", "gather")
 
 # every symbol include/svgf.h declares
 EXPORTS = ["svgf_version", "svgf_params_default", "svgf_create", "svgf_destroy", "svgf_reset", "svgf_denoise",
@@ -301,6 +303,21 @@ class Denoiser:
         """Wait for what has been enqueued on `stream` only (svgf_sync waits for the whole device, as the reference does)."""
         s = None if stream is None else (stream if isinstance(stream, int) else stream.cuda_stream)
         self._check(self.lib.svgf_sync_stream(self.h, s), "svgf_sync_stream")
+
+    def level_kernels(self) -> list[tuple[str, int, float | None, float | None]]:
+        """Experiments build only: per a-trous level of the last frame, (kernel name, step, lane estimate us, strip estimate us);
+        the estimates are None where the automatic lane / strip choice was not consulted.  Kernel names: LEVEL_KERNEL_NAMES."""
+        if not hasattr(self.lib, "svgf_exp_level_kernels"):
+            raise SvgfError("level_kernels: this context is not in the experiments build (Denoiser(..., experiments=True))")
+        kinds, steps = (C.c_int * MAX_LEVELS)(), (C.c_int * MAX_LEVELS)()
+        lane, strip = (C.c_double * MAX_LEVELS)(), (C.c_double * MAX_LEVELS)()
+        f = self.lib.svgf_exp_level_kernels
+        f.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int]
+        n = f(self.h, kinds, steps, lane, strip, MAX_LEVELS)
+        if n < 0:
+            raise SvgfError(f"svgf_exp_level_kernels -> {n}")
+        est = lambda v: None if np.isnan(v) else float(v)      # noqa: E731
+        return [(LEVEL_KERNEL_NAMES[kinds[k]], int(steps[k]), est(lane[k]), est(strip[k])) for k in range(n)]
 
     def set_capture(self, on: bool = True):
         self._check(self.lib.svgf_set_capture(self.h, 1 if on else 0), "svgf_set_capture")

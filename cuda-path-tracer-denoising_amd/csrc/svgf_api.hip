@@ -69,6 +69,14 @@ struct svgf_ctx {
     int n_cu;              // compute units of the context's device (launch-geometry cost model of the kernel choice)
     signed char lane_cheaper[8];   // per log2(step): -1 not evaluated yet, 1 the lane kernel's estimate is the lower one
     signed char fuse_pays;         // -1 not evaluated yet, 1: the fused temporal + first-level kernel is the cheaper way through both
+#ifdef SVGF_BUILD_EXPERIMENTS
+    double est_lane_us[8], est_strip_us[8];   // per log2(step): the two estimates lane_cheaper[] was decided from
+    // the a-trous levels of the last frame (svgf_exp_level_kernels): kernel (K_FUSED ..), step, and the estimates the automatic
+    // choice compared (NaN where it was not consulted)
+    int lk_n;
+    int lk_kind[SVGF_MAX_LEVELS], lk_step[SVGF_MAX_LEVELS];
+    double lk_lane_us[SVGF_MAX_LEVELS], lk_strip_us[SVGF_MAX_LEVELS];
+#endif
     float *nrm[2];
     int *gid[2];
     float *pos[2];
@@ -398,6 +406,23 @@ extern "C" int svgf_sync_stream(svgf_ctx *c, void *stream)
 
 extern "C" const char *svgf_last_error(const svgf_ctx *c) { return c ? c->err : g_create_err; }
 extern "C" int svgf_width(const svgf_ctx *c) { return c ? c->W : 0; }
+#ifdef SVGF_BUILD_EXPERIMENTS
+// The a-trous levels of the context's last frame, in order: the kernel each ran (0 fused first level, 1 lane, 2 lane with two
+// y-phases, 3 strip, 4 lattice, 5 gather), its step, and the lane / strip estimates (us) the automatic choice compared for that
+// step (NaN where kernel_variant != 0 or the choice was not made between those two).  Writes min(n, levels) entries of every
+// non-null array; returns the number of levels (0 for a frame without a cascade), or a negative error.
+extern "C" int svgf_exp_level_kernels(const svgf_ctx *c, int *kinds, int *steps, double *lane_us, double *strip_us, int n)
+{
+    if (!c || n < 0) return SVGF_ERR_INVALID_ARG;
+    for (int k = 0; k < c->lk_n && k < n; k++) {
+        if (kinds) kinds[k] = c->lk_kind[k];
+        if (steps) steps[k] = c->lk_step[k];
+        if (lane_us) lane_us[k] = c->lk_lane_us[k];
+        if (strip_us) strip_us[k] = c->lk_strip_us[k];
+    }
+    return c->lk_n;
+}
+#endif
 extern "C" int svgf_height(const svgf_ctx *c) { return c ? c->H : 0; }
 
 extern "C" int svgf_set_capture(svgf_ctx *c, int on)
@@ -662,13 +687,32 @@ static int enable_pipeline(svgf_ctx *c)
 // rounds x (segment rows + fixed rows) x the time of a row (1.86 us lane, 1.16 us strip: 42.7 against 48.8 us at 1920x1080).
 // The cheaper one runs.  Measured against that model at nine sizes (profiles/r03_exp_widths*.log): within 5 %, same choice as
 // the stopwatch everywhere — lane at 1920, 3840, 1600, 3440, 800 (steps 2-8), 2560 and 1280 (steps 2-8, 32); strip at 1024,
-// 2048, and at steps 16 of 800 / 1280 / 2560.
+// 2048, and at steps 16 of 800 / 1280 / 2560.  That holds for frames taller than about six lattice rows per level (H / step >= 6);
+// shorter phases are one segment each on both kernels, and the one-round launches then favour the strip kernel's shorter rows
+// at the coarse steps (tests/test_kernel_geometry_gpu.py holds the per-level table for a 256-CU device).
+// Every level of a phase shorter than 3 lattice rows is one segment on the lane kernel, whose segment search (4 .. nb_max + 1
+// rows) then evaluates nothing: such a level is costed here as that one segment, rounds x (nb_max + 6) rows.  The rounds of a
+// one-segment geometry do not depend on H, so they are those of a 3-row phase (the search's one candidate there: 4 + 6 rows).
+static double lane_estimate_us(svgf_ctx *c, const AtrousArgs &a)
+{
+    const int nb_max = (a.H + a.step - 1) / a.step;
+    if (nb_max >= 3) return atrous_lane_estimate_us(a, c->n_cu);
+    AtrousArgs three = a;
+    three.H = 3 * a.step;
+    return atrous_lane_estimate_us(three, c->n_cu) * (double)(nb_max + 6) / 10.0;
+}
+
 static bool lane_pays(svgf_ctx *c, const AtrousArgs &a)
 {
     int l = 0;
     while ((1 << l) < a.step && l < 7) l++;
-    if (c->lane_cheaper[l] < 0)          // depends on the image size and the device only: evaluated once per context and step
-        c->lane_cheaper[l] = atrous_lane_estimate_us(a, c->n_cu) <= atrous_strip_estimate_us(a, c->n_cu) ? 1 : 0;
+    if (c->lane_cheaper[l] < 0) {        // depends on the image size and the device only: evaluated once per context and step
+        const double lane = lane_estimate_us(c, a), strip = atrous_strip_estimate_us(a, c->n_cu);
+        c->lane_cheaper[l] = lane <= strip ? 1 : 0;
+#ifdef SVGF_BUILD_EXPERIMENTS
+        c->est_lane_us[l] = lane; c->est_strip_us[l] = strip;
+#endif
+    }
     return c->lane_cheaper[l] != 0;
 }
 
@@ -680,7 +724,7 @@ static bool lane_pays(svgf_ctx *c, const AtrousArgs &a)
 static bool fuse_pays(svgf_ctx *c, const AtrousArgs &a)
 {
     if (c->fuse_pays < 0) {
-        const double lane = atrous_lane_supported(a) ? atrous_lane_estimate_us(a, c->n_cu) : 1e30;
+        const double lane = atrous_lane_supported(a) ? lane_estimate_us(c, a) : 1e30;
         const double strip = atrous_strip_supported(a) ? atrous_strip_estimate_us(a, c->n_cu) : 1e30;
         const double level = lane < strip ? lane : strip;
         const double temporal_us = 0.0256e-3 * (double)c->W * (double)c->H;
@@ -884,6 +928,9 @@ static int denoise_frame(svgf_ctx *c, void *out_rgb_dev, const void *in_rgb_dev,
         c->ev_hist_valid[pq] = 1; c->ev_hist_cap[pq] = cap_id; hist_event_recorded = true;
     }
 
+#ifdef SVGF_BUILD_EXPERIMENTS
+    c->lk_n = 0;
+#endif
     // 2) debug views, pass-through or the a-trous cascade (:373-394)
     if (p->right_view_option == 1) {
         LAUNCH(SVGF_KERNEL_DEBUGVIEW, launch_debug_hlen(c->hlen[c->cur], out, n, 100.0f, s));   // pre-update lengths (:374)
@@ -930,6 +977,17 @@ static int denoise_frame(svgf_ctx *c, void *out_rgb_dev, const void *in_rgb_dev,
             else if (strip) which = K_STRIP;
             else if (lattice) which = K_LATTICE;
             else which = K_GATHER;
+#ifdef SVGF_BUILD_EXPERIMENTS
+            {
+                int l = 0;
+                while ((1 << l) < a.step && l < 7) l++;
+                const bool asked = p->kernel_variant == 0 && (which == K_FUSED || which == K_LANE || which == K_STRIP) && c->lane_cheaper[l] >= 0;
+                c->lk_kind[c->lk_n] = (int)which; c->lk_step[c->lk_n] = a.step;
+                c->lk_lane_us[c->lk_n] = asked ? c->est_lane_us[l] : __builtin_nan("");
+                c->lk_strip_us[c->lk_n] = asked ? c->est_strip_us[l] : __builtin_nan("");
+                c->lk_n++;
+            }
+#endif
             // Pre-blur rows (y-1, y+1 of the full-resolution image) of the lane / strip kernels.  At steps >= 16 they are
             // read as 4-byte gathers out of 16-byte colour texels whose lines nobody else on the XCD touches (PMC: 75.6 /
             // 72.6 B/px fetched against 40 algorithmic); there the kernels read them from a zero-margined 4-byte variance plane

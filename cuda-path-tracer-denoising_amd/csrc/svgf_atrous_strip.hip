@@ -652,12 +652,16 @@ __global__ __launch_bounds__(TX * ROWS + loader_threads(TX, ROWS)) void k_atrous
 // Segment length: every (strip, phase, segment) is one workgroup and `capacity` of them run at a time, so the grid runs in
 // rounds of equal-length workgroups.  Returns the minimum of rounds * (L + fixed cost) — in lattice rows; the fixed cost being
 // the 4 halo rows + the exposed prologue latency — and the segment length L that reaches it.
+// A phase of fewer than 3 * ROWS lattice rows leaves the search range empty: the one segment of nb_max rows is then the only
+// geometry, and it is costed like any other (the estimate is never the -1 of "nothing evaluated").
 long strip_segment_search(int n_strips, int S, int nb_max, int ROWS, int capacity, int *best_L_out)
 {
     int best_L = nb_max;
     long best_cost = -1;
     static const int fixed_rows = SVGF_TUNE("strip_fixed_rows", 8);   // tuning only
-    for (int L = ROWS * 4; L <= nb_max + ROWS; L++) {        // L need not be a multiple of ROWS: the last iteration idles rows
+    const bool one_segment = ROWS * 4 > nb_max + ROWS;
+    const int L_lo = one_segment ? nb_max : ROWS * 4, L_hi = one_segment ? nb_max : nb_max + ROWS;
+    for (int L = L_lo; L <= L_hi; L++) {                     // L need not be a multiple of ROWS: the last iteration idles rows
         const int segs_l = (nb_max + L - 1) / L;
         // (phase, segment) groups are dealt round-robin to the 8 XCDs (blockIdx % 8), all strips of a group to the same
         // XCD: the busiest XCD, with ceil(groups / 8) groups, sets the number of rounds

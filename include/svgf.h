@@ -81,8 +81,10 @@ typedef struct SvgfParams {
     /* --- extensions; 0 == reference behaviour --- */
     int   kernel_variant;     /* 0 auto (steps 2-32: the cheaper of the lane-marching and the LDS strip kernel by their
                                  launch-geometry cost model — lane at 1920, 3840, 1600, 3440 columns ..., strip at 1024,
-                                 2048 ...; the lane kernel at steps 16-32 also needs the variance plane the previous level
-                                 leaves; lattice sub-image kernel for steps >= 64; gather where none applies; on NON-temporal
+                                 2048 ..., for frames taller than about six lattice rows per level (H / step >= 6); shorter
+                                 ones mostly take the strip kernel at the coarse steps; the choice can differ per level
+                                 (1280 x 720: strip at step 16 only); the lane kernel at steps 16-32 also needs the
+                                 variance plane the previous level leaves; lattice sub-image kernel for steps >= 64; gather where none applies; on NON-temporal
                                  frames the prepare pass (variance fill + G-buffer split) rides in the first level's loader
                                  waves whenever that level runs the lane kernel at step 2 on the AoS boundary: one launch
                                  less, +39 % on BASELINE configs[0]),

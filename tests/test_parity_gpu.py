@@ -7,6 +7,8 @@ Tolerances (north_star: 1e-4 relative per channel):
     denominators, reciprocal instead of division — each ~1e-7).
 relerr() uses max(|ref|, 1e-2) as the denominator.
 """
+import os
+
 import numpy as np
 import pytest
 
@@ -198,15 +200,31 @@ def test_lattice_kernel_keeps_the_nan_semantics(pkg, orc):
     assert relerr(np.where(both_nan, 0, got), np.where(both_nan, 0, ref)).max() <= TOL_STRIP * 4
 
 
-@pytest.mark.parametrize("size,variant", [((1920, 70), 0), ((300, 200), 4), ((123, 77), 4), ((3840, 48), 0)])
+# kernel of the automatic choice at steps 16 / 32 on a 256-CU device (tests/test_kernel_geometry_gpu.py holds the whole table):
+# 70 and 48 rows are 5 / 3 and 3 / 2 lattice rows per phase there, one segment each, where the strip kernel's shorter rows win
+# (but for 3840 x 48 at step 32: 32 phases x 15 strips of the strip kernel take two rounds on 256 CUs)
+AUTO_16_32 = {(1920, 70): ("strip", "strip"), (3840, 48): ("strip", "lane"), (1920, 200): ("lane", "lane"), (3840, 200): ("lane", "lane")}
+
+
+@pytest.mark.parametrize("size,variant", [((1920, 70), 0), ((300, 200), 4), ((123, 77), 4), ((3840, 48), 0), ((1920, 200), 0), ((3840, 200), 0)])
 def test_lane_kernel_at_steps_16_and_32_nan_texels_and_options(pkg, orc, size, variant):
     """Steps 16 / 32 on the lane-marching kernel (chunked x-phases, variance pre-blur computed by the loader threads): widths
-    where the automatic choice takes it (1920, 3840) and small images with kernel_variant 4; non-finite normal / position texels
-    (the `careful` path), variance blur off, re-modulation on the last level, the history fed by level 4 / 5, paper step sizes
-    (step 16 as the LAST level: the variant without variance accumulators)."""
+    where the automatic choice takes it (1920 x 200, 3840 x 200) and small images with kernel_variant 4; the same frames where the
+    automatic choice runs the STRIP kernel at those steps (1920 x 70; 3840 x 48 at step 16: phases of at most 5 lattice rows); non-finite
+    normal / position texels (the `careful` path), variance blur off, re-modulation on the last level, the history fed by level
+    4 / 5, paper step sizes (step 16 as the LAST level: the variant without variance accumulators).  Where the experiments build
+    exists, its record of the kernels at steps 16 / 32 is checked, and its output must equal the product library's bit for bit."""
     W, H = size
     o = orc.Oracle(pkg, W, H, threads=16)
     d = pkg.Denoiser(W, H, 0)
+    de = pkg.Denoiser(W, H, 0, experiments=True) if os.path.exists(pkg.binding.LIB_EXP_PATH) else None
+    expect = None
+    if variant == 4:
+        expect = ("lane", "lane")
+    else:
+        import torch
+        if torch.cuda.get_device_properties(0).multi_processor_count == 256:
+            expect = AUTO_16_32[size]
     cfgs = [dict(temporal_enable=1, history_level=1, blur_variance=1),
             dict(temporal_enable=1, history_level=5, blur_variance=0, sepcolor=1, addcolor=1),
             dict(temporal_enable=1, history_level=4, blur_variance=1, paper_steps=1),
@@ -224,6 +242,19 @@ def test_lane_kernel_at_steps_16_and_32_nan_texels_and_options(pkg, orc, size, v
         both = np.isnan(got) & np.isnan(ref)
         e = relerr(np.where(both, 0, got), np.where(both, 0, ref))
         assert e.max() <= TOL_STRIP * 2, f"{W}x{H} variant {variant} frame {f} {kw}: {e.max():.3e}"
+        if de is not None:
+            out_e = de.denoise_host(c, g, cam, p)
+            # bit for bit only without non-finite texels: the lane kernel's switch to its careful loop (nan_seen) is raced by the
+            # loader that stages the texel, so the row computed during that iteration may round differently from run to run
+            if f == 0:
+                assert np.array_equal(out_e, got, equal_nan=True), f"{W}x{H} frame {f}: experiments build != product"
+            assert relerr(np.where(both, 0, out_e), np.where(both, 0, got)).max() <= TOL_STRIP, f"{W}x{H} frame {f}: experiments build vs product"
+            kinds = {step: kind for kind, step, _, _ in de.level_kernels()}
+            for step, want in zip((16, 32), expect or ()):
+                if step in kinds:
+                    assert kinds[step] == want, f"{W}x{H} variant {variant} frame {f} {kw}: step {step} ran {kinds[step]}"
+    if de is not None:
+        de.free()
     d.free(); o.free()
 
 
