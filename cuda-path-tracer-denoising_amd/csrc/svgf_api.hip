@@ -49,14 +49,13 @@ struct svgf_ctx {
     int pipe_serial;       // the probe at enable time found the two internal streams on ONE hardware queue: the promise is refused
     int ever_captured;     // a frame of this context has been recorded into a graph: promised frames order themselves behind `stream`
     hipStream_t pipe[2];
-    hipEvent_t ev_hist[2], ev_done[2], ev_in;
-    hipEvent_t ev_tdone[2];   // planar frames: behind the temporal pass (the last reader of the PREVIOUS frame's G-buffer planes, which the next producer overwrites)
-    int ev_tdone_valid[2];
+    // an event of the pipeline: recorded at least once since the last reset (`valid`), and the stream-capture id it was last recorded
+    // under (0: eagerly).  Only pipe_record / pipe_wait / pipe_reset touch these (the per-frame disarm of ev_tdone aside).
+    struct PipeEvent { hipEvent_t ev; int valid; unsigned long long cap; };
+    PipeEvent ev_hist[2], ev_done[2];
+    PipeEvent ev_tdone[2];    // planar frames: behind the temporal pass (the last reader of the PREVIOUS frame's G-buffer planes, which the next producer overwrites)
+    hipEvent_t ev_in;
     int last_modulated;       // the last frame's last level read the (single) albedo plane
-    int ev_hist_valid[2];
-    unsigned long long ev_hist_cap[2];      // the stream-capture id ev_hist[q] was last recorded under (0: eagerly)
-    int ev_done_valid[2];
-    unsigned long long ev_done_cap[2];
     long long pipe_frames;     // frames since the context became pipelined (parity = stream and plane set)
     int use_vplane;        // 0 only for A/B measurements (experiments build: svgf_exp_set("no_variance_plane", 1) before svgf_create)
     void *dump;            // 4 KB of scrap for the fused kernel (TemporalArgs::dump)
@@ -71,11 +70,10 @@ struct svgf_ctx {
     signed char fuse_pays;         // -1 not evaluated yet, 1: the fused temporal + first-level kernel is the cheaper way through both
 #ifdef SVGF_BUILD_EXPERIMENTS
     double est_lane_us[8], est_strip_us[8];   // per log2(step): the two estimates lane_cheaper[] was decided from
-    // the a-trous levels of the last frame (svgf_exp_level_kernels): kernel (K_FUSED ..), step, and the estimates the automatic
-    // choice compared (NaN where it was not consulted)
+    // the a-trous levels of the last frame (svgf_exp_level_kernels), a copy of its plan: kernel (K_FUSED ..), step, and whether the
+    // automatic choice compared the estimates of that step
     int lk_n;
-    int lk_kind[SVGF_MAX_LEVELS], lk_step[SVGF_MAX_LEVELS];
-    double lk_lane_us[SVGF_MAX_LEVELS], lk_strip_us[SVGF_MAX_LEVELS];
+    int lk_kind[SVGF_MAX_LEVELS], lk_step[SVGF_MAX_LEVELS], lk_asked[SVGF_MAX_LEVELS];
 #endif
     float *nrm[2];
     int *gid[2];
@@ -105,6 +103,7 @@ struct svgf_ctx {
 };
 
 static char g_create_err[512] = "";
+static int step_log2(int step) { int l = 0; while ((1 << l) < step && l < 7) l++; return l; }      // index of lane_cheaper[] / est_*_us[]
 
 #define HIPC(ctx, call)                                                                              \
     do {                                                                                             \
@@ -115,6 +114,12 @@ static char g_create_err[512] = "";
             return SVGF_ERR_HIP;                                                                     \
         }                                                                                            \
     } while (0)
+
+// Entry preamble: a null context is an invalid argument; the call runs on the context's device (SvgfDeviceGuard) or fails.
+#define SVGF_ENTER(ctx)                                                                              \
+    if (!(ctx)) return SVGF_ERR_INVALID_ARG;                                                         \
+    SvgfDeviceGuard dev_guard((ctx)->device);                                                        \
+    if (!dev_guard.ok) { snprintf((ctx)->err, sizeof((ctx)->err), "hipSetDevice(%d) failed", (ctx)->device); return SVGF_ERR_HIP; }
 
 // ---- host copy of the view-matrix construction (reference GetViewMatrix src/denoise.cu:342-347) -------------
 // inverse of the column-major matrix [right|0, up|0, view|0, position|1] by 2x2-minor (cofactor) expansion in the
@@ -220,6 +225,14 @@ static void *plane_carve(svgf_ctx *c, size_t *cursor, size_t bytes)
     return p;
 }
 
+// the profiler's arrays and the first n_events of its events
+static void profile_free(svgf_ctx *c, long long n_events)
+{
+    for (long long k = 0; c->ev && k < n_events; k++) (void)hipEventDestroy(c->ev[k]);
+    free(c->ev); free(c->ev_kind); free(c->ev_n);
+    c->ev = nullptr; c->ev_kind = nullptr; c->ev_n = nullptr;
+}
+
 static void free_all(svgf_ctx *c)
 {
     if (c->arena) (void)hipFree(c->arena);          // cv[], nrm[], gid[], mom[], hlen[], pos[], dump
@@ -227,9 +240,7 @@ static void free_all(svgf_ctx *c)
     for (int k = 3; k < 6; k++) if (c->cv[k]) (void)hipFree(reinterpret_cast<char *>(c->cv[k]) - kPlanePad);
     for (int q = 0; q < 2; q++) {
         if (c->pipe[q]) (void)hipStreamDestroy(c->pipe[q]);
-        if (c->ev_hist[q]) (void)hipEventDestroy(c->ev_hist[q]);
-        if (c->ev_done[q]) (void)hipEventDestroy(c->ev_done[q]);
-        if (c->ev_tdone[q]) (void)hipEventDestroy(c->ev_tdone[q]);
+        for (svgf_ctx::PipeEvent *e : { &c->ev_hist[q], &c->ev_done[q], &c->ev_tdone[q] }) if (e->ev) (void)hipEventDestroy(e->ev);
     }
     if (c->ev_in) (void)hipEventDestroy(c->ev_in);
     for (int k = 0; k < 2; k++) if (c->tp[k]) (void)hipFree(c->tp[k]);
@@ -238,10 +249,24 @@ static void free_all(svgf_ctx *c)
     if (c->st_in) (void)hipFree(c->st_in);
     if (c->st_out) (void)hipFree(c->st_out);
     if (c->st_g) (void)hipFree(c->st_g);
-    if (c->ev) {
-        for (long long k = 0; k < (long long)c->prof_frames * SVGF_MAX_KERNELS_PER_FRAME * 2; k++) (void)hipEventDestroy(c->ev[k]);
-        free(c->ev); free(c->ev_kind); free(c->ev_n);
-    }
+    profile_free(c, (long long)c->prof_frames * SVGF_MAX_KERNELS_PER_FRAME * 2);
+}
+
+// ---- the pipeline's events: record under a capture id, wait if recorded under the same one, forget everything ----
+static hipError_t pipe_record(svgf_ctx::PipeEvent &e, hipStream_t s, unsigned long long cap_id)
+{
+    const hipError_t rc = hipEventRecord(e.ev, s);
+    if (rc == hipSuccess) { e.valid = 1; e.cap = cap_id; }
+    return rc;
+}
+// (an event recorded under another capture, or eagerly while the waiting frame is captured, or vice versa, is not waited for: such
+// frames are ordered through the caller's stream)
+static bool pipe_live(const svgf_ctx::PipeEvent &e, unsigned long long cap_id) { return e.valid && e.cap == cap_id; }
+static hipError_t pipe_wait(hipStream_t s, const svgf_ctx::PipeEvent &e, unsigned long long cap_id) { return pipe_live(e, cap_id) ? hipStreamWaitEvent(s, e.ev, 0) : hipSuccess; }
+static void pipe_reset(svgf_ctx *c)
+{
+    c->pipe_frames = 0;
+    for (svgf_ctx::PipeEvent *e : { &c->ev_hist[0], &c->ev_hist[1], &c->ev_done[0], &c->ev_done[1], &c->ev_tdone[0], &c->ev_tdone[1] }) { e->valid = 0; e->cap = 0; }
 }
 
 static int zero_state(svgf_ctx *c)
@@ -249,9 +274,7 @@ static int zero_state(svgf_ctx *c)
     for (int k = 0; k < 6; k++) if (c->cv[k]) HIPC(c, hipMemset(c->cv[k], 0, c->n * sizeof(float4)));
     for (int k = 0; k < 6; k++) if (c->vp[k]) HIPC(c, hipMemset(c->vp[k], 0, (size_t)(c->W + 2) * (c->H + 2) * sizeof(float) + 64));
     c->vp_valid = 0;
-    c->pipe_frames = 0; c->ev_hist_valid[0] = c->ev_hist_valid[1] = 0; c->ev_hist_cap[0] = c->ev_hist_cap[1] = 0;      // (a pipelined context stays pipelined)
-    c->ev_done_valid[0] = c->ev_done_valid[1] = 0; c->ev_done_cap[0] = c->ev_done_cap[1] = 0;
-    c->ev_tdone_valid[0] = c->ev_tdone_valid[1] = 0;
+    pipe_reset(c);      // (a pipelined context stays pipelined)
     for (int k = 0; k < 2; k++) {
         HIPC(c, hipMemset(c->nrm[k], 0, c->n * 3 * sizeof(float)));
         HIPC(c, hipMemset(c->gid[k], 0, c->n * sizeof(int)));
@@ -331,23 +354,13 @@ extern "C" int svgf_create_ex(int device, int width, int height, unsigned flags,
     for (int k = 0; k < 3 && ok; k++) ok = hipMalloc((void **)&c->vp[k], (size_t)(width + 2) * (height + 2) * sizeof(float) + 64) == hipSuccess;
     // (the terms planes of the parked cross-level reuse: allocated here, never in the middle of a frame)
     for (int k = 0; k < 2 && ok && c->use_reuse; k++) ok = hipMalloc((void **)&c->tp[k], (size_t)(width + 64) * height * sizeof(float4)) == hipSuccess;
-    if (!ok) {
-        snprintf(g_create_err, sizeof(g_create_err), "svgf_create: hipMalloc failed for %dx%d", width, height);
+    int rc = ok ? zero_state(c) : SVGF_ERR_OOM;
+    if (rc == SVGF_OK && (flags & SVGF_CREATE_PIPELINED)) rc = enable_pipeline(c);
+    if (rc != SVGF_OK) {
+        if (!ok) snprintf(g_create_err, sizeof(g_create_err), "svgf_create: hipMalloc failed for %dx%d", width, height);
+        else snprintf(g_create_err, sizeof(g_create_err), "%s", c->err);
         free_all(c); delete c;
-        return SVGF_ERR_OOM;
-    }
-    if (zero_state(c) != SVGF_OK) {
-        snprintf(g_create_err, sizeof(g_create_err), "%s", c->err);
-        free_all(c); delete c;
-        return SVGF_ERR_HIP;
-    }
-    if (flags & SVGF_CREATE_PIPELINED) {
-        const int rc = enable_pipeline(c);
-        if (rc != SVGF_OK) {
-            snprintf(g_create_err, sizeof(g_create_err), "%s", c->err);
-            free_all(c); delete c;
-            return rc;
-        }
+        return rc;
     }
     *out = c;
     return SVGF_OK;
@@ -367,9 +380,7 @@ extern "C" int svgf_destroy(svgf_ctx *c)
 
 extern "C" int svgf_reset(svgf_ctx *c)
 {
-    if (!c) return SVGF_ERR_INVALID_ARG;
-    SvgfDeviceGuard dev_guard(c->device);
-    if (!dev_guard.ok) { snprintf(c->err, sizeof(c->err), "hipSetDevice(%d) failed", c->device); return SVGF_ERR_HIP; }
+    SVGF_ENTER(c);
     HIPC(c, hipDeviceSynchronize());
     return zero_state(c);
 }
@@ -379,17 +390,13 @@ extern "C" int svgf_pipeline_status(const svgf_ctx *c) { return !c || !c->pipeli
 
 extern "C" int svgf_enable_pipeline(svgf_ctx *c)
 {
-    if (!c) return SVGF_ERR_INVALID_ARG;
-    SvgfDeviceGuard dev_guard(c->device);
-    if (!dev_guard.ok) { snprintf(c->err, sizeof(c->err), "hipSetDevice(%d) failed", c->device); return SVGF_ERR_HIP; }
+    SVGF_ENTER(c);
     return enable_pipeline(c);
 }
 
 extern "C" int svgf_sync(svgf_ctx *c)
 {
-    if (!c) return SVGF_ERR_INVALID_ARG;
-    SvgfDeviceGuard dev_guard(c->device);
-    if (!dev_guard.ok) { snprintf(c->err, sizeof(c->err), "hipSetDevice(%d) failed", c->device); return SVGF_ERR_HIP; }
+    SVGF_ENTER(c);
     HIPC(c, hipDeviceSynchronize());
     return SVGF_OK;
 }
@@ -397,9 +404,7 @@ extern "C" int svgf_sync(svgf_ctx *c)
 // Stream-scoped completion: wait for what has been enqueued on `stream` (this context's frames included) and nothing else.
 extern "C" int svgf_sync_stream(svgf_ctx *c, void *stream)
 {
-    if (!c) return SVGF_ERR_INVALID_ARG;
-    SvgfDeviceGuard dev_guard(c->device);
-    if (!dev_guard.ok) { snprintf(c->err, sizeof(c->err), "hipSetDevice(%d) failed", c->device); return SVGF_ERR_HIP; }
+    SVGF_ENTER(c);
     HIPC(c, hipStreamSynchronize((hipStream_t)stream));
     return SVGF_OK;
 }
@@ -417,8 +422,8 @@ extern "C" int svgf_exp_level_kernels(const svgf_ctx *c, int *kinds, int *steps,
     for (int k = 0; k < c->lk_n && k < n; k++) {
         if (kinds) kinds[k] = c->lk_kind[k];
         if (steps) steps[k] = c->lk_step[k];
-        if (lane_us) lane_us[k] = c->lk_lane_us[k];
-        if (strip_us) strip_us[k] = c->lk_strip_us[k];
+        if (lane_us) lane_us[k] = c->lk_asked[k] ? c->est_lane_us[step_log2(c->lk_step[k])] : __builtin_nan("");
+        if (strip_us) strip_us[k] = c->lk_asked[k] ? c->est_strip_us[step_log2(c->lk_step[k])] : __builtin_nan("");
     }
     return c->lk_n;
 }
@@ -427,9 +432,7 @@ extern "C" int svgf_height(const svgf_ctx *c) { return c ? c->H : 0; }
 
 extern "C" int svgf_set_capture(svgf_ctx *c, int on)
 {
-    if (!c) return SVGF_ERR_INVALID_ARG;
-    SvgfDeviceGuard dev_guard(c->device);
-    if (!dev_guard.ok) { snprintf(c->err, sizeof(c->err), "hipSetDevice(%d) failed", c->device); return SVGF_ERR_HIP; }
+    SVGF_ENTER(c);
     if (on && !c->cv_capture) {
         HIPC(c, hipMalloc((void **)&c->cv_capture, c->n * sizeof(float4)));
         HIPC(c, hipMemset(c->cv_capture, 0, c->n * sizeof(float4)));
@@ -443,8 +446,7 @@ extern "C" int svgf_set_capture(svgf_ctx *c, int on)
 extern "C" int svgf_profile_enable(svgf_ctx *c, int nframes)
 {
     if (!c || nframes < 0) return SVGF_ERR_INVALID_ARG;
-    SvgfDeviceGuard dev_guard(c->device);
-    if (!dev_guard.ok) { snprintf(c->err, sizeof(c->err), "hipSetDevice(%d) failed", c->device); return SVGF_ERR_HIP; }
+    SVGF_ENTER(c);
     if (c->ev && nframes == c->prof_frames) {
         // Same number of slots as before: only the counters restart, the events are reused.  Creating a few hundred events takes
         // 0.2-2 ms, and a benchmark that re-arms the profiler between its warm-up and its timed frames would let the GPU idle for
@@ -453,11 +455,7 @@ extern "C" int svgf_profile_enable(svgf_ctx *c, int nframes)
         memset(c->ev_n, 0, sizeof(int) * (size_t)nframes);
         return SVGF_OK;
     }
-    if (c->ev) {
-        for (long long k = 0; k < (long long)c->prof_frames * SVGF_MAX_KERNELS_PER_FRAME * 2; k++) (void)hipEventDestroy(c->ev[k]);
-        free(c->ev); free(c->ev_kind); free(c->ev_n);
-        c->ev = nullptr; c->ev_kind = nullptr; c->ev_n = nullptr;
-    }
+    profile_free(c, (long long)c->prof_frames * SVGF_MAX_KERNELS_PER_FRAME * 2);
     c->prof_frames = 0; c->prof_count = 0; c->frame_no = 0;
     if (c->prof_stride < 1) c->prof_stride = 1;
     if (nframes == 0) return SVGF_OK;
@@ -465,17 +463,11 @@ extern "C" int svgf_profile_enable(svgf_ctx *c, int nframes)
     c->ev = (hipEvent_t *)calloc(ne, sizeof(hipEvent_t));
     c->ev_kind = (int *)calloc((size_t)nframes * SVGF_MAX_KERNELS_PER_FRAME, sizeof(int));
     c->ev_n = (int *)calloc(nframes, sizeof(int));
-    if (!c->ev || !c->ev_kind || !c->ev_n) {
-        free(c->ev); free(c->ev_kind); free(c->ev_n);
-        c->ev = nullptr; c->ev_kind = nullptr; c->ev_n = nullptr;
-        return SVGF_ERR_OOM;
-    }
+    if (!c->ev || !c->ev_kind || !c->ev_n) { profile_free(c, 0); return SVGF_ERR_OOM; }
     for (long long k = 0; k < ne; k++) {
         hipError_t e = hipEventCreate(&c->ev[k]);
         if (e != hipSuccess) {          // give back what was created: profiling stays off
-            for (long long j = 0; j < k; j++) (void)hipEventDestroy(c->ev[j]);
-            free(c->ev); free(c->ev_kind); free(c->ev_n);
-            c->ev = nullptr; c->ev_kind = nullptr; c->ev_n = nullptr;
+            profile_free(c, k);
             snprintf(c->err, sizeof(c->err), "svgf_profile_enable: hipEventCreate failed: %s", hipGetErrorString(e));
             return SVGF_ERR_HIP;
         }
@@ -496,8 +488,7 @@ extern "C" long long svgf_profile_frames(const svgf_ctx *c) { return c ? c->prof
 extern "C" int svgf_profile_read(svgf_ctx *c, int slot, int max_entries, int *kinds, float *ms, int *n_out)
 {
     if (!c || !n_out || slot < 0 || slot >= c->prof_frames) return SVGF_ERR_INVALID_ARG;
-    SvgfDeviceGuard dev_guard(c->device);
-    if (!dev_guard.ok) { snprintf(c->err, sizeof(c->err), "hipSetDevice(%d) failed", c->device); return SVGF_ERR_HIP; }
+    SVGF_ENTER(c);
     const int nk = c->ev_n[slot];
     int w = 0;
     for (int k = 0; k < nk && w < max_entries; k++, w++) {
@@ -647,9 +638,8 @@ static int enable_pipeline(svgf_ctx *c)
     }
     for (int q = 0; q < 2; q++) {
         if (!c->pipe[q]) HIPC(c, hipStreamCreateWithFlags(&c->pipe[q], hipStreamNonBlocking));
-        if (!c->ev_hist[q]) HIPC(c, hipEventCreateWithFlags(&c->ev_hist[q], hipEventDisableTiming));
-        if (!c->ev_done[q]) HIPC(c, hipEventCreateWithFlags(&c->ev_done[q], hipEventDisableTiming));
-        if (!c->ev_tdone[q]) HIPC(c, hipEventCreateWithFlags(&c->ev_tdone[q], hipEventDisableTiming));
+        for (svgf_ctx::PipeEvent *e : { &c->ev_hist[q], &c->ev_done[q], &c->ev_tdone[q] })
+            if (!e->ev) HIPC(c, hipEventCreateWithFlags(&e->ev, hipEventDisableTiming));
     }
     if (!c->ev_in) HIPC(c, hipEventCreateWithFlags(&c->ev_in, hipEventDisableTiming));
     bool overlap = true;
@@ -672,8 +662,7 @@ static int enable_pipeline(svgf_ctx *c)
     c->pipelined = 1;
     c->pipe_serial = overlap ? 0 : 1;
     c->piped_mode = overlap ? 1 : 0;      // (refused: frames stay plain ordered frames until one asks for inputs_ready = 2)
-    c->pipe_frames = 0; c->ev_hist_valid[0] = c->ev_hist_valid[1] = 0;
-    c->ev_done_valid[0] = c->ev_done_valid[1] = 0;
+    pipe_reset(c);
     if (!overlap)
         snprintf(c->err, sizeof(c->err), "frame pipeline: the context's internal streams share a hardware queue (six candidate pairs; two 200 us kernels took %.2fx one): "
                  "the inputs_ready = 1 promise is refused and such frames run ordered on the caller's stream; start the process with "
@@ -704,8 +693,7 @@ static double lane_estimate_us(svgf_ctx *c, const AtrousArgs &a)
 
 static bool lane_pays(svgf_ctx *c, const AtrousArgs &a)
 {
-    int l = 0;
-    while ((1 << l) < a.step && l < 7) l++;
+    const int l = step_log2(a.step);
     if (c->lane_cheaper[l] < 0) {        // depends on the image size and the device only: evaluated once per context and step
         const double lane = lane_estimate_us(c, a), strip = atrous_strip_estimate_us(a, c->n_cu);
         c->lane_cheaper[l] = lane <= strip ? 1 : 0;
@@ -734,15 +722,59 @@ static bool fuse_pays(svgf_ctx *c, const AtrousArgs &a)
 }
 #endif
 
-// gbuffer_dev == nullptr: the planar path (svgf_denoise_planar) — the current-frame planes nrm/pos/gid[1 - gcur] (and `albedo`)
-// were filled in place by the producer
-static int denoise_frame(svgf_ctx *c, void *out_rgb_dev, const void *in_rgb_dev, const void *gbuffer_dev,
-                         const SvgfCamera *cam, const SvgfParams *p, void *stream)
+// ---- the frame: plan (every decision, nothing enqueued), enqueue (walks the plan), commit (the context's state behind it) ----
+enum KernelKind { K_FUSED, K_LANE, K_LANE2Y, K_STRIP, K_LATTICE, K_GATHER };      // (the numbering svgf_exp_level_kernels reports)
+enum FrameExit { EXIT_CASCADE, EXIT_DEBUG_HLEN, EXIT_DEBUG_VAR, EXIT_COPY };
+
+struct LevelPlan {
+    KernelKind kind;
+    AtrousArgs a;
+    int dst;                        // cv index the level writes; -1: the last level writes `out` only
+    bool keep, last, asked;         // keep: the output becomes the colour history (:391); asked: the automatic choice compared the estimates of this step
+};
+struct FramePlan {
+    bool flip, piped, promise;      // the pipeline decision (see plan_frame); flip: the context goes into piped mode with this frame
+    bool wait_in_first;             // a promised frame that runs behind the caller's stream position as a whole
+    unsigned long long cap_id;      // != 0: `stream` is being captured into a graph
+    int pq;                         // parity: plane set, internal stream and events of this frame
+    hipStream_t s, s_user;
+    int hist_release;               // ev_hist[pq] is recorded behind level [hist_release]; -1: behind the temporal pass; n_levels: at the frame's end
+    bool timed; int slot;           // profiling brackets this frame's kernels, in slot `slot`
+    bool temporal, fused, split_fused, tdone, capture;      // what runs before the cascade; tdone: the temporal pass re-arms ev_tdone[pq] (planar frames)
+    int svf;                        // SvgfParams::spatial_variance_frames
+    TemporalArgs t;
+    FrameExit exit;
+    float *out;
+    int n_levels;
+    LevelPlan lv[SVGF_MAX_LEVELS];
+    int acc, hist, cur, gcur, last_modulated;      // the context's plane roles after the frame
+    unsigned vp_valid;
+};
+
+// The kernel of one a-trous level: the ONE place that chooses between the six.
+static KernelKind level_kernel(svgf_ctx *c, const SvgfParams *p, const AtrousArgs &a, bool fuse_here)
 {
-    if (!out_rgb_dev || !in_rgb_dev || !cam || !p) {
-        snprintf(c->err, sizeof(c->err), "svgf_denoise: null argument");
-        return SVGF_ERR_INVALID_ARG;
+    if (fuse_here) return K_FUSED;
+    const int kv = p->kernel_variant;
+    if (kv != 1 && atrous_strip_supported(a)) {
+#ifdef SVGF_BUILD_EXPERIMENTS
+        if (a.step == 2 && kv == 5 && atrous_lane_supported(a)) return K_LANE2Y;
+#endif
+        if (atrous_lane_supported(a) && (kv >= 4 || (kv == 0 && lane_pays(c, a)))) return K_LANE;
+        return K_STRIP;
     }
+    if (kv != 1 && kv != 2 && atrous_lattice_supported(a)) return K_LATTICE;     // steps 64, 128, ...
+    return K_GATHER;
+}
+
+// gbuffer_dev == nullptr: the planar path (svgf_denoise_planar) — the current-frame planes nrm/pos/gid[1 - gcur] (and `albedo`)
+// were filled in place by the producer.
+// Every level is decided and validated here, before anything is enqueued or any context state changes: a failure half-way
+// through the cascade would leave the colour history of this frame next to the G-buffer / moments of the previous one.  The
+// context is only read (the memoised estimates of lane_pays / fuse_pays aside).
+static int plan_frame(svgf_ctx *c, void *out_rgb_dev, const void *in_rgb_dev, const void *gbuffer_dev,
+                      const SvgfParams *p, void *stream, FramePlan &pl)
+{
     if (p->atrous_nlevel < 0 || p->atrous_nlevel > SVGF_MAX_LEVELS) {
         snprintf(c->err, sizeof(c->err), "svgf_denoise: atrous_nlevel %d outside 0..%d", p->atrous_nlevel, SVGF_MAX_LEVELS);
         return SVGF_ERR_INVALID_ARG;
@@ -760,22 +792,8 @@ static int denoise_frame(svgf_ctx *c, void *out_rgb_dev, const void *in_rgb_dev,
         return SVGF_ERR_UNSUPPORTED;
     }
 #endif
-    // every level is validated before anything is enqueued or any context state changes: a failure half-way through the
-    // cascade would leave the colour history of this frame next to the G-buffer / moments of the previous one
-    if (p->kernel_variant == 2 && p->spatial_enable && p->right_view_option != 1 && p->right_view_option != 2) {
-        for (int level = 1; level <= p->atrous_nlevel; level++) {
-            AtrousArgs probe;
-            memset(&probe, 0, sizeof(probe));
-            probe.W = c->W; probe.H = c->H; probe.step = 1 << (p->paper_steps ? level - 1 : level);
-            if (!atrous_strip_supported(probe)) {
-                snprintf(c->err, sizeof(c->err), "svgf_denoise: strip kernel does not support %dx%d step %d", c->W, c->H, probe.step);
-                return SVGF_ERR_UNSUPPORTED;
-            }
-        }
-    }
-    SvgfDeviceGuard dev_guard(c->device);
-    if (!dev_guard.ok) { snprintf(c->err, sizeof(c->err), "hipSetDevice(%d) failed", c->device); return SVGF_ERR_HIP; }
-    hipStream_t s_user = (hipStream_t)stream;
+    const float *in = (const float *)in_rgb_dev, *g = (const float *)gbuffer_dev;
+    pl.out = (float *)out_rgb_dev; pl.s_user = (hipStream_t)stream; pl.cap_id = 0;
     // Pipelined frames (see svgf_ctx::pipelined).  The promise behind inputs_ready = 1: at call time the inputs are complete (and stay
     // untouched until the work of this call is done) — so the frame need not order itself behind the caller's stream, which has
     // waited for the PREVIOUS frame's end, and runs on an internal stream; only the kernel that writes `out` waits for the caller's
@@ -800,52 +818,33 @@ static int denoise_frame(svgf_ctx *c, void *out_rgb_dev, const void *in_rgb_dev,
     // the resources were created, svgf_pipeline_status() == 1): refused, a promised frame is a plain ordered frame.
     bool promise = (p->inputs_ready == 1) && worth && c->pipelined && !c->pipe_serial;
     bool want_pipeline = promise || ((p->inputs_ready == 2) && worth && c->pipelined);
-    unsigned long long cap_id = 0;      // != 0: `stream` is being captured into a graph
     if (want_pipeline || c->piped_mode) {
         hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
         unsigned long long id = 0;
-        if (s_user && hipStreamGetCaptureInfo(s_user, &cs, &id) == hipSuccess && cs != hipStreamCaptureStatusNone) { cap_id = id ? id : 1; promise = false; }
+        if (pl.s_user && hipStreamGetCaptureInfo(pl.s_user, &cs, &id) == hipSuccess && cs != hipStreamCaptureStatusNone) { pl.cap_id = id ? id : 1; promise = false; }
         // a frame recorded into a graph did not run when it was recorded: the eager frames behind it order themselves behind the
         // caller's stream (where the graph is launched) until both parities' events are eager ones again
-        if (!cap_id && (c->ev_hist_cap[0] || c->ev_hist_cap[1])) promise = false;
+        if (!pl.cap_id && (c->ev_hist[0].cap || c->ev_hist[1].cap)) promise = false;
     }
 #ifdef SVGF_BUILD_EXPERIMENTS
     if (p->kernel_variant == 6 || p->kernel_variant == 5 || c->use_reuse || c->use_split_fused) { promise = false; want_pipeline = false; }
 #endif
-    if (want_pipeline && !cap_id && !c->piped_mode) {      // (a state flip, nothing is allocated: the colour history lies in plane set 0)
-        c->piped_mode = 1; c->pipe_frames = 0;
-        c->ev_hist_valid[0] = c->ev_hist_valid[1] = 0; c->ev_done_valid[0] = c->ev_done_valid[1] = 0;
-    }
-    const bool piped = c->piped_mode != 0;
-    if (piped && cap_id) c->ever_captured = 1;
-    if (piped) c->ev_tdone_valid[c->pipe_frames & 1] = 0;      // (re-armed below by a planar frame's temporal pass)
-    const int pq = piped ? (int)(c->pipe_frames & 1) : 0;
+    pl.flip = want_pipeline && !pl.cap_id && !c->piped_mode;
+    const bool piped = pl.piped = c->piped_mode || pl.flip;
+    const long long pipe_frames = pl.flip ? 0 : c->pipe_frames;
+    const int pq = pl.pq = piped ? (int)(pipe_frames & 1) : 0;
     const int pbase = piped ? 3 * pq : 0;          // this frame's plane set
     // A promised frame runs on the context's stream of its parity.  Every other frame of a pipelined context runs on the caller's own
     // stream, behind the previous frame of the same parity (same plane set), wherever that one ran: with one stream that is what an
     // ordered frame always was; with two streams used in turn (inputs_ready = 2) the caller's streams ARE the pipeline.
-    hipStream_t s = (piped && promise) ? c->pipe[pq] : s_user;
-    if (piped) {
-        if (promise) {
-            HIPC(c, hipEventRecord(c->ev_in, s_user));      // the caller's stream position at hand-over: the last level waits for it (`out`)
-            // the first pipelined frame: all of it behind the caller's stream.  So is every promised frame of a context that has ever
-            // been recorded into a graph: a replay of that graph on the caller's stream touches the same planes and is visible to this
-            // frame only through the caller's stream position
-            if (c->pipe_frames == 0 || c->ever_captured) HIPC(c, hipStreamWaitEvent(s, c->ev_in, 0));
-        }
-        if (c->ev_done_valid[pq] && c->ev_done_cap[pq] == cap_id) HIPC(c, hipStreamWaitEvent(s, c->ev_done[pq], 0));
-    }
-    float *out = (float *)out_rgb_dev;
-    const float *in = (const float *)in_rgb_dev;
-    const float *g = (const float *)gbuffer_dev;
-    const int n = (int)c->n;
-
-    KernelTimer timer{ c, s, 0, 0, false };
-    if (c->prof_frames && (c->frame_no % (c->prof_stride > 0 ? c->prof_stride : 1)) == 0) {
-        timer.on = true;
-        timer.slot = (int)(c->prof_count % c->prof_frames);
-        c->ev_n[timer.slot] = 0;
-    }
+    pl.promise = piped && promise;
+    pl.s = pl.promise ? c->pipe[pq] : pl.s_user;
+    // the first pipelined frame: all of it behind the caller's stream.  So is every promised frame of a context that has ever
+    // been recorded into a graph: a replay of that graph on the caller's stream touches the same planes and is visible to this
+    // frame only through the caller's stream position
+    pl.wait_in_first = pipe_frames == 0 || c->ever_captured;
+    pl.timed = c->prof_frames && (c->frame_no % (c->prof_stride > 0 ? c->prof_stride : 1)) == 0;
+    pl.slot = pl.timed ? (int)(c->prof_count % c->prof_frames) : 0;
 
     // 1) temporal accumulation, or constant variance (reference :360-371).  Writes a cv plane `acc` that does not hold the
     //    colour history, and the current-frame G-buffer planes.  When the frame runs the a-trous cascade on the fast path the
@@ -854,234 +853,229 @@ static int denoise_frame(svgf_ctx *c, void *out_rgb_dev, const void *in_rgb_dev,
     //    (Rounds 1-3 ran this pass alone on a side stream beside the previous frame's trailing levels — it lost 3-8 % once the lane
     //    kernel ran all five levels; round 5's frame pipeline, above, runs whole frames of alternating parity on two streams.)
     const int old_hist = c->hist;
-    const int acc = piped ? (pbase == old_hist ? pbase + 1 : pbase) : (old_hist + 1) % 3;
-    // the other stream's frame: this frame's temporal pass (and everything behind it) starts when that frame's colour history,
-    // moments, history lengths and G-buffer planes are final
-    // (an event recorded under another capture, or eagerly while this frame is captured, or vice versa, is not waited for: such
-    // frames are ordered through the caller's stream, see above)
-    if (piped && c->ev_hist_valid[1 - pq] && c->ev_hist_cap[1 - pq] == cap_id) HIPC(c, hipStreamWaitEvent(s, c->ev_hist[1 - pq], 0));
-    bool hist_event_recorded = false;
-    const int gnew = 1 - c->gcur;
+    const int acc = pl.acc = piped ? (pbase == old_hist ? pbase + 1 : pbase) : (old_hist + 1) % 3;
+    const int gnew = pl.gcur = 1 - c->gcur;
     const bool cascade = !(p->right_view_option == 1 || p->right_view_option == 2 || p->atrous_nlevel == 0 || !p->spatial_enable);
-    TemporalArgs t;
+    TemporalArgs &t = pl.t;
     memset(&t, 0, sizeof(t));
-    bool fused = false, split_fused = false;
-    if (p->temporal_enable) {
-        t.in_rgb = in; t.gbuf = g; t.cv_hist = c->cv[c->hist]; t.cv_acc = c->cv[acc];
+    pl.temporal = p->temporal_enable != 0; pl.fused = pl.split_fused = false; pl.svf = p->spatial_variance_frames;
+    t.in_rgb = in; t.gbuf = g; t.cv_acc = c->cv[acc];
+    t.nrm_cur = c->nrm[gnew]; t.gid_cur = c->gid[gnew]; t.pos_cur = c->pos[gnew];
+    t.W = c->W; t.H = c->H;
+    AtrousArgs probe;
+    memset(&probe, 0, sizeof(probe));
+    probe.W = c->W; probe.H = c->H; probe.step = 2;
+    if (pl.temporal) {
+        t.cv_hist = c->cv[c->hist];
         t.mom_hist = c->mom[c->cur]; t.mom_acc = c->mom[1 - c->cur];
         t.hlen = c->hlen[c->cur]; t.hlen_upd = c->hlen[1 - c->cur];
         t.nrm_prev = c->nrm[c->gcur]; t.gid_prev = c->gid[c->gcur];
-        t.nrm_cur = c->nrm[gnew]; t.gid_cur = c->gid[gnew]; t.pos_cur = c->pos[gnew];
         memcpy(t.M, c->view_prev, sizeof(t.M));
-        t.W = c->W; t.H = c->H; t.color_alpha_min = p->color_alpha; t.moment_alpha_min = p->moment_alpha;
+        t.color_alpha_min = p->color_alpha; t.moment_alpha_min = p->moment_alpha;
         t.reproj_sx = p->reproj_scale[0]; t.reproj_sy = p->reproj_scale[1];
         t.pos_prev = c->pos[c->gcur]; t.pos_tol = p->reproj_position_tol;
         t.dump = c->dump; t.arena = c->arena; t.arena_bytes = c->arena_bytes;
-#ifdef SVGF_BUILD_EXPERIMENTS      // parked: the temporal pass (or only its G-buffer split) in the first level's loaders, DESIGN.md 5.8
-        if (cascade && (p->kernel_variant == 0 || p->kernel_variant == 6) && !p->paper_steps && p->spatial_variance_frames <= 0) {
-            AtrousArgs probe;
-            memset(&probe, 0, sizeof(probe));
-            probe.W = c->W; probe.H = c->H; probe.step = 2;
-            fused = atrous_fused_supported(probe, t) && (p->kernel_variant == 6 || fuse_pays(c, probe));
-        }
-        // The G-buffer split alone can ride in the first level's loaders (svgf_atrous_fused.hip, FUSED = 4): the temporal pass then
-        // writes 28 B/px less.  Only where that level runs the lane kernel at step 2 and nothing reads the planes before it does.
-        if (!fused && c->use_split_fused && g && cascade && p->kernel_variant == 0 && !p->paper_steps && p->spatial_variance_frames <= 0) {
-            AtrousArgs probe;
-            memset(&probe, 0, sizeof(probe));
-            probe.W = c->W; probe.H = c->H; probe.step = 2; probe.src = c->cv[acc];
-            split_fused = atrous_split_fused_supported(probe, t) && atrous_strip_supported(probe) && atrous_lane_supported(probe) && lane_pays(c, probe);
-        }
+#ifdef SVGF_BUILD_EXPERIMENTS      // parked: the temporal pass in the first level's loaders, DESIGN.md 5.8
+        if (cascade && (p->kernel_variant == 0 || p->kernel_variant == 6) && !p->paper_steps && p->spatial_variance_frames <= 0)
+            pl.fused = atrous_fused_supported(probe, t) && (p->kernel_variant == 6 || fuse_pays(c, probe));
 #endif
-        t.skip_split = split_fused ? 1 : 0;
-        if (!fused) {
-            LAUNCH(SVGF_KERNEL_TEMPORAL, launch_temporal(t, s));
-            if (piped && !g && !cap_id) { HIPC(c, hipEventRecord(c->ev_tdone[pq], s)); c->ev_tdone_valid[pq] = 1; }
-            if (p->spatial_variance_frames > 0)      // f4 extension: spatial variance estimate for short histories (its own profiling slot, same kind)
-                LAUNCH(SVGF_KERNEL_TEMPORAL, launch_spatial_variance(c->cv[acc], c->mom[1 - c->cur], c->hlen[1 - c->cur], c->nrm[gnew], c->gid[gnew],
-                                                                     c->W, c->H, p->spatial_variance_frames, s));
-        }
-    } else {
+    } else if (g && cascade && (p->kernel_variant == 0 || p->kernel_variant == 6) && !p->paper_steps) {
         // Non-temporal mode.  On the AoS boundary the prepare pass (variance = 10, colour copy, G-buffer split) is loads and
         // stores only and rides in the first level's loader waves when the cascade starts with the lane kernel at step 2
         // (svgf_atrous_fused.hip, FUSED = 3): no prepare launch, no colour plane written and read back.
-        t.in_rgb = in; t.gbuf = g; t.cv_acc = c->cv[acc];
-        t.nrm_cur = c->nrm[gnew]; t.gid_cur = c->gid[gnew]; t.pos_cur = c->pos[gnew];
-        t.W = c->W; t.H = c->H;
-        if (g && cascade && (p->kernel_variant == 0 || p->kernel_variant == 6) && !p->paper_steps) {
-            AtrousArgs probe;
-            memset(&probe, 0, sizeof(probe));
-            probe.W = c->W; probe.H = c->H; probe.step = 2;
-            fused = atrous_prepare_fused_supported(probe, t) && atrous_strip_supported(probe) && atrous_lane_supported(probe) &&
-                    (p->kernel_variant == 6 || (kPrepareFusedByDefault && lane_pays(c, probe)));
-        }
-        if (!fused) LAUNCH(SVGF_KERNEL_PREPARE, launch_prepare(in, g, c->cv[acc], c->nrm[gnew], c->gid[gnew], c->pos[gnew], c->W, c->H, s));
+        pl.fused = atrous_prepare_fused_supported(probe, t) && atrous_strip_supported(probe) && atrous_lane_supported(probe) &&
+                   (p->kernel_variant == 6 || (kPrepareFusedByDefault && lane_pays(c, probe)));
     }
-    c->vp_valid &= ~(1u << acc);     // the temporal / prepare pass writes no variance plane: the first level gathers cv.w
-    c->acc = acc;
-    c->hist = acc;                                   // color_history <- color_acc / input (:366,370)
-    if (c->capture && !fused) { HIPC(c, hipMemcpyAsync(c->cv_capture, c->cv[acc], c->n * sizeof(float4), hipMemcpyDeviceToDevice, s)); }      // (before the early release below: the next frame's copy into the one capture buffer must not overtake this one)
-    if (piped && cascade && p->temporal_enable && !(p->history_level >= 1 && p->history_level <= p->atrous_nlevel)) {
-        // no level of this cascade writes the colour history: it IS the accumulated plane (which no level of this frame overwrites),
-        // and everything else the next temporal pass reads was final before: the other stream may go on behind the temporal pass
-        HIPC(c, hipEventRecord(c->ev_hist[pq], s));
-        c->ev_hist_valid[pq] = 1; c->ev_hist_cap[pq] = cap_id; hist_event_recorded = true;
-    }
+    pl.tdone = piped && !g && !pl.cap_id; pl.capture = c->capture != 0;
+    unsigned vp_valid = c->vp_valid & ~(1u << acc);     // the temporal / prepare pass writes no variance plane: the first level gathers cv.w
+    int hist = acc;                                    // color_history <- color_acc / input (:366,370)
 
-#ifdef SVGF_BUILD_EXPERIMENTS
-    c->lk_n = 0;
-#endif
     // 2) debug views, pass-through or the a-trous cascade (:373-394)
-    if (p->right_view_option == 1) {
-        LAUNCH(SVGF_KERNEL_DEBUGVIEW, launch_debug_hlen(c->hlen[c->cur], out, n, 100.0f, s));   // pre-update lengths (:374)
-    } else if (p->right_view_option == 2) {
-        LAUNCH(SVGF_KERNEL_DEBUGVIEW, launch_debug_var(c->cv[acc], out, n, 0.1f, s));            // (:377)
-    } else if (p->atrous_nlevel == 0 || !p->spatial_enable) {
-        LAUNCH(SVGF_KERNEL_COPYOUT, launch_copy_rgb(c->cv[c->hist], out, n, s));                 // (:382)
-    } else {
-        int src = c->hist;
-        int prev_terms = -1, prev_step = 0;      // tp[] index the previous level stored its geometric terms in, and that level's step
-        for (int level = 1; level <= p->atrous_nlevel; level++) {
-            const bool last = (level == p->atrous_nlevel);
-            const bool keep = (level == p->history_level);      // this level's output becomes the colour history (:391)
-            const bool fuse_here = fused && level == 1;
-            int dst = -1;
-            if (!last || keep) {
-                // (the fused level reads the OLD colour history while it writes: its destination is the third plane)
-                for (int k = pbase; k < pbase + 3; k++) if (k != src && k != c->hist && !(fuse_here && k == old_hist)) { dst = k; break; }
-            }
-            AtrousArgs a;
-            a.src = c->cv[src]; a.dst = dst >= 0 ? c->cv[dst] : nullptr; a.out_rgb = last ? out : nullptr;
-            a.nrm = c->nrm[gnew]; a.pos = c->pos[gnew]; a.gbuf = g; a.albedo = c->albedo;
-            a.W = c->W; a.H = c->H;
-            a.step = 1 << (p->paper_steps ? level - 1 : level);   // reference: level starts at 1 => steps 2,4,8,16,32 (:98,386)
-            a.sigma_c = p->sigma_l; a.sigma_n = p->sigma_n; a.sigma_x = p->sigma_x;
-            a.blur_variance = p->blur_variance ? 1 : 0;
-            a.modulate = (last && p->sepcolor && p->addcolor) ? 1 : 0;
-            // pre-blur source of steps >= 16: the zero-margined 4-byte variance plane the producer level wrote next to its colour
-            // plane (see below); the lane kernel at those steps REQUIRES it (its loaders blur the variance from it)
-            a.var = (c->use_vplane && a.step >= 16 && ((c->vp_valid >> src) & 1u)) ? c->vp[src] : nullptr;
-            a.var_dst = nullptr;
-            a.tin = nullptr; a.tout = nullptr; a.t_m = 0; a.t_m_out = 0;
-            bool strip = false, lattice = false;
-            if (p->kernel_variant != 1) {
-                strip = atrous_strip_supported(a);
-                lattice = !strip && p->kernel_variant != 2 && atrous_lattice_supported(a);     // steps 64, 128, ...
-            }
-            enum { K_FUSED, K_LANE, K_LANE2Y, K_STRIP, K_LATTICE, K_GATHER } which;
-            if (fuse_here) which = K_FUSED;
+    pl.exit = p->right_view_option == 1 ? EXIT_DEBUG_HLEN : p->right_view_option == 2 ? EXIT_DEBUG_VAR : !cascade ? EXIT_COPY : EXIT_CASCADE;
+    pl.n_levels = cascade ? p->atrous_nlevel : 0;
+    int src = hist;
 #ifdef SVGF_BUILD_EXPERIMENTS
-            else if (strip && a.step == 2 && p->kernel_variant == 5 && atrous_lane_supported(a)) which = K_LANE2Y;
+    int terms_out[SVGF_MAX_LEVELS];      // tp[] index a level stores its geometric terms in for the next one, -1: none
 #endif
-            else if (strip && atrous_lane_supported(a) && (p->kernel_variant >= 4 || (p->kernel_variant == 0 && lane_pays(c, a)))) which = K_LANE;
-            else if (strip) which = K_STRIP;
-            else if (lattice) which = K_LATTICE;
-            else which = K_GATHER;
-#ifdef SVGF_BUILD_EXPERIMENTS
-            {
-                int l = 0;
-                while ((1 << l) < a.step && l < 7) l++;
-                const bool asked = p->kernel_variant == 0 && (which == K_FUSED || which == K_LANE || which == K_STRIP) && c->lane_cheaper[l] >= 0;
-                c->lk_kind[c->lk_n] = (int)which; c->lk_step[c->lk_n] = a.step;
-                c->lk_lane_us[c->lk_n] = asked ? c->est_lane_us[l] : __builtin_nan("");
-                c->lk_strip_us[c->lk_n] = asked ? c->est_strip_us[l] : __builtin_nan("");
-                c->lk_n++;
-            }
-#endif
-            // Pre-blur rows (y-1, y+1 of the full-resolution image) of the lane / strip kernels.  At steps >= 16 they are
-            // read as 4-byte gathers out of 16-byte colour texels whose lines nobody else on the XCD touches (PMC: 75.6 /
-            // 72.6 B/px fetched against 40 algorithmic); there the kernels read them from a zero-margined 4-byte variance plane
-            // that the producer level writes next to its colour plane (51.3 / 48.8 B/px, +4 B/px written).  At steps 2-8
-            // the neighbouring rows are the sibling y-phases' own rows, already in L2: a plane would ADD 8 B/px (measured,
-            // profiles/r02_pmc_hbm.txt), so those levels keep reading colour.w and only the level feeding a step-16 level
-            // writes the plane.
-            if (which != K_LANE && which != K_STRIP) a.var = nullptr;
-            if ((which == K_LANE || which == K_STRIP) && c->use_vplane) {
-                if (dst >= 0 && !last && a.step >= 8) a.var_dst = c->vp[dst];
-            }
-            if (dst >= 0) { if (a.var_dst) c->vp_valid |= 1u << dst; else c->vp_valid &= ~(1u << dst); }
-            int terms_out = -1;
-#ifdef SVGF_BUILD_EXPERIMENTS
-            // Cross-level reuse of the geometric terms (svgf_atrous_lane_reuse.hip): a lane-kernel level reads the four terms the
-            // previous lane-kernel level stored for it (its step is twice that level's), and stores four for the next level if that
-            // one will run the lane kernel at twice this step.
-            if (which == K_LANE && c->use_reuse) {
-                if (prev_terms >= 0 && a.step == 2 * prev_step) { a.tin = c->tp[prev_terms]; a.t_m = (c->W + a.step - 1) / a.step; }
-                if (!last && 2 * a.step <= 32) {
-                    AtrousArgs nx = a;
-                    nx.step = 2 * a.step;
-                    nx.var = (c->use_vplane && nx.step >= 16 && a.var_dst) ? a.var_dst : nullptr;
-                    const bool next_lane = atrous_strip_supported(nx) && atrous_lane_supported(nx) &&
-                                           (p->kernel_variant >= 4 || (p->kernel_variant == 0 && lane_pays(c, nx)));
-                    if (next_lane) {
-                        terms_out = (prev_terms == 0) ? 1 : 0;
-                        a.tout = c->tp[terms_out]; a.t_m_out = (c->W + nx.step - 1) / nx.step;
-                    }
-                }
-            }
-#endif
-            prev_terms = terms_out; prev_step = a.step;
-            if (split_fused && level == 1 && which != K_LANE) {      // (the decision above and the kernel choice here use the same model)
-                snprintf(c->err, sizeof(c->err), "svgf_denoise: internal error, the G-buffer split was left to a first level that does not run the lane kernel");
-                return SVGF_ERR_HIP;
-            }
-            // The one kernel of a promised frame that writes the caller's `out`: behind what the caller's stream held when the frame
-            // was handed over (a reader of the same buffer enqueued behind an earlier call, for instance).  The promise is about the
-            // INPUTS only; the output buffer is protected by stream order like everywhere else.
-            if (piped && promise && last) HIPC(c, hipStreamWaitEvent(s, c->ev_in, 0));
-            switch (which) {
-            case K_FUSED:
-                // the accumulated plane itself is only written when something besides this level reads it: a later frame (the
-                // history is not this level's output) or a test (svgf_set_capture)
-                t.cv_acc = (!keep || c->capture) ? c->cv[acc] : nullptr;
-#ifdef SVGF_BUILD_EXPERIMENTS
-                if (p->temporal_enable) LAUNCH(SVGF_KERNEL_FUSED, launch_atrous_fused(a, t, s));
-                else
-#endif
-                LAUNCH(SVGF_KERNEL_FUSED, launch_atrous_prepare_fused(a, t, s));
-                if (c->capture) { HIPC(c, hipMemcpyAsync(c->cv_capture, c->cv[acc], c->n * sizeof(float4), hipMemcpyDeviceToDevice, s)); }
-                break;
-            case K_LANE:       // steps 2 .. 32: symmetric terms evaluated once
-#ifdef SVGF_BUILD_EXPERIMENTS
-                if (split_fused && level == 1) { LAUNCH(SVGF_KERNEL_ATROUS, launch_atrous_split_fused(a, t, s)); break; }
-                if (a.tin || a.tout) { LAUNCH(SVGF_KERNEL_ATROUS, launch_atrous_lane_reuse(a, s)); break; }
-#endif
-                LAUNCH(SVGF_KERNEL_ATROUS, launch_atrous_lane(a, s));
-                break;
-#ifdef SVGF_BUILD_EXPERIMENTS
-            case K_LANE2Y:  LAUNCH(SVGF_KERNEL_ATROUS, launch_atrous_lane_2y(a, s)); break;  // A/B partner of the fused kernel's geometry
-#endif
-            case K_STRIP:   LAUNCH(SVGF_KERNEL_ATROUS, launch_atrous_strip(a, s)); break;
-            case K_LATTICE: LAUNCH(SVGF_KERNEL_ATROUS, launch_atrous_lattice(a, s)); break;
-            default:        LAUNCH(SVGF_KERNEL_ATROUS, launch_atrous_gather(a, s)); break;
-            }
-            if (keep) c->hist = dst;
-            if (piped && keep && !hist_event_recorded) {
-                // everything the NEXT frame's temporal pass reads of this frame is final: the other stream may go on
-                HIPC(c, hipEventRecord(c->ev_hist[pq], s));
-                c->ev_hist_valid[pq] = 1; c->ev_hist_cap[pq] = cap_id; hist_event_recorded = true;
-            }
-            src = dst;
+    for (int i = 0; i < pl.n_levels; i++) {
+        LevelPlan &lv = pl.lv[i];
+        AtrousArgs &a = lv.a;
+        const int level = i + 1;
+        lv.last = (level == p->atrous_nlevel);
+        lv.keep = (level == p->history_level);
+        const bool fuse_here = pl.fused && level == 1;
+        int dst = -1;
+        if (!lv.last || lv.keep) {
+            // (the fused level reads the OLD colour history while it writes: its destination is the third plane)
+            for (int k = pbase; k < pbase + 3; k++) if (k != src && k != hist && !(fuse_here && k == old_hist)) { dst = k; break; }
         }
+        lv.dst = dst;
+        a.src = c->cv[src]; a.dst = dst >= 0 ? c->cv[dst] : nullptr; a.out_rgb = lv.last ? pl.out : nullptr;
+        a.nrm = c->nrm[gnew]; a.pos = c->pos[gnew]; a.gbuf = g; a.albedo = c->albedo;
+        a.W = c->W; a.H = c->H;
+        a.step = 1 << (p->paper_steps ? level - 1 : level);   // reference: level starts at 1 => steps 2,4,8,16,32 (:98,386)
+        a.sigma_c = p->sigma_l; a.sigma_n = p->sigma_n; a.sigma_x = p->sigma_x;
+        a.blur_variance = p->blur_variance ? 1 : 0;
+        a.modulate = (lv.last && p->sepcolor && p->addcolor) ? 1 : 0;
+        // pre-blur source of steps >= 16: the zero-margined 4-byte variance plane the producer level wrote next to its colour
+        // plane (see below); the lane kernel at those steps REQUIRES it (its loaders blur the variance from it)
+        a.var = (c->use_vplane && a.step >= 16 && ((vp_valid >> src) & 1u)) ? c->vp[src] : nullptr;
+        a.var_dst = nullptr;
+        a.tin = nullptr; a.tout = nullptr; a.t_m = 0; a.t_m_out = 0;
+        lv.kind = level_kernel(c, p, a, fuse_here);
+        if (p->kernel_variant == 2 && lv.kind != K_STRIP) {
+            snprintf(c->err, sizeof(c->err), "svgf_denoise: strip kernel does not support %dx%d step %d", c->W, c->H, a.step);
+            return SVGF_ERR_UNSUPPORTED;
+        }
+        lv.asked = p->kernel_variant == 0 && (lv.kind == K_FUSED || lv.kind == K_LANE || lv.kind == K_STRIP) && c->lane_cheaper[step_log2(a.step)] >= 0;
+        // Pre-blur rows (y-1, y+1 of the full-resolution image) of the lane / strip kernels.  At steps >= 16 they are
+        // read as 4-byte gathers out of 16-byte colour texels whose lines nobody else on the XCD touches (PMC: 75.6 /
+        // 72.6 B/px fetched against 40 algorithmic); there the kernels read them from a zero-margined 4-byte variance plane
+        // that the producer level writes next to its colour plane (51.3 / 48.8 B/px, +4 B/px written).  At steps 2-8
+        // the neighbouring rows are the sibling y-phases' own rows, already in L2: a plane would ADD 8 B/px (measured,
+        // profiles/r02_pmc_hbm.txt), so those levels keep reading colour.w and only the level feeding a step-16 level
+        // writes the plane.
+        if (lv.kind != K_LANE && lv.kind != K_STRIP) a.var = nullptr;
+        else if (c->use_vplane && dst >= 0 && !lv.last && a.step >= 8) a.var_dst = c->vp[dst];
+        if (dst >= 0) { if (a.var_dst) vp_valid |= 1u << dst; else vp_valid &= ~(1u << dst); }
+#ifdef SVGF_BUILD_EXPERIMENTS
+        terms_out[i] = -1;
+        // Cross-level reuse of the geometric terms (svgf_atrous_lane_reuse.hip): a lane-kernel level stores four terms for the next
+        // level if that one runs the lane kernel at twice its step, and that level reads them.
+        if (c->use_reuse && i > 0 && lv.kind == K_LANE && pl.lv[i - 1].kind == K_LANE && a.step == 2 * pl.lv[i - 1].a.step && a.step <= 32) {
+            terms_out[i - 1] = (i >= 2 && terms_out[i - 2] == 0) ? 1 : 0;
+            a.tin = pl.lv[i - 1].a.tout = c->tp[terms_out[i - 1]];
+            pl.lv[i - 1].a.t_m_out = a.t_m = (c->W + a.step - 1) / a.step;
+        }
+#endif
+        // the accumulated plane itself is only written by the fused level when something besides that level reads it: a later
+        // frame (the history is not this level's output) or a test (svgf_set_capture)
+        if (fuse_here) t.cv_acc = (!lv.keep || c->capture) ? c->cv[acc] : nullptr;
+        if (lv.keep) hist = dst;
+        src = dst;
     }
-
-    if (piped) {
-        // (frames without a cascade — debug views, pass-through, non-temporal frames — release the next frame at their end: they read
-        // state the next temporal pass rewrites)
-        if (!hist_event_recorded) { HIPC(c, hipEventRecord(c->ev_hist[pq], s)); c->ev_hist_valid[pq] = 1; c->ev_hist_cap[pq] = cap_id; }
-        HIPC(c, hipEventRecord(c->ev_done[pq], s));
-        c->ev_done_valid[pq] = 1; c->ev_done_cap[pq] = cap_id;
-        if (s != s_user) HIPC(c, hipStreamWaitEvent(s_user, c->ev_done[pq], 0));      // what the caller enqueues behind this call sees `out`
-        c->pipe_frames++;
-    }
-    c->last_modulated = (cascade && p->sepcolor && p->addcolor) ? 1 : 0;
-    // 3) history rotation (:396-399): planes swap roles instead of being copied
-    if (p->temporal_enable) c->cur = 1 - c->cur;
-    c->gcur = gnew;
-    view_matrix_from_camera(cam, c->view_prev);
-    if (timer.on) c->prof_count++;
-    c->frame_no++;
+#ifdef SVGF_BUILD_EXPERIMENTS
+    // The G-buffer split alone can ride in the first level's loaders (svgf_atrous_fused.hip, FUSED = 4): the temporal pass then
+    // writes 28 B/px less.  Only where that level runs the lane kernel at step 2 and nothing reads the planes before it does.
+    pl.split_fused = pl.temporal && !pl.fused && c->use_split_fused && g && cascade && p->kernel_variant == 0 && !p->paper_steps &&
+                     p->spatial_variance_frames <= 0 && pl.lv[0].kind == K_LANE && atrous_split_fused_supported(pl.lv[0].a, t);
+#endif
+    t.skip_split = pl.split_fused ? 1 : 0;
+    // The other stream's next temporal pass may go on once everything it reads of this frame is final: behind the level that
+    // writes the colour history; behind the temporal pass where no level of the cascade writes it (it IS the accumulated plane then,
+    // which no level of this frame overwrites, and everything else was final before); frames without a cascade (debug views,
+    // pass-through) and non-temporal frames without such a level release it at their end: they read state that pass rewrites.
+    pl.hist_release = pl.n_levels;
+    if (cascade && p->history_level >= 1 && p->history_level <= p->atrous_nlevel) pl.hist_release = p->history_level - 1;
+    else if (cascade && pl.temporal) pl.hist_release = -1;
+    pl.hist = hist; pl.vp_valid = vp_valid;
+    pl.cur = pl.temporal ? 1 - c->cur : c->cur;      // 3) history rotation (:396-399): planes swap roles instead of being copied
+    pl.last_modulated = (cascade && p->sepcolor && p->addcolor) ? 1 : 0;
     return SVGF_OK;
+}
+
+// Walks the plan.  Of the context it writes the pipeline's event records (and the switch into piped mode), and the profiling slot.
+static int enqueue_frame(svgf_ctx *c, const FramePlan &pl)
+{
+    const int pq = pl.pq, n = (int)c->n;
+    const hipStream_t s = pl.s; const TemporalArgs &t = pl.t;
+    if (pl.flip) { c->piped_mode = 1; pipe_reset(c); }      // (a state flip, nothing is allocated: the colour history lies in plane set 0)
+    if (pl.piped) {
+        c->ev_tdone[pq].valid = 0;      // (re-armed below by a planar frame's temporal pass)
+        if (pl.promise) {
+            HIPC(c, hipEventRecord(c->ev_in, pl.s_user));      // the caller's stream position at hand-over: the last level waits for it (`out`)
+            if (pl.wait_in_first) HIPC(c, hipStreamWaitEvent(s, c->ev_in, 0));
+        }
+        HIPC(c, pipe_wait(s, c->ev_done[pq], pl.cap_id));
+    }
+    KernelTimer timer{ c, s, pl.slot, 0, pl.timed };
+    if (pl.timed) c->ev_n[pl.slot] = 0;
+    // the other stream's frame: this frame's temporal pass (and everything behind it) starts when that frame's colour history,
+    // moments, history lengths and G-buffer planes are final
+    if (pl.piped) HIPC(c, pipe_wait(s, c->ev_hist[1 - pq], pl.cap_id));
+    if (pl.temporal && !pl.fused) {
+        LAUNCH(SVGF_KERNEL_TEMPORAL, launch_temporal(t, s));
+        if (pl.tdone) HIPC(c, pipe_record(c->ev_tdone[pq], s, 0));
+        if (pl.svf > 0)      // f4 extension: spatial variance estimate for short histories (its own profiling slot, same kind)
+            LAUNCH(SVGF_KERNEL_TEMPORAL, launch_spatial_variance(t.cv_acc, t.mom_acc, t.hlen_upd, t.nrm_cur, t.gid_cur, t.W, t.H, pl.svf, s));
+    } else if (!pl.fused) {
+        LAUNCH(SVGF_KERNEL_PREPARE, launch_prepare(t.in_rgb, t.gbuf, t.cv_acc, t.nrm_cur, t.gid_cur, t.pos_cur, t.W, t.H, s));
+    }
+    // (before the early release below: the next frame's copy into the one capture buffer must not overtake this one)
+    if (pl.capture && !pl.fused) HIPC(c, hipMemcpyAsync(c->cv_capture, c->cv[pl.acc], c->n * sizeof(float4), hipMemcpyDeviceToDevice, s));
+    if (pl.piped && pl.hist_release < 0) HIPC(c, pipe_record(c->ev_hist[pq], s, pl.cap_id));
+    switch (pl.exit) {
+    case EXIT_DEBUG_HLEN: LAUNCH(SVGF_KERNEL_DEBUGVIEW, launch_debug_hlen(c->hlen[c->cur], pl.out, n, 100.0f, s)); break;   // pre-update lengths (:374)
+    case EXIT_DEBUG_VAR:  LAUNCH(SVGF_KERNEL_DEBUGVIEW, launch_debug_var(c->cv[pl.acc], pl.out, n, 0.1f, s)); break;         // (:377)
+    case EXIT_COPY:       LAUNCH(SVGF_KERNEL_COPYOUT, launch_copy_rgb(c->cv[pl.acc], pl.out, n, s)); break;                  // (:382)
+    case EXIT_CASCADE:    break;
+    }
+    for (int i = 0; i < pl.n_levels; i++) {
+        const LevelPlan &lv = pl.lv[i]; const AtrousArgs &a = lv.a;
+        // The one kernel of a promised frame that writes the caller's `out`: behind what the caller's stream held when the frame
+        // was handed over (a reader of the same buffer enqueued behind an earlier call, for instance).  The promise is about the
+        // INPUTS only; the output buffer is protected by stream order like everywhere else.
+        if (pl.promise && lv.last) HIPC(c, hipStreamWaitEvent(s, c->ev_in, 0));
+        switch (lv.kind) {
+        case K_FUSED:
+#ifdef SVGF_BUILD_EXPERIMENTS
+            if (pl.temporal) LAUNCH(SVGF_KERNEL_FUSED, launch_atrous_fused(a, t, s));
+            else
+#endif
+            LAUNCH(SVGF_KERNEL_FUSED, launch_atrous_prepare_fused(a, t, s));
+            if (pl.capture) HIPC(c, hipMemcpyAsync(c->cv_capture, c->cv[pl.acc], c->n * sizeof(float4), hipMemcpyDeviceToDevice, s));
+            break;
+        case K_LANE:       // steps 2 .. 32: symmetric terms evaluated once
+#ifdef SVGF_BUILD_EXPERIMENTS
+            if (pl.split_fused && i == 0) { LAUNCH(SVGF_KERNEL_ATROUS, launch_atrous_split_fused(a, t, s)); break; }
+            if (a.tin || a.tout) { LAUNCH(SVGF_KERNEL_ATROUS, launch_atrous_lane_reuse(a, s)); break; }
+#endif
+            LAUNCH(SVGF_KERNEL_ATROUS, launch_atrous_lane(a, s));
+            break;
+#ifdef SVGF_BUILD_EXPERIMENTS
+        case K_LANE2Y:  LAUNCH(SVGF_KERNEL_ATROUS, launch_atrous_lane_2y(a, s)); break;  // A/B partner of the fused kernel's geometry
+#endif
+        case K_STRIP:   LAUNCH(SVGF_KERNEL_ATROUS, launch_atrous_strip(a, s)); break;
+        case K_LATTICE: LAUNCH(SVGF_KERNEL_ATROUS, launch_atrous_lattice(a, s)); break;
+        default:        LAUNCH(SVGF_KERNEL_ATROUS, launch_atrous_gather(a, s)); break;
+        }
+        if (pl.piped && i == pl.hist_release) HIPC(c, pipe_record(c->ev_hist[pq], s, pl.cap_id));
+    }
+    if (pl.piped) {
+        if (pl.hist_release == pl.n_levels) HIPC(c, pipe_record(c->ev_hist[pq], s, pl.cap_id));
+        HIPC(c, pipe_record(c->ev_done[pq], s, pl.cap_id));
+        if (s != pl.s_user) HIPC(c, hipStreamWaitEvent(pl.s_user, c->ev_done[pq].ev, 0));      // what the caller enqueues behind this call sees `out`
+    }
+    return SVGF_OK;
+}
+
+// The context behind a frame whose every call was accepted: the planes' roles rotate, the counters advance.
+static void commit_frame(svgf_ctx *c, const FramePlan &pl, const SvgfCamera *cam)
+{
+    c->acc = pl.acc; c->hist = pl.hist; c->cur = pl.cur; c->gcur = pl.gcur; c->vp_valid = pl.vp_valid; c->last_modulated = pl.last_modulated;
+    if (pl.piped) { c->pipe_frames++; if (pl.cap_id) c->ever_captured = 1; }
+    view_matrix_from_camera(cam, c->view_prev);
+    if (pl.timed) c->prof_count++;
+    c->frame_no++;
+#ifdef SVGF_BUILD_EXPERIMENTS
+    c->lk_n = pl.n_levels;
+    for (int i = 0; i < pl.n_levels; i++) { c->lk_kind[i] = (int)pl.lv[i].kind; c->lk_step[i] = pl.lv[i].a.step; c->lk_asked[i] = pl.lv[i].asked; }
+#endif
+}
+
+static int denoise_frame(svgf_ctx *c, void *out_rgb_dev, const void *in_rgb_dev, const void *gbuffer_dev,
+                         const SvgfCamera *cam, const SvgfParams *p, void *stream)
+{
+    if (!out_rgb_dev || !in_rgb_dev || !cam || !p) {
+        snprintf(c->err, sizeof(c->err), "svgf_denoise: null argument");
+        return SVGF_ERR_INVALID_ARG;
+    }
+    SVGF_ENTER(c);
+    FramePlan pl;
+    int rc = plan_frame(c, out_rgb_dev, in_rgb_dev, gbuffer_dev, p, stream, pl);
+    if (rc == SVGF_OK) rc = enqueue_frame(c, pl);
+    if (rc == SVGF_OK) commit_frame(c, pl, cam);
+    return rc;
 }
 
 extern "C" int svgf_denoise(svgf_ctx *c, void *out_rgb_dev, const void *in_rgb_dev, const void *gbuffer_dev,
@@ -1099,8 +1093,7 @@ extern "C" int svgf_denoise(svgf_ctx *c, void *out_rgb_dev, const void *in_rgb_d
 static int planar_gbuffer(svgf_ctx *c, SvgfPlanarGBuffer *out, bool have_stream, hipStream_t stream)
 {
     if (!c || !out) return SVGF_ERR_INVALID_ARG;
-    SvgfDeviceGuard dev_guard(c->device);
-    if (!dev_guard.ok) { snprintf(c->err, sizeof(c->err), "hipSetDevice(%d) failed", c->device); return SVGF_ERR_HIP; }
+    SVGF_ENTER(c);
     if (!c->albedo) {
         // (first call only.  The clear runs on the legacy stream; the producer that fills the plane may run on a non-blocking
         // stream that does not order itself behind it: the clear is complete before the pointer leaves this function.)
@@ -1119,10 +1112,11 @@ static int planar_gbuffer(svgf_ctx *c, SvgfPlanarGBuffer *out, bool have_stream,
         if (!have_stream) HIPC(c, hipDeviceSynchronize());
         else {
             const int pq = (int)(c->pipe_frames & 1);      // parity of the NEXT frame = parity of the frame before last
-            if (c->ev_done_valid[pq] && !c->ev_done_cap[pq]) HIPC(c, hipStreamWaitEvent(stream, c->ev_done[pq], 0));
-            if (c->ev_tdone_valid[1 - pq]) HIPC(c, hipStreamWaitEvent(stream, c->ev_tdone[1 - pq], 0));
-            else if (c->ev_done_valid[1 - pq] && !c->ev_done_cap[1 - pq]) HIPC(c, hipStreamWaitEvent(stream, c->ev_done[1 - pq], 0));      // (the last frame was not a planar one)
-            if (c->last_modulated && c->ev_done_valid[1 - pq] && !c->ev_done_cap[1 - pq]) HIPC(c, hipStreamWaitEvent(stream, c->ev_done[1 - pq], 0));
+            const svgf_ctx::PipeEvent &last_done = c->ev_done[1 - pq];      // (events recorded under a capture are not waited for: cap id 0)
+            HIPC(c, pipe_wait(stream, c->ev_done[pq], 0));
+            if (pipe_live(c->ev_tdone[1 - pq], 0)) HIPC(c, pipe_wait(stream, c->ev_tdone[1 - pq], 0));
+            else HIPC(c, pipe_wait(stream, last_done, 0));      // (the last frame was not a planar one)
+            if (c->last_modulated) HIPC(c, pipe_wait(stream, last_done, 0));
         }
     }
     const int gnew = 1 - c->gcur;        // the planes the next frame's temporal / prepare pass treats as "current"
@@ -1151,8 +1145,7 @@ extern "C" int svgf_denoise_host(svgf_ctx *c, float *out_rgb_host, const float *
         snprintf(c->err, sizeof(c->err), "svgf_denoise_host: null argument");
         return SVGF_ERR_INVALID_ARG;
     }
-    SvgfDeviceGuard dev_guard(c->device);
-    if (!dev_guard.ok) { snprintf(c->err, sizeof(c->err), "hipSetDevice(%d) failed", c->device); return SVGF_ERR_HIP; }
+    SVGF_ENTER(c);
     if (!c->st_in) HIPC(c, hipMalloc((void **)&c->st_in, c->n * 3 * sizeof(float)));
     if (!c->st_out) HIPC(c, hipMalloc((void **)&c->st_out, c->n * 3 * sizeof(float)));
     if (!c->st_g) HIPC(c, hipMalloc((void **)&c->st_g, c->n * sizeof(SvgfGBufferTexel)));
@@ -1170,8 +1163,7 @@ extern "C" int svgf_denoise_host(svgf_ctx *c, float *out_rgb_host, const float *
 extern "C" int svgf_read_state(svgf_ctx *c, int which, void *host_dst, unsigned long long host_bytes)
 {
     if (!c || !host_dst) return SVGF_ERR_INVALID_ARG;
-    SvgfDeviceGuard dev_guard(c->device);
-    if (!dev_guard.ok) { snprintf(c->err, sizeof(c->err), "hipSetDevice(%d) failed", c->device); return SVGF_ERR_HIP; }
+    SVGF_ENTER(c);
     HIPC(c, hipDeviceSynchronize());
     const size_t n = c->n;
     auto need = [&](size_t b) -> bool {

@@ -675,32 +675,37 @@ long strip_segment_search(int n_strips, int S, int nb_max, int ROWS, int capacit
     return best_cost;
 }
 
-template <int LOG2S, int TX, int ROWS, bool HASVAR>
-hipError_t launch_cfg(const AtrousArgs &a, hipStream_t s)
+// The launch geometry of a level, from the image, the step, the workgroup shape and the device's CU count: fills the geometry
+// launch_cfg launches and returns the cost in lattice rows atrous_strip_estimate_us prices (strip_lds_bytes: also pick()'s budget).
+constexpr size_t strip_lds_bytes(int S, int tx, int rows) { return (size_t)(4 + 2 * rows) * (tx + 4 * S) * 48 + (size_t)2 * rows * 2 * (tx + 2) * 4 + 16; }   // ring + blur rows
+long strip_geometry(int W, int H, int S, int tx, int rows, int n_cu, StripGeom *gm)
 {
-    constexpr int S = 1 << LOG2S, RW = TX + 4 * S, R = 4 + 2 * ROWS, BW = TX + 2;
-    const size_t lds = (size_t)R * RW * 48 + (size_t)2 * ROWS * 2 * BW * 4 + 16;
-    static SvgfLaunchCache cache;
-    int dev_id = 0;
-    if (hipError_t e = cache.init(reinterpret_cast<const void *>(&k_atrous_strip<LOG2S, TX, ROWS, HASVAR>), (int)lds, &dev_id); e != hipSuccess) return e;
-    const int n_cu = cache.n_cu[dev_id];
-    StripGeom gm;
-    gm.n_strips = (a.W + TX - 1) / TX;
-    const int nb_max = (a.H + S - 1) / S;
+    gm->n_strips = (W + tx - 1) / tx;
+    const int nb_max = (H + S - 1) / S;
     // Segment length: every (strip, phase, segment) is one workgroup, and LDS admits `bpc` workgroups per CU, so the
     // grid runs in ceil(blocks / (CUs * bpc)) rounds of equal-length workgroups.  Pick the segment length L that
     // minimises rounds * (L + fixed cost), the fixed cost being the 4 halo rows + the exposed prologue latency.
-    int bpc = (int)((160 * 1024) / lds);
-    constexpr int kLoaderThreads = loader_threads(TX, ROWS);
-    if (bpc > 2048 / (TX * ROWS + kLoaderThreads)) bpc = 2048 / (TX * ROWS + kLoaderThreads);
+    int bpc = (int)((160 * 1024) / strip_lds_bytes(S, tx, rows));
+    const int threads = tx * rows + loader_threads(tx, rows);
+    if (bpc > 2048 / threads) bpc = 2048 / threads;
     if (bpc < 1) bpc = 1;
-    const int capacity = n_cu * bpc;
-    int best_L = nb_max;
-    (void)strip_segment_search(gm.n_strips, S, nb_max, ROWS, capacity, &best_L);
-    if (const int v = SVGF_TUNE("strip_segrows", 0); v > 0) best_L = v;
-    gm.seg_rows = best_L;
-    gm.n_segs = (nb_max + best_L - 1) / best_L;
-    gm.n_groups = S * gm.n_segs;
+    const long cost = strip_segment_search(gm->n_strips, S, nb_max, rows, n_cu * bpc, &gm->seg_rows);
+    if (const int v = SVGF_TUNE("strip_segrows", 0); v > 0) gm->seg_rows = v;      // (tuning: the cost stays that of the searched length)
+    gm->n_segs = (nb_max + gm->seg_rows - 1) / gm->seg_rows;
+    gm->n_groups = S * gm->n_segs;
+    return cost;
+}
+
+template <int LOG2S, int TX, int ROWS, bool HASVAR>
+hipError_t launch_cfg(const AtrousArgs &a, hipStream_t s)
+{
+    constexpr int S = 1 << LOG2S, kLoaderThreads = loader_threads(TX, ROWS);
+    constexpr size_t lds = strip_lds_bytes(S, TX, ROWS);
+    static SvgfLaunchCache cache;
+    int dev_id = 0;
+    if (hipError_t e = cache.init(reinterpret_cast<const void *>(&k_atrous_strip<LOG2S, TX, ROWS, HASVAR>), (int)lds, &dev_id); e != hipSuccess) return e;
+    StripGeom gm;
+    (void)strip_geometry(a.W, a.H, S, TX, ROWS, cache.n_cu[dev_id], &gm);
     gm.dbg = nullptr; gm.dbg_block = 0;
     static unsigned long long *dbg_buf = nullptr;
     const int dbg_block = SVGF_TUNE("strip_dbg", -1);
@@ -762,8 +767,7 @@ void pick(int log2s, int W, int &tx, int &rows)
     if (const int v = SVGF_TUNE("strip_rows", 0); v >= 1 && v <= 3) rows = v;
     if (rows == 3 && tx != 256) rows = 2;
     // LDS budget: ring + blur rows <= 160 KiB
-    const int S = 1 << log2s;
-    while ((size_t)(4 + 2 * rows) * (tx + 4 * S) * 48 + (size_t)2 * rows * 2 * (tx + 2) * 4 + 16 > 160 * 1024 && rows > 1) rows--;
+    while (strip_lds_bytes(1 << log2s, tx, rows) > 160 * 1024 && rows > 1) rows--;
 }
 
 }  // namespace
@@ -783,14 +787,8 @@ double atrous_strip_estimate_us(const AtrousArgs &a, int n_cu)
     while ((1 << log2s) < a.step) log2s++;
     int tx, rows;
     pick(log2s, a.W, tx, rows);
-    const int S = 1 << log2s;
-    const size_t lds = (size_t)(4 + 2 * rows) * (tx + 4 * S) * 48 + (size_t)2 * rows * 2 * (tx + 2) * 4 + 16;
-    int bpc = (int)((160 * 1024) / lds);
-    const int threads = tx * rows + loader_threads(tx, rows);
-    if (bpc > 2048 / threads) bpc = 2048 / threads;
-    if (bpc < 1) bpc = 1;
-    int L = 0;
-    return 1.162 * (double)strip_segment_search((a.W + tx - 1) / tx, S, (a.H + S - 1) / S, rows, n_cu * bpc, &L);
+    StripGeom gm;
+    return 1.162 * (double)strip_geometry(a.W, a.H, 1 << log2s, tx, rows, n_cu, &gm);
 }
 
 #define STRIP_CASE(L, T, Rr) if (log2s == L && tx == T && rows == Rr) return a.dst ? launch_cfg<L, T, Rr, true>(a, s) : launch_cfg<L, T, Rr, false>(a, s);
