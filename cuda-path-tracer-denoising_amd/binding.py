@@ -114,6 +114,19 @@ def exp_clear():
     load_library(experiments=True).svgf_exp_clear()
 
 
+def atrous_geometry(kernel: str, W: int, H: int, step: int, blur_variance: int = 1, has_variance_plane: int = 1, n_cu: int = 256):
+    """svgf_exp_atrous_geometry of the experiments build: ([supported, n_strips, seg_rows, n_segs, n_groups, grid blocks, block threads,
+    LDS bytes], estimate in us or None) of one a-trous level on `kernel` (LEVEL_KERNEL_NAMES; lattice: [supported, log2k, pstride,
+    band_rows, n_bands, grid blocks, block threads, LDS bytes]).  Host arithmetic only: works without a device."""
+    out, est = (C.c_int * 8)(), C.c_double()
+    f = load_library(experiments=True).svgf_exp_atrous_geometry
+    f.argtypes = [C.c_int] * 7 + [C.POINTER(C.c_int), C.POINTER(C.c_double)]
+    rc = f(LEVEL_KERNEL_NAMES.index(kernel), W, H, step, blur_variance, has_variance_plane, n_cu, out, C.byref(est))
+    if rc != SVGF_OK:
+        raise SvgfError(f"svgf_exp_atrous_geometry({kernel}, {W}x{H}, step {step}, {n_cu} CUs) -> {rc}")
+    return list(out), (None if np.isnan(est.value) else est.value)
+
+
 def load_library(path: str | None = None, experiments: bool = False):
     """Load libsvgf_hip.so (or, experiments=True / after use_experiments_library(), libsvgf_hip_exp.so) and declare prototypes.
     Fails loudly when the library is absent.  No environment variable is read."""

@@ -14,7 +14,7 @@ LIB = os.path.join(_HERE, "libsvgf_hip.so")
 # (svgf_exp_set).  Test / tools infrastructure: nothing on the product path loads it (binding.load_library(experiments=True) does).
 LIB_EXP = os.path.join(_HERE, "libsvgf_hip_exp.so")
 
-HIP_SOURCES = ["svgf_api.hip", "svgf_kernels.hip", "svgf_atrous_strip.hip", "svgf_atrous_lane.hip", "svgf_atrous_prepare_fused.hip", "svgf_atrous_lattice.hip", "svgf_synth.hip", "svgf_scene.hip", "svgf_display.hip"]
+HIP_SOURCES = ["svgf_api.hip", "svgf_kernels.hip", "svgf_atrous_geometry.hip", "svgf_atrous_strip.hip", "svgf_atrous_lane.hip", "svgf_atrous_prepare_fused.hip", "svgf_atrous_lattice.hip", "svgf_synth.hip", "svgf_scene.hip", "svgf_display.hip"]
 HIP_SOURCES_EXPERIMENTS = ["svgf_atrous_lane_reuse.hip", "svgf_atrous_fused.hip"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unused-function"]
 # Per-file flags.  svgf_atrous_fused.hip: SimplifyCFG's common-code sinking merges the last store of the "bilinear history" branch
@@ -50,7 +50,7 @@ def build_hip(force: bool = False, experiments: bool = False) -> str:
     tuning table behind svgf_exp_set; what tools/experiments/ and the tests marked `experiments` load)."""
     LIB = LIB_EXP if experiments else globals()["LIB"]
     srcs = [os.path.join(CSRC, s) for s in HIP_SOURCES + (HIP_SOURCES_EXPERIMENTS if experiments else [])]
-    deps = srcs + [os.path.join(CSRC, h) for h in ("svgf_kernels.h", "svgf_temporal.h", "svgf_atrous_lane_impl.h", "svgf_atrous_lane_tfused.inc.h")] + [os.path.join(ROOT, "include", "svgf.h")]
+    deps = srcs + [os.path.join(CSRC, h) for h in sorted(os.listdir(CSRC)) if h.endswith(".h")] + [os.path.join(ROOT, "include", "svgf.h")]
     if not force and _newer(LIB, deps):
         return LIB
     tmp = LIB + f".tmp{os.getpid()}"

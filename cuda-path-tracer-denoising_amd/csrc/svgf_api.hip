@@ -14,7 +14,7 @@
 #include <new>
 
 #include "../../include/svgf.h"
-#include "svgf_kernels.h"
+#include "svgf_atrous_geometry.h"
 
 #define SVGF_MAX_KERNELS_PER_FRAME (SVGF_MAX_LEVELS + 4)
 // the prepare pass of the non-temporal mode fused into the first level (svgf_atrous_prepare_fused.hip, FUSED = 3): on by default
@@ -103,7 +103,7 @@ struct svgf_ctx {
 };
 
 static char g_create_err[512] = "";
-static int step_log2(int step) { int l = 0; while ((1 << l) < step && l < 7) l++; return l; }      // index of lane_cheaper[] / est_*_us[]
+static int step_log2(int step) { const int l = atrous_step_log2(step); return l < 7 ? l : 7; }      // index of lane_cheaper[] / est_*_us[]
 
 #define HIPC(ctx, call)                                                                              \
     do {                                                                                             \
@@ -670,32 +670,14 @@ static int enable_pipeline(svgf_ctx *c)
     return SVGF_OK;
 }
 
-// Auto selection between the two fast a-trous kernels for steps 2-32.  The lane-marching kernel works on 480-column strips (at
-// steps 16 / 32: 120 / 60 lattice columns of 4 / 8 x-phases), the strip kernel on 256-column strips; both cut the image into
-// (strip, y-phase, segment) workgroups that run in rounds of one per CU, and both know what their launch will cost:
-// rounds x (segment rows + fixed rows) x the time of a row (1.86 us lane, 1.16 us strip: 42.7 against 48.8 us at 1920x1080).
-// The cheaper one runs.  Measured against that model at nine sizes (profiles/r03_exp_widths*.log): within 5 %, same choice as
-// the stopwatch everywhere — lane at 1920, 3840, 1600, 3440, 800 (steps 2-8), 2560 and 1280 (steps 2-8, 32); strip at 1024,
-// 2048, and at steps 16 of 800 / 1280 / 2560.  That holds for frames taller than about six lattice rows per level (H / step >= 6);
-// shorter phases are one segment each on both kernels, and the one-round launches then favour the strip kernel's shorter rows
-// at the coarse steps (tests/test_kernel_geometry_gpu.py holds the per-level table for a 256-CU device).
-// Every level of a phase shorter than 3 lattice rows is one segment on the lane kernel, whose segment search (4 .. nb_max + 1
-// rows) then evaluates nothing: such a level is costed here as that one segment, rounds x (nb_max + 6) rows.  The rounds of a
-// one-segment geometry do not depend on H, so they are those of a 3-row phase (the search's one candidate there: 4 + 6 rows).
-static double lane_estimate_us(svgf_ctx *c, const AtrousArgs &a)
-{
-    const int nb_max = (a.H + a.step - 1) / a.step;
-    if (nb_max >= 3) return atrous_lane_estimate_us(a, c->n_cu);
-    AtrousArgs three = a;
-    three.H = 3 * a.step;
-    return atrous_lane_estimate_us(three, c->n_cu) * (double)(nb_max + 6) / 10.0;
-}
-
+// The automatic choice between the two fast a-trous kernels for steps 2-32: the one whose launch geometry is estimated cheaper runs
+// (the cost model: svgf_atrous_geometry.hip).  The estimates depend on the image size and the device only, so they are asked for
+// once per context and step.
 static bool lane_pays(svgf_ctx *c, const AtrousArgs &a)
 {
     const int l = step_log2(a.step);
-    if (c->lane_cheaper[l] < 0) {        // depends on the image size and the device only: evaluated once per context and step
-        const double lane = lane_estimate_us(c, a), strip = atrous_strip_estimate_us(a, c->n_cu);
+    if (c->lane_cheaper[l] < 0) {
+        const double lane = atrous_lane_estimate_us(a, c->n_cu), strip = atrous_strip_estimate_us(a, c->n_cu);
         c->lane_cheaper[l] = lane <= strip ? 1 : 0;
 #ifdef SVGF_BUILD_EXPERIMENTS
         c->est_lane_us[l] = lane; c->est_strip_us[l] = strip;
@@ -712,7 +694,7 @@ static bool lane_pays(svgf_ctx *c, const AtrousArgs &a)
 static bool fuse_pays(svgf_ctx *c, const AtrousArgs &a)
 {
     if (c->fuse_pays < 0) {
-        const double lane = atrous_lane_supported(a) ? lane_estimate_us(c, a) : 1e30;
+        const double lane = atrous_lane_supported(a) ? atrous_lane_estimate_us(a, c->n_cu) : 1e30;
         const double strip = atrous_strip_supported(a) ? atrous_strip_estimate_us(a, c->n_cu) : 1e30;
         const double level = lane < strip ? lane : strip;
         const double temporal_us = 0.0256e-3 * (double)c->W * (double)c->H;
@@ -725,6 +707,64 @@ static bool fuse_pays(svgf_ctx *c, const AtrousArgs &a)
 // ---- the frame: plan (every decision, nothing enqueued), enqueue (walks the plan), commit (the context's state behind it) ----
 enum KernelKind { K_FUSED, K_LANE, K_LANE2Y, K_STRIP, K_LATTICE, K_GATHER };      // (the numbering svgf_exp_level_kernels reports)
 enum FrameExit { EXIT_CASCADE, EXIT_DEBUG_HLEN, EXIT_DEBUG_VAR, EXIT_COPY };
+
+#ifdef SVGF_BUILD_EXPERIMENTS
+// The launch geometry of one a-trous level on one kernel (0 fused first level, 1 lane, 2 lane with two y-phases, 3 strip,
+// 4 lattice: the numbering of svgf_exp_level_kernels) for a W x H frame on a device of n_cu compute units, as the launcher would
+// compute it (svgf_atrous_geometry.h) — host arithmetic only, no device is touched.  out[0..7]: supported, n_strips, seg_rows,
+// n_segs, n_groups, grid blocks, block threads, LDS bytes (lattice: supported, log2k, pstride, band_rows, n_bands, grid blocks,
+// block threads, LDS bytes); all zero where the kernel does not run such a level.  *estimate_us: what the automatic choice compares (lane, strip,
+// fused), NaN for the others.  For the two-y-phase kernels "supported" is the geometry's own condition (step 2, the lane
+// kernel's limits), not the fused kernel's conditions on the context's planes.
+extern "C" int svgf_exp_atrous_geometry(int kernel, int W, int H, int step, int blur_variance, int has_variance_plane, int n_cu,
+                                        int *out, double *estimate_us)
+{
+    if (!out || !estimate_us || W < 1 || H < 1 || step < 1 || n_cu < 1) return SVGF_ERR_INVALID_ARG;
+    static const float plane = 0.0f;      // a.var is only tested for null here
+    AtrousArgs a;
+    memset(&a, 0, sizeof(a));
+    a.W = W; a.H = H; a.step = step; a.blur_variance = blur_variance; a.var = has_variance_plane ? &plane : nullptr;
+    for (int k = 0; k < 8; k++) out[k] = 0;
+    *estimate_us = __builtin_nan("");
+    SegmentGeom gm;
+    int threads = 0, lds = 0;
+    switch (kernel) {
+    case K_LANE:
+        if (!atrous_lane_supported(a)) return SVGF_OK;
+        (void)lane_geometry(a, 1, n_cu, &gm);
+        *estimate_us = atrous_lane_estimate_us(a, n_cu);
+        atrous_lane_block(a, &threads, &lds);
+        break;
+    case K_FUSED: case K_LANE2Y:
+        if (step != 2 || !atrous_lane_supported(a)) return SVGF_OK;
+        (void)lane_geometry(a, 2, n_cu, &gm);
+        if (kernel == K_FUSED) *estimate_us = atrous_fused_estimate_us(a, n_cu);
+        atrous_lane2y_block(kernel == K_FUSED, &threads, &lds);
+        break;
+    case K_STRIP: {
+        if (!atrous_strip_supported(a)) return SVGF_OK;
+        int tx, rows;
+        strip_pick(atrous_step_log2(step), tx, rows);
+        (void)strip_geometry(a, tx, rows, n_cu, &gm);
+        *estimate_us = atrous_strip_estimate_us(a, n_cu);
+        threads = strip_shape::block_threads(tx, rows); lds = (int)strip_shape::lds_bytes(step, tx, rows);
+        break;
+    }
+    case K_LATTICE: {
+        LatticeTiles lt;
+        if (!lattice_geometry(a, lt)) return SVGF_OK;
+        const int v[8] = { 1, lt.log2k, lt.pstride, lt.band_rows, lt.n_bands, (int)lattice_grid_blocks(lt), kLatticeThreads, (int)lattice_lds_bytes(lt) };
+        memcpy(out, v, sizeof(v));
+        return SVGF_OK;
+    }
+    default:
+        return SVGF_ERR_INVALID_ARG;
+    }
+    const int v[8] = { 1, gm.n_strips, gm.seg_rows, gm.n_segs, gm.n_groups, segment_grid_blocks(gm), threads, lds };
+    memcpy(out, v, sizeof(v));
+    return SVGF_OK;
+}
+#endif
 
 struct LevelPlan {
     KernelKind kind;

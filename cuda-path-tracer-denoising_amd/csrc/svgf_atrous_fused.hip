@@ -65,12 +65,6 @@ bool atrous_fused_supported(const AtrousArgs &a, const TemporalArgs &t)
     return fused_offsets(t, &f);                                     // every plane inside the context's one allocation
 }
 
-double atrous_fused_estimate_us(const AtrousArgs &a, int n_cu)
-{
-    int L = 0;
-    return 1.857 * (double)lane_segment_search(lane_strip_count(a.W, 2, 2), 1, (a.H + 1) / 2, n_cu, &L);
-}
-
 hipError_t launch_atrous_fused(const AtrousArgs &a, const TemporalArgs &t, hipStream_t s)
 {
     if (a.step != 2) return hipErrorInvalidValue;
@@ -104,4 +98,11 @@ hipError_t launch_atrous_lane_2y(const AtrousArgs &a, hipStream_t s)
 {
     if (a.step != 2) return hipErrorInvalidValue;
     return a.dst ? launch_lane_cfg<1, true, 1, 1, 0>(a, s) : launch_lane_cfg<1, false, 1, 1, 0>(a, s);
+}
+
+// svgf_exp_atrous_geometry: the workgroup of the two-y-phase kernels, with (fused) or without the temporal pass in the loaders
+void atrous_lane2y_block(bool fused, int *threads, int *lds_bytes)
+{
+    *threads = NT;
+    *lds_bytes = fused ? LaneLayout<1, 1, 1, 1>::lds_bytes : LaneLayout<1, 1, 1, 0>::lds_bytes;
 }

@@ -1,26 +1,6 @@
 // svgf_atrous_lane.hip — the plain a-trous levels on the lane-marching kernel (svgf_atrous_lane_impl.h): steps 1 .. 32.
 #include "svgf_atrous_lane_impl.h"
 
-// Estimated duration of a level on this kernel: the launch geometry's cost in lattice rows x 1.86 us (1920x1080: one round of
-// 17 + 6 rows = 42.7 us; profiles/r03_exp_widths*.log: within 5 % at eight other sizes).  Used by the automatic kernel choice.
-double atrous_lane_estimate_us(const AtrousArgs &a, int n_cu)
-{
-    const int S = a.step;
-    int L = 0;
-    return 1.857 * (double)lane_segment_search(lane_strip_count(a.W, S), S, (a.H + S - 1) / S, n_cu, &L);
-}
-
-bool atrous_lane_supported(const AtrousArgs &a)
-{
-    if (a.step == 16 || a.step == 32) {            // chunked x-phases: the loaders blur the variance from the 4-byte plane
-        if ((long long)a.W * a.H * 16 >= (1LL << 32)) return false;
-        return a.var != nullptr || !a.blur_variance;
-    }
-    if (a.step != 1 && a.step != 2 && a.step != 4 && a.step != 8) return false;   // step 1: SvgfParams::paper_steps
-    if ((long long)a.W * a.H * 16 >= (1LL << 32)) return false;
-    return true;
-}
-
 hipError_t launch_atrous_lane(const AtrousArgs &a, hipStream_t s)
 {
     if (a.tin || a.tout) return hipErrorInvalidValue;                 // cross-level reuse of the geometric terms: svgf_atrous_lane_reuse.hip (experiments build)
@@ -34,3 +14,14 @@ hipError_t launch_atrous_lane(const AtrousArgs &a, hipStream_t s)
     default: return hipErrorInvalidValue;
     }
 }
+
+#ifdef SVGF_BUILD_EXPERIMENTS
+// svgf_exp_atrous_geometry: the workgroup of the plain level of a.step
+void atrous_lane_block(const AtrousArgs &a, int *threads, int *lds_bytes)
+{
+    const int l = atrous_step_log2(a.step);
+    *threads = NT;
+    *lds_bytes = l == 0 ? LaneLayout<0, 0, 0, 0>::lds_bytes : l == 1 ? LaneLayout<1, 1, 0, 0>::lds_bytes : l == 2 ? LaneLayout<2, 2, 0, 0>::lds_bytes
+               : l == 3 ? LaneLayout<3, 3, 0, 0>::lds_bytes : l == 4 ? LaneLayout<4, 3, 0, 0>::lds_bytes : LaneLayout<5, 3, 0, 0>::lds_bytes;
+}
+#endif

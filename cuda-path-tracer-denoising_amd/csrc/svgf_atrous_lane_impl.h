@@ -29,11 +29,10 @@
 //
 // LDS: ring 6 rows (b-2 .. b+2 live, b+3 incoming) x (480 + 4S) pixels x 48 B = 140.5 .. 147.5 KB, + pre-blur rows.
 #pragma once
-#include "svgf_kernels.h"
+#include "svgf_atrous_geometry.h"
 #include "svgf_temporal.h"
 
 #include <cstdio>
-#include <cstdlib>
 #include <type_traits>
 
 #ifndef SVGF_LANE_SPLIT_PROLOGUE
@@ -60,18 +59,41 @@ constexpr int LOUT = 60;                     // output lanes per wave (2 halo la
 constexpr int TXO = NWC * LOUT;              // 480 output pixels per workgroup and iteration, for every S (one row of 480, or two rows of 240)
 constexpr int kLoaderGroups = 2, kLoaderGroup = 128, kLoaderThreads = kLoaderGroups * kLoaderGroup;
 constexpr int NC = NWC * 64, NT = NC + kLoaderThreads;
-constexpr int PXB = 48;
+constexpr int PXB = kStagedPixelBytes;
 constexpr int R = 6;                         // ring slots: rows b-2 .. b+2 live, b+3 incoming
 constexpr int BW = TXO + 2;                  // pre-blur row: pixel columns x0-1 .. x0+TXO (one y-phase per workgroup only)
 
 typedef float v2f __attribute__((ext_vector_type(2)));
 typedef float v4f __attribute__((ext_vector_type(4)));
 
-struct LaneGeom {
-    int n_strips, n_segs, seg_rows, n_groups;
-    float kn, kx;
-    unsigned long long *dbg;   // tuning only (-DSVGF_LANE_TIMELINE + svgf_exp_set("lane_dbg", <block>)): s_memtime stamps of one workgroup
-    int dbg_block;
+static_assert(TXO == kLaneStripColumns && LOUT * (NWC / kLaneChunkPhases) == kLaneChunkColumns, "lane_strip_count() counts these strips");
+
+struct LaneGeom : SegmentGeom {};      // (the kernels' symbol names carry this type's name)
+
+// LDS layout of one instantiation: what the kernel addresses and what its launcher asks for
+template <int LOG2S, int LOG2P, int LOG2Y, int FUSED>
+struct LaneLayout {
+    static constexpr int S = 1 << LOG2S;
+    static constexpr int P = 1 << LOG2P;                // x-phases held by one workgroup
+    static constexpr int YP = 1 << LOG2Y;               // y-phases held by one workgroup
+    static constexpr int WPP = NWC / (P * YP);          // waves per x-phase (and y-phase)
+    static constexpr int M = LOUT * WPP + 4;            // lattice columns per phase in the ring (2 halo either side)
+    // phase stride in records, padded so that (a) consecutive phases do not start on the same bank for the readers and (b) the
+    // loaders' 16-byte stores, which are served eight consecutive lanes = pixels at a time with banks counted mod 32, do not
+    // collide: with S = 4 those eight lanes are phases 0..3 of two lattice columns, and 124 * 12 = 16 (mod 32) put phases 0 / 2
+    // and 1 / 3 on the same banks (a third of the kernel's remaining conflict cycles); 126 * 12 = 8 (mod 32) spreads all eight
+    static constexpr int MP = (P == 4) ? M + 2 : ((M * 12 % 64 == 0) ? M + 1 : M);
+    static constexpr int RW = P * M;                    // staged pixel columns (= TXO + 4S when P == S)
+    static constexpr int ROWB = P * MP * PXB;           // bytes per ring row (one lattice row of one y-phase)
+    static constexpr int BM = (BW + S - 1) / S;         // pre-blur lattice columns per phase
+    static constexpr int RING_BYTES = R * YP * ROWB;    // ring row of (lattice row slot s, y-phase yp): s * YP + yp
+    static constexpr int BLUR_ROW = S * BM;             // floats per pre-blur row (phase-major)
+    static constexpr int BLUR_BUF = (YP > 1) ? 0 : (P < S ? P * M : 2 * BLUR_ROW);      // [y-1 | y+1], or the blurred variance [phase][column]; none with both y-phases in the ring
+    // ring, two pre-blur buffers (iteration parity), the nan_seen flag, and with the fused temporal pass its 48-byte dump record
+    // (svgf_atrous_lane_tfused.inc.h: kLdsDump)
+    static constexpr int lds_bytes = RING_BYTES + 2 * BLUR_BUF * 4 + 16 + ((FUSED == 1 || FUSED == 2) ? 80 : 0);
+    static_assert(lds_bytes <= 160 * 1024, "LDS budget");
+    static_assert(P == S || ((S == 16 || S == 32) && P == kLaneChunkPhases), "lane_strip_count() knows these chunk sizes");
 };
 
 struct Px {
@@ -155,9 +177,8 @@ template <int LOG2S, bool HASVAR, int LOG2P = LOG2S, int LOG2Y = 0, int FUSED = 
 __global__ __launch_bounds__(NT) void k_atrous_lane(AtrousArgs a, LaneGeom gm, std::conditional_t<FUSED != 0, LaneFused, LaneNoTemporal> ta)
 {
     constexpr bool REUSE_IN = (REUSE & 1) != 0, REUSE_OUT = (REUSE & 2) != 0;
-    constexpr int S = 1 << LOG2S;
-    constexpr int P = 1 << LOG2P;                // x-phases held by one workgroup
-    constexpr int YP = 1 << LOG2Y;               // y-phases held by one workgroup
+    using LY = LaneLayout<LOG2S, LOG2P, LOG2Y, FUSED>;
+    constexpr int S = LY::S, P = LY::P, YP = LY::YP;
     constexpr bool CHUNKED = (P < S);
     static_assert(YP == 1 || (YP == 2 && S == 2 && P == S), "two y-phases per workgroup: step 2 only");
     constexpr bool TFUSED = (FUSED == 1 || FUSED == 2), PFUSED = (FUSED == 3 || FUSED == 4);      // PFUSED: the loaders read texels and write the split planes
@@ -168,20 +189,9 @@ __global__ __launch_bounds__(NT) void k_atrous_lane(AtrousArgs a, LaneGeom gm, s
                   "experiments (-DSVGF_BUILD_EXPERIMENTS, libsvgf_hip_exp.so)");
 #endif
     static_assert(!PFUSED || (YP == 1 && P == S), "the fused prepare pass uses the plain geometry of steps <= 8");
-    constexpr int WPP = NWC / (P * YP);          // waves per x-phase (and y-phase)
+    constexpr int WPP = LY::WPP, M = LY::M, MP = LY::MP, RW = LY::RW, ROWB = LY::ROWB, BM = LY::BM;
+    constexpr int RING_BYTES = LY::RING_BYTES, BLUR_ROW = LY::BLUR_ROW, BLUR_BUF = LY::BLUR_BUF;
     constexpr int TXW = TXO / YP;                // output pixel columns per workgroup
-    constexpr int M = LOUT * WPP + 4;            // lattice columns per phase in the ring (2 halo either side)
-    // phase stride in records, padded so that (a) consecutive phases do not start on the same bank for the readers and (b) the
-    // loaders' 16-byte stores, which are served eight consecutive lanes = pixels at a time with banks counted mod 32, do not
-    // collide: with S = 4 those eight lanes are phases 0..3 of two lattice columns, and 124 * 12 = 16 (mod 32) put phases 0 / 2
-    // and 1 / 3 on the same banks (a third of the kernel's remaining conflict cycles); 126 * 12 = 8 (mod 32) spreads all eight
-    constexpr int MP = (P == 4) ? M + 2 : ((M * 12 % 64 == 0) ? M + 1 : M);
-    constexpr int RW = P * M;                    // staged pixel columns (= TXO + 4S when P == S)
-    constexpr int ROWB = P * MP * PXB;           // bytes per ring row (one lattice row of one y-phase)
-    constexpr int BM = (BW + S - 1) / S;         // pre-blur lattice columns per phase
-    constexpr int RING_BYTES = R * YP * ROWB;    // ring row of (lattice row slot s, y-phase yp): s * YP + yp
-    constexpr int BLUR_ROW = S * BM;             // floats per pre-blur row (phase-major)
-    constexpr int BLUR_BUF = (YP > 1) ? 0 : (CHUNKED ? P * M : 2 * BLUR_ROW);      // [y-1 | y+1], or the blurred variance [phase][column]; none with both y-phases in the ring
     constexpr int TXL = LOUT * WPP;              // lattice columns a workgroup outputs per phase
     static_assert(CHUNKED || RW == TXW + 4 * S, "layout");
     // chunked x-phases: each loader thread of a group blurs ONE unit of four staged columns per row (vblur_load / vblur_store)
@@ -1057,97 +1067,34 @@ __global__ __launch_bounds__(NT) void k_atrous_lane(AtrousArgs a, LaneGeom gm, s
     }
 }
 
-// strips: TXO contiguous pixel columns (one x-phase per wave group), or (lattice-column strip, group of P phases) pairs (chunked)
-inline int lane_strip_count(int W, int S, int YP = 1)
-{
-    if (S <= 8) return (W + TXO / YP - 1) / (TXO / YP);
-    const int P = 8, txl = LOUT * (NWC / P);      // steps 16, 32: chunks of 8 x-phases, one wave of 60 lattice columns each
-    return (((W + S - 1) / S + txl - 1) / txl) * (S / P);
-}
-
-// segment length: one workgroup per CU (LDS-bound); the busiest XCD sets the number of rounds (see the strip kernel).  Returns
-// the minimum of rounds * (L + 6) in lattice rows and the segment length that reaches it.
-// (S = number of y-phase groups a strip is cut into: the step, or step / 2 with both y-phases in one workgroup)
-inline long lane_segment_search(int n_strips, int S, int nb_max, int n_cu, int *best_L_out)
-{
-    int best_L = nb_max;
-    long best_cost = -1;
-    const long cu_xcd = n_cu / 8 > 0 ? n_cu / 8 : 1;
-    for (int L = 4; L <= nb_max + 1; L++) {
-        const int segs_l = (nb_max + L - 1) / L;
-        const long blocks_xcd = (long)n_strips * ((S * segs_l + 7) / 8);
-        const long rounds = (blocks_xcd + cu_xcd - 1) / cu_xcd;
-        const long cost = rounds * (L + 6);
-        if (best_cost < 0 || cost <= best_cost) { best_cost = cost; best_L = L; }
-    }
-    *best_L_out = best_L;
-    return best_cost;
-}
-
 template <int LOG2S, bool HASVAR, int LOG2P = LOG2S, int LOG2Y = 0, int FUSED = 0, int REUSE = 0>
 hipError_t launch_lane_cfg(const AtrousArgs &a, hipStream_t s, const LaneFused *ta = nullptr)
 {
-    constexpr int S = 1 << LOG2S, P = 1 << LOG2P, YP = 1 << LOG2Y, M = LOUT * (NWC / (P * YP)) + 4, MP = (P == 4) ? M + 2 : ((M * 12 % 64 == 0) ? M + 1 : M), BM = (BW + S - 1) / S;
-    constexpr size_t kLds = (size_t)R * YP * P * MP * PXB + (size_t)2 * (YP > 1 ? 0 : (P < S ? P * M : 2 * S * BM)) * 4 + 16 + ((FUSED == 1 || FUSED == 2) ? 80 : 0);
-    const size_t lds = kLds;
-    static_assert(kLds <= 160 * 1024, "LDS budget");
+    constexpr size_t lds = LaneLayout<LOG2S, LOG2P, LOG2Y, FUSED>::lds_bytes;
     static SvgfLaunchCache cache;
     int dev_id = 0;
     if (hipError_t e = cache.init(reinterpret_cast<const void *>(&k_atrous_lane<LOG2S, HASVAR, LOG2P, LOG2Y, FUSED, REUSE>), (int)lds, &dev_id); e != hipSuccess) return e;
-    const int n_cu = cache.n_cu[dev_id];
     LaneGeom gm;
-    gm.n_strips = lane_strip_count(a.W, S, YP);
-    static_assert(P == S || ((S == 16 || S == 32) && P == 8), "lane_strip_count knows these chunk sizes");
-    const int nb_max = (a.H + S - 1) / S;
-    int best_L = nb_max;
-    (void)lane_segment_search(gm.n_strips, S / YP, nb_max, n_cu, &best_L);
-    if (const int v = SVGF_TUNE("lane_segrows", 0); v > 0) best_L = v;      // experiments build only (tools/experiments/exp_small_frames.sh)
-    gm.seg_rows = best_L;
-    gm.n_segs = (nb_max + best_L - 1) / best_L;
-    gm.n_groups = (S / YP) * gm.n_segs;
-    gm.kn = (float)(1.4426950408889634 / ((double)a.sigma_n + 1e-6));
-    gm.kx = (float)(1.4426950408889634 / ((double)a.sigma_x + 1e-6));
-    const int groups_pad = (gm.n_groups + 7) / 8 * 8;
-    const int nblocks = groups_pad * gm.n_strips;
-    gm.dbg = nullptr; gm.dbg_block = 0;
+    (void)lane_geometry(a, 1 << LOG2Y, cache.n_cu[dev_id], &gm);
+    const int nblocks = segment_grid_blocks(gm);
 #ifdef SVGF_LANE_TIMELINE
-    static unsigned long long *dbg_buf = nullptr;
-    const int dbg_block = SVGF_TUNE("lane_dbg", -1);
-    const bool dbg_env = dbg_block >= 0;
-    if (dbg_env) {
-        if (!dbg_buf) (void)hipMalloc((void **)&dbg_buf, 16 * 16 * 8 * sizeof(unsigned long long));
-        (void)hipMemsetAsync(dbg_buf, 0, 16 * 16 * 8 * sizeof(unsigned long long), s);
-        gm.dbg = dbg_buf; gm.dbg_block = dbg_block;
-    }
+    static SegmentTimeline timeline;
+    const bool timed = timeline.arm("lane", s, &gm);
 #endif
     if constexpr (FUSED != 0) SVGF_LAUNCH_KERNEL((k_atrous_lane<LOG2S, HASVAR, LOG2P, LOG2Y, FUSED, REUSE>), dim3(nblocks), dim3(NT), lds, s, a, gm, *ta);
     else SVGF_LAUNCH_KERNEL((k_atrous_lane<LOG2S, HASVAR, LOG2P, LOG2Y, 0, REUSE>), dim3(nblocks), dim3(NT), lds, s, a, gm, LaneNoTemporal{});
 #ifdef SVGF_LANE_TIMELINE
-    if (dbg_env) {
-        static int skip = SVGF_TUNE("lane_dbg_skip", 0), prints = 0;
-        (void)hipStreamSynchronize(s);
-        unsigned long long h[16 * 16 * 8];
-        (void)hipMemcpy(h, dbg_buf, sizeof(h), hipMemcpyDeviceToHost);
-        if (skip > 0) skip--;
-        else if (prints++ < 4) {
-            fprintf(stderr, "[lane dbg] S=%d blocks=%d segs=%d seg_rows=%d lds=%zu\n", S, nblocks, gm.n_segs, gm.seg_rows, lds);
-            const int show[4] = { 0, NWC - 1, NWC, NWC + 3 };
-            for (int si = 0; si < 4; si++) {
-                const int w = show[si];
-                if (h[(w * 16) * 8 + 7])
-                    fprintf(stderr, "  wave %2d prologue: entry .. loads issued %6llu, .. barrier passed %6llu, .. first iteration %6llu ticks\n", w,
-                            h[(w * 16 + 2) * 8 + 7] - h[(w * 16) * 8 + 7], h[(w * 16 + 1) * 8 + 7] - h[(w * 16) * 8 + 7],
-                            h[(w * 16) * 8 + 0] - h[(w * 16) * 8 + 7]);
-                for (int it = 0; it < 8 && h[(w * 16 + it) * 8]; it++) {
-                    unsigned long long *t = &h[(w * 16 + it) * 8];
-                    if (w >= NWC && (FUSED == 1 || FUSED == 2)) fprintf(stderr, "  loader %2d it %2d: t0=%6llu first pixel: C2 (blend, commit) %5llu C1 (consistency, history request) %5llu B %5llu A %5llu | second pixel %6llu | barrier %5llu\n", w, it,
-                                                   t[0] - h[0], t[1] - t[0], t[2] - t[1], t[3] - t[2], t[4] - t[3], t[5] - t[4], t[6] - t[5]);
-                    else if (w >= NWC) fprintf(stderr, "  loader %2d it %2d: t0=%6llu work %6llu barrier %5llu\n", w, it, t[0] - h[0], t[5] - t[0], t[6] - t[5]);
-                    else fprintf(stderr, "  wave %2d it %2d: t0=%6llu centre %5llu back rows %5llu own %5llu fwd rows %5llu out %5llu barrier %5llu\n", w, it,
-                                 t[0] - h[0], t[1] - t[0], t[2] - t[1], t[3] - t[2], t[4] - t[3], t[5] - t[4], t[6] - t[5]);
-                }
-            }
-        }
+    if (timed) {
+        char title[128];
+        snprintf(title, sizeof(title), "S=%d blocks=%d segs=%d seg_rows=%d lds=%zu", 1 << LOG2S, nblocks, gm.n_segs, gm.seg_rows, lds);
+        const int waves[4] = { 0, NWC - 1, NWC, NWC + 3 };
+        // (prologue marks: slot 7 of iteration 0 = kernel entry, of iteration 1 = prologue barrier passed, of iteration 2 = loads issued)
+        static const SegmentTimeline::Span prologue[] = { { "entry .. loads issued", 7, 2 * 8 + 7 }, { ".. barrier passed", 7, 1 * 8 + 7 }, { ".. first iteration", 7, 0 }, {} },
+                                           compute[] = { { "centre", 0, 1 }, { "back rows", 1, 2 }, { "own", 2, 3 }, { "fwd rows", 3, 4 }, { "out", 4, 5 }, { "barrier", 5, 6 }, {} },
+                                           loader[] = { { "work", 0, 5 }, { "barrier", 5, 6 }, {} },
+                                           loader_tfused[] = { { "first pixel: C2 (blend, commit)", 0, 1 }, { "C1 (consistency, history request)", 1, 2 }, { "B", 2, 3 }, { "A", 3, 4 },
+                                                               { "| second pixel", 4, 5 }, { "| barrier", 5, 6 }, {} };
+        timeline.print("lane", s, title, 4, 8, waves, NWC, prologue, compute, (FUSED == 1 || FUSED == 2) ? loader_tfused : loader);
     }
 #endif
     return hipGetLastError();

@@ -19,32 +19,20 @@
 // compute loop (which run over the lattice columns of one phase) read consecutive records: conflict-free b128 reads.
 // Out-of-image encoding (luminance = +inf => weight 0), NaN handling (`careful`) and the tap arithmetic are the strip
 // kernel's.
-#include "svgf_kernels.h"
+#include "svgf_atrous_geometry.h"
 
 #include <type_traits>
 
 namespace {
 
 constexpr float kLog2e = 1.44269504088896340736f;
-constexpr int PXB = 48;                   // bytes per staged pixel
-#ifndef SVGF_LATTICE_NT
-#define SVGF_LATTICE_NT 1024
-#define SVGF_LATTICE_LDS_KB 150
-#endif
-constexpr int NT = SVGF_LATTICE_NT;       // 1024 threads / 150 KB: one workgroup per CU, 16 waves
-constexpr int kLdsBudget = SVGF_LATTICE_LDS_KB * 1024;
+constexpr int PXB = kStagedPixelBytes;
+constexpr int NT = kLatticeThreads;
 
 typedef float v2f __attribute__((ext_vector_type(2)));
 typedef float v4f __attribute__((ext_vector_type(4)));
 
-struct LatticeGeom {
-    int log2s, log2k;
-    int tw;          // staged lattice columns per phase row: ceil(W / S) + 4
-    int pstride;     // records per phase row in LDS (>= tw, padded: see geometry())
-    int band_rows;   // output lattice rows per workgroup
-    int n_bands;     // bands per sub-image
-    float kn, kx;    // log2(e) / (sigma_n + 1e-6), log2(e) / (sigma_x + 1e-6)
-};
+struct LatticeGeom : LatticeTiles {};      // (the kernels' symbol names carry this type's name)
 
 __device__ __forceinline__ float lum_f64(float r, float g, float b)
 {   // reference luminance: double products, rounded once to float (src/denoise.cu:121,138)
@@ -221,64 +209,21 @@ __global__ __launch_bounds__(NT) void k_atrous_lattice(AtrousArgs a, LatticeGeom
     }
 }
 
-// Tile geometry.  K: the largest of 8, 4, 2, 1 phases per workgroup whose tile holds whole sub-images or at least
-// 8-row bands within the LDS budget.  pstride: the row of one phase is padded so that the 16 lanes a b128 LDS access
-// serves per cycle (K phases x 16/K consecutive columns, 12 dwords apart) fall on 16 distinct 4-bank groups:
-// 12 * pstride mod 64 must be 32 (K = 2), 48 (K = 4) or 24 (K = 8).
-bool geometry(const AtrousArgs &a, LatticeGeom &gm)
-{
-    if (a.step < 64 || (a.step & (a.step - 1))) return false;
-    if ((long long)a.W * a.H * 16 >= (1LL << 32)) return false;     // 32-bit element offsets in the kernel
-    int log2s = 0;
-    while ((1 << log2s) < a.step) log2s++;
-    if (log2s > 12) return false;
-    const int S = a.step;
-    gm.log2s = log2s;
-    gm.tw = (a.W + S - 1) / S + 4;
-    const int mh_max = (a.H + S - 1) / S;
-    int chosen = -1, rows_fit = 0;
-    for (int log2k = 3; log2k >= 0 && chosen < 0; log2k--) {
-        const int K = 1 << log2k;
-        const int want = (K == 1) ? -1 : (K == 2 ? 32 : (K == 4 ? 48 : 24));
-        int P = gm.tw;
-        while (want >= 0 && (12 * P) % 64 != want) P++;
-        const int fit = kLdsBudget / (K * P * PXB) - 4;
-        if (fit >= (mh_max < 8 ? mh_max : 8) || (K == 1 && fit >= 1)) { chosen = log2k; rows_fit = fit; gm.pstride = P; }
-    }
-    if (chosen < 0) return false;                                   // a single lattice row does not fit: gather kernel
-    gm.log2k = chosen;
-    if (rows_fit > mh_max) rows_fit = mh_max;
-    gm.n_bands = (mh_max + rows_fit - 1) / rows_fit;
-    gm.band_rows = (mh_max + gm.n_bands - 1) / gm.n_bands;          // equal bands
-    if (((long long)S * S >> chosen) * gm.n_bands > (1LL << 30)) return false;
-    gm.kn = (float)(1.4426950408889634 / ((double)a.sigma_n + 1e-6));
-    gm.kx = (float)(1.4426950408889634 / ((double)a.sigma_x + 1e-6));
-    return true;
-}
-
 template <bool HASVAR>
 hipError_t launch_cfg(const AtrousArgs &a, const LatticeGeom &gm, hipStream_t s)
 {
     static SvgfLaunchCache cache;
     int dev_id = 0;
-    if (hipError_t e = cache.init(reinterpret_cast<const void *>(&k_atrous_lattice<HASVAR>), kLdsBudget, &dev_id); e != hipSuccess) return e;
-    const size_t lds = (size_t)(gm.pstride << gm.log2k) * (gm.band_rows + 4) * PXB;
-    const unsigned nblocks = (((unsigned)a.step * (unsigned)a.step) >> gm.log2k) * (unsigned)gm.n_bands;
-    SVGF_LAUNCH_KERNEL(k_atrous_lattice<HASVAR>, dim3(nblocks), dim3(NT), lds, s, a, gm);
+    if (hipError_t e = cache.init(reinterpret_cast<const void *>(&k_atrous_lattice<HASVAR>), kLatticeLdsBudget, &dev_id); e != hipSuccess) return e;
+    SVGF_LAUNCH_KERNEL(k_atrous_lattice<HASVAR>, dim3(lattice_grid_blocks(gm)), dim3(NT), lattice_lds_bytes(gm), s, a, gm);
     return hipGetLastError();
 }
 
 }  // namespace
 
-bool atrous_lattice_supported(const AtrousArgs &a)
-{
-    LatticeGeom gm;
-    return geometry(a, gm);
-}
-
 hipError_t launch_atrous_lattice(const AtrousArgs &a, hipStream_t s)
 {
     LatticeGeom gm;
-    if (!geometry(a, gm)) return hipErrorInvalidValue;
+    if (!lattice_geometry(a, gm)) return hipErrorInvalidValue;
     return a.dst ? launch_cfg<true>(a, gm, s) : launch_cfg<false>(a, gm, s);
 }

@@ -32,21 +32,14 @@
 // folded in.  Non-finite normals/positions make the reference's min(1, exp(NaN)) return 1 (fminf
 // semantics); a workgroup that stages such a texel switches to the `CAREFUL` tap routine that reproduces this, so
 // ordinary frames pay nothing for it.
-#include "svgf_kernels.h"
+#include "svgf_atrous_geometry.h"
 
 #include <cstdio>
-#include <cstdlib>
 #include <type_traits>
 
 namespace {
 
 constexpr float kLog2e = 1.44269504088896340736f;
-#ifndef SVGF_LOADER_GROUPS
-#define SVGF_LOADER_GROUPS 2
-#endif
-#ifndef SVGF_LOADER_DIV
-#define SVGF_LOADER_DIV 2
-#endif
 // Wave priorities (s_setprio).  The SIMD arbiter serves the oldest ready wave first, so of the two compute waves that
 // share a SIMD the older one used to finish its iteration ~2000 cycles early and idle at the barrier while the younger
 // ran alone, unable to hide its own latencies (profiles/r01_strip_phase_timeline_v3.log: taps 4300 vs 5650 cycles).
@@ -61,22 +54,12 @@ constexpr float kLog2e = 1.44269504088896340736f;
 #ifndef SVGF_LOADER_PRIO
 #define SVGF_LOADER_PRIO 1
 #endif
-// ROWS <= 2: SVGF_LOADER_GROUPS groups of TX / SVGF_LOADER_DIV threads take turns (issue / in flight / commit).
-// ROWS == 3: 12 compute waves leave room for 4 loader waves (1024 threads): one group of TX threads that commits and
-//            re-issues every iteration.
-__host__ __device__ constexpr int loader_groups(int rows) { return rows >= 3 ? 1 : SVGF_LOADER_GROUPS; }
-__host__ __device__ constexpr int loader_group(int tx, int rows) { return rows >= 3 ? tx : tx / SVGF_LOADER_DIV; }
-__host__ __device__ constexpr int loader_threads(int tx, int rows) { return loader_groups(rows) * loader_group(tx, rows); }
+// the workgroup's loader threads (svgf_atrous_geometry.h: the launcher and the launch geometry count them too)
+using strip_shape::loader_groups;
+using strip_shape::loader_group;
+using strip_shape::loader_threads;
 
-struct StripGeom {
-    int n_strips;   // strips of TX columns
-    int n_segs;     // lattice-row segments per phase
-    int seg_rows;   // lattice rows per segment
-    int n_groups;   // S * n_segs
-    float kn, kx;   // log2(e) / (sigma_n + 1e-6), log2(e) / (sigma_x + 1e-6)
-    unsigned long long *dbg;   // tuning only (experiments build, svgf_exp_set("strip_dbg", <block>)): per-phase s_memtime stamps of one workgroup
-    int dbg_block;
-};
+struct StripGeom : SegmentGeom {};      // (the kernels' symbol names carry this type's name)
 
 struct Px {   // one staged pixel in registers
     float4 cv;
@@ -649,157 +632,46 @@ __global__ __launch_bounds__(TX * ROWS + loader_threads(TX, ROWS)) void k_atrous
     }
 }
 
-// Segment length: every (strip, phase, segment) is one workgroup and `capacity` of them run at a time, so the grid runs in
-// rounds of equal-length workgroups.  Returns the minimum of rounds * (L + fixed cost) — in lattice rows; the fixed cost being
-// the 4 halo rows + the exposed prologue latency — and the segment length L that reaches it.
-// A phase of fewer than 3 * ROWS lattice rows leaves the search range empty: the one segment of nb_max rows is then the only
-// geometry, and it is costed like any other (the estimate is never the -1 of "nothing evaluated").
-long strip_segment_search(int n_strips, int S, int nb_max, int ROWS, int capacity, int *best_L_out)
-{
-    int best_L = nb_max;
-    long best_cost = -1;
-    static const int fixed_rows = SVGF_TUNE("strip_fixed_rows", 8);   // tuning only
-    const bool one_segment = ROWS * 4 > nb_max + ROWS;
-    const int L_lo = one_segment ? nb_max : ROWS * 4, L_hi = one_segment ? nb_max : nb_max + ROWS;
-    for (int L = L_lo; L <= L_hi; L++) {                     // L need not be a multiple of ROWS: the last iteration idles rows
-        const int segs_l = (nb_max + L - 1) / L;
-        // (phase, segment) groups are dealt round-robin to the 8 XCDs (blockIdx % 8), all strips of a group to the same
-        // XCD: the busiest XCD, with ceil(groups / 8) groups, sets the number of rounds
-        const long blocks_xcd = (long)n_strips * ((S * segs_l + 7) / 8);
-        const long cap_xcd = capacity / 8 > 0 ? capacity / 8 : 1;        // (a device with fewer than 8 CUs: one workgroup per "XCD" at a time)
-        const long rounds = (blocks_xcd + cap_xcd - 1) / cap_xcd;
-        const long cost = rounds * ((L + ROWS - 1) / ROWS * ROWS + fixed_rows);
-        if (best_cost < 0 || cost <= best_cost) { best_cost = cost; best_L = L; }   // ties: fewer, longer workgroups
-    }
-    *best_L_out = best_L;
-    return best_cost;
-}
-
-// The launch geometry of a level, from the image, the step, the workgroup shape and the device's CU count: fills the geometry
-// launch_cfg launches and returns the cost in lattice rows atrous_strip_estimate_us prices (strip_lds_bytes: also pick()'s budget).
-constexpr size_t strip_lds_bytes(int S, int tx, int rows) { return (size_t)(4 + 2 * rows) * (tx + 4 * S) * 48 + (size_t)2 * rows * 2 * (tx + 2) * 4 + 16; }   // ring + blur rows
-long strip_geometry(int W, int H, int S, int tx, int rows, int n_cu, StripGeom *gm)
-{
-    gm->n_strips = (W + tx - 1) / tx;
-    const int nb_max = (H + S - 1) / S;
-    // Segment length: every (strip, phase, segment) is one workgroup, and LDS admits `bpc` workgroups per CU, so the
-    // grid runs in ceil(blocks / (CUs * bpc)) rounds of equal-length workgroups.  Pick the segment length L that
-    // minimises rounds * (L + fixed cost), the fixed cost being the 4 halo rows + the exposed prologue latency.
-    int bpc = (int)((160 * 1024) / strip_lds_bytes(S, tx, rows));
-    const int threads = tx * rows + loader_threads(tx, rows);
-    if (bpc > 2048 / threads) bpc = 2048 / threads;
-    if (bpc < 1) bpc = 1;
-    const long cost = strip_segment_search(gm->n_strips, S, nb_max, rows, n_cu * bpc, &gm->seg_rows);
-    if (const int v = SVGF_TUNE("strip_segrows", 0); v > 0) gm->seg_rows = v;      // (tuning: the cost stays that of the searched length)
-    gm->n_segs = (nb_max + gm->seg_rows - 1) / gm->seg_rows;
-    gm->n_groups = S * gm->n_segs;
-    return cost;
-}
-
 template <int LOG2S, int TX, int ROWS, bool HASVAR>
 hipError_t launch_cfg(const AtrousArgs &a, hipStream_t s)
 {
-    constexpr int S = 1 << LOG2S, kLoaderThreads = loader_threads(TX, ROWS);
-    constexpr size_t lds = strip_lds_bytes(S, TX, ROWS);
+    constexpr size_t lds = strip_shape::lds_bytes(1 << LOG2S, TX, ROWS);
     static SvgfLaunchCache cache;
     int dev_id = 0;
     if (hipError_t e = cache.init(reinterpret_cast<const void *>(&k_atrous_strip<LOG2S, TX, ROWS, HASVAR>), (int)lds, &dev_id); e != hipSuccess) return e;
     StripGeom gm;
-    (void)strip_geometry(a.W, a.H, S, TX, ROWS, cache.n_cu[dev_id], &gm);
-    gm.dbg = nullptr; gm.dbg_block = 0;
-    static unsigned long long *dbg_buf = nullptr;
-    const int dbg_block = SVGF_TUNE("strip_dbg", -1);
-    const bool dbg_env = dbg_block >= 0;
-    if (dbg_env) {
-        if (!dbg_buf) (void)hipMalloc((void **)&dbg_buf, 16 * 16 * 8 * sizeof(unsigned long long));
-        (void)hipMemsetAsync(dbg_buf, 0, 16 * 16 * 8 * sizeof(unsigned long long), s);
-        gm.dbg = dbg_buf; gm.dbg_block = dbg_block;
+    (void)strip_geometry(a, TX, ROWS, cache.n_cu[dev_id], &gm);
+#ifdef SVGF_STRIP_TIMELINE
+    static SegmentTimeline timeline;
+    const bool timed = timeline.arm("strip", s, &gm);
+#endif
+    SVGF_LAUNCH_KERNEL((k_atrous_strip<LOG2S, TX, ROWS, HASVAR>), dim3(segment_grid_blocks(gm)), dim3(strip_shape::block_threads(TX, ROWS)), lds, s, a, gm);
+#ifdef SVGF_STRIP_TIMELINE
+    if (timed) {
+        constexpr int nw = strip_shape::block_threads(TX, ROWS) / 64, nlw = loader_threads(TX, ROWS) / 64;
+        char title[160];
+        snprintf(title, sizeof(title), "S=%d TX=%d ROWS=%d blocks=%d segs=%d seg_rows=%d lds=%zu waves=%d (last %d = loaders)", 1 << LOG2S, TX, ROWS,
+                 segment_grid_blocks(gm), gm.n_segs, gm.seg_rows, lds, nw, nlw);
+        const int waves[4] = { 0, nw - nlw - 1, nw - nlw, nw - 1 };
+        static const SegmentTimeline::Span prologue[] = { { "entry..loads issued", 7, 1 }, { "..stored", 7, 4 }, { "..first iteration", 7, 0 }, {} },
+                                           compute[] = { { "centre", 0, 2 }, { "taps", 2, 3 }, { "out", 3, 5 }, { "barrier", 5, 6 }, {} },
+                                           loader[] = { { "stage", 0, 5 }, { "barrier", 5, 6 }, {} };
+        timeline.print("strip", s, title, 10, 16, waves, nw - nlw, prologue, compute, loader);
     }
-    gm.kn = (float)(1.4426950408889634 / ((double)a.sigma_n + 1e-6));
-    gm.kx = (float)(1.4426950408889634 / ((double)a.sigma_x + 1e-6));
-    const int groups_pad = (gm.n_groups + 7) / 8 * 8;
-    const int nblocks = groups_pad * gm.n_strips;
-    SVGF_LAUNCH_KERNEL((k_atrous_strip<LOG2S, TX, ROWS, HASVAR>), dim3(nblocks), dim3(TX * ROWS + kLoaderThreads), lds, s, a, gm);
-    if (dbg_env) {
-        static int prints = 0;
-        (void)hipStreamSynchronize(s);
-        unsigned long long h[16 * 16 * 8];
-        (void)hipMemcpy(h, dbg_buf, sizeof(h), hipMemcpyDeviceToHost);
-        static int skip = SVGF_TUNE("strip_dbg_skip", 0);    // warm launches only
-        if (skip > 0) skip--;
-        else if (prints++ < 10) {
-            const int nw = (TX * ROWS + kLoaderThreads) / 64;
-            fprintf(stderr, "[strip dbg] S=%d TX=%d ROWS=%d blocks=%d segs=%d seg_rows=%d lds=%zu waves=%d (last 6 = loaders)\n", S, TX,
-                    ROWS, nblocks, gm.n_segs, gm.seg_rows, lds, nw);
-            const int nlw = kLoaderThreads / 64;
-            const int show[4] = { 0, nw - nlw - 1, nw - nlw, nw - 1 };
-            for (int si = 0; si < 4; si++) {
-                const int w = show[si];
-                if (h[(w * 16) * 8 + 7])
-                    fprintf(stderr, "  wave %2d prologue: entry..loads issued %5llu, ..stored %6llu, ..first iteration %6llu\n", w,
-                            h[(w * 16) * 8 + 1] - h[(w * 16) * 8 + 7], h[(w * 16) * 8 + 4] - h[(w * 16) * 8 + 7],
-                            h[(w * 16) * 8 + 0] - h[(w * 16) * 8 + 7]);
-                for (int it = 0; it < 16 && h[(w * 16 + it) * 8]; it++) {
-                    unsigned long long *t = &h[(w * 16 + it) * 8];
-                    if (w >= nw - nlw)
-                        fprintf(stderr, "  loader  it %2d: t0=%6llu stage %6llu barrier %5llu\n", it, t[0] - h[0], t[5] - t[0], t[6] - t[5]);
-                    else
-                        fprintf(stderr, "  wave %2d it %2d: t0=%6llu centre %5llu taps %6llu out %5llu barrier %5llu\n", w, it, t[0] - h[0],
-                                t[2] - t[0], t[3] - t[2], t[5] - t[3], t[6] - t[5]);
-                }
-            }
-        }
-    }
+#endif
     return hipGetLastError();
 }
 
-// default configuration per dilation; svgf_exp_set("strip_tx" / "strip_rows") override it in the experiments build
-void pick(int log2s, int W, int &tx, int &rows)
-{
-    // 256 columns x 2 rows per workgroup everywhere (profiles/r01_exp_tx_rows.log):
-    //  * 128-column strips (two workgroups per CU) run a lone S <= 8 level 3-4 % faster at 1080p (equal at 3840), but
-    //    the whole frame gets slower (6.46 vs 6.94 Gpix/s) once the next frame's temporal pass shares the GPU with
-    //    levels 2-3; at S >= 16 the 4S halo columns make narrow strips lose outright;
-    //  * ROWS = 3 (12 compute waves) is correct but not faster: two compute waves already saturate a SIMD's VALU.
-    (void)W;
-    tx = 256; rows = 2;
-    if (const int v = SVGF_TUNE("strip_tx", 0); v == 128 || v == 256) tx = v;
-    if (const int v = SVGF_TUNE("strip_rows", 0); v >= 1 && v <= 3) rows = v;
-    if (rows == 3 && tx != 256) rows = 2;
-    // LDS budget: ring + blur rows <= 160 KiB
-    while (strip_lds_bytes(1 << log2s, tx, rows) > 160 * 1024 && rows > 1) rows--;
-}
-
 }  // namespace
-
-bool atrous_strip_supported(const AtrousArgs &a)
-{
-    if (a.step < 1 || a.step > 32 || (a.step & (a.step - 1))) return false;      // step 1: SvgfParams::paper_steps
-    if ((long long)a.W * a.H * 16 >= (1LL << 32)) return false;   // 32-bit element offsets in the kernel
-    return true;
-}
-
-// Estimated duration of a level on this kernel: the launch geometry's cost in lattice rows x 1.16 us (1920x1080: one round of
-// 34 + 8 rows = 48.8 us; profiles/r03_exp_widths*.log: within 5 % at eight other sizes).  Used by the automatic kernel choice.
-double atrous_strip_estimate_us(const AtrousArgs &a, int n_cu)
-{
-    int log2s = 0;
-    while ((1 << log2s) < a.step) log2s++;
-    int tx, rows;
-    pick(log2s, a.W, tx, rows);
-    StripGeom gm;
-    return 1.162 * (double)strip_geometry(a.W, a.H, 1 << log2s, tx, rows, n_cu, &gm);
-}
 
 #define STRIP_CASE(L, T, Rr) if (log2s == L && tx == T && rows == Rr) return a.dst ? launch_cfg<L, T, Rr, true>(a, s) : launch_cfg<L, T, Rr, false>(a, s);
 
 hipError_t launch_atrous_strip(const AtrousArgs &a, hipStream_t s)
 {
-    int log2s = 0;
-    while ((1 << log2s) < a.step) log2s++;
+    const int log2s = atrous_step_log2(a.step);
     int tx, rows;
-    pick(log2s, a.W, tx, rows);
-    // product build: 256 columns x 2 rows per workgroup at every step (what pick() returns without tuning; 155.7 KB of LDS at step 32)
+    strip_pick(log2s, tx, rows);
+    // product build: 256 columns x 2 rows per workgroup at every step (what strip_pick() returns without tuning; 155.7 KB of LDS at step 32)
     STRIP_CASE(0, 256, 2) STRIP_CASE(1, 256, 2) STRIP_CASE(2, 256, 2) STRIP_CASE(3, 256, 2) STRIP_CASE(4, 256, 2) STRIP_CASE(5, 256, 2)
 #ifdef SVGF_BUILD_EXPERIMENTS
     STRIP_CASE(1, 256, 3) STRIP_CASE(2, 256, 3) STRIP_CASE(3, 256, 3)

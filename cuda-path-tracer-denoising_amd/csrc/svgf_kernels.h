@@ -1,5 +1,6 @@
 // svgf_kernels.h — launch wrappers shared between the host orchestration (svgf_api.hip) and the
-// kernel translation units.  Internal; the public boundary is include/svgf.h.
+// kernel translation units (which kernel can run a level, and with which launch geometry: svgf_atrous_geometry.h).
+// Internal; the public boundary is include/svgf.h.
 //
 // Device data layout (all planes W*H elements, index p = x + y*W, resident in HBM for the context's life):
 //   CV[k]   float4 {r, g, b, variance}   colour+variance planes; ping-pong / colour history (16 B/px each)
@@ -139,11 +140,7 @@ hipError_t launch_prepare(const float *in_rgb, const float *gbuf, float4 *cv, fl
                           int W, int H, hipStream_t s);
 hipError_t launch_atrous_gather(const AtrousArgs &a, hipStream_t s);   // strict one-thread-per-pixel gather kernel
 hipError_t launch_atrous_strip(const AtrousArgs &a, hipStream_t s);    // LDS strip-marching kernel (fast path)
-bool       atrous_strip_supported(const AtrousArgs &a);
-double     atrous_strip_estimate_us(const AtrousArgs &a, int n_cu);   // launch-geometry cost model (automatic kernel choice)
 hipError_t launch_atrous_lane(const AtrousArgs &a, hipStream_t s);     // lane-marching kernel, symmetric terms shared by DPP (steps 1 .. 32)
-bool       atrous_lane_supported(const AtrousArgs &a);
-double     atrous_lane_estimate_us(const AtrousArgs &a, int n_cu);
 // non-temporal mode: the prepare pass (variance fill + G-buffer split) fused into the first level (step 2, AoS boundary;
 // svgf_atrous_prepare_fused.hip)
 hipError_t launch_atrous_prepare_fused(const AtrousArgs &a, const TemporalArgs &t, hipStream_t s);
@@ -155,14 +152,15 @@ hipError_t launch_atrous_lane_reuse(const AtrousArgs &a, hipStream_t s);   // la
 // (svgf_atrous_fused.hip).  t.cv_acc may be null: the accumulated colour then exists only in LDS.
 hipError_t launch_atrous_fused(const AtrousArgs &a, const TemporalArgs &t, hipStream_t s);
 bool       atrous_fused_supported(const AtrousArgs &a, const TemporalArgs &t);
-double     atrous_fused_estimate_us(const AtrousArgs &a, int n_cu);
 // temporal frames: the G-buffer split alone in the first level's loaders (the temporal pass then runs with skip_split)
 hipError_t launch_atrous_split_fused(const AtrousArgs &a, const TemporalArgs &t, hipStream_t s);
 bool       atrous_split_fused_supported(const AtrousArgs &a, const TemporalArgs &t);
 hipError_t launch_atrous_lane_2y(const AtrousArgs &a, hipStream_t s);  // step 2, both y-phases per workgroup, not fused (A/B)
+// svgf_exp_atrous_geometry: threads and LDS bytes of a lane-kernel workgroup, from the kernel's own layout (svgf_atrous_lane_impl.h)
+void atrous_lane_block(const AtrousArgs &a, int *threads, int *lds_bytes);          // the plain level of a.step
+void atrous_lane2y_block(bool fused, int *threads, int *lds_bytes);                 // two y-phases per workgroup (step 2)
 #endif
 hipError_t launch_atrous_lattice(const AtrousArgs &a, hipStream_t s);  // lattice sub-images in LDS (steps >= 64)
-bool       atrous_lattice_supported(const AtrousArgs &a);
 // albedo * ialbedo of the last level's re-modulation (:166-168), from the AoS texel or from the planar path's plane
 __device__ __forceinline__ void svgf_modulate(const AtrousArgs &a, unsigned p, float &o0, float &o1, float &o2)
 {

@@ -117,7 +117,7 @@ def build_cases(pkg):
     cases.append(dict(name="atrous_synth128x72_n5", W=128, H=72, frames=fr169, cams=cams169, race_free=True,
                       calls=[(1, 0, default_params(spatial_enable=1, atrous_nlevel=5))], note="16:9"))
     # 470x11: the library's auto selection takes the lane-marching kernel (480-column strips fit); 1280x9: it takes the
-    # strip kernel for every step (svgf_api.hip lane_pays)
+    # strip kernel for every step (svgf_atrous_geometry.hip: the estimates lane_pays compares)
     for (W, H, seed) in ((37, 23, 5), (5, 3, 6), (1, 1, 7), (64, 9, 8), (470, 11, 15), (1280, 9, 16)):
         c, g = S.random_frame(W, H, seed=seed)
         cam0 = S.camera_for_frame(0, False)

@@ -102,6 +102,7 @@ def test_product_build_has_no_experiments_and_reads_no_environment(pkg):
     exported = {ln.split()[-1] for ln in syms.splitlines() if ln.strip()}
     assert "svgf_exp_set" not in exported and "svgf_exp_clear" not in exported
     assert "svgf_exp_level_kernels" not in exported      # the per-level kernel record is the experiments build's
+    assert "svgf_exp_atrous_geometry" not in exported    # and so is the launch geometry as numbers (tests/test_kernel_geometry.py)
     assert "getenv" not in subprocess.run(["nm", "-D", "--undefined-only", lib], stdout=subprocess.PIPE, text=True, check=True).stdout
     assert os.path.getsize(lib) < 1.5 * 1024 * 1024, os.path.getsize(lib)
     assert pkg.load_library().svgf_build_has_experiments() == 0
@@ -119,3 +120,4 @@ def test_product_build_has_no_experiments_and_reads_no_environment(pkg):
     if os.path.exists(exp):      # the experiments build of the same sources carries what the product build leaves out
         e = pkg.load_library(experiments=True)
         assert e.svgf_build_has_experiments() == 1 and hasattr(e, "svgf_exp_set") and hasattr(e, "svgf_exp_level_kernels")
+        assert hasattr(e, "svgf_exp_atrous_geometry")
