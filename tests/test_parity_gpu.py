@@ -154,9 +154,19 @@ def test_1080p_full_svgf_matches_oracle(pkg, orc):
 @pytest.mark.parametrize("size", [(1920, 1080), (3840, 640), (333, 517), (64, 64), (40, 200), (131, 3)])
 def test_levels_6_and_7_use_lattice_kernel_and_match_oracle(pkg, orc, size):
     """Steps 64 and 128 (levels 6-7 of the reference's 0..7 slider, src/preview.cpp:327) run on the lattice sub-image
-    kernel (svgf_atrous_lattice.hip): whole sub-images (1080p), row bands (3840 wide: 9-row bands), sub-images of one
-    pixel, images narrower than the step.  Checked against the CPU oracle and against the strict gather kernel."""
+    kernel (svgf_atrous_lattice.hip): whole sub-images everywhere (one band: 1080p with 4 phases per workgroup; 3840 x 640 with 2
+    phases and 10 lattice rows at step 64, 8 phases and 5 rows at step 128; 8 phases at the small sizes), sub-images of one pixel,
+    images narrower than the step.  Row bands, 1 phase per workgroup and frames that levels 6-7 change by more than rounding:
+    tests/test_lattice_gpu.py.  Checked against the CPU oracle and against the strict gather kernel; with the experiments build,
+    that the lattice kernel is what ran."""
     W, H = size
+    if os.path.exists(pkg.binding.LIB_EXP_PATH):
+        de = pkg.Denoiser(W, H, 0, experiments=True)
+        c, g, cam = pkg.synth.render_frame(W, H, 0, seed=41, moving=True)
+        de.denoise_host(c, g, cam, pkg.reference_defaults().set(spatial_enable=1, atrous_nlevel=7, kernel_variant=0))
+        rec = de.level_kernels()
+        de.free()
+        assert [(kind, step) for kind, step, _, _ in rec[5:]] == [("lattice", 64), ("lattice", 128)], f"{W}x{H}: {rec}"
     d = pkg.Denoiser(W, H, 0)
     o = orc.Oracle(pkg, W, H, threads=16)
     for f, kw in enumerate([dict(temporal_enable=1, history_level=7, blur_variance=1),
