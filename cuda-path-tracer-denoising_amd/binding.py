@@ -34,8 +34,11 @@ EXPORTS = ["svgf_version", "svgf_params_default", "svgf_create", "svgf_destroy",
            "svgf_synth_camera", "svgf_synth_render", "svgf_scene_render", "svgf_scene_render_mesh", "svgf_display_pack", "svgf_save_png",
            "svgf_planar_gbuffer", "svgf_denoise_planar", "svgf_synth_render_planar", "svgf_params_sizeof", "svgf_scene_render_mesh_planar",
            "svgf_sync_stream", "svgf_build_has_experiments", "svgf_is_pipelined", "svgf_create_ex", "svgf_enable_pipeline",
-           "svgf_pipeline_status", "svgf_planar_gbuffer_stream", "svgf_streams_overlap"]
+           "svgf_pipeline_status", "svgf_planar_gbuffer_stream", "svgf_streams_overlap",
+           "svgf_denoise_motion", "svgf_denoise_planar_motion", "svgf_motion_reproject"]
 CREATE_PIPELINED = 1
+# motion plane formats (svgf_denoise_motion): absolute previous coordinate, delta in float32, delta in float16
+MOTION_PREV_COORD_F32, MOTION_DELTA_F32, MOTION_DELTA_F16 = 1, 2, 3
 
 
 class SvgfCamera(C.Structure):
@@ -166,6 +169,9 @@ def load_library(path: str | None = None, experiments: bool = False):
     lib.svgf_destroy.argtypes = [vp]
     lib.svgf_reset.argtypes = [vp]
     lib.svgf_denoise.argtypes = [vp, vp, vp, vp, C.POINTER(SvgfCamera), C.POINTER(SvgfParams), vp]
+    lib.svgf_denoise_motion.argtypes = [vp, vp, vp, vp, vp, ip, C.POINTER(SvgfCamera), C.POINTER(SvgfParams), vp]
+    lib.svgf_denoise_planar_motion.argtypes = [vp, vp, vp, vp, ip, C.POINTER(SvgfCamera), C.POINTER(SvgfParams), vp]
+    lib.svgf_motion_reproject.argtypes = [ip, vp, ip, vp, vp, vp, ip, ip, C.POINTER(SvgfCamera), C.POINTER(C.c_float), vp, ip, vp]
     lib.svgf_denoise_host.argtypes = [vp, vp, vp, vp, C.POINTER(SvgfCamera), C.POINTER(SvgfParams)]
     lib.svgf_sync.argtypes = [vp]
     lib.svgf_sync_stream.argtypes = [vp, vp]
@@ -226,6 +232,7 @@ class Denoiser:
         experiments=True: the context lives in libsvgf_hip_exp.so (kernel_variant 5 / 6, exp_set knobs) — tests and tools only."""
         self.lib = load_library(experiments=experiments)
         self.width, self.height = int(width), int(height)
+        self.device = int(device)
         self.ui = SvgfParams()
         self.lib.svgf_params_default(C.byref(self.ui))
         h = C.c_void_p()
@@ -255,13 +262,20 @@ class Denoiser:
         except Exception:
             pass
 
-    def denoise(self, out, inp, gbuffer, camera, params: SvgfParams | None = None, stream=None):
-        """Device pointers (ints) or contiguous CUDA torch tensors.  Asynchronous on `stream`."""
+    def denoise(self, out, inp, gbuffer, camera, params: SvgfParams | None = None, stream=None, motion=None,
+                motion_format: int = MOTION_PREV_COORD_F32):
+        """Device pointers (ints) or contiguous CUDA torch tensors.  Asynchronous on `stream`.
+        motion: a device plane of per-pixel previous-frame coordinates in `motion_format` (svgf_denoise_motion); None: the
+        history is found through the previous camera (svgf_denoise)."""
         cam = camera if isinstance(camera, SvgfCamera) else SvgfCamera.from_dict(camera)
         p = params if params is not None else self.ui
         s = None if stream is None else (stream if isinstance(stream, int) else stream.cuda_stream)
-        self._check(self.lib.svgf_denoise(self.h, _ptr(out), _ptr(inp), _ptr(gbuffer), C.byref(cam), C.byref(p), s),
-                    "svgf_denoise")
+        if motion is None:
+            self._check(self.lib.svgf_denoise(self.h, _ptr(out), _ptr(inp), _ptr(gbuffer), C.byref(cam), C.byref(p), s),
+                        "svgf_denoise")
+        else:
+            self._check(self.lib.svgf_denoise_motion(self.h, _ptr(out), _ptr(inp), _ptr(gbuffer), _ptr(motion), int(motion_format),
+                                                     C.byref(cam), C.byref(p), s), "svgf_denoise_motion")
 
     def planar_gbuffer(self, stream=None) -> SvgfPlanarGBuffer:
         """The planes the NEXT denoise_planar() call consumes: a producer fills them in place.
@@ -275,24 +289,44 @@ class Denoiser:
             self._check(self.lib.svgf_planar_gbuffer_stream(self.h, C.byref(g), s), "svgf_planar_gbuffer_stream")
         return g
 
-    def denoise_planar(self, out, inp, camera, params: SvgfParams | None = None, stream=None):
-        """One frame whose G-buffer was written into planar_gbuffer()'s planes.  Asynchronous on `stream`."""
+    def denoise_planar(self, out, inp, camera, params: SvgfParams | None = None, stream=None, motion=None,
+                       motion_format: int = MOTION_PREV_COORD_F32):
+        """One frame whose G-buffer was written into planar_gbuffer()'s planes.  Asynchronous on `stream`.  motion: as in denoise()."""
         cam = camera if isinstance(camera, SvgfCamera) else SvgfCamera.from_dict(camera)
         p = params if params is not None else self.ui
         s = None if stream is None else (stream if isinstance(stream, int) else stream.cuda_stream)
-        self._check(self.lib.svgf_denoise_planar(self.h, _ptr(out), _ptr(inp), C.byref(cam), C.byref(p), s), "svgf_denoise_planar")
+        if motion is None:
+            self._check(self.lib.svgf_denoise_planar(self.h, _ptr(out), _ptr(inp), C.byref(cam), C.byref(p), s), "svgf_denoise_planar")
+        else:
+            self._check(self.lib.svgf_denoise_planar_motion(self.h, _ptr(out), _ptr(inp), _ptr(motion), int(motion_format),
+                                                            C.byref(cam), C.byref(p), s), "svgf_denoise_planar_motion")
 
-    def denoise_host(self, color: np.ndarray, gbuffer: np.ndarray, camera, params: SvgfParams | None = None) -> np.ndarray:
-        """numpy in, numpy out (uploads, runs, downloads, synchronises)."""
+    def denoise_host(self, color: np.ndarray, gbuffer: np.ndarray, camera, params: SvgfParams | None = None, motion=None,
+                     motion_format: int = MOTION_PREV_COORD_F32) -> np.ndarray:
+        """numpy in, numpy out (uploads, runs, downloads, synchronises).  motion: a HOST array of H*W previous-frame coordinates
+        in `motion_format` (float32[H, W, 2], or float16[H, W, 2] for MOTION_DELTA_F16); it is uploaded with torch."""
         color = np.ascontiguousarray(color, dtype=np.float32)
         gbuffer = np.ascontiguousarray(gbuffer)
         assert color.size == 3 * self.width * self.height and gbuffer.nbytes == 52 * self.width * self.height
         out = np.empty_like(color)
         cam = camera if isinstance(camera, SvgfCamera) else SvgfCamera.from_dict(camera)
         p = params if params is not None else self.ui
-        self._check(self.lib.svgf_denoise_host(self.h, out.ctypes.data, color.ctypes.data, gbuffer.ctypes.data,
-                                               C.byref(cam), C.byref(p)), "svgf_denoise_host")
-        return out
+        if motion is None:
+            self._check(self.lib.svgf_denoise_host(self.h, out.ctypes.data, color.ctypes.data, gbuffer.ctypes.data,
+                                                   C.byref(cam), C.byref(p)), "svgf_denoise_host")
+            return out
+        import torch
+        motion = np.ascontiguousarray(motion, dtype=np.float16 if motion_format == MOTION_DELTA_F16 else np.float32)
+        assert motion.size == 2 * self.width * self.height
+        dev = torch.device("cuda", self.device)
+        t_in = torch.from_numpy(color).to(dev)
+        t_g = torch.from_numpy(gbuffer.view(np.uint8).reshape(-1)).to(dev)
+        t_m = torch.from_numpy(motion).to(dev)
+        t_out = torch.empty(color.shape, dtype=torch.float32, device=dev)
+        torch.cuda.synchronize(dev)
+        self.denoise(t_out, t_in, t_g, cam, p, motion=t_m, motion_format=motion_format)
+        self.sync()
+        return t_out.cpu().numpy()
 
     def sync(self):
         self._check(self.lib.svgf_sync(self.h), "svgf_sync")
@@ -423,6 +457,26 @@ def synth_render_planar(out_rgb, planes: SvgfPlanarGBuffer, width: int, height: 
     rc = lib.svgf_synth_render_planar(int(device), _ptr(out_rgb), C.byref(planes), int(width), int(height), C.byref(cam), C.byref(sp), s)
     if rc != SVGF_OK:
         raise SvgfError(f"svgf_synth_render_planar failed ({rc})")
+
+
+# --- per-pixel motion vectors: the plane svgf_denoise_motion reads, for rigid motion --------------------------------------
+def motion_reproject(motion_out, width: int, height: int, prev_camera, gbuffer=None, position=None, geom_id=None,
+                     motion_format: int = MOTION_PREV_COORD_F32, reproj_scale=(0.0, 0.0), geom_xf=None, n_geoms: int | None = None,
+                     device: int = 0, stream=None):
+    """svgf_motion_reproject: per pixel the previous-frame coordinate of the texel's position (AoS `gbuffer`, or the `position` /
+    `geom_id` planes — tensors, raw pointers or a SvgfPlanarGBuffer's fields), mapped by geom_xf[geomId] (device float32[n, 12], 3x4
+    row-major, this frame's world -> the previous frame's) and projected through `prev_camera` exactly as the temporal pass does.
+    `motion_out`: device memory of width * height * 2 float32 (float16 for MOTION_DELTA_F16)."""
+    lib = load_library()
+    cam = prev_camera if isinstance(prev_camera, SvgfCamera) else SvgfCamera.from_dict(prev_camera)
+    rs = (C.c_float * 2)(float(reproj_scale[0]), float(reproj_scale[1]))
+    if geom_xf is not None and n_geoms is None:
+        n_geoms = int(geom_xf.numel()) // 12
+    s = None if stream is None else (stream if isinstance(stream, int) else stream.cuda_stream)
+    rc = lib.svgf_motion_reproject(int(device), _ptr(motion_out), int(motion_format), _ptr(gbuffer), _ptr(position), _ptr(geom_id),
+                                   int(width), int(height), C.byref(cam), rs, _ptr(geom_xf), int(n_geoms or 0), s)
+    if rc != SVGF_OK:
+        raise SvgfError(f"svgf_motion_reproject failed ({rc})")
 
 
 # --- SURVEY.md 8(f) row f2: the step after denoise() ----------------------------------------------------------------

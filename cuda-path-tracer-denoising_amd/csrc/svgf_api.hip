@@ -17,6 +17,8 @@
 #include "svgf_atrous_geometry.h"
 
 #define SVGF_MAX_KERNELS_PER_FRAME (SVGF_MAX_LEVELS + 4)
+static_assert(SVGF_MOTION_PREV_COORD_F32 == SVGF_MOTION_FMT_COORD && SVGF_MOTION_DELTA_F32 == SVGF_MOTION_FMT_D32 &&
+              SVGF_MOTION_DELTA_F16 == SVGF_MOTION_FMT_D16, "include/svgf.h and svgf_kernels.h name the same motion formats");
 // the prepare pass of the non-temporal mode fused into the first level (svgf_atrous_prepare_fused.hip, FUSED = 3): on by default
 // where the first level runs the lane kernel anyway (measured: profiles/r04_exp_prepare_fused.log)
 static const bool kPrepareFusedByDefault = true;
@@ -812,8 +814,10 @@ static KernelKind level_kernel(svgf_ctx *c, const SvgfParams *p, const AtrousArg
 // Every level is decided and validated here, before anything is enqueued or any context state changes: a failure half-way
 // through the cascade would leave the colour history of this frame next to the G-buffer / moments of the previous one.  The
 // context is only read (the memoised estimates of lane_pays / fuse_pays aside).
+// motion_dev != nullptr: the temporal pass reads the previous-frame coordinates from the caller's plane (svgf_denoise_motion); an
+// input like the colour image, read by that pass only.
 static int plan_frame(svgf_ctx *c, void *out_rgb_dev, const void *in_rgb_dev, const void *gbuffer_dev,
-                      const SvgfParams *p, void *stream, FramePlan &pl)
+                      const void *motion_dev, int motion_format, const SvgfParams *p, void *stream, FramePlan &pl)
 {
     if (p->atrous_nlevel < 0 || p->atrous_nlevel > SVGF_MAX_LEVELS) {
         snprintf(c->err, sizeof(c->err), "svgf_denoise: atrous_nlevel %d outside 0..%d", p->atrous_nlevel, SVGF_MAX_LEVELS);
@@ -829,6 +833,17 @@ static int plan_frame(svgf_ctx *c, void *out_rgb_dev, const void *in_rgb_dev, co
     if (p->kernel_variant == 5 || p->kernel_variant == 6) {
         snprintf(c->err, sizeof(c->err), "svgf_denoise: kernel_variant %d is a parked experiment (two-y-phase geometry / temporal pass fused into "
                  "the first level) and is not part of this build; build libsvgf_hip_exp.so (-DSVGF_BUILD_EXPERIMENTS)", p->kernel_variant);
+        return SVGF_ERR_UNSUPPORTED;
+    }
+#endif
+    if (motion_dev && !temporal_motion_format_known(motion_format)) {
+        snprintf(c->err, sizeof(c->err), "svgf_denoise_motion: motion_format %d unknown", motion_format);
+        return SVGF_ERR_INVALID_ARG;
+    }
+    const bool motion = motion_dev && p->temporal_enable;      // (a non-temporal frame has no history to look up: the plane is ignored)
+#ifdef SVGF_BUILD_EXPERIMENTS
+    if (motion && (p->kernel_variant == 6 || c->use_split_fused)) {
+        snprintf(c->err, sizeof(c->err), "svgf_denoise_motion: the parked fused temporal kernels (kernel_variant 6, split_fused) take no motion plane");
         return SVGF_ERR_UNSUPPORTED;
     }
 #endif
@@ -915,8 +930,9 @@ static int plan_frame(svgf_ctx *c, void *out_rgb_dev, const void *in_rgb_dev, co
         t.reproj_sx = p->reproj_scale[0]; t.reproj_sy = p->reproj_scale[1];
         t.pos_prev = c->pos[c->gcur]; t.pos_tol = p->reproj_position_tol;
         t.dump = c->dump; t.arena = c->arena; t.arena_bytes = c->arena_bytes;
+        if (motion) { t.motion = motion_dev; t.motion_format = motion_format; }
 #ifdef SVGF_BUILD_EXPERIMENTS      // parked: the temporal pass in the first level's loaders, DESIGN.md 5.8
-        if (cascade && (p->kernel_variant == 0 || p->kernel_variant == 6) && !p->paper_steps && p->spatial_variance_frames <= 0)
+        if (!motion && cascade && (p->kernel_variant == 0 || p->kernel_variant == 6) && !p->paper_steps && p->spatial_variance_frames <= 0)
             pl.fused = atrous_fused_supported(probe, t) && (p->kernel_variant == 6 || fuse_pays(c, probe));
 #endif
     } else if (g && cascade && (p->kernel_variant == 0 || p->kernel_variant == 6) && !p->paper_steps) {
@@ -1104,7 +1120,7 @@ static void commit_frame(svgf_ctx *c, const FramePlan &pl, const SvgfCamera *cam
 }
 
 static int denoise_frame(svgf_ctx *c, void *out_rgb_dev, const void *in_rgb_dev, const void *gbuffer_dev,
-                         const SvgfCamera *cam, const SvgfParams *p, void *stream)
+                         const void *motion_dev, int motion_format, const SvgfCamera *cam, const SvgfParams *p, void *stream)
 {
     if (!out_rgb_dev || !in_rgb_dev || !cam || !p) {
         snprintf(c->err, sizeof(c->err), "svgf_denoise: null argument");
@@ -1112,21 +1128,51 @@ static int denoise_frame(svgf_ctx *c, void *out_rgb_dev, const void *in_rgb_dev,
     }
     SVGF_ENTER(c);
     FramePlan pl;
-    int rc = plan_frame(c, out_rgb_dev, in_rgb_dev, gbuffer_dev, p, stream, pl);
+    int rc = plan_frame(c, out_rgb_dev, in_rgb_dev, gbuffer_dev, motion_dev, motion_format, p, stream, pl);
     if (rc == SVGF_OK) rc = enqueue_frame(c, pl);
     if (rc == SVGF_OK) commit_frame(c, pl, cam);
     return rc;
 }
 
-extern "C" int svgf_denoise(svgf_ctx *c, void *out_rgb_dev, const void *in_rgb_dev, const void *gbuffer_dev,
-                            const SvgfCamera *cam, const SvgfParams *p, void *stream)
+extern "C" int svgf_denoise_motion(svgf_ctx *c, void *out_rgb_dev, const void *in_rgb_dev, const void *gbuffer_dev,
+                                   const void *motion_dev, int motion_format, const SvgfCamera *cam, const SvgfParams *p, void *stream)
 {
     if (!c) return SVGF_ERR_INVALID_ARG;
     if (!gbuffer_dev) {
         snprintf(c->err, sizeof(c->err), "svgf_denoise: null argument");
         return SVGF_ERR_INVALID_ARG;
     }
-    return denoise_frame(c, out_rgb_dev, in_rgb_dev, gbuffer_dev, cam, p, stream);
+    return denoise_frame(c, out_rgb_dev, in_rgb_dev, gbuffer_dev, motion_dev, motion_format, cam, p, stream);
+}
+
+extern "C" int svgf_denoise(svgf_ctx *c, void *out_rgb_dev, const void *in_rgb_dev, const void *gbuffer_dev,
+                            const SvgfCamera *cam, const SvgfParams *p, void *stream)
+{
+    return svgf_denoise_motion(c, out_rgb_dev, in_rgb_dev, gbuffer_dev, nullptr, 0, cam, p, stream);
+}
+
+// The motion plane of a frame whose geometry moved rigidly, written with the camera path's own projection (k_motion_reproject,
+// svgf_kernels.hip) and the view matrix svgf_denoise would have retained for `prev_cam`.  Stateless.
+extern "C" int svgf_motion_reproject(int device, void *motion_out_dev, int motion_format, const void *gbuffer_dev,
+                                     const float *position_dev, const int *geom_id_dev, int width, int height,
+                                     const SvgfCamera *prev_cam, const float reproj_scale[2], const float *geom_xf_dev, int n_geoms,
+                                     void *stream)
+{
+    if (!motion_out_dev || !temporal_motion_format_known(motion_format) || (!gbuffer_dev && (!position_dev || !geom_id_dev)) ||
+        width <= 0 || height <= 0 || !prev_cam || n_geoms < 0)
+        return SVGF_ERR_INVALID_ARG;
+    if ((long long)width * height >= (1LL << 31) / 16) return SVGF_ERR_UNSUPPORTED;
+    SvgfDeviceGuard dev_guard(device);
+    if (!dev_guard.ok) return SVGF_ERR_NO_DEVICE;
+    MotionReprojArgs a;
+    memset(&a, 0, sizeof(a));
+    a.out = motion_out_dev; a.format = motion_format;
+    a.gbuf = (const float *)gbuffer_dev; a.pos = position_dev; a.gid = geom_id_dev;
+    view_matrix_from_camera(prev_cam, a.M);
+    a.W = width; a.H = height;
+    a.reproj_sx = reproj_scale ? reproj_scale[0] : 0.0f; a.reproj_sy = reproj_scale ? reproj_scale[1] : 0.0f;
+    a.xf = n_geoms > 0 ? geom_xf_dev : nullptr; a.n_geoms = a.xf ? n_geoms : 0;
+    return launch_motion_reproject(a, (hipStream_t)stream) == hipSuccess ? SVGF_OK : SVGF_ERR_HIP;
 }
 
 // ---- the planar path (the AoS -> plane repack fused into the producer) -----------------------
@@ -1169,12 +1215,18 @@ extern "C" int svgf_planar_gbuffer_stream(svgf_ctx *c, SvgfPlanarGBuffer *out, v
 
 extern "C" int svgf_denoise_planar(svgf_ctx *c, void *out_rgb_dev, const void *in_rgb_dev, const SvgfCamera *cam, const SvgfParams *p, void *stream)
 {
+    return svgf_denoise_planar_motion(c, out_rgb_dev, in_rgb_dev, nullptr, 0, cam, p, stream);
+}
+
+extern "C" int svgf_denoise_planar_motion(svgf_ctx *c, void *out_rgb_dev, const void *in_rgb_dev, const void *motion_dev, int motion_format,
+                                          const SvgfCamera *cam, const SvgfParams *p, void *stream)
+{
     if (!c) return SVGF_ERR_INVALID_ARG;
     if (p && p->sepcolor && p->addcolor && !c->albedo) {
         snprintf(c->err, sizeof(c->err), "svgf_denoise_planar: sepcolor && addcolor needs the albedo plane of svgf_planar_gbuffer");
         return SVGF_ERR_INVALID_ARG;
     }
-    return denoise_frame(c, out_rgb_dev, in_rgb_dev, nullptr, cam, p, stream);
+    return denoise_frame(c, out_rgb_dev, in_rgb_dev, nullptr, motion_dev, motion_format, cam, p, stream);
 }
 
 extern "C" int svgf_denoise_host(svgf_ctx *c, float *out_rgb_host, const float *in_rgb_host,

@@ -61,6 +61,7 @@ bool atrous_fused_supported(const AtrousArgs &a, const TemporalArgs &t)
     if (a.step != 2) return false;                                   // the reference's first level (src/denoise.cu:98,386)
     if ((long long)a.W * a.H + 8 >= (1LL << 24)) return false;       // 24-bit element indices (v_mad_u32_u24), 32-bit byte offsets
     if (t.pos_tol > 0.0f) return false;                              // f4 extension, k_temporal only
+    if (t.motion) return false;                                      // motion vectors (f5): k_temporal only
     LaneFused f;
     return fused_offsets(t, &f);                                     // every plane inside the context's one allocation
 }

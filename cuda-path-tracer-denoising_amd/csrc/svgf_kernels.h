@@ -128,9 +128,32 @@ struct TemporalArgs {
     size_t arena_bytes;       // the kernel addresses them as arena + 32-bit offset (svgf_atrous_lane_impl.h: LaneFused)
     int skip_split;           // k_temporal on the AoS boundary: do not write nrm_cur / pos_cur / gid_cur (the first a-trous level's
                               // loaders will: svgf_atrous_fused.hip, FUSED = 4)
+    const void *motion;       // k_temporal only: per-pixel previous-frame coordinates from the caller (svgf_denoise_motion) in
+    int motion_format;        // SVGF_MOTION_* layout, read INSTEAD of projecting pos through M; null: the camera path
 };
 
+// TemporalArgs::motion_format, the values of include/svgf.h's SVGF_MOTION_* (svgf_api.hip asserts the equality)
+#define SVGF_MOTION_FMT_NONE  0
+#define SVGF_MOTION_FMT_COORD 1      // SVGF_MOTION_PREV_COORD_F32
+#define SVGF_MOTION_FMT_D32   2      // SVGF_MOTION_DELTA_F32
+#define SVGF_MOTION_FMT_D16   3      // SVGF_MOTION_DELTA_F16
+// motion == null launches the camera-path kernel; otherwise the instantiation of motion_format (hipErrorInvalidValue if unknown)
 hipError_t launch_temporal(const TemporalArgs &a, hipStream_t s);
+bool       temporal_motion_format_known(int motion_format);
+// svgf_motion_reproject: the plane launch_temporal's motion kernels read, written with the camera path's own projection
+struct MotionReprojArgs {
+    void *out;                // W*H elements of `format`
+    int format;               // SVGF_MOTION_*
+    const float *gbuf;        // raw 52-B texels, or null:
+    const float *pos;         //   packed float3 positions and
+    const int *gid;           //   int geomId plane
+    float M[16];              // previous view matrix, column-major
+    int W, H;
+    float reproj_sx, reproj_sy;
+    const float *xf;          // n_geoms 3x4 row-major maps, this frame's world space -> the previous frame's; may be null
+    int n_geoms;
+};
+hipError_t launch_motion_reproject(const MotionReprojArgs &a, hipStream_t s);
 // SvgfParams::spatial_variance_frames (f4): variance of short-history pixels from the 7x7 neighbourhood's moments
 hipError_t launch_spatial_variance(float4 *cv_acc, const float2 *mom_acc, const int *hlen_upd, const float *nrm, const int *gid,
                                    int W, int H, int K, hipStream_t s);

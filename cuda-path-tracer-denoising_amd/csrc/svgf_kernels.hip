@@ -44,7 +44,9 @@ __device__ __forceinline__ int reproj_valid_pos(const TemporalArgs &a, int q, fl
     return (dist3_strict(pp[0], pp[1], pp[2], px, py, pz) <= a.pos_tol) ? q : -1;
 }
 
-template <int BLOCK>
+// MOTION (SVGF_MOTION_FMT_*): 0 projects the pixel's position through the previous camera; the others read the previous-frame
+// coordinate from the caller's plane in that format.  A template parameter: the camera path's kernel carries no trace of them.
+template <int BLOCK, int MOTION>
 __global__ __launch_bounds__(BLOCK) void k_temporal(TemporalArgs a)
 {
 #pragma clang fp contract(off)
@@ -77,10 +79,16 @@ __global__ __launch_bounds__(BLOCK) void k_temporal(TemporalArgs a)
     bool valid = false;
     SvgfHistSum hs = { 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f };
     if (N > 0 && gid != -1) {
-        const SvgfReproj rp = svgf_reproject(a, px, py, pz);          // previous-frame pixel coordinate (:198-209)
+        SvgfReproj rp;                                                // previous-frame pixel coordinate (:198-209)
+        if constexpr (MOTION == SVGF_MOTION_FMT_NONE) {
+            rp = svgf_reproject(a, px, py, pz);
+        } else {
+            const SvgfPrevCoord c = svgf_motion_prev_coord<MOTION>(a, p);
+            rp = svgf_reproj_from_coord(c.x, c.y);
+        }
         const float fx = rp.fx, fy = rp.fy;
 
-        valid = (fx >= 0.0f && fy >= 0.0f && fx < (float)a.W && fy < (float)a.H);
+        valid = svgf_reproj_on_screen(a, rp);
         int q4[4];
 #pragma unroll
         for (int k = 0; k < 4; k++) {
@@ -130,7 +138,73 @@ __global__ __launch_bounds__(BLOCK) void k_temporal(TemporalArgs a)
 hipError_t launch_temporal(const TemporalArgs &a, hipStream_t s)
 {
     const long long n = (long long)a.W * a.H;
-    SVGF_LAUNCH_KERNEL(k_temporal<SVGF_BLOCK>, dim3(div_up(n, SVGF_BLOCK)), dim3(SVGF_BLOCK), 0, s, a);
+    const dim3 grid(div_up(n, SVGF_BLOCK)), block(SVGF_BLOCK);
+    if (!a.motion) {
+        SVGF_LAUNCH_KERNEL((k_temporal<SVGF_BLOCK, SVGF_MOTION_FMT_NONE>), grid, block, 0, s, a);
+        return hipGetLastError();
+    }
+    switch (a.motion_format) {
+    case SVGF_MOTION_FMT_COORD: SVGF_LAUNCH_KERNEL((k_temporal<SVGF_BLOCK, SVGF_MOTION_FMT_COORD>), grid, block, 0, s, a); break;
+    case SVGF_MOTION_FMT_D32:   SVGF_LAUNCH_KERNEL((k_temporal<SVGF_BLOCK, SVGF_MOTION_FMT_D32>), grid, block, 0, s, a); break;
+    case SVGF_MOTION_FMT_D16:   SVGF_LAUNCH_KERNEL((k_temporal<SVGF_BLOCK, SVGF_MOTION_FMT_D16>), grid, block, 0, s, a); break;
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+bool temporal_motion_format_known(int f) { return f == SVGF_MOTION_FMT_COORD || f == SVGF_MOTION_FMT_D32 || f == SVGF_MOTION_FMT_D16; }
+
+// ----------------------------------------------------------------------------------------------------
+// svgf_motion_reproject: writes the motion plane of a frame.  Per pixel: the texel's position, moved into the previous frame's
+// world space by its object's 3x4 map where one is given, through svgf_project_prev — the camera path's own projection — and
+// stored in the requested format (delta formats: prev - (float)pixel).  Ray misses (geomId == -1) get NaN: no usable tap.
+// ----------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(SVGF_BLOCK) void k_motion_reproject(MotionReprojArgs a)
+{
+#pragma clang fp contract(off)
+    const int n = a.W * a.H;
+    const int p = blockIdx.x * SVGF_BLOCK + threadIdx.x;
+    if (p >= n) return;
+    float px, py, pz;
+    int gid;
+    if (a.gbuf) {
+        const float *t = a.gbuf + 13 * (size_t)p;
+        px = t[3]; py = t[4]; pz = t[5];
+        gid = __float_as_int(t[12]);
+    } else {
+        px = a.pos[3 * (size_t)p]; py = a.pos[3 * (size_t)p + 1]; pz = a.pos[3 * (size_t)p + 2];
+        gid = a.gid[p];
+    }
+    float ox, oy;
+    if (gid == -1) {
+        ox = oy = __uint_as_float(0x7fc00000u);
+    } else {
+        if (a.xf && gid >= 0 && gid < a.n_geoms) {                   // ((m0 v0 + m1 v1) + m2 v2) + m3, as svgf_scene.hip's apply
+            const float *m = a.xf + 12 * (size_t)gid;
+            float q[3];
+#pragma unroll
+            for (int r = 0; r < 3; r++) {
+                float t0 = m[4 * r] * px + m[4 * r + 1] * py;
+                t0 = t0 + m[4 * r + 2] * pz;
+                q[r] = t0 + m[4 * r + 3];
+            }
+            px = q[0]; py = q[1]; pz = q[2];
+        }
+        const SvgfPrevCoord c = svgf_project_prev(a.M, a.W, a.H, a.reproj_sx, a.reproj_sy, px, py, pz);
+        ox = c.x; oy = c.y;
+        if (a.format != SVGF_MOTION_FMT_COORD) {
+            const int y = p / a.W, x = p - y * a.W;
+            ox = ox - (float)x; oy = oy - (float)y;
+        }
+    }
+    if (a.format == SVGF_MOTION_FMT_D16) ((__half2 *)a.out)[p] = __halves2half2(__float2half(ox), __float2half(oy));
+    else ((float2 *)a.out)[p] = make_float2(ox, oy);
+}
+
+hipError_t launch_motion_reproject(const MotionReprojArgs &a, hipStream_t s)
+{
+    const long long n = (long long)a.W * a.H;
+    SVGF_LAUNCH_KERNEL(k_motion_reproject, dim3(div_up(n, SVGF_BLOCK)), dim3(SVGF_BLOCK), 0, s, a);
     return hipGetLastError();
 }
 

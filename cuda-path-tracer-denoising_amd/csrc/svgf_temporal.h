@@ -6,6 +6,7 @@
 // glm mat4 * vec4 association (m0 v0 + m1 v1) + (m2 v2 + m3 v3), luminance in double, alpha on the current side for colour
 // (:297) and on the history side for the moments (:300-301), (int) truncation of the interpolated history length (:294).
 #pragma once
+#include <hip/hip_fp16.h>
 #include "svgf_kernels.h"
 
 // luminance with the reference's double promotion (src/denoise.cu:121,138,196)
@@ -27,27 +28,79 @@ __device__ __forceinline__ float svgf_dist3_strict(float ax, float ay, float az,
     return sqrtf(s);
 }
 
-// previous-frame pixel coordinate of world position (px,py,pz) (:198-209): floor and fraction of the reprojected position
-struct SvgfReproj { float fx, fy, fracx, fracy; };
-__device__ __forceinline__ SvgfReproj svgf_reproject(const TemporalArgs &a, float px, float py, float pz)
+// The projection half of the reprojection (:198-206): world position (px,py,pz) through the previous view matrix M (column-major)
+// to the previous-frame pixel coordinate, pixel centres at integers.  The one place this arithmetic lives: the camera path of the
+// temporal pass and the motion-plane writer (k_motion_reproject, svgf_kernels.hip) both call it, so a plane written by the latter
+// holds exactly the coordinates the former would have computed.
+struct SvgfPrevCoord { float x, y; };
+__device__ __forceinline__ SvgfPrevCoord svgf_project_prev(const float *M, int W, int H, float reproj_sx, float reproj_sy,
+                                                           float px, float py, float pz)
 {
 #pragma clang fp contract(off)
     float vs[3];
 #pragma unroll
     for (int r = 0; r < 3; r++) {
-        float a0 = a.M[0 * 4 + r] * px + a.M[1 * 4 + r] * py;
-        float a1 = a.M[2 * 4 + r] * pz + a.M[3 * 4 + r] * 1.0f;
+        float a0 = M[0 * 4 + r] * px + M[1 * 4 + r] * py;
+        float a1 = M[2 * 4 + r] * pz + M[3 * 4 + r] * 1.0f;
         vs[r] = a0 + a1;
     }
     float clipx = vs[0] / vs[2], clipy = vs[1] / vs[2];          // no tan(fov), no aspect (:202-203)
-    if (a.reproj_sx > 0.0f) clipx = clipx / a.reproj_sx;          // f4 extension: exact for any fov / aspect
-    if (a.reproj_sy > 0.0f) clipy = clipy / a.reproj_sy;
+    if (reproj_sx > 0.0f) clipx = clipx / reproj_sx;              // f4 extension: exact for any fov / aspect
+    if (reproj_sy > 0.0f) clipy = clipy / reproj_sy;
     float ndcx = -clipx * 0.5f + 0.5f, ndcy = -clipy * 0.5f + 0.5f;
-    float prevx = ndcx * (float)a.W - 0.5f, prevy = ndcy * (float)a.H - 0.5f;
+    SvgfPrevCoord c;
+    c.x = ndcx * (float)W - 0.5f; c.y = ndcy * (float)H - 0.5f;
+    return c;
+}
+
+// The other half (:207-209): floor and fraction of a previous-frame pixel coordinate, wherever it came from (the projection above
+// or a caller's motion plane).  Any float is a defined input: NaN stays NaN, +-inf stays +-inf, and both fail svgf_reproj_on_screen
+// and svgf_tap_index below before an address is formed.
+struct SvgfReproj { float fx, fy, fracx, fracy; };
+__device__ __forceinline__ SvgfReproj svgf_reproj_from_coord(float prevx, float prevy)
+{
+#pragma clang fp contract(off)
     SvgfReproj r;
     r.fx = floorf(prevx); r.fy = floorf(prevy);
     r.fracx = prevx - r.fx; r.fracy = prevy - r.fy;
     return r;
+}
+// the reference's bounds rule on the floor (:210-211); false for NaN
+__device__ __forceinline__ bool svgf_reproj_on_screen(const TemporalArgs &a, const SvgfReproj &r)
+{
+    return r.fx >= 0.0f && r.fy >= 0.0f && r.fx < (float)a.W && r.fy < (float)a.H;
+}
+
+// previous-frame pixel coordinate of world position (px,py,pz) (:198-209): floor and fraction of the reprojected position
+__device__ __forceinline__ SvgfReproj svgf_reproject(const TemporalArgs &a, float px, float py, float pz)
+{
+    const SvgfPrevCoord c = svgf_project_prev(a.M, a.W, a.H, a.reproj_sx, a.reproj_sy, px, py, pz);
+    return svgf_reproj_from_coord(c.x, c.y);
+}
+
+// Motion input (include/svgf.h SVGF_MOTION_*): the previous-frame coordinate of pixel p = x + y*W read from the caller's plane
+// instead of being projected.  FORMAT is a compile-time constant of the kernel instantiation.
+template <int FORMAT>
+__device__ __forceinline__ SvgfPrevCoord svgf_motion_prev_coord(const TemporalArgs &a, int p)
+{
+#pragma clang fp contract(off)
+    SvgfPrevCoord c;
+    if constexpr (FORMAT == SVGF_MOTION_FMT_COORD) {
+        const float2 m = ((const float2 *)a.motion)[p];
+        c.x = m.x; c.y = m.y;
+    } else {
+        const int y = p / a.W, x = p - y * a.W;
+        float dx, dy;
+        if constexpr (FORMAT == SVGF_MOTION_FMT_D32) {
+            const float2 m = ((const float2 *)a.motion)[p];
+            dx = m.x; dy = m.y;
+        } else {
+            const __half2 m = ((const __half2 *)a.motion)[p];
+            dx = __low2float(m); dy = __high2float(m);
+        }
+        c.x = (float)x + dx; c.y = (float)y + dy;
+    }
+    return c;
 }
 
 // bounds part of isReprjValid (:173-176): texel index of the tap at float coordinate (qx, qy), -1 when it is outside the

@@ -375,6 +375,31 @@ int svgf_scene_render_mesh_planar(int device, void *out_rgb_dev, const SvgfPlana
                                   const int *tri_tex, const int *tex_desc, const unsigned char *tex_data, int n_tex,
                                   const float light[3], void *stream);
 
+/* ---- "next" row f5: per-pixel motion vectors (added after 0.9; probe the symbol) ----------------------------------
+ * The temporal pass finds a pixel's history at the coordinate the caller gives instead of projecting the pixel's position
+ * through the previous camera: history survives on geometry that moved.  `motion_dev`: W*H elements in device memory, an
+ * INPUT like the colour image (inputs_ready covers it); NULL = exactly svgf_denoise / svgf_denoise_planar.  Ignored when
+ * temporal_enable == 0.  Any float is defined: NaN, +-inf and off-screen values mean "no history".  INTEGRATION.md has
+ * the conventions (pixel centres at integers; `prev` is where this pixel's surface point was in the previous frame). */
+#define SVGF_MOTION_PREV_COORD_F32 1   /* float[2]: prev.x, prev.y */
+#define SVGF_MOTION_DELTA_F32      2   /* float[2]: prev - (x, y) */
+#define SVGF_MOTION_DELTA_F16      3   /* __half[2]: the same, converted to float first */
+int svgf_denoise_motion(svgf_ctx *ctx, void *out_rgb_dev, const void *in_rgb_dev, const void *gbuffer_dev,
+                        const void *motion_dev, int motion_format, const SvgfCamera *cam, const SvgfParams *params,
+                        void *stream);
+/* added after 0.9; probe the symbol.  svgf_denoise_planar with the motion plane of svgf_denoise_motion. */
+int svgf_denoise_planar_motion(svgf_ctx *ctx, void *out_rgb_dev, const void *in_rgb_dev, const void *motion_dev,
+                               int motion_format, const SvgfCamera *cam, const SvgfParams *params, void *stream);
+/* added after 0.9; probe the symbol.  Writes such a plane for rigid motion: per pixel the texel's position (AoS texels, or
+ * NULL and the two planes), mapped by geom_xf_dev[geomId] (3x4 row-major, this frame's world -> the previous frame's; NULL /
+ * out-of-range id: unmoved), through the camera path's own projection with `prev_cam` and `reproj_scale` (NULL = 0, 0).
+ * geomId == -1 gets NaN.  With n_geoms = 0 the plane reproduces svgf_denoise bit for bit (SVGF_MOTION_PREV_COORD_F32).
+ * Stateless, asynchronous on `stream`, allocates nothing. */
+int svgf_motion_reproject(int device, void *motion_out_dev, int motion_format, const void *gbuffer_dev,
+                          const float *position_dev, const int *geom_id_dev, int width, int height,
+                          const SvgfCamera *prev_cam, const float reproj_scale[2], const float *geom_xf_dev, int n_geoms,
+                          void *stream);
+
 /* ---- "next" row f2: the step right after denoise() ------------------------------------------------
  * svgf_display_pack: reference sendTwoImagesToPBO (src/pathtrace.cu:45-77, launched at :446): `left` (the 1-spp
  *   image) and `right` (the denoised image), both packed rgb floats in device memory, side by side into a

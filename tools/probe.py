@@ -33,6 +33,8 @@ def main():
     ap.add_argument("--blur", type=int, default=1, help="SvgfParams.blur_variance")
     ap.add_argument("--reps", type=int, default=20, help="frames of the back-to-back wall-time loop (no per-kernel events)")
     ap.add_argument("--planar", action="store_true", help="G-buffer handed over as planes (svgf_denoise_planar), static scene")
+    ap.add_argument("--motion", choices=["coord", "delta", "delta16"], default=None, help="the temporal pass reads per-pixel motion vectors in this format "
+                    "(svgf_denoise_motion; the plane is written once by svgf_motion_reproject for the static camera) instead of projecting through the previous camera")
     ap.add_argument("--sustain", type=float, default=0.0, help="seconds of back-to-back frames in front of every measurement (the sustained clock / "
                     "power state bench.py measures in, DESIGN.md 6.2); 0 = measure from wherever the GPU is (cold after start-up)")
     ap.add_argument("--telemetry-json", default=None, help="append one JSON line per variant: {variant, frame_us, telemetry summary} (the A/B scripts' clock check)")
@@ -58,6 +60,18 @@ def main():
                 d.denoise_planar(out, d_in[0], cam[0], p)
             torch.cuda.synchronize()
             d.denoise = lambda o, i, g, c, pp, _d=d: _d.denoise_planar(o, i, c, pp)
+        if a.motion:      # one plane per source frame (same camera, same geometry: what the camera path computes, read instead)
+            fmt = {"coord": pkg.binding.MOTION_PREV_COORD_F32, "delta": pkg.binding.MOTION_DELTA_F32, "delta16": pkg.binding.MOTION_DELTA_F16}[a.motion]
+            mv = {}
+            for k in range(nsrc):
+                m = torch.empty((H, W, 2), dtype=torch.float16 if a.motion == "delta16" else torch.float32, device="cuda")
+                pkg.binding.motion_reproject(m, W, H, cam[k], gbuffer=d_g[k], motion_format=fmt)
+                mv[d_g[k].data_ptr()] = m
+            torch.cuda.synchronize()
+            if a.planar:
+                d.denoise = lambda o, i, g, c, pp, _d=d: _d.denoise_planar(o, i, c, pp, motion=mv[g.data_ptr()], motion_format=fmt)
+            else:
+                d.denoise = lambda o, i, g, c, pp, _f=type(d).denoise, _d=d: _f(_d, o, i, g, c, pp, motion=mv[g.data_ptr()], motion_format=fmt)
         def sustain():
             if a.sustain <= 0:
                 return
