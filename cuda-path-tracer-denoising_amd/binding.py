@@ -35,7 +35,8 @@ EXPORTS = ["svgf_version", "svgf_params_default", "svgf_create", "svgf_destroy",
            "svgf_planar_gbuffer", "svgf_denoise_planar", "svgf_synth_render_planar", "svgf_params_sizeof", "svgf_scene_render_mesh_planar",
            "svgf_sync_stream", "svgf_build_has_experiments", "svgf_is_pipelined", "svgf_create_ex", "svgf_enable_pipeline",
            "svgf_pipeline_status", "svgf_planar_gbuffer_stream", "svgf_streams_overlap",
-           "svgf_denoise_motion", "svgf_denoise_planar_motion", "svgf_motion_reproject"]
+           "svgf_denoise_motion", "svgf_denoise_planar_motion", "svgf_motion_reproject",
+           "svgf_set_history_clamp", "svgf_get_history_clamp"]
 CREATE_PIPELINED = 1
 # motion plane formats (svgf_denoise_motion): absolute previous coordinate, delta in float32, delta in float16
 MOTION_PREV_COORD_F32, MOTION_DELTA_F32, MOTION_DELTA_F16 = 1, 2, 3
@@ -172,6 +173,8 @@ def load_library(path: str | None = None, experiments: bool = False):
     lib.svgf_denoise_motion.argtypes = [vp, vp, vp, vp, vp, ip, C.POINTER(SvgfCamera), C.POINTER(SvgfParams), vp]
     lib.svgf_denoise_planar_motion.argtypes = [vp, vp, vp, vp, ip, C.POINTER(SvgfCamera), C.POINTER(SvgfParams), vp]
     lib.svgf_motion_reproject.argtypes = [ip, vp, ip, vp, vp, vp, ip, ip, C.POINTER(SvgfCamera), C.POINTER(C.c_float), vp, ip, vp]
+    lib.svgf_set_history_clamp.argtypes = [vp, ip, C.c_float]
+    lib.svgf_get_history_clamp.argtypes = [vp, C.POINTER(ip), C.POINTER(C.c_float)]
     lib.svgf_denoise_host.argtypes = [vp, vp, vp, vp, C.POINTER(SvgfCamera), C.POINTER(SvgfParams)]
     lib.svgf_sync.argtypes = [vp]
     lib.svgf_sync_stream.argtypes = [vp, vp]
@@ -368,6 +371,17 @@ class Denoiser:
 
     def set_capture(self, on: bool = True):
         self._check(self.lib.svgf_set_capture(self.h, 1 if on else 0), "svgf_set_capture")
+
+    def set_history_clamp(self, radius: int, sigma_scale: float = 1.0):
+        """svgf_set_history_clamp: clamp the reprojected history colour to mean +- sigma_scale * sigma of the current frame's
+        (2 radius + 1)^2 colour window before the blend; radius 0 (the default) = off, 1..3.  Survives reset()."""
+        self._check(self.lib.svgf_set_history_clamp(self.h, int(radius), float(sigma_scale)), "svgf_set_history_clamp")
+
+    def history_clamp(self) -> tuple[int, float]:
+        """(radius, sigma_scale) as set by set_history_clamp(); (0, 0.0) on a fresh context."""
+        r, k = C.c_int(), C.c_float()
+        self._check(self.lib.svgf_get_history_clamp(self.h, C.byref(r), C.byref(k)), "svgf_get_history_clamp")
+        return int(r.value), float(k.value)
 
     def read_state(self, which: int) -> np.ndarray:
         n = self.width * self.height

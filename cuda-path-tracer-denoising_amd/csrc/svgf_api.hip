@@ -88,6 +88,9 @@ struct svgf_ctx {
     int cur;       // mom/hlen index holding the history the next frame reads
     int gcur;      // nrm/gid/pos index holding the previous frame's planes
     float view_prev[16];   // column-major; identity until the first frame (reference src/denoise.cu:15)
+    // svgf_set_history_clamp: configuration, not history (svgf_reset keeps it); read by plan_frame when a frame is enqueued
+    int clamp_radius;      // 0 = off
+    float clamp_k;
     // state capture for tests
     int capture;
     float4 *cv_capture;
@@ -385,6 +388,30 @@ extern "C" int svgf_reset(svgf_ctx *c)
     SVGF_ENTER(c);
     HIPC(c, hipDeviceSynchronize());
     return zero_state(c);
+}
+
+// History clamp of the temporal pass (include/svgf.h).  Host state only: no device work, nothing to order.
+extern "C" int svgf_set_history_clamp(svgf_ctx *c, int radius, float sigma_scale)
+{
+    if (!c) return SVGF_ERR_INVALID_ARG;
+    if (radius < 0 || radius > 3) {
+        snprintf(c->err, sizeof(c->err), "svgf_set_history_clamp: radius %d outside 0..3", radius);
+        return SVGF_ERR_INVALID_ARG;
+    }
+    if (!(sigma_scale >= 0.0f) || sigma_scale > 3.402823466e38f) {      // NaN, negative, +inf
+        snprintf(c->err, sizeof(c->err), "svgf_set_history_clamp: sigma_scale %g is not a finite number >= 0", (double)sigma_scale);
+        return SVGF_ERR_INVALID_ARG;
+    }
+    c->clamp_radius = radius; c->clamp_k = sigma_scale;
+    return SVGF_OK;
+}
+
+extern "C" int svgf_get_history_clamp(const svgf_ctx *c, int *radius, float *sigma_scale)
+{
+    if (!c) return SVGF_ERR_INVALID_ARG;
+    if (radius) *radius = c->clamp_radius;
+    if (sigma_scale) *sigma_scale = c->clamp_k;
+    return SVGF_OK;
 }
 
 extern "C" int svgf_is_pipelined(const svgf_ctx *c) { return (c && c->pipelined && c->piped_mode) ? 1 : 0; }
@@ -847,6 +874,17 @@ static int plan_frame(svgf_ctx *c, void *out_rgb_dev, const void *in_rgb_dev, co
         return SVGF_ERR_UNSUPPORTED;
     }
 #endif
+    const bool clamp = c->clamp_radius > 0 && p->temporal_enable;      // svgf_set_history_clamp (a non-temporal frame gathers no history)
+    if (clamp && !temporal_clamp_supported(c->W, c->H)) {
+        snprintf(c->err, sizeof(c->err), "svgf_denoise: the history clamp (svgf_set_history_clamp) is limited to images of at most 262140 rows, this context has %d", c->H);
+        return SVGF_ERR_UNSUPPORTED;
+    }
+#ifdef SVGF_BUILD_EXPERIMENTS
+    if (clamp && (p->kernel_variant == 6 || c->use_split_fused)) {
+        snprintf(c->err, sizeof(c->err), "svgf_denoise: the parked fused temporal kernels (kernel_variant 6, split_fused) have no history clamp (svgf_set_history_clamp)");
+        return SVGF_ERR_UNSUPPORTED;
+    }
+#endif
     const float *in = (const float *)in_rgb_dev, *g = (const float *)gbuffer_dev;
     pl.out = (float *)out_rgb_dev; pl.s_user = (hipStream_t)stream; pl.cap_id = 0;
     // Pipelined frames (see svgf_ctx::pipelined).  The promise behind inputs_ready = 1: at call time the inputs are complete (and stay
@@ -931,8 +969,9 @@ static int plan_frame(svgf_ctx *c, void *out_rgb_dev, const void *in_rgb_dev, co
         t.pos_prev = c->pos[c->gcur]; t.pos_tol = p->reproj_position_tol;
         t.dump = c->dump; t.arena = c->arena; t.arena_bytes = c->arena_bytes;
         if (motion) { t.motion = motion_dev; t.motion_format = motion_format; }
+        if (clamp) { t.clamp_radius = c->clamp_radius; t.clamp_k = c->clamp_k; }
 #ifdef SVGF_BUILD_EXPERIMENTS      // parked: the temporal pass in the first level's loaders, DESIGN.md 5.8
-        if (!motion && cascade && (p->kernel_variant == 0 || p->kernel_variant == 6) && !p->paper_steps && p->spatial_variance_frames <= 0)
+        if (!motion && !clamp && cascade && (p->kernel_variant == 0 || p->kernel_variant == 6) && !p->paper_steps && p->spatial_variance_frames <= 0)
             pl.fused = atrous_fused_supported(probe, t) && (p->kernel_variant == 6 || fuse_pays(c, probe));
 #endif
     } else if (g && cascade && (p->kernel_variant == 0 || p->kernel_variant == 6) && !p->paper_steps) {

@@ -130,6 +130,8 @@ struct TemporalArgs {
                               // loaders will: svgf_atrous_fused.hip, FUSED = 4)
     const void *motion;       // k_temporal only: per-pixel previous-frame coordinates from the caller (svgf_denoise_motion) in
     int motion_format;        // SVGF_MOTION_* layout, read INSTEAD of projecting pos through M; null: the camera path
+    int clamp_radius;         // svgf_set_history_clamp: 0 launches k_temporal, which reads neither field; 1..3 the clamped kernels
+    float clamp_k;            //   (history colour clamped to mean +- clamp_k * sigma of in_rgb's (2r+1)^2 window, svgf_temporal.h)
 };
 
 // TemporalArgs::motion_format, the values of include/svgf.h's SVGF_MOTION_* (svgf_api.hip asserts the equality)
@@ -137,9 +139,11 @@ struct TemporalArgs {
 #define SVGF_MOTION_FMT_COORD 1      // SVGF_MOTION_PREV_COORD_F32
 #define SVGF_MOTION_FMT_D32   2      // SVGF_MOTION_DELTA_F32
 #define SVGF_MOTION_FMT_D16   3      // SVGF_MOTION_DELTA_F16
-// motion == null launches the camera-path kernel; otherwise the instantiation of motion_format (hipErrorInvalidValue if unknown)
+// motion == null launches the camera-path kernel; otherwise the instantiation of motion_format (hipErrorInvalidValue if unknown);
+// clamp_radius 1..3: the clamped instantiation of the same (svgf_kernels.hip: k_temporal_clamped)
 hipError_t launch_temporal(const TemporalArgs &a, hipStream_t s);
 bool       temporal_motion_format_known(int motion_format);
+bool       temporal_clamp_supported(int W, int H);      // images the clamped kernels can be launched on (H <= 262140)
 // svgf_motion_reproject: the plane launch_temporal's motion kernels read, written with the camera path's own projection
 struct MotionReprojArgs {
     void *out;                // W*H elements of `format`

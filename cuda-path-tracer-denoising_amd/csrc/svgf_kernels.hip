@@ -1,4 +1,4 @@
-// svgf_kernels.hip — temporal accumulation, G-buffer split, strict a-trous gather, debug/copy kernels (gfx950).
+// svgf_kernels.hip — temporal accumulation (with and without the history clamp), G-buffer split, strict a-trous gather, debug/copy kernels (gfx950).
 //
 // The temporal kernel and the strict gather kernel keep the reference's arithmetic order and double promotions
 // (reference src/denoise.cu:121,138,143-145,159,196,252) with FMA contraction off, so that they agree with the CPU
@@ -44,6 +44,17 @@ __device__ __forceinline__ int reproj_valid_pos(const TemporalArgs &a, int q, fl
     return (dist3_strict(pp[0], pp[1], pp[2], px, py, pz) <= a.pos_tol) ? q : -1;
 }
 
+// History clamp (svgf_set_history_clamp): the tile of the current frame's colour a workgroup of the clamped kernels stages in LDS,
+// TILE_W x TILE_H pixels and a margin of R on every side, as three float planes (packed 12-byte records would sit off the natural
+// alignment of the wide LDS reads).
+#define SVGF_CLAMP_TILE_W 64
+#define SVGF_CLAMP_TILE_H (SVGF_BLOCK / SVGF_CLAMP_TILE_W)
+template <int R> struct ClampTile {
+    static constexpr int PITCH = SVGF_CLAMP_TILE_W + 2 * R, ROWS = SVGF_CLAMP_TILE_H + 2 * R, PLANE = PITCH * ROWS;
+    const float *c0, *c1, *c2;      // the pixel's own entry in the three planes
+    int x, y;                       // the pixel
+};
+
 // MOTION (SVGF_MOTION_FMT_*): 0 projects the pixel's position through the previous camera; the others read the previous-frame
 // coordinate from the caller's plane in that format.  A template parameter: the camera path's kernel carries no trace of them.
 template <int BLOCK, int MOTION>
@@ -53,90 +64,69 @@ __global__ __launch_bounds__(BLOCK) void k_temporal(TemporalArgs a)
     const int n = a.W * a.H;
     const int p = blockIdx.x * BLOCK + threadIdx.x;
     if (p >= n) return;
-
-    float nx, ny, nz, px, py, pz;
-    int gid;
-    if (a.gbuf) {             // the boundary's AoS texel (52 B): read once, split into the planes every later kernel reads
-        const float *t = a.gbuf + 13 * (size_t)p;
-        nx = t[0]; ny = t[1]; nz = t[2];
-        px = t[3]; py = t[4]; pz = t[5];
-        gid = __float_as_int(t[12]);
-        if (!a.skip_split) {
-            a.nrm_cur[3 * (size_t)p] = nx; a.nrm_cur[3 * (size_t)p + 1] = ny; a.nrm_cur[3 * (size_t)p + 2] = nz;
-            a.pos_cur[3 * (size_t)p] = px; a.pos_cur[3 * (size_t)p + 1] = py; a.pos_cur[3 * (size_t)p + 2] = pz;
-            a.gid_cur[p] = gid;
-        }
-    } else {                  // planar path: the producer wrote the planes in place (svgf_planar_gbuffer), 28 B read, nothing split
-        nx = a.nrm_cur[3 * (size_t)p]; ny = a.nrm_cur[3 * (size_t)p + 1]; nz = a.nrm_cur[3 * (size_t)p + 2];
-        px = a.pos_cur[3 * (size_t)p]; py = a.pos_cur[3 * (size_t)p + 1]; pz = a.pos_cur[3 * (size_t)p + 2];
-        gid = a.gid_cur[p];
-    }
-
-    const float cr = a.in_rgb[3 * (size_t)p], cg = a.in_rgb[3 * (size_t)p + 1], cb = a.in_rgb[3 * (size_t)p + 2];
-    const float lum = lum_strict(cr, cg, cb);
-    const int N = a.hlen[p];
-
-    bool valid = false;
-    SvgfHistSum hs = { 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f };
-    if (N > 0 && gid != -1) {
-        SvgfReproj rp;                                                // previous-frame pixel coordinate (:198-209)
-        if constexpr (MOTION == SVGF_MOTION_FMT_NONE) {
-            rp = svgf_reproject(a, px, py, pz);
-        } else {
-            const SvgfPrevCoord c = svgf_motion_prev_coord<MOTION>(a, p);
-            rp = svgf_reproj_from_coord(c.x, c.y);
-        }
-        const float fx = rp.fx, fy = rp.fy;
-
-        valid = svgf_reproj_on_screen(a, rp);
-        int q4[4];
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            q4[k] = reproj_valid_pos(a, reproj_valid(a, fx + (float)(k & 1), fy + (float)(k >> 1), gid, nx, ny, nz), px, py, pz);
-            valid = valid && (q4[k] >= 0);
-        }
-
-        if (valid) {                                                  // bilinear (:234-259)
-            float w[4];
-            svgf_bilinear_weights(rp.fracx, rp.fracy, w);
-            float sumw = 0.0f;
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                const int q = q4[k];
-                const float4 ch = a.cv_hist[q];
-                const float2 mh = a.mom_hist[q];
-                svgf_hist_add_weighted(hs, w[k], ch.x, ch.y, ch.z, mh.x, mh.y, a.hlen[q]);
-                sumw += w[k];
-            }
-            if ((double)sumw >= 0.01) svgf_hist_div(hs, sumw);
-        } else {                                                      // 3x3 box around floor (:262-286)
-            float cnt = 0.0f;
-            for (int yy = -1; yy <= 1; yy++)
-                for (int xx = -1; xx <= 1; xx++) {
-                    // the four taps with xx, yy in {0, 1} are the bilinear taps tested above: same arguments, same answer
-                    const int q = (xx >= 0 && yy >= 0) ? q4[xx + 2 * yy]
-                                                       : reproj_valid_pos(a, reproj_valid(a, fx + (float)xx, fy + (float)yy, gid, nx, ny, nz), px, py, pz);
-                    if (q >= 0) {
-                        const float4 ch = a.cv_hist[q];
-                        const float2 mh = a.mom_hist[q];
-                        svgf_hist_add(hs, ch.x, ch.y, ch.z, mh.x, mh.y, a.hlen[q]);
-                        cnt += 1.0f;
-                    }
-                }
-            if (cnt > 0.0f) {
-                svgf_hist_div(hs, cnt);
-                valid = true;
-            }
-        }
-    }
-    const SvgfTemporalOut o = svgf_temporal_blend(a, cr, cg, cb, lum, N, valid, hs);
-    a.hlen_upd[p] = o.hlen;
-    a.mom_acc[p] = o.mom;
-    a.cv_acc[p] = o.cv;
+    constexpr int R = 0;                                              // no history clamp: the body below compiles to what it always was
+    const ClampTile<R> tile = {};
+#include "svgf_temporal_pixel.inc.h"
 }
+
+// The temporal pass with the history clamp of radius R = 1, 2, 3.  A workgroup owns a tile of 64 x 4 pixels — one wave per row
+// piece, so every per-pixel stream is read and written in the same 64-pixel runs as by k_temporal — and stages the tile's colour
+// with its margin (DESIGN.md 5.1 has the reasons for the 2-D tile).  A tile row is 3 * PITCH consecutive floats of in_rgb: they are
+// loaded as such, one float per lane, and scattered into the three planes.  Nothing outside the image is read: those entries
+// are zero and svgf_history_clamp never looks at them.
+template <int BLOCK, int MOTION, int R>
+__global__ __launch_bounds__(BLOCK) void k_temporal_clamped(TemporalArgs a)
+{
+#pragma clang fp contract(off)
+    typedef ClampTile<R> T;
+    static_assert(BLOCK == SVGF_CLAMP_TILE_W * SVGF_CLAMP_TILE_H, "one thread per pixel of the tile");
+    __shared__ float lds[3 * T::PLANE];
+    const int x0 = blockIdx.x * SVGF_CLAMP_TILE_W, y0 = blockIdx.y * SVGF_CLAMP_TILE_H;
+    for (int j = threadIdx.x; j < 3 * T::PLANE; j += BLOCK) {
+        const int row = j / (3 * T::PITCH), k = j - row * (3 * T::PITCH), col = k / 3, ch = k - 3 * col;
+        const int gx = x0 - R + col, gy = y0 - R + row;
+        float v = 0.0f;
+        if (gx >= 0 && gx < a.W && gy >= 0 && gy < a.H) v = a.in_rgb[3 * ((size_t)gy * a.W + gx) + ch];
+        lds[ch * T::PLANE + row * T::PITCH + col] = v;
+    }
+    __syncthreads();
+    const int tx = threadIdx.x % SVGF_CLAMP_TILE_W, ty = threadIdx.x / SVGF_CLAMP_TILE_W;
+    T tile;
+    tile.x = x0 + tx; tile.y = y0 + ty;
+    if (tile.x >= a.W || tile.y >= a.H) return;
+    tile.c0 = lds + (ty + R) * T::PITCH + (tx + R); tile.c1 = tile.c0 + T::PLANE; tile.c2 = tile.c1 + T::PLANE;
+    const int p = tile.x + tile.y * a.W;
+#include "svgf_temporal_pixel.inc.h"
+}
+
+template <int MOTION>
+static hipError_t launch_temporal_clamped(const TemporalArgs &a, hipStream_t s)
+{
+    const dim3 grid(div_up(a.W, SVGF_CLAMP_TILE_W), div_up(a.H, SVGF_CLAMP_TILE_H)), block(SVGF_BLOCK);
+    switch (a.clamp_radius) {
+    case 1: SVGF_LAUNCH_KERNEL((k_temporal_clamped<SVGF_BLOCK, MOTION, 1>), grid, block, 0, s, a); break;
+    case 2: SVGF_LAUNCH_KERNEL((k_temporal_clamped<SVGF_BLOCK, MOTION, 2>), grid, block, 0, s, a); break;
+    case 3: SVGF_LAUNCH_KERNEL((k_temporal_clamped<SVGF_BLOCK, MOTION, 3>), grid, block, 0, s, a); break;
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+// the clamped kernels' grid has one row of workgroups per SVGF_CLAMP_TILE_H image rows (grid.y <= 65535)
+bool temporal_clamp_supported(int W, int H) { (void)W; return H <= 65535 * SVGF_CLAMP_TILE_H; }
 
 hipError_t launch_temporal(const TemporalArgs &a, hipStream_t s)
 {
+    if (a.clamp_radius != 0) {
+        if (!temporal_clamp_supported(a.W, a.H)) return hipErrorInvalidValue;
+        if (!a.motion) return launch_temporal_clamped<SVGF_MOTION_FMT_NONE>(a, s);
+        switch (a.motion_format) {
+        case SVGF_MOTION_FMT_COORD: return launch_temporal_clamped<SVGF_MOTION_FMT_COORD>(a, s);
+        case SVGF_MOTION_FMT_D32:   return launch_temporal_clamped<SVGF_MOTION_FMT_D32>(a, s);
+        case SVGF_MOTION_FMT_D16:   return launch_temporal_clamped<SVGF_MOTION_FMT_D16>(a, s);
+        default: return hipErrorInvalidValue;
+        }
+    }
     const long long n = (long long)a.W * a.H;
     const dim3 grid(div_up(n, SVGF_BLOCK)), block(SVGF_BLOCK);
     if (!a.motion) {

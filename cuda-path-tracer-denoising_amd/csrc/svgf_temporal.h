@@ -161,6 +161,61 @@ __device__ __forceinline__ void svgf_hist_div(SvgfHistSum &h, float d)
     h.pc0 /= d; h.pc1 /= d; h.pc2 /= d; h.pm0 /= d; h.pm1 /= d; h.plen /= d;
 }
 
+// History clamp (include/svgf.h: svgf_set_history_clamp; variance clipping): the gathered history colour is clamped, per channel,
+// to mean +- k * sigma of the CURRENT frame's colour over the (2R+1)^2 window around the pixel, before the blend.  Normative
+// arithmetic: taps (x+xx, y+yy) with yy outer and xx inner, only those inside the image (n = their count, centre included);
+// s = sum v; m = s / n; q = sum (v - m)(v - m), the product rounded and then added; sd = sqrtf(q / n); lo = m - k sd, hi = m + k sd.
+// Two passes on purpose: E[x^2] - E[x]^2 cancels on flat regions.  Comparisons, not fminf / fmaxf: a NaN history value or NaN
+// bounds leave the value as it is.
+// c0 / c1 / c2: the pixel's own entry in the three colour planes of a staged tile with row pitch PITCH (LDS; the entries of taps
+// outside the image are never read).  Moments, length and validity are not touched.
+__device__ __forceinline__ float svgf_clamp_to_box(float pc, float m, float q, float n, float k)
+{
+#pragma clang fp contract(off)
+    const float sd = sqrtf(q / n);
+    const float ksd = k * sd;
+    const float lo = m - ksd, hi = m + ksd;
+    if (pc < lo) pc = lo;
+    if (pc > hi) pc = hi;
+    return pc;
+}
+template <int R, int PITCH>
+__device__ __forceinline__ void svgf_history_clamp(SvgfHistSum &h, const float *c0, const float *c1, const float *c2,
+                                                   int x, int y, int W, int H, float k)
+{
+#pragma clang fp contract(off)
+    bool in_y[2 * R + 1], in_x[2 * R + 1];
+#pragma unroll
+    for (int d = -R; d <= R; d++) {
+        in_y[d + R] = (unsigned)(y + d) < (unsigned)H;
+        in_x[d + R] = (unsigned)(x + d) < (unsigned)W;
+    }
+    float n = 0.0f, s0 = 0.0f, s1 = 0.0f, s2 = 0.0f;
+#pragma unroll
+    for (int yy = -R; yy <= R; yy++)
+#pragma unroll
+        for (int xx = -R; xx <= R; xx++)
+            if (in_y[yy + R] && in_x[xx + R]) {
+                const int o = yy * PITCH + xx;
+                s0 += c0[o]; s1 += c1[o]; s2 += c2[o];
+                n += 1.0f;
+            }
+    const float m0 = s0 / n, m1 = s1 / n, m2 = s2 / n;
+    float q0 = 0.0f, q1 = 0.0f, q2 = 0.0f;
+#pragma unroll
+    for (int yy = -R; yy <= R; yy++)
+#pragma unroll
+        for (int xx = -R; xx <= R; xx++)
+            if (in_y[yy + R] && in_x[xx + R]) {
+                const int o = yy * PITCH + xx;
+                const float d0 = c0[o] - m0, d1 = c1[o] - m1, d2 = c2[o] - m2;
+                q0 += d0 * d0; q1 += d1 * d1; q2 += d2 * d2;
+            }
+    h.pc0 = svgf_clamp_to_box(h.pc0, m0, q0, n, k);
+    h.pc1 = svgf_clamp_to_box(h.pc1, m1, q1, n, k);
+    h.pc2 = svgf_clamp_to_box(h.pc2, m2, q2, n, k);
+}
+
 // The accumulated pixel.  `valid`: a usable history value (pc*, pm*, plen: interpolated colour, moments, length) was found.
 struct SvgfTemporalOut { float4 cv; float2 mom; int hlen; };
 __device__ __forceinline__ SvgfTemporalOut svgf_temporal_blend(const TemporalArgs &a, float cr, float cg, float cb, float lum, int N,

@@ -400,6 +400,22 @@ int svgf_motion_reproject(int device, void *motion_out_dev, int motion_format, c
                           const SvgfCamera *prev_cam, const float reproj_scale[2], const float *geom_xf_dev, int n_geoms,
                           void *stream);
 
+/* ---- "next" row f6: history clamp of the temporal pass (added after 0.9; probe the symbol) ------------------------
+ * Variance clipping: where the temporal pass found a usable history value, its COLOUR is clamped per channel to
+ * mean +- sigma_scale * sigma of the current frame's in_rgb over the (2 radius + 1)^2 window around the pixel, before the blend.
+ * History whose shading is no longer plausible (a shadow that moved on, a light switched) stops ghosting; moments, history
+ * length and validity are untouched.  Normative arithmetic, float32 without contraction: taps (x+xx, y+yy), yy outer, xx inner,
+ * inside the image only (n of them, centre included); s = sum v; m = s / n; q = sum (v - m)(v - m); sd = sqrtf(q / n);
+ * lo = m - k sd; hi = m + k sd; if (pc < lo) pc = lo; if (pc > hi) pc = hi (NaN history or bounds: unchanged).
+ * radius 0 = off (the default), 1..3; sigma_scale finite and >= 0; otherwise SVGF_ERR_INVALID_ARG, as for a NULL context.
+ * Configuration of the context, not history: svgf_reset keeps it.  Read when a frame is enqueued, by all four svgf_denoise*
+ * entry points and every inputs_ready mode; frames with temporal_enable == 0 ignore it.  Host state only, no device work.
+ * (A clamped temporal frame on a context of more than 262140 rows answers SVGF_ERR_UNSUPPORTED.)
+ * INTEGRATION.md 5b says which values to start from. */
+int svgf_set_history_clamp(svgf_ctx *ctx, int radius, float sigma_scale);
+/* added after 0.9; probe the symbol.  Either pointer may be NULL. */
+int svgf_get_history_clamp(const svgf_ctx *ctx, int *radius, float *sigma_scale);
+
 /* ---- "next" row f2: the step right after denoise() ------------------------------------------------
  * svgf_display_pack: reference sendTwoImagesToPBO (src/pathtrace.cu:45-77, launched at :446): `left` (the 1-spp
  *   image) and `right` (the denoised image), both packed rgb floats in device memory, side by side into a

@@ -35,6 +35,8 @@ def main():
     ap.add_argument("--planar", action="store_true", help="G-buffer handed over as planes (svgf_denoise_planar), static scene")
     ap.add_argument("--motion", choices=["coord", "delta", "delta16"], default=None, help="the temporal pass reads per-pixel motion vectors in this format "
                     "(svgf_denoise_motion; the plane is written once by svgf_motion_reproject for the static camera) instead of projecting through the previous camera")
+    ap.add_argument("--clamp", default=None, metavar="R[,K]", help="svgf_set_history_clamp(R, K) on the context before the first frame (K defaults to 1): "
+                    "the temporal pass runs its clamped kernel of radius R")
     ap.add_argument("--sustain", type=float, default=0.0, help="seconds of back-to-back frames in front of every measurement (the sustained clock / "
                     "power state bench.py measures in, DESIGN.md 6.2); 0 = measure from wherever the GPU is (cold after start-up)")
     ap.add_argument("--telemetry-json", default=None, help="append one JSON line per variant: {variant, frame_us, telemetry summary} (the A/B scripts' clock check)")
@@ -53,6 +55,9 @@ def main():
     for v in [int(x) for x in a.variants.split(",")]:
         d = pkg.Denoiser(W, H, 0, experiments=v in (5, 6), pipelined=a.overlap != 0)      # parked variants live in libsvgf_hip_exp.so
         p = pkg.reference_defaults().set(temporal_enable=1, spatial_enable=1, atrous_nlevel=a.nlevel, kernel_variant=v, inputs_ready=a.overlap, blur_variance=a.blur)
+        if a.clamp:
+            rk = a.clamp.split(",")
+            d.set_history_clamp(int(rk[0]), float(rk[1]) if len(rk) > 1 else 1.0)
         if a.planar:      # both plane sets (they alternate with the history) get the static scene's G-buffer; d.denoise then means denoise_planar
             cam_dict = pkg.synth.camera_for_frame(0, False)
             for _ in range(2):
