@@ -36,7 +36,7 @@ EXPORTS = ["svgf_version", "svgf_params_default", "svgf_create", "svgf_destroy",
            "svgf_sync_stream", "svgf_build_has_experiments", "svgf_is_pipelined", "svgf_create_ex", "svgf_enable_pipeline",
            "svgf_pipeline_status", "svgf_planar_gbuffer_stream", "svgf_streams_overlap",
            "svgf_denoise_motion", "svgf_denoise_planar_motion", "svgf_motion_reproject",
-           "svgf_set_history_clamp", "svgf_get_history_clamp"]
+           "svgf_set_history_clamp", "svgf_get_history_clamp", "svgf_set_object_motion", "svgf_get_object_motion"]
 CREATE_PIPELINED = 1
 # motion plane formats (svgf_denoise_motion): absolute previous coordinate, delta in float32, delta in float16
 MOTION_PREV_COORD_F32, MOTION_DELTA_F32, MOTION_DELTA_F16 = 1, 2, 3
@@ -175,6 +175,8 @@ def load_library(path: str | None = None, experiments: bool = False):
     lib.svgf_motion_reproject.argtypes = [ip, vp, ip, vp, vp, vp, ip, ip, C.POINTER(SvgfCamera), C.POINTER(C.c_float), vp, ip, vp]
     lib.svgf_set_history_clamp.argtypes = [vp, ip, C.c_float]
     lib.svgf_get_history_clamp.argtypes = [vp, C.POINTER(ip), C.POINTER(C.c_float)]
+    lib.svgf_set_object_motion.argtypes = [vp, vp, ip]
+    lib.svgf_get_object_motion.argtypes = [vp, C.POINTER(vp), C.POINTER(ip)]
     lib.svgf_denoise_host.argtypes = [vp, vp, vp, vp, C.POINTER(SvgfCamera), C.POINTER(SvgfParams)]
     lib.svgf_sync.argtypes = [vp]
     lib.svgf_sync_stream.argtypes = [vp, vp]
@@ -382,6 +384,22 @@ class Denoiser:
         r, k = C.c_int(), C.c_float()
         self._check(self.lib.svgf_get_history_clamp(self.h, C.byref(r), C.byref(k)), "svgf_get_history_clamp")
         return int(r.value), float(k.value)
+
+    def set_object_motion(self, geom_xf, n_geoms: int | None = None):
+        """svgf_set_object_motion: geom_xf is a contiguous device float32[n, 12] tensor (or a raw pointer with n_geoms) of 3x4
+        row-major maps, this frame's world space -> the previous frame's, indexed by geomId; None = off.  The temporal pass tests
+        a tap's history against the pixel's normal and position moved by its object's map, and without a motion plane looks the
+        history up where the moved position projects.  The context keeps the POINTER: the tensor must stay alive, and is
+        refreshed in place on the frame's stream before each frame.  Survives reset()."""
+        if n_geoms is None:
+            n_geoms = 0 if geom_xf is None else int(geom_xf.numel()) // 12
+        self._check(self.lib.svgf_set_object_motion(self.h, _ptr(geom_xf), int(n_geoms)), "svgf_set_object_motion")
+
+    def object_motion(self) -> tuple[int | None, int]:
+        """(device pointer or None, n_geoms) as set by set_object_motion(); (None, 0) on a fresh context."""
+        ptr, n = C.c_void_p(), C.c_int()
+        self._check(self.lib.svgf_get_object_motion(self.h, C.byref(ptr), C.byref(n)), "svgf_get_object_motion")
+        return ptr.value, int(n.value)
 
     def read_state(self, which: int) -> np.ndarray:
         n = self.width * self.height

@@ -7,6 +7,7 @@
 //   * variance is never updated in place: each a-trous level reads {colour,variance} plane A and writes plane B,
 //     which is the "snapshot" semantics the parity contract fixes (SURVEY.md §7 hard parts, §8c).
 #include <hip/hip_runtime.h>
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -91,6 +92,9 @@ struct svgf_ctx {
     // svgf_set_history_clamp: configuration, not history (svgf_reset keeps it); read by plan_frame when a frame is enqueued
     int clamp_radius;      // 0 = off
     float clamp_k;
+    // svgf_set_object_motion: configuration like the clamp; the pointer and count are read by plan_frame, the table by the temporal kernel
+    const float *xf_dev;   // null or xf_n == 0: off
+    int xf_n;
     // state capture for tests
     int capture;
     float4 *cv_capture;
@@ -411,6 +415,34 @@ extern "C" int svgf_get_history_clamp(const svgf_ctx *c, int *radius, float *sig
     if (!c) return SVGF_ERR_INVALID_ARG;
     if (radius) *radius = c->clamp_radius;
     if (sigma_scale) *sigma_scale = c->clamp_k;
+    return SVGF_OK;
+}
+
+// Per-object rigid motion of the temporal pass (include/svgf.h).  Host state only, like the clamp: the table is the caller's memory.
+extern "C" int svgf_set_object_motion(svgf_ctx *c, const float *geom_xf_dev, int n_geoms)
+{
+    if (!c) return SVGF_ERR_INVALID_ARG;
+    if (n_geoms < 0) {
+        snprintf(c->err, sizeof(c->err), "svgf_set_object_motion: n_geoms %d is negative", n_geoms);
+        return SVGF_ERR_INVALID_ARG;
+    }
+    if (!geom_xf_dev && n_geoms > 0) {
+        snprintf(c->err, sizeof(c->err), "svgf_set_object_motion: null table with n_geoms %d", n_geoms);
+        return SVGF_ERR_INVALID_ARG;
+    }
+    if ((uintptr_t)geom_xf_dev & 15) {      // the kernel loads a row of a map as one 16-byte value
+        snprintf(c->err, sizeof(c->err), "svgf_set_object_motion: the table at %p is not 16-byte aligned", (const void *)geom_xf_dev);
+        return SVGF_ERR_INVALID_ARG;
+    }
+    c->xf_dev = geom_xf_dev; c->xf_n = n_geoms;
+    return SVGF_OK;
+}
+
+extern "C" int svgf_get_object_motion(const svgf_ctx *c, const float **geom_xf_dev, int *n_geoms)
+{
+    if (!c) return SVGF_ERR_INVALID_ARG;
+    if (geom_xf_dev) *geom_xf_dev = c->xf_dev;
+    if (n_geoms) *n_geoms = c->xf_n;
     return SVGF_OK;
 }
 
@@ -885,6 +917,13 @@ static int plan_frame(svgf_ctx *c, void *out_rgb_dev, const void *in_rgb_dev, co
         return SVGF_ERR_UNSUPPORTED;
     }
 #endif
+    const bool xform = c->xf_dev && c->xf_n > 0 && p->temporal_enable;      // svgf_set_object_motion (a non-temporal frame tests no history)
+#ifdef SVGF_BUILD_EXPERIMENTS
+    if (xform && (p->kernel_variant == 6 || c->use_split_fused)) {
+        snprintf(c->err, sizeof(c->err), "svgf_denoise: the parked fused temporal kernels (kernel_variant 6, split_fused) take no object motion table (svgf_set_object_motion)");
+        return SVGF_ERR_UNSUPPORTED;
+    }
+#endif
     const float *in = (const float *)in_rgb_dev, *g = (const float *)gbuffer_dev;
     pl.out = (float *)out_rgb_dev; pl.s_user = (hipStream_t)stream; pl.cap_id = 0;
     // Pipelined frames (see svgf_ctx::pipelined).  The promise behind inputs_ready = 1: at call time the inputs are complete (and stay
@@ -970,8 +1009,9 @@ static int plan_frame(svgf_ctx *c, void *out_rgb_dev, const void *in_rgb_dev, co
         t.dump = c->dump; t.arena = c->arena; t.arena_bytes = c->arena_bytes;
         if (motion) { t.motion = motion_dev; t.motion_format = motion_format; }
         if (clamp) { t.clamp_radius = c->clamp_radius; t.clamp_k = c->clamp_k; }
+        if (xform) { t.xf = c->xf_dev; t.n_geoms = c->xf_n; }
 #ifdef SVGF_BUILD_EXPERIMENTS      // parked: the temporal pass in the first level's loaders, DESIGN.md 5.8
-        if (!motion && !clamp && cascade && (p->kernel_variant == 0 || p->kernel_variant == 6) && !p->paper_steps && p->spatial_variance_frames <= 0)
+        if (!motion && !clamp && !xform && cascade && (p->kernel_variant == 0 || p->kernel_variant == 6) && !p->paper_steps && p->spatial_variance_frames <= 0)
             pl.fused = atrous_fused_supported(probe, t) && (p->kernel_variant == 6 || fuse_pays(c, probe));
 #endif
     } else if (g && cascade && (p->kernel_variant == 0 || p->kernel_variant == 6) && !p->paper_steps) {

@@ -132,6 +132,8 @@ struct TemporalArgs {
     int motion_format;        // SVGF_MOTION_* layout, read INSTEAD of projecting pos through M; null: the camera path
     int clamp_radius;         // svgf_set_history_clamp: 0 launches k_temporal, which reads neither field; 1..3 the clamped kernels
     float clamp_k;            //   (history colour clamped to mean +- clamp_k * sigma of in_rgb's (2r+1)^2 window, svgf_temporal.h)
+    const float *xf;          // svgf_set_object_motion: n_geoms 3x4 row-major maps (16-byte aligned), this frame's world space -> the previous
+    int n_geoms;              //   frame's, applied to what the history tests compare (svgf_temporal.h); null / 0 launches the kernels without
 };
 
 // TemporalArgs::motion_format, the values of include/svgf.h's SVGF_MOTION_* (svgf_api.hip asserts the equality)
@@ -140,7 +142,8 @@ struct TemporalArgs {
 #define SVGF_MOTION_FMT_D32   2      // SVGF_MOTION_DELTA_F32
 #define SVGF_MOTION_FMT_D16   3      // SVGF_MOTION_DELTA_F16
 // motion == null launches the camera-path kernel; otherwise the instantiation of motion_format (hipErrorInvalidValue if unknown);
-// clamp_radius 1..3: the clamped instantiation of the same (svgf_kernels.hip: k_temporal_clamped)
+// clamp_radius 1..3: the clamped instantiation of the same (svgf_kernels.hip: k_temporal_clamped); xf with n_geoms > 0: the
+// object-motion instantiation of either
 hipError_t launch_temporal(const TemporalArgs &a, hipStream_t s);
 bool       temporal_motion_format_known(int motion_format);
 bool       temporal_clamp_supported(int W, int H);      // images the clamped kernels can be launched on (H <= 262140)

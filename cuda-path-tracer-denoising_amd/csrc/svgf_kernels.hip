@@ -57,7 +57,9 @@ template <int R> struct ClampTile {
 
 // MOTION (SVGF_MOTION_FMT_*): 0 projects the pixel's position through the previous camera; the others read the previous-frame
 // coordinate from the caller's plane in that format.  A template parameter: the camera path's kernel carries no trace of them.
-template <int BLOCK, int MOTION>
+// XF: the history tests (and the camera path's projection) use the pixel's normal and position moved by the caller's per-object maps
+// (svgf_set_object_motion); false: no trace of the table either.
+template <int BLOCK, int MOTION, bool XF>
 __global__ __launch_bounds__(BLOCK) void k_temporal(TemporalArgs a)
 {
 #pragma clang fp contract(off)
@@ -74,7 +76,7 @@ __global__ __launch_bounds__(BLOCK) void k_temporal(TemporalArgs a)
 // with its margin (DESIGN.md 5.1 has the reasons for the 2-D tile).  A tile row is 3 * PITCH consecutive floats of in_rgb: they are
 // loaded as such, one float per lane, and scattered into the three planes.  Nothing outside the image is read: those entries
 // are zero and svgf_history_clamp never looks at them.
-template <int BLOCK, int MOTION, int R>
+template <int BLOCK, int MOTION, bool XF, int R>
 __global__ __launch_bounds__(BLOCK) void k_temporal_clamped(TemporalArgs a)
 {
 #pragma clang fp contract(off)
@@ -99,14 +101,14 @@ __global__ __launch_bounds__(BLOCK) void k_temporal_clamped(TemporalArgs a)
 #include "svgf_temporal_pixel.inc.h"
 }
 
-template <int MOTION>
+template <int MOTION, bool XF>
 static hipError_t launch_temporal_clamped(const TemporalArgs &a, hipStream_t s)
 {
     const dim3 grid(div_up(a.W, SVGF_CLAMP_TILE_W), div_up(a.H, SVGF_CLAMP_TILE_H)), block(SVGF_BLOCK);
     switch (a.clamp_radius) {
-    case 1: SVGF_LAUNCH_KERNEL((k_temporal_clamped<SVGF_BLOCK, MOTION, 1>), grid, block, 0, s, a); break;
-    case 2: SVGF_LAUNCH_KERNEL((k_temporal_clamped<SVGF_BLOCK, MOTION, 2>), grid, block, 0, s, a); break;
-    case 3: SVGF_LAUNCH_KERNEL((k_temporal_clamped<SVGF_BLOCK, MOTION, 3>), grid, block, 0, s, a); break;
+    case 1: SVGF_LAUNCH_KERNEL((k_temporal_clamped<SVGF_BLOCK, MOTION, XF, 1>), grid, block, 0, s, a); break;
+    case 2: SVGF_LAUNCH_KERNEL((k_temporal_clamped<SVGF_BLOCK, MOTION, XF, 2>), grid, block, 0, s, a); break;
+    case 3: SVGF_LAUNCH_KERNEL((k_temporal_clamped<SVGF_BLOCK, MOTION, XF, 3>), grid, block, 0, s, a); break;
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
@@ -115,31 +117,37 @@ static hipError_t launch_temporal_clamped(const TemporalArgs &a, hipStream_t s)
 // the clamped kernels' grid has one row of workgroups per SVGF_CLAMP_TILE_H image rows (grid.y <= 65535)
 bool temporal_clamp_supported(int W, int H) { (void)W; return H <= 65535 * SVGF_CLAMP_TILE_H; }
 
-hipError_t launch_temporal(const TemporalArgs &a, hipStream_t s)
+template <bool XF>
+static hipError_t launch_temporal_xf(const TemporalArgs &a, hipStream_t s)
 {
     if (a.clamp_radius != 0) {
         if (!temporal_clamp_supported(a.W, a.H)) return hipErrorInvalidValue;
-        if (!a.motion) return launch_temporal_clamped<SVGF_MOTION_FMT_NONE>(a, s);
+        if (!a.motion) return launch_temporal_clamped<SVGF_MOTION_FMT_NONE, XF>(a, s);
         switch (a.motion_format) {
-        case SVGF_MOTION_FMT_COORD: return launch_temporal_clamped<SVGF_MOTION_FMT_COORD>(a, s);
-        case SVGF_MOTION_FMT_D32:   return launch_temporal_clamped<SVGF_MOTION_FMT_D32>(a, s);
-        case SVGF_MOTION_FMT_D16:   return launch_temporal_clamped<SVGF_MOTION_FMT_D16>(a, s);
+        case SVGF_MOTION_FMT_COORD: return launch_temporal_clamped<SVGF_MOTION_FMT_COORD, XF>(a, s);
+        case SVGF_MOTION_FMT_D32:   return launch_temporal_clamped<SVGF_MOTION_FMT_D32, XF>(a, s);
+        case SVGF_MOTION_FMT_D16:   return launch_temporal_clamped<SVGF_MOTION_FMT_D16, XF>(a, s);
         default: return hipErrorInvalidValue;
         }
     }
     const long long n = (long long)a.W * a.H;
     const dim3 grid(div_up(n, SVGF_BLOCK)), block(SVGF_BLOCK);
     if (!a.motion) {
-        SVGF_LAUNCH_KERNEL((k_temporal<SVGF_BLOCK, SVGF_MOTION_FMT_NONE>), grid, block, 0, s, a);
+        SVGF_LAUNCH_KERNEL((k_temporal<SVGF_BLOCK, SVGF_MOTION_FMT_NONE, XF>), grid, block, 0, s, a);
         return hipGetLastError();
     }
     switch (a.motion_format) {
-    case SVGF_MOTION_FMT_COORD: SVGF_LAUNCH_KERNEL((k_temporal<SVGF_BLOCK, SVGF_MOTION_FMT_COORD>), grid, block, 0, s, a); break;
-    case SVGF_MOTION_FMT_D32:   SVGF_LAUNCH_KERNEL((k_temporal<SVGF_BLOCK, SVGF_MOTION_FMT_D32>), grid, block, 0, s, a); break;
-    case SVGF_MOTION_FMT_D16:   SVGF_LAUNCH_KERNEL((k_temporal<SVGF_BLOCK, SVGF_MOTION_FMT_D16>), grid, block, 0, s, a); break;
+    case SVGF_MOTION_FMT_COORD: SVGF_LAUNCH_KERNEL((k_temporal<SVGF_BLOCK, SVGF_MOTION_FMT_COORD, XF>), grid, block, 0, s, a); break;
+    case SVGF_MOTION_FMT_D32:   SVGF_LAUNCH_KERNEL((k_temporal<SVGF_BLOCK, SVGF_MOTION_FMT_D32, XF>), grid, block, 0, s, a); break;
+    case SVGF_MOTION_FMT_D16:   SVGF_LAUNCH_KERNEL((k_temporal<SVGF_BLOCK, SVGF_MOTION_FMT_D16, XF>), grid, block, 0, s, a); break;
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
+}
+
+hipError_t launch_temporal(const TemporalArgs &a, hipStream_t s)
+{
+    return (a.xf && a.n_geoms > 0) ? launch_temporal_xf<true>(a, s) : launch_temporal_xf<false>(a, s);
 }
 
 bool temporal_motion_format_known(int f) { return f == SVGF_MOTION_FMT_COORD || f == SVGF_MOTION_FMT_D32 || f == SVGF_MOTION_FMT_D16; }

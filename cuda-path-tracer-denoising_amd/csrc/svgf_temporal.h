@@ -103,6 +103,30 @@ __device__ __forceinline__ SvgfPrevCoord svgf_motion_prev_coord(const TemporalAr
     return c;
 }
 
+// Object motion (include/svgf.h: svgf_set_object_motion): the pixel's position and normal moved into the previous frame's world space
+// by its object's rigid map M = xf[gid] (3x4 row-major; the caller has checked 0 <= gid < n_geoms).  Normative arithmetic, the
+// position's being k_motion_reproject's own sequence: q[r] = ((M[4r] px + M[4r+1] py) + M[4r+2] pz) + M[4r+3]; the normal takes the
+// linear block only and is not renormalised: m[r] = (M[4r] nx + M[4r+1] ny) + M[4r+2] nz.  Every float is a defined input.
+// A row is one 16-byte load (the table is 16-byte aligned, a map is 48 bytes); geomId is almost wave-uniform and the table a few
+// cache lines, so the three loads of a wave touch one or two lines of L1 / L2.
+__device__ __forceinline__ void svgf_to_prev_space(const float *xf, int gid, float &px, float &py, float &pz, float &nx, float &ny, float &nz)
+{
+#pragma clang fp contract(off)
+    const float4 *m = (const float4 *)xf + 3 * (size_t)gid;
+    float q[3], n[3];
+#pragma unroll
+    for (int r = 0; r < 3; r++) {
+        const float4 row = m[r];
+        float t0 = row.x * px + row.y * py;
+        t0 = t0 + row.z * pz;
+        q[r] = t0 + row.w;
+        float t1 = row.x * nx + row.y * ny;
+        n[r] = t1 + row.z * nz;
+    }
+    px = q[0]; py = q[1]; pz = q[2];
+    nx = n[0]; ny = n[1]; nz = n[2];
+}
+
 // bounds part of isReprjValid (:173-176): texel index of the tap at float coordinate (qx, qy), -1 when it is outside the
 // screen (a NaN coordinate is DEFINED as outside; the reference would index texel (int)NaN)
 __device__ __forceinline__ int svgf_tap_index(const TemporalArgs &a, float qx, float qy)

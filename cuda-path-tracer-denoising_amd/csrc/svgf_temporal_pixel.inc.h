@@ -5,6 +5,9 @@
 //   p      int, the pixel (x + y * W, inside the image)
 //   MOTION SVGF_MOTION_FMT_*: 0 projects the pixel's position through the previous camera; the others read the previous-frame
 //          coordinate from the caller's plane in that format.  A template parameter: the camera path's kernel carries no trace of them.
+//   XF     bool, svgf_set_object_motion: the tests that decide whether a tap's history may be used compare it with the pixel's normal
+//          and position moved into the previous frame's space by a.xf[geomId]; on the camera path (MOTION 0) the moved position
+//          is also the one projected.  A template parameter like MOTION: false compiles to the kernels that knew no table.
 //   R      constexpr int, radius of the history clamp; 0 = none: `tile` is not looked at
 //   tile   ClampTile<R>
 // No include guard: it is a function body.
@@ -38,9 +41,13 @@
     bool valid = false;
     SvgfHistSum hs = { 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f };
     if (N > 0 && gid != -1) {
+        float tnx = nx, tny = ny, tnz = nz, tpx = px, tpy = py, tpz = pz;   // what the taps are tested against (the planes above keep the true values)
+        if constexpr (XF) {
+            if (gid >= 0 && gid < a.n_geoms) svgf_to_prev_space(a.xf, gid, tpx, tpy, tpz, tnx, tny, tnz);
+        }
         SvgfReproj rp;                                                // previous-frame pixel coordinate (:198-209)
         if constexpr (MOTION == SVGF_MOTION_FMT_NONE) {
-            rp = svgf_reproject(a, px, py, pz);
+            rp = svgf_reproject(a, tpx, tpy, tpz);
         } else {
             const SvgfPrevCoord c = svgf_motion_prev_coord<MOTION>(a, p);
             rp = svgf_reproj_from_coord(c.x, c.y);
@@ -51,7 +58,7 @@
         int q4[4];
 #pragma unroll
         for (int k = 0; k < 4; k++) {
-            q4[k] = reproj_valid_pos(a, reproj_valid(a, fx + (float)(k & 1), fy + (float)(k >> 1), gid, nx, ny, nz), px, py, pz);
+            q4[k] = reproj_valid_pos(a, reproj_valid(a, fx + (float)(k & 1), fy + (float)(k >> 1), gid, tnx, tny, tnz), tpx, tpy, tpz);
             valid = valid && (q4[k] >= 0);
         }
 
@@ -74,7 +81,7 @@
                 for (int xx = -1; xx <= 1; xx++) {
                     // the four taps with xx, yy in {0, 1} are the bilinear taps tested above: same arguments, same answer
                     const int q = (xx >= 0 && yy >= 0) ? q4[xx + 2 * yy]
-                                                       : reproj_valid_pos(a, reproj_valid(a, fx + (float)xx, fy + (float)yy, gid, nx, ny, nz), px, py, pz);
+                                                       : reproj_valid_pos(a, reproj_valid(a, fx + (float)xx, fy + (float)yy, gid, tnx, tny, tnz), tpx, tpy, tpz);
                     if (q >= 0) {
                         const float4 ch = a.cv_hist[q];
                         const float2 mh = a.mom_hist[q];

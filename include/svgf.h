@@ -416,6 +416,35 @@ int svgf_set_history_clamp(svgf_ctx *ctx, int radius, float sigma_scale);
 /* added after 0.9; probe the symbol.  Either pointer may be NULL. */
 int svgf_get_history_clamp(const svgf_ctx *ctx, int *radius, float *sigma_scale);
 
+/* ---- "next" row f7: rigid object motion in the temporal pass (added after 0.9; probe the symbol) -------------------
+ * Gives the temporal pass the per-object rigid maps of the current frame, the table svgf_motion_reproject takes:
+ * geom_xf_dev is device memory of n_geoms x 12 floats, 3x4 row-major, indexed by geomId; each map takes this frame's world
+ * space to the previous frame's, xf_prev[g] * inverse(xf_cur[g]).  A geomId outside [0, n_geoms) is unmoved.  NULL or
+ * n_geoms == 0 = off (the default).  SVGF_ERR_INVALID_ARG (setting unchanged) for a NULL context, n_geoms < 0, NULL with
+ * n_geoms > 0 and a pointer that is not 16-byte aligned (a row of a map is loaded as one 16-byte value).
+ * Normative arithmetic, float32 without contraction, per pixel with 0 <= geomId < n_geoms that looks history up, M = X[geomId],
+ * p / n the texel's position / normal:
+ *   q[r] = ((M[4r] px + M[4r+1] py) + M[4r+2] pz) + M[4r+3]      (svgf_motion_reproject's own sequence)
+ *   m[r] = (M[4r] nx + M[4r+1] ny) + M[4r+2] nz                  (linear block only, not renormalised)
+ * every other pixel: q = p, m = n, through a branch (no multiplication by an identity).  Effect:
+ *   1. svgf_denoise / svgf_denoise_planar (no motion plane): history is looked up at the projection of q through the previous
+ *      camera — bit for bit the coordinate svgf_motion_reproject(X) would have written and svgf_denoise_motion read.
+ *      With a motion plane the plane gives the coordinate and the table serves the two tests only.
+ *   2. the normal test of all nine taps compares the tap's previous normal with m,
+ *   3. the position test (SvgfParams::reproj_position_tol > 0) the tap's previous position with q.
+ * Nothing else moves: the planes the pass keeps for the next frame hold the true normal and position; blend, moments, clamp
+ * and every a-trous level are as they are.  The maps must be rigid (rotation + translation; not checked).  Every float in the
+ * table is a defined input: the arithmetic runs as written and the existing predicates see its results.
+ * Configuration of the context, like the history clamp: svgf_reset keeps it; host state only, no device work.  Pointer and
+ * count are read when a frame is enqueued (a frame recorded into a graph keeps what it was recorded with); the CONTENTS are
+ * read by the temporal kernel when it runs: refresh the table on the frame's stream before each frame.  inputs_ready = 1
+ * covers the table (complete at call time, untouched until the frame is done).  Honoured by all four svgf_denoise* entry
+ * points, svgf_denoise_host and every inputs_ready mode; frames with temporal_enable == 0 ignore it.
+ * INTEGRATION.md 5c says when to use the table alone and when table + plane. */
+int svgf_set_object_motion(svgf_ctx *ctx, const float *geom_xf_dev, int n_geoms);
+/* added after 0.9; probe the symbol.  Either pointer may be NULL. */
+int svgf_get_object_motion(const svgf_ctx *ctx, const float **geom_xf_dev, int *n_geoms);
+
 /* ---- "next" row f2: the step right after denoise() ------------------------------------------------
  * svgf_display_pack: reference sendTwoImagesToPBO (src/pathtrace.cu:45-77, launched at :446): `left` (the 1-spp
  *   image) and `right` (the denoised image), both packed rgb floats in device memory, side by side into a

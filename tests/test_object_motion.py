@@ -1,0 +1,704 @@
+"""Rigid object motion in the temporal pass (include/svgf.h: svgf_set_object_motion / svgf_get_object_motion).
+
+The yardstick is tests/object_motion_model.py, a float32 numpy model of the whole temporal pass.  The oracle knows no table;
+the tests of section 2 pin the model three ways: to tests/history_clamp_model.py without a table, to the oracle's position test
+without a table, and to the oracle on texels whose normal and position were replaced by the moved ones (as far as that
+substitution reaches: two frames, the oracle keeps the substituted texels as its history).
+
+Bounds: every comparison of the kernel with the model is on the bits of every pixel (NaNs in the same place count as equal).
+Both sides perform the same float32 operations in the same order without contraction, and division and square root are
+correctly rounded on both: there is no arithmetic that may differ, so there is no tolerance to choose.  The one tolerance in
+this file, 1e-5 between kernel_variant 0 and 1 on whole frames, is the project's existing gate between its a-trous kernels
+(tests/test_parity_gpu.py, tests/test_history_clamp.py): the table changes their input, not them.  The fractions 0.10 / 0.95 of
+the turning block are the issue's (the oracle gives 0.00 / 1.00)."""
+import ctypes
+import os
+
+import numpy as np
+import pytest
+
+import history_clamp_model as hm
+import object_motion_model as om
+from conftest import ROOT, relerr
+
+F = np.float32
+COORD, D32, D16 = om.COORD, om.D32, om.D16
+SCENE = os.path.join(ROOT, "tests", "golden", "scenes", "box_room.txt")
+NEW_SYMBOLS = ("svgf_set_object_motion", "svgf_get_object_motion")
+STATES = ("hlen", "mom", "color", "variance", "acc")      # svgf_read_state 0..4
+TOLS = (0.0, 0.3)
+
+
+def same_bits(a, b):
+    a, b = np.asarray(a), np.asarray(b)
+    if a.shape != b.shape or a.dtype != b.dtype:
+        return False
+    if a.dtype.kind != "f":
+        return bool(np.array_equal(a, b))
+    na, nb = np.isnan(a), np.isnan(b)
+    return bool(np.array_equal(na, nb) and np.array_equal(a.view(np.uint32)[~na], b.view(np.uint32)[~nb]))
+
+
+def assert_frames_equal(got, ref, what):
+    """got: per frame the five states read from a context; ref: per frame the model's dict (acc = color with the spatial filter off)."""
+    assert len(got) == len(ref)
+    for f, (g, r) in enumerate(zip(got, ref)):
+        for name in STATES:
+            want = r["color" if name == "acc" else name]
+            bad = "" if same_bits(g[name], want) else f"{np.count_nonzero(~np.isclose(g[name], want, rtol=0, atol=0, equal_nan=True))} values differ"
+            assert not bad, f"{what}: {name}, frame {f}: {bad}"
+
+
+def temporal_only(pkg, **kw):
+    return pkg.reference_defaults().set(**{**dict(temporal_enable=1, spatial_enable=0), **kw})
+
+
+def scales(pkg, W, H):
+    """SvgfParams::reproj_scale that makes the reprojection exact at any aspect (as tests/test_history_clamp.py)."""
+    plx, ply = pkg.synth._pixel_length(W, H, 45.0)
+    return float(plx) * W / 2.0, float(ply) * H / 2.0
+
+
+def synth_params(pkg, W, H, **kw):
+    p = temporal_only(pkg, **kw)
+    p.reproj_scale[0], p.reproj_scale[1] = scales(pkg, W, H)
+    return p
+
+
+def rotation(axis, degrees):
+    a = np.deg2rad(degrees)
+    c, s = np.cos(a), np.sin(a)
+    return {"x": np.array([[1, 0, 0], [0, c, -s], [0, s, c]]), "y": np.array([[c, 0, s], [0, 1, 0], [-s, 0, c]]),
+            "z": np.array([[c, -s, 0], [s, c, 0], [0, 0, 1]])}[axis]
+
+
+# ---- inputs ---------------------------------------------------------------------------------------------------------------------------
+BAD_ROW = 6
+
+
+def mixed_table():
+    """Nine maps, indexed by the synthetic scene's geomIds 0..8: rotations of 0-12 degrees (svgf_normals_close rejects above about
+    5.7) with translations of 0-0.45 (around the position tolerance 0.3); row 0 is the exact identity, row 6 holds NaN and inf."""
+    spec = [("y", 0.0, (0.0, 0.0, 0.0)), ("y", 2.0, (0.05, 0.0, 0.0)), ("x", 4.0, (0.0, 0.02, 0.1)), ("z", 5.5, (0.0, 0.0, 0.0)),
+            ("y", 6.0, (0.2, 0.0, 0.0)), ("x", 8.0, (0.0, 0.0, -0.3)), ("y", 1.0, (0.0, 0.0, 0.0)), ("y", 12.0, (0.4, 0.1, 0.0)),
+            ("z", 0.0, (0.25, 0.0, 0.15))]
+    X = np.stack([np.concatenate([rotation(ax, deg), np.array(t)[:, None]], axis=1).reshape(-1) for ax, deg, t in spec]).astype(F)
+    X[BAD_ROW, 1], X[BAD_ROW, 7], X[BAD_ROW, 8] = np.nan, np.inf, -np.inf
+    return X
+
+
+def mixed_sequence(pkg, orc, W, H, n=4, finite=False):
+    """n frames of the synthetic scene under its moving camera with the texels of tests/test_motion_vectors.py::_texels_for_helper:
+    ray misses, ids beyond the table, non-finite and behind-the-camera positions.  Per frame (colour[H, W, 3], texels[H, W],
+    camera, view matrix).
+    finite: the same texels without the non-finite positions, for frames that run the a-trous levels.  A staged non-finite texel
+    switches a workgroup of the lane a-trous kernel to its careful loop, and that switch is raced by the loader which stages the
+    texel: the row computed meanwhile may round differently from run to run (tests/test_parity_gpu.py compares such frames bit
+    for bit "only without non-finite texels"), so two contexts agree exactly only on finite texels.  The temporal pass, which
+    is what this file tests, has no such race and is compared on the non-finite texels with the a-trous levels off."""
+    cache = mixed_sequence.__dict__.setdefault("cache", {})
+    if (W, H, n, finite) not in cache:
+        seq = []
+        for f in range(n):
+            col, gb, cam = pkg.synth.render_frame(W, H, f, seed=11, moving=True, noise_model="hash")
+            gb = gb.copy().reshape(H, W)
+            rng = np.random.default_rng(W * 1000 + H + 17 * f)
+            flat = gb.reshape(-1)
+            m = flat.size
+            flat["geomId"][rng.integers(0, m, max(1, m // 7))] = -1
+            flat["geomId"][rng.integers(0, m, max(1, m // 9))] = 40             # beyond the table: unmoved
+            if m > 4:
+                bad = rng.integers(0, m, 3)      # (drawn either way: the other texels are the same in both forms)
+                if not finite:
+                    flat["position"][bad] = (np.nan, np.inf, -1e30)
+                flat["position"][rng.integers(0, m, 2)] = (0.0, 5.0, 60.0)      # behind the camera
+            seq.append((np.asarray(col, F).reshape(H, W, 3), gb, cam, orc.view_matrix(pkg, cam)))
+        cache[(W, H, n, finite)] = seq
+    return cache[(W, H, n, finite)]
+
+
+def clean_sequence(pkg, orc, W, H, n=4):
+    """The same frames with the texels as rendered (finite positions), seed 31: the sequence of tests/test_history_clamp.py."""
+    cache = clean_sequence.__dict__.setdefault("cache", {})
+    if (W, H, n) not in cache:
+        seq = []
+        for f in range(n):
+            col, gb, cam = pkg.synth.render_frame(W, H, f, seed=31, moving=True, noise_model="hash")
+            seq.append((np.asarray(col, F).reshape(H, W, 3), gb.reshape(H, W), cam, orc.view_matrix(pkg, cam)))
+        cache[(W, H, n)] = seq
+    return cache[(W, H, n)]
+
+
+def mixed_model(pkg, orc, W, H, fmt, tol, radius=0, k=0.0):
+    """The model on mixed_sequence with mixed_table: fmt None = the camera path (the moved position projected through the previous
+    frame's camera); otherwise through the plane svgf_motion_reproject(X) writes in that format, converted as the header says."""
+    cache = mixed_model.__dict__.setdefault("cache", {})
+    key = (W, H, fmt, tol, radius, k)
+    if key not in cache:
+        seq, X = mixed_sequence(pkg, orc, W, H), mixed_table()
+        sx, sy = scales(pkg, W, H)
+        views = [seq[max(f - 1, 0)][3] for f in range(len(seq))]
+        coords = None
+        if fmt is not None:
+            coords = [om.coord_plane(om.motion_plane(views[f], W, H, seq[f][1], X, fmt, F(sx), F(sy)), fmt, W, H) for f in range(len(seq))]
+        cache[key] = om.run_sequence([(c, g) for c, g, _, _ in seq], coords=coords, tables=[X] * len(seq), views=views, scale=(sx, sy),
+                                     pos_tol=tol, radius=radius, k=k)
+    return cache[key]
+
+
+TURNING_OBJECT, TURN_DEG, SLIDE_X, TURN_FRAMES, SIDE = 7, 9.0, 1.0, 4, 96
+
+
+def block_sequence(pkg, n, slide_x, turn_deg):
+    """n frames of box_room at 96x96 under a static camera, the turned block (object 7) rotated by turn_deg about y and translated
+    by slide_x in x per frame.  Returns (camera, [(colour, texels, X float32[n_geoms, 12])]); X[g] = xf_prev[g] * inv_cur[g] composed
+    in float64 and rounded: this frame's world space to the previous frame's (frame 0: identities).  Computed once per session."""
+    cache = block_sequence.__dict__.setdefault("cache", {})
+    if (n, slide_x, turn_deg) not in cache:
+        sc = pkg.scene.parse_scene(open(SCENE).read())
+        cam = pkg.scene.camera_for_frame(sc, 0, False)
+        t0, r0 = tuple(sc.objects[TURNING_OBJECT]["trans"]), tuple(sc.objects[TURNING_OBJECT]["rotat"])
+        frames, prev = [], None
+        for f in range(n):
+            o = sc.objects[TURNING_OBJECT]
+            o["trans"] = (t0[0] + slide_x * f,) + t0[1:]
+            o["rotat"] = (r0[0], r0[1] + turn_deg * f, r0[2])
+            g = pkg.scene.geom_array(sc)
+            col, gb = pkg.scene.render_scene(SIDE, SIDE, f, g, cam, seed=3)
+            X = np.tile(np.eye(3, 4).reshape(-1), (len(g), 1))
+            if prev is not None:
+                for k in range(len(g)):
+                    a = np.vstack([prev[k]["xf"].astype(np.float64).reshape(3, 4), [0, 0, 0, 1]])
+                    b = np.vstack([g[k]["inv"].astype(np.float64).reshape(3, 4), [0, 0, 0, 1]])
+                    X[k] = (a @ b)[:3].reshape(-1)
+            frames.append((np.asarray(col, F).reshape(SIDE, SIDE, 3), gb.reshape(SIDE, SIDE), X.astype(F)))
+            prev = g
+        cache[(n, slide_x, turn_deg)] = (cam, frames)
+    return cache[(n, slide_x, turn_deg)]
+
+
+def turning_block_sequence(pkg):
+    """The issue's sequence: four frames, +9 degrees about y and +1.0 in x per frame."""
+    return block_sequence(pkg, TURN_FRAMES, SLIDE_X, TURN_DEG)
+
+
+def moving_block_sequence(pkg):
+    """The six frames of tests/test_history_clamp.py and tests/test_motion_vectors.py: +0.4 in x per frame, no rotation."""
+    return block_sequence(pkg, 6, 0.4, 0.0)
+
+
+def turning_block_model(pkg, orc, table, tol):
+    """table True: the feature (camera path, the table moves coordinate, normal and position).  False: f5 as it stands — the
+    coordinate from motion_plane(X), the tests on the true normal and position."""
+    cache = turning_block_model.__dict__.setdefault("cache", {})
+    if (table, tol) not in cache:
+        cam, frames = turning_block_sequence(pkg)
+        M = orc.view_matrix(pkg, cam)
+        fr = [(c, g) for c, g, _ in frames]
+        if table:
+            cache[(table, tol)] = om.run_sequence(fr, tables=[X for _, _, X in frames], views=[M] * len(fr), pos_tol=tol)
+        else:
+            coords = [om.motion_plane(M, SIDE, SIDE, gb, X, COORD) for _, gb, X in frames]
+            cache[(table, tol)] = om.run_sequence(fr, coords=coords, pos_tol=tol)
+    return cache[(table, tol)]
+
+
+def kept_fraction(hlen, gb):
+    """The fraction of the block's pixels whose history length is at least 2."""
+    block = gb["geomId"] == TURNING_OBJECT
+    assert np.count_nonzero(block) > 150
+    return float(np.count_nonzero(hlen[block] >= 2)) / float(np.count_nonzero(block))
+
+
+# ---- the GPU side ---------------------------------------------------------------------------------------------------------------------
+def _hip():
+    """The HIP runtime already loaded into this process (torch's), for plain host-to-device copies into raw pointers."""
+    for ln in open("/proc/self/maps"):
+        if "libamdhip64" in ln:
+            return ctypes.CDLL(ln.split()[-1])
+    raise RuntimeError("no HIP runtime loaded")
+
+
+def read_states(den):
+    return {name: den.read_state(k) for k, name in enumerate(STATES)}
+
+
+def run_gpu(pkg, den, frames, params, cams, leg="aos", plane_fmt=None, plane_tables=None):
+    """frames: [(colour, texels)]; cams: per frame.  The context's table is whatever the caller set.  plane_fmt: the history is
+    looked up through the plane svgf_motion_reproject writes in that format for the previous frame's camera, params' reproj_scale
+    and plane_tables[f] (None: the camera path).  Returns per frame the five states.  `leg`: aos | planar."""
+    import torch
+    H, W = frames[0][1].shape
+    den.set_capture(True)
+    out, res, keep = torch.empty((H, W, 3), dtype=torch.float32, device="cuda"), [], []
+    rs = (params.reproj_scale[0], params.reproj_scale[1])
+    for f, (col, gb) in enumerate(frames):
+        t_c = torch.from_numpy(np.ascontiguousarray(col, dtype=F)).cuda()
+        t_g = torch.from_numpy(np.ascontiguousarray(gb).view(np.uint8).reshape(-1).copy()).cuda()
+        mv = None
+        if plane_fmt is not None:
+            mv = torch.empty((H, W, 2), dtype=torch.float16 if plane_fmt == D16 else torch.float32, device="cuda")
+            t_x = None if plane_tables is None or plane_tables[f] is None else torch.from_numpy(np.ascontiguousarray(plane_tables[f])).cuda()
+            pkg.binding.motion_reproject(mv, W, H, cams[max(f - 1, 0)], gbuffer=t_g, motion_format=plane_fmt, reproj_scale=rs, geom_xf=t_x)
+            keep.append(t_x)
+        keep.append((t_c, t_g, mv))      # (a promised frame's inputs stay untouched until its work is done)
+        torch.cuda.synchronize()
+        if leg == "planar":
+            g = den.planar_gbuffer()
+            hip = _hip()
+            hip.hipMemcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
+            flat = np.ascontiguousarray(gb).reshape(-1)
+            for dst, arr in ((g.normal, flat["normal"]), (g.position, flat["position"]), (g.geom_id, flat["geomId"]),
+                             (g.albedo, (flat["albedo"] * flat["ialbedo"]).astype(F))):
+                arr = np.ascontiguousarray(arr)
+                assert hip.hipMemcpy(dst, arr.ctypes.data, arr.nbytes, 1) == 0
+            den.denoise_planar(out, t_c, cams[f], params, motion=mv, motion_format=plane_fmt or COORD)
+        else:
+            den.denoise(out, t_c, t_g, cams[f], params, motion=mv, motion_format=plane_fmt or COORD)
+        den.sync()
+        res.append(read_states(den))
+    return res
+
+
+def device_table(X):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(X, dtype=F)).cuda()
+
+
+# ---- 1. CPU: symbols and the NULL context ----------------------------------------------------------------------------------------------
+def test_symbols_are_exported_and_a_null_context_is_invalid(pkg):
+    lib = pkg.load_library()
+    for n in NEW_SYMBOLS:
+        assert hasattr(lib, n), n
+        assert n in pkg.binding.EXPORTS, n
+    assert lib.svgf_set_object_motion(None, None, 0) == -1
+    assert lib.svgf_set_object_motion(None, 4096, 3) == -1
+    ptr, n = ctypes.c_void_p(64), ctypes.c_int(7)
+    assert lib.svgf_get_object_motion(None, ctypes.byref(ptr), ctypes.byref(n)) == -1
+    assert lib.svgf_get_object_motion(None, None, None) == -1
+    assert (ptr.value, n.value) == (64, 7), "nothing is written on failure"
+    assert hasattr(pkg.Denoiser, "set_object_motion") and hasattr(pkg.Denoiser, "object_motion")
+
+
+# ---- 2. CPU: the model is a model --------------------------------------------------------------------------------------------------------
+def test_model_without_table_is_the_clamp_model_on_the_moving_block(pkg, orc):
+    """No table, tol 0, the six frames of tests/test_history_clamp.py's moving block, the history clamp off and on."""
+    cam, frames = moving_block_sequence(pkg)
+    M = orc.view_matrix(pkg, cam)
+    coords = [hm.motion_plane(M, SIDE, SIDE, gb, X, COORD) for _, gb, X in frames]
+    fr = [(c, g) for c, g, _ in frames]
+    for radius, k in ((0, 0.0), (2, 1.0)):
+        ref, got = hm.run_sequence(fr, coords, radius=radius, k=k), om.run_sequence(fr, coords=coords, radius=radius, k=k)
+        for f in range(len(fr)):
+            for name in ("hlen", "mom", "color", "variance"):
+                assert same_bits(got[f][name], ref[f][name]), f"radius {radius}: {name}, frame {f}"
+    # and its camera path is that model fed the plane of the substituted positions
+    cam_path = om.run_sequence(fr, tables=[X for _, _, X in frames], views=[M] * len(fr))
+    assert same_bits(cam_path[1]["hlen"], hm.run_sequence(fr, coords)[1]["hlen"]), "a pure translation leaves the normals alone"
+
+
+@pytest.mark.parametrize("tol", [0.3, 0.05])
+def test_model_position_test_is_the_oracle(pkg, orc, tol):
+    """No table, reproj_position_tol 0.3 and 0.05, four frames of synth.render_frame(67, 41, moving=True)."""
+    W, H = 67, 41
+    seq = clean_sequence(pkg, orc, W, H)
+    views = [seq[max(f - 1, 0)][3] for f in range(len(seq))]
+    ref = om.run_sequence([(c, g) for c, g, _, _ in seq], views=views, scale=scales(pkg, W, H), pos_tol=tol)
+    off = om.run_sequence([(c, g) for c, g, _, _ in seq], views=views, scale=scales(pkg, W, H))
+    p = synth_params(pkg, W, H, reproj_position_tol=tol)
+    o = orc.Oracle(pkg, W, H, threads=4)
+    try:
+        for f, (col, gb, cam, _) in enumerate(seq):
+            o.denoise(col, gb, cam, p)
+            assert same_bits(o.read_state(0), ref[f]["hlen"]), f"history length, frame {f}"
+            assert same_bits(o.read_state(1), ref[f]["mom"]), f"moments, frame {f}"
+            assert same_bits(o.read_state(2), ref[f]["color"]), f"colour history, frame {f}"
+    finally:
+        o.free()
+    assert ref[-1]["hlen"].max() == len(seq), "some history passes the position test"
+    assert not np.array_equal(ref[-1]["hlen"], off[-1]["hlen"]), "and some fails it alone"
+
+
+@pytest.mark.parametrize("tol", TOLS)
+def test_model_with_table_is_the_oracle_on_substituted_texels(pkg, orc, tol):
+    """Two frames of the turning, sliding block: the oracle is fed frame 1's texels with normal and position replaced by m and q."""
+    cam, frames = turning_block_sequence(pkg)
+    ref = turning_block_model(pkg, orc, True, tol)
+    p = temporal_only(pkg, reproj_position_tol=tol)
+    o = orc.Oracle(pkg, SIDE, SIDE, threads=4)
+    try:
+        for f, (col, gb, X) in enumerate(frames[:2]):
+            sub = gb.copy()
+            sub["position"] = om.apply_xf(X, gb["geomId"], gb["position"])
+            sub["normal"] = om.moved_normal(X, gb["geomId"], gb["normal"])
+            o.denoise(col, sub, cam, p)
+            assert same_bits(o.read_state(0), ref[f]["hlen"]), f"history length, frame {f}"
+            assert same_bits(o.read_state(1), ref[f]["mom"]), f"moments, frame {f}"
+            assert same_bits(o.read_state(2), ref[f]["color"]), f"colour history, frame {f}"
+    finally:
+        o.free()
+    assert kept_fraction(ref[1]["hlen"], frames[1][1]) >= 0.95
+
+
+# ---- 3. CPU: what the feature is for, on the model -----------------------------------------------------------------------------------------
+@pytest.mark.parametrize("tol", TOLS)
+def test_model_turning_block_loses_its_history_without_the_table_and_keeps_it_with(pkg, orc, tol):
+    _, frames = turning_block_sequence(pkg)
+    gb = frames[-1][1]
+    lost = kept_fraction(turning_block_model(pkg, orc, False, tol)[-1]["hlen"], gb)
+    kept = kept_fraction(turning_block_model(pkg, orc, True, tol)[-1]["hlen"], gb)
+    print(f"tol {tol}: block pixels {np.count_nonzero(gb['geomId'] == TURNING_OBJECT)}, history >= 2 on {lost:.3f} (plane, true normal and "
+          f"position), {kept:.3f} (table)")
+    assert lost <= 0.10
+    assert kept >= 0.95
+
+
+def test_model_inputs_of_the_gpu_suite_fall_on_both_sides_of_both_tests(pkg, orc):
+    """mixed_sequence / mixed_table at 67x41: the table changes what survives, the position test changes it again, pixels of the
+    row of NaN and inf never find history, and history survives somewhere."""
+    W, H = 67, 41
+    seq = mixed_sequence(pkg, orc, W, H)
+    on0, on3 = mixed_model(pkg, orc, W, H, None, 0.0), mixed_model(pkg, orc, W, H, None, 0.3)
+    views = [seq[max(f - 1, 0)][3] for f in range(len(seq))]
+    off = om.run_sequence([(c, g) for c, g, _, _ in seq], views=views, scale=scales(pkg, W, H))
+    last = seq[-1][1]["geomId"]
+    assert on0[-1]["hlen"].max() >= 3 and on3[-1]["hlen"].max() >= 3
+    assert not np.array_equal(on0[-1]["hlen"], off[-1]["hlen"])
+    assert not np.array_equal(on0[-1]["hlen"], on3[-1]["hlen"])
+    assert np.count_nonzero(last == BAD_ROW) > 0 and (on0[-1]["hlen"][last == BAD_ROW] == 1).all()
+    for g in (1, 2, 3):      # rotations below the normal test's threshold keep history
+        assert (on0[-1]["hlen"][last == g] > 1).any(), g
+    for g in (4, 7):         # 6 and 12 degrees: on a flat surface the previous normals are too far from the moved normal
+        assert (on0[-1]["hlen"][last == g] == 1).any(), g
+
+
+# ---- 4. GPU: HIP equals the model, bit for bit, on every pixel ----------------------------------------------------------------------------
+SIZES = [(1, 1), (5, 3), (67, 41), (257, 131)]
+LEGS = ["aos", "planar", "promised", "coord_f32", "delta_f32", "delta_f16", "clamped"]
+PLANE_LEGS = {"coord_f32": COORD, "delta_f32": D32, "delta_f16": D16}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("leg", LEGS)
+@pytest.mark.parametrize("W,H", SIZES)
+def test_hip_equals_the_model_on_every_pixel(pkg, orc, W, H, leg):
+    """Four frames under the moving camera with mixed_table set, at reproj_position_tol 0 and 0.3; one context per leg, reset
+    between the two runs.  The plane legs look history up through the plane svgf_motion_reproject(X) writes; the clamped leg
+    adds svgf_set_history_clamp(2, 1.0)."""
+    seq, X = mixed_sequence(pkg, orc, W, H), mixed_table()
+    frames, cams = [(c, g) for c, g, _, _ in seq], [c for _, _, c, _ in seq]
+    fmt = PLANE_LEGS.get(leg)
+    radius, k = (2, 1.0) if leg == "clamped" else (0, 0.0)
+    den = pkg.Denoiser(W, H, 0, pipelined=leg == "promised")
+    t_x = device_table(X)
+    try:
+        if leg == "promised" and den.pipeline_status() == 2:
+            pytest.skip("the context's two streams share a hardware queue: the promise is refused")
+        den.set_object_motion(t_x)
+        den.set_history_clamp(radius, k)
+        for tol in TOLS:
+            params = synth_params(pkg, W, H, reproj_position_tol=tol)
+            if leg == "promised":
+                params.inputs_ready = 1
+            den.reset()
+            got = run_gpu(pkg, den, frames, params, cams, leg="planar" if leg == "planar" else "aos", plane_fmt=fmt,
+                          plane_tables=[X] * len(frames))
+            assert_frames_equal(got, mixed_model(pkg, orc, W, H, fmt, tol, radius, k), f"{W}x{H} {leg} tol {tol}")
+    finally:
+        den.free()
+
+
+# ---- 5. GPU: one launch equals two ------------------------------------------------------------------------------------------------------
+def _full(pkg, W, H, **kw):
+    p = pkg.reference_defaults().set(**{**dict(temporal_enable=1, spatial_enable=1, atrous_nlevel=5, history_level=1), **kw})
+    p.reproj_scale[0], p.reproj_scale[1] = scales(pkg, W, H)
+    return p
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("tol", TOLS)
+def test_table_alone_equals_table_and_the_plane_motion_reproject_writes(pkg, orc, tol):
+    """Context A: table, svgf_denoise.  Context B: table, svgf_motion_reproject(X) -> svgf_denoise_motion(PREV_COORD_F32).  Full
+    SVGF, 5 levels, history from level 1: output and states 0-2 equal on every frame.  The texels are the mixed ones (ray misses,
+    ids beyond the table, positions behind the camera, the table's NaN / inf row) with finite positions: see mixed_sequence for
+    why two runs of the a-trous levels are comparable bit for bit only there; test_hip_equals_the_model_on_every_pixel holds the
+    temporal pass to the model on the non-finite ones, with and without the plane."""
+    import torch
+    W, H = 67, 41
+    seq, X = mixed_sequence(pkg, orc, W, H, finite=True), mixed_table()
+    p = _full(pkg, W, H, reproj_position_tol=tol)
+    rs = (p.reproj_scale[0], p.reproj_scale[1])
+    a, b = pkg.Denoiser(W, H), pkg.Denoiser(W, H)
+    t_x = device_table(X)
+    a.set_object_motion(t_x)
+    b.set_object_motion(t_x)
+    out_a = torch.empty((H, W, 3), dtype=torch.float32, device="cuda")
+    out_b, mv = torch.empty_like(out_a), torch.empty((H, W, 2), dtype=torch.float32, device="cuda")
+    try:
+        for f, (col, gb, cam, _) in enumerate(seq):
+            t_c = torch.from_numpy(col).cuda()
+            t_g = torch.from_numpy(gb.view(np.uint8).reshape(-1).copy()).cuda()
+            a.denoise(out_a, t_c, t_g, cam, p)
+            pkg.binding.motion_reproject(mv, W, H, seq[max(f - 1, 0)][2], gbuffer=t_g, reproj_scale=rs, geom_xf=t_x)
+            b.denoise(out_b, t_c, t_g, cam, p, motion=mv, motion_format=COORD)
+            torch.cuda.synchronize()
+            assert same_bits(out_a.cpu().numpy(), out_b.cpu().numpy()), f"output, frame {f}"
+            for which in (0, 1, 2):
+                assert same_bits(a.read_state(which), b.read_state(which)), f"state {which}, frame {f}"
+        assert a.read_state(0).max() > 1, "some history survives"
+    finally:
+        a.free(); b.free()
+
+
+@pytest.mark.gpu
+def test_a_table_of_exact_identities_is_plain_svgf_denoise(pkg, orc):
+    """On frames with finite positions ((1 p + 0 p) + 0 p) + 0 is p; whole frames, 5 levels."""
+    import torch
+    W, H = 67, 41
+    seq = clean_sequence(pkg, orc, W, H)
+    p = _full(pkg, W, H, reproj_position_tol=0.3)
+    a, b = pkg.Denoiser(W, H), pkg.Denoiser(W, H)
+    t_x = device_table(np.tile(np.eye(3, 4).reshape(-1), (9, 1)))
+    b.set_object_motion(t_x)
+    out_a = torch.empty((H, W, 3), dtype=torch.float32, device="cuda")
+    out_b = torch.empty_like(out_a)
+    try:
+        for f, (col, gb, cam, _) in enumerate(seq):
+            assert np.isfinite(gb["position"]).all()
+            t_c = torch.from_numpy(col).cuda()
+            t_g = torch.from_numpy(gb.view(np.uint8).reshape(-1).copy()).cuda()
+            a.denoise(out_a, t_c, t_g, cam, p)
+            b.denoise(out_b, t_c, t_g, cam, p)
+            torch.cuda.synchronize()
+            assert same_bits(out_a.cpu().numpy(), out_b.cpu().numpy()), f"output, frame {f}"
+            for which in (0, 1, 2):
+                assert same_bits(a.read_state(which), b.read_state(which)), f"state {which}, frame {f}"
+        assert a.read_state(0).max() == len(seq)
+    finally:
+        a.free(); b.free()
+
+
+# ---- 6. GPU: the turning, sliding block ---------------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+@pytest.mark.parametrize("tol", TOLS)
+def test_turning_block_keeps_its_history_with_the_table_and_equals_the_model(pkg, orc, tol):
+    import torch
+    cam, frames = turning_block_sequence(pkg)
+    W = H = SIDE
+    p = temporal_only(pkg, reproj_position_tol=tol)
+    den, plane = pkg.Denoiser(W, H), pkg.Denoiser(W, H)
+    den.set_capture(True)
+    plane.set_capture(True)
+    n_geoms = frames[0][2].shape[0]
+    t_x = torch.empty((n_geoms, 12), dtype=torch.float32, device="cuda")      # refreshed in place before each frame
+    den.set_object_motion(t_x)
+    mv = torch.empty((H, W, 2), dtype=torch.float32, device="cuda")
+    out = torch.empty((H, W, 3), dtype=torch.float32, device="cuda")
+    got, got_plane = [], []
+    try:
+        for col, gb, X in frames:
+            t_c = torch.from_numpy(col).cuda()
+            t_g = torch.from_numpy(gb.view(np.uint8).reshape(-1).copy()).cuda()
+            t_x.copy_(torch.from_numpy(X))
+            den.denoise(out, t_c, t_g, cam, p)
+            pkg.binding.motion_reproject(mv, W, H, cam, gbuffer=t_g, geom_xf=t_x)
+            plane.denoise(out.clone(), t_c, t_g, cam, p, motion=mv)
+            torch.cuda.synchronize()
+            got.append(read_states(den))
+            got_plane.append(read_states(plane))
+    finally:
+        den.free(); plane.free()
+    assert_frames_equal(got, turning_block_model(pkg, orc, True, tol), f"table, tol {tol}")
+    assert_frames_equal(got_plane, turning_block_model(pkg, orc, False, tol), f"plane without table, tol {tol}")
+    gb = frames[-1][1]
+    kept, lost = kept_fraction(got[-1]["hlen"], gb), kept_fraction(got_plane[-1]["hlen"], gb)
+    print(f"tol {tol}: block pixels with history >= 2: {kept:.3f} with the table, {lost:.3f} with plane + svgf_denoise_motion alone")
+    assert kept >= 0.95
+    assert lost <= 0.10
+
+
+# ---- 7. GPU: off is off ---------------------------------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+def test_off_is_off_and_the_pass_stays_one_temporal_kernel(pkg, orc):
+    W, H = 67, 41
+    seq, X = mixed_sequence(pkg, orc, W, H), mixed_table()
+    frames, cams = [(c, g) for c, g, _, _ in seq], [c for _, _, c, _ in seq]
+    params = synth_params(pkg, W, H, reproj_position_tol=0.3)
+    t_x = device_table(X)
+    fresh, toggled = pkg.Denoiser(W, H), pkg.Denoiser(W, H)
+    assert fresh.object_motion() == (None, 0)
+    toggled.set_object_motion(t_x)
+    assert toggled.object_motion() == (t_x.data_ptr(), 9), "the getter returns what was set"
+    n = ctypes.c_int(-1)
+    assert pkg.load_library().svgf_get_object_motion(toggled.h, None, ctypes.byref(n)) == 0 and n.value == 9
+    toggled.set_object_motion(None)
+    assert toggled.object_motion() == (None, 0)
+    a, b = run_gpu(pkg, fresh, frames, params, cams), run_gpu(pkg, toggled, frames, params, cams)
+    views = [seq[max(f - 1, 0)][3] for f in range(len(seq))]
+    ref = om.run_sequence(frames, views=views, scale=scales(pkg, W, H), pos_tol=0.3)
+    assert_frames_equal(a, ref, "never set")
+    assert_frames_equal(b, ref, "set, then unset")
+    # a pointer with n_geoms 0 is off too
+    toggled.reset()
+    toggled.set_object_motion(t_x.data_ptr(), 0)
+    assert toggled.object_motion() == (t_x.data_ptr(), 0)
+    assert_frames_equal(run_gpu(pkg, toggled, frames, params, cams), ref, "n_geoms 0")
+    # svgf_reset keeps the setting: the frames behind it are the model's with the table
+    toggled.set_object_motion(t_x)
+    run_gpu(pkg, toggled, frames[:2], params, cams)
+    toggled.reset()
+    assert toggled.object_motion() == (t_x.data_ptr(), 9)
+    assert_frames_equal(run_gpu(pkg, toggled, frames, params, cams), mixed_model(pkg, orc, W, H, None, 0.3), "behind svgf_reset")
+    fresh.free(); toggled.free()
+    # a non-temporal frame ignores the table (finite positions: two runs of the a-trous levels are compared, see mixed_sequence)
+    spatial = pkg.reference_defaults().set(temporal_enable=0, spatial_enable=1)
+    finite = [(c, g) for c, g, _, _ in mixed_sequence(pkg, orc, W, H, finite=True)]
+    outs = []
+    for table in (False, True):
+        e = pkg.Denoiser(W, H)
+        if table:
+            e.set_object_motion(t_x)
+        outs.append([e.denoise_host(c, g, cam, spatial) for (c, g), cam in zip(finite[:2], cams)])
+        e.free()
+    for x, y in zip(*outs):
+        assert same_bits(x, y)
+    # whole frames through svgf_denoise_host, profiled: one TEMPORAL per frame, table on or off, and the table acts
+    full = _full(pkg, W, H)
+    kinds, hl = {}, {}
+    for table in (False, True):
+        d = pkg.Denoiser(W, H)
+        if table:
+            d.set_object_motion(t_x)
+        d.profile_stride(1)
+        d.profile_enable(len(frames))
+        for (col, gb), cam in zip(frames, cams):
+            d.denoise_host(col, gb, cam, full)
+        d.sync()
+        assert d.profile_frames() == len(frames)
+        kinds[table] = [[kk for kk, _ in d.profile_read(s)] for s in range(len(frames))]
+        hl[table] = d.read_state(0)
+        d.free()
+    assert kinds[False] == kinds[True]
+    for row in kinds[True]:
+        assert row == [pkg.binding.KERNEL_TEMPORAL] + [pkg.binding.KERNEL_ATROUS] * 5, row
+    assert same_bits(hl[True], mixed_model(pkg, orc, W, H, None, 0.0)[-1]["hlen"]), "svgf_denoise_host honours the table"
+    assert not np.array_equal(hl[True], hl[False])
+
+
+# ---- 8. GPU: contract -------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+def test_contract_errors_leave_the_setting_as_it_was(pkg, orc):
+    W, H = 67, 41
+    seq, X = mixed_sequence(pkg, orc, W, H), mixed_table()
+    frames, cams = [(c, g) for c, g, _, _ in seq], [c for _, _, c, _ in seq]
+    params = synth_params(pkg, W, H)
+    ref = mixed_model(pkg, orc, W, H, None, 0.0)
+    lib = pkg.load_library()
+    t_x = device_table(X)
+    other = device_table(np.tile(np.eye(3, 4).reshape(-1), (12, 1)))
+    d = pkg.Denoiser(W, H)
+    d.set_object_motion(t_x)
+    assert_frames_equal(run_gpu(pkg, d, frames[:2], params, cams), ref[:2], "before the refused calls")
+    for ptr, n, word in ((other.data_ptr(), -1, "negative"), (None, 3, "null"), (other.data_ptr() + 4, 12, "aligned"),
+                         (other.data_ptr() + 8, 12, "aligned")):
+        assert lib.svgf_set_object_motion(d.h, ptr, n) == -1, (ptr, n)
+        assert word in d.last_error(), d.last_error()
+        with pytest.raises(pkg.SvgfError, match="-> -1"):
+            d.set_object_motion(ptr, n)
+        assert d.object_motion() == (t_x.data_ptr(), 9), "a refused call changes nothing"
+    assert lib.svgf_set_object_motion(None, other.data_ptr(), 12) == -1
+    got = run_gpu(pkg, d, frames[2:], params, cams[2:])      # the history of frames 0-1 goes on under the table that was set
+    assert_frames_equal(got, ref[2:], "behind the refused calls")
+    d.set_object_motion(other)
+    assert d.object_motion() == (other.data_ptr(), 12)
+    d.free()
+
+
+@pytest.mark.gpu
+@pytest.mark.experiments
+@pytest.mark.parametrize("which", ["kernel_variant_6", "split_fused"])
+def test_parked_fused_temporal_kernels_refuse_a_frame_with_a_table(pkg, experiments_lib, which):
+    import torch
+    W, H = 64, 48
+    rgb = torch.zeros((H, W, 3), dtype=torch.float32, device="cuda")
+    gbt = torch.zeros((H * W * 52,), dtype=torch.uint8, device="cuda")
+    out = torch.empty_like(rgb)
+    t_x = device_table(mixed_table())
+    cam = pkg.synth.camera_for_frame(0, False)
+    p = pkg.reference_defaults().set(temporal_enable=1, spatial_enable=1)
+    if which == "split_fused":
+        experiments_lib.exp_set("split_fused", 1)      # read by svgf_create
+    else:
+        p.kernel_variant = 6
+    e = pkg.Denoiser(W, H, experiments=True)
+    e.denoise(out, rgb, gbt, cam, p)                   # no table: runs
+    e.sync()
+    before = e.read_state(0).copy()
+    e.set_object_motion(t_x)
+    with pytest.raises(pkg.SvgfError, match="-> -5"):
+        e.denoise(out, rgb, gbt, cam, p)
+    assert "object motion" in e.last_error()
+    e.sync()
+    assert np.array_equal(e.read_state(0), before), "a refused frame enqueues nothing"
+    e.denoise(out, rgb, gbt, cam, pkg.SvgfParams.from_buffer_copy(p).set(temporal_enable=0))      # no temporal pass: not refused
+    e.sync()
+    e.set_object_motion(None)
+    e.denoise(out, rgb, gbt, cam, p)                   # table off again: runs
+    e.sync()
+    e.free()
+
+
+# ---- 9. GPU: whole frames ------------------------------------------------------------------------------------------------------------------
+def _whole_frames(pkg, den, params, frames, cam):
+    import torch
+    H = W = SIDE
+    outs, keep = [], []
+    n_geoms = frames[0][2].shape[0]
+    for col, gb, X in frames:
+        t_c = torch.from_numpy(col).cuda()
+        t_g = torch.from_numpy(gb.view(np.uint8).reshape(-1).copy()).cuda()
+        t_x = device_table(X)      # one table per frame: a promised frame's table stays untouched until the frame is done
+        out = torch.empty((H, W, 3), dtype=torch.float32, device="cuda")
+        keep.append((t_c, t_g, t_x, out))
+        torch.cuda.synchronize()
+        den.set_object_motion(t_x, n_geoms)
+        den.denoise(out, t_c, t_g, cam, params)
+    den.sync()
+    return [o.cpu().numpy() for _, _, _, o in keep], [den.read_state(k) for k in (0, 1, 2)]
+
+
+@pytest.mark.gpu
+def test_whole_frames_ordered_promised_and_strict_gather_agree(pkg):
+    """Full SVGF, 5 levels, history from level 1, on the turning block with its table: the bounds of
+    tests/test_history_clamp.py::test_whole_frames_ordered_promised_and_strict_gather_agree."""
+    cam, frames = turning_block_sequence(pkg)
+    full = pkg.reference_defaults().set(temporal_enable=1, spatial_enable=1, atrous_nlevel=5, history_level=1)
+
+    def run(variant=0, promised=False):
+        d = pkg.Denoiser(SIDE, SIDE, 0, pipelined=promised)
+        p = pkg.SvgfParams.from_buffer_copy(full).set(kernel_variant=variant)
+        if promised:
+            if d.pipeline_status() == 2:
+                d.free()
+                return None
+            p.inputs_ready = 1
+        try:
+            res = _whole_frames(pkg, d, p, frames, cam)
+            if promised:
+                assert d.is_pipelined()
+            return res
+        finally:
+            d.free()
+
+    ordered, strict, promised = run(), run(variant=1), run(promised=True)
+    assert kept_fraction(ordered[1][0], frames[-1][1]) >= 0.95, "the table acts on whole frames"
+    for f in range(TURN_FRAMES):
+        err = float(relerr(ordered[0][f], strict[0][f]).max())
+        print(f"frame {f}: kernel_variant 0 against 1, max relative error {err:.3e}")
+        assert err <= 1e-5, f"frame {f}"
+    if promised is None:
+        pytest.skip("the context's two streams share a hardware queue: the promise is refused (variants 0 and 1 agreed)")
+    for f in range(TURN_FRAMES):
+        assert same_bits(ordered[0][f], promised[0][f]), f"output, frame {f}"
+    for k in range(3):
+        assert same_bits(ordered[1][k], promised[1][k]), f"state {k}"

@@ -37,6 +37,9 @@ def main():
                     "(svgf_denoise_motion; the plane is written once by svgf_motion_reproject for the static camera) instead of projecting through the previous camera")
     ap.add_argument("--clamp", default=None, metavar="R[,K]", help="svgf_set_history_clamp(R, K) on the context before the first frame (K defaults to 1): "
                     "the temporal pass runs its clamped kernel of radius R")
+    ap.add_argument("--object-motion", action="store_true", help="svgf_set_object_motion with a table of 16 identity maps on the context before the first "
+                    "frame: the temporal pass runs its object-motion kernel (three 16-byte loads and the two maps per pixel; the same taps pass as without); "
+                    "with --motion the plane is written with the same table")
     ap.add_argument("--sustain", type=float, default=0.0, help="seconds of back-to-back frames in front of every measurement (the sustained clock / "
                     "power state bench.py measures in, DESIGN.md 6.2); 0 = measure from wherever the GPU is (cold after start-up)")
     ap.add_argument("--telemetry-json", default=None, help="append one JSON line per variant: {variant, frame_us, telemetry summary} (the A/B scripts' clock check)")
@@ -58,6 +61,10 @@ def main():
         if a.clamp:
             rk = a.clamp.split(",")
             d.set_history_clamp(int(rk[0]), float(rk[1]) if len(rk) > 1 else 1.0)
+        xf = None
+        if a.object_motion:
+            xf = torch.from_numpy(np.tile(np.eye(3, 4, dtype=np.float32).reshape(-1), (16, 1))).cuda()
+            d.set_object_motion(xf)
         if a.planar:      # both plane sets (they alternate with the history) get the static scene's G-buffer; d.denoise then means denoise_planar
             cam_dict = pkg.synth.camera_for_frame(0, False)
             for _ in range(2):
@@ -70,7 +77,7 @@ def main():
             mv = {}
             for k in range(nsrc):
                 m = torch.empty((H, W, 2), dtype=torch.float16 if a.motion == "delta16" else torch.float32, device="cuda")
-                pkg.binding.motion_reproject(m, W, H, cam[k], gbuffer=d_g[k], motion_format=fmt)
+                pkg.binding.motion_reproject(m, W, H, cam[k], gbuffer=d_g[k], motion_format=fmt, geom_xf=xf)
                 mv[d_g[k].data_ptr()] = m
             torch.cuda.synchronize()
             if a.planar:
