@@ -1,0 +1,187 @@
+"""What the temporal-pass suites share (tests/test_motion_vectors.py, test_history_clamp.py, test_object_motion.py): how frames
+are compared with tests/temporal_model.py, the parameter sets, the two input sequences and the loop that runs a sequence
+through a context and reads its states back.  Test infrastructure only; not part of the package."""
+import ctypes
+import os
+
+import numpy as np
+
+import temporal_model as tm
+from conftest import ROOT
+
+F = np.float32
+COORD, D32, D16 = tm.COORD, tm.D32, tm.D16
+SCENE = os.path.join(ROOT, "tests", "golden", "scenes", "box_room.txt")
+STATES = ("hlen", "mom", "color", "variance", "acc")      # svgf_read_state 0..4
+
+
+# ---- comparison and parameters ----------------------------------------------------------------------------------------------------------
+def same_bits(a, b):
+    a, b = np.asarray(a), np.asarray(b)
+    if a.shape != b.shape or a.dtype != b.dtype:
+        return False
+    if a.dtype.kind != "f":
+        return bool(np.array_equal(a, b))
+    na, nb = np.isnan(a), np.isnan(b)
+    return bool(np.array_equal(na, nb) and np.array_equal(a.view(np.uint32)[~na], b.view(np.uint32)[~nb]))
+
+
+def assert_frames_equal(got, ref, what):
+    """got: per frame the five states read from a context; ref: per frame the model's dict (acc = color with the spatial filter off)."""
+    assert len(got) == len(ref)
+    for f, (g, r) in enumerate(zip(got, ref)):
+        for name in STATES:
+            want = r["color" if name == "acc" else name]
+            bad = "" if same_bits(g[name], want) else f"{np.count_nonzero(~np.isclose(g[name], want, rtol=0, atol=0, equal_nan=True))} values differ"
+            assert not bad, f"{what}: {name}, frame {f}: {bad}"
+
+
+def temporal_only(pkg, **kw):
+    return pkg.reference_defaults().set(**{**dict(temporal_enable=1, spatial_enable=0), **kw})
+
+
+def scales(pkg, W, H):
+    """SvgfParams::reproj_scale that makes the reprojection exact at any aspect, (tan(FOVY) * W / H, tan(FOVY)): the reference's
+    own mapping loses every pixel's history at 300x9, and nothing behind the reprojection would run there."""
+    plx, ply = pkg.synth._pixel_length(W, H, 45.0)
+    return float(plx) * W / 2.0, float(ply) * H / 2.0
+
+
+def synth_params(pkg, W, H, **kw):
+    p = temporal_only(pkg, **kw)
+    p.reproj_scale[0], p.reproj_scale[1] = scales(pkg, W, H)
+    return p
+
+
+# ---- inputs ---------------------------------------------------------------------------------------------------------------------------
+def synth_sequence(pkg, orc, W, H, n=4, seed=31):
+    """n frames of the synthetic scene under its moving camera, texels as rendered (finite positions): per frame
+    (colour[H, W, 3], texels[H, W], camera, view matrix).  Computed once per session; callers that change a frame copy it."""
+    cache = synth_sequence.__dict__.setdefault("cache", {})
+    if (W, H, n, seed) not in cache:
+        seq = []
+        for f in range(n):
+            col, gb, cam = pkg.synth.render_frame(W, H, f, seed=seed, moving=True, noise_model="hash")
+            seq.append((np.asarray(col, F).reshape(H, W, 3), gb.reshape(H, W), cam, orc.view_matrix(pkg, cam)))
+        cache[(W, H, n, seed)] = seq
+    return cache[(W, H, n, seed)]
+
+
+BLOCK, SIDE = 7, 96      # the turned block of box_room.txt; every box_room frame is SIDE x SIDE
+
+
+def block_sequence(pkg, n, slide_x, turn_deg):
+    """n frames of box_room at 96x96 under a static camera, the turned block (object 7) rotated by turn_deg about y and translated
+    by slide_x in x per frame.  Returns (camera, [(colour[H, W, 3], texels[H, W], X float32[n_geoms, 12])]); X[g] = xf_prev[g] *
+    inv_cur[g] composed in float64 and rounded: this frame's world space to the previous frame's (frame 0: identities).  Computed
+    once per session."""
+    cache = block_sequence.__dict__.setdefault("cache", {})
+    if (n, slide_x, turn_deg) not in cache:
+        sc = pkg.scene.parse_scene(open(SCENE).read())
+        cam = pkg.scene.camera_for_frame(sc, 0, False)
+        t0, r0 = tuple(sc.objects[BLOCK]["trans"]), tuple(sc.objects[BLOCK]["rotat"])
+        frames, prev = [], None
+        for f in range(n):
+            o = sc.objects[BLOCK]
+            o["trans"] = (t0[0] + slide_x * f,) + t0[1:]
+            o["rotat"] = (r0[0], r0[1] + turn_deg * f, r0[2])
+            g = pkg.scene.geom_array(sc)
+            col, gb = pkg.scene.render_scene(SIDE, SIDE, f, g, cam, seed=3)
+            X = np.tile(np.eye(3, 4).reshape(-1), (len(g), 1))
+            if prev is not None:
+                for k in range(len(g)):
+                    a = np.vstack([prev[k]["xf"].astype(np.float64).reshape(3, 4), [0, 0, 0, 1]])
+                    b = np.vstack([g[k]["inv"].astype(np.float64).reshape(3, 4), [0, 0, 0, 1]])
+                    X[k] = (a @ b)[:3].reshape(-1)
+            frames.append((np.asarray(col, F).reshape(SIDE, SIDE, 3), gb.reshape(SIDE, SIDE), X.astype(F)))
+            prev = g
+        cache[(n, slide_x, turn_deg)] = (cam, frames)
+    return cache[(n, slide_x, turn_deg)]
+
+
+MOVING_FRAMES = 6
+
+
+def moving_block_sequence(pkg):
+    """Six frames, the block translated by +0.4 in x per frame, no rotation."""
+    return block_sequence(pkg, MOVING_FRAMES, 0.4, 0.0)
+
+
+# ---- the GPU side ---------------------------------------------------------------------------------------------------------------------
+def _hip():
+    """The HIP runtime already loaded into this process (torch's), for plain host-to-device copies into raw pointers."""
+    for ln in open("/proc/self/maps"):
+        if "libamdhip64" in ln:
+            return ctypes.CDLL(ln.split()[-1])
+    raise RuntimeError("no HIP runtime loaded")
+
+
+def read_states(den):
+    return {name: den.read_state(k) for k, name in enumerate(STATES)}
+
+
+def device_table(X):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(X, dtype=F)).cuda()
+
+
+def run_gpu(pkg, den, frames, params, cams, leg="aos", planes=None, fmt=COORD, plane_fmt=None, plane_tables=None):
+    """frames: [(colour, texels)]; cams: per frame.  The context's clamp and table are whatever the caller set.  The history is
+    looked up through the camera path, or through a motion plane given in one of two ways:
+    planes, fmt: per frame a host plane of format `fmt` (the model's), uploaded;
+    plane_fmt, plane_tables: the plane svgf_motion_reproject writes on the device in that format for the previous frame's camera,
+    params' reproj_scale and plane_tables[f] (None: no table).
+    Returns per frame the five states.  `leg`: aos | planar."""
+    import torch
+    assert planes is None or plane_fmt is None
+    H, W = frames[0][1].shape
+    den.set_capture(True)
+    out, res, keep = torch.empty((H, W, 3), dtype=torch.float32, device="cuda"), [], []
+    rs = (params.reproj_scale[0], params.reproj_scale[1])
+    for f, (col, gb) in enumerate(frames):
+        t_c = torch.from_numpy(np.ascontiguousarray(col, dtype=F)).cuda()
+        t_g = torch.from_numpy(np.ascontiguousarray(gb).view(np.uint8).reshape(-1).copy()).cuda()
+        mv = None if planes is None else torch.from_numpy(np.ascontiguousarray(planes[f])).cuda()
+        if plane_fmt is not None:
+            fmt = plane_fmt
+            mv = torch.empty((H, W, 2), dtype=torch.float16 if fmt == D16 else torch.float32, device="cuda")
+            t_x = None if plane_tables is None or plane_tables[f] is None else device_table(plane_tables[f])
+            pkg.binding.motion_reproject(mv, W, H, cams[max(f - 1, 0)], gbuffer=t_g, motion_format=fmt, reproj_scale=rs, geom_xf=t_x)
+            keep.append(t_x)
+        keep.append((t_c, t_g, mv))      # (a promised frame's inputs stay untouched until its work is done)
+        torch.cuda.synchronize()
+        if leg == "planar":
+            g = den.planar_gbuffer()
+            hip = _hip()
+            hip.hipMemcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
+            flat = np.ascontiguousarray(gb).reshape(-1)
+            for dst, arr in ((g.normal, flat["normal"]), (g.position, flat["position"]), (g.geom_id, flat["geomId"]),
+                             (g.albedo, (flat["albedo"] * flat["ialbedo"]).astype(F))):
+                arr = np.ascontiguousarray(arr)
+                assert hip.hipMemcpy(dst, arr.ctypes.data, arr.nbytes, 1) == 0
+            den.denoise_planar(out, t_c, cams[f], params, motion=mv, motion_format=fmt)
+        else:
+            den.denoise(out, t_c, t_g, cams[f], params, motion=mv, motion_format=fmt)
+        den.sync()
+        res.append(read_states(den))
+    return res
+
+
+def _whole_frames(pkg, den, params, frames, cam, tables=False):
+    """The frames of a block_sequence through svgf_denoise, none waited for before the last is enqueued.  tables: each frame's X
+    is set as the context's object motion table before the frame.  Returns (per frame the output, states 0-2 after the last)."""
+    import torch
+    H = W = SIDE
+    keep = []
+    for col, gb, X in frames:
+        t_c = torch.from_numpy(col).cuda()
+        t_g = torch.from_numpy(gb.view(np.uint8).reshape(-1).copy()).cuda()
+        t_x = device_table(X) if tables else None      # one per frame: a promised frame's table stays untouched until the frame is done
+        out = torch.empty((H, W, 3), dtype=torch.float32, device="cuda")
+        keep.append((t_c, t_g, t_x, out))
+        torch.cuda.synchronize()
+        if tables:
+            den.set_object_motion(t_x, X.shape[0])
+        den.denoise(out, t_c, t_g, cam, params)
+    den.sync()
+    return [o.cpu().numpy() for _, _, _, o in keep], [den.read_state(k) for k in (0, 1, 2)]

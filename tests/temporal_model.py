@@ -1,8 +1,9 @@
-"""A float32 numpy model of the temporal pass (csrc/svgf_temporal.h, svgf_temporal_pixel.inc.h) with the history clamp of
-svgf_set_history_clamp, the position test of SvgfParams::reproj_position_tol and the object motion table of
-svgf_set_object_motion — the yardstick of tests/test_object_motion.py.  Test infrastructure only; not part of the package.
-tests/history_clamp_model.py extended (that file is the yardstick of its own suite and stays as it is; test_object_motion.py pins
-this model to it).
+"""The float32 numpy model of the temporal pass (csrc/svgf_temporal.h, svgf_temporal_pixel.inc.h) — the yardstick of
+tests/test_motion_vectors.py, test_history_clamp.py and test_object_motion.py.  Test infrastructure only; not part of the package.
+
+One model with three optional parts, each off at its default: the history clamp of svgf_set_history_clamp (`radius`, `k`), the
+position test of SvgfParams::reproj_position_tol (`pos_tol`) and the object motion table of svgf_set_object_motion (`tables`,
+`compare_normal` / `compare_position`).
 
 The model looks a pixel's history up at the coordinate a PREV_COORD_F32 plane gives (svgf_denoise_motion); the camera path is
 the same model fed the plane svgf_motion_reproject would write (project_prev below: the camera path's own projection) — with a
@@ -12,7 +13,18 @@ table, moved_normal() / apply_xf() with one.  The state kept for the next frame 
 
 numpy rounds every array operation to float32 and never contracts a multiply and an add, which is the kernel's arithmetic
 (`#pragma clang fp contract(off)`); sums are written as the kernel's sequences of additions, in its order.  Division and sqrt
-are correctly rounded on both sides."""
+are correctly rounded on both sides.
+
+What pins the model, on the CPU (the oracle knows no plane, no clamp and no table, so each part is pinned where it can be):
+- without clamp, position test and table, to the C oracle on the moving block of box_room:
+  test_history_clamp.py::test_model_without_clamp_is_the_oracle_on_the_moving_block;
+- the position test, to the oracle's: test_object_motion.py::test_model_position_test_is_the_oracle;
+- the table, to the oracle on texels whose normal and position were replaced by the moved ones:
+  test_object_motion.py::test_model_with_table_is_the_oracle_on_substituted_texels;
+- the clamp (and everything else on the moving block, radius 0 to 3), to the results recorded in
+  tests/golden/temporal_model/moving_block.json from the model the clamp's suite was first written against:
+  test_object_motion.py::test_model_without_table_is_the_clamp_model_on_the_moving_block.
+The GPU suites then hold the kernels to the model on the bits of every pixel."""
 import numpy as np
 
 F = np.float32
@@ -20,7 +32,7 @@ COORD, D32, D16 = 1, 2, 3      # SVGF_MOTION_PREV_COORD_F32, SVGF_MOTION_DELTA_F
 NORMAL_THRESHOLD = np.array([0x3c23d70b], dtype=np.uint32).view(F)[0]      # svgf_normals_close: squared distance
 
 
-# ---- coordinates (copies of the replicas in tests/test_motion_vectors.py) -----------------------------------------------------------
+# ---- coordinates: replicas of svgf_to_prev_space, svgf_project_prev and svgf_motion_reproject -------------------------------------
 def apply_xf(X, gid, pos):
     """pos float32[..., 3] mapped by X[gid] (float32[n, 12], 3x4 row-major) where 0 <= gid < n: ((m0 v0 + m1 v1) + m2 v2) + m3."""
     pos = np.asarray(pos, dtype=F)

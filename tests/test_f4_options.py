@@ -10,17 +10,13 @@ import numpy as np
 import pytest
 
 from conftest import relerr
-
-
-def _scales(pkg, W, H):
-    plx, ply = pkg.synth._pixel_length(W, H, 45.0)
-    return float(plx) * W / 2.0, float(ply) * H / 2.0
+from temporal_harness import scales
 
 
 def _params(pkg, W, H, tol=0.0, K=0, nlevel=5):
     p = pkg.reference_defaults().set(temporal_enable=1, spatial_enable=1, atrous_nlevel=nlevel, history_level=1,
                                      reproj_position_tol=tol, spatial_variance_frames=K)
-    p.reproj_scale[0], p.reproj_scale[1] = _scales(pkg, W, H)       # exact reprojection, so that histories survive at 16:9
+    p.reproj_scale[0], p.reproj_scale[1] = scales(pkg, W, H)       # exact reprojection, so that histories survive at 16:9
     return p
 
 

@@ -1,6 +1,6 @@
 """History clamp of the temporal pass (include/svgf.h: svgf_set_history_clamp / svgf_get_history_clamp).
 
-The yardstick is tests/history_clamp_model.py, a float32 numpy model of the whole temporal pass.  The oracle knows no clamp;
+The yardstick is tests/temporal_model.py, the float32 numpy model of the whole temporal pass.  The oracle knows no clamp;
 test 2 pins the model to the oracle with the clamp off, bit for bit, so that with the clamp on any difference is the clamp's.
 
 Bounds: every comparison of the kernel with the model is on the bits of every pixel (NaNs in the same place count as equal).
@@ -9,107 +9,28 @@ correctly rounded on both: there is no arithmetic that may differ, so there is n
 this file, 1e-5 between kernel_variant 0 and 1 on whole frames, is the project's existing gate between its a-trous kernels
 (tests/test_parity_gpu.py): the clamp changes their input, not them."""
 import ctypes
-import os
 
 import numpy as np
 import pytest
 
-import history_clamp_model as hm
-from conftest import ROOT, relerr
+import temporal_model as tm
+from conftest import relerr
+from temporal_harness import (MOVING_FRAMES, SIDE, _whole_frames, assert_frames_equal, moving_block_sequence, read_states, run_gpu,
+                              same_bits, scales, synth_params, synth_sequence, temporal_only)
 
 F = np.float32
-COORD, D32, D16 = hm.COORD, hm.D32, hm.D16
-SCENE = os.path.join(ROOT, "tests", "golden", "scenes", "box_room.txt")
+COORD, D32, D16 = tm.COORD, tm.D32, tm.D16
 NEW_SYMBOLS = ("svgf_set_history_clamp", "svgf_get_history_clamp")
 RADII, KS = (1, 2, 3), (0.0, 1.0, 2.5)
-STATES = ("hlen", "mom", "color", "variance", "acc")      # svgf_read_state 0..4
-
-
-def same_bits(a, b):
-    a, b = np.asarray(a), np.asarray(b)
-    if a.shape != b.shape or a.dtype != b.dtype:
-        return False
-    if a.dtype.kind != "f":
-        return bool(np.array_equal(a, b))
-    na, nb = np.isnan(a), np.isnan(b)
-    return bool(np.array_equal(na, nb) and np.array_equal(a.view(np.uint32)[~na], b.view(np.uint32)[~nb]))
-
-
-def assert_frames_equal(got, ref, what):
-    """got: per frame the five states read from a context; ref: per frame the model's dict (acc = color with the spatial filter off)."""
-    assert len(got) == len(ref)
-    for f, (g, r) in enumerate(zip(got, ref)):
-        for name in STATES:
-            want = r["color" if name == "acc" else name]
-            bad = "" if same_bits(g[name], want) else f"{np.count_nonzero(~np.isclose(g[name], want, rtol=0, atol=0, equal_nan=True))} values differ"
-            assert not bad, f"{what}: {name}, frame {f}: {bad}"
-
-
-def temporal_only(pkg, **kw):
-    return pkg.reference_defaults().set(**{**dict(temporal_enable=1, spatial_enable=0), **kw})
-
-
-def scales(pkg, W, H):
-    """SvgfParams::reproj_scale that makes the reprojection exact at any aspect (the reference's own mapping loses every pixel's
-    history at 300x9, and the clamp would never run there)."""
-    plx, ply = pkg.synth._pixel_length(W, H, 45.0)
-    return float(plx) * W / 2.0, float(ply) * H / 2.0
-
-
-def synth_params(pkg, W, H, **kw):
-    p = temporal_only(pkg, **kw)
-    p.reproj_scale[0], p.reproj_scale[1] = scales(pkg, W, H)
-    return p
 
 
 # ---- inputs ---------------------------------------------------------------------------------------------------------------------------
-def synth_sequence(pkg, orc, W, H, n=4):
-    """n frames of the synthetic scene under its moving camera: per frame (colour[H, W, 3], texels[H, W], camera, view matrix)."""
-    cache = synth_sequence.__dict__.setdefault("cache", {})
-    if (W, H, n) not in cache:
-        seq = []
-        for f in range(n):
-            col, gb, cam = pkg.synth.render_frame(W, H, f, seed=31, moving=True, noise_model="hash")
-            seq.append((np.asarray(col, F).reshape(H, W, 3), gb.reshape(H, W), cam, orc.view_matrix(pkg, cam)))
-        cache[(W, H, n)] = seq
-    return cache[(W, H, n)]
-
-
 def camera_planes(pkg, seq, fmt):
     """Per frame the plane svgf_motion_reproject writes for the previous frame's camera and synth_params' reproj_scale (frame 0: its
     own camera; never looked at)."""
     H, W = seq[0][1].shape
     sx, sy = scales(pkg, W, H)
-    return [hm.motion_plane(seq[max(f - 1, 0)][3], W, H, seq[f][1], None, fmt, F(sx), F(sy)) for f in range(len(seq))]
-
-
-MOVING_OBJECT, STEP_X, N_FRAMES, SIDE = 7, 0.4, 6, 96
-
-
-def moving_block_sequence(pkg):
-    """Six frames of box_room at 96x96 under a static camera, the turned block translated by +0.4 in x per frame (the sequence of
-    tests/test_motion_vectors.py).  Returns (camera, [(colour, texels, X float32[n, 12])]), X[g]: this frame's world space to the
-    previous frame's."""
-    if not hasattr(moving_block_sequence, "cache"):
-        sc = pkg.scene.parse_scene(open(SCENE).read())
-        cam = pkg.scene.camera_for_frame(sc, 0, False)
-        x0 = sc.objects[MOVING_OBJECT]["trans"][0]
-        frames, prev = [], None
-        for f in range(N_FRAMES):
-            o = sc.objects[MOVING_OBJECT]
-            o["trans"] = (x0 + STEP_X * f,) + tuple(o["trans"][1:])
-            g = pkg.scene.geom_array(sc)
-            col, gb = pkg.scene.render_scene(SIDE, SIDE, f, g, cam, seed=3)
-            X = np.tile(np.eye(3, 4).reshape(-1), (len(g), 1))
-            if prev is not None:
-                for k in range(len(g)):
-                    a = np.vstack([prev[k]["xf"].astype(np.float64).reshape(3, 4), [0, 0, 0, 1]])
-                    b = np.vstack([g[k]["inv"].astype(np.float64).reshape(3, 4), [0, 0, 0, 1]])
-                    X[k] = (a @ b)[:3].reshape(-1)
-            frames.append((np.asarray(col, F).reshape(SIDE, SIDE, 3), gb.reshape(SIDE, SIDE), X.astype(F)))
-            prev = g
-        moving_block_sequence.cache = (cam, frames)
-    return moving_block_sequence.cache
+    return [tm.motion_plane(seq[max(f - 1, 0)][3], W, H, seq[f][1], None, fmt, F(sx), F(sy)) for f in range(len(seq))]
 
 
 def moving_block_model(pkg, orc, radius, k):
@@ -117,8 +38,8 @@ def moving_block_model(pkg, orc, radius, k):
     if (radius, k) not in cache:
         cam, frames = moving_block_sequence(pkg)
         M = orc.view_matrix(pkg, cam)
-        coords = [hm.motion_plane(M, SIDE, SIDE, gb, X, COORD) for _, gb, X in frames]
-        cache[(radius, k)] = hm.run_sequence([(c, g) for c, g, _ in frames], coords, radius=radius, k=k)
+        coords = [tm.motion_plane(M, SIDE, SIDE, gb, X, COORD) for _, gb, X in frames]
+        cache[(radius, k)] = tm.run_sequence([(c, g) for c, g, _ in frames], coords, radius=radius, k=k)
     return cache[(radius, k)]
 
 
@@ -128,8 +49,8 @@ def model_on(pkg, seq, fmt, radius, k, tag):
     key = (tag, fmt, radius, k)
     if key not in cache:
         H, W = seq[0][1].shape
-        coords = [hm.coord_plane(pl, fmt, W, H) for pl in camera_planes(pkg, seq, fmt)]
-        cache[key] = hm.run_sequence([(c, g) for c, g, _, _ in seq], coords, radius=radius, k=k)
+        coords = [tm.coord_plane(pl, fmt, W, H) for pl in camera_planes(pkg, seq, fmt)]
+        cache[key] = tm.run_sequence([(c, g) for c, g, _, _ in seq], coords, radius=radius, k=k)
     return cache[key]
 
 
@@ -166,51 +87,6 @@ def assert_feature(last, radius):
     assert (last["hlen"] == 5).all()
 
 
-# ---- the GPU side ---------------------------------------------------------------------------------------------------------------------
-def _hip():
-    """The HIP runtime already loaded into this process (torch's), for plain host-to-device copies into raw pointers."""
-    for ln in open("/proc/self/maps"):
-        if "libamdhip64" in ln:
-            return ctypes.CDLL(ln.split()[-1])
-    raise RuntimeError("no HIP runtime loaded")
-
-
-def read_states(den):
-    return {name: den.read_state(k) for k, name in enumerate(STATES)}
-
-
-def run_gpu(pkg, den, frames, params, leg="aos", planes=None, fmt=COORD, cams=None):
-    """frames: [(colour, texels)]; cams: per frame; planes: per frame a host motion plane of `fmt` or None (camera path).
-    Returns per frame the five states.  `leg`: aos | planar."""
-    import torch
-    H, W = frames[0][1].shape
-    den.set_capture(True)
-    out, res, keep = torch.empty((H, W, 3), dtype=torch.float32, device="cuda"), [], []
-    for f, (col, gb) in enumerate(frames):
-        t_c = torch.from_numpy(np.ascontiguousarray(col, dtype=F)).cuda()
-        mv = None if planes is None else torch.from_numpy(np.ascontiguousarray(planes[f])).cuda()
-        keep.append((t_c, mv))      # (a promised frame's inputs stay untouched until its work is done)
-        torch.cuda.synchronize()
-        if leg == "planar":
-            g = den.planar_gbuffer()
-            hip = _hip()
-            hip.hipMemcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
-            flat = np.ascontiguousarray(gb).reshape(-1)
-            for dst, arr in ((g.normal, flat["normal"]), (g.position, flat["position"]), (g.geom_id, flat["geomId"]),
-                             (g.albedo, (flat["albedo"] * flat["ialbedo"]).astype(F))):
-                arr = np.ascontiguousarray(arr)
-                assert hip.hipMemcpy(dst, arr.ctypes.data, arr.nbytes, 1) == 0
-            den.denoise_planar(out, t_c, cams[f], params, motion=mv, motion_format=fmt)
-        else:
-            t_g = torch.from_numpy(np.ascontiguousarray(gb).view(np.uint8).reshape(-1).copy()).cuda()
-            keep.append(t_g)
-            torch.cuda.synchronize()
-            den.denoise(out, t_c, t_g, cams[f], params, motion=mv, motion_format=fmt)
-        den.sync()
-        res.append(read_states(den))
-    return res
-
-
 # ---- 1. CPU: symbols and the NULL context ----------------------------------------------------------------------------------------------
 def test_symbols_are_exported_and_a_null_context_is_invalid(pkg):
     lib = pkg.load_library()
@@ -236,7 +112,7 @@ def test_model_without_clamp_is_the_oracle_on_the_moving_block(pkg, orc):
     try:
         for f, (col, gb, X) in enumerate(frames):
             sub = gb.copy()
-            sub["position"] = hm.apply_xf(X, gb["geomId"], gb["position"])
+            sub["position"] = tm.apply_xf(X, gb["geomId"], gb["position"])
             o.denoise(col, sub, cam, temporal_only(pkg))
             assert same_bits(o.read_state(0), ref[f]["hlen"]), f"history length, frame {f}"
             assert same_bits(o.read_state(1), ref[f]["mom"]), f"moments, frame {f}"
@@ -244,16 +120,16 @@ def test_model_without_clamp_is_the_oracle_on_the_moving_block(pkg, orc):
     finally:
         o.free()
     hl = ref[-1]["hlen"]
-    assert hl.max() == N_FRAMES and hl.min() == 1, "the sequence keeps some history and loses some"
+    assert hl.max() == MOVING_FRAMES and hl.min() == 1, "the sequence keeps some history and loses some"
 
 
 # ---- 3. CPU: the statement of the feature, on the model alone ------------------------------------------------------------------------------
 @pytest.mark.parametrize("radius", [0, 1, 2, 3])
 def test_model_a_lighting_change_inside_a_constant_window_is_taken_at_once(pkg, radius):
     frames = feature_sequence(pkg)
-    coords = [hm.pixel_grid(FEATURE_W, FEATURE_H)] * len(frames)
+    coords = [tm.pixel_grid(FEATURE_W, FEATURE_H)] * len(frames)
     for k in ((0.0,) if radius == 0 else (0.0, 1.0, 7.5)):      # any k: sd is 0 where the window is constant
-        res = hm.run_sequence(frames, coords, color_alpha=0.25, moment_alpha=0.25, radius=radius, k=k)
+        res = tm.run_sequence(frames, coords, color_alpha=0.25, moment_alpha=0.25, radius=radius, k=k)
         assert (res[3]["color"] == C0).all() and (res[3]["hlen"] == 4).all(), "frames 0-3 accumulate exactly C0"
         assert_feature(res[4], radius)
 
@@ -364,7 +240,7 @@ def test_gpu_a_lighting_change_inside_a_constant_window_is_taken_at_once(pkg, ra
     W, H = FEATURE_W, FEATURE_H
     frames = feature_sequence(pkg)
     cam = pkg.synth.camera_for_frame(0, False)
-    planes = [hm.pixel_grid(W, H)] * len(frames)
+    planes = [tm.pixel_grid(W, H)] * len(frames)
     params = temporal_only(pkg, color_alpha=0.25, moment_alpha=0.25)
     den = pkg.Denoiser(W, H)
     den.set_history_clamp(radius, 1.0)
@@ -394,7 +270,7 @@ def test_non_finite_colours_are_defined_inputs(pkg, orc, radius, k):
     frames[1] = (col1, frames[1][1])
     cams = [c for _, _, c, _ in seq]
     coords = camera_planes(pkg, seq, COORD)
-    ref = hm.run_sequence(frames, coords, radius=radius, k=k)
+    ref = tm.run_sequence(frames, coords, radius=radius, k=k)
     assert np.isnan(ref[1]["color"]).any() and np.isnan(ref[3]["color"]).any(), "non-finite values reach the history"
     assert np.isfinite(ref[3]["color"]).sum() > ref[3]["color"].size // 2
     den = pkg.Denoiser(W, H)
@@ -405,21 +281,6 @@ def test_non_finite_colours_are_defined_inputs(pkg, orc, radius, k):
 
 
 # ---- 8. GPU: whole frames ------------------------------------------------------------------------------------------------------------------
-def _whole_frames(pkg, den, params, frames, cam):
-    import torch
-    H = W = SIDE
-    outs, keep = [], []
-    for col, gb, _ in frames:
-        t_c = torch.from_numpy(col).cuda()
-        t_g = torch.from_numpy(gb.view(np.uint8).reshape(-1).copy()).cuda()
-        out = torch.empty((H, W, 3), dtype=torch.float32, device="cuda")
-        keep.append((t_c, t_g, out))
-        torch.cuda.synchronize()
-        den.denoise(out, t_c, t_g, cam, params)
-    den.sync()
-    return [o.cpu().numpy() for _, _, o in keep], [den.read_state(k) for k in (0, 1, 2)]
-
-
 @pytest.mark.gpu
 def test_whole_frames_ordered_promised_and_strict_gather_agree(pkg):
     cam, frames = moving_block_sequence(pkg)
@@ -443,13 +304,13 @@ def test_whole_frames_ordered_promised_and_strict_gather_agree(pkg):
             d.free()
 
     ordered, strict, promised = run(), run(variant=1), run(promised=True)
-    for f in range(N_FRAMES):
+    for f in range(MOVING_FRAMES):
         err = float(relerr(ordered[0][f], strict[0][f]).max())
         print(f"frame {f}: kernel_variant 0 against 1, max relative error {err:.3e}")
         assert err <= 1e-5, f"frame {f}"
     if promised is None:
         pytest.skip("the context's two streams share a hardware queue: the promise is refused (variants 0 and 1 agreed)")
-    for f in range(N_FRAMES):
+    for f in range(MOVING_FRAMES):
         assert same_bits(ordered[0][f], promised[0][f]), f"output, frame {f}"
     for k in range(3):
         assert same_bits(ordered[1][k], promised[1][k]), f"state {k}"

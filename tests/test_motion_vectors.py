@@ -8,112 +8,34 @@ bit.  That substitution is the reference of the moving-object test; the camera-p
 by svgf_motion_reproject with no object maps must reproduce svgf_denoise exactly.
 
 Bounds: every comparison here is np.array_equal.  The helper and the camera path share one device function for the projection,
-the numpy replica performs the same float32 operations in the same order without contraction, and everything behind the
-coordinate is the same kernel code; there is no arithmetic that may differ, so there is no tolerance to choose.  The two history
-fractions (<= 0.10 without motion, >= 0.95 with) are the statement of what the feature is for; the oracle gives 0.00 and 1.00."""
+the numpy replica (tests/temporal_model.py) performs the same float32 operations in the same order without contraction, and
+everything behind the coordinate is the same kernel code; there is no arithmetic that may differ, so there is no tolerance to
+choose.  The two history fractions (<= 0.10 without motion, >= 0.95 with) are the statement of what the feature is for; the
+oracle gives 0.00 and 1.00."""
 import ctypes
-import os
 
 import numpy as np
 import pytest
 
-from conftest import ROOT, denoiser_for
+from conftest import denoiser_for
+from temporal_harness import BLOCK, MOVING_FRAMES, SIDE, moving_block_sequence, scales, temporal_only
+from temporal_model import COORD, D16, D32, apply_xf, motion_plane
 
 F = np.float32
-SCENE = os.path.join(ROOT, "tests", "golden", "scenes", "box_room.txt")
-COORD, D32, D16 = 1, 2, 3      # SVGF_MOTION_PREV_COORD_F32, SVGF_MOTION_DELTA_F32, SVGF_MOTION_DELTA_F16
 NEW_SYMBOLS = ("svgf_denoise_motion", "svgf_denoise_planar_motion", "svgf_motion_reproject")
 
 
-# ---- float32 replicas (numpy rounds every array operation to float32: the kernel's arithmetic with contraction off) -------------
-def apply_xf(X, gid, pos):
-    """pos float32[..., 3] mapped by X[gid] (float32[n, 12], 3x4 row-major) where 0 <= gid < n: ((m0 v0 + m1 v1) + m2 v2) + m3."""
-    pos = np.asarray(pos, dtype=F)
-    if X is None or len(X) == 0:
-        return pos
-    ok = (gid >= 0) & (gid < len(X))
-    m = np.asarray(X, dtype=F).reshape(-1, 3, 4)[np.where(ok, gid, 0)]
-    out = np.stack([((m[..., r, 0] * pos[..., 0] + m[..., r, 1] * pos[..., 1]) + m[..., r, 2] * pos[..., 2]) + m[..., r, 3]
-                    for r in range(3)], axis=-1).astype(F)
-    return np.where(ok[..., None], out, pos)
-
-
-def project_prev(M, W, H, sx, sy, pos):
-    """svgf_project_prev: world position through the previous view matrix M (float32[16], column-major) to (prevx, prevy)."""
-    M = np.asarray(M, dtype=F)
-    px, py, pz = pos[..., 0], pos[..., 1], pos[..., 2]
-    with np.errstate(all="ignore"):
-        vs = [(M[r] * px + M[4 + r] * py) + (M[8 + r] * pz + M[12 + r] * F(1)) for r in range(3)]
-        clipx, clipy = vs[0] / vs[2], vs[1] / vs[2]
-        if sx > 0:
-            clipx = clipx / F(sx)
-        if sy > 0:
-            clipy = clipy / F(sy)
-        ndcx, ndcy = -clipx * F(0.5) + F(0.5), -clipy * F(0.5) + F(0.5)
-        return np.stack([ndcx * F(W) - F(0.5), ndcy * F(H) - F(0.5)], axis=-1).astype(F)
-
-
-def motion_plane(M, W, H, sx, sy, gb, X, fmt):
-    """What svgf_motion_reproject writes for the texels `gb` (GBUFFER_DTYPE[H, W])."""
-    gid = gb["geomId"]
-    prev = project_prev(M, W, H, sx, sy, apply_xf(X, gid, gb["position"]))
-    if fmt != COORD:
-        ys, xs = np.mgrid[0:H, 0:W]
-        prev = (prev - np.stack([xs, ys], axis=-1).astype(F)).astype(F)
-    prev = np.where((gid == -1)[..., None], F(np.nan), prev).astype(F)
-    with np.errstate(over="ignore"):
-        return prev.astype(np.float16) if fmt == D16 else prev
-
-
-def scales(pkg, W, H):
-    plx, ply = pkg.synth._pixel_length(W, H, 45.0)
-    return float(plx) * W / 2.0, float(ply) * H / 2.0
-
-
 # ---- the moving block of box_room.txt (checks 1 and 5) ---------------------------------------------------------------------------
-MOVING_OBJECT, STEP_X, N_FRAMES, SIDE = 7, 0.4, 6, 96
-
-
-def moving_block_sequence(pkg):
-    """Six frames of box_room at 96x96 under a static camera, the turned block translated by +0.4 in x per frame.  Per frame:
-    (colour, true texels, X float32[n, 12]), X[g] = xf_prev[g] * inv_cur[g] composed in float64 and rounded — this frame's world
-    space to the previous frame's (frame 0: identities).  Computed once per session."""
-    if not hasattr(moving_block_sequence, "cache"):
-        sc = pkg.scene.parse_scene(open(SCENE).read())
-        cam = pkg.scene.camera_for_frame(sc, 0, False)
-        x0 = sc.objects[MOVING_OBJECT]["trans"][0]
-        frames, prev = [], None
-        for f in range(N_FRAMES):
-            o = sc.objects[MOVING_OBJECT]
-            o["trans"] = (x0 + STEP_X * f,) + tuple(o["trans"][1:])
-            g = pkg.scene.geom_array(sc)
-            col, gb = pkg.scene.render_scene(SIDE, SIDE, f, g, cam, seed=3)
-            X = np.tile(np.eye(3, 4).reshape(-1), (len(g), 1))
-            if prev is not None:
-                for k in range(len(g)):
-                    a = np.vstack([prev[k]["xf"].astype(np.float64).reshape(3, 4), [0, 0, 0, 1]])
-                    b = np.vstack([g[k]["inv"].astype(np.float64).reshape(3, 4), [0, 0, 0, 1]])
-                    X[k] = (a @ b)[:3].reshape(-1)
-            frames.append((col, gb, X.astype(F)))
-            prev = g
-        moving_block_sequence.cache = (cam, frames)
-    return moving_block_sequence.cache
-
-
 def substituted(gb, X):
     out = gb.copy()
     out["position"] = apply_xf(X, gb["geomId"], gb["position"])
     return out
 
 
-def temporal_only(pkg):
-    return pkg.reference_defaults().set(temporal_enable=1, spatial_enable=0)
-
-
 def full_history_fraction(hlen, gb):
-    block = gb["geomId"] == MOVING_OBJECT
+    block = gb["geomId"] == BLOCK
     assert np.count_nonzero(block) > 150
-    return float(np.count_nonzero(hlen[block] == N_FRAMES)) / float(np.count_nonzero(block))
+    return float(np.count_nonzero(hlen[block] == MOVING_FRAMES)) / float(np.count_nonzero(block))
 
 
 def oracle_moving_block(pkg, orc, substitute):
@@ -158,7 +80,7 @@ def test_oracle_loses_the_moving_block_and_keeps_it_with_its_previous_position(p
     gb = frames[-1][1]
     lost = full_history_fraction(oracle_moving_block(pkg, orc, False)[-1][1], gb)
     kept = full_history_fraction(oracle_moving_block(pkg, orc, True)[-1][1], gb)
-    print(f"block pixels {np.count_nonzero(gb['geomId'] == MOVING_OBJECT)}: full history on {lost:.3f} (true positions), {kept:.3f} (substituted)")
+    print(f"block pixels {np.count_nonzero(gb['geomId'] == BLOCK)}: full history on {lost:.3f} (true positions), {kept:.3f} (substituted)")
     assert lost <= 0.10
     assert kept >= 0.95
 
@@ -201,7 +123,7 @@ def test_motion_reproject_matches_numpy_bit_for_bit(pkg, orc, W, H, planes):
                 pkg.binding.motion_reproject(out, W, H, cam, motion_format=fmt, reproj_scale=(sx, sy),
                                              geom_xf=None if xf is None else t_x, **src)
                 torch.cuda.synchronize()
-                got, ref = out.cpu().numpy(), motion_plane(M, W, H, sx, sy, gb, xf, fmt)
+                got, ref = out.cpu().numpy(), motion_plane(M, W, H, gb, xf, fmt, sx, sy)
                 assert np.isnan(got[gb["geomId"] == -1]).all(), "ray misses are NaN"
                 bits = np.uint16 if fmt == D16 else np.uint32
                 nan = np.isnan(ref)
@@ -334,7 +256,7 @@ def test_non_finite_and_huge_coordinates_mean_no_history(pkg, orc, fmt):
     frames = [pkg.synth.render_frame(W, H, f, seed=13, moving=False, noise_model="hash") for f in range(2)]
     cam = frames[0][2]
     M = orc.view_matrix(pkg, cam)
-    clean = motion_plane(M, W, H, F(sx), F(sy), frames[1][1].reshape(H, W), None, fmt)
+    clean = motion_plane(M, W, H, frames[1][1].reshape(H, W), None, fmt, F(sx), F(sy))
     bad_values = [F(np.nan), F(np.inf), F(-np.inf), F(1e30), F(-1e30)]
     runs = {}
     for tag in ("clean", "bad"):

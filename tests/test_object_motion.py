@@ -1,9 +1,10 @@
 """Rigid object motion in the temporal pass (include/svgf.h: svgf_set_object_motion / svgf_get_object_motion).
 
-The yardstick is tests/object_motion_model.py, a float32 numpy model of the whole temporal pass.  The oracle knows no table;
-the tests of section 2 pin the model three ways: to tests/history_clamp_model.py without a table, to the oracle's position test
-without a table, and to the oracle on texels whose normal and position were replaced by the moved ones (as far as that
-substitution reaches: two frames, the oracle keeps the substituted texels as its history).
+The yardstick is tests/temporal_model.py, the float32 numpy model of the whole temporal pass.  The oracle knows no table;
+the tests of section 2 pin the model three ways: without a table, to the results recorded from the model the history clamp's
+suite was written against (tests/golden/temporal_model/moving_block.json); to the oracle's position test without a table; and to
+the oracle on texels whose normal and position were replaced by the moved ones (as far as that substitution reaches: two frames,
+the oracle keeps the substituted texels as its history).
 
 Bounds: every comparison of the kernel with the model is on the bits of every pixel (NaNs in the same place count as equal).
 Both sides perform the same float32 operations in the same order without contraction, and division and square root are
@@ -12,57 +13,23 @@ this file, 1e-5 between kernel_variant 0 and 1 on whole frames, is the project's
 (tests/test_parity_gpu.py, tests/test_history_clamp.py): the table changes their input, not them.  The fractions 0.10 / 0.95 of
 the turning block are the issue's (the oracle gives 0.00 / 1.00)."""
 import ctypes
+import hashlib
+import json
 import os
 
 import numpy as np
 import pytest
 
-import history_clamp_model as hm
-import object_motion_model as om
+import temporal_model as tm
 from conftest import ROOT, relerr
+from temporal_harness import (BLOCK, SIDE, _whole_frames, assert_frames_equal, block_sequence, device_table, moving_block_sequence,
+                              read_states, run_gpu, same_bits, scales, synth_params, synth_sequence, temporal_only)
 
 F = np.float32
-COORD, D32, D16 = om.COORD, om.D32, om.D16
-SCENE = os.path.join(ROOT, "tests", "golden", "scenes", "box_room.txt")
+COORD, D32, D16 = tm.COORD, tm.D32, tm.D16
 NEW_SYMBOLS = ("svgf_set_object_motion", "svgf_get_object_motion")
-STATES = ("hlen", "mom", "color", "variance", "acc")      # svgf_read_state 0..4
+MODEL_GOLDEN = os.path.join(ROOT, "tests", "golden", "temporal_model", "moving_block.json")
 TOLS = (0.0, 0.3)
-
-
-def same_bits(a, b):
-    a, b = np.asarray(a), np.asarray(b)
-    if a.shape != b.shape or a.dtype != b.dtype:
-        return False
-    if a.dtype.kind != "f":
-        return bool(np.array_equal(a, b))
-    na, nb = np.isnan(a), np.isnan(b)
-    return bool(np.array_equal(na, nb) and np.array_equal(a.view(np.uint32)[~na], b.view(np.uint32)[~nb]))
-
-
-def assert_frames_equal(got, ref, what):
-    """got: per frame the five states read from a context; ref: per frame the model's dict (acc = color with the spatial filter off)."""
-    assert len(got) == len(ref)
-    for f, (g, r) in enumerate(zip(got, ref)):
-        for name in STATES:
-            want = r["color" if name == "acc" else name]
-            bad = "" if same_bits(g[name], want) else f"{np.count_nonzero(~np.isclose(g[name], want, rtol=0, atol=0, equal_nan=True))} values differ"
-            assert not bad, f"{what}: {name}, frame {f}: {bad}"
-
-
-def temporal_only(pkg, **kw):
-    return pkg.reference_defaults().set(**{**dict(temporal_enable=1, spatial_enable=0), **kw})
-
-
-def scales(pkg, W, H):
-    """SvgfParams::reproj_scale that makes the reprojection exact at any aspect (as tests/test_history_clamp.py)."""
-    plx, ply = pkg.synth._pixel_length(W, H, 45.0)
-    return float(plx) * W / 2.0, float(ply) * H / 2.0
-
-
-def synth_params(pkg, W, H, **kw):
-    p = temporal_only(pkg, **kw)
-    p.reproj_scale[0], p.reproj_scale[1] = scales(pkg, W, H)
-    return p
 
 
 def rotation(axis, degrees):
@@ -99,9 +66,8 @@ def mixed_sequence(pkg, orc, W, H, n=4, finite=False):
     cache = mixed_sequence.__dict__.setdefault("cache", {})
     if (W, H, n, finite) not in cache:
         seq = []
-        for f in range(n):
-            col, gb, cam = pkg.synth.render_frame(W, H, f, seed=11, moving=True, noise_model="hash")
-            gb = gb.copy().reshape(H, W)
+        for f, (col, gb, cam, M) in enumerate(synth_sequence(pkg, orc, W, H, n, seed=11)):
+            gb = gb.copy()
             rng = np.random.default_rng(W * 1000 + H + 17 * f)
             flat = gb.reshape(-1)
             m = flat.size
@@ -112,21 +78,9 @@ def mixed_sequence(pkg, orc, W, H, n=4, finite=False):
                 if not finite:
                     flat["position"][bad] = (np.nan, np.inf, -1e30)
                 flat["position"][rng.integers(0, m, 2)] = (0.0, 5.0, 60.0)      # behind the camera
-            seq.append((np.asarray(col, F).reshape(H, W, 3), gb, cam, orc.view_matrix(pkg, cam)))
+            seq.append((col, gb, cam, M))
         cache[(W, H, n, finite)] = seq
     return cache[(W, H, n, finite)]
-
-
-def clean_sequence(pkg, orc, W, H, n=4):
-    """The same frames with the texels as rendered (finite positions), seed 31: the sequence of tests/test_history_clamp.py."""
-    cache = clean_sequence.__dict__.setdefault("cache", {})
-    if (W, H, n) not in cache:
-        seq = []
-        for f in range(n):
-            col, gb, cam = pkg.synth.render_frame(W, H, f, seed=31, moving=True, noise_model="hash")
-            seq.append((np.asarray(col, F).reshape(H, W, 3), gb.reshape(H, W), cam, orc.view_matrix(pkg, cam)))
-        cache[(W, H, n)] = seq
-    return cache[(W, H, n)]
 
 
 def mixed_model(pkg, orc, W, H, fmt, tol, radius=0, k=0.0):
@@ -140,51 +94,18 @@ def mixed_model(pkg, orc, W, H, fmt, tol, radius=0, k=0.0):
         views = [seq[max(f - 1, 0)][3] for f in range(len(seq))]
         coords = None
         if fmt is not None:
-            coords = [om.coord_plane(om.motion_plane(views[f], W, H, seq[f][1], X, fmt, F(sx), F(sy)), fmt, W, H) for f in range(len(seq))]
-        cache[key] = om.run_sequence([(c, g) for c, g, _, _ in seq], coords=coords, tables=[X] * len(seq), views=views, scale=(sx, sy),
+            coords = [tm.coord_plane(tm.motion_plane(views[f], W, H, seq[f][1], X, fmt, F(sx), F(sy)), fmt, W, H) for f in range(len(seq))]
+        cache[key] = tm.run_sequence([(c, g) for c, g, _, _ in seq], coords=coords, tables=[X] * len(seq), views=views, scale=(sx, sy),
                                      pos_tol=tol, radius=radius, k=k)
     return cache[key]
 
 
-TURNING_OBJECT, TURN_DEG, SLIDE_X, TURN_FRAMES, SIDE = 7, 9.0, 1.0, 4, 96
-
-
-def block_sequence(pkg, n, slide_x, turn_deg):
-    """n frames of box_room at 96x96 under a static camera, the turned block (object 7) rotated by turn_deg about y and translated
-    by slide_x in x per frame.  Returns (camera, [(colour, texels, X float32[n_geoms, 12])]); X[g] = xf_prev[g] * inv_cur[g] composed
-    in float64 and rounded: this frame's world space to the previous frame's (frame 0: identities).  Computed once per session."""
-    cache = block_sequence.__dict__.setdefault("cache", {})
-    if (n, slide_x, turn_deg) not in cache:
-        sc = pkg.scene.parse_scene(open(SCENE).read())
-        cam = pkg.scene.camera_for_frame(sc, 0, False)
-        t0, r0 = tuple(sc.objects[TURNING_OBJECT]["trans"]), tuple(sc.objects[TURNING_OBJECT]["rotat"])
-        frames, prev = [], None
-        for f in range(n):
-            o = sc.objects[TURNING_OBJECT]
-            o["trans"] = (t0[0] + slide_x * f,) + t0[1:]
-            o["rotat"] = (r0[0], r0[1] + turn_deg * f, r0[2])
-            g = pkg.scene.geom_array(sc)
-            col, gb = pkg.scene.render_scene(SIDE, SIDE, f, g, cam, seed=3)
-            X = np.tile(np.eye(3, 4).reshape(-1), (len(g), 1))
-            if prev is not None:
-                for k in range(len(g)):
-                    a = np.vstack([prev[k]["xf"].astype(np.float64).reshape(3, 4), [0, 0, 0, 1]])
-                    b = np.vstack([g[k]["inv"].astype(np.float64).reshape(3, 4), [0, 0, 0, 1]])
-                    X[k] = (a @ b)[:3].reshape(-1)
-            frames.append((np.asarray(col, F).reshape(SIDE, SIDE, 3), gb.reshape(SIDE, SIDE), X.astype(F)))
-            prev = g
-        cache[(n, slide_x, turn_deg)] = (cam, frames)
-    return cache[(n, slide_x, turn_deg)]
+TURN_DEG, SLIDE_X, TURN_FRAMES = 9.0, 1.0, 4
 
 
 def turning_block_sequence(pkg):
     """The issue's sequence: four frames, +9 degrees about y and +1.0 in x per frame."""
     return block_sequence(pkg, TURN_FRAMES, SLIDE_X, TURN_DEG)
-
-
-def moving_block_sequence(pkg):
-    """The six frames of tests/test_history_clamp.py and tests/test_motion_vectors.py: +0.4 in x per frame, no rotation."""
-    return block_sequence(pkg, 6, 0.4, 0.0)
 
 
 def turning_block_model(pkg, orc, table, tol):
@@ -196,73 +117,18 @@ def turning_block_model(pkg, orc, table, tol):
         M = orc.view_matrix(pkg, cam)
         fr = [(c, g) for c, g, _ in frames]
         if table:
-            cache[(table, tol)] = om.run_sequence(fr, tables=[X for _, _, X in frames], views=[M] * len(fr), pos_tol=tol)
+            cache[(table, tol)] = tm.run_sequence(fr, tables=[X for _, _, X in frames], views=[M] * len(fr), pos_tol=tol)
         else:
-            coords = [om.motion_plane(M, SIDE, SIDE, gb, X, COORD) for _, gb, X in frames]
-            cache[(table, tol)] = om.run_sequence(fr, coords=coords, pos_tol=tol)
+            coords = [tm.motion_plane(M, SIDE, SIDE, gb, X, COORD) for _, gb, X in frames]
+            cache[(table, tol)] = tm.run_sequence(fr, coords=coords, pos_tol=tol)
     return cache[(table, tol)]
 
 
 def kept_fraction(hlen, gb):
     """The fraction of the block's pixels whose history length is at least 2."""
-    block = gb["geomId"] == TURNING_OBJECT
+    block = gb["geomId"] == BLOCK
     assert np.count_nonzero(block) > 150
     return float(np.count_nonzero(hlen[block] >= 2)) / float(np.count_nonzero(block))
-
-
-# ---- the GPU side ---------------------------------------------------------------------------------------------------------------------
-def _hip():
-    """The HIP runtime already loaded into this process (torch's), for plain host-to-device copies into raw pointers."""
-    for ln in open("/proc/self/maps"):
-        if "libamdhip64" in ln:
-            return ctypes.CDLL(ln.split()[-1])
-    raise RuntimeError("no HIP runtime loaded")
-
-
-def read_states(den):
-    return {name: den.read_state(k) for k, name in enumerate(STATES)}
-
-
-def run_gpu(pkg, den, frames, params, cams, leg="aos", plane_fmt=None, plane_tables=None):
-    """frames: [(colour, texels)]; cams: per frame.  The context's table is whatever the caller set.  plane_fmt: the history is
-    looked up through the plane svgf_motion_reproject writes in that format for the previous frame's camera, params' reproj_scale
-    and plane_tables[f] (None: the camera path).  Returns per frame the five states.  `leg`: aos | planar."""
-    import torch
-    H, W = frames[0][1].shape
-    den.set_capture(True)
-    out, res, keep = torch.empty((H, W, 3), dtype=torch.float32, device="cuda"), [], []
-    rs = (params.reproj_scale[0], params.reproj_scale[1])
-    for f, (col, gb) in enumerate(frames):
-        t_c = torch.from_numpy(np.ascontiguousarray(col, dtype=F)).cuda()
-        t_g = torch.from_numpy(np.ascontiguousarray(gb).view(np.uint8).reshape(-1).copy()).cuda()
-        mv = None
-        if plane_fmt is not None:
-            mv = torch.empty((H, W, 2), dtype=torch.float16 if plane_fmt == D16 else torch.float32, device="cuda")
-            t_x = None if plane_tables is None or plane_tables[f] is None else torch.from_numpy(np.ascontiguousarray(plane_tables[f])).cuda()
-            pkg.binding.motion_reproject(mv, W, H, cams[max(f - 1, 0)], gbuffer=t_g, motion_format=plane_fmt, reproj_scale=rs, geom_xf=t_x)
-            keep.append(t_x)
-        keep.append((t_c, t_g, mv))      # (a promised frame's inputs stay untouched until its work is done)
-        torch.cuda.synchronize()
-        if leg == "planar":
-            g = den.planar_gbuffer()
-            hip = _hip()
-            hip.hipMemcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
-            flat = np.ascontiguousarray(gb).reshape(-1)
-            for dst, arr in ((g.normal, flat["normal"]), (g.position, flat["position"]), (g.geom_id, flat["geomId"]),
-                             (g.albedo, (flat["albedo"] * flat["ialbedo"]).astype(F))):
-                arr = np.ascontiguousarray(arr)
-                assert hip.hipMemcpy(dst, arr.ctypes.data, arr.nbytes, 1) == 0
-            den.denoise_planar(out, t_c, cams[f], params, motion=mv, motion_format=plane_fmt or COORD)
-        else:
-            den.denoise(out, t_c, t_g, cams[f], params, motion=mv, motion_format=plane_fmt or COORD)
-        den.sync()
-        res.append(read_states(den))
-    return res
-
-
-def device_table(X):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(X, dtype=F)).cuda()
 
 
 # ---- 1. CPU: symbols and the NULL context ----------------------------------------------------------------------------------------------
@@ -281,30 +147,61 @@ def test_symbols_are_exported_and_a_null_context_is_invalid(pkg):
 
 
 # ---- 2. CPU: the model is a model --------------------------------------------------------------------------------------------------------
+def _digest(a):
+    """dtype, shape and the SHA-256 of the array's bytes, every NaN first set to the one pattern 0x7fc00000."""
+    a = np.ascontiguousarray(a).copy()
+    if a.dtype.kind == "f":
+        a.view(np.uint32)[np.isnan(a)] = 0x7fc00000
+    return dict(dtype=str(a.dtype), shape=list(a.shape), sha256=hashlib.sha256(a.tobytes()).hexdigest())
+
+
+GOLDEN_SETTINGS = ((0, 0.0), (1, 1.0), (2, 1.0), (3, 2.5))      # (radius, k)
+
+
 def test_model_without_table_is_the_clamp_model_on_the_moving_block(pkg, orc):
-    """No table, tol 0, the six frames of tests/test_history_clamp.py's moving block, the history clamp off and on."""
+    """No table, tol 0, the six frames of the moving block, the history clamp off and at three settings: the model reproduces
+    what tests/history_clamp_model.py gave (the model test_history_clamp.py was written against, the file as of commit 4a1160b;
+    tests/temporal_model.py is that file extended).  MODEL_GOLDEN holds, per setting, frame and state, that result's digest.  It
+    is a record, not to be rewritten from temporal_model.py; it was written, with that file put back beside this one, by
+
+        import history_clamp_model as hm
+        cam, frames = moving_block_sequence(pkg)
+        M = orc.view_matrix(pkg, cam)
+        coords = [hm.motion_plane(M, SIDE, SIDE, gb, X, COORD) for _, gb, X in frames]
+        fr = [(c, g) for c, g, _ in frames]
+        doc = {f"radius={radius},k={k}": [{name: _digest(res[name]) for name in ("hlen", "mom", "color", "variance")}
+                                          for res in hm.run_sequence(fr, coords, radius=radius, k=k)]
+               for radius, k in GOLDEN_SETTINGS}
+        os.makedirs(os.path.dirname(MODEL_GOLDEN), exist_ok=True)
+        json.dump(doc, open(MODEL_GOLDEN, "w"), indent=1)
+
+    in place of this test's body."""
     cam, frames = moving_block_sequence(pkg)
     M = orc.view_matrix(pkg, cam)
-    coords = [hm.motion_plane(M, SIDE, SIDE, gb, X, COORD) for _, gb, X in frames]
+    coords = [tm.motion_plane(M, SIDE, SIDE, gb, X, COORD) for _, gb, X in frames]
     fr = [(c, g) for c, g, _ in frames]
-    for radius, k in ((0, 0.0), (2, 1.0)):
-        ref, got = hm.run_sequence(fr, coords, radius=radius, k=k), om.run_sequence(fr, coords=coords, radius=radius, k=k)
+    golden = json.load(open(MODEL_GOLDEN))
+    assert sorted(golden) == sorted(f"radius={radius},k={k}" for radius, k in GOLDEN_SETTINGS)
+    for radius, k in GOLDEN_SETTINGS:
+        ref, got = golden[f"radius={radius},k={k}"], tm.run_sequence(fr, coords=coords, radius=radius, k=k)
+        assert len(got) == len(ref) == len(fr)
         for f in range(len(fr)):
-            for name in ("hlen", "mom", "color", "variance"):
-                assert same_bits(got[f][name], ref[f][name]), f"radius {radius}: {name}, frame {f}"
+            assert sorted(ref[f]) == ["color", "hlen", "mom", "variance"]
+            for name in ref[f]:
+                assert _digest(got[f][name]) == ref[f][name], f"radius {radius}, k {k}: {name}, frame {f}"
     # and its camera path is that model fed the plane of the substituted positions
-    cam_path = om.run_sequence(fr, tables=[X for _, _, X in frames], views=[M] * len(fr))
-    assert same_bits(cam_path[1]["hlen"], hm.run_sequence(fr, coords)[1]["hlen"]), "a pure translation leaves the normals alone"
+    cam_path = tm.run_sequence(fr, tables=[X for _, _, X in frames], views=[M] * len(fr))
+    assert same_bits(cam_path[1]["hlen"], tm.run_sequence(fr, coords=coords)[1]["hlen"]), "a pure translation leaves the normals alone"
 
 
 @pytest.mark.parametrize("tol", [0.3, 0.05])
 def test_model_position_test_is_the_oracle(pkg, orc, tol):
     """No table, reproj_position_tol 0.3 and 0.05, four frames of synth.render_frame(67, 41, moving=True)."""
     W, H = 67, 41
-    seq = clean_sequence(pkg, orc, W, H)
+    seq = synth_sequence(pkg, orc, W, H)
     views = [seq[max(f - 1, 0)][3] for f in range(len(seq))]
-    ref = om.run_sequence([(c, g) for c, g, _, _ in seq], views=views, scale=scales(pkg, W, H), pos_tol=tol)
-    off = om.run_sequence([(c, g) for c, g, _, _ in seq], views=views, scale=scales(pkg, W, H))
+    ref = tm.run_sequence([(c, g) for c, g, _, _ in seq], views=views, scale=scales(pkg, W, H), pos_tol=tol)
+    off = tm.run_sequence([(c, g) for c, g, _, _ in seq], views=views, scale=scales(pkg, W, H))
     p = synth_params(pkg, W, H, reproj_position_tol=tol)
     o = orc.Oracle(pkg, W, H, threads=4)
     try:
@@ -329,8 +226,8 @@ def test_model_with_table_is_the_oracle_on_substituted_texels(pkg, orc, tol):
     try:
         for f, (col, gb, X) in enumerate(frames[:2]):
             sub = gb.copy()
-            sub["position"] = om.apply_xf(X, gb["geomId"], gb["position"])
-            sub["normal"] = om.moved_normal(X, gb["geomId"], gb["normal"])
+            sub["position"] = tm.apply_xf(X, gb["geomId"], gb["position"])
+            sub["normal"] = tm.moved_normal(X, gb["geomId"], gb["normal"])
             o.denoise(col, sub, cam, p)
             assert same_bits(o.read_state(0), ref[f]["hlen"]), f"history length, frame {f}"
             assert same_bits(o.read_state(1), ref[f]["mom"]), f"moments, frame {f}"
@@ -347,7 +244,7 @@ def test_model_turning_block_loses_its_history_without_the_table_and_keeps_it_wi
     gb = frames[-1][1]
     lost = kept_fraction(turning_block_model(pkg, orc, False, tol)[-1]["hlen"], gb)
     kept = kept_fraction(turning_block_model(pkg, orc, True, tol)[-1]["hlen"], gb)
-    print(f"tol {tol}: block pixels {np.count_nonzero(gb['geomId'] == TURNING_OBJECT)}, history >= 2 on {lost:.3f} (plane, true normal and "
+    print(f"tol {tol}: block pixels {np.count_nonzero(gb['geomId'] == BLOCK)}, history >= 2 on {lost:.3f} (plane, true normal and "
           f"position), {kept:.3f} (table)")
     assert lost <= 0.10
     assert kept >= 0.95
@@ -360,7 +257,7 @@ def test_model_inputs_of_the_gpu_suite_fall_on_both_sides_of_both_tests(pkg, orc
     seq = mixed_sequence(pkg, orc, W, H)
     on0, on3 = mixed_model(pkg, orc, W, H, None, 0.0), mixed_model(pkg, orc, W, H, None, 0.3)
     views = [seq[max(f - 1, 0)][3] for f in range(len(seq))]
-    off = om.run_sequence([(c, g) for c, g, _, _ in seq], views=views, scale=scales(pkg, W, H))
+    off = tm.run_sequence([(c, g) for c, g, _, _ in seq], views=views, scale=scales(pkg, W, H))
     last = seq[-1][1]["geomId"]
     assert on0[-1]["hlen"].max() >= 3 and on3[-1]["hlen"].max() >= 3
     assert not np.array_equal(on0[-1]["hlen"], off[-1]["hlen"])
@@ -455,7 +352,7 @@ def test_a_table_of_exact_identities_is_plain_svgf_denoise(pkg, orc):
     """On frames with finite positions ((1 p + 0 p) + 0 p) + 0 is p; whole frames, 5 levels."""
     import torch
     W, H = 67, 41
-    seq = clean_sequence(pkg, orc, W, H)
+    seq = synth_sequence(pkg, orc, W, H)
     p = _full(pkg, W, H, reproj_position_tol=0.3)
     a, b = pkg.Denoiser(W, H), pkg.Denoiser(W, H)
     t_x = device_table(np.tile(np.eye(3, 4).reshape(-1), (9, 1)))
@@ -535,7 +432,7 @@ def test_off_is_off_and_the_pass_stays_one_temporal_kernel(pkg, orc):
     assert toggled.object_motion() == (None, 0)
     a, b = run_gpu(pkg, fresh, frames, params, cams), run_gpu(pkg, toggled, frames, params, cams)
     views = [seq[max(f - 1, 0)][3] for f in range(len(seq))]
-    ref = om.run_sequence(frames, views=views, scale=scales(pkg, W, H), pos_tol=0.3)
+    ref = tm.run_sequence(frames, views=views, scale=scales(pkg, W, H), pos_tol=0.3)
     assert_frames_equal(a, ref, "never set")
     assert_frames_equal(b, ref, "set, then unset")
     # a pointer with n_geoms 0 is off too
@@ -649,24 +546,6 @@ def test_parked_fused_temporal_kernels_refuse_a_frame_with_a_table(pkg, experime
 
 
 # ---- 9. GPU: whole frames ------------------------------------------------------------------------------------------------------------------
-def _whole_frames(pkg, den, params, frames, cam):
-    import torch
-    H = W = SIDE
-    outs, keep = [], []
-    n_geoms = frames[0][2].shape[0]
-    for col, gb, X in frames:
-        t_c = torch.from_numpy(col).cuda()
-        t_g = torch.from_numpy(gb.view(np.uint8).reshape(-1).copy()).cuda()
-        t_x = device_table(X)      # one table per frame: a promised frame's table stays untouched until the frame is done
-        out = torch.empty((H, W, 3), dtype=torch.float32, device="cuda")
-        keep.append((t_c, t_g, t_x, out))
-        torch.cuda.synchronize()
-        den.set_object_motion(t_x, n_geoms)
-        den.denoise(out, t_c, t_g, cam, params)
-    den.sync()
-    return [o.cpu().numpy() for _, _, _, o in keep], [den.read_state(k) for k in (0, 1, 2)]
-
-
 @pytest.mark.gpu
 def test_whole_frames_ordered_promised_and_strict_gather_agree(pkg):
     """Full SVGF, 5 levels, history from level 1, on the turning block with its table: the bounds of
@@ -683,7 +562,7 @@ def test_whole_frames_ordered_promised_and_strict_gather_agree(pkg):
                 return None
             p.inputs_ready = 1
         try:
-            res = _whole_frames(pkg, d, p, frames, cam)
+            res = _whole_frames(pkg, d, p, frames, cam, tables=True)
             if promised:
                 assert d.is_pipelined()
             return res

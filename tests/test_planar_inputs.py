@@ -8,16 +8,9 @@ import numpy as np
 import pytest
 
 from conftest import denoiser_for, golden_cases, load_golden, replay
+from temporal_harness import _hip
 
 pytestmark = pytest.mark.gpu
-
-
-def _hip():
-    """The HIP runtime already loaded into this process (torch's), for plain host-to-device copies into raw pointers."""
-    for ln in open("/proc/self/maps"):
-        if "libamdhip64" in ln:
-            return ctypes.CDLL(ln.split()[-1])
-    raise RuntimeError("no HIP runtime loaded")
 
 
 class AosEngine:

@@ -7,11 +7,7 @@ import numpy as np
 import pytest
 
 from conftest import relerr
-
-
-def _scales(pkg, W, H):
-    plx, ply = pkg.synth._pixel_length(W, H, 45.0)
-    return float(plx) * W / 2.0, float(ply) * H / 2.0        # (tan(FOVY) * W / H, tan(FOVY))
+from temporal_harness import scales
 
 
 def _params(pkg, sx, sy, nlevel=5):
@@ -24,7 +20,7 @@ def test_exact_reprojection_keeps_history_at_16_9(pkg, orc):
     """Static camera, 16:9: the reference mapping loses the history of most pixels every frame (SURVEY.md §8a row A6);
     with reproj_scale every visible surface pixel re-finds itself."""
     W, H, nf = 320, 180, 5
-    sx, sy = _scales(pkg, W, H)
+    sx, sy = scales(pkg, W, H)
     assert sx == pytest.approx(16.0 / 9.0, rel=1e-6) and sy == pytest.approx(1.0, rel=1e-6)
     frames = [pkg.synth.render_frame(W, H, f, seed=4, noise_model="hash") for f in range(nf)]
     hit = frames[0][1]["geomId"] >= 0
@@ -56,7 +52,7 @@ def test_zero_scale_is_the_reference_path(pkg, orc):
 @pytest.mark.parametrize("W,H,moving", [(320, 180, False), (320, 180, True), (200, 200, True), (257, 131, True)])
 def test_hip_matches_oracle_with_reproj_scale(pkg, orc, W, H, moving):
     nf = 4
-    sx, sy = _scales(pkg, W, H)
+    sx, sy = scales(pkg, W, H)
     params = _params(pkg, sx, sy)
     frames = [pkg.synth.render_frame(W, H, f, seed=6, moving=moving, noise_model="hash") for f in range(nf)]
     den = pkg.Denoiser(W, H)

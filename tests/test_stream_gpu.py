@@ -14,15 +14,9 @@ import ctypes
 import numpy as np
 import pytest
 
+from temporal_harness import _hip
+
 pytestmark = pytest.mark.gpu
-
-
-def _hip():
-    """The HIP runtime already loaded into this process (torch's)."""
-    for ln in open("/proc/self/maps"):
-        if "libamdhip64" in ln:
-            return ctypes.CDLL(ln.split()[-1])
-    raise RuntimeError("no HIP runtime loaded")
 
 
 def _frames(pkg, W, H, n, seed):
