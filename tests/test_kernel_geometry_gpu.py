@@ -8,7 +8,10 @@ the kernel of every level of the last frame (Denoiser.level_kernels); these test
 to what the product library computes (bit-identical outputs), and compare EVERY level, not only the last, with the oracle.
 
 The segment-length sweep forces every segment length 1 .. 13 through svgf_exp_set("lane_segrows" / "strip_segrows"): every level
-of every length meets the oracle bar, and two lengths differ by no more than rounding (TOL_ACROSS_L)."""
+of every length meets the oracle bar, and two lengths differ by no more than rounding (TOL_ACROSS_L).
+
+The frames here run with the reference's default sigmas, on which levels 4 and 5 give their taps next to no weight: the coarse levels
+are held to the oracle on frames they act on by tests/test_coarse_levels_gpu.py (inputs and conditions: tests/test_coarse_levels_coverage.py)."""
 import numpy as np
 import pytest
 
