@@ -36,7 +36,8 @@ EXPORTS = ["svgf_version", "svgf_params_default", "svgf_create", "svgf_destroy",
            "svgf_sync_stream", "svgf_build_has_experiments", "svgf_is_pipelined", "svgf_create_ex", "svgf_enable_pipeline",
            "svgf_pipeline_status", "svgf_planar_gbuffer_stream", "svgf_streams_overlap",
            "svgf_denoise_motion", "svgf_denoise_planar_motion", "svgf_motion_reproject",
-           "svgf_set_history_clamp", "svgf_get_history_clamp", "svgf_set_object_motion", "svgf_get_object_motion"]
+           "svgf_set_history_clamp", "svgf_get_history_clamp", "svgf_set_object_motion", "svgf_get_object_motion",
+           "svgf_set_firefly_filter", "svgf_get_firefly_filter"]
 CREATE_PIPELINED = 1
 # motion plane formats (svgf_denoise_motion): absolute previous coordinate, delta in float32, delta in float16
 MOTION_PREV_COORD_F32, MOTION_DELTA_F32, MOTION_DELTA_F16 = 1, 2, 3
@@ -175,6 +176,8 @@ def load_library(path: str | None = None, experiments: bool = False):
     lib.svgf_motion_reproject.argtypes = [ip, vp, ip, vp, vp, vp, ip, ip, C.POINTER(SvgfCamera), C.POINTER(C.c_float), vp, ip, vp]
     lib.svgf_set_history_clamp.argtypes = [vp, ip, C.c_float]
     lib.svgf_get_history_clamp.argtypes = [vp, C.POINTER(ip), C.POINTER(C.c_float)]
+    lib.svgf_set_firefly_filter.argtypes = [vp, ip, C.c_float]
+    lib.svgf_get_firefly_filter.argtypes = [vp, C.POINTER(ip), C.POINTER(C.c_float)]
     lib.svgf_set_object_motion.argtypes = [vp, vp, ip]
     lib.svgf_get_object_motion.argtypes = [vp, C.POINTER(vp), C.POINTER(ip)]
     lib.svgf_denoise_host.argtypes = [vp, vp, vp, vp, C.POINTER(SvgfCamera), C.POINTER(SvgfParams)]
@@ -383,6 +386,17 @@ class Denoiser:
         """(radius, sigma_scale) as set by set_history_clamp(); (0, 0.0) on a fresh context."""
         r, k = C.c_int(), C.c_float()
         self._check(self.lib.svgf_get_history_clamp(self.h, C.byref(r), C.byref(k)), "svgf_get_history_clamp")
+        return int(r.value), float(k.value)
+
+    def set_firefly_filter(self, rank: int, scale: float = 1.0):
+        """svgf_set_firefly_filter: frames run as if the input colour had been filtered, every pixel brighter than scale times the
+        rank-th largest luminance of its 8 neighbours scaled down to that bound; rank 0 (the default) = off, 1..3.  Survives reset()."""
+        self._check(self.lib.svgf_set_firefly_filter(self.h, int(rank), float(scale)), "svgf_set_firefly_filter")
+
+    def firefly_filter(self) -> tuple[int, float]:
+        """(rank, scale) as set by set_firefly_filter(); (0, 0.0) on a fresh context."""
+        r, k = C.c_int(), C.c_float()
+        self._check(self.lib.svgf_get_firefly_filter(self.h, C.byref(r), C.byref(k)), "svgf_get_firefly_filter")
         return int(r.value), float(k.value)
 
     def set_object_motion(self, geom_xf, n_geoms: int | None = None):

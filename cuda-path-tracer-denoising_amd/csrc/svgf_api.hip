@@ -92,6 +92,9 @@ struct svgf_ctx {
     // svgf_set_history_clamp: configuration, not history (svgf_reset keeps it); read by plan_frame when a frame is enqueued
     int clamp_radius;      // 0 = off
     float clamp_k;
+    // svgf_set_firefly_filter: configuration like the clamp; temporal and non-temporal frames alike run on F(in_rgb)
+    int firefly_rank;      // 0 = off
+    float firefly_scale;
     // svgf_set_object_motion: configuration like the clamp; the pointer and count are read by plan_frame, the table by the temporal kernel
     const float *xf_dev;   // null or xf_n == 0: off
     int xf_n;
@@ -415,6 +418,30 @@ extern "C" int svgf_get_history_clamp(const svgf_ctx *c, int *radius, float *sig
     if (!c) return SVGF_ERR_INVALID_ARG;
     if (radius) *radius = c->clamp_radius;
     if (sigma_scale) *sigma_scale = c->clamp_k;
+    return SVGF_OK;
+}
+
+// Firefly filter of the input colour (include/svgf.h).  Host state only, like the clamp.
+extern "C" int svgf_set_firefly_filter(svgf_ctx *c, int rank, float scale)
+{
+    if (!c) return SVGF_ERR_INVALID_ARG;
+    if (rank < 0 || rank > 3) {
+        snprintf(c->err, sizeof(c->err), "svgf_set_firefly_filter: rank %d outside 0..3", rank);
+        return SVGF_ERR_INVALID_ARG;
+    }
+    if (!(scale >= 0.0f) || scale > 3.402823466e38f) {      // NaN, negative, +inf
+        snprintf(c->err, sizeof(c->err), "svgf_set_firefly_filter: scale %g is not a finite number >= 0", (double)scale);
+        return SVGF_ERR_INVALID_ARG;
+    }
+    c->firefly_rank = rank; c->firefly_scale = scale;
+    return SVGF_OK;
+}
+
+extern "C" int svgf_get_firefly_filter(const svgf_ctx *c, int *rank, float *scale)
+{
+    if (!c) return SVGF_ERR_INVALID_ARG;
+    if (rank) *rank = c->firefly_rank;
+    if (scale) *scale = c->firefly_scale;
     return SVGF_OK;
 }
 
@@ -924,6 +951,17 @@ static int plan_frame(svgf_ctx *c, void *out_rgb_dev, const void *in_rgb_dev, co
         return SVGF_ERR_UNSUPPORTED;
     }
 #endif
+    const bool firefly = c->firefly_rank > 0;      // svgf_set_firefly_filter: temporal and non-temporal frames alike
+    if (firefly && !temporal_clamp_supported(c->W, c->H)) {
+        snprintf(c->err, sizeof(c->err), "svgf_denoise: the firefly filter (svgf_set_firefly_filter) is limited to images of at most 262140 rows, this context has %d", c->H);
+        return SVGF_ERR_UNSUPPORTED;
+    }
+#ifdef SVGF_BUILD_EXPERIMENTS
+    if (firefly && (p->kernel_variant == 6 || c->use_split_fused)) {
+        snprintf(c->err, sizeof(c->err), "svgf_denoise: the parked fused temporal kernels (kernel_variant 6, split_fused) have no firefly filter (svgf_set_firefly_filter)");
+        return SVGF_ERR_UNSUPPORTED;
+    }
+#endif
     const float *in = (const float *)in_rgb_dev, *g = (const float *)gbuffer_dev;
     pl.out = (float *)out_rgb_dev; pl.s_user = (hipStream_t)stream; pl.cap_id = 0;
     // Pipelined frames (see svgf_ctx::pipelined).  The promise behind inputs_ready = 1: at call time the inputs are complete (and stay
@@ -994,6 +1032,7 @@ static int plan_frame(svgf_ctx *c, void *out_rgb_dev, const void *in_rgb_dev, co
     t.in_rgb = in; t.gbuf = g; t.cv_acc = c->cv[acc];
     t.nrm_cur = c->nrm[gnew]; t.gid_cur = c->gid[gnew]; t.pos_cur = c->pos[gnew];
     t.W = c->W; t.H = c->H;
+    if (firefly) { t.firefly_rank = c->firefly_rank; t.firefly_scale = c->firefly_scale; }
     AtrousArgs probe;
     memset(&probe, 0, sizeof(probe));
     probe.W = c->W; probe.H = c->H; probe.step = 2;
@@ -1011,13 +1050,14 @@ static int plan_frame(svgf_ctx *c, void *out_rgb_dev, const void *in_rgb_dev, co
         if (clamp) { t.clamp_radius = c->clamp_radius; t.clamp_k = c->clamp_k; }
         if (xform) { t.xf = c->xf_dev; t.n_geoms = c->xf_n; }
 #ifdef SVGF_BUILD_EXPERIMENTS      // parked: the temporal pass in the first level's loaders, DESIGN.md 5.8
-        if (!motion && !clamp && !xform && cascade && (p->kernel_variant == 0 || p->kernel_variant == 6) && !p->paper_steps && p->spatial_variance_frames <= 0)
+        if (!motion && !clamp && !xform && !firefly && cascade && (p->kernel_variant == 0 || p->kernel_variant == 6) && !p->paper_steps && p->spatial_variance_frames <= 0)
             pl.fused = atrous_fused_supported(probe, t) && (p->kernel_variant == 6 || fuse_pays(c, probe));
 #endif
-    } else if (g && cascade && (p->kernel_variant == 0 || p->kernel_variant == 6) && !p->paper_steps) {
+    } else if (g && !firefly && cascade && (p->kernel_variant == 0 || p->kernel_variant == 6) && !p->paper_steps) {
         // Non-temporal mode.  On the AoS boundary the prepare pass (variance = 10, colour copy, G-buffer split) is loads and
         // stores only and rides in the first level's loader waves when the cascade starts with the lane kernel at step 2
-        // (svgf_atrous_fused.hip, FUSED = 3): no prepare launch, no colour plane written and read back.
+        // (svgf_atrous_fused.hip, FUSED = 3): no prepare launch, no colour plane written and read back.  (Not with the firefly filter:
+        // those loaders stage no neighbourhood of the input; the frame then runs the tiled prepare kernel, one launch more.)
         pl.fused = atrous_prepare_fused_supported(probe, t) && atrous_strip_supported(probe) && atrous_lane_supported(probe) &&
                    (p->kernel_variant == 6 || (kPrepareFusedByDefault && lane_pays(c, probe)));
     }
@@ -1134,7 +1174,9 @@ static int enqueue_frame(svgf_ctx *c, const FramePlan &pl)
         if (pl.svf > 0)      // f4 extension: spatial variance estimate for short histories (its own profiling slot, same kind)
             LAUNCH(SVGF_KERNEL_TEMPORAL, launch_spatial_variance(t.cv_acc, t.mom_acc, t.hlen_upd, t.nrm_cur, t.gid_cur, t.W, t.H, pl.svf, s));
     } else if (!pl.fused) {
-        LAUNCH(SVGF_KERNEL_PREPARE, launch_prepare(t.in_rgb, t.gbuf, t.cv_acc, t.nrm_cur, t.gid_cur, t.pos_cur, t.W, t.H, s));
+        if (t.firefly_rank) LAUNCH(SVGF_KERNEL_PREPARE, launch_prepare_filtered(t.in_rgb, t.gbuf, t.cv_acc, t.nrm_cur, t.gid_cur, t.pos_cur, t.W, t.H,
+                                                                                t.firefly_rank, t.firefly_scale, s));
+        else LAUNCH(SVGF_KERNEL_PREPARE, launch_prepare(t.in_rgb, t.gbuf, t.cv_acc, t.nrm_cur, t.gid_cur, t.pos_cur, t.W, t.H, s));
     }
     // (before the early release below: the next frame's copy into the one capture buffer must not overtake this one)
     if (pl.capture && !pl.fused) HIPC(c, hipMemcpyAsync(c->cv_capture, c->cv[pl.acc], c->n * sizeof(float4), hipMemcpyDeviceToDevice, s));

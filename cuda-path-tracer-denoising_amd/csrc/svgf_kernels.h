@@ -134,6 +134,8 @@ struct TemporalArgs {
     float clamp_k;            //   (history colour clamped to mean +- clamp_k * sigma of in_rgb's (2r+1)^2 window, svgf_temporal.h)
     const float *xf;          // svgf_set_object_motion: n_geoms 3x4 row-major maps (16-byte aligned), this frame's world space -> the previous
     int n_geoms;              //   frame's, applied to what the history tests compare (svgf_temporal.h); null / 0 launches the kernels without
+    int firefly_rank;         // svgf_set_firefly_filter: 0 launches the kernels above, which read neither field; 1..3 the filtered kernels
+    float firefly_scale;      //   (k_temporal_filtered: the frame runs as if in_rgb were F(in_rgb), svgf_temporal.h: svgf_firefly_filter)
 };
 
 // TemporalArgs::motion_format, the values of include/svgf.h's SVGF_MOTION_* (svgf_api.hip asserts the equality)
@@ -141,12 +143,14 @@ struct TemporalArgs {
 #define SVGF_MOTION_FMT_COORD 1      // SVGF_MOTION_PREV_COORD_F32
 #define SVGF_MOTION_FMT_D32   2      // SVGF_MOTION_DELTA_F32
 #define SVGF_MOTION_FMT_D16   3      // SVGF_MOTION_DELTA_F16
+#define SVGF_MOTION_FMT_RUNTIME (-1) // not a format: the kernel instantiation that reads motion / motion_format when it runs (k_temporal_filtered)
 // motion == null launches the camera-path kernel; otherwise the instantiation of motion_format (hipErrorInvalidValue if unknown);
 // clamp_radius 1..3: the clamped instantiation of the same (svgf_kernels.hip: k_temporal_clamped); xf with n_geoms > 0: the
-// object-motion instantiation of either
+// object-motion instantiation of either; firefly_rank 1..3: the filtered kernel (k_temporal_filtered) of clamp_radius 0..3, which
+// takes motion, motion_format and xf as it finds them
 hipError_t launch_temporal(const TemporalArgs &a, hipStream_t s);
 bool       temporal_motion_format_known(int motion_format);
-bool       temporal_clamp_supported(int W, int H);      // images the clamped kernels can be launched on (H <= 262140)
+bool       temporal_clamp_supported(int W, int H);      // images the clamped / filtered kernels' tiled grids can be launched on (H <= 262140)
 // svgf_motion_reproject: the plane launch_temporal's motion kernels read, written with the camera path's own projection
 struct MotionReprojArgs {
     void *out;                // W*H elements of `format`
@@ -168,6 +172,9 @@ hipError_t launch_spatial_variance(float4 *cv_acc, const float2 *mom_acc, const 
 // (gbuf null: the planar path, the planes are already filled and only the colour plane is written)
 hipError_t launch_prepare(const float *in_rgb, const float *gbuf, float4 *cv, float *nrm, int *gid, float *pos,
                           int W, int H, hipStream_t s);
+// the same with the firefly filter (svgf_set_firefly_filter, rank 1..3): colour = F(input); tiled, so temporal_clamp_supported(W, H)
+hipError_t launch_prepare_filtered(const float *in_rgb, const float *gbuf, float4 *cv, float *nrm, int *gid, float *pos,
+                                   int W, int H, int rank, float scale, hipStream_t s);
 hipError_t launch_atrous_gather(const AtrousArgs &a, hipStream_t s);   // strict one-thread-per-pixel gather kernel
 hipError_t launch_atrous_strip(const AtrousArgs &a, hipStream_t s);    // LDS strip-marching kernel (fast path)
 hipError_t launch_atrous_lane(const AtrousArgs &a, hipStream_t s);     // lane-marching kernel, symmetric terms shared by DPP (steps 1 .. 32)

@@ -67,6 +67,7 @@ __global__ __launch_bounds__(BLOCK) void k_temporal(TemporalArgs a)
     const int p = blockIdx.x * BLOCK + threadIdx.x;
     if (p >= n) return;
     constexpr int R = 0;                                              // no history clamp: the body below compiles to what it always was
+    constexpr bool FILTERED = false;
     const ClampTile<R> tile = {};
 #include "svgf_temporal_pixel.inc.h"
 }
@@ -98,7 +99,91 @@ __global__ __launch_bounds__(BLOCK) void k_temporal_clamped(TemporalArgs a)
     if (tile.x >= a.W || tile.y >= a.H) return;
     tile.c0 = lds + (ty + R) * T::PITCH + (tx + R); tile.c1 = tile.c0 + T::PLANE; tile.c2 = tile.c1 + T::PLANE;
     const int p = tile.x + tile.y * a.W;
+    constexpr bool FILTERED = false;
 #include "svgf_temporal_pixel.inc.h"
+}
+
+// Firefly filter (svgf_set_firefly_filter): the raw colour of a 64 x 4 tile with a margin of M, staged in LDS as three colour planes
+// and one plane of svgf_lum_strict, which is so evaluated once per staged texel and not once per neighbourhood it belongs to.  One
+// texel per lane: its three floats are 12 consecutive bytes, a wave's a run of 768.  Nothing outside the image is read: those entries
+// are zero and svgf_firefly_filter never looks at them.
+template <int M> struct FireflyRaw {
+    static constexpr int PITCH = SVGF_CLAMP_TILE_W + 2 * M, ROWS = SVGF_CLAMP_TILE_H + 2 * M, PLANE = PITCH * ROWS;
+};
+template <int BLOCK, int M>
+__device__ __forceinline__ void firefly_stage(float *raw, const float *__restrict__ in_rgb, int x0, int y0, int W, int H)
+{
+    typedef FireflyRaw<M> S;
+    for (int j = threadIdx.x; j < S::PLANE; j += BLOCK) {
+        const int row = j / S::PITCH, col = j - row * S::PITCH;
+        const int gx = x0 - M + col, gy = y0 - M + row;
+        float r = 0.0f, g = 0.0f, b = 0.0f;
+        if (gx >= 0 && gx < W && gy >= 0 && gy < H) {
+            const float *c = in_rgb + 3 * ((size_t)gy * W + gx);
+            r = c[0]; g = c[1]; b = c[2];
+        }
+        raw[j] = r; raw[S::PLANE + j] = g; raw[2 * S::PLANE + j] = b;
+        raw[3 * S::PLANE + j] = lum_strict(r, g, b);
+    }
+}
+
+// The temporal pass on the filtered colour, with the history clamp of radius R = 0 (none) .. 3: k_temporal_clamped's tile and pixel
+// body, behind two more steps in LDS.  The raw tile is staged with margin R + 1; after a barrier the workgroup writes F of the tile
+// with margin R into the planes the clamped kernel would have loaded from in_rgb; after a second barrier every pixel runs the shared
+// body on those: its own colour, its luminance and the clamp's window statistics are the filtered image's.  in_rgb is only read.
+// rank and scale are runtime arguments (TemporalArgs), and so are the motion input and the object motion table here: one
+// instantiation per R.  (One per (MOTION, XF, R), as for the clamped kernels, is 32 more kernels and 0.6 MB more library than
+// tests/test_abi.py allows the product; the choice between the four motion inputs is a wave-uniform branch on a kernel argument,
+// and the XF body with n_geoms == 0 moves nothing: both compute what the specialised kernels compute, bit for bit.)
+// Static LDS: 4 (PITCH + 2)(ROWS + 2) + 3 PITCH ROWS floats = 9408 / 13456 / 17728 / 22224 bytes for R = 0 / 1 / 2 / 3.
+template <int BLOCK, int R>
+__global__ __launch_bounds__(BLOCK) void k_temporal_filtered(TemporalArgs a)
+{
+#pragma clang fp contract(off)
+    typedef ClampTile<R> T;
+    typedef FireflyRaw<R + 1> S;
+    static_assert(BLOCK == SVGF_CLAMP_TILE_W * SVGF_CLAMP_TILE_H, "one thread per pixel of the tile");
+    __shared__ float raw[4 * S::PLANE];
+    __shared__ float lds[3 * T::PLANE];
+    const int x0 = blockIdx.x * SVGF_CLAMP_TILE_W, y0 = blockIdx.y * SVGF_CLAMP_TILE_H;
+    firefly_stage<BLOCK, R + 1>(raw, a.in_rgb, x0, y0, a.W, a.H);
+    __syncthreads();
+    for (int j = threadIdx.x; j < T::PLANE; j += BLOCK) {
+        const int row = j / T::PITCH, col = j - row * T::PITCH;
+        const int gx = x0 - R + col, gy = y0 - R + row;
+        float r = 0.0f, g = 0.0f, b = 0.0f;
+        if (gx >= 0 && gx < a.W && gy >= 0 && gy < a.H) {
+            const int o = (row + 1) * S::PITCH + (col + 1);
+            r = raw[o]; g = raw[S::PLANE + o]; b = raw[2 * S::PLANE + o];
+            svgf_firefly_filter<S::PITCH>(raw + 3 * S::PLANE + o, gx, gy, a.W, a.H, a.firefly_rank, a.firefly_scale, r, g, b);
+        }
+        lds[j] = r; lds[T::PLANE + j] = g; lds[2 * T::PLANE + j] = b;
+    }
+    __syncthreads();
+    const int tx = threadIdx.x % SVGF_CLAMP_TILE_W, ty = threadIdx.x / SVGF_CLAMP_TILE_W;
+    T tile;
+    tile.x = x0 + tx; tile.y = y0 + ty;
+    if (tile.x >= a.W || tile.y >= a.H) return;
+    tile.c0 = lds + (ty + R) * T::PITCH + (tx + R); tile.c1 = tile.c0 + T::PLANE; tile.c2 = tile.c1 + T::PLANE;
+    const int p = tile.x + tile.y * a.W;
+    constexpr bool FILTERED = true, XF = true;
+    constexpr int MOTION = SVGF_MOTION_FMT_RUNTIME;
+#include "svgf_temporal_pixel.inc.h"
+}
+
+static hipError_t launch_temporal_filtered(const TemporalArgs &a, hipStream_t s)
+{
+    if (a.firefly_rank < 1 || a.firefly_rank > 3 || !temporal_clamp_supported(a.W, a.H)) return hipErrorInvalidValue;
+    if (a.motion && !temporal_motion_format_known(a.motion_format)) return hipErrorInvalidValue;
+    const dim3 grid(div_up(a.W, SVGF_CLAMP_TILE_W), div_up(a.H, SVGF_CLAMP_TILE_H)), block(SVGF_BLOCK);
+    switch (a.clamp_radius) {
+    case 0: SVGF_LAUNCH_KERNEL((k_temporal_filtered<SVGF_BLOCK, 0>), grid, block, 0, s, a); break;
+    case 1: SVGF_LAUNCH_KERNEL((k_temporal_filtered<SVGF_BLOCK, 1>), grid, block, 0, s, a); break;
+    case 2: SVGF_LAUNCH_KERNEL((k_temporal_filtered<SVGF_BLOCK, 2>), grid, block, 0, s, a); break;
+    case 3: SVGF_LAUNCH_KERNEL((k_temporal_filtered<SVGF_BLOCK, 3>), grid, block, 0, s, a); break;
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
 }
 
 template <int MOTION, bool XF>
@@ -114,7 +199,7 @@ static hipError_t launch_temporal_clamped(const TemporalArgs &a, hipStream_t s)
     return hipGetLastError();
 }
 
-// the clamped kernels' grid has one row of workgroups per SVGF_CLAMP_TILE_H image rows (grid.y <= 65535)
+// the clamped and the filtered kernels' grids have one row of workgroups per SVGF_CLAMP_TILE_H image rows (grid.y <= 65535)
 bool temporal_clamp_supported(int W, int H) { (void)W; return H <= 65535 * SVGF_CLAMP_TILE_H; }
 
 template <bool XF>
@@ -147,6 +232,7 @@ static hipError_t launch_temporal_xf(const TemporalArgs &a, hipStream_t s)
 
 hipError_t launch_temporal(const TemporalArgs &a, hipStream_t s)
 {
+    if (a.firefly_rank != 0) return launch_temporal_filtered(a, s);
     return (a.xf && a.n_geoms > 0) ? launch_temporal_xf<true>(a, s) : launch_temporal_xf<false>(a, s);
 }
 
@@ -277,6 +363,44 @@ hipError_t launch_prepare(const float *in_rgb, const float *gbuf, float4 *cv, fl
 {
     const long long n = (long long)W * H;
     SVGF_LAUNCH_KERNEL(k_prepare, dim3(div_up(n, SVGF_BLOCK)), dim3(SVGF_BLOCK), 0, s, in_rgb, gbuf, cv, nrm, gid, pos, (int)n);
+    return hipGetLastError();
+}
+
+// The same on the firefly-filtered colour (svgf_set_firefly_filter): cv = (F(input), 10).  A 64 x 4 tile per workgroup, the raw
+// colour and its luminance staged with a margin of 1 (firefly_stage, 3.2 KB of LDS); every thread then filters its own pixel.
+__global__ __launch_bounds__(SVGF_BLOCK) void k_prepare_filtered(const float *__restrict__ in_rgb, const float *__restrict__ gbuf,
+                                                                float4 *__restrict__ cv, float *__restrict__ nrm,
+                                                                int *__restrict__ gid, float *__restrict__ pos, int W, int H,
+                                                                int rank, float scale)
+{
+#pragma clang fp contract(off)
+    typedef FireflyRaw<1> S;
+    __shared__ float raw[4 * S::PLANE];
+    const int x0 = blockIdx.x * SVGF_CLAMP_TILE_W, y0 = blockIdx.y * SVGF_CLAMP_TILE_H;
+    firefly_stage<SVGF_BLOCK, 1>(raw, in_rgb, x0, y0, W, H);
+    __syncthreads();
+    const int tx = threadIdx.x % SVGF_CLAMP_TILE_W, ty = threadIdx.x / SVGF_CLAMP_TILE_W;
+    const int x = x0 + tx, y = y0 + ty;
+    if (x >= W || y >= H) return;
+    const int p = x + y * W;
+    if (gbuf) {               // null on the planar path: the producer filled the planes itself
+        const float *t = gbuf + 13 * (size_t)p;
+        nrm[3 * (size_t)p] = t[0]; nrm[3 * (size_t)p + 1] = t[1]; nrm[3 * (size_t)p + 2] = t[2];
+        pos[3 * (size_t)p] = t[3]; pos[3 * (size_t)p + 1] = t[4]; pos[3 * (size_t)p + 2] = t[5];
+        gid[p] = __float_as_int(t[12]);
+    }
+    const int o = (ty + 1) * S::PITCH + (tx + 1);
+    float r = raw[o], g = raw[S::PLANE + o], b = raw[2 * S::PLANE + o];
+    svgf_firefly_filter<S::PITCH>(raw + 3 * S::PLANE + o, x, y, W, H, rank, scale, r, g, b);
+    cv[p] = make_float4(r, g, b, 10.0f);
+}
+
+hipError_t launch_prepare_filtered(const float *in_rgb, const float *gbuf, float4 *cv, float *nrm, int *gid, float *pos,
+                                   int W, int H, int rank, float scale, hipStream_t s)
+{
+    if (rank < 1 || rank > 3 || !temporal_clamp_supported(W, H)) return hipErrorInvalidValue;
+    SVGF_LAUNCH_KERNEL(k_prepare_filtered, dim3(div_up(W, SVGF_CLAMP_TILE_W), div_up(H, SVGF_CLAMP_TILE_H)), dim3(SVGF_BLOCK), 0, s,
+                       in_rgb, gbuf, cv, nrm, gid, pos, W, H, rank, scale);
     return hipGetLastError();
 }
 

@@ -240,6 +240,48 @@ __device__ __forceinline__ void svgf_history_clamp(SvgfHistSum &h, const float *
     h.pc2 = svgf_clamp_to_box(h.pc2, m2, q2, n, k);
 }
 
+// Firefly filter (include/svgf.h: svgf_set_firefly_filter; rank clamp of the INPUT colour): a pixel whose luminance exceeds scale
+// times the rank-th largest luminance among its up to eight neighbours (centre excluded, inside the image, NaN not counted) is
+// scaled down to that bound.  Normative arithmetic: neighbours yy outer, xx inner; each counted luminance is inserted into the
+// descending list t[0..rank-1] by the swap sequence below (so that +-0 and ties select the same bits everywhere);
+// B = t[min(rank, n) - 1]; bound = scale * B; if (Lp > bound) c *= bound / Lp, one rounded quotient and one product per channel.
+// A NaN centre, a NaN bound and a pixel without a counted neighbour are left as they are.
+// lum: the pixel's own entry in the luminance plane (svgf_lum_strict of every staged texel) of a tile with row pitch PITCH and a
+// margin of at least 1 around the pixel; the entries of taps outside the image are never read.
+template <int PITCH>
+__device__ __forceinline__ void svgf_firefly_filter(const float *lum, int x, int y, int W, int H, int rank, float scale,
+                                                    float &r, float &g, float &b)
+{
+#pragma clang fp contract(off)
+    const float ninf = __uint_as_float(0xff800000u);
+    float t0 = ninf, t1 = ninf, t2 = ninf;
+    int n = 0;
+#pragma unroll
+    for (int yy = -1; yy <= 1; yy++)
+#pragma unroll
+        for (int xx = -1; xx <= 1; xx++) {
+            if (xx == 0 && yy == 0) continue;
+            if ((unsigned)(x + xx) < (unsigned)W && (unsigned)(y + yy) < (unsigned)H) {
+                float v = lum[yy * PITCH + xx];
+                if (v == v) {
+                    n += 1;
+                    if (v > t0) { const float u = t0; t0 = v; v = u; }
+                    if (rank > 1 && v > t1) { const float u = t1; t1 = v; v = u; }
+                    if (rank > 2 && v > t2) { const float u = t2; t2 = v; v = u; }
+                }
+            }
+        }
+    if (n == 0) return;
+    const int k = rank < n ? rank : n;
+    const float B = k <= 1 ? t0 : (k == 2 ? t1 : t2);
+    const float bound = scale * B;
+    const float Lp = lum[0];
+    if (Lp > bound) {
+        const float s = bound / Lp;
+        r = r * s; g = g * s; b = b * s;
+    }
+}
+
 // The accumulated pixel.  `valid`: a usable history value (pc*, pm*, plen: interpolated colour, moments, length) was found.
 struct SvgfTemporalOut { float4 cv; float2 mom; int hlen; };
 __device__ __forceinline__ SvgfTemporalOut svgf_temporal_blend(const TemporalArgs &a, float cr, float cg, float cb, float lum, int N,

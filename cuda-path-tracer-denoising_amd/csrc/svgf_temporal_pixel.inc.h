@@ -5,11 +5,13 @@
 //   p      int, the pixel (x + y * W, inside the image)
 //   MOTION SVGF_MOTION_FMT_*: 0 projects the pixel's position through the previous camera; the others read the previous-frame
 //          coordinate from the caller's plane in that format.  A template parameter: the camera path's kernel carries no trace of them.
+//          SVGF_MOTION_FMT_RUNTIME (the filtered kernels): a.motion / a.motion_format decide, wave-uniformly, between the same four.
 //   XF     bool, svgf_set_object_motion: the tests that decide whether a tap's history may be used compare it with the pixel's normal
 //          and position moved into the previous frame's space by a.xf[geomId]; on the camera path (MOTION 0) the moved position
 //          is also the one projected.  A template parameter like MOTION: false compiles to the kernels that knew no table.
 //   R      constexpr int, radius of the history clamp; 0 = none: `tile` is not looked at
 //   tile   ClampTile<R>
+//   FILTERED constexpr bool, svgf_set_firefly_filter: the tile holds the FILTERED colour and the pixel's own is read from it at R = 0 too
 // No include guard: it is a function body.
     float nx, ny, nz, px, py, pz;
     int gid;
@@ -30,7 +32,7 @@
     }
 
     float cr, cg, cb;
-    if constexpr (R > 0) {    // staged already
+    if constexpr (R > 0 || FILTERED) {    // staged already
         cr = *tile.c0; cg = *tile.c1; cb = *tile.c2;
     } else {
         cr = a.in_rgb[3 * (size_t)p]; cg = a.in_rgb[3 * (size_t)p + 1]; cb = a.in_rgb[3 * (size_t)p + 2];
@@ -48,6 +50,18 @@
         SvgfReproj rp;                                                // previous-frame pixel coordinate (:198-209)
         if constexpr (MOTION == SVGF_MOTION_FMT_NONE) {
             rp = svgf_reproject(a, tpx, tpy, tpz);
+        } else if constexpr (MOTION == SVGF_MOTION_FMT_RUNTIME) {
+            if (!a.motion) {
+                rp = svgf_reproject(a, tpx, tpy, tpz);
+            } else {
+                SvgfPrevCoord c;
+                switch (a.motion_format) {
+                case SVGF_MOTION_FMT_COORD: c = svgf_motion_prev_coord<SVGF_MOTION_FMT_COORD>(a, p); break;
+                case SVGF_MOTION_FMT_D32:   c = svgf_motion_prev_coord<SVGF_MOTION_FMT_D32>(a, p); break;
+                default:                    c = svgf_motion_prev_coord<SVGF_MOTION_FMT_D16>(a, p); break;
+                }
+                rp = svgf_reproj_from_coord(c.x, c.y);
+            }
         } else {
             const SvgfPrevCoord c = svgf_motion_prev_coord<MOTION>(a, p);
             rp = svgf_reproj_from_coord(c.x, c.y);

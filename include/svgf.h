@@ -416,6 +416,31 @@ int svgf_set_history_clamp(svgf_ctx *ctx, int radius, float sigma_scale);
 /* added after 0.9; probe the symbol.  Either pointer may be NULL. */
 int svgf_get_history_clamp(const svgf_ctx *ctx, int *radius, float *sigma_scale);
 
+/* ---- "next" row f8: firefly filter of the input colour (added after 0.9; probe the symbol) -----------------------
+ * Rank clamp of the CURRENT frame's colour: with the filter on, the frame runs exactly as if in_rgb had been the filtered image
+ * F(in_rgb) - the colour that is blended and the luminance that feeds the moments, the window statistics of the history clamp
+ * (svgf_set_history_clamp) when one is set, and the colour the non-temporal prepare pass copies.  in_rgb itself is never written.
+ * Normative arithmetic of F, float32 without contraction, per pixel p = (x, y) with colour c; L is the library's luminance,
+ * (float)((0.2126 (double)r + 0.7152 (double)g) + 0.0722 (double)b):
+ *   Lp = L(c_p);  t[0..rank-1] = -inf;  n = 0
+ *   for yy = -1..1 (outer), xx = -1..1 (inner), (xx, yy) != (0, 0), (x+xx, y+yy) inside the image:
+ *       v = L(c_q);  if (v == v) { n += 1;  for j = 0..rank-1: if (v > t[j]) swap(v, t[j]); }
+ *   if (n == 0) unchanged
+ *   B = t[min(rank, n) - 1]          the min(rank, n)-th largest neighbour luminance; the centre is excluded, NaN is not counted
+ *   bound = scale * B
+ *   if (Lp > bound) { s = bound / Lp;  c_p = (r s, g s, b s); }          a NaN Lp or bound: unchanged
+ * Every float is a defined input and the arithmetic runs as written (an infinite centre over a finite bound: s = 0, inf * 0 = NaN).
+ * rank 0 = off (the default), 1..3; scale finite and >= 0; otherwise SVGF_ERR_INVALID_ARG, as for a NULL context, and the
+ * setting is unchanged.  Configuration of the context, not history: svgf_reset keeps it.  Read when a frame is enqueued (a frame
+ * already recorded into a graph keeps what it was recorded with), by all four svgf_denoise* entry points, svgf_denoise_host,
+ * every inputs_ready mode, AoS and planar frames, temporal frames AND frames with temporal_enable == 0.  Host state only.
+ * A temporal frame stays one temporal launch; a non-temporal frame runs its prepare pass as a launch of its own instead of inside
+ * the first level.  (A filtered frame on a context of more than 262140 rows answers SVGF_ERR_UNSUPPORTED.)
+ * INTEGRATION.md 5d says which values to start from and what they cost. */
+int svgf_set_firefly_filter(svgf_ctx *ctx, int rank, float scale);
+/* added after 0.9; probe the symbol.  Either pointer may be NULL. */
+int svgf_get_firefly_filter(const svgf_ctx *ctx, int *rank, float *scale);
+
 /* ---- "next" row f7: rigid object motion in the temporal pass (added after 0.9; probe the symbol) -------------------
  * Gives the temporal pass the per-object rigid maps of the current frame, the table svgf_motion_reproject takes:
  * geom_xf_dev is device memory of n_geoms x 12 floats, 3x4 row-major, indexed by geomId; each map takes this frame's world

@@ -37,6 +37,8 @@ def main():
                     "(svgf_denoise_motion; the plane is written once by svgf_motion_reproject for the static camera) instead of projecting through the previous camera")
     ap.add_argument("--clamp", default=None, metavar="R[,K]", help="svgf_set_history_clamp(R, K) on the context before the first frame (K defaults to 1): "
                     "the temporal pass runs its clamped kernel of radius R")
+    ap.add_argument("--firefly", default=None, metavar="RANK[,SCALE]", help="svgf_set_firefly_filter(RANK, SCALE) on the context before the first frame (SCALE "
+                    "defaults to 1): the temporal pass runs its filtered kernel (of the clamp radius --clamp gives, or 0)")
     ap.add_argument("--object-motion", action="store_true", help="svgf_set_object_motion with a table of 16 identity maps on the context before the first "
                     "frame: the temporal pass runs its object-motion kernel (three 16-byte loads and the two maps per pixel; the same taps pass as without); "
                     "with --motion the plane is written with the same table")
@@ -61,6 +63,9 @@ def main():
         if a.clamp:
             rk = a.clamp.split(",")
             d.set_history_clamp(int(rk[0]), float(rk[1]) if len(rk) > 1 else 1.0)
+        if a.firefly:
+            rs = a.firefly.split(",")
+            d.set_firefly_filter(int(rs[0]), float(rs[1]) if len(rs) > 1 else 1.0)
         xf = None
         if a.object_motion:
             xf = torch.from_numpy(np.tile(np.eye(3, 4, dtype=np.float32).reshape(-1), (16, 1))).cuda()
