@@ -22,7 +22,7 @@ LIB_EXP_PATH = os.path.join(_HERE, "libsvgf_hip_exp.so")     # -DSVGF_BUILD_EXPE
 
 SVGF_OK = 0
 STATE_HISTORY_LENGTH, STATE_MOMENTS, STATE_COLOR_HISTORY, STATE_VARIANCE_TEMPORAL, STATE_COLOR_ACC = range(5)
-KERNEL_TEMPORAL, KERNEL_PREPARE, KERNEL_ATROUS, KERNEL_DEBUGVIEW, KERNEL_COPYOUT, KERNEL_FUSED = 1, 2, 3, 4, 5, 6
+KERNEL_TEMPORAL, KERNEL_PREPARE, KERNEL_ATROUS, KERNEL_DEBUGVIEW, KERNEL_COPYOUT, KERNEL_FUSED, KERNEL_OUTPUT_TAA = 1, 2, 3, 4, 5, 6, 7
 MAX_LEVELS = 10
 # svgf_exp_level_kernels (experiments build): the kernel an a-trous level ran
 LEVEL_KERNEL_NAMES = ("fused", "lane", "lane2y", "strip", "lattice", "gather")
@@ -37,7 +37,7 @@ EXPORTS = ["svgf_version", "svgf_params_default", "svgf_create", "svgf_destroy",
            "svgf_pipeline_status", "svgf_planar_gbuffer_stream", "svgf_streams_overlap",
            "svgf_denoise_motion", "svgf_denoise_planar_motion", "svgf_motion_reproject",
            "svgf_set_history_clamp", "svgf_get_history_clamp", "svgf_set_object_motion", "svgf_get_object_motion",
-           "svgf_set_firefly_filter", "svgf_get_firefly_filter"]
+           "svgf_set_firefly_filter", "svgf_get_firefly_filter", "svgf_set_output_taa", "svgf_get_output_taa"]
 CREATE_PIPELINED = 1
 # motion plane formats (svgf_denoise_motion): absolute previous coordinate, delta in float32, delta in float16
 MOTION_PREV_COORD_F32, MOTION_DELTA_F32, MOTION_DELTA_F16 = 1, 2, 3
@@ -178,6 +178,8 @@ def load_library(path: str | None = None, experiments: bool = False):
     lib.svgf_get_history_clamp.argtypes = [vp, C.POINTER(ip), C.POINTER(C.c_float)]
     lib.svgf_set_firefly_filter.argtypes = [vp, ip, C.c_float]
     lib.svgf_get_firefly_filter.argtypes = [vp, C.POINTER(ip), C.POINTER(C.c_float)]
+    lib.svgf_set_output_taa.argtypes = [vp, C.c_float, C.c_float]
+    lib.svgf_get_output_taa.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     lib.svgf_set_object_motion.argtypes = [vp, vp, ip]
     lib.svgf_get_object_motion.argtypes = [vp, C.POINTER(vp), C.POINTER(ip)]
     lib.svgf_denoise_host.argtypes = [vp, vp, vp, vp, C.POINTER(SvgfCamera), C.POINTER(SvgfParams)]
@@ -398,6 +400,19 @@ class Denoiser:
         r, k = C.c_int(), C.c_float()
         self._check(self.lib.svgf_get_firefly_filter(self.h, C.byref(r), C.byref(k)), "svgf_get_firefly_filter")
         return int(r.value), float(k.value)
+
+    def set_output_taa(self, alpha: float, sigma_scale: float = 1.0):
+        """svgf_set_output_taa: blend every frame's image with the previous frame's output, reprojected like the temporal pass's
+        history and clipped to mean +- sigma_scale * sigma of the image's 3x3 window: out = alpha * image + (1 - alpha) * history.
+        alpha 0 (the default) = off, else 0 < alpha <= 1.  The first call that turns it on allocates 44 B/px and may synchronise
+        the device.  Survives reset() (the output history does not)."""
+        self._check(self.lib.svgf_set_output_taa(self.h, float(alpha), float(sigma_scale)), "svgf_set_output_taa")
+
+    def output_taa(self) -> tuple[float, float]:
+        """(alpha, sigma_scale) as set by set_output_taa(); (0.0, 0.0) on a fresh context."""
+        a, k = C.c_float(), C.c_float()
+        self._check(self.lib.svgf_get_output_taa(self.h, C.byref(a), C.byref(k)), "svgf_get_output_taa")
+        return float(a.value), float(k.value)
 
     def set_object_motion(self, geom_xf, n_geoms: int | None = None):
         """svgf_set_object_motion: geom_xf is a contiguous device float32[n, 12] tensor (or a raw pointer with n_geoms) of 3x4

@@ -98,6 +98,13 @@ struct svgf_ctx {
     // svgf_set_object_motion: configuration like the clamp; the pointer and count are read by plan_frame, the table by the temporal kernel
     const float *xf_dev;   // null or xf_n == 0: off
     int xf_n;
+    // svgf_set_output_taa: configuration like the clamp (svgf_reset keeps it); the planes exist from the first call that turns it on
+    float taa_alpha;       // 0 = off
+    float taa_k;
+    float *taa_pre;        // packed rgb: the frame's image, written by the last level / the pass-through copy in place of `out`
+    float4 *taa_hist[2];   // {output, geomId bits}: the previous frame's and the one being written
+    int taa_cur;           // taa_hist index the next frame reads
+    int taa_valid;         // taa_hist[taa_cur] holds the last frame's output (history, not configuration: svgf_reset clears it)
     // state capture for tests
     int capture;
     float4 *cv_capture;
@@ -257,6 +264,8 @@ static void free_all(svgf_ctx *c)
     if (c->ev_in) (void)hipEventDestroy(c->ev_in);
     for (int k = 0; k < 2; k++) if (c->tp[k]) (void)hipFree(c->tp[k]);
     if (c->albedo) (void)hipFree(c->albedo);
+    if (c->taa_pre) (void)hipFree(c->taa_pre);
+    for (int k = 0; k < 2; k++) if (c->taa_hist[k]) (void)hipFree(c->taa_hist[k]);
     if (c->cv_capture) (void)hipFree(c->cv_capture);
     if (c->st_in) (void)hipFree(c->st_in);
     if (c->st_out) (void)hipFree(c->st_out);
@@ -297,6 +306,7 @@ static int zero_state(svgf_ctx *c)
     // gcur is deliberately NOT reset: the pointers svgf_planar_gbuffer handed out (planes 1 - gcur) stay the ones the next
     // frame reads, so planar_gbuffer() -> reset() -> producer -> denoise_planar() works (both plane sets are zero again)
     c->hist = 0; c->acc = 0; c->cur = 0;
+    c->taa_valid = 0;      // (the output history is dropped; svgf_set_output_taa's setting stays)
     // The clears above run on the legacy stream; a caller may enqueue the next svgf_denoise on a non-blocking stream that does not
     // order itself behind them: they are complete before svgf_create / svgf_reset return.
     HIPC(c, hipStreamSynchronize(nullptr));
@@ -470,6 +480,50 @@ extern "C" int svgf_get_object_motion(const svgf_ctx *c, const float **geom_xf_d
     if (!c) return SVGF_ERR_INVALID_ARG;
     if (geom_xf_dev) *geom_xf_dev = c->xf_dev;
     if (n_geoms) *n_geoms = c->xf_n;
+    return SVGF_OK;
+}
+
+// Output TAA (include/svgf.h).  Configuration like the clamp, but the first call that turns it on allocates the pass's three planes.
+extern "C" int svgf_set_output_taa(svgf_ctx *c, float alpha, float sigma_scale)
+{
+    if (!c) return SVGF_ERR_INVALID_ARG;
+    if (!(alpha >= 0.0f && alpha <= 1.0f)) {      // NaN included
+        snprintf(c->err, sizeof(c->err), "svgf_set_output_taa: alpha %g outside 0..1", (double)alpha);
+        return SVGF_ERR_INVALID_ARG;
+    }
+    if (!(sigma_scale >= 0.0f) || sigma_scale > 3.402823466e38f) {      // NaN, negative, +inf
+        snprintf(c->err, sizeof(c->err), "svgf_set_output_taa: sigma_scale %g is not a finite number >= 0", (double)sigma_scale);
+        return SVGF_ERR_INVALID_ARG;
+    }
+    if (alpha > 0.0f && !c->taa_pre) {
+        SVGF_ENTER(c);
+        float *pre = nullptr;
+        float4 *h[2] = { nullptr, nullptr };
+        const bool ok = hipMalloc((void **)&pre, c->n * 3 * sizeof(float)) == hipSuccess &&
+                        hipMalloc((void **)&h[0], c->n * sizeof(float4)) == hipSuccess &&
+                        hipMalloc((void **)&h[1], c->n * sizeof(float4)) == hipSuccess;
+        // (cleared once, on the legacy stream, and complete before the call returns: a frame may follow on a non-blocking stream)
+        const bool cleared = ok && hipMemset(pre, 0, c->n * 3 * sizeof(float)) == hipSuccess && hipMemset(h[0], 0, c->n * sizeof(float4)) == hipSuccess &&
+                             hipMemset(h[1], 0, c->n * sizeof(float4)) == hipSuccess && hipStreamSynchronize(nullptr) == hipSuccess;
+        if (!cleared) {
+            if (pre) (void)hipFree(pre);
+            for (int k = 0; k < 2; k++) if (h[k]) (void)hipFree(h[k]);
+            (void)hipGetLastError();
+            snprintf(c->err, sizeof(c->err), "svgf_set_output_taa: %s for the output pass's planes (%zu bytes)", ok ? "hipMemset failed" : "hipMalloc failed", c->n * 44);
+            return ok ? SVGF_ERR_HIP : SVGF_ERR_OOM;
+        }
+        c->taa_pre = pre; c->taa_hist[0] = h[0]; c->taa_hist[1] = h[1];
+    }
+    if (alpha > 0.0f && !(c->taa_alpha > 0.0f)) c->taa_valid = 0;      // turned on: the first frame behind this call has no output history
+    c->taa_alpha = alpha; c->taa_k = sigma_scale;
+    return SVGF_OK;
+}
+
+extern "C" int svgf_get_output_taa(const svgf_ctx *c, float *alpha, float *sigma_scale)
+{
+    if (!c) return SVGF_ERR_INVALID_ARG;
+    if (alpha) *alpha = c->taa_alpha;
+    if (sigma_scale) *sigma_scale = c->taa_k;
     return SVGF_OK;
 }
 
@@ -873,6 +927,10 @@ struct FramePlan {
     TemporalArgs t;
     FrameExit exit;
     float *out;
+    float *out_c;                   // where the last level / the pass-through copy writes the image: `out`, or the output pass's `pre` plane
+    bool taa;                       // svgf_set_output_taa: the output pass runs, last
+    OutputTaaArgs o;
+    int taa_cur, taa_valid;         // the context's output history after the frame
     int n_levels;
     LevelPlan lv[SVGF_MAX_LEVELS];
     int acc, hist, cur, gcur, last_modulated;      // the context's plane roles after the frame
@@ -962,8 +1020,20 @@ static int plan_frame(svgf_ctx *c, void *out_rgb_dev, const void *in_rgb_dev, co
         return SVGF_ERR_UNSUPPORTED;
     }
 #endif
+    // svgf_set_output_taa: every frame that writes the image (debug views are written as they are and drop the output history)
+    const bool taa = pl.taa = c->taa_alpha > 0.0f && p->right_view_option != 1 && p->right_view_option != 2;
+    if (taa && !temporal_clamp_supported(c->W, c->H)) {
+        snprintf(c->err, sizeof(c->err), "svgf_denoise: the output pass (svgf_set_output_taa) is limited to images of at most 262140 rows, this context has %d", c->H);
+        return SVGF_ERR_UNSUPPORTED;
+    }
+#ifdef SVGF_BUILD_EXPERIMENTS
+    if (taa && (p->kernel_variant == 6 || c->use_split_fused)) {
+        snprintf(c->err, sizeof(c->err), "svgf_denoise: the parked fused temporal kernels (kernel_variant 6, split_fused) have no output pass (svgf_set_output_taa)");
+        return SVGF_ERR_UNSUPPORTED;
+    }
+#endif
     const float *in = (const float *)in_rgb_dev, *g = (const float *)gbuffer_dev;
-    pl.out = (float *)out_rgb_dev; pl.s_user = (hipStream_t)stream; pl.cap_id = 0;
+    pl.out = (float *)out_rgb_dev; pl.out_c = taa ? c->taa_pre : pl.out; pl.s_user = (hipStream_t)stream; pl.cap_id = 0;
     // Pipelined frames (see svgf_ctx::pipelined).  The promise behind inputs_ready = 1: at call time the inputs are complete (and stay
     // untouched until the work of this call is done) — so the frame need not order itself behind the caller's stream, which has
     // waited for the PREVIOUS frame's end, and runs on an internal stream; only the kernel that writes `out` waits for the caller's
@@ -1085,7 +1155,7 @@ static int plan_frame(svgf_ctx *c, void *out_rgb_dev, const void *in_rgb_dev, co
             for (int k = pbase; k < pbase + 3; k++) if (k != src && k != hist && !(fuse_here && k == old_hist)) { dst = k; break; }
         }
         lv.dst = dst;
-        a.src = c->cv[src]; a.dst = dst >= 0 ? c->cv[dst] : nullptr; a.out_rgb = lv.last ? pl.out : nullptr;
+        a.src = c->cv[src]; a.dst = dst >= 0 ? c->cv[dst] : nullptr; a.out_rgb = lv.last ? pl.out_c : nullptr;
         a.nrm = c->nrm[gnew]; a.pos = c->pos[gnew]; a.gbuf = g; a.albedo = c->albedo;
         a.W = c->W; a.H = c->H;
         a.step = 1 << (p->paper_steps ? level - 1 : level);   // reference: level starts at 1 => steps 2,4,8,16,32 (:98,386)
@@ -1146,6 +1216,24 @@ static int plan_frame(svgf_ctx *c, void *out_rgb_dev, const void *in_rgb_dev, co
     pl.hist = hist; pl.vp_valid = vp_valid;
     pl.cur = pl.temporal ? 1 - c->cur : c->cur;      // 3) history rotation (:396-399): planes swap roles instead of being copied
     pl.last_modulated = (cascade && p->sepcolor && p->addcolor) ? 1 : 0;
+    // The output pass.  It reads this frame's position / geomId planes (written by the temporal or prepare pass, the first level's
+    // loaders or the producer), the call's motion plane even on a frame with temporal_enable == 0, and the output history of the
+    // last frame if that frame left one; a frame without the pass drops the history.
+    pl.taa_cur = c->taa_cur; pl.taa_valid = 0;
+    if (taa) {
+        OutputTaaArgs &o = pl.o;
+        memset(&o, 0, sizeof(o));
+        o.pre = c->taa_pre; o.out = pl.out;
+        o.hist = c->taa_valid ? c->taa_hist[c->taa_cur] : nullptr; o.hist_new = c->taa_hist[1 - c->taa_cur];
+        o.pos = c->pos[gnew]; o.gid = c->gid[gnew];
+        if (motion_dev) { o.motion = motion_dev; o.motion_format = motion_format; }
+        if (c->xf_dev && c->xf_n > 0) { o.xf = c->xf_dev; o.n_geoms = c->xf_n; }
+        memcpy(o.M, c->view_prev, sizeof(o.M));
+        o.W = c->W; o.H = c->H;
+        o.reproj_sx = p->reproj_scale[0]; o.reproj_sy = p->reproj_scale[1];
+        o.alpha = c->taa_alpha; o.k = c->taa_k;
+        pl.taa_cur = 1 - c->taa_cur; pl.taa_valid = 1;
+    }
     return SVGF_OK;
 }
 
@@ -1184,7 +1272,10 @@ static int enqueue_frame(svgf_ctx *c, const FramePlan &pl)
     switch (pl.exit) {
     case EXIT_DEBUG_HLEN: LAUNCH(SVGF_KERNEL_DEBUGVIEW, launch_debug_hlen(c->hlen[c->cur], pl.out, n, 100.0f, s)); break;   // pre-update lengths (:374)
     case EXIT_DEBUG_VAR:  LAUNCH(SVGF_KERNEL_DEBUGVIEW, launch_debug_var(c->cv[pl.acc], pl.out, n, 0.1f, s)); break;         // (:377)
-    case EXIT_COPY:       LAUNCH(SVGF_KERNEL_COPYOUT, launch_copy_rgb(c->cv[pl.acc], pl.out, n, s)); break;                  // (:382)
+    case EXIT_COPY:                                                                                                          // (:382)
+        if (pl.taa && pl.piped) HIPC(c, pipe_wait(s, c->ev_done[1 - pq], pl.cap_id));      // (`pre`: see the last level below)
+        LAUNCH(SVGF_KERNEL_COPYOUT, launch_copy_rgb(c->cv[pl.acc], pl.out_c, n, s));
+        break;
     case EXIT_CASCADE:    break;
     }
     for (int i = 0; i < pl.n_levels; i++) {
@@ -1192,7 +1283,10 @@ static int enqueue_frame(svgf_ctx *c, const FramePlan &pl)
         // The one kernel of a promised frame that writes the caller's `out`: behind what the caller's stream held when the frame
         // was handed over (a reader of the same buffer enqueued behind an earlier call, for instance).  The promise is about the
         // INPUTS only; the output buffer is protected by stream order like everywhere else.
-        if (pl.promise && lv.last) HIPC(c, hipStreamWaitEvent(s, c->ev_in, 0));
+        // With the output pass that kernel is the pass itself (below); the last level writes the ONE `pre` plane instead, which the
+        // other parity's output pass reads: behind that frame's end (long past by now where frames overlap at all).
+        if (pl.promise && lv.last && !pl.taa) HIPC(c, hipStreamWaitEvent(s, c->ev_in, 0));
+        if (pl.taa && pl.piped && lv.last) HIPC(c, pipe_wait(s, c->ev_done[1 - pq], pl.cap_id));
         switch (lv.kind) {
         case K_FUSED:
 #ifdef SVGF_BUILD_EXPERIMENTS
@@ -1218,8 +1312,14 @@ static int enqueue_frame(svgf_ctx *c, const FramePlan &pl)
         }
         if (pl.piped && i == pl.hist_release) HIPC(c, pipe_record(c->ev_hist[pq], s, pl.cap_id));
     }
+    if (pl.piped && pl.hist_release == pl.n_levels) HIPC(c, pipe_record(c->ev_hist[pq], s, pl.cap_id));
+    if (pl.taa) {
+        // reads the output history the other parity's frame wrote and overwrites the one it read: behind that frame's end (the
+        // writer of `pre` above has waited for it already where the frame is pipelined); writes the caller's `out`
+        if (pl.promise) HIPC(c, hipStreamWaitEvent(s, c->ev_in, 0));
+        LAUNCH(SVGF_KERNEL_OUTPUT_TAA, launch_output_taa(pl.o, s));
+    }
     if (pl.piped) {
-        if (pl.hist_release == pl.n_levels) HIPC(c, pipe_record(c->ev_hist[pq], s, pl.cap_id));
         HIPC(c, pipe_record(c->ev_done[pq], s, pl.cap_id));
         if (s != pl.s_user) HIPC(c, hipStreamWaitEvent(pl.s_user, c->ev_done[pq].ev, 0));      // what the caller enqueues behind this call sees `out`
     }
@@ -1230,6 +1330,7 @@ static int enqueue_frame(svgf_ctx *c, const FramePlan &pl)
 static void commit_frame(svgf_ctx *c, const FramePlan &pl, const SvgfCamera *cam)
 {
     c->acc = pl.acc; c->hist = pl.hist; c->cur = pl.cur; c->gcur = pl.gcur; c->vp_valid = pl.vp_valid; c->last_modulated = pl.last_modulated;
+    c->taa_cur = pl.taa_cur; c->taa_valid = pl.taa_valid;
     if (pl.piped) { c->pipe_frames++; if (pl.cap_id) c->ever_captured = 1; }
     view_matrix_from_camera(cam, c->view_prev);
     if (pl.timed) c->prof_count++;

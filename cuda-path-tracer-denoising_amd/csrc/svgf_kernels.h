@@ -165,6 +165,28 @@ struct MotionReprojArgs {
     int n_geoms;
 };
 hipError_t launch_motion_reproject(const MotionReprojArgs &a, hipStream_t s);
+// svgf_set_output_taa: the last launch of a frame.  `pre` holds the image the frame would have written to `out` (the last level or
+// the pass-through copy was pointed at it); per pixel the previous OUTPUT is looked up at the temporal pass's previous-frame
+// coordinate, clipped to the 3x3 window of `pre` (svgf_history_clamp<1>) and blended.  The output history carries the geomId it was
+// written for in .w (__int_as_float): the pass reads no plane of the previous frame's G-buffer.
+struct OutputTaaArgs {
+    const float *pre;         // packed rgb, the frame's image C (the context's own plane)
+    float *out;               // packed rgb, the caller's output
+    const float4 *hist;       // {previous output, geomId bits}; null: the context has no output history (every pixel: out = C)
+    float4 *hist_new;         // written for the next frame
+    const float *pos;         // this frame's positions (packed float3), read on the camera path only
+    const int *gid;           // this frame's geomId plane
+    const void *motion;       // the call's motion plane (SVGF_MOTION_* layout), or null: the camera path
+    int motion_format;
+    const float *xf;          // svgf_set_object_motion's table (camera path: the position is moved first), or null
+    int n_geoms;
+    float M[16];              // previous view matrix, column-major
+    int W, H;
+    float reproj_sx, reproj_sy;
+    float alpha, k;           // blend weight of the current image; sigma_scale of the clip
+};
+// motion format and object table are read at run time (wave-uniform): one kernel.  temporal_clamp_supported(W, H) images only.
+hipError_t launch_output_taa(const OutputTaaArgs &a, hipStream_t s);
 // SvgfParams::spatial_variance_frames (f4): variance of short-history pixels from the 7x7 neighbourhood's moments
 hipError_t launch_spatial_variance(float4 *cv_acc, const float2 *mom_acc, const int *hlen_upd, const float *nrm, const int *gid,
                                    int W, int H, int K, hipStream_t s);

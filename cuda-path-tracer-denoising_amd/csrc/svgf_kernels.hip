@@ -1,4 +1,4 @@
-// svgf_kernels.hip — temporal accumulation (with and without the history clamp), G-buffer split, strict a-trous gather, debug/copy kernels (gfx950).
+// svgf_kernels.hip — temporal accumulation (with and without the history clamp), G-buffer split, output TAA, strict a-trous gather, debug/copy kernels (gfx950).
 //
 // The temporal kernel and the strict gather kernel keep the reference's arithmetic order and double promotions
 // (reference src/denoise.cu:121,138,143-145,159,196,252) with FMA contraction off, so that they agree with the CPU
@@ -289,6 +289,94 @@ hipError_t launch_motion_reproject(const MotionReprojArgs &a, hipStream_t s)
 {
     const long long n = (long long)a.W * a.H;
     SVGF_LAUNCH_KERNEL(k_motion_reproject, dim3(div_up(n, SVGF_BLOCK)), dim3(SVGF_BLOCK), 0, s, a);
+    return hipGetLastError();
+}
+
+// ----------------------------------------------------------------------------------------------------
+// Output TAA (svgf_set_output_taa; include/svgf.h has the normative arithmetic): the frame's image C, which the last level or the
+// pass-through copy wrote to the context's `pre` plane, blended with the previous frame's OUTPUT.  k_temporal_clamped<.., 1>'s
+// shape: a 64 x 4 tile of C with a margin of 1 staged in LDS as three float planes, one float per lane from consecutive addresses;
+// one thread per pixel; the four history taps are 16-byte reads from global memory (neighbouring pixels reproject to
+// neighbouring texels).  The coordinate is the temporal pass's own: the call's motion plane in its format, or the (moved)
+// position through the previous camera — chosen at run time, wave-uniformly, as in k_temporal_filtered.  A tap counts when it
+// lies inside the image and the geomId stored with it equals the pixel's; no address is formed from a coordinate that failed
+// svgf_reproj_on_screen / svgf_tap_index.
+// ----------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(SVGF_BLOCK) void k_output_taa(OutputTaaArgs a)
+{
+#pragma clang fp contract(off)
+    typedef ClampTile<1> T;
+    static_assert(SVGF_BLOCK == SVGF_CLAMP_TILE_W * SVGF_CLAMP_TILE_H, "one thread per pixel of the tile");
+    __shared__ float lds[3 * T::PLANE];
+    const int x0 = blockIdx.x * SVGF_CLAMP_TILE_W, y0 = blockIdx.y * SVGF_CLAMP_TILE_H;
+    for (int j = threadIdx.x; j < 3 * T::PLANE; j += SVGF_BLOCK) {
+        const int row = j / (3 * T::PITCH), k = j - row * (3 * T::PITCH), col = k / 3, ch = k - 3 * col;
+        const int gx = x0 - 1 + col, gy = y0 - 1 + row;
+        float v = 0.0f;
+        if (gx >= 0 && gx < a.W && gy >= 0 && gy < a.H) v = a.pre[3 * ((size_t)gy * a.W + gx) + ch];
+        lds[ch * T::PLANE + row * T::PITCH + col] = v;
+    }
+    __syncthreads();
+    const int tx = threadIdx.x % SVGF_CLAMP_TILE_W, ty = threadIdx.x / SVGF_CLAMP_TILE_W;
+    const int x = x0 + tx, y = y0 + ty;
+    if (x >= a.W || y >= a.H) return;
+    const float *c0 = lds + (ty + 1) * T::PITCH + (tx + 1), *c1 = c0 + T::PLANE, *c2 = c1 + T::PLANE;
+    const int p = x + y * a.W;
+    const float cr = *c0, cg = *c1, cb = *c2;
+    const int gid = a.gid[p];
+    float o0 = cr, o1 = cg, o2 = cb;
+    if (a.hist && gid != -1) {
+        TemporalArgs t = {};                                          // what the shared coordinate functions look at: the image size, the plane
+        t.W = a.W; t.H = a.H; t.motion = a.motion;
+        SvgfPrevCoord pc;
+        if (!a.motion) {
+            float px = a.pos[3 * (size_t)p], py = a.pos[3 * (size_t)p + 1], pz = a.pos[3 * (size_t)p + 2];
+            if (a.xf && gid >= 0 && gid < a.n_geoms) {
+                float nx = 0.0f, ny = 0.0f, nz = 0.0f;                // (the normal's half of the map is not used here)
+                svgf_to_prev_space(a.xf, gid, px, py, pz, nx, ny, nz);
+            }
+            pc = svgf_project_prev(a.M, a.W, a.H, a.reproj_sx, a.reproj_sy, px, py, pz);
+        } else {
+            switch (a.motion_format) {
+            case SVGF_MOTION_FMT_COORD: pc = svgf_motion_prev_coord<SVGF_MOTION_FMT_COORD>(t, p); break;
+            case SVGF_MOTION_FMT_D32:   pc = svgf_motion_prev_coord<SVGF_MOTION_FMT_D32>(t, p); break;
+            default:                    pc = svgf_motion_prev_coord<SVGF_MOTION_FMT_D16>(t, p); break;
+            }
+        }
+        const SvgfReproj rp = svgf_reproj_from_coord(pc.x, pc.y);
+        if (svgf_reproj_on_screen(t, rp)) {
+            float w[4];
+            svgf_bilinear_weights(rp.fracx, rp.fracy, w);
+            SvgfHistSum hs = { 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f };
+            float sumw = 0.0f;
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const int q = svgf_tap_index(t, rp.fx + (float)(k & 1), rp.fy + (float)(k >> 1));
+                if (q < 0) continue;
+                const float4 h = a.hist[q];
+                if (__float_as_int(h.w) != gid) continue;
+                hs.pc0 += w[k] * h.x; hs.pc1 += w[k] * h.y; hs.pc2 += w[k] * h.z;
+                sumw += w[k];
+            }
+            if ((double)sumw >= 0.01) {                               // NaN: no history
+                hs.pc0 = hs.pc0 / sumw; hs.pc1 = hs.pc1 / sumw; hs.pc2 = hs.pc2 / sumw;
+                svgf_history_clamp<1, T::PITCH>(hs, c0, c1, c2, x, y, a.W, a.H, a.k);
+                const float b = 1.0f - a.alpha;
+                o0 = (a.alpha * cr) + (b * hs.pc0);
+                o1 = (a.alpha * cg) + (b * hs.pc1);
+                o2 = (a.alpha * cb) + (b * hs.pc2);
+            }
+        }
+    }
+    a.out[3 * (size_t)p] = o0; a.out[3 * (size_t)p + 1] = o1; a.out[3 * (size_t)p + 2] = o2;
+    a.hist_new[p] = make_float4(o0, o1, o2, __int_as_float(gid));
+}
+
+hipError_t launch_output_taa(const OutputTaaArgs &a, hipStream_t s)
+{
+    if (!temporal_clamp_supported(a.W, a.H)) return hipErrorInvalidValue;
+    if (a.motion && !temporal_motion_format_known(a.motion_format)) return hipErrorInvalidValue;
+    SVGF_LAUNCH_KERNEL(k_output_taa, dim3(div_up(a.W, SVGF_CLAMP_TILE_W), div_up(a.H, SVGF_CLAMP_TILE_H)), dim3(SVGF_BLOCK), 0, s, a);
     return hipGetLastError();
 }
 

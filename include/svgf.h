@@ -470,6 +470,48 @@ int svgf_set_object_motion(svgf_ctx *ctx, const float *geom_xf_dev, int n_geoms)
 /* added after 0.9; probe the symbol.  Either pointer may be NULL. */
 int svgf_get_object_motion(const svgf_ctx *ctx, const float **geom_xf_dev, int *n_geoms);
 
+/* ---- "next" row f9: output TAA, the last stage of the SVGF pipeline (added after 0.9; probe the symbol) --------------------
+ * Temporal anti-aliasing of the FILTERED image (Schied et al. 2017, the step behind the a-trous cascade): with the feature on, the
+ * image the frame would have written to `out` - call it C: the last level's output, its sepcolor && addcolor modulation included,
+ * or the pass-through copy where there is no cascade - is blended with the previous frame's OUTPUT, found at the temporal pass's
+ * previous-frame coordinate and clipped to C's 3x3 neighbourhood.  One more launch at the end of the frame (SVGF_KERNEL_OUTPUT_TAA
+ * in svgf_profile_read, always the last entry).  Normative arithmetic, float32 without contraction, every float a defined input;
+ * per pixel p = (x, y) with c = C[p] and g = this frame's geomId[p]:
+ *   1. no history - o = c - when g == -1 or the context has no output history (the first frame after svgf_create, svgf_reset or
+ *      the call that turned the feature on, and any frame after one that dropped it, below);
+ *   2. previous coordinate, the temporal pass's own rule: the call's motion plane in its format (svgf_denoise_motion /
+ *      svgf_denoise_planar_motion; the output pass reads the plane on frames with temporal_enable == 0 too, where the temporal
+ *      side ignores it), else the projection of the pixel's position through the previous camera with params->reproj_scale, the
+ *      position first moved by svgf_set_object_motion's map when one is set and 0 <= g < n_geoms; fx = floor, frac = coord - floor;
+ *      no history unless 0 <= fx < W and 0 <= fy < H (NaN and +-inf fail);
+ *   3. taps k = 0..3 at (fx + (k & 1), fy + (k >> 1)), weights w = {(1-fracx)(1-fracy), fracx (1-fracy), (1-fracx) fracy, fracx fracy};
+ *      a tap counts when it lies inside the image and the geomId stored with the output history at that texel equals g; for the
+ *      counted taps in order of k: h += w[k] * hist, sumw += w[k]; if ((double)sumw >= 0.01) h = h / sumw, else no history;
+ *   4. h is clamped per channel to mean +- sigma_scale * sigma of C over the 3x3 window around p, exactly the arithmetic of
+ *      svgf_set_history_clamp with radius 1 (taps inside the image only; comparisons, so NaN leaves h as it is);
+ *   5. o = (alpha * c) + ((1.0f - alpha) * h);
+ *   6. out[p] = o, and (o, g) is the output history at p for the next frame.
+ * No normal or position test: the clip bounds a wrong history, the geomId test keeps colour from crossing objects.  The pass
+ * reads no plane of the previous frame's G-buffer (the output history carries its geomId).
+ * alpha == 0 = off (the default); otherwise 0 < alpha <= 1; sigma_scale finite and >= 0 in either case.  Anything else, NaN
+ * included, is SVGF_ERR_INVALID_ARG, as is a NULL context: the setting is unchanged and svgf_get_output_taa writes nothing.
+ * The first call that turns the feature on allocates the pass's planes (+44 B/px: one packed-rgb plane for C, two 16 B/px output
+ * histories; they live until svgf_destroy): it may synchronise the device and must not be made under stream capture, like
+ * svgf_enable_pipeline.  SVGF_ERR_OOM when the allocation fails, the setting unchanged.
+ * Configuration of the context, not history: svgf_reset keeps alpha and sigma_scale and drops the output history.  Read when a
+ * frame is enqueued: a frame recorded into a graph keeps what it was recorded with, including which history plane it reads and
+ * whether a history exists (replay graphs of an even number of frames, as svgf_sync_stream's text asks).  Honoured by all four
+ * svgf_denoise* entry points and svgf_denoise_host, AoS and planar frames, every inputs_ready mode, temporal and non-temporal
+ * frames and every kernel_variant of this build, whenever right_view_option is not a debug view.  Debug views (right_view_option
+ * 1 or 2) are written as they are and drop the output history; so does a frame enqueued while the feature is off.  With the
+ * feature off a frame enqueues exactly what it did before the feature existed.
+ * (A frame with the feature on, on a context of more than 262140 rows, answers SVGF_ERR_UNSUPPORTED before anything is enqueued.)
+ * INTEGRATION.md 5e says which values to start from and what the pass costs. */
+int svgf_set_output_taa(svgf_ctx *ctx, float alpha, float sigma_scale);
+/* added after 0.9; probe the symbol.  Either pointer may be NULL. */
+int svgf_get_output_taa(const svgf_ctx *ctx, float *alpha, float *sigma_scale);
+#define SVGF_KERNEL_OUTPUT_TAA 7   /* svgf_profile_read: the output pass, the last entry of a frame that runs it */
+
 /* ---- "next" row f2: the step right after denoise() ------------------------------------------------
  * svgf_display_pack: reference sendTwoImagesToPBO (src/pathtrace.cu:45-77, launched at :446): `left` (the 1-spp
  *   image) and `right` (the denoised image), both packed rgb floats in device memory, side by side into a
