@@ -1,5 +1,6 @@
 """The float32 numpy model of the temporal pass (csrc/svgf_temporal.h, svgf_temporal_pixel.inc.h) — the yardstick of
-tests/test_motion_vectors.py, test_history_clamp.py and test_object_motion.py.  Test infrastructure only; not part of the package.
+tests/test_motion_vectors.py, test_history_clamp.py, test_object_motion.py and (behind tests/firefly_model.py) test_firefly_filter.py
+and test_temporal_matrix.py.  Test infrastructure only; not part of the package.
 
 One model with three optional parts, each off at its default: the history clamp of svgf_set_history_clamp (`radius`, `k`), the
 position test of SvgfParams::reproj_position_tol (`pos_tol`) and the object motion table of svgf_set_object_motion (`tables`,

@@ -22,8 +22,9 @@ import pytest
 
 import temporal_model as tm
 from conftest import ROOT, relerr
-from temporal_harness import (BLOCK, SIDE, _whole_frames, assert_frames_equal, block_sequence, device_table, moving_block_sequence,
-                              read_states, run_gpu, same_bits, scales, synth_params, synth_sequence, temporal_only)
+from temporal_harness import (BAD_ROW, BLOCK, SIDE, _whole_frames, assert_frames_equal, block_sequence, device_table, mixed_model,
+                              mixed_sequence, mixed_table, moving_block_sequence, read_states, run_gpu, same_bits, scales, synth_params,
+                              synth_sequence, temporal_only)
 
 F = np.float32
 COORD, D32, D16 = tm.COORD, tm.D32, tm.D16
@@ -32,74 +33,7 @@ MODEL_GOLDEN = os.path.join(ROOT, "tests", "golden", "temporal_model", "moving_b
 TOLS = (0.0, 0.3)
 
 
-def rotation(axis, degrees):
-    a = np.deg2rad(degrees)
-    c, s = np.cos(a), np.sin(a)
-    return {"x": np.array([[1, 0, 0], [0, c, -s], [0, s, c]]), "y": np.array([[c, 0, s], [0, 1, 0], [-s, 0, c]]),
-            "z": np.array([[c, -s, 0], [s, c, 0], [0, 0, 1]])}[axis]
-
-
 # ---- inputs ---------------------------------------------------------------------------------------------------------------------------
-BAD_ROW = 6
-
-
-def mixed_table():
-    """Nine maps, indexed by the synthetic scene's geomIds 0..8: rotations of 0-12 degrees (svgf_normals_close rejects above about
-    5.7) with translations of 0-0.45 (around the position tolerance 0.3); row 0 is the exact identity, row 6 holds NaN and inf."""
-    spec = [("y", 0.0, (0.0, 0.0, 0.0)), ("y", 2.0, (0.05, 0.0, 0.0)), ("x", 4.0, (0.0, 0.02, 0.1)), ("z", 5.5, (0.0, 0.0, 0.0)),
-            ("y", 6.0, (0.2, 0.0, 0.0)), ("x", 8.0, (0.0, 0.0, -0.3)), ("y", 1.0, (0.0, 0.0, 0.0)), ("y", 12.0, (0.4, 0.1, 0.0)),
-            ("z", 0.0, (0.25, 0.0, 0.15))]
-    X = np.stack([np.concatenate([rotation(ax, deg), np.array(t)[:, None]], axis=1).reshape(-1) for ax, deg, t in spec]).astype(F)
-    X[BAD_ROW, 1], X[BAD_ROW, 7], X[BAD_ROW, 8] = np.nan, np.inf, -np.inf
-    return X
-
-
-def mixed_sequence(pkg, orc, W, H, n=4, finite=False):
-    """n frames of the synthetic scene under its moving camera with the texels of tests/test_motion_vectors.py::_texels_for_helper:
-    ray misses, ids beyond the table, non-finite and behind-the-camera positions.  Per frame (colour[H, W, 3], texels[H, W],
-    camera, view matrix).
-    finite: the same texels without the non-finite positions, for frames that run the a-trous levels.  A staged non-finite texel
-    switches a workgroup of the lane a-trous kernel to its careful loop, and that switch is raced by the loader which stages the
-    texel: the row computed meanwhile may round differently from run to run (tests/test_parity_gpu.py compares such frames bit
-    for bit "only without non-finite texels"), so two contexts agree exactly only on finite texels.  The temporal pass, which
-    is what this file tests, has no such race and is compared on the non-finite texels with the a-trous levels off."""
-    cache = mixed_sequence.__dict__.setdefault("cache", {})
-    if (W, H, n, finite) not in cache:
-        seq = []
-        for f, (col, gb, cam, M) in enumerate(synth_sequence(pkg, orc, W, H, n, seed=11)):
-            gb = gb.copy()
-            rng = np.random.default_rng(W * 1000 + H + 17 * f)
-            flat = gb.reshape(-1)
-            m = flat.size
-            flat["geomId"][rng.integers(0, m, max(1, m // 7))] = -1
-            flat["geomId"][rng.integers(0, m, max(1, m // 9))] = 40             # beyond the table: unmoved
-            if m > 4:
-                bad = rng.integers(0, m, 3)      # (drawn either way: the other texels are the same in both forms)
-                if not finite:
-                    flat["position"][bad] = (np.nan, np.inf, -1e30)
-                flat["position"][rng.integers(0, m, 2)] = (0.0, 5.0, 60.0)      # behind the camera
-            seq.append((col, gb, cam, M))
-        cache[(W, H, n, finite)] = seq
-    return cache[(W, H, n, finite)]
-
-
-def mixed_model(pkg, orc, W, H, fmt, tol, radius=0, k=0.0):
-    """The model on mixed_sequence with mixed_table: fmt None = the camera path (the moved position projected through the previous
-    frame's camera); otherwise through the plane svgf_motion_reproject(X) writes in that format, converted as the header says."""
-    cache = mixed_model.__dict__.setdefault("cache", {})
-    key = (W, H, fmt, tol, radius, k)
-    if key not in cache:
-        seq, X = mixed_sequence(pkg, orc, W, H), mixed_table()
-        sx, sy = scales(pkg, W, H)
-        views = [seq[max(f - 1, 0)][3] for f in range(len(seq))]
-        coords = None
-        if fmt is not None:
-            coords = [tm.coord_plane(tm.motion_plane(views[f], W, H, seq[f][1], X, fmt, F(sx), F(sy)), fmt, W, H) for f in range(len(seq))]
-        cache[key] = tm.run_sequence([(c, g) for c, g, _, _ in seq], coords=coords, tables=[X] * len(seq), views=views, scale=(sx, sy),
-                                     pos_tol=tol, radius=radius, k=k)
-    return cache[key]
-
-
 TURN_DEG, SLIDE_X, TURN_FRAMES = 9.0, 1.0, 4
 
 
