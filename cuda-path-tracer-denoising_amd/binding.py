@@ -37,7 +37,8 @@ EXPORTS = ["svgf_version", "svgf_params_default", "svgf_create", "svgf_destroy",
            "svgf_pipeline_status", "svgf_planar_gbuffer_stream", "svgf_streams_overlap",
            "svgf_denoise_motion", "svgf_denoise_planar_motion", "svgf_motion_reproject",
            "svgf_set_history_clamp", "svgf_get_history_clamp", "svgf_set_object_motion", "svgf_get_object_motion",
-           "svgf_set_firefly_filter", "svgf_get_firefly_filter", "svgf_set_output_taa", "svgf_get_output_taa"]
+           "svgf_set_firefly_filter", "svgf_get_firefly_filter", "svgf_set_output_taa", "svgf_get_output_taa",
+           "svgf_upsample"]
 CREATE_PIPELINED = 1
 # motion plane formats (svgf_denoise_motion): absolute previous coordinate, delta in float32, delta in float16
 MOTION_PREV_COORD_F32, MOTION_DELTA_F32, MOTION_DELTA_F16 = 1, 2, 3
@@ -76,6 +77,16 @@ class SvgfPlanarGBuffer(C.Structure):
     """Device pointers of the context's current-frame planes (svgf_planar_gbuffer): packed float3 normal / position / albedo,
     int geomId."""
     _fields_ = [("normal", C.c_void_p), ("position", C.c_void_p), ("geom_id", C.c_void_p), ("albedo", C.c_void_p)]
+
+
+class SvgfGuide(C.Structure):
+    """One resolution's G-buffer for svgf_upsample: device pointers of AoS texels (`gbuffer`, wins when set) or of the planes of
+    svgf_planar_gbuffer's layout; `albedo` (albedo * ialbedo) is only read on the hi side with modulate."""
+    _fields_ = [("gbuffer", C.c_void_p), ("normal", C.c_void_p), ("position", C.c_void_p), ("geom_id", C.c_void_p), ("albedo", C.c_void_p)]
+
+
+class SvgfUpsampleParams(C.Structure):
+    _fields_ = [("sigma_n", C.c_float), ("sigma_x", C.c_float), ("modulate", C.c_int)]
 
 
 class SvgfSynthParams(C.Structure):
@@ -174,6 +185,7 @@ def load_library(path: str | None = None, experiments: bool = False):
     lib.svgf_denoise_motion.argtypes = [vp, vp, vp, vp, vp, ip, C.POINTER(SvgfCamera), C.POINTER(SvgfParams), vp]
     lib.svgf_denoise_planar_motion.argtypes = [vp, vp, vp, vp, ip, C.POINTER(SvgfCamera), C.POINTER(SvgfParams), vp]
     lib.svgf_motion_reproject.argtypes = [ip, vp, ip, vp, vp, vp, ip, ip, C.POINTER(SvgfCamera), C.POINTER(C.c_float), vp, ip, vp]
+    lib.svgf_upsample.argtypes = [ip, vp, C.POINTER(SvgfGuide), ip, ip, vp, C.POINTER(SvgfGuide), ip, ip, C.POINTER(SvgfUpsampleParams), vp]
     lib.svgf_set_history_clamp.argtypes = [vp, ip, C.c_float]
     lib.svgf_get_history_clamp.argtypes = [vp, C.POINTER(ip), C.POINTER(C.c_float)]
     lib.svgf_set_firefly_filter.argtypes = [vp, ip, C.c_float]
@@ -538,6 +550,27 @@ def motion_reproject(motion_out, width: int, height: int, prev_camera, gbuffer=N
                                    int(width), int(height), C.byref(cam), rs, _ptr(geom_xf), int(n_geoms or 0), s)
     if rc != SVGF_OK:
         raise SvgfError(f"svgf_motion_reproject failed ({rc})")
+
+
+# --- guided upsampling: the full-size image from a reduced-size denoise ----------------------------------------------------
+def guide(gbuffer=None, normal=None, position=None, geom_id=None, albedo=None) -> SvgfGuide:
+    """A SvgfGuide from AoS texels (`gbuffer`) or planes: tensors, raw pointers or a SvgfPlanarGBuffer's fields."""
+    return SvgfGuide(_ptr(gbuffer), _ptr(normal), _ptr(position), _ptr(geom_id), _ptr(albedo))
+
+
+def upsample(out, hi_guide, width_hi: int, height_hi: int, rgb_lo, lo_guide, width_lo: int, height_lo: int,
+             sigma_n: float, sigma_x: float, modulate, device: int = 0, stream=None):
+    """svgf_upsample: `out` (device, height_hi * width_hi * 3 float32) from `rgb_lo`, the output of a denoise at width_lo x height_lo
+    run with sepcolor = 1 and addcolor = 0, guided by the two G-buffers.  A guide is a SvgfGuide (guide(...)) or the AoS texels
+    themselves (a tensor or a raw pointer).  sigma_x is in the scene's world units; 0 turns a term off."""
+    lib = load_library()
+    hi, lo = (g if isinstance(g, SvgfGuide) else guide(gbuffer=g) for g in (hi_guide, lo_guide))
+    up = SvgfUpsampleParams(float(sigma_n), float(sigma_x), int(modulate))
+    s = None if stream is None else (stream if isinstance(stream, int) else stream.cuda_stream)
+    rc = lib.svgf_upsample(int(device), _ptr(out), C.byref(hi), int(width_hi), int(height_hi), _ptr(rgb_lo), C.byref(lo),
+                           int(width_lo), int(height_lo), C.byref(up), s)
+    if rc != SVGF_OK:
+        raise SvgfError(f"svgf_upsample failed ({rc})")
 
 
 # --- SURVEY.md 8(f) row f2: the step after denoise() ----------------------------------------------------------------

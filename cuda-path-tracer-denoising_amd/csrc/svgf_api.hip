@@ -7,6 +7,7 @@
 //   * variance is never updated in place: each a-trous level reads {colour,variance} plane A and writes plane B,
 //     which is the "snapshot" semantics the parity contract fixes (SURVEY.md §7 hard parts, §8c).
 #include <hip/hip_runtime.h>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -1395,6 +1396,40 @@ extern "C" int svgf_motion_reproject(int device, void *motion_out_dev, int motio
     a.reproj_sx = reproj_scale ? reproj_scale[0] : 0.0f; a.reproj_sy = reproj_scale ? reproj_scale[1] : 0.0f;
     a.xf = n_geoms > 0 ? geom_xf_dev : nullptr; a.n_geoms = a.xf ? n_geoms : 0;
     return launch_motion_reproject(a, (hipStream_t)stream) == hipSuccess ? SVGF_OK : SVGF_ERR_HIP;
+}
+
+// Guided upsampling (k_upsample, svgf_upsample.hip): the full-size image from a reduced-size denoise.  Stateless; every argument is
+// answered before the first HIP call.
+static bool upsample_guide_ok(const SvgfGuide *g) { return g->gbuffer || (g->normal && g->position && g->geom_id); }
+static UpsampleGuide upsample_guide(const SvgfGuide *g)
+{
+    UpsampleGuide u;
+    u.gbuf = (const float *)g->gbuffer;
+    u.nrm = g->normal; u.pos = g->position; u.gid = g->geom_id; u.albedo = g->albedo;
+    return u;
+}
+extern "C" int svgf_upsample(int device, void *out_rgb_hi_dev, const SvgfGuide *hi, int width_hi, int height_hi,
+                             const void *rgb_lo_dev, const SvgfGuide *lo, int width_lo, int height_lo,
+                             const SvgfUpsampleParams *up, void *stream)
+{
+    if (!out_rgb_hi_dev || !rgb_lo_dev || !hi || !lo || !up) return SVGF_ERR_INVALID_ARG;
+    if (!upsample_guide_ok(hi) || !upsample_guide_ok(lo)) return SVGF_ERR_INVALID_ARG;
+    if (up->modulate != 0 && up->modulate != 1) return SVGF_ERR_INVALID_ARG;
+    if (up->modulate && !hi->gbuffer && !hi->albedo) return SVGF_ERR_INVALID_ARG;
+    if (width_hi <= 0 || height_hi <= 0 || width_lo <= 0 || height_lo <= 0 || width_lo > width_hi || height_lo > height_hi)
+        return SVGF_ERR_INVALID_ARG;
+    if (!(up->sigma_n >= 0.0f) || !(up->sigma_x >= 0.0f) || std::isinf(up->sigma_n) || std::isinf(up->sigma_x)) return SVGF_ERR_INVALID_ARG;
+    if ((long long)width_hi * height_hi >= (1LL << 31) / 16) return SVGF_ERR_UNSUPPORTED;
+    SvgfDeviceGuard dev_guard(device);
+    if (!dev_guard.ok) return SVGF_ERR_NO_DEVICE;
+    UpsampleArgs a;
+    memset(&a, 0, sizeof(a));
+    a.out = (float *)out_rgb_hi_dev; a.rgb_lo = (const float *)rgb_lo_dev;
+    a.hi = upsample_guide(hi); a.lo = upsample_guide(lo);
+    a.Wh = width_hi; a.Hh = height_hi; a.Wl = width_lo; a.Hl = height_lo;
+    a.rx = (float)width_lo / (float)width_hi; a.ry = (float)height_lo / (float)height_hi;
+    a.sigma_n = up->sigma_n; a.sigma_x = up->sigma_x; a.modulate = up->modulate;
+    return launch_upsample(a, (hipStream_t)stream) == hipSuccess ? SVGF_OK : SVGF_ERR_HIP;
 }
 
 // ---- the planar path (the AoS -> plane repack fused into the producer) -----------------------

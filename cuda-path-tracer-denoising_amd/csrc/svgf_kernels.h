@@ -165,6 +165,23 @@ struct MotionReprojArgs {
     int n_geoms;
 };
 hipError_t launch_motion_reproject(const MotionReprojArgs &a, hipStream_t s);
+// svgf_upsample: the full-size image from a reduced-size denoise and the full-size G-buffer (svgf_upsample.hip)
+struct UpsampleGuide {        // one resolution's G-buffer
+    const float *gbuf;        // raw 52-B texels, or null:
+    const float *nrm, *pos;   //   packed float3 planes and
+    const int *gid;           //   int geomId plane
+    const float *albedo;      // packed float3 albedo * ialbedo; read on the hi side only, when modulate and gbuf is null
+};
+struct UpsampleArgs {
+    float *out;               // packed rgb, Wh * Hh
+    const float *rgb_lo;      // packed rgb, Wl * Hl
+    UpsampleGuide hi, lo;
+    int Wh, Hh, Wl, Hl;
+    float rx, ry;             // (float)Wl / (float)Wh, (float)Hl / (float)Hh
+    float sigma_n, sigma_x;   // 0 = term off
+    int modulate;
+};
+hipError_t launch_upsample(const UpsampleArgs &a, hipStream_t s);
 // svgf_set_output_taa: the last launch of a frame.  `pre` holds the image the frame would have written to `out` (the last level or
 // the pass-through copy was pointed at it); per pixel the previous OUTPUT is looked up at the temporal pass's previous-frame
 // coordinate, clipped to the 3x3 window of `pre` (svgf_history_clamp<1>) and blended.  The output history carries the geomId it was

@@ -512,6 +512,46 @@ int svgf_set_output_taa(svgf_ctx *ctx, float alpha, float sigma_scale);
 int svgf_get_output_taa(const svgf_ctx *ctx, float *alpha, float *sigma_scale);
 #define SVGF_KERNEL_OUTPUT_TAA 7   /* svgf_profile_read: the output pass, the last entry of a frame that runs it */
 
+/* ---- "next" row f10: guided upsampling (added after 0.9; probe the symbol) -------------------------------------------------
+ * The full-size image rebuilt from a reduced-size denoise and the full-size G-buffer of the same frame: a renderer traces and
+ * denoises the illumination at W_lo x H_lo, keeps its W_hi x H_hi G-buffer (which costs it almost nothing), and multiplies the
+ * albedo back at full size, so textures and object edges stay sharp.  `rgb_lo` is the `out` of a svgf_denoise* run on the small
+ * frame WITHOUT the final modulation (sepcolor = 1, addcolor = 0), `lo` that frame's G-buffer, `hi` the full-size one.
+ * Stateless, asynchronous on `stream`, allocates nothing, one launch.  All image pointers are device pointers; colour images are
+ * packed rgb.  Normative arithmetic, float32 without contraction, every float a defined input; per hi pixel P = (x, y) with
+ * g, n, p its geomId, normal and position:
+ *   rx = (float)width_lo / (float)width_hi, ry = (float)height_lo / (float)height_hi             (float32 divisions)
+ *   u = ((float)x + 0.5f) * rx - 0.5f, v = ((float)y + 0.5f) * ry - 0.5f;  fx = floorf(u), ax = u - fx;  fy = floorf(v), ay = v - fy
+ *   wb = {(1-ax)(1-ay), ax (1-ay), (1-ax) ay, ax ay};  tap k = 0..3 at (fx + (k & 1), fy + (k >> 1)), INSIDE when it lies in the lo image
+ *   pass A (guided): a tap counts when it is inside and geomId_lo == g.  w = wb[k]; if g != -1:
+ *       if sigma_n > 0: d = n_lo - n; s = (d.x d.x + d.y d.y) + d.z d.z; t = 1 - sqrtf(s) / sigma_n; if (!(t > 0)) t = 0; w = w t
+ *       if sigma_x > 0: d = p_lo - p; s = (n.x d.x + n.y d.y) + n.z d.z; t = 1 - fabsf(s) / sigma_x; if (!(t > 0)) t = 0; w = w t
+ *     in order of k: acc[c] += w * rgb_lo[c], sumw += w.  If (double)sumw >= 0.01: o = acc / sumw (a NaN sumw fails the test).
+ *   pass B (same object), only if A did not accept: the same sum with w = wb[k] over the inside taps with geomId_lo == g; the same test.
+ *   pass C (plain), only if B did not accept: the same sum over all inside taps; the same test; otherwise o = 0.  (With lo <= hi the
+ *     nearest inside tap weighs about 0.25 or more: C accepts.)
+ *   if modulate: o = o * a per channel, a = albedo * ialbedo of the hi texel (AoS) or the hi albedo plane's value
+ *   out[P] = o
+ * SVGF_ERR_INVALID_ARG, answered before any device work: a NULL out, rgb_lo, hi, lo or up; a guide with neither `gbuffer` nor all
+ * three of normal, position and geom_id; modulate with a planar hi guide whose albedo is NULL; modulate other than 0 or 1; a size
+ * <= 0; width_lo > width_hi or height_lo > height_hi; a sigma that is negative, NaN or infinite.  SVGF_ERR_UNSUPPORTED for
+ * width_hi * height_hi >= 2^31 / 16, as svgf_motion_reproject answers.
+ * INTEGRATION.md 5f says what to feed it; sigma_x is in the scene's world units. */
+typedef struct SvgfGuide {          /* one resolution's G-buffer: AoS texels, or planes (gbuffer != NULL wins) */
+    const void  *gbuffer;           /* W*H SvgfGBufferTexel, or NULL */
+    const float *normal, *position; /* packed float3 per pixel (svgf_planar_gbuffer's layout) */
+    const int   *geom_id;
+    const float *albedo;            /* packed float3 holding albedo * ialbedo; only read on the hi side with modulate */
+} SvgfGuide;
+typedef struct SvgfUpsampleParams {
+    float sigma_n;   /* width of the normal term, 0 = term off */
+    float sigma_x;   /* width of the plane-distance term (world units), 0 = term off */
+    int   modulate;  /* 1: multiply the result by the hi side's albedo * ialbedo */
+} SvgfUpsampleParams;
+int svgf_upsample(int device, void *out_rgb_hi_dev, const SvgfGuide *hi, int width_hi, int height_hi,
+                  const void *rgb_lo_dev, const SvgfGuide *lo, int width_lo, int height_lo,
+                  const SvgfUpsampleParams *up, void *stream);
+
 /* ---- "next" row f2: the step right after denoise() ------------------------------------------------
  * svgf_display_pack: reference sendTwoImagesToPBO (src/pathtrace.cu:45-77, launched at :446): `left` (the 1-spp
  *   image) and `right` (the denoised image), both packed rgb floats in device memory, side by side into a
