@@ -5,8 +5,9 @@
 // (src/pathtrace.cu:317-323, intersection conventions of src/intersections.h:50,104: cube [-0.5,0.5]^3 and sphere
 // r = 0.5 in object space, t measured in world space).  The host side (cuda-path-tracer-denoising_amd/scene.py) parses
 // the text and builds the SvgfSceneGeom records; this kernel casts the primary rays against them and writes the
-// denoiser's inputs with the same shading / noise stub as svgf_synth.hip.  Oracle: scene.render_scene (numpy), mirrored
-// here operation for operation in fp32 with contraction off.
+// denoiser's inputs with the same shading / noise stub as svgf_synth.hip.  Oracle: scene.render_scene (numpy) for the primitives,
+// tests/scene_model.py for every branch (geom_ids, triangles, textures, colour), mirrored here operation for operation in fp32
+// with contraction off.
 #include "svgf_kernels.h"
 #include "../../include/svgf.h"
 
@@ -90,7 +91,9 @@ __global__ __launch_bounds__(256) void k_scene_frame(SceneArgs a)
             int amin = 0, amax = 0;
             for (int ax = 0; ax < 3; ax++) {
                 const float t1 = (-0.5f - qo[ax]) / qd[ax], t2 = (0.5f - qo[ax]) / qd[ax];
-                const float ta = fminf(t1, t2), tb = fmaxf(t1, t2);
+                // glm::min / glm::max (src/intersections.h:65-66) as the reference's GLM defines them, x < y ? x : y and x > y ? x : y:
+                // a NaN on either side (a ray in the plane of a face: 0/0) gives t2, where fminf / fmaxf give the other operand
+                const float ta = t1 < t2 ? t1 : t2, tb = t1 > t2 ? t1 : t2;
                 if (ta > 0.0f && ta > tmin) { tmin = ta; amin = ax; }
                 if (tb < tmax) { tmax = tb; amax = ax; }
             }

@@ -7,8 +7,10 @@ triangles to scene.render_scene's primitives exactly as the reference's first bo
 Triangle::Intersect, src/sceneStructs.h:157-180 — note its normal weights (b.x, b.y, 1-b.x-b.y) against the uv weights
 (1-b.x-b.y, b.x, b.y); Texture::getColor, src/sceneStructs.h:208-219).
 
-Host-side Python only: it is the oracle / fixture checker of this row (tests/test_ref_scenes.py compares it with the
-G-buffers the reference's own path tracer wrote); the device producer (csrc/svgf_scene.hip) still casts primitives only.
+Host-side Python only: it is the fixture checker of this row (tests/test_ref_scenes.py compares it with the G-buffers the
+reference's own path tracer wrote).  The device producer (csrc/svgf_scene.hip) casts the same triangles and textures after its
+primitives; `first_hit_gbuffer` is NOT its operation-for-operation model (np.cross and `@` leave the order of the sums to numpy,
+and it has no colour): that model is tests/scene_model.py, which tests/test_scene_model.py holds the kernel to bit for bit.
 """
 from __future__ import annotations
 

@@ -215,7 +215,9 @@ def render_scene(W: int, H: int, frame: int, geoms: np.ndarray, cam: dict, seed:
             if g["type"] == CUBE:
                 t1 = ((F(-0.5) - qo) / qd).astype(F)
                 t2 = ((F(0.5) - qo) / qd).astype(F)
-                ta, tb = np.minimum(t1, t2), np.maximum(t1, t2)
+                # glm::min / glm::max as the reference's GLM defines them (x < y ? x : y, x > y ? x : y): a NaN on either side gives
+                # t2.  np.minimum would give the NaN and fminf the other operand; they differ when a ray runs in a face's plane.
+                ta, tb = np.where(t1 < t2, t1, t2), np.where(t1 > t2, t1, t2)
                 tmin = np.full((H, W), F(-1e38), dtype=F)
                 tmax = np.full((H, W), F(1e38), dtype=F)
                 amin = np.zeros((H, W), dtype=np.int32)
