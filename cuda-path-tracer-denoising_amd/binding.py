@@ -22,6 +22,8 @@ LIB_EXP_PATH = os.path.join(_HERE, "libsvgf_hip_exp.so")     # -DSVGF_BUILD_EXPE
 
 SVGF_OK = 0
 STATE_HISTORY_LENGTH, STATE_MOMENTS, STATE_COLOR_HISTORY, STATE_VARIANCE_TEMPORAL, STATE_COLOR_ACC = range(5)
+# what the NEXT frame reads of the previous G-buffer, and svgf_set_output_taa's history (svgf_transfer_history moves all of them)
+STATE_PREV_NORMAL, STATE_PREV_POSITION, STATE_PREV_GEOM_ID, STATE_OUTPUT_HISTORY = 5, 6, 7, 8
 KERNEL_TEMPORAL, KERNEL_PREPARE, KERNEL_ATROUS, KERNEL_DEBUGVIEW, KERNEL_COPYOUT, KERNEL_FUSED, KERNEL_OUTPUT_TAA = 1, 2, 3, 4, 5, 6, 7
 MAX_LEVELS = 10
 # svgf_exp_level_kernels (experiments build): the kernel an a-trous level ran
@@ -38,7 +40,7 @@ EXPORTS = ["svgf_version", "svgf_params_default", "svgf_create", "svgf_destroy",
            "svgf_denoise_motion", "svgf_denoise_planar_motion", "svgf_motion_reproject",
            "svgf_set_history_clamp", "svgf_get_history_clamp", "svgf_set_object_motion", "svgf_get_object_motion",
            "svgf_set_firefly_filter", "svgf_get_firefly_filter", "svgf_set_output_taa", "svgf_get_output_taa",
-           "svgf_upsample"]
+           "svgf_upsample", "svgf_transfer_history"]
 CREATE_PIPELINED = 1
 # motion plane formats (svgf_denoise_motion): absolute previous coordinate, delta in float32, delta in float16
 MOTION_PREV_COORD_F32, MOTION_DELTA_F32, MOTION_DELTA_F16 = 1, 2, 3
@@ -186,6 +188,7 @@ def load_library(path: str | None = None, experiments: bool = False):
     lib.svgf_denoise_planar_motion.argtypes = [vp, vp, vp, vp, ip, C.POINTER(SvgfCamera), C.POINTER(SvgfParams), vp]
     lib.svgf_motion_reproject.argtypes = [ip, vp, ip, vp, vp, vp, ip, ip, C.POINTER(SvgfCamera), C.POINTER(C.c_float), vp, ip, vp]
     lib.svgf_upsample.argtypes = [ip, vp, C.POINTER(SvgfGuide), ip, ip, vp, C.POINTER(SvgfGuide), ip, ip, C.POINTER(SvgfUpsampleParams), vp]
+    lib.svgf_transfer_history.argtypes = [vp, vp, vp]
     lib.svgf_set_history_clamp.argtypes = [vp, ip, C.c_float]
     lib.svgf_get_history_clamp.argtypes = [vp, C.POINTER(ip), C.POINTER(C.c_float)]
     lib.svgf_set_firefly_filter.argtypes = [vp, ip, C.c_float]
@@ -442,13 +445,30 @@ class Denoiser:
         self._check(self.lib.svgf_get_object_motion(self.h, C.byref(ptr), C.byref(n)), "svgf_get_object_motion")
         return ptr.value, int(n.value)
 
+    def transfer_history_from(self, src: "Denoiser", stream=None):
+        """svgf_transfer_history: everything this context's next frame reads as history becomes `src`'s, resampled to this
+        context's size (colour history, moments, history lengths, previous G-buffer planes, previous view, and the output history
+        when both contexts have one); at equal sizes a bit-exact clone.  One launch on `stream`; this context's settings stay,
+        `src` is only read.  Both contexts' unfinished frames must have been given to `stream`, and this context's next frame
+        goes there too."""
+        if not isinstance(src, Denoiser) or src.lib is not self.lib:
+            raise SvgfError("transfer_history_from: src must be a Denoiser of the same library")
+        s = None if stream is None else (stream if isinstance(stream, int) else stream.cuda_stream)
+        self._check(self.lib.svgf_transfer_history(self.h, src.h, s), "svgf_transfer_history")
+
     def read_state(self, which: int) -> np.ndarray:
+        """Host copy of one state plane (STATE_*); STATE_OUTPUT_HISTORY is float32[H, W, 4] = {r, g, b, geomId bits} and raises
+        while the context has no output history."""
         n = self.width * self.height
         shape, dt = {STATE_HISTORY_LENGTH: ((self.height, self.width), np.int32),
                      STATE_MOMENTS: ((self.height, self.width, 2), np.float32),
                      STATE_COLOR_HISTORY: ((self.height, self.width, 3), np.float32),
                      STATE_VARIANCE_TEMPORAL: ((self.height, self.width), np.float32),
-                     STATE_COLOR_ACC: ((self.height, self.width, 3), np.float32)}[which]
+                     STATE_COLOR_ACC: ((self.height, self.width, 3), np.float32),
+                     STATE_PREV_NORMAL: ((self.height, self.width, 3), np.float32),
+                     STATE_PREV_POSITION: ((self.height, self.width, 3), np.float32),
+                     STATE_PREV_GEOM_ID: ((self.height, self.width), np.int32),
+                     STATE_OUTPUT_HISTORY: ((self.height, self.width, 4), np.float32)}[which]
         a = np.empty(shape, dtype=dt)
         assert a.size >= n
         self._check(self.lib.svgf_read_state(self.h, which, a.ctypes.data, a.nbytes), "svgf_read_state")

@@ -14,7 +14,7 @@ LIB = os.path.join(_HERE, "libsvgf_hip.so")
 # (svgf_exp_set).  Test / tools infrastructure: nothing on the product path loads it (binding.load_library(experiments=True) does).
 LIB_EXP = os.path.join(_HERE, "libsvgf_hip_exp.so")
 
-HIP_SOURCES = ["svgf_api.hip", "svgf_kernels.hip", "svgf_atrous_geometry.hip", "svgf_atrous_strip.hip", "svgf_atrous_lane.hip", "svgf_atrous_prepare_fused.hip", "svgf_atrous_lattice.hip", "svgf_synth.hip", "svgf_scene.hip", "svgf_display.hip", "svgf_upsample.hip"]
+HIP_SOURCES = ["svgf_api.hip", "svgf_kernels.hip", "svgf_atrous_geometry.hip", "svgf_atrous_strip.hip", "svgf_atrous_lane.hip", "svgf_atrous_prepare_fused.hip", "svgf_atrous_lattice.hip", "svgf_synth.hip", "svgf_scene.hip", "svgf_display.hip", "svgf_upsample.hip", "svgf_transfer.hip"]
 HIP_SOURCES_EXPERIMENTS = ["svgf_atrous_lane_reuse.hip", "svgf_atrous_fused.hip"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unused-function"]
 # Per-file flags.  svgf_atrous_fused.hip: SimplifyCFG's common-code sinking merges the last store of the "bilinear history" branch
@@ -74,11 +74,12 @@ def build_hip(force: bool = False, experiments: bool = False) -> str:
 
 def build_examples(force: bool = False) -> str:
     """examples/farm.cpp (N contexts on N GPUs from one C++ process), examples/pipeline.cpp (a renderer's frame loop on the frame
-    pipeline), examples/cadence.cpp (a fixed-rate loop + the effective shader clock) and examples/upsample.cpp (denoise at a reduced
-    size, svgf_upsample to the full size), through the C ABI -> examples/farm, examples/pipeline, examples/cadence,
-    examples/upsample, linked against the product library in-tree."""
+    pipeline), examples/cadence.cpp (a fixed-rate loop + the effective shader clock), examples/upsample.cpp (denoise at a reduced
+    size, svgf_upsample to the full size) and examples/dynres.cpp (the reduced size changes every few frames,
+    svgf_transfer_history carries the sequence along), through the C ABI -> examples/farm, examples/pipeline, examples/cadence,
+    examples/upsample, examples/dynres, linked against the product library in-tree."""
     out = ""
-    for name in ("pipeline", "farm", "cadence", "upsample"):
+    for name in ("pipeline", "farm", "cadence", "upsample", "dynres"):
         src = os.path.join(ROOT, "examples", name + ".cpp")
         out = os.path.join(ROOT, "examples", name)
         if not force and _newer(out, [src, os.path.join(ROOT, "include", "svgf.h"), LIB]):

@@ -1432,6 +1432,62 @@ extern "C" int svgf_upsample(int device, void *out_rgb_hi_dev, const SvgfGuide *
     return launch_upsample(a, (hipStream_t)stream) == hipSuccess ? SVGF_OK : SVGF_ERR_HIP;
 }
 
+// History transfer (k_transfer_history, svgf_transfer.hip): everything dst's next frame reads as history becomes src's, resampled to
+// dst's size.  One launch on `stream`; the planes written are the ones the indices hist, cur, gcur and taa_cur name.  Not a frame: no
+// profile entry, frame_no unchanged.  On contexts without pipeline resources it neither synchronises nor allocates.
+extern "C" int svgf_transfer_history(svgf_ctx *dst, svgf_ctx *src, void *stream)
+{
+    if (!dst || !src) return SVGF_ERR_INVALID_ARG;      // (neither context is touched)
+    if (dst == src) {
+        snprintf(dst->err, sizeof(dst->err), "svgf_transfer_history: dst and src are the same context");
+        return SVGF_ERR_INVALID_ARG;
+    }
+    if (dst->device != src->device) {
+        snprintf(dst->err, sizeof(dst->err), "svgf_transfer_history: dst lives on device %d, src on device %d", dst->device, src->device);
+        return SVGF_ERR_UNSUPPORTED;
+    }
+    SVGF_ENTER(dst);
+    const hipStream_t s = (hipStream_t)stream;
+    if (s) {      // (the legacy stream cannot be captured)
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(s, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) {
+            snprintf(dst->err, sizeof(dst->err), "svgf_transfer_history: `stream` is being captured into a graph; the call changes host state a replay would not");
+            return SVGF_ERR_UNSUPPORTED;
+        }
+    }
+    // Frames of a pipelined context may be running on its internal streams or on another stream of the caller's: wait for the device,
+    // as svgf_planar_gbuffer does.  dst's events are forgotten: its next frame orders itself behind the caller's stream as a whole
+    // (pipe_frames == 0), that is, behind the launch below.
+    const bool piped = dst->pipelined || src->pipelined;
+    if (piped) {
+        HIPC(dst, hipDeviceSynchronize());
+        pipe_reset(dst);
+    }
+    TransferArgs a;
+    memset(&a, 0, sizeof(a));
+    a.cv_s = src->cv[src->hist]; a.mom_s = src->mom[src->cur]; a.hlen_s = src->hlen[src->cur];
+    a.nrm_s = src->nrm[src->gcur]; a.pos_s = src->pos[src->gcur]; a.gid_s = src->gid[src->gcur];
+    a.cv_d = dst->cv[dst->hist]; a.mom_d = dst->mom[dst->cur]; a.hlen_d = dst->hlen[dst->cur];
+    a.nrm_d = dst->nrm[dst->gcur]; a.pos_d = dst->pos[dst->gcur]; a.gid_d = dst->gid[dst->gcur];
+    // the output history moves when dst has the pass on and src holds one; otherwise dst has none afterwards
+    const bool taa = dst->taa_hist[0] && dst->taa_alpha != 0.0f && src->taa_valid && src->taa_hist[0];
+    if (taa) { a.taa_s = src->taa_hist[src->taa_cur]; a.taa_d = dst->taa_hist[dst->taa_cur]; }
+    a.Ws = src->W; a.Hs = src->H; a.Wd = dst->W; a.Hd = dst->H;
+    a.rx = (float)src->W / (float)dst->W; a.ry = (float)src->H / (float)dst->H;
+    a.identity = (src->W == dst->W && src->H == dst->H) ? 1 : 0;
+    HIPC(dst, launch_transfer_history(a, s));
+    // the internal streams of a pipelined context carry its promised frames: whatever they run next runs behind the launch
+    for (svgf_ctx *c : { dst, src }) {
+        if (!c->pipelined) continue;
+        HIPC(dst, hipEventRecord(c->ev_in, s));
+        for (int q = 0; q < 2; q++) HIPC(dst, hipStreamWaitEvent(c->pipe[q], c->ev_in, 0));
+    }
+    memcpy(dst->view_prev, src->view_prev, sizeof(dst->view_prev));
+    dst->vp_valid = 0;      // derived from planes that hold something else now
+    dst->taa_valid = taa ? 1 : 0;
+    return SVGF_OK;
+}
+
 // ---- the planar path (the AoS -> plane repack fused into the producer) -----------------------
 static int planar_gbuffer(svgf_ctx *c, SvgfPlanarGBuffer *out, bool have_stream, hipStream_t stream)
 {
@@ -1548,6 +1604,23 @@ extern "C" int svgf_read_state(svgf_ctx *c, int which, void *host_dst, unsigned 
         free(tmp);
         return SVGF_OK;
     }
+    case SVGF_STATE_PREV_NORMAL:
+    case SVGF_STATE_PREV_POSITION:
+        if (!need(n * 3 * sizeof(float))) return SVGF_ERR_INVALID_ARG;
+        HIPC(c, hipMemcpy(host_dst, which == SVGF_STATE_PREV_NORMAL ? c->nrm[c->gcur] : c->pos[c->gcur], n * 3 * sizeof(float), hipMemcpyDeviceToHost));
+        return SVGF_OK;
+    case SVGF_STATE_PREV_GEOM_ID:
+        if (!need(n * sizeof(int))) return SVGF_ERR_INVALID_ARG;
+        HIPC(c, hipMemcpy(host_dst, c->gid[c->gcur], n * sizeof(int), hipMemcpyDeviceToHost));
+        return SVGF_OK;
+    case SVGF_STATE_OUTPUT_HISTORY:
+        if (!c->taa_valid || !c->taa_hist[c->taa_cur]) {
+            snprintf(c->err, sizeof(c->err), "svgf_read_state: the context has no output history");
+            return SVGF_ERR_INVALID_ARG;
+        }
+        if (!need(n * sizeof(float4))) return SVGF_ERR_INVALID_ARG;
+        HIPC(c, hipMemcpy(host_dst, c->taa_hist[c->taa_cur], n * sizeof(float4), hipMemcpyDeviceToHost));
+        return SVGF_OK;
     default:
         snprintf(c->err, sizeof(c->err), "svgf_read_state: unknown state %d", which);
         return SVGF_ERR_INVALID_ARG;

@@ -182,6 +182,25 @@ struct UpsampleArgs {
     int modulate;
 };
 hipError_t launch_upsample(const UpsampleArgs &a, hipStream_t s);
+// svgf_transfer_history: what the next frame of one context reads as history, resampled from another context (svgf_transfer.hip)
+struct TransferArgs {
+    const float4 *cv_s;       // src: colour history (+ variance in .w)
+    const float2 *mom_s;
+    const int *hlen_s;
+    const float *nrm_s, *pos_s;   // packed float3 planes of the previous G-buffer
+    const int *gid_s;
+    const float4 *taa_s;      // {output, geomId bits}; null: no output history moves (taa_d is not written)
+    float4 *cv_d;             // dst: the same planes
+    float2 *mom_d;
+    int *hlen_d;
+    float *nrm_d, *pos_d;
+    int *gid_d;
+    float4 *taa_d;
+    int Ws, Hs, Wd, Hd;
+    float rx, ry;             // (float)Ws / (float)Wd, (float)Hs / (float)Hd
+    int identity;             // Ws == Wd && Hs == Hd: every plane is copied bit for bit
+};
+hipError_t launch_transfer_history(const TransferArgs &a, hipStream_t s);
 // svgf_set_output_taa: the last launch of a frame.  `pre` holds the image the frame would have written to `out` (the last level or
 // the pass-through copy was pointed at it); per pixel the previous OUTPUT is looked up at the temporal pass's previous-frame
 // coordinate, clipped to the 3x3 window of `pre` (svgf_history_clamp<1>) and blended.  The output history carries the geomId it was

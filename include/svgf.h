@@ -552,6 +552,60 @@ int svgf_upsample(int device, void *out_rgb_hi_dev, const SvgfGuide *hi, int wid
                   const void *rgb_lo_dev, const SvgfGuide *lo, int width_lo, int height_lo,
                   const SvgfUpsampleParams *up, void *stream);
 
+/* ---- "next" row f11: history transfer across a resolution change (added after 0.9; probe the symbol) ----------------------------
+ * A renderer that denoises at a reduced size (row f10) changes that size from frame to frame; a context is bound to one size for
+ * life.  svgf_transfer_history carries the whole history of `src` into `dst`, a context of a different (or the same) size on the same
+ * device: everything the next frame of `dst` reads as history becomes `src`'s, resampled to `dst`'s size - the colour history, the
+ * moments and history lengths, the previous normals, positions and geomIds, the previous view matrix (copied on the host) and, when
+ * both contexts have one, f9's output history.  Whatever `dst` held before is gone, as after svgf_reset(dst).  One launch on
+ * `stream`; at equal sizes a bit-exact clone of a sequence.
+ * What does not move: `dst`'s configuration (history clamp, firefly filter, object motion, output-TAA settings, pipeline resources,
+ * profiling, capture) is unchanged; `src` is only read - a frame given to it afterwards is bit-identical to that frame on a `src` that
+ * was never transferred from; data derived from the planes written (the variance copies of the coarse levels) is invalidated, not
+ * transferred; the call is not a frame: no profile entry, the frame counters are unchanged.
+ * Normative arithmetic, float32 without contraction, every float a defined input; Ws x Hs = src's size, Wd x Hd = dst's:
+ *   Ws == Wd && Hs == Hd: every plane is copied bit for bit.  No arithmetic touches the values: NaN and inf survive unchanged.
+ *   otherwise, per dst pixel P = (x, y):
+ *     rx = (float)Ws / (float)Wd;  ry = (float)Hs / (float)Hd                                      (float32 divisions)
+ *     u = ((float)x + 0.5f) * rx - 0.5f;  v = ((float)y + 0.5f) * ry - 0.5f                        (svgf_upsample's mapping)
+ *     anchor A = (min(max((int)floorf(u + 0.5f), 0), Ws - 1), min(max((int)floorf(v + 0.5f), 0), Hs - 1))
+ *     g = gid_s[A]
+ *     gid_d[P] = g;  normal_d[P] = normal_s[A];  position_d[P] = position_s[A];  hlen_d[P] = hlen_s[A]    (bit copies: true texels, never blends)
+ *     fx = floorf(u), ax = u - fx;  fy = floorf(v), ay = v - fy;  w = {(1-ax)(1-ay), ax (1-ay), (1-ax) ay, ax ay}
+ *     tap k = 0..3 at (fx + (k & 1), fy + (k >> 1)); a tap counts when it lies inside the src image and gid_s[tap] == g
+ *     in order of k over the counted taps:  col += w[k] * colour_s[tap];  mom += w[k] * moments_s[tap];  sumw += w[k]
+ *     if ((double)sumw >= 0.01) { colour_d[P] = col / sumw;  moments_d[P] = mom / sumw }  else  { the anchor's values, bit copies }
+ *     (the anchor is always one of the four taps, with weight about 0.25 or more: the else branch is there for NaN weights only)
+ *   the fourth component of the colour plane (the variance the history plane carries along) is the anchor's.
+ *   The history length is the anchor's on purpose: a weighted mean truncated to int can lose 1 to rounding on a constant field, and a
+ *   transfer must neither age nor rejuvenate a sequence.
+ *   Output history: when `dst` has f9 on (svgf_set_output_taa with alpha != 0) and `src` holds a valid output history, the same gather
+ *   runs on the output history's rgb, the anchor and g taken from the geomId bits stored with src's output history, and {result, g} is
+ *   written to the plane dst's next frame reads: dst's output history is valid.  In every other case `dst` has no output history
+ *   afterwards and its next frame takes f9's rule 1.
+ * Ratios above 2 subsample (the footprint stays 2 x 2 src texels).  The previous positions are texels of src's grid: with
+ * SvgfParams::reproj_position_tol > 0 a transferred tap sits up to half a src texel away from where a native previous frame of dst's
+ * size would have put it - choose the tolerance with that in mind.  Motion vectors of dst's next frame are in
+ * dst's pixel units, as always.
+ * Errors, answered before any device work: NULL dst or src, and dst == src: SVGF_ERR_INVALID_ARG; contexts on different devices:
+ * SVGF_ERR_UNSUPPORTED; a `stream` that is being captured into a graph: SVGF_ERR_UNSUPPORTED (the call changes host state that a
+ * replay would not).  Pixel indices are 64-bit: every size svgf_create accepts is supported.
+ * Ordering: the launch is enqueued on `stream` (a hipStream_t, NULL = default stream).  The caller's contract: frames of both contexts
+ * that are not complete have been given to `stream` (or `stream` has been ordered behind them), and dst's next frame goes to `stream`
+ * or is ordered behind it; so is whatever overwrites src's history (its frame after next).  On contexts without pipeline resources
+ * the call never synchronises and never allocates.  If either context has pipeline resources the call first waits for the device, as
+ * svgf_planar_gbuffer does on such a context, forgets dst's pipeline events - dst's next frame runs behind `stream` as a whole, like
+ * the first frame after svgf_reset; whether dst alternates its plane sets stays as it is - and orders the internal streams of
+ * both contexts behind the launch.  It writes exactly the planes dst's next frame reads.
+ * The planes are read back through svgf_read_state kinds 0-2 and 5-8 below; INTEGRATION.md 5g has the recipe (one context per
+ * resolution step), examples/dynres.cpp a loop. */
+int svgf_transfer_history(svgf_ctx *dst, svgf_ctx *src, void *stream);
+/* added after 0.9; probe the symbol (SVGF_ERR_INVALID_ARG from a library that lacks them).  More svgf_read_state kinds. */
+#define SVGF_STATE_PREV_NORMAL     5   /* float[3*W*H] the normals the NEXT frame tests its taps against */
+#define SVGF_STATE_PREV_POSITION   6   /* float[3*W*H] */
+#define SVGF_STATE_PREV_GEOM_ID    7   /* int32[W*H]   */
+#define SVGF_STATE_OUTPUT_HISTORY  8   /* float[4*W*H] {r, g, b, geomId bits}: f9's output history; SVGF_ERR_INVALID_ARG while the context has none */
+
 /* ---- "next" row f2: the step right after denoise() ------------------------------------------------
  * svgf_display_pack: reference sendTwoImagesToPBO (src/pathtrace.cu:45-77, launched at :446): `left` (the 1-spp
  *   image) and `right` (the denoised image), both packed rgb floats in device memory, side by side into a
