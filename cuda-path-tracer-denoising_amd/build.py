@@ -14,8 +14,8 @@ LIB = os.path.join(_HERE, "libsvgf_hip.so")
 # (svgf_exp_set).  Test / tools infrastructure: nothing on the product path loads it (binding.load_library(experiments=True) does).
 LIB_EXP = os.path.join(_HERE, "libsvgf_hip_exp.so")
 
-HIP_SOURCES = ["svgf_api.hip", "svgf_kernels.hip", "svgf_atrous_geometry.hip", "svgf_atrous_strip.hip", "svgf_atrous_lane.hip", "svgf_atrous_prepare_fused.hip", "svgf_atrous_lattice.hip", "svgf_synth.hip", "svgf_scene.hip", "svgf_display.hip", "svgf_upsample.hip", "svgf_transfer.hip"]
-HIP_SOURCES_EXPERIMENTS = ["svgf_atrous_lane_reuse.hip", "svgf_atrous_fused.hip"]
+HIP_SOURCES = ["svgf_api.hip", "svgf_frame.hip", "svgf_pipeline.hip", "svgf_profiler.hip", "svgf_kernels.hip", "svgf_atrous_geometry.hip", "svgf_atrous_strip.hip", "svgf_atrous_lane.hip", "svgf_atrous_prepare_fused.hip", "svgf_atrous_lattice.hip", "svgf_synth.hip", "svgf_scene.hip", "svgf_display.hip", "svgf_upsample.hip", "svgf_transfer.hip"]
+HIP_SOURCES_EXPERIMENTS = ["svgf_experiments.hip", "svgf_atrous_lane_reuse.hip", "svgf_atrous_fused.hip"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unused-function"]
 # Per-file flags.  svgf_atrous_fused.hip: SimplifyCFG's common-code sinking merges the last store of the "bilinear history" branch
 # with the last store of the "fallback consistency data" branch of the temporal stage into ONE store through a phi of two

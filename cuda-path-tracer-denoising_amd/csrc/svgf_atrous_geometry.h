@@ -1,6 +1,6 @@
 // svgf_atrous_geometry.h — how an a-trous level is launched: which kernels can run it, how the image is cut into workgroups,
 // and what the launch is estimated to cost.  Host arithmetic on (AtrousArgs, CU count) only — no kernel, no device call — so the
-// planner (svgf_api.hip), the launchers in the kernel files and, in the experiments build, svgf_exp_atrous_geometry
+// planner (svgf_frame.hip), the launchers in the kernel files and, in the experiments build, svgf_exp_atrous_geometry
 // (tests/test_kernel_geometry.py, which needs no GPU) all ask the same functions.  Internal, like svgf_kernels.h.
 #pragma once
 #include "svgf_kernels.h"

@@ -5,7 +5,7 @@
 // steps 16 / 32: 120 / 60 lattice columns of 4 / 8 x-phases), the strip kernel on 256-column strips; both cut the image into
 // (strip, y-phase, segment) workgroups that run in rounds of one per CU, and both know what their launch will cost:
 // rounds x (segment rows + fixed rows) x the time of a row (1.86 us lane, 1.16 us strip: 42.7 against 48.8 us at 1920x1080).
-// The cheaper one runs (lane_pays, svgf_api.hip).  Measured against that model at nine sizes (profiles/r03_exp_widths*.log): within
+// The cheaper one runs (lane_pays, svgf_frame.hip).  Measured against that model at nine sizes (profiles/r03_exp_widths*.log): within
 // 5 %, same choice as the stopwatch everywhere — lane at 1920, 3840, 1600, 3440, 800 (steps 2-8), 2560 and 1280 (steps 2-8, 32);
 // strip at 1024, 2048, and at steps 16 of 800 / 1280 / 2560.  That holds for frames taller than about six lattice rows per level
 // (H / step >= 6); shorter phases are one segment each on both kernels, and the one-round launches then favour the strip kernel's

@@ -1,4 +1,4 @@
-// svgf_kernels.h — launch wrappers shared between the host orchestration (svgf_api.hip) and the
+// svgf_kernels.h — launch wrappers shared between the host orchestration (svgf_frame.hip) and the
 // kernel translation units (which kernel can run a level, and with which launch geometry: svgf_atrous_geometry.h).
 // Internal; the public boundary is include/svgf.h.
 //
@@ -20,19 +20,19 @@
 // by tools/experiments/ and the tests marked `experiments`): a name -> int table filled through svgf_exp_set().  The product build
 // compiles every SVGF_TUNE() to its default, reads no environment variable and instantiates none of the parked kernels.
 #ifdef SVGF_BUILD_EXPERIMENTS
-int svgf_exp_get(const char *name, int dflt);       // svgf_api.hip
+int svgf_exp_get(const char *name, int dflt);       // svgf_experiments.hip
 #define SVGF_TUNE(name, dflt) svgf_exp_get(name, dflt)
 #else
 #define SVGF_TUNE(name, dflt) (dflt)
 #endif
 
-// Profiling hand-off.  svgf_api.hip's KernelTimer arms an event pair for the NEXT kernel launch of this host thread; the launch
+// Profiling hand-off.  svgf_profiler.hip's KernelTimer arms an event pair for the NEXT kernel launch of this host thread; the launch
 // macro hands it to hipExtLaunchKernelGGL, which attaches the events to the DISPATCH itself: start / stop are the kernel's own
 // begin / end timestamps (what rocprofv3 reports), and nothing is added to the stream.  hipEventRecord pairs around a launch —
 // rounds 1-3 — put a barrier packet on either side of every kernel: the intervals read 2-3 us long and an instrumented frame
 // ran 23-46 us longer (profiles/r04_clock_states.txt).
 struct SvgfLaunchEvents { hipEvent_t start, stop; };
-extern thread_local SvgfLaunchEvents g_svgf_launch_events;      // defined in svgf_api.hip
+extern thread_local SvgfLaunchEvents g_svgf_launch_events;      // defined in svgf_profiler.hip
 #define SVGF_LAUNCH_KERNEL(kernel, grid, block, lds, stream, ...)                                                        \
     do {                                                                                                                 \
         if (g_svgf_launch_events.start) {                                                                                \

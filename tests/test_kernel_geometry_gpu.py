@@ -2,7 +2,7 @@
 
 With kernel_variant 0 every level at steps 2-32 runs the lane-marching kernel (svgf_atrous_lane_impl.h) or the LDS strip kernel
 (svgf_atrous_strip.hip), whichever the launch-geometry cost model (csrc/svgf_atrous_geometry.hip; memoised per context by lane_pays,
-csrc/svgf_api.hip) estimates cheaper; each kernel then cuts the image into (strip, y-phase, segment) workgroups by the segment-length
+csrc/svgf_frame.hip) estimates cheaper; each kernel then cuts the image into (strip, y-phase, segment) workgroups by the segment-length
 search of the same file (tests/test_kernel_geometry.py holds that arithmetic to a table, and CHOICE_256 below, without a GPU).  The experiments build records
 the kernel of every level of the last frame (Denoiser.level_kernels); these tests hold that record to a committed table, tie it
 to what the product library computes (bit-identical outputs), and compare EVERY level, not only the last, with the oracle.
