@@ -12,4 +12,5 @@ name `cuda_path_tracer_denoising_amd`.
 from . import binding, build, farm, scene, synth  # noqa: F401
 from .binding import Denoiser, SvgfCamera, SvgfParams, SvgfError, load_library, reference_defaults  # noqa: F401
 from .binding import SvgfGuide, SvgfUpsampleParams, upsample  # noqa: F401
+from .binding import SvgfExposureParams, SvgfTonemapParams, exposure_state, exposure_reset, exposure_meter, display_tonemap, srgb_table  # noqa: F401
 from .binding import STATE_PREV_NORMAL, STATE_PREV_POSITION, STATE_PREV_GEOM_ID, STATE_OUTPUT_HISTORY  # noqa: F401

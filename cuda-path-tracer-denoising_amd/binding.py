@@ -40,8 +40,13 @@ EXPORTS = ["svgf_version", "svgf_params_default", "svgf_create", "svgf_destroy",
            "svgf_denoise_motion", "svgf_denoise_planar_motion", "svgf_motion_reproject",
            "svgf_set_history_clamp", "svgf_get_history_clamp", "svgf_set_object_motion", "svgf_get_object_motion",
            "svgf_set_firefly_filter", "svgf_get_firefly_filter", "svgf_set_output_taa", "svgf_get_output_taa",
-           "svgf_upsample", "svgf_transfer_history"]
+           "svgf_upsample", "svgf_transfer_history",
+           "svgf_exposure_reset", "svgf_exposure_meter", "svgf_display_tonemap", "svgf_tonemap_srgb_table"]
 CREATE_PIPELINED = 1
+EXPOSURE_STATE_WORDS = 520
+# SvgfTonemapParams.op / .transfer
+TONEMAP_NONE, TONEMAP_REINHARD, TONEMAP_ACES = 0, 1, 2
+TRANSFER_LINEAR, TRANSFER_GAMMA2, TRANSFER_SRGB = 0, 1, 2
 # motion plane formats (svgf_denoise_motion): absolute previous coordinate, delta in float32, delta in float16
 MOTION_PREV_COORD_F32, MOTION_DELTA_F32, MOTION_DELTA_F16 = 1, 2, 3
 
@@ -89,6 +94,17 @@ class SvgfGuide(C.Structure):
 
 class SvgfUpsampleParams(C.Structure):
     _fields_ = [("sigma_n", C.c_float), ("sigma_x", C.c_float), ("modulate", C.c_int)]
+
+
+class SvgfExposureParams(C.Structure):
+    """svgf_exposure_meter: the metered average is mapped to `key`; trims in 1/1024 of the counted pixels; `adapt` is the share of
+    the way to the target taken per metering."""
+    _fields_ = [("key", C.c_float), ("trim_low_1024", C.c_int), ("trim_high_1024", C.c_int), ("min_exposure", C.c_float),
+                ("max_exposure", C.c_float), ("adapt", C.c_float)]
+
+
+class SvgfTonemapParams(C.Structure):
+    _fields_ = [("op", C.c_int), ("transfer", C.c_int), ("exposure_bias", C.c_float), ("white", C.c_float)]
 
 
 class SvgfSynthParams(C.Structure):
@@ -230,6 +246,10 @@ def load_library(path: str | None = None, experiments: bool = False):
         raise SvgfError(f"libsvgf_hip.so was built with sizeof(SvgfParams) = {lib.svgf_params_sizeof()}, this binding has {C.sizeof(SvgfParams)}")
     lib.svgf_display_pack.argtypes = [ip, vp, vp, vp, ip, ip, vp]
     lib.svgf_save_png.argtypes = [C.c_char_p, vp, ip, ip, ip]
+    lib.svgf_exposure_reset.argtypes = [ip, vp, vp]
+    lib.svgf_exposure_meter.argtypes = [ip, vp, vp, ip, ip, C.POINTER(SvgfExposureParams), vp]
+    lib.svgf_display_tonemap.argtypes = [ip, vp, vp, vp, ip, ip, C.POINTER(SvgfTonemapParams), vp, vp]
+    lib.svgf_tonemap_srgb_table.argtypes = [C.POINTER(C.c_float)]
     if path == LIB_PATH:
         _lib = lib
     return lib
@@ -601,6 +621,56 @@ def display_pack(pbo, left, right, width: int, height: int, device: int = 0, str
     rc = lib.svgf_display_pack(int(device), _ptr(pbo), _ptr(left), _ptr(right), int(width), int(height), s)
     if rc != SVGF_OK:
         raise SvgfError(f"svgf_display_pack failed ({rc})")
+
+
+# --- row f12: HDR display (luminance histogram, auto-exposure, tone-mapped pack) ---------------------------------------------------
+def _stream(stream):
+    return None if stream is None else (stream if isinstance(stream, int) else stream.cuda_stream)
+
+
+def exposure_reset(state, device: int = 0, stream=None):
+    """svgf_exposure_reset: `state` (device, EXPOSURE_STATE_WORDS int32) back to "no metering yet", exposure 1."""
+    rc = load_library().svgf_exposure_reset(int(device), _ptr(state), _stream(stream))
+    if rc != SVGF_OK:
+        raise SvgfError(f"svgf_exposure_reset failed ({rc})")
+
+
+def exposure_state(device: int = 0):
+    """A fresh exposure state on `device`: a 520-element int32 tensor, already reset (the reset has completed on return)."""
+    import torch
+    state = torch.empty((EXPOSURE_STATE_WORDS,), dtype=torch.int32, device=f"cuda:{int(device)}")
+    exposure_reset(state, device=device)
+    torch.cuda.synchronize(int(device))
+    return state
+
+
+def exposure_meter(state, rgb, width: int, height: int, key: float = 0.18, trim_low_1024: int = 51, trim_high_1024: int = 51,
+                   min_exposure: float = 1.0 / 64.0, max_exposure: float = 64.0, adapt: float = 1.0, device: int = 0, stream=None):
+    """svgf_exposure_meter: the luminance histogram of `rgb` (packed rgb float, device) and the exposure step, into `state`."""
+    ep = SvgfExposureParams(float(key), int(trim_low_1024), int(trim_high_1024), float(min_exposure), float(max_exposure), float(adapt))
+    rc = load_library().svgf_exposure_meter(int(device), _ptr(state), _ptr(rgb), int(width), int(height), C.byref(ep), _stream(stream))
+    if rc != SVGF_OK:
+        raise SvgfError(f"svgf_exposure_meter failed ({rc})")
+
+
+def display_tonemap(pbo, left, right, width: int, height: int, op: int = TONEMAP_ACES, transfer: int = TRANSFER_SRGB,
+                    exposure_bias: float = 1.0, white: float = 0.0, state=None, device: int = 0, stream=None):
+    """svgf_display_tonemap: `left` | `right` (or `right` alone when `left` is None) through exposure (exposure_bias x the metered
+    exposure of `state`, or exposure_bias alone), tone curve and display transfer -> (height, 2*width or width, 4) uint8 on the device."""
+    tp = SvgfTonemapParams(int(op), int(transfer), float(exposure_bias), float(white))
+    rc = load_library().svgf_display_tonemap(int(device), _ptr(pbo), _ptr(left), _ptr(right), int(width), int(height), C.byref(tp),
+                                             _ptr(state), _stream(stream))
+    if rc != SVGF_OK:
+        raise SvgfError(f"svgf_display_tonemap failed ({rc})")
+
+
+def srgb_table() -> np.ndarray:
+    """svgf_tonemap_srgb_table: the 256 float32 thresholds transfer 2 searches."""
+    t = np.empty(256, dtype=np.float32)
+    rc = load_library().svgf_tonemap_srgb_table(t.ctypes.data_as(C.POINTER(C.c_float)))
+    if rc != SVGF_OK:
+        raise SvgfError(f"svgf_tonemap_srgb_table failed ({rc})")
+    return t
 
 
 def save_png(path: str, rgb: np.ndarray, mirror_x: bool = True):

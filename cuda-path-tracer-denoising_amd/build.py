@@ -75,11 +75,12 @@ def build_hip(force: bool = False, experiments: bool = False) -> str:
 def build_examples(force: bool = False) -> str:
     """examples/farm.cpp (N contexts on N GPUs from one C++ process), examples/pipeline.cpp (a renderer's frame loop on the frame
     pipeline), examples/cadence.cpp (a fixed-rate loop + the effective shader clock), examples/upsample.cpp (denoise at a reduced
-    size, svgf_upsample to the full size) and examples/dynres.cpp (the reduced size changes every few frames,
-    svgf_transfer_history carries the sequence along), through the C ABI -> examples/farm, examples/pipeline, examples/cadence,
-    examples/upsample, examples/dynres, linked against the product library in-tree."""
+    size, svgf_upsample to the full size), examples/dynres.cpp (the reduced size changes every few frames,
+    svgf_transfer_history carries the sequence along) and examples/hdr_display.cpp (an emitter far above 1: svgf_exposure_meter on
+    the denoised image, svgf_display_tonemap beside the plain pack), through the C ABI -> examples/farm, examples/pipeline,
+    examples/cadence, examples/upsample, examples/dynres, examples/hdr_display, linked against the product library in-tree."""
     out = ""
-    for name in ("pipeline", "farm", "cadence", "upsample", "dynres"):
+    for name in ("pipeline", "farm", "cadence", "upsample", "dynres", "hdr_display"):
         src = os.path.join(ROOT, "examples", name + ".cpp")
         out = os.path.join(ROOT, "examples", name)
         if not force and _newer(out, [src, os.path.join(ROOT, "include", "svgf.h"), LIB]):

@@ -616,6 +616,75 @@ int svgf_display_pack(int device, void *pbo_rgba8_dev, const void *left_rgb_dev,
                       int height, void *stream);
 int svgf_save_png(const char *path, const float *rgb_host, int width, int height, int mirror_x);
 
+/* ---- "next" row f12: HDR display - luminance histogram, auto-exposure, tone-mapped pack (added after 0.9; probe the symbol) ------
+ * Everything upstream of svgf_display_pack is HDR radiance and the pack clips it at 1.  These entry points meter an image (a
+ * log-luminance histogram over the whole chip), keep an exposure that follows the metered average, and pack with that exposure, a
+ * tone curve and a display transfer.  All three device entry points are stateless (the exposure lives in SVGF_EXPOSURE_STATE_WORDS
+ * 32-bit words of DEVICE memory the caller owns, 4-byte aligned), asynchronous on `stream` and allocate nothing; calls on one stream
+ * are ordered.  Normative arithmetic: float32 without contraction, integers otherwise, every float a defined input, no
+ * transcendental anywhere.
+ * State words: [0..255] accumulating histogram, zero between meterings; [256..511] histogram of the last metered image; [512] n;
+ *   [513] m; [514] Lbits; [515] target (float); [516] exposure (float); [517] meterings since reset; [518..519] 0.
+ * svgf_exposure_reset (one launch) writes all 520 words: zero, except [515] = [516] = 1.0f.
+ * svgf_exposure_meter, launch 1, per pixel of `rgb_dev` (packed rgb, width x height):
+ *   L = the library's luminance, (float)((0.2126 (double)r + 0.7152 (double)g) + 0.0722 (double)b)
+ *   the pixel is counted iff L == L && L > 0 && L < +inf
+ *   bin = min(max((int)(bits(L) >> 20) - 888, 0), 255)      sign, exponent and three mantissa bits: eight bins per octave from
+ *                                                            2^-16; bin 0 also takes everything smaller, bin 255 everything from 61440 up
+ *   word[bin] += 1                                           integers: the result does not depend on arrival order
+ * launch 2 (one workgroup):
+ *   h = word[0..255];  n = sum h
+ *   lo = (n * trim_low_1024) >> 10;  hi = (n * trim_high_1024) >> 10                                (64-bit products)
+ *   P[0] = 0;  P[b+1] = P[b] + h[b];  c[b] = max(0, min(P[b+1], n - hi) - max(P[b], lo));  m = sum c
+ *   if m > 0:  S = sum c[b] * (2 * (888 + b) + 1) (64 bits);  Lbits = (uint32)(((S << 19) + (m >> 1)) / m);  Lavg = as_float(Lbits)
+ *              (the mean of the bins' centre bit patterns: the inverse of the piecewise-linear logarithm the binning uses)
+ *              t = key / Lavg;  if (t < min_exposure) t = min_exposure;  if (t > max_exposure) t = max_exposure
+ *   if m == 0: Lbits = 0;  t = (word[517] > 0) ? as_float(word[516]) : 1.0f
+ *   prev = as_float(word[516]);  e = (word[517] == 0) ? t : prev + ((t - prev) * adapt)
+ *   writes: word[256 + b] = h[b];  word[b] = 0;  [512] = n;  [513] = m;  [514] = Lbits;  [515] = t;  [516] = e;
+ *           [517] = min(word[517] + 1, 2^31 - 1);  [518] = [519] = 0
+ *   The second launch zeroes the accumulating bins: consecutive meterings on one stream are independent and the caller never clears
+ *   anything after the one reset.
+ * svgf_display_tonemap (one launch):
+ *   e = state_dev ? exposure_bias * as_float(state[516]) : exposure_bias                            (multiplied on the device)
+ *   iw2 = white > 0 ? 1.0f / (white * white) : 0.0f                                                 (on the host)
+ *   per channel v of either image:  x = v * e
+ *   op 0: y = x.   ops 1 and 2 first:  if (!(x > 0.0f)) x = 0.0f;  if (x > 65504.0f) x = 65504.0f
+ *   op 1: y = (x * (1.0f + x * iw2)) / (1.0f + x)
+ *   op 2: y = (x * (2.51f * x + 0.03f)) / (x * (2.43f * x + 0.59f) + 0.14f)
+ *   transfer 0: byte = clamp((int)((double)y * 255.0), 0, 255); the conversion saturates and maps NaN to 0: svgf_display_pack's
+ *   transfer 1: the same conversion of sqrtf(y)
+ *   transfer 2: byte = #{k in 1..255 : y >= T[k]}, T[k] the float32 nearest to the sRGB decode of k / 255 computed in double
+ *               (c / 12.92 for c <= 0.04045, else ((c + 0.055) / 1.055)^2.4); the 256 values are literals of the library, which
+ *               never calls pow; svgf_tonemap_srgb_table returns them
+ *   alpha = 0.  left_rgb_dev == NULL: the buffer is width x height and holds `right` alone; otherwise it is (2 width) x height, side
+ *   by side as svgf_display_pack packs, and both halves get the same mapping.
+ * SVGF_ERR_INVALID_ARG, answered before any device work: a NULL state_dev (reset and meter), rgb_dev, pbo_rgba8_dev, right_rgb_dev,
+ * ep, tp or thresholds; a size <= 0; key, min_exposure or max_exposure that is not finite and > 0, or min_exposure > max_exposure;
+ * adapt outside (0, 1]; a trim outside [0, 1023] or trim_low_1024 + trim_high_1024 > 1023 (within the limit m >= 1 whenever
+ * n >= 1); op or transfer outside 0..2; exposure_bias or white negative, NaN or infinite.  SVGF_ERR_UNSUPPORTED:
+ * width * height >= 2^31 / 16.  INTEGRATION.md 6a says what to meter and which values to start from. */
+#define SVGF_EXPOSURE_STATE_WORDS 520            /* 2080 bytes of DEVICE memory the caller owns, 4-byte aligned */
+typedef struct SvgfExposureParams {              /* 24 bytes */
+    float key;              /* luminance the metered average is mapped to (0.18) */
+    int   trim_low_1024;    /* darkest  share of the counted pixels left out, in 1/1024 (51)  */
+    int   trim_high_1024;   /* brightest share left out, in 1/1024 (51) */
+    float min_exposure, max_exposure;            /* clamp of the target (1/64, 64) */
+    float adapt;            /* share of the way to the target taken per metering, (0, 1]; the caller turns dt into it */
+} SvgfExposureParams;
+typedef struct SvgfTonemapParams {               /* 16 bytes */
+    int   op;               /* 0 none, 1 extended Reinhard per channel, 2 ACES fit (Narkowicz) */
+    int   transfer;         /* 0 linear (the reference), 1 gamma 2.0 (sqrtf), 2 sRGB by threshold table */
+    float exposure_bias;    /* multiplies the metered exposure (or stands alone when state == NULL) */
+    float white;            /* op 1: white point, 0 = plain Reinhard */
+} SvgfTonemapParams;
+int svgf_exposure_reset (int device, void *state_dev, void *stream);
+int svgf_exposure_meter (int device, void *state_dev, const void *rgb_dev, int width, int height,
+                         const SvgfExposureParams *ep, void *stream);
+int svgf_display_tonemap(int device, void *pbo_rgba8_dev, const void *left_rgb_dev, const void *right_rgb_dev,
+                         int width, int height, const SvgfTonemapParams *tp, const void *state_dev, void *stream);
+int svgf_tonemap_srgb_table(float thresholds[256]);      /* host only: the table transfer 2 uses */
+
 #ifdef __cplusplus
 }
 #endif
