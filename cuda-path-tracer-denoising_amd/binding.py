@@ -41,7 +41,8 @@ EXPORTS = ["svgf_version", "svgf_params_default", "svgf_create", "svgf_destroy",
            "svgf_set_history_clamp", "svgf_get_history_clamp", "svgf_set_object_motion", "svgf_get_object_motion",
            "svgf_set_firefly_filter", "svgf_get_firefly_filter", "svgf_set_output_taa", "svgf_get_output_taa",
            "svgf_upsample", "svgf_transfer_history",
-           "svgf_exposure_reset", "svgf_exposure_meter", "svgf_display_tonemap", "svgf_tonemap_srgb_table"]
+           "svgf_exposure_reset", "svgf_exposure_meter", "svgf_display_tonemap", "svgf_tonemap_srgb_table",
+           "svgf_quality_state_bytes", "svgf_quality_windows", "svgf_quality_meter", "svgf_quality_read"]
 CREATE_PIPELINED = 1
 EXPOSURE_STATE_WORDS = 520
 # SvgfTonemapParams.op / .transfer
@@ -105,6 +106,18 @@ class SvgfExposureParams(C.Structure):
 
 class SvgfTonemapParams(C.Structure):
     _fields_ = [("op", C.c_int), ("transfer", C.c_int), ("exposure_bias", C.c_float), ("white", C.c_float)]
+
+
+class SvgfQualityParams(C.Structure):
+    """svgf_quality_meter: `peak` is the signal's white, `scale` multiplies both images first, `clamp` = 1 clamps to [0, peak]."""
+    _fields_ = [("peak", C.c_float), ("scale", C.c_float), ("clamp", C.c_int)]
+
+
+class SvgfQualityResult(C.Structure):
+    """svgf_quality_read: the eight device words, then the three quotients formed on the host."""
+    _fields_ = [("n_pixels", C.c_ulonglong), ("n_windows", C.c_ulonglong), ("sum_se", C.c_double), ("sum_ssim", C.c_double),
+                ("max_abs", C.c_double), ("min_ssim", C.c_double), ("peak", C.c_double), ("scale", C.c_double),
+                ("mse", C.c_double), ("psnr_db", C.c_double), ("mean_ssim", C.c_double)]
 
 
 class SvgfSynthParams(C.Structure):
@@ -250,6 +263,11 @@ def load_library(path: str | None = None, experiments: bool = False):
     lib.svgf_exposure_meter.argtypes = [ip, vp, vp, ip, ip, C.POINTER(SvgfExposureParams), vp]
     lib.svgf_display_tonemap.argtypes = [ip, vp, vp, vp, ip, ip, C.POINTER(SvgfTonemapParams), vp, vp]
     lib.svgf_tonemap_srgb_table.argtypes = [C.POINTER(C.c_float)]
+    lib.svgf_quality_state_bytes.argtypes = [ip, ip]
+    lib.svgf_quality_state_bytes.restype = C.c_ulonglong
+    lib.svgf_quality_windows.argtypes = [ip, ip, C.POINTER(ip), C.POINTER(ip)]
+    lib.svgf_quality_meter.argtypes = [ip, vp, vp, vp, ip, ip, C.POINTER(SvgfQualityParams), vp, vp, vp, vp]
+    lib.svgf_quality_read.argtypes = [ip, vp, C.POINTER(SvgfQualityResult), vp]
     if path == LIB_PATH:
         _lib = lib
     return lib
@@ -671,6 +689,47 @@ def srgb_table() -> np.ndarray:
     if rc != SVGF_OK:
         raise SvgfError(f"svgf_tonemap_srgb_table failed ({rc})")
     return t
+
+
+# --- row f13: image-quality meter (MSE / PSNR, largest error, windowed SSIM of two device images) ----------------------------------
+def quality_windows(width: int, height: int):
+    """svgf_quality_windows: (nwx, nwy), the 8 x 8 windows at stride 4 that fit; (0, 0) below 8 pixels either way."""
+    nwx, nwy = C.c_int(), C.c_int()
+    rc = load_library().svgf_quality_windows(int(width), int(height), C.byref(nwx), C.byref(nwy))
+    if rc != SVGF_OK:
+        raise SvgfError(f"svgf_quality_windows failed ({rc})")
+    return nwx.value, nwy.value
+
+
+def quality_state(width: int, height: int, device: int = 0):
+    """The meter's state for a width x height comparison on `device`: svgf_quality_state_bytes bytes as an int64 tensor (the first
+    eight words are the result block), deliberately NOT zeroed: svgf_quality_meter rewrites everything it later reads."""
+    import torch
+    n = int(load_library().svgf_quality_state_bytes(int(width), int(height)))
+    if n == 0:
+        raise SvgfError(f"svgf_quality_state_bytes({width}, {height}) = 0: a size <= 0 or an unsupported one")
+    return torch.empty((n // 8,), dtype=torch.int64, device=f"cuda:{int(device)}")
+
+
+def quality_meter(state, a, b, width: int, height: int, peak: float = 1.0, scale: float = 1.0, clamp: int = 0, exposure_state=None,
+                  se_map=None, ssim_map=None, device: int = 0, stream=None):
+    """svgf_quality_meter: `a` (under test) against `b` (the reference), packed rgb float on the device, into `state`
+    (quality_state); `exposure_state` is f12's state (the effective scale is scale x its exposure); the maps are optional device
+    float32 outputs of height x width and quality_windows' nwy x nwx elements."""
+    qp = SvgfQualityParams(float(peak), float(scale), int(clamp))
+    rc = load_library().svgf_quality_meter(int(device), _ptr(state), _ptr(a), _ptr(b), int(width), int(height), C.byref(qp),
+                                           _ptr(exposure_state), _ptr(se_map), _ptr(ssim_map), _stream(stream))
+    if rc != SVGF_OK:
+        raise SvgfError(f"svgf_quality_meter failed ({rc})")
+
+
+def quality_read(state, device: int = 0, stream=None) -> dict:
+    """svgf_quality_read: waits for `stream` and returns the result block and mse / psnr_db / mean_ssim as a dict."""
+    r = SvgfQualityResult()
+    rc = load_library().svgf_quality_read(int(device), _ptr(state), C.byref(r), _stream(stream))
+    if rc != SVGF_OK:
+        raise SvgfError(f"svgf_quality_read failed ({rc})")
+    return {n: getattr(r, n) for n, _ in SvgfQualityResult._fields_}
 
 
 def save_png(path: str, rgb: np.ndarray, mirror_x: bool = True):

@@ -14,7 +14,7 @@ LIB = os.path.join(_HERE, "libsvgf_hip.so")
 # (svgf_exp_set).  Test / tools infrastructure: nothing on the product path loads it (binding.load_library(experiments=True) does).
 LIB_EXP = os.path.join(_HERE, "libsvgf_hip_exp.so")
 
-HIP_SOURCES = ["svgf_api.hip", "svgf_frame.hip", "svgf_pipeline.hip", "svgf_profiler.hip", "svgf_kernels.hip", "svgf_atrous_geometry.hip", "svgf_atrous_strip.hip", "svgf_atrous_lane.hip", "svgf_atrous_prepare_fused.hip", "svgf_atrous_lattice.hip", "svgf_synth.hip", "svgf_scene.hip", "svgf_display.hip", "svgf_upsample.hip", "svgf_transfer.hip"]
+HIP_SOURCES = ["svgf_api.hip", "svgf_frame.hip", "svgf_pipeline.hip", "svgf_profiler.hip", "svgf_kernels.hip", "svgf_atrous_geometry.hip", "svgf_atrous_strip.hip", "svgf_atrous_lane.hip", "svgf_atrous_prepare_fused.hip", "svgf_atrous_lattice.hip", "svgf_synth.hip", "svgf_scene.hip", "svgf_display.hip", "svgf_upsample.hip", "svgf_transfer.hip", "svgf_quality.hip"]
 HIP_SOURCES_EXPERIMENTS = ["svgf_experiments.hip", "svgf_atrous_lane_reuse.hip", "svgf_atrous_fused.hip"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unused-function"]
 # Per-file flags.  svgf_atrous_fused.hip: SimplifyCFG's common-code sinking merges the last store of the "bilinear history" branch
@@ -76,11 +76,13 @@ def build_examples(force: bool = False) -> str:
     """examples/farm.cpp (N contexts on N GPUs from one C++ process), examples/pipeline.cpp (a renderer's frame loop on the frame
     pipeline), examples/cadence.cpp (a fixed-rate loop + the effective shader clock), examples/upsample.cpp (denoise at a reduced
     size, svgf_upsample to the full size), examples/dynres.cpp (the reduced size changes every few frames,
-    svgf_transfer_history carries the sequence along) and examples/hdr_display.cpp (an emitter far above 1: svgf_exposure_meter on
-    the denoised image, svgf_display_tonemap beside the plain pack), through the C ABI -> examples/farm, examples/pipeline,
-    examples/cadence, examples/upsample, examples/dynres, examples/hdr_display, linked against the product library in-tree."""
+    svgf_transfer_history carries the sequence along), examples/hdr_display.cpp (an emitter far above 1: svgf_exposure_meter on
+    the denoised image, svgf_display_tonemap beside the plain pack) and examples/quality.cpp (svgf_quality_meter: PSNR / SSIM of the
+    noisy and the denoised frame against the clean one, and of consecutive outputs), through the C ABI -> examples/farm,
+    examples/pipeline, examples/cadence, examples/upsample, examples/dynres, examples/hdr_display, examples/quality, linked against the
+    product library in-tree."""
     out = ""
-    for name in ("pipeline", "farm", "cadence", "upsample", "dynres", "hdr_display"):
+    for name in ("pipeline", "farm", "cadence", "upsample", "dynres", "hdr_display", "quality"):
         src = os.path.join(ROOT, "examples", name + ".cpp")
         out = os.path.join(ROOT, "examples", name)
         if not force and _newer(out, [src, os.path.join(ROOT, "include", "svgf.h"), LIB]):

@@ -685,6 +685,66 @@ int svgf_display_tonemap(int device, void *pbo_rgba8_dev, const void *left_rgb_d
                          int width, int height, const SvgfTonemapParams *tp, const void *state_dev, void *stream);
 int svgf_tonemap_srgb_table(float thresholds[256]);      /* host only: the table transfer 2 uses */
 
+/* ---- "next" row f13: image-quality meter - MSE / PSNR, largest error, windowed SSIM of two device images (added after 0.9; probe the symbol) ----
+ * svgf_quality_meter compares two packed-rgb DEVICE images, `a` the image under test and `b` the reference (width x height pixels,
+ * 4-byte aligned), and leaves the totals in device memory.  It is stateless, asynchronous on `stream`, allocates nothing and takes
+ * two launches (a tile kernel and a one-workgroup resolve); it changes nothing a frame enqueues.
+ * state_dev: svgf_quality_state_bytes(width, height) bytes of DEVICE memory the caller owns, 8-byte aligned.  It needs NO
+ *   initialisation: a call rewrites everything it later reads.  The first 64 bytes are the result block, eight 8-byte words:
+ *     [0] n_pixels (integer)  [1] n_windows (integer)  [2] sum_se  [3] sum_ssim  [4] max_abs  [5] min_ssim  [6] (double)peak
+ *     [7] (double)e                                                                                     ([2]..[7] are doubles)
+ *   the rest is the kernels' scratch (six 8-byte words per 64 x 32-pixel tile).
+ * exposure_state_dev: NULL, or f12's 520-word state; then e = scale * as_float(word[516]) in float32, multiplied on the device as
+ *   svgf_display_tonemap does.  NULL: e = scale.
+ * se_map_dev (width x height floats) and ssim_map_dev (nwx x nwy floats, svgf_quality_windows) are optional outputs, 4-byte aligned.
+ * Normative arithmetic - every float is a defined input; float32 where stated, DOUBLE elsewhere, nothing contracted.
+ * Per pixel:
+ *   for each of the six channel values v: t = v * e in float32.  The pixel is COUNTED iff all six t are finite.
+ *   if clamp: if (t < 0) t = 0; if (t > peak) t = peak
+ *   d_c = (double)ta_c - (double)tb_c;  se = (d_r d_r + d_g d_g) + d_b d_b
+ *   La, Lb = the library's luminance of the transformed channels, (float)((0.2126 (double)r + 0.7152 (double)g) + 0.0722 (double)b)
+ *   over counted pixels: n_pixels; sum_se = sum of se; max_abs = max |d_c| (0 when no pixel is counted)
+ *   se_map[p] = (float)se; the bit pattern 0x7FC00000 for a pixel that is not counted
+ * Windows: 8 x 8 at stride 4 (x264's layout), origins (4 i, 4 j), i < nwx, j < nwy, n = (d >= 8) ? (d - 8) / 4 + 1 : 0.  Pixels right
+ *   of or below the last window belong to no window (they still count for the error).  A window is counted iff all 64 of its pixels
+ *   are.  It is built from four 4 x 4 CELLS.  A cell's five sums, in double: La, Lb, La La, Lb Lb, La Lb (products of the floats
+ *   widened to double); a row of a cell is ((v0 + v1) + v2) + v3, the cell ((r0 + r1) + r2) + r3; the window ((c00 + c10) + c01) + c11
+ *   with cells c[x][y].  Then
+ *     k = 0.015625;  ma = sa k;  mb = sb k;  va = saa k - ma ma;  vb = sbb k - mb mb;  cv = sab k - ma mb
+ *     C1 = (0.01 (double)peak)^2;  C2 = (0.03 (double)peak)^2
+ *     ssim = ((2.0 ma mb + C1) (2.0 cv + C2)) / (((ma ma + mb mb) + C1) ((va + vb) + C2))
+ *   over counted windows: n_windows; sum_ssim; min_ssim (+inf when no window is counted)
+ *   ssim_map[i + j nwx] = (float)ssim; the bit pattern 0x7FC00000 for a window that is not counted
+ *   In double the form gives exactly 1.0 for a == b and is exactly symmetric in (a, b); in float32 the cancellation in
+ *   saa / 64 - ma ma costs up to 2.6e-4 of a window's value on near-flat bright images - which is what a denoised image is.
+ * The two sums: workgroups write per-tile partials into the state and the resolve adds them in index order (contiguous runs of
+ *   tiles, then the runs); the order is fixed and no floating-point atomic is used, so two calls on the same inputs leave the same
+ *   64 bytes.  Against the exact sum of the per-pixel / per-window doubles above, a sum of n terms differs by at most
+ *   n 2^-52 sum |term| (any order of n - 1 double additions errs by at most (n - 1) 2^-53 sum |term| to first order; the bound
+ *   doubles that).  Everything else in the block is exact: the counts, the max, the min.
+ * svgf_quality_read copies the block on `stream`, waits for that stream only, and fills the HOST struct:
+ *   mse = sum_se / (3.0 n_pixels);  psnr_db = 10 log10(peak^2 / mse), +inf for mse == 0;  mean_ssim = sum_ssim / n_windows;
+ *   NaN where n_pixels == 0 (mse, psnr_db) or n_windows == 0 (mean_ssim).
+ * SVGF_ERR_INVALID_ARG, answered before any device work: a NULL state_dev, a_rgb_dev, b_rgb_dev, qp or out_host; a size <= 0; peak
+ * or scale that is not finite and > 0; clamp other than 0 or 1.  SVGF_ERR_UNSUPPORTED: width * height >= 2^31 / 16;
+ * svgf_quality_state_bytes returns 0 for those sizes and for a size <= 0.  INTEGRATION.md 6b says what to compare with what. */
+typedef struct SvgfQualityParams {               /* 12 bytes */
+    float peak;             /* the signal's white: PSNR's peak, SSIM's dynamic range L; finite, > 0 */
+    float scale;            /* multiplies every channel of both images first (an exposure); finite, > 0 */
+    int   clamp;            /* 1: channels clamped to [0, peak] after scaling (display-referred metric); 0: as they are */
+} SvgfQualityParams;
+typedef struct SvgfQualityResult {               /* 88 bytes, HOST */
+    unsigned long long n_pixels, n_windows;
+    double sum_se, sum_ssim, max_abs, min_ssim, peak, scale;      /* the eight device words; scale is e, the effective one */
+    double mse, psnr_db, mean_ssim;                                /* formed by svgf_quality_read on the host */
+} SvgfQualityResult;
+unsigned long long svgf_quality_state_bytes(int width, int height);      /* host; a multiple of 8, >= 64; 0 for a size <= 0 or an unsupported one */
+int svgf_quality_windows(int width, int height, int *nwx, int *nwy);     /* host; either pointer may be NULL; SVGF_ERR_INVALID_ARG for a size <= 0 */
+int svgf_quality_meter(int device, void *state_dev, const void *a_rgb_dev, const void *b_rgb_dev, int width, int height,
+                       const SvgfQualityParams *qp, const void *exposure_state_dev, float *se_map_dev, float *ssim_map_dev,
+                       void *stream);
+int svgf_quality_read (int device, const void *state_dev, SvgfQualityResult *out_host, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
