@@ -14,4 +14,5 @@ from .binding import Denoiser, SvgfCamera, SvgfParams, SvgfError, load_library, 
 from .binding import SvgfGuide, SvgfUpsampleParams, upsample  # noqa: F401
 from .binding import SvgfExposureParams, SvgfTonemapParams, exposure_state, exposure_reset, exposure_meter, display_tonemap, srgb_table  # noqa: F401
 from .binding import SvgfQualityParams, SvgfQualityResult, quality_state, quality_windows, quality_meter, quality_read  # noqa: F401
+from .binding import Scene, SvgfSceneBuildParams, SvgfSceneInfo, bvh_build_host  # noqa: F401
 from .binding import STATE_PREV_NORMAL, STATE_PREV_POSITION, STATE_PREV_GEOM_ID, STATE_OUTPUT_HISTORY  # noqa: F401

@@ -42,7 +42,9 @@ EXPORTS = ["svgf_version", "svgf_params_default", "svgf_create", "svgf_destroy",
            "svgf_set_firefly_filter", "svgf_get_firefly_filter", "svgf_set_output_taa", "svgf_get_output_taa",
            "svgf_upsample", "svgf_transfer_history",
            "svgf_exposure_reset", "svgf_exposure_meter", "svgf_display_tonemap", "svgf_tonemap_srgb_table",
-           "svgf_quality_state_bytes", "svgf_quality_windows", "svgf_quality_meter", "svgf_quality_read"]
+           "svgf_quality_state_bytes", "svgf_quality_windows", "svgf_quality_meter", "svgf_quality_read",
+           "svgf_scene_create", "svgf_scene_destroy", "svgf_scene_info", "svgf_scene_draw", "svgf_scene_draw_planar", "svgf_bvh_build_host"]
+SCENE_MAX_DEPTH = 48
 CREATE_PIPELINED = 1
 EXPOSURE_STATE_WORDS = 520
 # SvgfTonemapParams.op / .transfer
@@ -118,6 +120,20 @@ class SvgfQualityResult(C.Structure):
     _fields_ = [("n_pixels", C.c_ulonglong), ("n_windows", C.c_ulonglong), ("sum_se", C.c_double), ("sum_ssim", C.c_double),
                 ("max_abs", C.c_double), ("min_ssim", C.c_double), ("peak", C.c_double), ("scale", C.c_double),
                 ("mse", C.c_double), ("psnr_db", C.c_double), ("mean_ssim", C.c_double)]
+
+
+class SvgfSceneBuildParams(C.Structure):
+    """svgf_scene_create / svgf_bvh_build_host: max_leaf_tris 1..8 (0 = 4); split 0 = binned SAH, 1 = equal counts."""
+    _fields_ = [("max_leaf_tris", C.c_int), ("split", C.c_int)]
+
+
+class SvgfSceneInfo(C.Structure):
+    _fields_ = [("n_geoms", C.c_int), ("n_tris", C.c_int), ("n_tex", C.c_int), ("n_nodes", C.c_int), ("n_leaves", C.c_int),
+                ("depth", C.c_int), ("max_leaf_tris", C.c_int), ("device_bytes", C.c_ulonglong)]
+
+
+# SvgfBvhNode, 32 bytes: count > 0 a leaf over order[first : first + count], count == 0 an inner node with children first, first + 1
+BVH_NODE_DTYPE = np.dtype([("lo", np.float32, 3), ("first", np.int32), ("hi", np.float32, 3), ("count", np.int32)])
 
 
 class SvgfSynthParams(C.Structure):
@@ -268,6 +284,13 @@ def load_library(path: str | None = None, experiments: bool = False):
     lib.svgf_quality_windows.argtypes = [ip, ip, C.POINTER(ip), C.POINTER(ip)]
     lib.svgf_quality_meter.argtypes = [ip, vp, vp, vp, ip, ip, C.POINTER(SvgfQualityParams), vp, vp, vp, vp]
     lib.svgf_quality_read.argtypes = [ip, vp, C.POINTER(SvgfQualityResult), vp]
+    lib.svgf_scene_create.argtypes = [ip, vp, ip, vp, vp, vp, vp, ip, vp, vp, vp, ip, C.POINTER(SvgfSceneBuildParams), C.POINTER(vp)]
+    lib.svgf_scene_destroy.argtypes = [vp]
+    lib.svgf_scene_info.argtypes = [vp, C.POINTER(SvgfSceneInfo)]
+    lib.svgf_scene_draw.argtypes = [vp, vp, vp, ip, ip, C.POINTER(SvgfCamera), C.POINTER(SvgfSynthParams), C.POINTER(C.c_float), vp]
+    lib.svgf_scene_draw_planar.argtypes = [vp, vp, C.POINTER(SvgfPlanarGBuffer), ip, ip, C.POINTER(SvgfCamera), C.POINTER(SvgfSynthParams),
+                                           C.POINTER(C.c_float), vp]
+    lib.svgf_bvh_build_host.argtypes = [vp, ip, C.POINTER(SvgfSceneBuildParams), vp, C.POINTER(ip), vp, C.POINTER(ip)]
     if path == LIB_PATH:
         _lib = lib
     return lib
@@ -815,3 +838,92 @@ def scene_render_mesh(out_rgb, out_gbuffer, width: int, height: int, camera, geo
     if stream is None:
         import torch
         torch.cuda.synchronize(int(device))
+
+
+# --- row f14: resident scene (upload once, BVH over the triangles, one launch per frame) ------------------------------------------
+def _scene_arrays(geoms, geom_ids, tris, tri_ids, tri_albedo, tri_tex, textures):
+    """The host arrays svgf_scene_render_mesh / svgf_scene_create take, as (arrays to keep alive, ctypes arguments)."""
+    from . import scene as _scene
+    geoms = np.zeros(0, _scene.SCENE_GEOM_DTYPE) if geoms is None else np.ascontiguousarray(geoms, dtype=_scene.SCENE_GEOM_DTYPE)
+    gi = np.ascontiguousarray(geom_ids if geom_ids is not None else np.zeros(0, np.int32), dtype=np.int32)
+    tr = np.ascontiguousarray(tris if tris is not None else np.zeros((0, 24), np.float32), dtype=np.float32).reshape(-1, 24)
+    ti = np.ascontiguousarray(tri_ids if tri_ids is not None else np.zeros(0, np.int32), dtype=np.int32)
+    ta = np.ascontiguousarray(tri_albedo if tri_albedo is not None else np.zeros((0, 3), np.float32), dtype=np.float32).reshape(-1, 3)
+    n_tex, tt, td, tx = 0, None, None, None
+    if textures is not None and len(textures) and tri_tex is not None:      # list of uint8[h, w, 3]; tri_tex: index per triangle, -1 = none
+        n_tex = len(textures)
+        tt = np.ascontiguousarray(tri_tex, dtype=np.int32)
+        blobs = [np.ascontiguousarray(t, dtype=np.uint8) for t in textures]
+        offs = np.cumsum([0] + [b.size for b in blobs[:-1]])
+        td = np.array([[o, b.shape[1], b.shape[0]] for o, b in zip(offs, blobs)], dtype=np.int32)
+        tx = np.concatenate([b.reshape(-1) for b in blobs])
+    ptr = lambda a, on=True: a.ctypes.data if (a is not None and on and a.size) else None       # noqa: E731
+    args = (ptr(geoms), int(len(geoms)), ptr(gi), ptr(tr), ptr(ti), ptr(ta), int(len(tr)), ptr(tt, n_tex), ptr(td, n_tex), ptr(tx, n_tex), int(n_tex))
+    return (geoms, gi, tr, ti, ta, tt, td, tx), args
+
+
+def bvh_build_host(tris, max_leaf_tris: int = 0, split: int = 0):
+    """svgf_bvh_build_host (no device needed): (nodes BVH_NODE_DTYPE[n_nodes], order int32[n_tris], depth) of `tris`
+    (float32[n, 3, 8] or [n, 24])."""
+    tr = np.ascontiguousarray(tris, dtype=np.float32).reshape(-1, 24)
+    n = len(tr)
+    nodes, order = np.zeros(2 * max(n, 1), BVH_NODE_DTYPE), np.zeros(max(n, 1), np.int32)
+    n_nodes, depth = C.c_int(-1), C.c_int(-1)
+    bp = SvgfSceneBuildParams(int(max_leaf_tris), int(split))
+    rc = load_library().svgf_bvh_build_host(tr.ctypes.data if n else None, n, C.byref(bp), nodes.ctypes.data, C.byref(n_nodes),
+                                            order.ctypes.data, C.byref(depth))
+    if rc != SVGF_OK:
+        raise SvgfError(f"svgf_bvh_build_host failed ({rc})")
+    return nodes[:n_nodes.value].copy(), order[:n].copy(), depth.value
+
+
+class Scene:
+    """A resident scene: svgf_scene_create once (validates, builds the BVH, uploads; allocates and synchronises), then draw() /
+    draw_planar() per frame - one launch each on `stream`, nothing else.  Static: camera, light and noise change per draw."""
+
+    def __init__(self, handle, device):
+        self.lib, self.h, self.device = load_library(), handle, int(device)
+
+    @classmethod
+    def create(cls, geoms, geom_ids, tris, tri_ids, tri_albedo, tri_tex=None, textures=None, max_leaf_tris: int = 0, split: int = 0,
+               device: int = 0):
+        _keep, args = _scene_arrays(geoms, geom_ids, tris, tri_ids, tri_albedo, tri_tex, textures)
+        h = C.c_void_p()
+        bp = SvgfSceneBuildParams(int(max_leaf_tris), int(split))
+        rc = load_library().svgf_scene_create(int(device), *args, C.byref(bp), C.byref(h))
+        if rc != SVGF_OK:
+            raise SvgfError(f"svgf_scene_create failed ({rc})")
+        return cls(h, device)
+
+    def info(self) -> dict:
+        i = SvgfSceneInfo()
+        rc = self.lib.svgf_scene_info(self.h, C.byref(i))
+        if rc != SVGF_OK:
+            raise SvgfError(f"svgf_scene_info failed ({rc})")
+        return {k: int(getattr(i, k)) for k, _ in SvgfSceneInfo._fields_}
+
+    def draw(self, out_rgb, out_gbuffer, width: int, height: int, camera, light, frame: int, seed: int = 1, noise: float = 0.6,
+             fireflies: float = 0.02, pixel_length=None, stream=None):
+        """svgf_scene_draw, or svgf_scene_draw_planar when `out_gbuffer` is a SvgfPlanarGBuffer.  Asynchronous on `stream` (a torch
+        stream, a raw handle or None = the default stream); never waits."""
+        from . import synth as _synth
+        cam = camera if isinstance(camera, SvgfCamera) else SvgfCamera.from_dict(camera)
+        if pixel_length is None:
+            fovy = camera.get("fovy_deg", 45.0) if isinstance(camera, dict) else 45.0
+            pixel_length = _synth._pixel_length(width, height, fovy)
+        sp = SvgfSynthParams(int(frame), int(seed), float(noise), float(fireflies))
+        sp.pixel_length[0], sp.pixel_length[1] = float(pixel_length[0]), float(pixel_length[1])
+        larr = (C.c_float * 3)(float(light[0]), float(light[1]), float(light[2]))
+        planar = isinstance(out_gbuffer, SvgfPlanarGBuffer)
+        fn = self.lib.svgf_scene_draw_planar if planar else self.lib.svgf_scene_draw
+        rc = fn(self.h, _ptr(out_rgb), C.byref(out_gbuffer) if planar else _ptr(out_gbuffer), int(width), int(height), C.byref(cam),
+                C.byref(sp), larr, _stream(stream))
+        if rc != SVGF_OK:
+            raise SvgfError(f"svgf_scene_draw failed ({rc})")
+
+    draw_planar = draw
+
+    def free(self):
+        if self.h:
+            self.lib.svgf_scene_destroy(self.h)
+            self.h = None

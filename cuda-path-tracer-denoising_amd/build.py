@@ -14,7 +14,10 @@ LIB = os.path.join(_HERE, "libsvgf_hip.so")
 # (svgf_exp_set).  Test / tools infrastructure: nothing on the product path loads it (binding.load_library(experiments=True) does).
 LIB_EXP = os.path.join(_HERE, "libsvgf_hip_exp.so")
 
-HIP_SOURCES = ["svgf_api.hip", "svgf_frame.hip", "svgf_pipeline.hip", "svgf_profiler.hip", "svgf_kernels.hip", "svgf_atrous_geometry.hip", "svgf_atrous_strip.hip", "svgf_atrous_lane.hip", "svgf_atrous_prepare_fused.hip", "svgf_atrous_lattice.hip", "svgf_synth.hip", "svgf_scene.hip", "svgf_display.hip", "svgf_upsample.hip", "svgf_transfer.hip", "svgf_quality.hip"]
+HIP_SOURCES = ["svgf_api.hip", "svgf_frame.hip", "svgf_pipeline.hip", "svgf_profiler.hip", "svgf_kernels.hip", "svgf_atrous_geometry.hip", "svgf_atrous_strip.hip", "svgf_atrous_lane.hip", "svgf_atrous_prepare_fused.hip", "svgf_atrous_lattice.hip", "svgf_synth.hip", "svgf_scene.hip", "svgf_display.hip", "svgf_upsample.hip", "svgf_transfer.hip", "svgf_quality.hip", "svgf_scene_bvh.hip"]
+# plain C++ (no HIP in them; compiled as C++, for the host only): the resident scene's BVH builder
+CXX_SOURCES = ["svgf_bvh_build.cpp"]
+CXX_FLAGS = ["-x", "c++", "-O3", "-std=c++17", "-fPIC", "-Wall", "-ffp-contract=off"]
 HIP_SOURCES_EXPERIMENTS = ["svgf_experiments.hip", "svgf_atrous_lane_reuse.hip", "svgf_atrous_fused.hip"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unused-function"]
 # Per-file flags.  svgf_atrous_fused.hip: SimplifyCFG's common-code sinking merges the last store of the "bilinear history" branch
@@ -49,7 +52,7 @@ def build_hip(force: bool = False, experiments: bool = False) -> str:
     experiments=True, into libsvgf_hip_exp.so (-DSVGF_BUILD_EXPERIMENTS: parked kernel variants 5 / 6, cross-level term reuse, the
     tuning table behind svgf_exp_set; what tools/experiments/ and the tests marked `experiments` load)."""
     LIB = LIB_EXP if experiments else globals()["LIB"]
-    srcs = [os.path.join(CSRC, s) for s in HIP_SOURCES + (HIP_SOURCES_EXPERIMENTS if experiments else [])]
+    srcs = [os.path.join(CSRC, s) for s in HIP_SOURCES + (HIP_SOURCES_EXPERIMENTS if experiments else []) + CXX_SOURCES]
     deps = srcs + [os.path.join(CSRC, h) for h in sorted(os.listdir(CSRC)) if h.endswith(".h")] + [os.path.join(ROOT, "include", "svgf.h")]
     if not force and _newer(LIB, deps):
         return LIB
@@ -65,7 +68,8 @@ def build_hip(force: bool = False, experiments: bool = False) -> str:
     with tempfile.TemporaryDirectory(prefix="svgf_build_") as scratch:
         objs = [os.path.join(scratch, os.path.basename(x) + ".o") for x in srcs]
         with concurrent.futures.ThreadPoolExecutor(max_workers=min(len(srcs), os.cpu_count() or 1)) as pool:
-            list(pool.map(lambda so: _run([hipcc_path()] + cflags + HIPCC_FILE_FLAGS.get(os.path.basename(so[0]), []) + extra + ["-c", so[0], "-o", so[1]]),
+            list(pool.map(lambda so: _run([hipcc_path()] + (CXX_FLAGS if os.path.basename(so[0]) in CXX_SOURCES else
+                                                            cflags + HIPCC_FILE_FLAGS.get(os.path.basename(so[0]), []) + extra) + ["-c", so[0], "-o", so[1]]),
                           zip(srcs, objs)))
         _run([hipcc_path(), "--offload-arch=gfx950", "-shared", "-fPIC"] + objs + ["-o", tmp])
     os.replace(tmp, LIB)              # atomic: concurrent ranks never see a half-written library
@@ -78,11 +82,12 @@ def build_examples(force: bool = False) -> str:
     size, svgf_upsample to the full size), examples/dynres.cpp (the reduced size changes every few frames,
     svgf_transfer_history carries the sequence along), examples/hdr_display.cpp (an emitter far above 1: svgf_exposure_meter on
     the denoised image, svgf_display_tonemap beside the plain pack) and examples/quality.cpp (svgf_quality_meter: PSNR / SSIM of the
-    noisy and the denoised frame against the clean one, and of consecutive outputs), through the C ABI -> examples/farm,
-    examples/pipeline, examples/cadence, examples/upsample, examples/dynres, examples/hdr_display, examples/quality, linked against the
-    product library in-tree."""
+    noisy and the denoised frame against the clean one, and of consecutive outputs) and examples/resident_scene.cpp (svgf_scene_create
+    once, then svgf_scene_draw + svgf_denoise per frame), through the C ABI -> examples/farm, examples/pipeline, examples/cadence,
+    examples/upsample, examples/dynres, examples/hdr_display, examples/quality, examples/resident_scene, linked against the product
+    library in-tree."""
     out = ""
-    for name in ("pipeline", "farm", "cadence", "upsample", "dynres", "hdr_display", "quality"):
+    for name in ("pipeline", "farm", "cadence", "upsample", "dynres", "hdr_display", "quality", "resident_scene"):
         src = os.path.join(ROOT, "examples", name + ".cpp")
         out = os.path.join(ROOT, "examples", name)
         if not force and _newer(out, [src, os.path.join(ROOT, "include", "svgf.h"), LIB]):

@@ -352,7 +352,7 @@ int svgf_scene_render(int device, void *out_rgb_dev, void *out_gbuffer_dev, int 
                       const SvgfCamera *cam, const SvgfSynthParams *sp, const SvgfSceneGeom *geoms, int n_geoms,
                       const float light[3], void *stream);
 /* The same with the scene's triangle meshes (Scene::loadMesh's world-space triangles, src/scene.cpp:234-311; host arrays, read
- * completely before the call returns like `geoms`; every triangle is tested for every pixel — no BVH, the reference's
+ * completely before the call returns like `geoms`; every triangle is tested for every pixel — no BVH here (row f14 below has one), the reference's
  * scenes have 38 .. 4 968 triangles — so n_tris x width x height is what a call costs): `tris` = n_tris x 3 vertices x {pos[3], normal[3], uv[2]}, `tri_ids` = the object index written as
  * geomId for each triangle, `tri_albedo` = n_tris x rgb (the mesh's material colour), `geom_ids` = the object index written
  * as geomId for each primitive (NULL: its position in `geoms`).  Textures (n_tex may be 0): `tex_data` = 8-bit RGB images, rows
@@ -744,6 +744,69 @@ int svgf_quality_meter(int device, void *state_dev, const void *a_rgb_dev, const
                        const SvgfQualityParams *qp, const void *exposure_state_dev, float *se_map_dev, float *ssim_map_dev,
                        void *stream);
 int svgf_quality_read (int device, const void *state_dev, SvgfQualityResult *out_host, void *stream);
+
+/* ---- "next" row f14: resident scene - upload once, BVH over the triangles, draw per frame (added after 0.9; probe the symbol) ----
+ * svgf_scene_render_mesh uploads the whole scene, waits for that upload and tests every triangle for every pixel on EVERY call.
+ * A resident scene is the same scene kept on the device with a bounding-volume hierarchy over its triangles: svgf_scene_create
+ * validates, builds and uploads once; svgf_scene_draw / svgf_scene_draw_planar are exactly one launch on `stream` - no allocation,
+ * no upload, no host synchronisation, legal under stream capture.  Resident scenes are STATIC: what moves from frame to frame is
+ * the camera, the light and SvgfSynthParams; primitives or triangles that move stay with svgf_scene_render_mesh.
+ * svgf_scene_create: the scene arguments are svgf_scene_render_mesh's (host arrays, read completely before it returns), with the
+ *   same validation and error codes, and in addition SVGF_ERR_INVALID_ARG for a vertex POSITION that is not finite (normals and uvs
+ *   may be anything), for bp->max_leaf_tris outside 0..8, bp->split outside 0..1 and a NULL `out`; device outside 0..63:
+ *   SVGF_ERR_UNSUPPORTED.  All of that is answered before any device work.  One device allocation holds the scene's arrays, the
+ *   nodes, the triangle order and the padded triangle boxes.  It allocates and synchronises: not under capture.
+ * svgf_scene_destroy waits for the device first (draws in flight read the allocation); NULL is accepted.
+ * svgf_scene_draw*: SVGF_ERR_INVALID_ARG for a NULL scene, output, cam, sp or light, a planar target without normal, position and
+ *   geom_id, a size <= 0; SVGF_ERR_UNSUPPORTED for width * height >= 2^31 / 16; all before any device work.
+ * Normative semantics - a GATED brute force; every tree gives the same frame.  float32, one rounding per operation, no contraction:
+ *   Padded box of triangle i, computed once on the host and stored (the device never recomputes it).  Per axis c:
+ *     mn = min(min(v0, v1), v2), mx likewise;  ext = max over c of (mx_c - mn_c)
+ *     pad_c = (ext * 2^-8) + (2^-16 * max(1, |mn_c|, |mx_c|));  lo_c = mn_c - pad_c;  hi_c = mx_c + pad_c
+ *   Slab test S(box, ray) -> (pass, tn), ray origin o and direction d:  tn = 0, tf = +inf; per axis c:
+ *     if fabsf(d_c) < 2^-100: the axis passes iff lo_c <= o_c <= hi_c, and leaves the interval alone;
+ *     otherwise inv = 1.0f / d_c; t1 = (lo_c - o_c) * inv; t2 = (hi_c - o_c) * inv; tn = max(tn, min(t1, t2)); tf = min(tf, max(t1, t2))
+ *     pass = every axis passes && tn <= tf.  No NaN arises from finite inputs.
+ *   Triangle i COUNTS for a ray iff svgf_scene_render_mesh's own intersection arithmetic gives a t > 0, S(padded box i) passes, and
+ *     t >= tn_i.  Among the counting triangles with t below the primitives' nearest hit the smallest t wins; equal t: the lowest
+ *     index; a primitive keeps a tie with a triangle.  Everything else - primitives, corner weights, textures, shading, noise, the
+ *     stores - is svgf_scene_render_mesh's, the same device code.
+ *   A node's box is the exact union (min / max, no arithmetic) of the stored padded boxes below it; a node is skipped iff S(node)
+ *     fails or tn_node > the nearest t so far.  Subtraction, multiplication by an `inv` of fixed sign, min and max are monotone, so a
+ *     larger box never has a larger tn nor fails where a smaller one passes: skipping is exact and the visiting order is free.
+ *   Wherever the winner of svgf_scene_render_mesh's ungated loop passes its own gate - every pixel of every scene the tests hold,
+ *   the reference's recorded scenes included - the frame equals svgf_scene_render_mesh's bit for bit.  The gate exists because the
+ *   float32 intersection test accepts, at grazing incidence, hits that lie off the triangle, which no box can promise to keep.
+ * Builder: binned SAH over the centroids (split 0) or equal counts along the widest centroid axis (split 1); a split that is
+ *   degenerate, or whose sides would not fit the depth left, is replaced by equal counts by position in the list.  For every input up
+ *   to SVGF_SCENE_MAX_TRIS: depth <= SVGF_SCENE_MAX_DEPTH (root = 0), every leaf holds 1..max_leaf_tris triangles, n_nodes =
+ *   2 * n_leaves - 1, and the same input gives the same nodes.  n_tris == 0: n_nodes = 0, and a draw skips the triangle part.
+ * INTEGRATION.md 5h has the frame loop and what it costs, examples/resident_scene.cpp runs it. */
+typedef struct svgf_scene svgf_scene;
+typedef struct SvgfSceneBuildParams {
+    int max_leaf_tris;       /* 1..8, 0 = default 4 */
+    int split;               /* 0 binned SAH, 1 equal counts on the widest centroid axis */
+} SvgfSceneBuildParams;
+typedef struct SvgfSceneInfo {
+    int n_geoms, n_tris, n_tex, n_nodes, n_leaves, depth, max_leaf_tris;
+    unsigned long long device_bytes;
+} SvgfSceneInfo;
+#define SVGF_SCENE_MAX_DEPTH 48
+int svgf_scene_create(int device, const SvgfSceneGeom *geoms, int n_geoms, const int *geom_ids, const float *tris, const int *tri_ids,
+                      const float *tri_albedo, int n_tris, const int *tri_tex, const int *tex_desc, const unsigned char *tex_data,
+                      int n_tex, const SvgfSceneBuildParams *bp /* NULL = defaults */, svgf_scene **out);
+int svgf_scene_destroy(svgf_scene *scene);
+int svgf_scene_info(const svgf_scene *scene, SvgfSceneInfo *out);
+int svgf_scene_draw(const svgf_scene *scene, void *out_rgb_dev, void *out_gbuffer_dev, int width, int height,
+                    const SvgfCamera *cam, const SvgfSynthParams *sp, const float light[3], void *stream);
+int svgf_scene_draw_planar(const svgf_scene *scene, void *out_rgb_dev, const SvgfPlanarGBuffer *planes, int width, int height,
+                           const SvgfCamera *cam, const SvgfSynthParams *sp, const float light[3], void *stream);
+/* The builder by itself: host only, no device needed.  count > 0: a leaf over triangles order[first .. first + count);
+ * count == 0: an inner node with children first and first + 1; node 0 is the root.  `tris` as svgf_scene_render_mesh takes them
+ * (24 floats per triangle; positions must be finite); `nodes` has room for 2 * max(n_tris, 1), `order` for n_tris. */
+typedef struct SvgfBvhNode { float lo[3]; int first; float hi[3]; int count; } SvgfBvhNode;   /* 32 bytes */
+int svgf_bvh_build_host(const float *tris, int n_tris, const SvgfSceneBuildParams *bp, SvgfBvhNode *nodes, int *n_nodes,
+                        int *order, int *depth);
 
 #ifdef __cplusplus
 }
