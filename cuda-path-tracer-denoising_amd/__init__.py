@@ -15,4 +15,5 @@ from .binding import SvgfGuide, SvgfUpsampleParams, upsample  # noqa: F401
 from .binding import SvgfExposureParams, SvgfTonemapParams, exposure_state, exposure_reset, exposure_meter, display_tonemap, srgb_table  # noqa: F401
 from .binding import SvgfQualityParams, SvgfQualityResult, quality_state, quality_windows, quality_meter, quality_read  # noqa: F401
 from .binding import Scene, SvgfSceneBuildParams, SvgfSceneInfo, bvh_build_host  # noqa: F401
+from .binding import ResidentScene, SCENE_POSE_DTYPE, pose_rigid, pose_identity, bvh_refit_plan_host  # noqa: F401
 from .binding import STATE_PREV_NORMAL, STATE_PREV_POSITION, STATE_PREV_GEOM_ID, STATE_OUTPUT_HISTORY  # noqa: F401

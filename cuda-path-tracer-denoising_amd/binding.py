@@ -43,8 +43,16 @@ EXPORTS = ["svgf_version", "svgf_params_default", "svgf_create", "svgf_destroy",
            "svgf_upsample", "svgf_transfer_history",
            "svgf_exposure_reset", "svgf_exposure_meter", "svgf_display_tonemap", "svgf_tonemap_srgb_table",
            "svgf_quality_state_bytes", "svgf_quality_windows", "svgf_quality_meter", "svgf_quality_read",
-           "svgf_scene_create", "svgf_scene_destroy", "svgf_scene_info", "svgf_scene_draw", "svgf_scene_draw_planar", "svgf_bvh_build_host"]
+           "svgf_scene_create", "svgf_scene_destroy", "svgf_scene_info", "svgf_scene_draw", "svgf_scene_draw_planar", "svgf_bvh_build_host",
+           "svgf_scene_enable_pose", "svgf_scene_pose", "svgf_scene_read", "svgf_pose_rigid", "svgf_bvh_refit_plan_host"]
 SCENE_MAX_DEPTH = 48
+SCENE_MAX_POSED = 1024
+SCENE_REFIT_CAP = 1024
+# svgf_scene_read kinds
+SCENE_READ_TRIS, SCENE_READ_TRI_BOXES, SCENE_READ_NODES, SCENE_READ_GEOMS, SCENE_READ_ORDER, SCENE_READ_HELD_POSE = 0, 1, 2, 3, 4, 5
+# SvgfScenePose / SvgfRefitTreelet (row f15)
+SCENE_POSE_DTYPE = np.dtype([("xf", np.float32, (12,)), ("inv", np.float32, (12,))])
+REFIT_TREELET_DTYPE = np.dtype([("root", np.int32), ("begin", np.int32), ("count", np.int32), ("levels", np.int32)])
 CREATE_PIPELINED = 1
 EXPOSURE_STATE_WORDS = 520
 # SvgfTonemapParams.op / .transfer
@@ -291,6 +299,11 @@ def load_library(path: str | None = None, experiments: bool = False):
     lib.svgf_scene_draw_planar.argtypes = [vp, vp, C.POINTER(SvgfPlanarGBuffer), ip, ip, C.POINTER(SvgfCamera), C.POINTER(SvgfSynthParams),
                                            C.POINTER(C.c_float), vp]
     lib.svgf_bvh_build_host.argtypes = [vp, ip, C.POINTER(SvgfSceneBuildParams), vp, C.POINTER(ip), vp, C.POINTER(ip)]
+    lib.svgf_scene_enable_pose.argtypes = [vp, ip]
+    lib.svgf_scene_pose.argtypes = [vp, vp, ip, vp, vp]
+    lib.svgf_scene_read.argtypes = [vp, ip, vp, C.c_ulonglong]
+    lib.svgf_pose_rigid.argtypes = [C.POINTER(C.c_float), C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float), vp]
+    lib.svgf_bvh_refit_plan_host.argtypes = [vp, ip, ip, vp, vp, vp, vp, vp]
     if path == LIB_PATH:
         _lib = lib
     return lib
@@ -877,9 +890,43 @@ def bvh_build_host(tris, max_leaf_tris: int = 0, split: int = 0):
     return nodes[:n_nodes.value].copy(), order[:n].copy(), depth.value
 
 
+def pose_rigid(axis, angle_rad: float, pivot=(0.0, 0.0, 0.0), translate=(0.0, 0.0, 0.0)) -> np.ndarray:
+    """svgf_pose_rigid (host only): one SCENE_POSE_DTYPE record - the rotation by angle_rad about `axis` through `pivot`, then
+    `translate`, and its analytic inverse."""
+    out = np.zeros(1, SCENE_POSE_DTYPE)
+    v3 = lambda v: (C.c_float * 3)(*[float(x) for x in v])      # noqa: E731
+    rc = load_library().svgf_pose_rigid(v3(axis), float(angle_rad), v3(pivot), v3(translate), out.ctypes.data)
+    if rc != SVGF_OK:
+        raise SvgfError(f"svgf_pose_rigid failed ({rc})")
+    return out[0]
+
+
+def pose_identity(n: int) -> np.ndarray:
+    """n identity SCENE_POSE_DTYPE records."""
+    out = np.zeros(int(n), SCENE_POSE_DTYPE)
+    out["xf"][:, [0, 5, 10]] = 1.0
+    out["inv"][:, [0, 5, 10]] = 1.0
+    return out
+
+
+def bvh_refit_plan_host(nodes, cap: int = SCENE_REFIT_CAP) -> dict:
+    """svgf_bvh_refit_plan_host (no device needed): dict(treelets REFIT_TREELET_DTYPE[n_treelets], level uint8[n_nodes],
+    top int32[n_top], top_seg int32[n_top_depths + 1]) of BVH_NODE_DTYPE `nodes`."""
+    nd = np.ascontiguousarray(nodes, dtype=BVH_NODE_DTYPE)
+    n = len(nd)
+    treelets, level, top = np.zeros(max(n, 1), REFIT_TREELET_DTYPE), np.zeros(max(n, 1), np.uint8), np.zeros(max(n, 1), np.int32)
+    seg, info = np.zeros(SCENE_MAX_DEPTH + 2, np.int32), np.zeros(4, np.int32)
+    rc = load_library().svgf_bvh_refit_plan_host(nd.ctypes.data if n else None, n, int(cap), treelets.ctypes.data, level.ctypes.data,
+                                                 top.ctypes.data, seg.ctypes.data, info.ctypes.data)
+    if rc != SVGF_OK:
+        raise SvgfError(f"svgf_bvh_refit_plan_host failed ({rc})")
+    return dict(treelets=treelets[:info[0]].copy(), level=level[:n].copy(), top=top[:info[1]].copy(), top_seg=seg[:info[2] + 1].copy())
+
+
 class Scene:
     """A resident scene: svgf_scene_create once (validates, builds the BVH, uploads; allocates and synchronises), then draw() /
-    draw_planar() per frame - one launch each on `stream`, nothing else.  Static: camera, light and noise change per draw."""
+    draw_planar() per frame - one launch each on `stream`, nothing else.  Camera, light and noise change per draw; with
+    enable_pose(n) once and pose(table) per frame (row f15) the objects move rigidly too.  Topology and textures are fixed."""
 
     def __init__(self, handle, device):
         self.lib, self.h, self.device = load_library(), handle, int(device)
@@ -923,7 +970,38 @@ class Scene:
 
     draw_planar = draw
 
+    def enable_pose(self, n_objects: int):
+        """svgf_scene_enable_pose: allocates the animation side (allocates and synchronises; not under capture)."""
+        rc = self.lib.svgf_scene_enable_pose(self.h, int(n_objects))
+        if rc != SVGF_OK:
+            raise SvgfError(f"svgf_scene_enable_pose failed ({rc})")
+        self.n_objects = int(n_objects)
+
+    def pose(self, table, motion_out=None, stream=None):
+        """svgf_scene_pose: `table` is DEVICE memory of n_objects SCENE_POSE_DTYPE records (a torch tensor of 24 * n_objects float32
+        or a raw pointer), read when the kernels run; `motion_out` device memory of 12 * n_objects float32 or None.  Asynchronous on
+        `stream`; never waits."""
+        rc = self.lib.svgf_scene_pose(self.h, _ptr(table), int(getattr(self, "n_objects", 0)), _ptr(motion_out), _stream(stream))
+        if rc != SVGF_OK:
+            raise SvgfError(f"svgf_scene_pose failed ({rc})")
+
+    def read(self, which: int) -> np.ndarray:
+        """svgf_scene_read (blocking): 0 float32[n_tris, 3, 8], 1 / 2 BVH_NODE_DTYPE, 3 scene.SCENE_GEOM_DTYPE, 4 int32, 5 SCENE_POSE_DTYPE."""
+        from . import scene as _scene
+        i = self.info()
+        n, dt = {0: (i["n_tris"] * 24, np.float32), 1: (i["n_tris"], BVH_NODE_DTYPE), 2: (i["n_nodes"], BVH_NODE_DTYPE),
+                 3: (i["n_geoms"], _scene.SCENE_GEOM_DTYPE), 4: (i["n_tris"], np.int32),
+                 5: (getattr(self, "n_objects", 0), SCENE_POSE_DTYPE)}[int(which)]
+        out = np.zeros(n, dt)
+        rc = self.lib.svgf_scene_read(self.h, int(which), out.ctypes.data if n else None, out.nbytes)
+        if rc != SVGF_OK:
+            raise SvgfError(f"svgf_scene_read failed ({rc})")
+        return out.reshape(-1, 3, 8) if int(which) == 0 else out
+
     def free(self):
         if self.h:
             self.lib.svgf_scene_destroy(self.h)
             self.h = None
+
+
+ResidentScene = Scene

@@ -71,7 +71,9 @@ def build_hip(force: bool = False, experiments: bool = False) -> str:
             list(pool.map(lambda so: _run([hipcc_path()] + (CXX_FLAGS if os.path.basename(so[0]) in CXX_SOURCES else
                                                             cflags + HIPCC_FILE_FLAGS.get(os.path.basename(so[0]), []) + extra) + ["-c", so[0], "-o", so[1]]),
                           zip(srcs, objs)))
-        _run([hipcc_path(), "--offload-arch=gfx950", "-shared", "-fPIC"] + objs + ["-o", tmp])
+        # the product library is linked stripped (-Wl,-s: host side, link line only): .symtab / .strtab go, the dynamic symbols and
+        # the device code objects (.dynsym, .hip_fatbin) stay; DESIGN.md 5.4g has the sizes with and without
+        _run([hipcc_path(), "--offload-arch=gfx950", "-shared", "-fPIC"] + ([] if experiments else ["-Wl,-s"]) + objs + ["-o", tmp])
     os.replace(tmp, LIB)              # atomic: concurrent ranks never see a half-written library
     return LIB
 
@@ -83,11 +85,12 @@ def build_examples(force: bool = False) -> str:
     svgf_transfer_history carries the sequence along), examples/hdr_display.cpp (an emitter far above 1: svgf_exposure_meter on
     the denoised image, svgf_display_tonemap beside the plain pack) and examples/quality.cpp (svgf_quality_meter: PSNR / SSIM of the
     noisy and the denoised frame against the clean one, and of consecutive outputs) and examples/resident_scene.cpp (svgf_scene_create
-    once, then svgf_scene_draw + svgf_denoise per frame), through the C ABI -> examples/farm, examples/pipeline, examples/cadence,
-    examples/upsample, examples/dynres, examples/hdr_display, examples/quality, examples/resident_scene, linked against the product
-    library in-tree."""
+    once, then svgf_scene_draw + svgf_denoise per frame) and examples/animated_scene.cpp (svgf_scene_pose with a motion table ahead of
+    each draw), through the C ABI -> examples/farm, examples/pipeline, examples/cadence, examples/upsample, examples/dynres,
+    examples/hdr_display, examples/quality, examples/resident_scene, examples/animated_scene, linked against the product library
+    in-tree."""
     out = ""
-    for name in ("pipeline", "farm", "cadence", "upsample", "dynres", "hdr_display", "quality", "resident_scene"):
+    for name in ("pipeline", "farm", "cadence", "upsample", "dynres", "hdr_display", "quality", "resident_scene", "animated_scene"):
         src = os.path.join(ROOT, "examples", name + ".cpp")
         out = os.path.join(ROOT, "examples", name)
         if not force and _newer(out, [src, os.path.join(ROOT, "include", "svgf.h"), LIB]):

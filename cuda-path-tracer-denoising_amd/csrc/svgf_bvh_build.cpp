@@ -3,7 +3,7 @@
 // svgf_bvh_build_host orders the triangles and writes SvgfBvhNode records: count > 0 a leaf over order[first .. first + count),
 // count == 0 an inner node with children first and first + 1.  A node's box is the exact union (min / max, no arithmetic) of the
 // PADDED boxes of the triangles below it; svgf_bvh_tri_box is the one place that computes a padded box (float32, one rounding per
-// operation, contraction off), and the device reads what was stored here, never recomputes it.  That, with the slab test of
+// operation, contraction off); a pose (row f15) restates it on the device with the same literals and nesting.  That, with the slab test of
 // svgf_scene_bvh.hip, is what makes the drawn frame independent of the tree (include/svgf.h, row f14).
 //
 // Split: binned SAH over the centroids (split 0) or equal counts along the widest centroid axis (split 1).  Depth bound: a node with
@@ -20,7 +20,7 @@
 
 #pragma clang fp contract(off)
 
-void svgf_bvh_tri_box(const float *T, float lo[3], float hi[3]);       // below; svgf_scene_bvh.hip uploads what it returns
+void svgf_bvh_tri_box(const float *T, float lo[3], float hi[3]);       // below; svgf_scene_bvh.hip uploads what it returns (and restates it in k_scene_pose)
 
 namespace {
 
@@ -184,5 +184,95 @@ extern "C" int svgf_bvh_build_host(const float *tris, int n_tris, const SvgfScen
     bd.tmp.resize((size_t)n_tris);
     bd.build(0, 0, n_tris, 0);
     *n_nodes = bd.n_nodes; *depth = bd.depth;
+    return SVGF_OK;
+}
+
+// ---- row f15: the refit plan of an animated resident scene, and the pose helper -----------------------------------------------------------
+// The plan partitions the nodes for a refit without any traffic between workgroups: TREELETS (whole subtrees of at most `cap` nodes
+// whose parent's subtree is larger; one workgroup sweeps one in LDS) and the TOP (every node whose subtree is larger than `cap`: the
+// ancestors of treelet roots; one workgroup, deepest first).  It is a function of the nodes alone.  The layout it relies on - and
+// checks - is the builder's: children in pairs behind their parent, a node's descendants in ONE index range that starts at its first
+// child, so that a treelet is its root plus a range.
+extern "C" int svgf_bvh_refit_plan_host(const SvgfBvhNode *nodes, int n_nodes, int cap, SvgfRefitTreelet *treelets, unsigned char *level,
+                                        int *top, int *top_seg, SvgfRefitPlanInfo *info)
+{
+    if (!info || !top_seg || n_nodes < 0 || n_nodes > 2 * SVGF_SCENE_MAX_TRIS || cap < 1) return SVGF_ERR_INVALID_ARG;
+    if (n_nodes > 0 && (!nodes || !treelets || !level || !top)) return SVGF_ERR_INVALID_ARG;
+    *info = SvgfRefitPlanInfo{ 0, 0, 0, cap };
+    top_seg[0] = 0;
+    if (n_nodes == 0) return SVGF_OK;
+    const size_t n = (size_t)n_nodes;
+    std::vector<int> parent(n, -1), size(n, 1), depth(n, 0);
+    for (int k = 0; k < n_nodes; k++) {
+        const SvgfBvhNode &nd = nodes[k];
+        if (nd.count < 0 || nd.first < 0) return SVGF_ERR_INVALID_ARG;
+        if (nd.count > 0) continue;
+        if (nd.first <= k || (long long)nd.first + 1 >= n_nodes) return SVGF_ERR_INVALID_ARG;       // children lie behind their parent
+        for (int c = nd.first; c <= nd.first + 1; c++) {
+            if (parent[c] != -1) return SVGF_ERR_INVALID_ARG;                                       // a tree: one parent per node
+            parent[c] = k;
+        }
+    }
+    for (int k = 1; k < n_nodes; k++) {
+        if (parent[k] < 0) return SVGF_ERR_INVALID_ARG;                                             // ... and every node reached
+        depth[k] = depth[parent[k]] + 1;                                                            // parent[k] < k: already set
+        if (depth[k] > SVGF_SCENE_MAX_DEPTH) return SVGF_ERR_UNSUPPORTED;
+    }
+    for (int k = n_nodes - 1; k >= 1; k--) size[parent[k]] += size[k];
+    for (int k = 0; k < n_nodes; k++) {                 // the builder's layout: descendants of k are [first, first + size - 1)
+        if (nodes[k].count > 0) continue;
+        const int a = nodes[k].first;
+        if (k == 0 && a != 1) return SVGF_ERR_UNSUPPORTED;
+        if (nodes[a].count == 0 && nodes[a].first != a + 2) return SVGF_ERR_UNSUPPORTED;
+        if (nodes[a + 1].count == 0 && nodes[a + 1].first != a + 1 + size[a]) return SVGF_ERR_UNSUPPORTED;
+    }
+    int n_treelets = 0, n_top = 0, count_at[SVGF_SCENE_MAX_DEPTH + 1] = { 0 };
+    for (int k = 0; k < n_nodes; k++) {
+        if (size[k] > cap) { level[k] = (unsigned char)depth[k]; count_at[depth[k]]++; n_top++; continue; }
+        if (k != 0 && size[parent[k]] <= cap) continue;                                             // inside a treelet
+        SvgfRefitTreelet &t = treelets[n_treelets++];
+        t.root = k; t.begin = nodes[k].count > 0 ? 0 : nodes[k].first; t.count = size[k] - 1;
+        t.levels = nodes[k].count > 0 ? 0 : 1;
+        level[k] = 0;
+        for (int g = t.begin; g < t.begin + t.count; g++) {
+            const int l = depth[g] - depth[k];
+            level[g] = (unsigned char)l;
+            if (nodes[g].count == 0 && l + 1 > t.levels) t.levels = l + 1;
+        }
+    }
+    // the top list: deepest first, one segment per depth that occurs, so that a node's children are treelet roots or stand in an
+    // earlier segment
+    int at[SVGF_SCENE_MAX_DEPTH + 1], n_seg = 0, pos = 0;
+    for (int d = SVGF_SCENE_MAX_DEPTH; d >= 0; d--) {
+        at[d] = pos;
+        if (count_at[d] > 0) { pos += count_at[d]; top_seg[++n_seg] = pos; }
+    }
+    for (int k = 0; k < n_nodes; k++)
+        if (size[k] > cap) top[at[depth[k]]++] = k;
+    *info = SvgfRefitPlanInfo{ n_treelets, n_top, n_seg, cap };
+    return SVGF_OK;
+}
+
+// Rotation by angle_rad about `axis` through `pivot`, then `translate`: computed in double, each of the 24 values rounded once.
+extern "C" int svgf_pose_rigid(const float axis[3], float angle_rad, const float pivot[3], const float translate[3], SvgfScenePose *out)
+{
+    if (!axis || !pivot || !translate || !out || !std::isfinite(angle_rad)) return SVGF_ERR_INVALID_ARG;
+    for (int c = 0; c < 3; c++)
+        if (!std::isfinite(axis[c]) || !std::isfinite(pivot[c]) || !std::isfinite(translate[c])) return SVGF_ERR_INVALID_ARG;
+    const double len = std::sqrt((double)axis[0] * axis[0] + (double)axis[1] * axis[1] + (double)axis[2] * axis[2]);
+    if (!(len > 0.0)) return SVGF_ERR_INVALID_ARG;
+    const double u[3] = { axis[0] / len, axis[1] / len, axis[2] / len };
+    const double c = std::cos((double)angle_rad), s = std::sin((double)angle_rad), v = 1.0 - c;
+    const double R[3][3] = { { c + v * u[0] * u[0], v * u[0] * u[1] - s * u[2], v * u[0] * u[2] + s * u[1] },
+                             { v * u[1] * u[0] + s * u[2], c + v * u[1] * u[1], v * u[1] * u[2] - s * u[0] },
+                             { v * u[2] * u[0] - s * u[1], v * u[2] * u[1] + s * u[0], c + v * u[2] * u[2] } };
+    double t[3];
+    for (int r = 0; r < 3; r++) t[r] = ((double)pivot[r] - (R[r][0] * pivot[0] + R[r][1] * pivot[1] + R[r][2] * pivot[2])) + translate[r];
+    for (int r = 0; r < 3; r++) {
+        // "+ 0.0": a zero is +0 (angle 0 gives the identity on every bit, whatever the axis)
+        for (int k = 0; k < 3; k++) { out->xf[4 * r + k] = (float)(R[r][k] + 0.0); out->inv[4 * r + k] = (float)(R[k][r] + 0.0); }
+        out->xf[4 * r + 3] = (float)(t[r] + 0.0);
+        out->inv[4 * r + 3] = (float)(0.0 - (R[0][r] * t[0] + R[1][r] * t[1] + R[2][r] * t[2]));      // (R^T, -R^T t): the analytic inverse
+    }
     return SVGF_OK;
 }

@@ -1,5 +1,6 @@
 // svgf_scene_bvh.hip — the resident scene (row f14): the scene producer's inputs kept on the device with a BVH over the triangles,
-// and a draw that is one launch.  include/svgf.h states the semantics (a gated brute force that every tree reproduces);
+// and a draw that is one launch.  Row f15 (below the draw kernel) animates it: per-object poses applied to the rest state and a
+// refit of the node boxes, three launches per frame.  include/svgf.h states the semantics (a gated brute force that every tree reproduces);
 // svgf_bvh_build.cpp builds the tree on the host; the per-pixel body around the triangle search is svgf_scene_pixel.inc.h, the text
 // k_scene_frame compiles too.
 //
@@ -15,6 +16,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <cstdint>
 #include <cstring>
 #include <new>
 #include <vector>
@@ -110,15 +112,233 @@ __global__ __launch_bounds__(256) void k_scene_bvh(SceneBvhArgs b)
     }
 }
 
+// ---- row f15: pose + refit ------------------------------------------------------------------------------------------------------------------
+// Three launches, and no data passes between workgroups inside one of them (the per-XCD L2s are not coherent, and nothing here spins
+// or climbs the tree with atomics): k_scene_pose writes posed triangles, their boxes, the primitives, the motion rows and the held
+// table; k_scene_refit_treelets sweeps one treelet per workgroup in LDS; k_scene_refit_top, ONE workgroup, the nodes above them.
+constexpr int kRefitCap = SVGF_SCENE_REFIT_CAP;
+
+struct ScenePoseArgs {
+    int n_tris, n_geoms, n_objects, tri_blocks;
+    const float4 *rest_tris;    // 6 float4 per triangle: per vertex {px, py, pz, nx}, {ny, nz, u, v}
+    float4 *tris;
+    const int *tri_ids;
+    float4 *tri_boxes;
+    const SvgfSceneGeom *rest_geoms;
+    SvgfSceneGeom *geoms;
+    const int *geom_ids;
+    const float4 *pose;         // 6 float4 per object: xf rows, inv rows
+    float4 *held;
+    float4 *motion;             // 3 float4 per object, or null
+};
+
+struct SceneRefitArgs {
+    float4 *nodes;
+    const int *order;
+    const float4 *tri_boxes;
+    const int4 *treelets;
+    const unsigned char *level;
+    const int *top, *top_seg;
+    int n_top_depths;
+};
+
+// C = A o B (include/svgf.h, row f15); rows as float4 {m0, m1, m2, m3}
+__device__ __forceinline__ void compose34(const float *A, const float *B, float *C)
+{
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int r = 0; r < 3; r++) {
+#pragma unroll
+        for (int c = 0; c < 3; c++) C[4 * r + c] = (A[4 * r] * B[c] + A[4 * r + 1] * B[4 + c]) + A[4 * r + 2] * B[8 + c];
+        C[4 * r + 3] = ((A[4 * r] * B[3] + A[4 * r + 1] * B[7]) + A[4 * r + 2] * B[11]) + A[4 * r + 3];
+    }
+}
+
+__device__ __forceinline__ void load12(const float4 *src, float *m)
+{
+#pragma unroll
+    for (int r = 0; r < 3; r++) { const float4 q = src[r]; m[4 * r] = q.x; m[4 * r + 1] = q.y; m[4 * r + 2] = q.z; m[4 * r + 3] = q.w; }
+}
+
+__global__ __launch_bounds__(256) void k_scene_pose(ScenePoseArgs a)
+{
+#pragma clang fp contract(off)
+    if ((int)blockIdx.x < a.tri_blocks) {
+        const int i = blockIdx.x * 256 + threadIdx.x;
+        if (i >= a.n_tris) return;
+        float4 q[6];
+#pragma unroll
+        for (int k = 0; k < 6; k++) q[k] = a.rest_tris[6 * (size_t)i + k];
+        const int id = a.tri_ids[i];
+        if (id >= 0 && id < a.n_objects) {
+            float M[12];
+            load12(a.pose + 6 * (size_t)id, M);
+#pragma unroll
+            for (int v = 0; v < 3; v++) {
+                const float p[3] = { q[2 * v].x, q[2 * v].y, q[2 * v].z }, n[3] = { q[2 * v].w, q[2 * v + 1].x, q[2 * v + 1].y };
+                float pp[3], nn[3];
+#pragma unroll
+                for (int r = 0; r < 3; r++) {
+                    pp[r] = ((M[4 * r] * p[0] + M[4 * r + 1] * p[1]) + M[4 * r + 2] * p[2]) + M[4 * r + 3];
+                    nn[r] = (M[4 * r] * n[0] + M[4 * r + 1] * n[1]) + M[4 * r + 2] * n[2];
+                }
+                q[2 * v] = make_float4(pp[0], pp[1], pp[2], nn[0]);
+                q[2 * v + 1].x = nn[1]; q[2 * v + 1].y = nn[2];
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < 6; k++) a.tris[6 * (size_t)i + k] = q[k];
+        // svgf_bvh_tri_box on the posed positions: the same literals, the same nesting
+        const float P[3][3] = { { q[0].x, q[0].y, q[0].z }, { q[2].x, q[2].y, q[2].z }, { q[4].x, q[4].y, q[4].z } };
+        float mn[3], mx[3], ext = 0.0f, lo[3], hi[3];
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            mn[c] = fminf(fminf(P[0][c], P[1][c]), P[2][c]);
+            mx[c] = fmaxf(fmaxf(P[0][c], P[1][c]), P[2][c]);
+            const float e = mx[c] - mn[c];
+            ext = e > ext ? e : ext;
+        }
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            const float m = fmaxf(1.0f, fmaxf(fabsf(mn[c]), fabsf(mx[c])));
+            const float pad = (ext * 0.00390625f) + (0.0000152587890625f * m);
+            lo[c] = mn[c] - pad; hi[c] = mx[c] + pad;
+        }
+        a.tri_boxes[2 * (size_t)i] = make_float4(lo[0], lo[1], lo[2], __int_as_float(i));
+        a.tri_boxes[2 * (size_t)i + 1] = make_float4(hi[0], hi[1], hi[2], __int_as_float(1));
+        return;
+    }
+    // the tail blocks: thread j poses primitive j and writes table row j
+    const int j = ((int)blockIdx.x - a.tri_blocks) * 256 + threadIdx.x;
+    if (j < a.n_geoms) {
+        const SvgfSceneGeom *g = a.rest_geoms + j;
+        SvgfSceneGeom *o = a.geoms + j;
+        o->type = g->type; o->material = g->material; o->emittance = g->emittance;
+#pragma unroll
+        for (int c = 0; c < 3; c++) o->albedo[c] = g->albedo[c];
+        float Gx[12], Gi[12], Ox[12], Oi[12];
+#pragma unroll
+        for (int k = 0; k < 12; k++) { Gx[k] = g->xf[k]; Gi[k] = g->inv[k]; }
+        const int id = a.geom_ids ? a.geom_ids[j] : j;
+        if (id >= 0 && id < a.n_objects) {
+            float X[12], I[12];
+            load12(a.pose + 6 * (size_t)id, X);
+            load12(a.pose + 6 * (size_t)id + 3, I);
+            compose34(X, Gx, Ox);
+            compose34(Gi, I, Oi);
+#pragma unroll
+            for (int k = 0; k < 12; k++) { o->xf[k] = Ox[k]; o->inv[k] = Oi[k]; }
+#pragma unroll
+            for (int r = 0; r < 3; r++) { o->invT[3 * r] = Oi[r]; o->invT[3 * r + 1] = Oi[4 + r]; o->invT[3 * r + 2] = Oi[8 + r]; }
+        } else {
+#pragma unroll
+            for (int k = 0; k < 12; k++) { o->xf[k] = Gx[k]; o->inv[k] = Gi[k]; }
+#pragma unroll
+            for (int k = 0; k < 9; k++) o->invT[k] = g->invT[k];
+        }
+    }
+    if (j < a.n_objects) {
+        const float4 p0 = a.pose[6 * (size_t)j], p1 = a.pose[6 * (size_t)j + 1], p2 = a.pose[6 * (size_t)j + 2];
+        const float4 p3 = a.pose[6 * (size_t)j + 3], p4 = a.pose[6 * (size_t)j + 4], p5 = a.pose[6 * (size_t)j + 5];
+        if (a.motion) {
+            float Hx[12], Mo[12];
+            load12(a.held + 6 * (size_t)j, Hx);
+            const float I[12] = { p3.x, p3.y, p3.z, p3.w, p4.x, p4.y, p4.z, p4.w, p5.x, p5.y, p5.z, p5.w };
+            compose34(Hx, I, Mo);
+#pragma unroll
+            for (int r = 0; r < 3; r++) a.motion[3 * (size_t)j + r] = make_float4(Mo[4 * r], Mo[4 * r + 1], Mo[4 * r + 2], Mo[4 * r + 3]);
+        }
+        float4 *h = a.held + 6 * (size_t)j;
+        h[0] = p0; h[1] = p1; h[2] = p2; h[3] = p3; h[4] = p4; h[5] = p5;
+    }
+}
+
+__device__ __forceinline__ void box_union(float4 &lo, float4 &hi, const float4 &blo, const float4 &bhi)
+{
+    lo.x = fminf(lo.x, blo.x); lo.y = fminf(lo.y, blo.y); lo.z = fminf(lo.z, blo.z);
+    hi.x = fmaxf(hi.x, bhi.x); hi.y = fmaxf(hi.y, bhi.y); hi.z = fmaxf(hi.z, bhi.z);
+}
+
+// One workgroup per treelet (svgf_bvh_refit_plan_host): local index 0 is the root, 1 + (g - begin) a descendant.  Leaves are filled
+// from the posed triangle boxes, then the inner nodes level by level from the deepest, one barrier per level; every node box is
+// stored once.  first / count travel through LDS unchanged in the .w lanes.
+__global__ __launch_bounds__(256) void k_scene_refit_treelets(SceneRefitArgs r)
+{
+    __shared__ float4 box[2 * kRefitCap];
+    __shared__ unsigned char lev[kRefitCap];
+    const int4 t = r.treelets[blockIdx.x];      // root, begin, count, levels
+    const int n = t.z + 1;
+    for (int l = threadIdx.x; l < n; l += 256) {
+        const int g = l == 0 ? t.x : t.y + l - 1;
+        float4 lo = r.nodes[2 * (size_t)g], hi = r.nodes[2 * (size_t)g + 1];
+        const int first = __float_as_int(lo.w), count = __float_as_int(hi.w);
+        if (count > 0) {
+            int i = r.order[first];
+            const float4 b0 = r.tri_boxes[2 * (size_t)i], b1 = r.tri_boxes[2 * (size_t)i + 1];
+            lo.x = b0.x; lo.y = b0.y; lo.z = b0.z; hi.x = b1.x; hi.y = b1.y; hi.z = b1.z;
+            for (int k = first + 1; k < first + count; k++) {
+                i = r.order[k];
+                box_union(lo, hi, r.tri_boxes[2 * (size_t)i], r.tri_boxes[2 * (size_t)i + 1]);
+            }
+        }
+        box[2 * l] = lo; box[2 * l + 1] = hi;
+        lev[l] = r.level[g];
+    }
+    __syncthreads();
+    for (int L = t.w - 1; L >= 0; L--) {
+        for (int l = threadIdx.x; l < n; l += 256) {
+            if (lev[l] != L) continue;
+            float4 lo = box[2 * l], hi = box[2 * l + 1];
+            if (__float_as_int(hi.w) > 0) continue;
+            const int c = __float_as_int(lo.w) - t.y + 1;       // the first child's local index; children are descendants: >= 1
+            const float4 alo = box[2 * c], ahi = box[2 * c + 1];
+            lo.x = alo.x; lo.y = alo.y; lo.z = alo.z; hi.x = ahi.x; hi.y = ahi.y; hi.z = ahi.z;
+            box_union(lo, hi, box[2 * c + 2], box[2 * c + 3]);
+            box[2 * l] = lo; box[2 * l + 1] = hi;
+        }
+        __syncthreads();
+    }
+    for (int l = threadIdx.x; l < n; l += 256) {
+        const int g = l == 0 ? t.x : t.y + l - 1;
+        r.nodes[2 * (size_t)g] = box[2 * l]; r.nodes[2 * (size_t)g + 1] = box[2 * l + 1];
+    }
+}
+
+// ONE workgroup: the nodes above the treelets, deepest depth first; the children of a node are treelet roots (the launch before) or
+// nodes of an earlier segment (this workgroup, behind a barrier).
+__global__ __launch_bounds__(256) void k_scene_refit_top(SceneRefitArgs r)
+{
+    for (int s = 0; s < r.n_top_depths; s++) {
+        const int b = r.top_seg[s], e = r.top_seg[s + 1];
+        for (int i = b + (int)threadIdx.x; i < e; i += 256) {
+            const int g = r.top[i];
+            float4 lo = r.nodes[2 * (size_t)g], hi = r.nodes[2 * (size_t)g + 1];
+            const int c = __float_as_int(lo.w);
+            const float4 alo = r.nodes[2 * (size_t)c], ahi = r.nodes[2 * (size_t)c + 1];
+            lo.x = alo.x; lo.y = alo.y; lo.z = alo.z; hi.x = ahi.x; hi.y = ahi.y; hi.z = ahi.z;
+            box_union(lo, hi, r.nodes[2 * (size_t)c + 2], r.nodes[2 * (size_t)c + 3]);
+            r.nodes[2 * (size_t)g] = lo; r.nodes[2 * (size_t)g + 1] = hi;
+        }
+        __syncthreads();
+    }
+}
+
 constexpr size_t align16(size_t n) { return (n + 15) & ~(size_t)15; }
+
+const float kIdentityPose[24] = { 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0 };
 
 }  // namespace
 
 struct svgf_scene {
     int device;
-    char *dev;                  // the one allocation
-    SceneBvhArgs args;          // the scene's pointers; camera, outputs and frame are filled per draw
+    char *dev;                  // the one allocation of svgf_scene_create: the REST state once a scene is posed
+    SceneBvhArgs args;          // the scene's pointers (what the draws read); camera, outputs and frame are filled per draw
     SvgfSceneInfo info;
+    // row f15, all zero on a static scene
+    char *anim;                 // the one allocation of svgf_scene_enable_pose
+    int n_objects, n_treelets, n_top;
+    ScenePoseArgs pose;
+    SceneRefitArgs refit;
 };
 
 extern "C" int svgf_scene_create(int device, const SvgfSceneGeom *geoms, int n_geoms, const int *geom_ids, const float *tris, const int *tri_ids,
@@ -197,6 +417,7 @@ extern "C" int svgf_scene_destroy(svgf_scene *scene)
     SvgfDeviceGuard dev_guard(scene->device);
     int rc = SVGF_OK;
     if (!dev_guard.ok || hipDeviceSynchronize() != hipSuccess || hipFree(scene->dev) != hipSuccess) rc = SVGF_ERR_HIP;
+    if (scene->anim && (!dev_guard.ok || hipFree(scene->anim) != hipSuccess)) rc = SVGF_ERR_HIP;
     delete scene;
     return rc;
 }
@@ -240,4 +461,100 @@ extern "C" int svgf_scene_draw_planar(const svgf_scene *scene, void *out_rgb_dev
 {
     if (!planes) return SVGF_ERR_INVALID_ARG;
     return scene_draw_impl(scene, out_rgb_dev, nullptr, planes, width, height, cam, sp, light, stream);
+}
+
+// ---- row f15: the animated resident scene ---------------------------------------------------------------------------------------------------
+extern "C" int svgf_scene_enable_pose(svgf_scene *scene, int n_objects)
+{
+    if (!scene || n_objects < 1 || n_objects > SVGF_SCENE_MAX_POSED) return SVGF_ERR_INVALID_ARG;
+    if (scene->anim) return n_objects == scene->n_objects ? SVGF_OK : SVGF_ERR_INVALID_ARG;
+    const SvgfSceneInfo &in = scene->info;
+    const size_t nt = (size_t)(in.n_tris > 0 ? in.n_tris : 1), ng = (size_t)(in.n_geoms > 0 ? in.n_geoms : 1), nn = (size_t)(in.n_nodes > 0 ? in.n_nodes : 1);
+    // the plan, from the nodes as created (a blocking read; this call is not for use under capture)
+    SvgfDeviceGuard dev_guard(scene->device);
+    if (!dev_guard.ok) return SVGF_ERR_NO_DEVICE;
+    std::vector<SvgfBvhNode> nodes(nn);
+    if (in.n_nodes > 0 && hipMemcpy(nodes.data(), scene->args.nodes, sizeof(SvgfBvhNode) * (size_t)in.n_nodes, hipMemcpyDeviceToHost) != hipSuccess) return SVGF_ERR_HIP;
+    std::vector<SvgfRefitTreelet> treelets(nn);
+    std::vector<unsigned char> level(nn);
+    std::vector<int> top(nn), top_seg(SVGF_SCENE_MAX_DEPTH + 2, 0);
+    SvgfRefitPlanInfo plan;
+    const int rc = svgf_bvh_refit_plan_host(nodes.data(), in.n_nodes, kRefitCap, treelets.data(), level.data(), top.data(), top_seg.data(), &plan);
+    if (rc != SVGF_OK) return rc;
+    for (int k = 0; k < plan.n_treelets; k++)
+        if (treelets[k].count + 1 > kRefitCap) return SVGF_ERR_UNSUPPORTED;      // the treelet kernel's LDS; the plan never goes there
+    // one allocation: [tris | tri_boxes | nodes | geoms | held | treelets | level | top | top_seg], 16-byte aligned parts
+    const size_t o_t = 0, o_b = o_t + align16(sizeof(float) * 24 * nt), o_n = o_b + sizeof(SvgfBvhNode) * nt, o_g = o_n + sizeof(SvgfBvhNode) * nn;
+    const size_t o_h = o_g + align16(sizeof(SvgfSceneGeom) * ng), o_tl = o_h + sizeof(SvgfScenePose) * (size_t)n_objects;
+    const size_t o_lv = o_tl + sizeof(SvgfRefitTreelet) * nn, o_tp = o_lv + align16(nn), o_ts = o_tp + align16(sizeof(int) * nn);
+    const size_t bytes = o_ts + align16(sizeof(int) * top_seg.size());
+    char *d = nullptr;
+    if (hipMalloc(reinterpret_cast<void **>(&d), bytes) != hipSuccess) return SVGF_ERR_OOM;
+    const SceneArgs &a = scene->args.s;
+    std::vector<float> held(24 * (size_t)n_objects);
+    for (int k = 0; k < n_objects; k++) std::memcpy(&held[24 * (size_t)k], kIdentityPose, sizeof(kIdentityPose));
+    bool ok = hipMemset(d, 0, bytes) == hipSuccess;
+    if (in.n_tris > 0) {
+        ok = ok && hipMemcpy(d + o_t, a.tris, sizeof(float) * 24 * (size_t)in.n_tris, hipMemcpyDeviceToDevice) == hipSuccess;
+        ok = ok && hipMemcpy(d + o_b, scene->args.tri_boxes, sizeof(SvgfBvhNode) * (size_t)in.n_tris, hipMemcpyDeviceToDevice) == hipSuccess;
+        ok = ok && hipMemcpy(d + o_n, scene->args.nodes, sizeof(SvgfBvhNode) * (size_t)in.n_nodes, hipMemcpyDeviceToDevice) == hipSuccess;
+        ok = ok && hipMemcpy(d + o_tl, treelets.data(), sizeof(SvgfRefitTreelet) * (size_t)plan.n_treelets, hipMemcpyHostToDevice) == hipSuccess;
+        ok = ok && hipMemcpy(d + o_lv, level.data(), (size_t)in.n_nodes, hipMemcpyHostToDevice) == hipSuccess;
+        ok = ok && (plan.n_top == 0 || hipMemcpy(d + o_tp, top.data(), sizeof(int) * (size_t)plan.n_top, hipMemcpyHostToDevice) == hipSuccess);
+        ok = ok && hipMemcpy(d + o_ts, top_seg.data(), sizeof(int) * top_seg.size(), hipMemcpyHostToDevice) == hipSuccess;
+    }
+    if (in.n_geoms > 0) ok = ok && hipMemcpy(d + o_g, a.geoms, sizeof(SvgfSceneGeom) * (size_t)in.n_geoms, hipMemcpyDeviceToDevice) == hipSuccess;
+    ok = ok && hipMemcpy(d + o_h, held.data(), sizeof(float) * held.size(), hipMemcpyHostToDevice) == hipSuccess;
+    ok = ok && hipDeviceSynchronize() == hipSuccess;
+    if (!ok) { (void)hipFree(d); return SVGF_ERR_HIP; }
+    ScenePoseArgs &p = scene->pose;
+    p.n_tris = in.n_tris; p.n_geoms = in.n_geoms; p.n_objects = n_objects; p.tri_blocks = (in.n_tris + 255) / 256;
+    p.rest_tris = reinterpret_cast<const float4 *>(a.tris); p.tris = reinterpret_cast<float4 *>(d + o_t);
+    p.tri_ids = a.tri_ids; p.tri_boxes = reinterpret_cast<float4 *>(d + o_b);
+    p.rest_geoms = a.geoms; p.geoms = reinterpret_cast<SvgfSceneGeom *>(d + o_g); p.geom_ids = a.geom_ids;
+    p.pose = nullptr; p.held = reinterpret_cast<float4 *>(d + o_h); p.motion = nullptr;
+    SceneRefitArgs &r = scene->refit;
+    r.nodes = reinterpret_cast<float4 *>(d + o_n); r.order = scene->args.order; r.tri_boxes = p.tri_boxes;
+    r.treelets = reinterpret_cast<const int4 *>(d + o_tl); r.level = reinterpret_cast<const unsigned char *>(d + o_lv);
+    r.top = reinterpret_cast<const int *>(d + o_tp); r.top_seg = reinterpret_cast<const int *>(d + o_ts); r.n_top_depths = plan.n_top_depths;
+    // from here on the draws read the posed copies
+    scene->args.s.tris = reinterpret_cast<const float *>(p.tris);
+    scene->args.s.geoms = p.geoms;
+    scene->args.tri_boxes = p.tri_boxes;
+    scene->args.nodes = r.nodes;
+    scene->anim = d; scene->n_objects = n_objects; scene->n_treelets = plan.n_treelets; scene->n_top = plan.n_top;
+    scene->info.device_bytes += (unsigned long long)bytes;
+    return SVGF_OK;
+}
+
+extern "C" int svgf_scene_pose(svgf_scene *scene, const SvgfScenePose *pose_dev, int n_objects, float *motion_out_dev, void *stream)
+{
+    if (!scene || !pose_dev || !scene->anim || n_objects != scene->n_objects) return SVGF_ERR_INVALID_ARG;
+    if ((reinterpret_cast<uintptr_t>(pose_dev) & 15) || (reinterpret_cast<uintptr_t>(motion_out_dev) & 15)) return SVGF_ERR_INVALID_ARG;
+    SvgfDeviceGuard dev_guard(scene->device);
+    if (!dev_guard.ok) return SVGF_ERR_NO_DEVICE;
+    ScenePoseArgs p = scene->pose;
+    p.pose = reinterpret_cast<const float4 *>(pose_dev);
+    p.motion = reinterpret_cast<float4 *>(motion_out_dev);
+    const int tail = (p.n_geoms > p.n_objects ? p.n_geoms : p.n_objects);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(k_scene_pose, dim3(p.tri_blocks + (tail + 255) / 256), dim3(256), 0, st, p);
+    if (scene->n_treelets > 0) hipLaunchKernelGGL(k_scene_refit_treelets, dim3(scene->n_treelets), dim3(256), 0, st, scene->refit);
+    if (scene->n_top > 0) hipLaunchKernelGGL(k_scene_refit_top, dim3(1), dim3(256), 0, st, scene->refit);
+    return hipGetLastError() == hipSuccess ? SVGF_OK : SVGF_ERR_HIP;
+}
+
+extern "C" int svgf_scene_read(const svgf_scene *scene, int which, void *host_dst, unsigned long long host_bytes)
+{
+    if (!scene || which < 0 || which > 5 || (which == 5 && !scene->anim)) return SVGF_ERR_INVALID_ARG;
+    const SvgfSceneInfo &in = scene->info;
+    const void *src[6] = { scene->args.s.tris, scene->args.tri_boxes, scene->args.nodes, scene->args.s.geoms, scene->args.order, scene->pose.held };
+    const unsigned long long size[6] = { 96ull * in.n_tris, 32ull * in.n_tris, 32ull * in.n_nodes, (unsigned long long)sizeof(SvgfSceneGeom) * in.n_geoms,
+                                         4ull * in.n_tris, (unsigned long long)sizeof(SvgfScenePose) * scene->n_objects };
+    if (host_bytes != size[which] || (host_bytes > 0 && !host_dst)) return SVGF_ERR_INVALID_ARG;
+    if (host_bytes == 0) return SVGF_OK;
+    SvgfDeviceGuard dev_guard(scene->device);
+    if (!dev_guard.ok) return SVGF_ERR_NO_DEVICE;
+    if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(host_dst, src[which], (size_t)host_bytes, hipMemcpyDeviceToHost) != hipSuccess) return SVGF_ERR_HIP;
+    return SVGF_OK;
 }

@@ -749,8 +749,8 @@ int svgf_quality_read (int device, const void *state_dev, SvgfQualityResult *out
  * svgf_scene_render_mesh uploads the whole scene, waits for that upload and tests every triangle for every pixel on EVERY call.
  * A resident scene is the same scene kept on the device with a bounding-volume hierarchy over its triangles: svgf_scene_create
  * validates, builds and uploads once; svgf_scene_draw / svgf_scene_draw_planar are exactly one launch on `stream` - no allocation,
- * no upload, no host synchronisation, legal under stream capture.  Resident scenes are STATIC: what moves from frame to frame is
- * the camera, the light and SvgfSynthParams; primitives or triangles that move stay with svgf_scene_render_mesh.
+ * no upload, no host synchronisation, legal under stream capture.  What moves from frame to frame is the camera, the light,
+ * SvgfSynthParams and - with row f15 below - rigid per-object poses; topology, textures and the set of objects are fixed at creation.
  * svgf_scene_create: the scene arguments are svgf_scene_render_mesh's (host arrays, read completely before it returns), with the
  *   same validation and error codes, and in addition SVGF_ERR_INVALID_ARG for a vertex POSITION that is not finite (normals and uvs
  *   may be anything), for bp->max_leaf_tris outside 0..8, bp->split outside 0..1 and a NULL `out`; device outside 0..63:
@@ -760,7 +760,7 @@ int svgf_quality_read (int device, const void *state_dev, SvgfQualityResult *out
  * svgf_scene_draw*: SVGF_ERR_INVALID_ARG for a NULL scene, output, cam, sp or light, a planar target without normal, position and
  *   geom_id, a size <= 0; SVGF_ERR_UNSUPPORTED for width * height >= 2^31 / 16; all before any device work.
  * Normative semantics - a GATED brute force; every tree gives the same frame.  float32, one rounding per operation, no contraction:
- *   Padded box of triangle i, computed once on the host and stored (the device never recomputes it).  Per axis c:
+ *   Padded box of triangle i, computed by this one formula, on the host at creation and on the device by a pose (row f15).  Per axis c:
  *     mn = min(min(v0, v1), v2), mx likewise;  ext = max over c of (mx_c - mn_c)
  *     pad_c = (ext * 2^-8) + (2^-16 * max(1, |mn_c|, |mx_c|));  lo_c = mn_c - pad_c;  hi_c = mx_c + pad_c
  *   Slab test S(box, ray) -> (pass, tn), ray origin o and direction d:  tn = 0, tf = +inf; per axis c:
@@ -807,6 +807,70 @@ int svgf_scene_draw_planar(const svgf_scene *scene, void *out_rgb_dev, const Svg
 typedef struct SvgfBvhNode { float lo[3]; int first; float hi[3]; int count; } SvgfBvhNode;   /* 32 bytes */
 int svgf_bvh_build_host(const float *tris, int n_tris, const SvgfSceneBuildParams *bp, SvgfBvhNode *nodes, int *n_nodes,
                         int *order, int *depth);
+
+/* ---- "next" row f15: animated resident scene - pose objects and refit the BVH on the device (added after 0.9; probe the symbol) ----
+ * A resident scene whose objects move rigidly: per frame the caller hands over a DEVICE table of per-object poses, and
+ * svgf_scene_pose re-poses the triangles and primitives from their rest state, recomputes the padded triangle boxes, refits the
+ * node boxes and writes row f7's motion table for the same frame - at most three launches on `stream`, no allocation, no upload, no
+ * host wait, legal under stream capture.  Nothing of row f14's contract moves: the frame is the gated brute force over the POSED
+ * triangles, which every tree reproduces, so a refitted tree draws the frame a tree rebuilt at that pose would.
+ * What stays static: the topology (nodes' first / count, the triangle order - the tree is refitted, never re-split, however loose its
+ * boxes become), the textures, and the set of objects.
+ * svgf_scene_enable_pose(scene, n_objects): allocates the animation side once - posed copies of the triangles, triangle boxes, nodes
+ *   and primitives, the HELD pose table (identity) and the refit plan.  The arrays svgf_scene_create uploaded become the REST state
+ *   and are never written again; the posed copies start as bit copies of them and the draws read them from now on.  Allocates and
+ *   synchronises: not under capture (like svgf_enable_pipeline).  A second call with the same n_objects is a no-op; a different
+ *   n_objects, n_objects outside 1..SVGF_SCENE_MAX_POSED or a NULL scene is SVGF_ERR_INVALID_ARG, before any device work.  A scene
+ *   that never calls it is byte for byte row f14's.  svgf_scene_info's device_bytes grows by the second allocation.
+ * svgf_scene_pose(scene, pose_dev, n_objects, motion_out_dev, stream): one call per frame, ahead of the draw, on the draw's stream.
+ *   pose_dev: n_objects SvgfScenePose records in device memory, whose CONTENTS the kernels read when they run (row f7's rule: a
+ *   captured pose replays with whatever the table holds then).  Object id k is tri_ids / geom_ids (a primitive's index where geom_ids
+ *   was NULL); an id outside [0, n_objects) keeps its rest state through a branch (a bit copy, no arithmetic).  Poses apply to the
+ *   REST state, never to the previous pose: the same table twice leaves the same bytes, nothing drifts.
+ *   SVGF_ERR_INVALID_ARG, before any device work, the scene untouched: a NULL scene or table, n_objects other than what was enabled,
+ *   a scene without svgf_scene_enable_pose, a pose_dev or motion_out_dev that is not 16-byte aligned.
+ * Normative arithmetic - float32, one rounding per operation, no contraction; M = pose[id].xf:
+ *   vertex position  p'[r] = ((M[4r] px + M[4r+1] py) + M[4r+2] pz) + M[4r+3]
+ *   vertex normal    n'[r] = (M[4r] nx + M[4r+1] ny) + M[4r+2] nz         (linear block, not renormalised: row f7's rule)
+ *   uv, albedo, texture index, id: untouched.
+ *   Padded box of a posed triangle: row f14's formula on the posed positions - computed by that one formula, on the host at creation
+ *   and on the device by a pose.
+ *   C = A o B of two 3x4 maps: C[r][c] = (A[r][0] B[0][c] + A[r][1] B[1][c]) + A[r][2] B[2][c], and for c == 3 "+ A[r][3]" last.
+ *   Primitive with a posed id: xf' = pose.xf o xf_rest; inv' = inv_rest o pose.inv; invT' = transpose of inv's 3x3 block; the rest copied.
+ *   Motion table: motion_out_dev non-NULL: row k < n_objects (12 floats) = held[k].xf o pose[k].inv - this frame's world to the
+ *   previous frame's, what svgf_set_object_motion and svgf_motion_reproject take.  Then held := pose (also with NULL), on the device in
+ *   stream order, so a replayed graph chains.  held is the identity after svgf_scene_enable_pose.
+ *   Node boxes: a leaf = fminf / fmaxf union of the posed boxes of order[first .. first + count); an inner node = the union of its two
+ *   children.  A pose is expected to be finite and rigid (not checked); every float is a defined input to the above, and because the
+ *   topology is fixed a NaN or inf cannot make a draw loop or read out of bounds.
+ * svgf_scene_read: a blocking read-back (tests, debugging; like svgf_read_state).  Kinds: 0 triangles as drawn (96 B each),
+ *   1 padded triangle boxes as drawn (SvgfBvhNode: first = i, count = 1), 2 nodes, 3 primitives as drawn (SvgfSceneGeom), 4 order,
+ *   5 the held pose table (posed scenes only).  host_bytes must be the array's size exactly; otherwise, or for another kind,
+ *   SVGF_ERR_INVALID_ARG.  Works on a static scene (what was created).
+ * svgf_pose_rigid (host only): rotation by angle_rad about `axis` through `pivot`, then `translate`; computed in double, inv the
+ *   analytic inverse (R^T, -R^T t), each of the 24 values rounded to float32 once.  A zero axis or a non-finite argument:
+ *   SVGF_ERR_INVALID_ARG.
+ * svgf_bvh_refit_plan_host (host only, no device needed): the partition svgf_scene_pose refits by, from the nodes alone.  A TREELET
+ *   is a whole subtree of at most `cap` nodes whose parent's subtree is larger: node `root` and its descendants, nodes
+ *   [begin, begin + count); `levels` = 1 + the deepest local level (root = 0) that holds an inner node, 0 for a single leaf.  The TOP
+ *   is every node whose subtree exceeds `cap`, listed deepest first in n_top_depths segments top[top_seg[s] .. top_seg[s + 1]), one
+ *   per depth: a top node's children are treelet roots or stand in an earlier segment.  level[k] = the local level of a treelet node,
+ *   the depth of a top node.  Room: treelets, level, top: n_nodes; top_seg: SVGF_SCENE_MAX_DEPTH + 2.  SVGF_ERR_INVALID_ARG for
+ *   arrays that are no binary tree by the SvgfBvhNode rules (a child at or before its parent, two parents, an unreached node, a
+ *   negative first / count) or cap < 1; SVGF_ERR_UNSUPPORTED for a depth above SVGF_SCENE_MAX_DEPTH or a tree not laid out as the
+ *   builder lays it out (children in pairs, a node's descendants in one index range starting at its first child).
+ * INTEGRATION.md 5i has the frame loop and what a pose costs, examples/animated_scene.cpp runs it. */
+typedef struct SvgfScenePose { float xf[12]; float inv[12]; } SvgfScenePose;  /* rest world -> this frame's world, and back; 3x4 row-major */
+#define SVGF_SCENE_MAX_POSED 1024
+#define SVGF_SCENE_REFIT_CAP 1024    /* nodes per treelet of svgf_scene_pose's refit (32 KB of LDS) */
+typedef struct SvgfRefitTreelet { int root, begin, count, levels; } SvgfRefitTreelet;
+typedef struct SvgfRefitPlanInfo { int n_treelets, n_top, n_top_depths, cap; } SvgfRefitPlanInfo;
+int svgf_scene_enable_pose(svgf_scene *scene, int n_objects);
+int svgf_scene_pose(svgf_scene *scene, const SvgfScenePose *pose_dev, int n_objects, float *motion_out_dev, void *stream);
+int svgf_scene_read(const svgf_scene *scene, int which, void *host_dst, unsigned long long host_bytes);
+int svgf_pose_rigid(const float axis[3], float angle_rad, const float pivot[3], const float translate[3], SvgfScenePose *out);
+int svgf_bvh_refit_plan_host(const SvgfBvhNode *nodes, int n_nodes, int cap, SvgfRefitTreelet *treelets, unsigned char *level,
+                             int *top, int *top_seg, SvgfRefitPlanInfo *info);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,733 @@
+"""The animated resident scene (include/svgf.h row f15: svgf_scene_enable_pose / svgf_scene_pose / svgf_scene_read / svgf_pose_rigid /
+svgf_bvh_refit_plan_host).
+
+The yardstick is tests/scene_pose_model.py (numpy float32, the header's arithmetic) and, for frames, tests/scene_model.py and
+svgf_scene_render_mesh fed the model's posed arrays.  Row f14's contract stands - the frame is a gated brute force that every tree
+reproduces - so a refitted tree must draw the frame of the posed triangles, and everything here is compared on bits (NaNs in the same
+place count as equal: an x86 host and the GPU give a NaN they create different sign and payload bits, which no model can follow).
+Both sides perform the same float32 operations in the same order without contraction: there is no tolerance to choose.  The frame
+comparisons carry test_scene_model.cap(W, H) as their allowance, as every frame comparison of the scene producer does (expected: 0).
+
+svgf_pose_rigid's bound, 8 * 2^-24 * (1 + |t|_inf) per entry of xf o inv - I (evaluated in float64 from the float32 tables): each of
+the 24 values is one rounding of a double result of magnitude at most max(1, sqrt(3) |t|_inf), which gives about 5.5 * 2^-24 |t|_inf
+on the translation column and 2 * 2^-24 on the linear block.
+
+Node counts: a tree whose inner nodes all have two children has an odd number of nodes, so "trees of CAP - 1, CAP and CAP + 1 nodes"
+are realised as trees of 1023 and 1025 nodes at cap 1024 and as a 1023-node tree at caps 1022, 1023 and 1024.
+
+bunny: frames against svgf_scene_render_mesh only, as in test_resident_scene.py (the numpy frame over 4 968 triangles is slow).
+"""
+import ctypes
+import functools
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import resident_scene_model as rm
+import scene_model as sm
+import scene_pose_model as pm
+import test_resident_scene as trs
+import test_scene_model as tsm
+from conftest import ROOT
+from test_scene_model import FRAME, SEED, cap, counts
+
+F = np.float32
+CAP = 1024
+BUILDS = trs.BUILDS
+POSES = ("identity", "translate", "turn9", "skew170")
+SET_NAMES = ("one", "copies300", "zero_area257", "huge_over_500", "line4096")
+STATE_INPUTS = ("A", "room", "bunny") + SET_NAMES
+FRAME_INPUTS = ("A", "room", "bunny", "F_cube", "F_sphere")
+
+
+def same_bits(a, b):
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    if a.shape != b.shape or a.dtype != b.dtype:
+        return False
+    if a.dtype.kind != "f":
+        return bool(np.array_equal(a, b))
+    na, nb = np.isnan(a), np.isnan(b)
+    return bool(np.array_equal(na, nb) and np.array_equal(a.view(np.uint32)[~na], b.view(np.uint32)[~nb]))
+
+
+# ---- inputs ------------------------------------------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def _input(name):
+    """(scene dict, W, H, n_objects).  Triangle sets get ids i % 3, one id of -1 and one beyond the table, under scene A's camera."""
+    if name in ("room", "bunny"):
+        s, W, H = trs._recorded(name, 0)
+        return s, W, H, min(int(np.max(s["tri_ids"])) + 1, 1024)
+    if name in SET_NAMES:
+        tris = trs._tri_set(name)
+        n = len(tris)
+        ids = (np.arange(n) % 3).astype(np.int32)
+        if n >= 3:
+            ids[n // 2], ids[n // 3] = -1, 7
+        s = dict(cam=tsm._scene("A")["cam"], geoms=tsm._scene("A")["geoms"], geom_ids=None, tris=tris, tri_ids=ids, tri_albedo=tsm._colours(n, 15),
+                 tri_tex=None, textures=None, light=(1.0, 3.0, 4.0))
+        return s, 67, 41, 3
+    s = tsm._scene(name)
+    return s, 67, 41, (16 if name == "A" else 3)       # A: ids 10..17, so 16 and 17 lie beyond the table
+
+
+@functools.lru_cache(maxsize=None)
+def _pivot(name):
+    s = _input(name)[0]
+    return tuple(float(v) for v in np.asarray(s["tris"], F).reshape(-1, 8)[:, 0:3].mean(axis=0).astype(F))
+
+
+@functools.lru_cache(maxsize=None)
+def _table(name, pose):
+    """The pose table of an input: every object the named pose, but every third (k % 3 == 2) the identity."""
+    import __graft_entry__ as ge
+    B = ge.load_package().binding
+    n = _input(name)[3]
+    t = B.pose_identity(n)
+    if pose == "translate":
+        p = B.pose_rigid((0, 1, 0), 0.0, (0, 0, 0), (0.25, -0.125, 0.5))
+    elif pose == "turn9":           # the turning block of test_object_motion.py: 9 degrees about y and a slide in x
+        p = B.pose_rigid((0, 1, 0), np.deg2rad(9.0), _pivot(name), (0.25, 0, 0))
+    elif pose == "skew170":
+        p = B.pose_rigid((0.3, -0.5, 0.8), np.deg2rad(170.0), _pivot(name), (0.125, 0.0625, -0.25))
+    else:
+        return t
+    for k in range(n):
+        if k % 3 != 2:
+            t[k] = p
+    return t
+
+
+@functools.lru_cache(maxsize=None)
+def _posed(name, pose):
+    return pm.posed_scene(_input(name)[0], _table(name, pose))
+
+
+@functools.lru_cache(maxsize=None)
+def _posed_model(name, pose, W, H):
+    s = _posed(name, pose)
+    col, gb = sm.render(W, H, FRAME, s["cam"], s["geoms"], s["geom_ids"], s["tris"], s["tri_ids"], s["tri_albedo"], s["tri_tex"], s["textures"],
+                        s["light"], seed=SEED)
+    col.setflags(write=False); gb.setflags(write=False)
+    return col, gb
+
+
+def _hand_made():
+    return {"chain48": pm.chain(48), "perfect_2cap-1": pm.balanced(CAP), "1023_nodes": pm.balanced(512), "1025_nodes": pm.balanced(513),
+            "single_leaf": pm.tree(1, None), "mixed_1025": pm.tree(513, lambda n: n - 1 if n <= 40 else (n + 1) // 2)}
+
+
+# ---- CPU 1: the plan -------------------------------------------------------------------------------------------------------------------
+def _check_plan(pkg, nodes, order, cap_, lo, hi, what):
+    plan = pkg.bvh_refit_plan_host(nodes, cap_)
+    n = len(nodes)
+    parent, size = np.full(n, -1), np.ones(n, int)
+    for k in range(n):
+        if nodes[k]["count"] == 0:
+            parent[int(nodes[k]["first"])] = parent[int(nodes[k]["first"]) + 1] = k
+    for k in range(n - 1, 0, -1):
+        size[parent[k]] += size[k]
+    owner = np.zeros(n, int)
+    roots = set()
+    for t in plan["treelets"]:
+        r, b, c = int(t["root"]), int(t["begin"]), int(t["count"])
+        assert c + 1 == size[r] <= cap_, f"{what}: treelet {r} is not a whole subtree of at most cap nodes"
+        assert r == 0 or size[parent[r]] > cap_, f"{what}: treelet {r} could be larger"
+        members = [r] + list(range(b, b + c))
+        assert sorted(members) == sorted(_subtree(nodes, r)), f"{what}: treelet {r} is not its root plus one range"
+        owner[members] += 1
+        roots.add(r)
+        inner = [plan["level"][g] for g in members if nodes[g]["count"] == 0]
+        assert int(t["levels"]) == (max(inner) + 1 if inner else 0)
+    seg = plan["top_seg"]
+    assert seg[0] == 0 and seg[-1] == len(plan["top"]) and (np.diff(seg) > 0).all()
+    done = set()
+    for s_ in range(len(seg) - 1):
+        now = [int(g) for g in plan["top"][seg[s_]:seg[s_ + 1]]]
+        for g in now:
+            owner[g] += 1
+            a = int(nodes[g]["first"])
+            assert nodes[g]["count"] == 0 and all(c in roots or c in done for c in (a, a + 1)), f"{what}: top node {g} before its children"
+        done.update(now)
+    assert (owner == 1).all(), f"{what}: a node lies in no or in two parts of the plan"
+    if n == 1:
+        assert len(plan["treelets"]) == 1 and plan["treelets"][0]["levels"] == 0 and len(plan["top"]) == 0
+    if n <= cap_:
+        assert len(plan["treelets"]) == 1 and len(plan["top"]) == 0
+    nlo, nhi = pm.replay_plan(plan, nodes, order, lo, hi)
+    mlo, mhi = pm.node_boxes(nodes, order, lo, hi)
+    assert same_bits(nlo, mlo) and same_bits(nhi, mhi), f"{what}: the replayed plan's boxes differ from the model's"
+    return plan
+
+
+def _subtree(nodes, k):
+    out, todo = [], [k]
+    while todo:
+        g = todo.pop()
+        out.append(g)
+        if nodes[g]["count"] == 0:
+            todo += [int(nodes[g]["first"]), int(nodes[g]["first"]) + 1]
+    return out
+
+
+@pytest.mark.parametrize("name", [n for n in trs.TRI_SETS if n != "none"])
+def test_plan_invariants_on_builder_trees(pkg, name):
+    tris = trs._tri_set(name)
+    lo, hi = rm.padded_boxes(tris)
+    for ml, sp in BUILDS:
+        nodes, order, _ = pkg.bvh_build_host(tris, ml, sp)
+        for cap_ in (CAP, 16) if len(nodes) < 3000 else (CAP,):
+            plan = _check_plan(pkg, nodes, order, cap_, lo, hi, f"{name} leaf {ml} split {sp} cap {cap_}")
+        print(f"{name} leaf {ml} split {sp}: {len(nodes)} nodes, {len(plan['treelets'])} treelets, {len(plan['top'])} top nodes in {len(plan['top_seg']) - 1} depths")
+    assert len(pkg.bvh_refit_plan_host(np.zeros(0, pkg.binding.BVH_NODE_DTYPE))["treelets"]) == 0       # the scene without triangles
+
+
+def test_plan_invariants_on_hand_made_trees(pkg):
+    rng = np.random.default_rng(15)
+    for what, (nodes, order) in _hand_made().items():
+        n = len(order)
+        lo = rng.uniform(-1, 1, (n, 3)).astype(F)
+        hi = (lo + rng.uniform(0, 1, (n, 3)).astype(F)).astype(F)
+        lo[n // 2], hi[n // 3] = np.nan, np.inf
+        caps = (CAP, 1, 3, 7) + ((1022, 1023) if what == "1023_nodes" else ())
+        for cap_ in caps:
+            plan = _check_plan(pkg, nodes, order, cap_, lo, hi, f"{what} cap {cap_}")
+        print(f"{what}: {len(nodes)} nodes; cap 7: {len(plan['treelets'])} treelets, {len(plan['top'])} top nodes")
+    big = pkg.bvh_refit_plan_host(_hand_made()["perfect_2cap-1"][0], CAP)
+    assert len(big["treelets"]) == 2 and list(big["top"]) == [0]
+    assert len(pkg.bvh_refit_plan_host(_hand_made()["1025_nodes"][0], CAP)["top"]) == 1
+    assert len(pkg.bvh_refit_plan_host(_hand_made()["chain48"][0], 3)["top_seg"]) - 1 == 47     # one top node per depth 0..46
+
+
+# ---- CPU 2: svgf_pose_rigid ------------------------------------------------------------------------------------------------------------
+def _h(m):
+    return np.vstack([np.asarray(m, np.float64).reshape(3, 4), [0, 0, 0, 1]])
+
+
+@pytest.mark.parametrize("axis,deg,pivot,tr", [((0, 1, 0), 9.0, (0.5, 0.25, -1.0), (1.0, 0, 0)), ((0.3, -0.5, 0.8), 170.0, (1.0, -2.0, 0.5), (0.125, 0.0625, -0.25)),
+                                               ((1, 1, 1), -123.0, (0, 0, 0), (40.0, -7.5, 100.0)), ((0, 0, 2), 360.0 * 3 + 1, (2.0, 2.0, 2.0), (0, 0, 0))])
+def test_pose_rigid_inverse_and_pivot(pkg, axis, deg, pivot, tr):
+    p = pkg.pose_rigid(axis, np.deg2rad(deg), pivot, tr)
+    X, I = _h(p["xf"]), _h(p["inv"])
+    bound = 8 * 2.0 ** -24 * (1 + np.abs(X[:3, 3]).max())
+    e1, e2 = np.abs(X @ I - np.eye(4)).max(), np.abs(I @ X - np.eye(4)).max()
+    fixed = np.abs(X @ np.array(pivot + (1,), np.float64) - np.array([pivot[k] + tr[k] for k in range(3)] + [1], np.float64)).max()
+    print(f"axis {axis} {deg} deg: |xf o inv - I| {e1:.3e}, |inv o xf - I| {e2:.3e}, pivot moves off by {fixed:.3e}; bound {bound:.3e}")
+    assert e1 <= bound and e2 <= bound and fixed <= bound
+
+
+def test_pose_rigid_angle_zero_is_the_exact_identity_and_errors(pkg):
+    B = pkg.binding
+    for axis in ((0, 1, 0), (0.3, -0.5, 0.8), (-1, -1, -1)):
+        p = B.pose_rigid(axis, 0.0, (0.5, -3.0, 2.0), (0, 0, 0))
+        assert p.tobytes() == B.pose_identity(1)[0].tobytes(), axis
+    lib = pkg.load_library()
+    v3 = lambda *v: (ctypes.c_float * 3)(*v)      # noqa: E731
+    out = np.zeros(1, B.SCENE_POSE_DTYPE)
+    ok = (v3(0, 1, 0), 0.5, v3(0, 0, 0), v3(0, 0, 0), out.ctypes.data)
+    assert lib.svgf_pose_rigid(*ok) == 0
+    assert lib.svgf_pose_rigid(v3(0, 0, 0), *ok[1:]) == -1
+    for bad in (np.nan, np.inf):
+        assert lib.svgf_pose_rigid(v3(bad, 1, 0), *ok[1:]) == -1 and lib.svgf_pose_rigid(ok[0], bad, *ok[2:]) == -1
+        assert lib.svgf_pose_rigid(ok[0], 0.5, v3(0, bad, 0), *ok[3:]) == -1 and lib.svgf_pose_rigid(*ok[:3], v3(0, 0, bad), ok[4]) == -1
+    assert lib.svgf_pose_rigid(None, *ok[1:]) == -1 and lib.svgf_pose_rigid(*ok[:4], None) == -1
+
+
+# ---- CPU 3: the gate precondition of every posed input the GPU part draws ----------------------------------------------------------------
+@pytest.mark.parametrize("pose", POSES)
+@pytest.mark.parametrize("name", FRAME_INPUTS + ("copies300",))
+def test_gate_precondition_of_posed_inputs(name, pose):
+    s, W, H, _ = _input(name)
+    r = rm.gate_report(W, H, s["cam"], _posed(name, pose)["tris"])
+    print(f"{name} {pose} {W}x{H}: {int((r['best'] >= 0).sum())} pixels with a triangle winner, {r['winner_fails']} winners fail the gate")
+    assert r["winner_fails"] == 0
+    if pose in ("identity", "translate") and name in ("A", "room", "bunny", "copies300"):
+        assert (r["best"] >= 0).sum() > cap(W, H), "the input shows no triangles"
+
+
+# ---- CPU 4: argument errors that need no device ------------------------------------------------------------------------------------------
+def test_argument_errors_without_a_device(pkg):
+    lib, B = pkg.load_library(), pkg.binding
+    assert lib.svgf_scene_enable_pose(None, 4) == -1
+    assert lib.svgf_scene_pose(None, 16, 4, None, None) == -1
+    assert lib.svgf_scene_read(None, 0, None, 0) == -1
+    nodes, _ = pm.balanced(8)
+    n, room = len(nodes), 256
+    tl, lv, top = np.zeros(room, B.REFIT_TREELET_DTYPE), np.zeros(room, np.uint8), np.zeros(room, np.int32)
+    seg, info = np.zeros(B.SCENE_MAX_DEPTH + 2, np.int32), np.zeros(4, np.int32)
+
+    def plan(nd, n_=None, cap_=4, tl_=tl, info_=info):
+        return lib.svgf_bvh_refit_plan_host(nd.ctypes.data if nd is not None else None, (len(nd) if nd is not None else n) if n_ is None else n_, cap_,
+                                            tl_.ctypes.data if tl_ is not None else None, lv.ctypes.data, top.ctypes.data, seg.ctypes.data,
+                                            info_.ctypes.data if info_ is not None else None)
+    assert plan(nodes) == 0 and info[0] > 1 and info[1] > 0
+    assert plan(nodes, cap_=0) == -1 and plan(nodes, n_=-1) == -1 and plan(None) == -1 and plan(nodes, tl_=None) == -1 and plan(nodes, info_=None) == -1
+    bad = nodes.copy(); bad[1]["first"] = 1                         # a child at its parent
+    assert plan(bad) == -1
+    bad = nodes.copy(); bad[2]["first"] = bad[1]["first"]           # two parents
+    assert plan(bad) == -1
+    bad = nodes.copy(); bad[0]["first"] = n - 1                     # a child pair that runs off the end
+    assert plan(bad) == -1
+    bad = nodes.copy(); bad[3]["count"] = -1
+    assert plan(bad) == -1
+    assert plan(pm.chain(48)[0]) == 0 and plan(pm.chain(49)[0]) == -5      # deeper than SVGF_SCENE_MAX_DEPTH
+    swapped = nodes.copy()                                          # a legal tree, but not the builder's layout: the root's children swapped
+    a = int(swapped[0]["first"])
+    swapped[[a, a + 1]] = swapped[[a + 1, a]]
+    assert plan(swapped) == -5
+
+
+# ---- CPU 5: the plan under AddressSanitizer / UBSan, as a stand-alone program -----------------------------------------------------------
+def test_refit_plan_native_program_under_sanitizers(tmp_path):
+    import shutil
+    cxx = shutil.which("g++") or shutil.which("clang++") or shutil.which("c++")
+    assert cxx, "no host C++ compiler"
+    exe = str(tmp_path / "refit_plan_main")
+    src = [os.path.join(ROOT, "tests", "native", "refit_plan_main.cpp"), os.path.join(ROOT, "cuda-path-tracer-denoising_amd", "csrc", "svgf_bvh_build.cpp")]
+    r = subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I", os.path.join(ROOT, "include")] + src +
+                       ["-o", exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    assert r.returncode == 0, r.stdout
+    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=120)
+    print(r.stdout)
+    assert r.returncode == 0 and "all plans hold" in r.stdout, r.stdout
+
+
+# ---- GPU helpers -------------------------------------------------------------------------------------------------------------------------
+def _dev(a):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).cuda()
+
+
+def _motion_buffer(n):
+    import torch
+    return torch.full((n, 12), float("nan"), dtype=torch.float32, device="cuda")
+
+
+def _assert_state(pkg, scene, s, table, nodes, order, what, kinds=(0, 1, 2, 3, 5)):
+    m = pm.state(s, table, nodes, order)
+    n = len(m["tris"])
+    if 0 in kinds:
+        assert same_bits(scene.read(0), m["tris"]), f"{what}: triangles"
+    if 1 in kinds:
+        b = scene.read(1)
+        assert same_bits(b["lo"], m["lo"]) and same_bits(b["hi"], m["hi"]), f"{what}: triangle boxes"
+        assert np.array_equal(b["first"], np.arange(n)) and (b["count"] == 1).all()
+    if 2 in kinds:
+        nd = scene.read(2)
+        assert same_bits(nd["lo"], m["nlo"]) and same_bits(nd["hi"], m["nhi"]), f"{what}: node boxes"
+        assert np.array_equal(nd["first"], nodes["first"]) and np.array_equal(nd["count"], nodes["count"]), f"{what}: topology"
+    if 3 in kinds:
+        g = scene.read(3)
+        for f in g.dtype.names:
+            assert same_bits(g[f], m["geoms"][f]), f"{what}: primitives, {f}"
+    if 5 in kinds:
+        h = scene.read(5)
+        assert same_bits(h["xf"], table["xf"]) and same_bits(h["inv"], table["inv"]), f"{what}: held table"
+
+
+def _graph_api():
+    from temporal_harness import _hip
+    hip = _hip()
+    vp = ctypes.c_void_p
+    hip.hipStreamBeginCapture.argtypes = [vp, ctypes.c_int]
+    hip.hipStreamEndCapture.argtypes = [vp, ctypes.POINTER(vp)]
+    hip.hipGraphInstantiate.argtypes = [ctypes.POINTER(vp), vp, vp, vp, ctypes.c_size_t]
+    hip.hipGraphLaunch.argtypes = [vp, vp]
+    hip.hipGraphExecDestroy.argtypes = [vp]
+    hip.hipGraphDestroy.argtypes = [vp]
+    hip.hipGraphGetNodes.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_size_t)]
+    hip.hipGraphNodeGetType.argtypes = [vp, ctypes.POINTER(ctypes.c_int)]
+    return hip
+
+
+def _node_types(hip, graph):
+    n = ctypes.c_size_t(0)
+    assert hip.hipGraphGetNodes(graph, None, ctypes.byref(n)) == 0
+    arr = (ctypes.c_void_p * max(n.value, 1))()
+    assert hip.hipGraphGetNodes(graph, arr, ctypes.byref(n)) == 0
+    types = []
+    for k in range(n.value):
+        t = ctypes.c_int(-1)
+        assert hip.hipGraphNodeGetType(arr[k], ctypes.byref(t)) == 0
+        types.append(t.value)
+    return types        # hipGraphNodeTypeKernel 0, Memcpy 1, Memset 2
+
+
+def _draw_planar(pkg, scene, den, W, H, s, frame, seed):
+    import torch
+    from temporal_harness import _hip
+    planes = den.planar_gbuffer()
+    rgb = torch.empty((H, W, 3), dtype=torch.float32, device="cuda")
+    scene.draw_planar(rgb, planes, W, H, s["cam"], s["light"], frame, seed=seed)
+    torch.cuda.synchronize()
+    hip = _hip()
+    hip.hipMemcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
+    gb = np.zeros((H, W), dtype=pkg.synth.GBUFFER_DTYPE)
+    for field, ptr in (("normal", planes.normal), ("position", planes.position), ("albedo", planes.albedo), ("geomId", planes.geom_id)):
+        host = np.zeros((H, W, 3) if field != "geomId" else (H, W), F if field != "geomId" else np.int32)
+        assert hip.hipMemcpy(host.ctypes.data, ptr, host.nbytes, 2) == 0
+        gb[field] = host
+    gb["ialbedo"] = F(1.0)
+    return rgb.cpu().numpy(), gb
+
+
+# ---- GPU 6: state on bits ----------------------------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", STATE_INPUTS)
+def test_state_after_a_pose_equals_the_model_on_bits(pkg, name):
+    s, W, H, n_obj = _input(name)
+    for ml, sp in BUILDS:
+        nodes, order, _ = pkg.bvh_build_host(s["tris"], ml, sp)
+        scene = trs._create(pkg, s, ml, sp)
+        scene.enable_pose(n_obj)
+        assert np.array_equal(scene.read(4), order), "order"
+        for pose in POSES:
+            table = _table(name, pose)
+            scene.pose(_dev(table))
+            _assert_state(pkg, scene, s, table, nodes, order, f"{name} leaf {ml} split {sp} {pose}")
+        assert np.array_equal(scene.read(4), order), "order after the poses"
+        scene.free()
+    if name == "line4096":
+        nodes = pkg.bvh_build_host(s["tris"], 1, 0)[0]
+        plan = pkg.bvh_refit_plan_host(nodes)
+        assert len(nodes) == 8191 and len(plan["treelets"]) > 2 and len(plan["top"]) > 1, "this input should cross the treelet size"
+
+
+# ---- GPU 7: frames on bits ---------------------------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+@pytest.mark.parametrize("pose", POSES)
+@pytest.mark.parametrize("name", FRAME_INPUTS)
+def test_posed_frame_equals_model_and_mesh_path(pkg, name, pose):
+    s, W, H, n_obj = _input(name)
+    ps = _posed(name, pose)
+    scene = trs._create(pkg, s)
+    scene.enable_pose(n_obj)
+    scene.pose(_dev(_table(name, pose)))
+    got = trs._draw(pkg, scene, W, H, s, FRAME, SEED)
+    den = pkg.Denoiser(W, H, 0)
+    planar = _draw_planar(pkg, scene, den, W, H, s, FRAME, SEED)
+    den.free(); scene.free()
+    mesh = tsm._device(pkg, W, H, ps, FRAME, SEED)
+    trs._same(got, mesh, W, H, f"{name} {pose}: draw vs svgf_scene_render_mesh on the model's arrays")
+    trs._same(planar, got, W, H, f"{name} {pose}: draw_planar vs draw")
+    if name != "bunny":
+        trs._same(got, _posed_model(name, pose, W, H), W, H, f"{name} {pose}: draw vs model")
+    if pose in ("identity", "translate"):
+        assert (got[1]["geomId"] >= 0).sum() > cap(W, H), "the frame shows nothing"
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["A", "room"])
+def test_every_build_draws_the_same_posed_frame(pkg, name):
+    s, W, H, n_obj = _input(name)
+    frames = {}
+    for ml, sp in BUILDS:
+        scene = trs._create(pkg, s, ml, sp)
+        scene.enable_pose(n_obj)
+        for pose in POSES:
+            scene.pose(_dev(_table(name, pose)))
+            frames[(ml, sp, pose)] = trs._draw(pkg, scene, W, H, s, FRAME, SEED)
+        scene.free()
+    for pose in POSES:
+        for ml, sp in BUILDS[1:]:
+            c = counts(frames[(ml, sp, pose)], frames[BUILDS[0] + (pose,)])
+            assert not any(c.values()), f"{pose}: leaf {ml} split {sp} differs from leaf 1 split 0: {c}"
+    assert any(counts(frames[BUILDS[0] + ("turn9",)], frames[BUILDS[0] + ("identity",)]).values()), "the pose should move the picture"
+
+
+# ---- GPU 8: lifecycle ----------------------------------------------------------------------------------------------------------------------
+def _all_state(scene):
+    return [scene.read(k).tobytes() for k in (0, 1, 2, 3, 5)]
+
+
+@pytest.mark.gpu
+def test_lifecycle(pkg):
+    s, W, H, n_obj = _input("F_cube")
+    static = trs._create(pkg, s)
+    created = trs._draw(pkg, static, W, H, s, FRAME, SEED)
+    static_state = [static.read(k).tobytes() for k in (0, 1, 2, 3, 4)]
+    info = static.info()
+    scene = trs._create(pkg, s)
+    assert scene.info() == info
+    scene.enable_pose(n_obj)
+    enabled = [scene.read(k).tobytes() for k in (0, 1, 2, 3, 4)]
+    assert enabled == static_state, "the posed copies start as bit copies of the rest state"
+    assert scene.info()["device_bytes"] > info["device_bytes"]
+    scene.enable_pose(n_obj)                                            # twice: a no-op
+    assert [scene.read(k).tobytes() for k in (0, 1, 2, 3, 4)] == enabled
+    assert scene.lib.svgf_scene_enable_pose(scene.h, n_obj + 1) == -1
+    assert not any(counts(trs._draw(pkg, scene, W, H, s, FRAME, SEED), created).values()), "enable_pose alone changes the frame"
+    a, b = _dev(_table("F_cube", "turn9")), _dev(_table("F_cube", "skew170"))
+    scene.pose(a)
+    once = _all_state(scene)
+    scene.pose(a)
+    assert _all_state(scene) == once, "the same table twice leaves other bytes"
+    scene.pose(b)
+    fresh = trs._create(pkg, s)
+    fresh.enable_pose(n_obj)
+    fresh.pose(b)
+    assert _all_state(scene) == _all_state(fresh), "pose A then B differs from a fresh scene posed B"
+    assert not any(counts(trs._draw(pkg, scene, W, H, s, FRAME, SEED), trs._draw(pkg, fresh, W, H, s, FRAME, SEED)).values())
+    scene.pose(_dev(_table("F_cube", "identity")))
+    assert not any(counts(trs._draw(pkg, scene, W, H, s, FRAME, SEED), created).values()), "the identity pose does not restore the created frame"
+    # (the frame, not every byte of the state: the identity goes through the arithmetic, and (1 * -0 + 0 * y) + 0 * z is +0)
+    assert [static.read(k).tobytes() for k in (0, 1, 2, 3, 4)] == static_state and static.info() == info, "the static scene moved"
+    assert not any(counts(trs._draw(pkg, static, W, H, s, FRAME, SEED), created).values())
+    for sc in (static, scene, fresh):
+        sc.free()
+
+
+# ---- GPU 9: the motion table ---------------------------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+def test_motion_table_rows(pkg):
+    import torch
+    B = pkg.binding
+    s, W, H, n_obj = _input("A")
+    scene = trs._create(pkg, s)
+    scene.enable_pose(n_obj)
+    held = B.pose_identity(n_obj)
+    out = _motion_buffer(n_obj + 1)                                     # one row more: the call must not write past n_objects
+    for f, pose in enumerate(("turn9", "skew170", "translate")):
+        table = _table("A", pose)
+        scene.pose(_dev(table), out)
+        torch.cuda.synchronize()
+        rows = out.cpu().numpy()
+        want = pm.motion_rows(held, table)
+        assert same_bits(rows[:n_obj], want), f"call {f}: the motion rows differ from held.xf o pose.inv"
+        assert np.isnan(rows[n_obj]).all()
+        if f == 0:
+            assert same_bits(want, pm.compose(B.pose_identity(n_obj)["xf"], table["inv"]))
+        held = table
+    out.fill_(float("nan"))
+    last = _table("A", "turn9")
+    scene.pose(_dev(last), None)                                        # NULL: nothing written, held still follows
+    torch.cuda.synchronize()
+    assert np.isnan(out.cpu().numpy()).all()
+    h = scene.read(5)
+    assert same_bits(h["xf"], last["xf"]) and same_bits(h["inv"], last["inv"])
+    scene.free()
+
+
+# ---- GPU 10: stream behaviour --------------------------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+def test_eight_pose_and_draw_pairs_queued_without_host_waits(pkg):
+    import torch
+    s, W, H, n_obj = _input("A")
+    seq = [POSES[f % 4] for f in range(8)]
+    tables = [_dev(_table("A", p)) for p in seq]
+    motions = [_motion_buffer(n_obj) for _ in seq]
+    scene = trs._create(pkg, s)
+    scene.enable_pose(n_obj)
+    st = torch.cuda.Stream()
+    torch.cuda.synchronize()
+    bufs = [trs._buffers(W, H) for _ in seq]
+    for f, (rgb, gbt) in enumerate(bufs):
+        scene.pose(tables[f], motions[f], stream=st)
+        scene.draw(rgb, gbt, W, H, s["cam"], s["light"], f, seed=SEED, stream=st)
+    st.synchronize()
+    queued = [(trs._host(pkg, rgb, gbt, W, H), m.cpu().numpy()) for (rgb, gbt), m in zip(bufs, motions)]
+    scene.free()
+    scene = trs._create(pkg, s)
+    scene.enable_pose(n_obj)
+    for f, p in enumerate(seq):
+        m = _motion_buffer(n_obj)
+        scene.pose(tables[f], m)
+        torch.cuda.synchronize()
+        alone = trs._draw(pkg, scene, W, H, s, f, SEED)
+        assert not any(counts(queued[f][0], alone).values()), f"frame {f}"
+        assert same_bits(queued[f][1], m.cpu().numpy()), f"motion rows, frame {f}"
+    scene.free()
+
+
+@pytest.mark.gpu
+def test_a_captured_pose_and_draw_replays_with_the_table_of_the_moment(pkg):
+    import torch
+    hip = _graph_api()
+    s, W, H, n_obj = _input("A")
+    scene = trs._create(pkg, s)
+    scene.enable_pose(n_obj)
+    st = torch.cuda.Stream()
+    t1, t2 = _table("A", "turn9"), _table("A", "skew170")
+    table, motion = _dev(t1), _motion_buffer(n_obj)
+    rgb, gbt = trs._buffers(W, H)
+    torch.cuda.synchronize()
+    scene.pose(table, motion, stream=st)                                # eager first: a first launch may set kernel attributes
+    scene.draw(rgb, gbt, W, H, s["cam"], s["light"], FRAME, seed=SEED, stream=st)
+    scene.pose(_dev(pkg.binding.pose_identity(n_obj)), None, stream=st)         # held back to the identity
+    st.synchronize()
+    graph, gexec = ctypes.c_void_p(), ctypes.c_void_p()
+    assert hip.hipStreamBeginCapture(st.cuda_stream, 2) == 0
+    scene.pose(table, motion, stream=st)
+    scene.draw(rgb, gbt, W, H, s["cam"], s["light"], FRAME, seed=SEED, stream=st)
+    assert hip.hipStreamEndCapture(st.cuda_stream, ctypes.byref(graph)) == 0 and graph.value
+    assert hip.hipGraphInstantiate(ctypes.byref(gexec), graph, None, None, 0) == 0
+    got = []
+    for t in (t1, t2):
+        with torch.cuda.stream(st):
+            table.copy_(_dev(t)); rgb.zero_(); gbt.zero_()
+        assert hip.hipGraphLaunch(gexec, st.cuda_stream) == 0
+        st.synchronize()
+        got.append((trs._host(pkg, rgb, gbt, W, H), motion.cpu().numpy()))
+    hip.hipGraphExecDestroy(gexec); hip.hipGraphDestroy(graph)
+    scene.free()
+    for k, pose in enumerate(("turn9", "skew170")):
+        trs._same(got[k][0], _posed_model("A", pose, W, H), W, H, f"replay {k} vs model")
+    assert same_bits(got[0][1], pm.motion_rows(pkg.binding.pose_identity(n_obj), t1))
+    assert same_bits(got[1][1], pm.motion_rows(t1, t2)), "the second replay's motion rows should use the first replay's pose"
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name,ml", [("line4096", 1), ("one", 4)])
+def test_a_captured_pose_is_at_most_three_kernel_nodes(pkg, name, ml):
+    import torch
+    hip = _graph_api()
+    s, W, H, n_obj = _input(name)
+    scene = trs._create(pkg, s, ml, 0)
+    scene.enable_pose(n_obj)
+    st = torch.cuda.Stream()
+    table, motion = _dev(_table(name, "turn9")), _motion_buffer(n_obj)
+    torch.cuda.synchronize()
+    scene.pose(table, motion, stream=st)
+    st.synchronize()
+    graph = ctypes.c_void_p()
+    assert hip.hipStreamBeginCapture(st.cuda_stream, 2) == 0
+    scene.pose(table, motion, stream=st)
+    assert hip.hipStreamEndCapture(st.cuda_stream, ctypes.byref(graph)) == 0 and graph.value
+    types = _node_types(hip, graph)
+    hip.hipGraphDestroy(graph)
+    scene.free()
+    print(f"{name}: captured pose = node types {types}")
+    assert 1 <= len(types) <= 3 and all(t == 0 for t in types), types
+    assert len(types) == (3 if name == "line4096" else 2)
+
+
+# ---- GPU 11: a table that is not finite ------------------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+def test_non_finite_rows(pkg):
+    s, W, H, n_obj = _input("copies300")
+    table = _table("copies300", "translate").copy()
+    table[2] = table[0]                                                 # object 2 stays finite (and moved)
+    table["xf"][0], table["inv"][0] = np.nan, np.nan
+    table["xf"][1], table["inv"][1] = np.inf, np.inf
+    nodes, order, _ = pkg.bvh_build_host(s["tris"], 4, 0)
+    scene = trs._create(pkg, s, 4, 0)
+    scene.enable_pose(n_obj)
+    scene.pose(_dev(table))
+    _assert_state(pkg, scene, s, table, nodes, order, "non-finite table", kinds=(0, 1, 2))
+    got = trs._draw(pkg, scene, W, H, s, FRAME, SEED)                   # completes
+    scene.free()
+    ps = pm.posed_scene(s, table)
+    ref = sm.render(W, H, FRAME, ps["cam"], ps["geoms"], ps["geom_ids"], ps["tris"], ps["tri_ids"], ps["tri_albedo"], None, None, ps["light"], seed=SEED)
+    finite = ref[1]["geomId"] == 2
+    assert finite.sum() > cap(W, H), "the finite object should be in the picture"
+    for f in tsm.FIELDS:
+        assert not tsm.differing(got[1][f], ref[1][f])[finite].any(), f
+    assert not tsm.differing(got[0], ref[0])[finite].any(), "colour"
+
+
+# ---- GPU 12: end to end - the turning, sliding block -----------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def _block_inputs():
+    """box_room as a resident scene of primitives; six frames, the block 9 degrees further about y through its centre and 1.0
+    further in x per frame (test_object_motion.py's motion), as pose tables over the rest state."""
+    import __graft_entry__ as ge
+    from temporal_harness import BLOCK, SCENE
+    pkg = ge.load_package()
+    sc = pkg.scene.parse_scene(open(SCENE).read())
+    cam = pkg.scene.camera_for_frame(sc, 0, False)
+    geoms = pkg.scene.geom_array(sc)
+    centre = tuple(float(v) for v in sc.objects[BLOCK]["trans"])
+    tables = []
+    for f in range(6):
+        t = pkg.binding.pose_identity(len(geoms))
+        t[BLOCK] = pkg.binding.pose_rigid((0, 1, 0), np.deg2rad(9.0 * f), centre, (1.0 * f, 0, 0))
+        tables.append(t)
+    s = dict(cam=cam, geoms=geoms, geom_ids=None, tris=None, tri_ids=None, tri_albedo=None, tri_tex=None, textures=None,
+             light=pkg.scene.light_position(geoms))
+    return s, tables
+
+
+@pytest.mark.gpu
+def test_turning_block_end_to_end(pkg, orc):
+    import torch
+    import temporal_model as tm
+    from temporal_harness import BLOCK, SIDE, assert_frames_equal, read_states, temporal_only
+    s, tables = _block_inputs()
+    W = H = SIDE
+    n = len(s["geoms"])
+    held, frames, motion = pkg.binding.pose_identity(n), [], []
+    for f, t in enumerate(tables):
+        ps = pm.posed_scene(s, t)
+        col, gb = sm.render(W, H, f, ps["cam"], ps["geoms"], None, None, None, None, None, None, ps["light"], seed=3)
+        frames.append((np.asarray(col, F).reshape(H, W, 3), gb.reshape(H, W)))
+        motion.append(pm.motion_rows(held, t))
+        held = t
+    M = orc.view_matrix(pkg, s["cam"])
+    want = {True: tm.run_sequence(frames, tables=motion, views=[M] * len(frames)), False: tm.run_sequence(frames, views=[M] * len(frames))}
+    p = temporal_only(pkg)
+    got = {}
+    for with_table in (True, False):
+        scene = trs._create(pkg, s)
+        scene.enable_pose(n)
+        den = pkg.Denoiser(W, H)
+        den.set_capture(True)
+        t_x = _motion_buffer(n)
+        if with_table:
+            den.set_object_motion(t_x)
+        rgb, gbt = trs._buffers(W, H)
+        out = torch.empty((H, W, 3), dtype=torch.float32, device="cuda")
+        got[with_table] = []
+        try:
+            for f, t in enumerate(tables):
+                scene.pose(_dev(t), t_x)
+                scene.draw(rgb, gbt, W, H, s["cam"], s["light"], f, seed=3)
+                den.denoise(out, rgb, gbt, s["cam"], p)
+                torch.cuda.synchronize()
+                assert same_bits(t_x.cpu().numpy(), motion[f]), f"motion table, frame {f}"
+                got[with_table].append(read_states(den))
+        finally:
+            den.free(); scene.free()
+        assert_frames_equal(got[with_table], want[with_table], "with the table" if with_table else "without the table")
+    # the block slides out of the picture over the six frames (216 pixels on frames 0..2, 33 on the last): every frame behind the
+    # first is held to the figures, and the frames together show enough of it
+    shown = 0
+    for f in range(1, len(frames)):
+        block = frames[f][1]["geomId"] == BLOCK
+        assert block.any()
+        shown += int(block.sum())
+        kept = float((got[True][f]["hlen"][block] >= 2).sum()) / float(block.sum())
+        lost = float((got[False][f]["hlen"][block] >= 2).sum()) / float(block.sum())
+        print(f"frame {f}: {int(block.sum())} block pixels, history >= 2 on {kept:.3f} with the table, {lost:.3f} without")
+        assert kept == 1.0 and lost == 0.0
+    assert shown > 150
+
+
+# ---- GPU 13: errors ------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+def test_errors_leave_the_scene_drawing_the_previous_frame(pkg):
+    import torch
+    s, W, H, n_obj = _input("A")
+    scene = trs._create(pkg, s)
+    lib = scene.lib
+    table, motion = _dev(_table("A", "turn9")), _motion_buffer(n_obj + 1)
+    assert lib.svgf_scene_enable_pose(scene.h, 0) == -1 and lib.svgf_scene_enable_pose(scene.h, 1025) == -1 and lib.svgf_scene_enable_pose(scene.h, -3) == -1
+    assert lib.svgf_scene_pose(scene.h, table.data_ptr(), n_obj, None, None) == -1, "a scene without svgf_scene_enable_pose"
+    assert lib.svgf_scene_read(scene.h, 5, None, 0) == -1 and lib.svgf_scene_read(scene.h, 6, None, 0) == -1 and lib.svgf_scene_read(scene.h, -1, None, 0) == -1
+    host = np.zeros(len(s["tris"]) * 24, F)
+    assert lib.svgf_scene_read(scene.h, 0, host.ctypes.data, host.nbytes - 4) == -1 and lib.svgf_scene_read(scene.h, 0, None, host.nbytes) == -1
+    assert lib.svgf_scene_read(scene.h, 0, host.ctypes.data, host.nbytes) == 0 and same_bits(host.reshape(-1, 3, 8), np.asarray(s["tris"], F))
+    scene.enable_pose(n_obj)
+    scene.pose(table, motion)
+    before, state = trs._draw(pkg, scene, W, H, s, FRAME, SEED), _all_state(scene)
+    other = _dev(_table("A", "skew170"))
+    pad = torch.zeros(24 * n_obj + 4, dtype=torch.float32, device="cuda")
+    for what, rc in (("NULL table", lib.svgf_scene_pose(scene.h, None, n_obj, None, None)),
+                     ("NULL scene", lib.svgf_scene_pose(None, other.data_ptr(), n_obj, None, None)),
+                     ("another n_objects", lib.svgf_scene_pose(scene.h, other.data_ptr(), n_obj - 1, None, None)),
+                     ("a misaligned table", lib.svgf_scene_pose(scene.h, pad.data_ptr() + 4, n_obj, None, None)),
+                     ("a misaligned motion table", lib.svgf_scene_pose(scene.h, other.data_ptr(), n_obj, motion.data_ptr() + 8, None))):
+        assert rc == -1, what
+        assert _all_state(scene) == state, what
+        assert not any(counts(trs._draw(pkg, scene, W, H, s, FRAME, SEED), before).values()), what
+    scene.free()
