@@ -44,10 +44,12 @@ EXPORTS = ["svgf_version", "svgf_params_default", "svgf_create", "svgf_destroy",
            "svgf_exposure_reset", "svgf_exposure_meter", "svgf_display_tonemap", "svgf_tonemap_srgb_table",
            "svgf_quality_state_bytes", "svgf_quality_windows", "svgf_quality_meter", "svgf_quality_read",
            "svgf_scene_create", "svgf_scene_destroy", "svgf_scene_info", "svgf_scene_draw", "svgf_scene_draw_planar", "svgf_bvh_build_host",
-           "svgf_scene_enable_pose", "svgf_scene_pose", "svgf_scene_read", "svgf_pose_rigid", "svgf_bvh_refit_plan_host"]
+           "svgf_scene_enable_pose", "svgf_scene_pose", "svgf_scene_read", "svgf_pose_rigid", "svgf_bvh_refit_plan_host",
+           "svgf_scene_draw_shadowed"]
 SCENE_MAX_DEPTH = 48
 SCENE_MAX_POSED = 1024
 SCENE_REFIT_CAP = 1024
+SCENE_MAX_SHADOW_SAMPLES = 64
 # svgf_scene_read kinds
 SCENE_READ_TRIS, SCENE_READ_TRI_BOXES, SCENE_READ_NODES, SCENE_READ_GEOMS, SCENE_READ_ORDER, SCENE_READ_HELD_POSE = 0, 1, 2, 3, 4, 5
 # SvgfScenePose / SvgfRefitTreelet (row f15)
@@ -138,6 +140,20 @@ class SvgfSceneBuildParams(C.Structure):
 class SvgfSceneInfo(C.Structure):
     _fields_ = [("n_geoms", C.c_int), ("n_tris", C.c_int), ("n_tex", C.c_int), ("n_nodes", C.c_int), ("n_leaves", C.c_int),
                 ("depth", C.c_int), ("max_leaf_tris", C.c_int), ("device_bytes", C.c_ulonglong)]
+
+
+class SvgfSceneLight(C.Structure):
+    """svgf_scene_draw_shadowed: a parallelogram light centre +- edge_u +- edge_v (both edges zero: a point light) and the number of
+    shadow rays per pixel and frame, 1..SCENE_MAX_SHADOW_SAMPLES."""
+    _fields_ = [("centre", C.c_float * 3), ("edge_u", C.c_float * 3), ("edge_v", C.c_float * 3), ("samples", C.c_int)]
+
+    @classmethod
+    def make(cls, centre, edge_u=(0, 0, 0), edge_v=(0, 0, 0), samples: int = 1):
+        l = cls()
+        for i in range(3):
+            l.centre[i], l.edge_u[i], l.edge_v[i] = float(centre[i]), float(edge_u[i]), float(edge_v[i])
+        l.samples = int(samples)
+        return l
 
 
 # SvgfBvhNode, 32 bytes: count > 0 a leaf over order[first : first + count], count == 0 an inner node with children first, first + 1
@@ -302,6 +318,8 @@ def load_library(path: str | None = None, experiments: bool = False):
     lib.svgf_scene_enable_pose.argtypes = [vp, ip]
     lib.svgf_scene_pose.argtypes = [vp, vp, ip, vp, vp]
     lib.svgf_scene_read.argtypes = [vp, ip, vp, C.c_ulonglong]
+    lib.svgf_scene_draw_shadowed.argtypes = [vp, vp, vp, C.POINTER(SvgfPlanarGBuffer), ip, ip, C.POINTER(SvgfCamera), C.POINTER(SvgfSynthParams),
+                                             C.POINTER(SvgfSceneLight), vp]
     lib.svgf_pose_rigid.argtypes = [C.POINTER(C.c_float), C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float), vp]
     lib.svgf_bvh_refit_plan_host.argtypes = [vp, ip, ip, vp, vp, vp, vp, vp]
     if path == LIB_PATH:
@@ -969,6 +987,23 @@ class Scene:
             raise SvgfError(f"svgf_scene_draw failed ({rc})")
 
     draw_planar = draw
+
+    def draw_shadowed(self, out_rgb, out_gbuffer, width: int, height: int, camera, light, frame: int, seed: int = 1, noise: float = 0.6,
+                      fireflies: float = 0.02, pixel_length=None, stream=None):
+        """svgf_scene_draw_shadowed (row f16): `light` is a SvgfSceneLight (SvgfSceneLight.make(centre, edge_u, edge_v, samples));
+        `out_gbuffer` AoS texels or a SvgfPlanarGBuffer.  One launch on `stream`; never waits."""
+        from . import synth as _synth
+        cam = camera if isinstance(camera, SvgfCamera) else SvgfCamera.from_dict(camera)
+        if pixel_length is None:
+            fovy = camera.get("fovy_deg", 45.0) if isinstance(camera, dict) else 45.0
+            pixel_length = _synth._pixel_length(width, height, fovy)
+        sp = SvgfSynthParams(int(frame), int(seed), float(noise), float(fireflies))
+        sp.pixel_length[0], sp.pixel_length[1] = float(pixel_length[0]), float(pixel_length[1])
+        planar = isinstance(out_gbuffer, SvgfPlanarGBuffer)
+        rc = self.lib.svgf_scene_draw_shadowed(self.h, _ptr(out_rgb), None if planar else _ptr(out_gbuffer), C.byref(out_gbuffer) if planar else None,
+                                               int(width), int(height), C.byref(cam), C.byref(sp), C.byref(light), _stream(stream))
+        if rc != SVGF_OK:
+            raise SvgfError(f"svgf_scene_draw_shadowed failed ({rc})")
 
     def enable_pose(self, n_objects: int):
         """svgf_scene_enable_pose: allocates the animation side (allocates and synchronises; not under capture)."""

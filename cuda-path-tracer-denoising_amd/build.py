@@ -86,11 +86,11 @@ def build_examples(force: bool = False) -> str:
     the denoised image, svgf_display_tonemap beside the plain pack) and examples/quality.cpp (svgf_quality_meter: PSNR / SSIM of the
     noisy and the denoised frame against the clean one, and of consecutive outputs) and examples/resident_scene.cpp (svgf_scene_create
     once, then svgf_scene_draw + svgf_denoise per frame) and examples/animated_scene.cpp (svgf_scene_pose with a motion table ahead of
-    each draw), through the C ABI -> examples/farm, examples/pipeline, examples/cadence, examples/upsample, examples/dynres,
-    examples/hdr_display, examples/quality, examples/resident_scene, examples/animated_scene, linked against the product library
+    each draw) and examples/shadowed_scene.cpp (svgf_scene_draw_shadowed: one shadow ray per pixel, denoised, against 64), through the C ABI -> examples/farm, examples/pipeline, examples/cadence, examples/upsample, examples/dynres,
+    examples/hdr_display, examples/quality, examples/resident_scene, examples/animated_scene, examples/shadowed_scene, linked against the product library
     in-tree."""
     out = ""
-    for name in ("pipeline", "farm", "cadence", "upsample", "dynres", "hdr_display", "quality", "resident_scene", "animated_scene"):
+    for name in ("pipeline", "farm", "cadence", "upsample", "dynres", "hdr_display", "quality", "resident_scene", "animated_scene", "shadowed_scene"):
         src = os.path.join(ROOT, "examples", name + ".cpp")
         out = os.path.join(ROOT, "examples", name)
         if not force and _newer(out, [src, os.path.join(ROOT, "include", "svgf.h"), LIB]):

@@ -1,6 +1,7 @@
 // svgf_scene_bvh.hip — the resident scene (row f14): the scene producer's inputs kept on the device with a BVH over the triangles,
 // and a draw that is one launch.  Row f15 (below the draw kernel) animates it: per-object poses applied to the rest state and a
-// refit of the node boxes, three launches per frame.  include/svgf.h states the semantics (a gated brute force that every tree reproduces);
+// refit of the node boxes, three launches per frame.  Row f16 adds the shadowed form of the draw kernel (shadow rays as any-hit walks
+// on the same stack).  include/svgf.h states the semantics (a gated brute force that every tree reproduces);
 // svgf_bvh_build.cpp builds the tree on the host; the per-pixel body around the triangle search is svgf_scene_pixel.inc.h, the text
 // k_scene_frame compiles too.
 //
@@ -19,6 +20,7 @@
 #include <cstdint>
 #include <cstring>
 #include <new>
+#include <type_traits>
 #include <vector>
 
 void svgf_bvh_tri_box(const float *T, float lo[3], float hi[3]);       // svgf_bvh_build.cpp
@@ -56,10 +58,107 @@ __device__ __forceinline__ bool scene_slab(const float4 &lo4, const float4 &hi4,
     return pass && (tn <= tf);
 }
 
-__global__ __launch_bounds__(256) void k_scene_bvh(SceneBvhArgs b)
+// ---- row f16: shadow rays ---------------------------------------------------------------------------------------------------------------------
+// svgf_scene_draw_shadowed (include/svgf.h states the rule): the primary walk as above, then per sample a point on the parallelogram
+// light, the ray from the surface to it and an ANY-hit search inside (t_lo, t_hi): the primitives that do not emit, then a walk over
+// the same nodes that leaves at the first counting triangle.  Occlusion is an OR, so neither the visiting order nor the early exit
+// can change it.  The walk parks nodes on the same per-lane stack - the primary walk has emptied it by then - and the samples are a
+// runtime loop (one copy of the walk in the code object, whatever `samples` is).
+struct SceneShadowArgs {
+    SceneBvhArgs b;
+    float edge_u[3], edge_v[3];
+    int samples;
+};
+
+__device__ __forceinline__ const SceneBvhArgs &scene_bvh_args(const SceneBvhArgs &b) { return b; }
+__device__ __forceinline__ const SceneBvhArgs &scene_bvh_args(const SceneShadowArgs &sa) { return sa.b; }
+
+// true iff an occluder counts on the ray r with t_lo < t < t_hi
+__device__ __forceinline__ bool scene_occluded(const SceneBvhArgs &b, const SceneRay &r, int *const stk, float t_lo, float t_hi)
+{
+#pragma clang fp contract(off)
+    const SceneArgs &a = b.s;
+    for (int k = 0; k < a.n_geoms; k++) {
+        const SvgfSceneGeom &g = a.geoms[k];
+        if (g.emittance != 0.0f) continue;
+        bool hit;
+        float tw, nw[3], pw[3];
+        scene_primitive_test(g, r.o, r.d, hit, tw, nw, pw);
+        if (hit && (tw > t_lo) && (tw < t_hi)) return true;
+    }
+    if (a.n_tris <= 0) return false;
+    int sp = 0;
+    float4 nlo = b.nodes[0], nhi = b.nodes[1];
+    float tn;
+    bool go = scene_slab(nlo, nhi, r, tn) && !(tn > t_hi);
+    while (go) {
+        const int first = __float_as_int(nlo.w), count = __float_as_int(nhi.w);
+        bool down = false;
+        if (count > 0) {
+            for (int k = first; k < first + count; k++) {
+                const int i = b.order[k];
+                float bx, by, t;
+                if (!scene_tri_test(a.tris + 24 * (size_t)i, r.o, r.d, bx, by, t) || !(t > t_lo) || !(t < t_hi)) continue;
+                float tni;
+                if (scene_slab(b.tri_boxes[2 * (size_t)i], b.tri_boxes[2 * (size_t)i + 1], r, tni) && (t >= tni)) return true;
+            }
+        } else {
+            const float4 alo = b.nodes[2 * (size_t)first], ahi = b.nodes[2 * (size_t)first + 1];
+            const float4 blo = b.nodes[2 * (size_t)first + 2], bhi = b.nodes[2 * (size_t)first + 3];
+            float ta, tb;
+            const bool pa = scene_slab(alo, ahi, r, ta) && !(ta > t_hi), pb = scene_slab(blo, bhi, r, tb) && !(tb > t_hi);
+            if (pa && pb) { stk[256 * sp] = first + 1; sp++; }
+            if (pa || pb) { nlo = pa ? alo : blo; nhi = pa ? ahi : bhi; down = true; }
+        }
+        if (!down) {
+            go = false;
+            while (sp > 0 && !go) {
+                sp--;
+                const int cur = stk[256 * sp];
+                nlo = b.nodes[2 * (size_t)cur]; nhi = b.nodes[2 * (size_t)cur + 1];
+                go = scene_slab(nlo, nhi, r, tn) && !(tn > t_hi);
+            }
+        }
+    }
+    return false;
+}
+
+// vis of pixel p: the share of its shadow rays that reach the light.  r holds the primary ray and is reused for the shadow rays.
+__device__ __forceinline__ float scene_visibility(const SceneShadowArgs &sa, SceneRay &r, const SceneHit &h, const float pos[3], int *const stk, int p)
+{
+#pragma clang fp contract(off)
+    const SceneArgs &a = sa.b.s;
+    int unoccluded = sa.samples;
+    if (h.gid >= 0 && !(h.emit > 0.0f)) {       // a miss and an emitter cast no ray
+        unoccluded = 0;
+        for (int c = 0; c < 3; c++) r.o[c] = pos[c];
+        for (int s = 0; s < sa.samples; s++) {
+            const float u = scene_hash(a.seed, a.frame, (unsigned)p, 8 + 2 * s), v = scene_hash(a.seed, a.frame, (unsigned)p, 9 + 2 * s);
+            const float su = 2.0f * u - 1.0f, sv = 2.0f * v - 1.0f;
+            float q[3];
+            for (int c = 0; c < 3; c++) q[c] = ((a.light[c] + su * sa.edge_u[c]) + sv * sa.edge_v[c]) - pos[c];
+            const float dl = sqrtf((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]);
+            bool occluded = false;
+            if (dl > 0.0f) {
+                for (int c = 0; c < 3; c++) { r.d[c] = q[c] / dl; r.flat[c] = fabsf(r.d[c]) < 0x1p-100f; r.inv[c] = 1.0f / r.d[c]; }
+                const float t_lo = 0x1p-10f * fmaxf(1.0f, dl);
+                occluded = scene_occluded(sa.b, r, stk, t_lo, dl - t_lo);
+            }
+            unoccluded += occluded ? 0 : 1;
+        }
+    }
+    return (float)unoccluded / (float)sa.samples;
+}
+__device__ __forceinline__ float scene_visibility(const SceneBvhArgs &, SceneRay &, const SceneHit &, const float *, int *, int) { return 1.0f; }
+
+// SHADOWED = false is svgf_scene_draw's kernel, statement for statement what it was before row f16; true adds the part between the
+// primary walk and the shared tail.
+template <bool SHADOWED>
+__global__ __launch_bounds__(256) void k_scene_bvh(typename std::conditional<SHADOWED, SceneShadowArgs, SceneBvhArgs>::type arg)
 {
 #pragma clang fp contract(off)
     __shared__ int stack[SVGF_SCENE_MAX_DEPTH * 256];
+    const SceneBvhArgs &b = scene_bvh_args(arg);
     const SceneArgs &a = b.s;
     const int p = blockIdx.x * 256 + threadIdx.x;
     if (p < a.W * a.H) {
@@ -108,7 +207,13 @@ __global__ __launch_bounds__(256) void k_scene_bvh(SceneBvhArgs b)
                 }
             }
         }
-        scene_finish(a, p, r.o, r.d, h, best, bt, bbx, bby);
+        if constexpr (SHADOWED) {
+            float pos[3];
+            scene_surface(a, r.o, r.d, h, best, bt, bbx, bby, pos);
+            scene_shade<true>(a, p, h, pos, scene_visibility(arg, r, h, pos, stack + threadIdx.x, p));
+        } else {
+            scene_finish(a, p, r.o, r.d, h, best, bt, bbx, bby);
+        }
     }
 }
 
@@ -429,8 +534,9 @@ extern "C" int svgf_scene_info(const svgf_scene *scene, SvgfSceneInfo *out)
     return SVGF_OK;
 }
 
+// `area` NULL: svgf_scene_draw*, k_scene_bvh; otherwise svgf_scene_draw_shadowed (light == area->centre), k_scene_bvh<true>
 static int scene_draw_impl(const svgf_scene *scene, void *out_rgb_dev, void *out_gbuffer_dev, const SvgfPlanarGBuffer *planes, int width, int height,
-                           const SvgfCamera *cam, const SvgfSynthParams *sp, const float light[3], void *stream)
+                           const SvgfCamera *cam, const SvgfSynthParams *sp, const float light[3], const SvgfSceneLight *area, void *stream)
 {
     if (!scene || !out_rgb_dev || (!out_gbuffer_dev && !planes) || !cam || !sp || !light || width <= 0 || height <= 0) return SVGF_ERR_INVALID_ARG;
     if (!out_gbuffer_dev && (!planes->normal || !planes->position || !planes->geom_id)) return SVGF_ERR_INVALID_ARG;
@@ -444,7 +550,15 @@ static int scene_draw_impl(const svgf_scene *scene, void *out_rgb_dev, void *out
     b.s.pl_nrm = planes ? planes->normal : nullptr; b.s.pl_pos = planes ? planes->position : nullptr;
     b.s.pl_alb = planes ? planes->albedo : nullptr; b.s.pl_gid = planes ? planes->geom_id : nullptr;
     const int n = width * height;
-    hipLaunchKernelGGL(k_scene_bvh, dim3((n + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), b);
+    if (area) {
+        SceneShadowArgs sa;
+        sa.b = b;
+        for (int c = 0; c < 3; c++) { sa.edge_u[c] = area->edge_u[c]; sa.edge_v[c] = area->edge_v[c]; }
+        sa.samples = area->samples;
+        hipLaunchKernelGGL(k_scene_bvh<true>, dim3((n + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), sa);
+    } else {
+        hipLaunchKernelGGL(k_scene_bvh<false>, dim3((n + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), b);
+    }
     return hipGetLastError() == hipSuccess ? SVGF_OK : SVGF_ERR_HIP;
 }
 
@@ -452,7 +566,7 @@ extern "C" int svgf_scene_draw(const svgf_scene *scene, void *out_rgb_dev, void 
                                const SvgfSynthParams *sp, const float light[3], void *stream)
 {
     if (!out_gbuffer_dev) return SVGF_ERR_INVALID_ARG;
-    return scene_draw_impl(scene, out_rgb_dev, out_gbuffer_dev, nullptr, width, height, cam, sp, light, stream);
+    return scene_draw_impl(scene, out_rgb_dev, out_gbuffer_dev, nullptr, width, height, cam, sp, light, nullptr, stream);
 }
 
 // the same frame written into the planes of svgf_planar_gbuffer
@@ -460,7 +574,19 @@ extern "C" int svgf_scene_draw_planar(const svgf_scene *scene, void *out_rgb_dev
                                       const SvgfCamera *cam, const SvgfSynthParams *sp, const float light[3], void *stream)
 {
     if (!planes) return SVGF_ERR_INVALID_ARG;
-    return scene_draw_impl(scene, out_rgb_dev, nullptr, planes, width, height, cam, sp, light, stream);
+    return scene_draw_impl(scene, out_rgb_dev, nullptr, planes, width, height, cam, sp, light, nullptr, stream);
+}
+
+// row f16: the same frame with stochastic shadow rays towards a parallelogram light; AoS or planar target, exactly one of them
+extern "C" int svgf_scene_draw_shadowed(const svgf_scene *scene, void *out_rgb_dev, void *out_gbuffer_dev, const SvgfPlanarGBuffer *planes,
+                                        int width, int height, const SvgfCamera *cam, const SvgfSynthParams *sp, const SvgfSceneLight *light,
+                                        void *stream)
+{
+    if (!light || light->samples < 1 || light->samples > SVGF_SCENE_MAX_SHADOW_SAMPLES) return SVGF_ERR_INVALID_ARG;
+    for (int c = 0; c < 3; c++)
+        if (!std::isfinite(light->centre[c]) || !std::isfinite(light->edge_u[c]) || !std::isfinite(light->edge_v[c])) return SVGF_ERR_INVALID_ARG;
+    if ((out_gbuffer_dev != nullptr) == (planes != nullptr)) return SVGF_ERR_INVALID_ARG;
+    return scene_draw_impl(scene, out_rgb_dev, out_gbuffer_dev, planes, width, height, cam, sp, light->centre, light, stream);
 }
 
 // ---- row f15: the animated resident scene ---------------------------------------------------------------------------------------------------

@@ -1,6 +1,7 @@
-// svgf_scene_pixel.inc.h — the per-pixel body of the scene producer, shared as TEXT by its two kernels (as svgf_temporal_pixel.inc.h
+// svgf_scene_pixel.inc.h — the per-pixel body of the scene producer, shared as TEXT by its kernels (as svgf_temporal_pixel.inc.h
 // is by the temporal kernels): k_scene_frame (svgf_scene.hip: every triangle for every pixel) and k_scene_bvh (svgf_scene_bvh.hip:
-// the resident scene's BVH walk).  The ray, the primitives loop, the triangle test and everything behind the choice of the nearest
+// the resident scene's BVH walk, and in its shadowed form the shadow rays of row f16, which reuse the per-primitive test and the
+// triangle test).  The ray, the primitives loop, the triangle test and everything behind the choice of the nearest
 // triangle (corner weights, texture, shading, noise, the AoS / planar stores) live here, so both kernels compile the same
 // arithmetic; only the loop that offers triangles to scene_tri_test differs.  float32, contraction off in every function.
 // Include inside an anonymous namespace, after svgf.h and hip_runtime.h.
@@ -65,6 +66,55 @@ __device__ __forceinline__ void scene_ray(const SceneArgs &a, int x, int y, floa
     o[0] = a.o[0]; o[1] = a.o[1]; o[2] = a.o[2];
 }
 
+// One primitive against the ray (o, d): the cube / sphere test of the reference, the world-space normal nw and point pw of the hit
+// it reports, and tw, its distance from o measured in world space.  The text both users compile: scene_primitives (the nearest hit)
+// and the shadow rays of svgf_scene_draw_shadowed (any hit inside an interval; nw and pw unused there).
+__device__ __forceinline__ void scene_primitive_test(const SvgfSceneGeom &g, const float o[3], const float d[3], bool &hit, float &tw,
+                                                     float nw[3], float pw[3])
+{
+#pragma clang fp contract(off)
+    float qo[3], qd[3];
+    apply34(g.inv, o, 1.0f, qo);
+    apply34(g.inv, d, 0.0f, qd);
+    normalise3(qd);
+    float tt;
+    if (g.type == 0) {      // unit cube: slab test, entering face (or leaving face when the origin is inside)
+        float tmin = -1e38f, tmax = 1e38f;
+        int amin = 0, amax = 0;
+        for (int ax = 0; ax < 3; ax++) {
+            const float t1 = (-0.5f - qo[ax]) / qd[ax], t2 = (0.5f - qo[ax]) / qd[ax];
+            // glm::min / glm::max (src/intersections.h:65-66) as the reference's GLM defines them, x < y ? x : y and x > y ? x : y:
+            // a NaN on either side (a ray in the plane of a face: 0/0) gives t2, where fminf / fmaxf give the other operand
+            const float ta = t1 < t2 ? t1 : t2, tb = t1 > t2 ? t1 : t2;
+            if (ta > 0.0f && ta > tmin) { tmin = ta; amin = ax; }
+            if (tb < tmax) { tmax = tb; amax = ax; }
+        }
+        hit = (tmax >= tmin) && (tmax > 0.0f);
+        const bool inside = tmin <= 0.0f;
+        tt = inside ? tmax : tmin;
+        const int axis = inside ? amax : amin;
+        const float sgn = (qd[axis] < 0.0f) ? 1.0f : -1.0f;             // the face normal that looks at the ray
+        const float no[3] = { axis == 0 ? sgn : 0.0f, axis == 1 ? sgn : 0.0f, axis == 2 ? sgn : 0.0f };
+        apply34(g.xf, no, 0.0f, nw);
+        normalise3(nw);
+    } else {                // unit sphere, radius 0.5
+        const float b = (qo[0] * qd[0] + qo[1] * qd[1]) + qo[2] * qd[2];
+        const float rad = b * b - (((qo[0] * qo[0] + qo[1] * qo[1]) + qo[2] * qo[2]) - 0.25f);
+        const float sq = sqrtf(fmaxf(rad, 0.0f));
+        const float ta = -b + sq, tb = -b - sq;
+        const bool both_pos = (ta > 0.0f) && (tb > 0.0f), both_neg = (ta < 0.0f) && (tb < 0.0f);
+        tt = both_pos ? fminf(ta, tb) : fmaxf(ta, tb);
+        hit = (rad >= 0.0f) && !both_neg;
+        const float po[3] = { qo[0] + tt * qd[0], qo[1] + tt * qd[1], qo[2] + tt * qd[2] };
+        for (int r = 0; r < 3; r++) nw[r] = (g.invT[3 * r] * po[0] + g.invT[3 * r + 1] * po[1]) + g.invT[3 * r + 2] * po[2];
+        normalise3(nw);
+    }
+    const float po[3] = { qo[0] + tt * qd[0], qo[1] + tt * qd[1], qo[2] + tt * qd[2] };
+    apply34(g.xf, po, 1.0f, pw);
+    const float dv0 = o[0] - pw[0], dv1 = o[1] - pw[1], dv2 = o[2] - pw[2];
+    tw = sqrtf((dv0 * dv0 + dv1 * dv1) + dv2 * dv2);                    // t is measured in world space
+}
+
 // nearest hit among the primitives
 __device__ __forceinline__ void scene_primitives(const SceneArgs &a, const float o[3], const float d[3], SceneHit &h)
 {
@@ -75,48 +125,9 @@ __device__ __forceinline__ void scene_primitives(const SceneArgs &a, const float
     h.emit = 0.0f;
     for (int k = 0; k < a.n_geoms; k++) {
         const SvgfSceneGeom &g = a.geoms[k];
-        float qo[3], qd[3];
-        apply34(g.inv, o, 1.0f, qo);
-        apply34(g.inv, d, 0.0f, qd);
-        normalise3(qd);
         bool hit;
-        float tt, nw[3];
-        if (g.type == 0) {      // unit cube: slab test, entering face (or leaving face when the origin is inside)
-            float tmin = -1e38f, tmax = 1e38f;
-            int amin = 0, amax = 0;
-            for (int ax = 0; ax < 3; ax++) {
-                const float t1 = (-0.5f - qo[ax]) / qd[ax], t2 = (0.5f - qo[ax]) / qd[ax];
-                // glm::min / glm::max (src/intersections.h:65-66) as the reference's GLM defines them, x < y ? x : y and x > y ? x : y:
-                // a NaN on either side (a ray in the plane of a face: 0/0) gives t2, where fminf / fmaxf give the other operand
-                const float ta = t1 < t2 ? t1 : t2, tb = t1 > t2 ? t1 : t2;
-                if (ta > 0.0f && ta > tmin) { tmin = ta; amin = ax; }
-                if (tb < tmax) { tmax = tb; amax = ax; }
-            }
-            hit = (tmax >= tmin) && (tmax > 0.0f);
-            const bool inside = tmin <= 0.0f;
-            tt = inside ? tmax : tmin;
-            const int axis = inside ? amax : amin;
-            const float sgn = (qd[axis] < 0.0f) ? 1.0f : -1.0f;             // the face normal that looks at the ray
-            const float no[3] = { axis == 0 ? sgn : 0.0f, axis == 1 ? sgn : 0.0f, axis == 2 ? sgn : 0.0f };
-            apply34(g.xf, no, 0.0f, nw);
-            normalise3(nw);
-        } else {                // unit sphere, radius 0.5
-            const float b = (qo[0] * qd[0] + qo[1] * qd[1]) + qo[2] * qd[2];
-            const float rad = b * b - (((qo[0] * qo[0] + qo[1] * qo[1]) + qo[2] * qo[2]) - 0.25f);
-            const float sq = sqrtf(fmaxf(rad, 0.0f));
-            const float ta = -b + sq, tb = -b - sq;
-            const bool both_pos = (ta > 0.0f) && (tb > 0.0f), both_neg = (ta < 0.0f) && (tb < 0.0f);
-            tt = both_pos ? fminf(ta, tb) : fmaxf(ta, tb);
-            hit = (rad >= 0.0f) && !both_neg;
-            const float po[3] = { qo[0] + tt * qd[0], qo[1] + tt * qd[1], qo[2] + tt * qd[2] };
-            for (int r = 0; r < 3; r++) nw[r] = (g.invT[3 * r] * po[0] + g.invT[3 * r + 1] * po[1]) + g.invT[3 * r + 2] * po[2];
-            normalise3(nw);
-        }
-        const float po[3] = { qo[0] + tt * qd[0], qo[1] + tt * qd[1], qo[2] + tt * qd[2] };
-        float pw[3];
-        apply34(g.xf, po, 1.0f, pw);
-        const float dv0 = o[0] - pw[0], dv1 = o[1] - pw[1], dv2 = o[2] - pw[2];
-        const float tw = sqrtf((dv0 * dv0 + dv1 * dv1) + dv2 * dv2);        // t is measured in world space
+        float tw, nw[3], pw[3];
+        scene_primitive_test(g, o, d, hit, tw, nw, pw);
         if (hit && (tw > 1e-4f) && (tw < h.t_best)) {
             h.t_best = tw; h.gid = a.geom_ids ? a.geom_ids[k] : k;
             h.n[0] = nw[0]; h.n[1] = nw[1]; h.n[2] = nw[2];
@@ -149,8 +160,11 @@ __device__ __forceinline__ bool scene_tri_test(const float *T, const float o[3],
 // The tail: the nearest triangle `best` (-1: none nearer than the primitives) at distance bt with barycentrics (bbx, bby) replaces
 // the primitives' hit; then the miss position, shading, noise and the AoS / planar stores of pixel p.
 // normal = n0 * b.x + n1 * b.y + n2 * (1 - b.x - b.y) normalised (Triangle::Intersect, src/sceneStructs.h:168-172, sic)
-__device__ __forceinline__ void scene_finish(const SceneArgs &a, int p, const float o[3], const float d[3], SceneHit &h, int best, float bt,
-                                             float bbx, float bby)
+// It comes in two halves so that svgf_scene_draw_shadowed can cast its shadow rays from `pos` in between: scene_surface settles
+// the hit and the position, scene_shade<SHADOWED> does the rest, with the light's term scaled by `vis` in the shadowed form only
+// (the unshadowed instantiation compiles the statement it always did).
+__device__ __forceinline__ void scene_surface(const SceneArgs &a, const float o[3], const float d[3], SceneHit &h, int best, float bt,
+                                              float bbx, float bby, float pos[3])
 {
 #pragma clang fp contract(off)
     if (best >= 0) {
@@ -175,19 +189,24 @@ __device__ __forceinline__ void scene_finish(const SceneArgs &a, int p, const fl
         h.gid = a.tri_ids[best];
         h.t_best = bt;
     }
+    const bool miss = h.gid < 0;
+    for (int c = 0; c < 3; c++) pos[c] = miss ? (o[c] + -1.0f * d[c]) : h.ph[c];    // t = -1 on a miss (src/pathtrace.cu:318)
+}
+
+template <bool SHADOWED>
+__device__ __forceinline__ void scene_shade(const SceneArgs &a, int p, const SceneHit &h, const float pos[3], float vis)
+{
+#pragma clang fp contract(off)
     const float *n = h.n, *alb = h.alb;
     const int gid = h.gid;
-
     const bool miss = gid < 0;
-    float pos[3];
-    for (int c = 0; c < 3; c++) pos[c] = miss ? (o[c] + -1.0f * d[c]) : h.ph[c];    // t = -1 on a miss (src/pathtrace.cu:318)
 
     float tl[3];
     for (int c = 0; c < 3; c++) tl[c] = a.light[c] - pos[c];
     const float dist2 = (tl[0] * tl[0] + tl[1] * tl[1]) + tl[2] * tl[2];
     const float dl = sqrtf(dist2);
     const float lam = fmaxf(((tl[0] / dl) * n[0] + (tl[1] / dl) * n[1]) + (tl[2] / dl) * n[2], 0.0f);
-    float shade = 0.15f + (30.0f * lam) / (4.0f + dist2);
+    float shade = SHADOWED ? 0.15f + vis * ((30.0f * lam) / (4.0f + dist2)) : 0.15f + (30.0f * lam) / (4.0f + dist2);
     if (h.emit > 0.0f) shade = h.emit;
 
     const unsigned up = (unsigned)p;
@@ -214,6 +233,14 @@ __device__ __forceinline__ void scene_finish(const SceneArgs &a, int p, const fl
     g[6] = alb[0]; g[7] = alb[1]; g[8] = alb[2];
     g[9] = 1.0f; g[10] = 1.0f; g[11] = 1.0f;
     reinterpret_cast<int *>(g)[12] = gid;
+}
+
+__device__ __forceinline__ void scene_finish(const SceneArgs &a, int p, const float o[3], const float d[3], SceneHit &h, int best, float bt,
+                                             float bbx, float bby)
+{
+    float pos[3];
+    scene_surface(a, o, d, h, best, bt, bbx, bby, pos);
+    scene_shade<false>(a, p, h, pos, 1.0f);
 }
 
 // ---- host side, shared by svgf_scene_render* and the resident scene ---------------------------------------------------------------------

@@ -872,6 +872,45 @@ int svgf_pose_rigid(const float axis[3], float angle_rad, const float pivot[3], 
 int svgf_bvh_refit_plan_host(const SvgfBvhNode *nodes, int n_nodes, int cap, SvgfRefitTreelet *treelets, unsigned char *level,
                              int *top, int *top_seg, SvgfRefitPlanInfo *info);
 
+/* ---- "next" row f16: shadowed resident scene - stochastic shadow rays through the BVH (added after 0.9; probe the symbol) ----
+ * svgf_scene_draw shades every hit towards a point light whatever stands in between.  svgf_scene_draw_shadowed draws the same
+ * frame and, per pixel, casts `samples` shadow rays from the surface towards points of a parallelogram light: the one-sample
+ * visibility estimate of an area light, the noise SVGF was designed for (a penumbra pixel is lit or dark in any one frame, the
+ * truth is the mean over frames).  One launch on `stream`, no allocation, no upload, no host wait, legal under stream capture; on a
+ * static scene and on a posed one (row f15), where it reads the posed arrays exactly as svgf_scene_draw does.
+ * Exactly one of out_gbuffer_dev (AoS texels) and planes (svgf_planar_gbuffer's layout) is non-NULL.
+ * Errors: svgf_scene_draw's, and in addition SVGF_ERR_INVALID_ARG for a NULL light, samples outside
+ *   1..SVGF_SCENE_MAX_SHADOW_SAMPLES, a light field that is not finite, both targets given or neither; all before any device work.
+ * Normative semantics - float32, one rounding per operation, no contraction:
+ *   G-buffer: every field (AoS or planes) is what svgf_scene_draw writes with light = centre, bit for bit.  Shadows touch colour only.
+ *   A miss (geomId < 0) and an emissive hit (emittance > 0) cast no ray and get svgf_scene_draw's colour.
+ *   Every other pixel p (= y * width + x), pos its G-buffer position, sample s = 0 .. samples - 1:
+ *     u = hash(seed, frame, p, 8 + 2s), v = hash(seed, frame, p, 9 + 2s)    (svgf_synth_render's hash; streams 0..4 stay the noise)
+ *     L_c = (centre_c + (2u - 1) * edge_u_c) + (2v - 1) * edge_v_c;   q_c = L_c - pos_c;   dl = sqrtf((q0 q0 + q1 q1) + q2 q2)
+ *     !(dl > 0): the sample is unoccluded, no ray is formed.  Otherwise d_c = q_c / dl, t_lo = 2^-10 * fmaxf(1, dl), t_hi = dl - t_lo,
+ *     and the sample is OCCLUDED iff an occluder counts on the ray (pos, d) with t_lo < t < t_hi.  Occluders:
+ *       triangle i: row f14's rule on that ray - svgf_scene_render_mesh's intersection arithmetic (back-face cull included) gives t,
+ *         S(padded box i) passes and t >= tn_i;
+ *       primitive k with emittance == 0: its cube / sphere test - the one the primary ray runs - reports a hit and the world-space
+ *         distance tw of that hit lies in the interval.  Every primitive, not only the nearest.  An emitter never occludes.
+ *   Occlusion is an OR over the counting occluders, so it does not depend on visiting order, tree or leaf size: a node is skipped
+ *     iff S(node) fails or tn_node > t_hi (exact by row f14's monotonicity argument), and leaving at the first occluder is free.
+ *   Colour: vis = (float)unoccluded / (float)samples, and the shade of svgf_scene_draw becomes
+ *     0.15f + vis * ((30.0f * lam) / (4.0f + dist2))        lam, dist2 from `centre` exactly as svgf_scene_draw forms them;
+ *     everything behind the shade (noise multiplier, fireflies, chroma, stores) is unchanged.  With nothing in the way vis = 1 and
+ *     the colour is svgf_scene_draw's on every bit.  edge_u = edge_v = 0 is a point light: vis is 0 or 1, hard shadows.
+ * INTEGRATION.md 5j has the frame loop and what a shadow ray costs, examples/shadowed_scene.cpp runs it. */
+typedef struct SvgfSceneLight {
+    float centre[3];      /* what svgf_scene_draw takes as `light`: the Lambert term and the fall-off use it, unchanged */
+    float edge_u[3];      /* half-edges of a parallelogram light around centre; both zero = a point light, hard shadows */
+    float edge_v[3];
+    int   samples;        /* shadow rays per pixel and frame, 1..SVGF_SCENE_MAX_SHADOW_SAMPLES */
+} SvgfSceneLight;
+#define SVGF_SCENE_MAX_SHADOW_SAMPLES 64
+int svgf_scene_draw_shadowed(const svgf_scene *scene, void *out_rgb_dev, void *out_gbuffer_dev /* or NULL */,
+                             const SvgfPlanarGBuffer *planes /* or NULL */, int width, int height, const SvgfCamera *cam,
+                             const SvgfSynthParams *sp, const SvgfSceneLight *light, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
