@@ -18,6 +18,7 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libsvgf_hip.so")
+LIB_TRACE_PATH = os.path.join(_HERE, "libsvgf_trace.so")      # the companion library of row f17 (include/svgf_trace.h)
 LIB_EXP_PATH = os.path.join(_HERE, "libsvgf_hip_exp.so")     # -DSVGF_BUILD_EXPERIMENTS: parked variants + tuning table (tests / tools only)
 
 SVGF_OK = 0
@@ -45,7 +46,10 @@ EXPORTS = ["svgf_version", "svgf_params_default", "svgf_create", "svgf_destroy",
            "svgf_quality_state_bytes", "svgf_quality_windows", "svgf_quality_meter", "svgf_quality_read",
            "svgf_scene_create", "svgf_scene_destroy", "svgf_scene_info", "svgf_scene_draw", "svgf_scene_draw_planar", "svgf_bvh_build_host",
            "svgf_scene_enable_pose", "svgf_scene_pose", "svgf_scene_read", "svgf_pose_rigid", "svgf_bvh_refit_plan_host",
-           "svgf_scene_draw_shadowed"]
+           "svgf_scene_draw_shadowed", "svgf_scene_view"]
+# every symbol include/svgf_trace.h declares (libsvgf_trace.so, the companion library of row f17)
+TRACE_EXPORTS = ["svgf_trace_draw", "svgf_trace_version"]
+TRACE_MAX_BOUNCE_SAMPLES = 8
 SCENE_MAX_DEPTH = 48
 SCENE_MAX_POSED = 1024
 SCENE_REFIT_CAP = 1024
@@ -154,6 +158,21 @@ class SvgfSceneLight(C.Structure):
             l.centre[i], l.edge_u[i], l.edge_v[i] = float(centre[i]), float(edge_u[i]), float(edge_v[i])
         l.samples = int(samples)
         return l
+
+
+class SvgfSceneView(C.Structure):
+    """svgf_scene_view: the device pointers the draws read (the posed arrays on a posed scene), valid until svgf_scene_destroy or
+    svgf_scene_enable_pose."""
+    _fields_ = [("device", C.c_int), ("n_geoms", C.c_int), ("n_tris", C.c_int), ("n_tex", C.c_int), ("n_nodes", C.c_int), ("depth", C.c_int),
+                ("geoms", C.c_void_p), ("geom_ids", C.c_void_p), ("tris", C.c_void_p), ("tri_ids", C.c_void_p), ("tri_albedo", C.c_void_p),
+                ("tri_tex", C.c_void_p), ("tex_desc", C.c_void_p), ("tex", C.c_void_p), ("nodes", C.c_void_p), ("order", C.c_void_p),
+                ("tri_boxes", C.c_void_p)]
+
+
+class SvgfTraceParams(C.Structure):
+    """svgf_trace_draw: directions gathered per pixel (0..TRACE_MAX_BOUNCE_SAMPLES), the constant term, and whether the bounce's hit
+    casts a shadow ray of its own."""
+    _fields_ = [("bounce_samples", C.c_int), ("ambient", C.c_float), ("shadow_secondary", C.c_int)]
 
 
 # SvgfBvhNode, 32 bytes: count > 0 a leaf over order[first : first + count], count == 0 an inner node with children first, first + 1
@@ -320,10 +339,34 @@ def load_library(path: str | None = None, experiments: bool = False):
     lib.svgf_scene_read.argtypes = [vp, ip, vp, C.c_ulonglong]
     lib.svgf_scene_draw_shadowed.argtypes = [vp, vp, vp, C.POINTER(SvgfPlanarGBuffer), ip, ip, C.POINTER(SvgfCamera), C.POINTER(SvgfSynthParams),
                                              C.POINTER(SvgfSceneLight), vp]
+    lib.svgf_scene_view.argtypes = [vp, C.POINTER(SvgfSceneView)]
     lib.svgf_pose_rigid.argtypes = [C.POINTER(C.c_float), C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float), vp]
     lib.svgf_bvh_refit_plan_host.argtypes = [vp, ip, ip, vp, vp, vp, vp, vp]
     if path == LIB_PATH:
         _lib = lib
+    return lib
+
+
+_lib_trace = None
+
+
+def load_trace_library():
+    """Load libsvgf_trace.so (after the product library it links against) and declare its prototypes.  Fails loudly when it is
+    absent, and when it was compiled against another svgf.h than the product library found."""
+    global _lib_trace
+    if _lib_trace is not None:
+        return _lib_trace
+    product = load_library()
+    if not os.path.exists(LIB_TRACE_PATH):
+        raise SvgfError(f"{LIB_TRACE_PATH} not found: build it first (python -c 'import __graft_entry__ as g; g.build()').")
+    lib = C.CDLL(LIB_TRACE_PATH)
+    vp, ip = C.c_void_p, C.c_int
+    lib.svgf_trace_version.restype = ip
+    if lib.svgf_trace_version() != product.svgf_version():
+        raise SvgfError(f"libsvgf_trace.so was built for ABI {lib.svgf_trace_version():#x}, libsvgf_hip.so is {product.svgf_version():#x}")
+    lib.svgf_trace_draw.argtypes = [vp, vp, vp, C.POINTER(SvgfPlanarGBuffer), ip, ip, C.POINTER(SvgfCamera), C.POINTER(SvgfSynthParams),
+                                    C.POINTER(SvgfSceneLight), C.POINTER(SvgfTraceParams), vp]
+    _lib_trace = lib
     return lib
 
 
@@ -1004,6 +1047,33 @@ class Scene:
                                                int(width), int(height), C.byref(cam), C.byref(sp), C.byref(light), _stream(stream))
         if rc != SVGF_OK:
             raise SvgfError(f"svgf_scene_draw_shadowed failed ({rc})")
+
+    def draw_traced(self, out_rgb, out_gbuffer, width: int, height: int, camera, light, frame: int, bounce_samples: int = 1,
+                    ambient: float = 0.15, shadow_secondary: int = 1, seed: int = 1, noise: float = 0.6, fireflies: float = 0.02,
+                    pixel_length=None, stream=None):
+        """svgf_trace_draw of libsvgf_trace.so (row f17): draw_shadowed's frame plus one diffuse bounce gathered over
+        `bounce_samples` directions.  One launch on `stream`; never waits."""
+        from . import synth as _synth
+        cam = camera if isinstance(camera, SvgfCamera) else SvgfCamera.from_dict(camera)
+        if pixel_length is None:
+            fovy = camera.get("fovy_deg", 45.0) if isinstance(camera, dict) else 45.0
+            pixel_length = _synth._pixel_length(width, height, fovy)
+        sp = SvgfSynthParams(int(frame), int(seed), float(noise), float(fireflies))
+        sp.pixel_length[0], sp.pixel_length[1] = float(pixel_length[0]), float(pixel_length[1])
+        tp = SvgfTraceParams(int(bounce_samples), float(ambient), int(shadow_secondary))
+        planar = isinstance(out_gbuffer, SvgfPlanarGBuffer)
+        rc = load_trace_library().svgf_trace_draw(self.h, _ptr(out_rgb), None if planar else _ptr(out_gbuffer), C.byref(out_gbuffer) if planar else None,
+                                                  int(width), int(height), C.byref(cam), C.byref(sp), C.byref(light), C.byref(tp), _stream(stream))
+        if rc != SVGF_OK:
+            raise SvgfError(f"svgf_trace_draw failed ({rc})")
+
+    def view(self) -> dict:
+        """svgf_scene_view (host only): the device index, the counts and the device pointers the draws read, as integers (0 = NULL)."""
+        v = SvgfSceneView()
+        rc = self.lib.svgf_scene_view(self.h, C.byref(v))
+        if rc != SVGF_OK:
+            raise SvgfError(f"svgf_scene_view failed ({rc})")
+        return {k: int(getattr(v, k) or 0) for k, _ in SvgfSceneView._fields_}
 
     def enable_pose(self, n_objects: int):
         """svgf_scene_enable_pose: allocates the animation side (allocates and synchronises; not under capture)."""

@@ -18,6 +18,10 @@ HIP_SOURCES = ["svgf_api.hip", "svgf_frame.hip", "svgf_pipeline.hip", "svgf_prof
 # plain C++ (no HIP in them; compiled as C++, for the host only): the resident scene's BVH builder
 CXX_SOURCES = ["svgf_bvh_build.cpp"]
 CXX_FLAGS = ["-x", "c++", "-O3", "-std=c++17", "-fPIC", "-Wall", "-ffp-contract=off"]
+# The companion library of row f17 (include/svgf_trace.h: the path-traced draw): renderer-side code, built from the same tree and
+# linked against the product library, which stays what it was (tests/test_abi.py caps its size).
+LIB_TRACE = os.path.join(_HERE, "libsvgf_trace.so")
+TRACE_SOURCES = ["svgf_scene_trace.hip"]
 HIP_SOURCES_EXPERIMENTS = ["svgf_experiments.hip", "svgf_atrous_lane_reuse.hip", "svgf_atrous_fused.hip"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unused-function"]
 # Per-file flags.  svgf_atrous_fused.hip: SimplifyCFG's common-code sinking merges the last store of the "bilinear history" branch
@@ -78,6 +82,21 @@ def build_hip(force: bool = False, experiments: bool = False) -> str:
     return LIB
 
 
+def build_trace(force: bool = False) -> str:
+    """Compile csrc/svgf_scene_trace.hip for gfx950 into cuda-path-tracer-denoising_amd/libsvgf_trace.so, linked against the product
+    library beside it (the examples' rpath scheme: the build directory, then $ORIGIN, so the pair can be moved together)."""
+    build_hip()
+    srcs = [os.path.join(CSRC, s) for s in TRACE_SOURCES]
+    deps = srcs + [os.path.join(CSRC, h) for h in sorted(os.listdir(CSRC)) if h.endswith(".h")] + \
+        [os.path.join(ROOT, "include", "svgf.h"), os.path.join(ROOT, "include", "svgf_trace.h"), LIB]
+    if not force and _newer(LIB_TRACE, deps):
+        return LIB_TRACE
+    tmp = LIB_TRACE + f".tmp{os.getpid()}"
+    _run([hipcc_path()] + HIPCC_FLAGS + srcs + ["-L", _HERE, "-lsvgf_hip", "-Wl,-rpath," + _HERE, "-Wl,-rpath,$ORIGIN", "-Wl,-s", "-o", tmp])
+    os.replace(tmp, LIB_TRACE)
+    return LIB_TRACE
+
+
 def build_examples(force: bool = False) -> str:
     """examples/farm.cpp (N contexts on N GPUs from one C++ process), examples/pipeline.cpp (a renderer's frame loop on the frame
     pipeline), examples/cadence.cpp (a fixed-rate loop + the effective shader clock), examples/upsample.cpp (denoise at a reduced
@@ -88,15 +107,18 @@ def build_examples(force: bool = False) -> str:
     once, then svgf_scene_draw + svgf_denoise per frame) and examples/animated_scene.cpp (svgf_scene_pose with a motion table ahead of
     each draw) and examples/shadowed_scene.cpp (svgf_scene_draw_shadowed: one shadow ray per pixel, denoised, against 64), through the C ABI -> examples/farm, examples/pipeline, examples/cadence, examples/upsample, examples/dynres,
     examples/hdr_display, examples/quality, examples/resident_scene, examples/animated_scene, examples/shadowed_scene, linked against the product library
-    in-tree."""
+    in-tree; and examples/traced_scene.cpp (svgf_trace_draw: one bounce sample and one shadow ray per pixel, denoised three ways,
+    against a converged frame), linked against the companion library too."""
+    build_trace()
     out = ""
-    for name in ("pipeline", "farm", "cadence", "upsample", "dynres", "hdr_display", "quality", "resident_scene", "animated_scene", "shadowed_scene"):
+    for name in ("pipeline", "farm", "cadence", "upsample", "dynres", "hdr_display", "quality", "resident_scene", "animated_scene", "shadowed_scene", "traced_scene"):
         src = os.path.join(ROOT, "examples", name + ".cpp")
         out = os.path.join(ROOT, "examples", name)
-        if not force and _newer(out, [src, os.path.join(ROOT, "include", "svgf.h"), LIB]):
+        traced = name == "traced_scene"
+        if not force and _newer(out, [src, os.path.join(ROOT, "include", "svgf.h"), LIB] + ([os.path.join(ROOT, "include", "svgf_trace.h"), LIB_TRACE] if traced else [])):
             continue
         tmp = out + f".tmp{os.getpid()}"
-        _run([hipcc_path(), "--offload-arch=gfx950", "-O2", "-I", os.path.join(ROOT, "include"), src, "-L", _HERE, "-lsvgf_hip",
+        _run([hipcc_path(), "--offload-arch=gfx950", "-O2", "-I", os.path.join(ROOT, "include"), src, "-L", _HERE] + (["-lsvgf_trace"] if traced else []) + ["-lsvgf_hip",
               "-Wl,-rpath," + _HERE, "-Wl,-rpath,$ORIGIN/../cuda-path-tracer-denoising_amd", "-o", tmp])
         os.replace(tmp, out)
     return out

@@ -5,12 +5,12 @@
 // svgf_bvh_build.cpp builds the tree on the host; the per-pixel body around the triangle search is svgf_scene_pixel.inc.h, the text
 // k_scene_frame compiles too.
 //
-// k_scene_bvh: one thread per pixel, 256 per block.  The walk keeps the current node in registers, descends into the nearer child
-// and parks the other one on a per-lane stack in LDS: stack[level][lane], 48 levels x 256 lanes x 4 B = 48 KB per block, a lane's
+// k_scene_bvh: one thread per pixel, 256 per block.  The walk (svgf_scene_walk.inc.h) keeps the current node in registers, descends
+// into the nearer child and parks the other one on a per-lane stack in LDS: stack[level][lane], 48 x 256 x 4 B = 48 KB per block, a lane's
 // entries 1 KB apart so that the 64 lanes of a wave always touch 64 consecutive words (no bank conflict, no runtime-indexed private
 // array, no scratch).  A parked node is tested again when it is popped - the nearest hit may have come closer since - which costs one
 // 32-byte load of a node that was loaded as a child before.  SVGF_SCENE_MAX_DEPTH bounds the stack: a lane holds one entry per
-// level above its current node.
+// level above its current node.  Row f17's companion library (svgf_scene_trace.hip) compiles the same walks.
 #include "svgf_kernels.h"
 #include "../../include/svgf.h"
 
@@ -29,34 +29,7 @@ namespace {
 
 #include "svgf_scene_pixel.inc.h"
 
-struct SceneBvhArgs {
-    SceneArgs s;
-    const float4 *nodes;        // SvgfBvhNode as two float4: {lo, first}, {hi, count}
-    const int *order;
-    const float4 *tri_boxes;    // the padded box of triangle i, the same 32-byte layout: {lo, -}, {hi, -}
-};
-
-struct SceneRay { float o[3], d[3], inv[3]; bool flat[3]; };
-
-// S(box, ray) of include/svgf.h
-__device__ __forceinline__ bool scene_slab(const float4 &lo4, const float4 &hi4, const SceneRay &r, float &tn)
-{
-#pragma clang fp contract(off)
-    const float lo[3] = { lo4.x, lo4.y, lo4.z }, hi[3] = { hi4.x, hi4.y, hi4.z };
-    float tf = __builtin_huge_valf();
-    bool pass = true;
-    tn = 0.0f;
-    for (int c = 0; c < 3; c++) {
-        if (r.flat[c]) {
-            pass = pass && (lo[c] <= r.o[c]) && (r.o[c] <= hi[c]);
-        } else {
-            const float t1 = (lo[c] - r.o[c]) * r.inv[c], t2 = (hi[c] - r.o[c]) * r.inv[c];
-            tn = fmaxf(tn, fminf(t1, t2));
-            tf = fminf(tf, fmaxf(t1, t2));
-        }
-    }
-    return pass && (tn <= tf);
-}
+#include "svgf_scene_walk.inc.h"     // SceneBvhArgs, SceneRay, scene_slab, scene_nearest, scene_occluded, scene_shadow_sample
 
 // ---- row f16: shadow rays ---------------------------------------------------------------------------------------------------------------------
 // svgf_scene_draw_shadowed (include/svgf.h states the rule): the primary walk as above, then per sample a point on the parallelogram
@@ -73,86 +46,24 @@ struct SceneShadowArgs {
 __device__ __forceinline__ const SceneBvhArgs &scene_bvh_args(const SceneBvhArgs &b) { return b; }
 __device__ __forceinline__ const SceneBvhArgs &scene_bvh_args(const SceneShadowArgs &sa) { return sa.b; }
 
-// true iff an occluder counts on the ray r with t_lo < t < t_hi
-__device__ __forceinline__ bool scene_occluded(const SceneBvhArgs &b, const SceneRay &r, int *const stk, float t_lo, float t_hi)
-{
-#pragma clang fp contract(off)
-    const SceneArgs &a = b.s;
-    for (int k = 0; k < a.n_geoms; k++) {
-        const SvgfSceneGeom &g = a.geoms[k];
-        if (g.emittance != 0.0f) continue;
-        bool hit;
-        float tw, nw[3], pw[3];
-        scene_primitive_test(g, r.o, r.d, hit, tw, nw, pw);
-        if (hit && (tw > t_lo) && (tw < t_hi)) return true;
-    }
-    if (a.n_tris <= 0) return false;
-    int sp = 0;
-    float4 nlo = b.nodes[0], nhi = b.nodes[1];
-    float tn;
-    bool go = scene_slab(nlo, nhi, r, tn) && !(tn > t_hi);
-    while (go) {
-        const int first = __float_as_int(nlo.w), count = __float_as_int(nhi.w);
-        bool down = false;
-        if (count > 0) {
-            for (int k = first; k < first + count; k++) {
-                const int i = b.order[k];
-                float bx, by, t;
-                if (!scene_tri_test(a.tris + 24 * (size_t)i, r.o, r.d, bx, by, t) || !(t > t_lo) || !(t < t_hi)) continue;
-                float tni;
-                if (scene_slab(b.tri_boxes[2 * (size_t)i], b.tri_boxes[2 * (size_t)i + 1], r, tni) && (t >= tni)) return true;
-            }
-        } else {
-            const float4 alo = b.nodes[2 * (size_t)first], ahi = b.nodes[2 * (size_t)first + 1];
-            const float4 blo = b.nodes[2 * (size_t)first + 2], bhi = b.nodes[2 * (size_t)first + 3];
-            float ta, tb;
-            const bool pa = scene_slab(alo, ahi, r, ta) && !(ta > t_hi), pb = scene_slab(blo, bhi, r, tb) && !(tb > t_hi);
-            if (pa && pb) { stk[256 * sp] = first + 1; sp++; }
-            if (pa || pb) { nlo = pa ? alo : blo; nhi = pa ? ahi : bhi; down = true; }
-        }
-        if (!down) {
-            go = false;
-            while (sp > 0 && !go) {
-                sp--;
-                const int cur = stk[256 * sp];
-                nlo = b.nodes[2 * (size_t)cur]; nhi = b.nodes[2 * (size_t)cur + 1];
-                go = scene_slab(nlo, nhi, r, tn) && !(tn > t_hi);
-            }
-        }
-    }
-    return false;
-}
-
 // vis of pixel p: the share of its shadow rays that reach the light.  r holds the primary ray and is reused for the shadow rays.
 __device__ __forceinline__ float scene_visibility(const SceneShadowArgs &sa, SceneRay &r, const SceneHit &h, const float pos[3], int *const stk, int p)
 {
 #pragma clang fp contract(off)
-    const SceneArgs &a = sa.b.s;
     int unoccluded = sa.samples;
     if (h.gid >= 0 && !(h.emit > 0.0f)) {       // a miss and an emitter cast no ray
         unoccluded = 0;
         for (int c = 0; c < 3; c++) r.o[c] = pos[c];
-        for (int s = 0; s < sa.samples; s++) {
-            const float u = scene_hash(a.seed, a.frame, (unsigned)p, 8 + 2 * s), v = scene_hash(a.seed, a.frame, (unsigned)p, 9 + 2 * s);
-            const float su = 2.0f * u - 1.0f, sv = 2.0f * v - 1.0f;
-            float q[3];
-            for (int c = 0; c < 3; c++) q[c] = ((a.light[c] + su * sa.edge_u[c]) + sv * sa.edge_v[c]) - pos[c];
-            const float dl = sqrtf((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]);
-            bool occluded = false;
-            if (dl > 0.0f) {
-                for (int c = 0; c < 3; c++) { r.d[c] = q[c] / dl; r.flat[c] = fabsf(r.d[c]) < 0x1p-100f; r.inv[c] = 1.0f / r.d[c]; }
-                const float t_lo = 0x1p-10f * fmaxf(1.0f, dl);
-                occluded = scene_occluded(sa.b, r, stk, t_lo, dl - t_lo);
-            }
-            unoccluded += occluded ? 0 : 1;
-        }
+        for (int s = 0; s < sa.samples; s++)
+            unoccluded += scene_shadow_sample(sa.b, sa.edge_u, sa.edge_v, r, pos, stk, p, 8 + 2 * s, 9 + 2 * s) ? 0 : 1;
     }
     return (float)unoccluded / (float)sa.samples;
 }
 __device__ __forceinline__ float scene_visibility(const SceneBvhArgs &, SceneRay &, const SceneHit &, const float *, int *, int) { return 1.0f; }
 
-// SHADOWED = false is svgf_scene_draw's kernel, statement for statement what it was before row f16; true adds the part between the
-// primary walk and the shared tail.
+// SHADOWED = false is svgf_scene_draw's kernel, what it was before row f16 (the primary walk is scene_nearest of
+// svgf_scene_walk.inc.h since row f17: the same statements, the same 64 VGPRs); true adds the part between the primary walk and the
+// shared tail.
 template <bool SHADOWED>
 __global__ __launch_bounds__(256) void k_scene_bvh(typename std::conditional<SHADOWED, SceneShadowArgs, SceneBvhArgs>::type arg)
 {
@@ -169,44 +80,7 @@ __global__ __launch_bounds__(256) void k_scene_bvh(typename std::conditional<SHA
         for (int c = 0; c < 3; c++) { r.flat[c] = fabsf(r.d[c]) < 0x1p-100f; r.inv[c] = 1.0f / r.d[c]; }
         int best = -1;
         float bt = h.t_best, bbx = 0.0f, bby = 0.0f;
-        if (a.n_tris > 0) {
-            int *const stk = stack + threadIdx.x;
-            int sp = 0;
-            float4 nlo = b.nodes[0], nhi = b.nodes[1];
-            float tn;
-            bool go = scene_slab(nlo, nhi, r, tn) && !(tn > bt);
-            while (go) {
-                const int first = __float_as_int(nlo.w), count = __float_as_int(nhi.w);
-                bool down = false;
-                if (count > 0) {
-                    for (int k = first; k < first + count; k++) {
-                        const int i = b.order[k];
-                        float bx, by, t;
-                        if (!scene_tri_test(a.tris + 24 * (size_t)i, r.o, r.d, bx, by, t) || !(t > 0.0f)) continue;
-                        float tni;
-                        if (!scene_slab(b.tri_boxes[2 * (size_t)i], b.tri_boxes[2 * (size_t)i + 1], r, tni) || !(t >= tni)) continue;
-                        if (t < bt || (t == bt && best >= 0 && i < best)) { bt = t; best = i; bbx = bx; bby = by; }
-                    }
-                } else {
-                    const float4 alo = b.nodes[2 * (size_t)first], ahi = b.nodes[2 * (size_t)first + 1];
-                    const float4 blo = b.nodes[2 * (size_t)first + 2], bhi = b.nodes[2 * (size_t)first + 3];
-                    float ta, tb;
-                    const bool pa = scene_slab(alo, ahi, r, ta) && !(ta > bt), pb = scene_slab(blo, bhi, r, tb) && !(tb > bt);
-                    const bool a_first = pa && (!pb || ta <= tb);
-                    if (pa && pb) { stk[256 * sp] = a_first ? first + 1 : first; sp++; }
-                    if (pa || pb) { nlo = a_first ? alo : blo; nhi = a_first ? ahi : bhi; down = true; }
-                }
-                if (!down) {
-                    go = false;
-                    while (sp > 0 && !go) {
-                        sp--;
-                        const int cur = stk[256 * sp];
-                        nlo = b.nodes[2 * (size_t)cur]; nhi = b.nodes[2 * (size_t)cur + 1];
-                        go = scene_slab(nlo, nhi, r, tn) && !(tn > bt);
-                    }
-                }
-            }
-        }
+        scene_nearest(b, r, stack + threadIdx.x, 0.0f, bt, best, bbx, bby);
         if constexpr (SHADOWED) {
             float pos[3];
             scene_surface(a, r.o, r.d, h, best, bt, bbx, bby, pos);
@@ -531,6 +405,18 @@ extern "C" int svgf_scene_info(const svgf_scene *scene, SvgfSceneInfo *out)
 {
     if (!scene || !out) return SVGF_ERR_INVALID_ARG;
     *out = scene->info;
+    return SVGF_OK;
+}
+
+// row f17: what the draws read, for a renderer-side library that traces its own rays (svgf_scene_trace.hip); host only
+extern "C" int svgf_scene_view(const svgf_scene *scene, SvgfSceneView *out)
+{
+    if (!scene || !out) return SVGF_ERR_INVALID_ARG;
+    const SceneArgs &a = scene->args.s;
+    const SvgfSceneInfo &in = scene->info;
+    *out = SvgfSceneView{ scene->device, in.n_geoms, in.n_tris, in.n_tex, in.n_nodes, in.depth, a.geoms, a.geom_ids, a.tris, a.tri_ids, a.tri_albedo,
+                          a.tri_tex, a.tex_desc, a.tex, reinterpret_cast<const SvgfBvhNode *>(scene->args.nodes), scene->args.order,
+                          reinterpret_cast<const SvgfBvhNode *>(scene->args.tri_boxes) };
     return SVGF_OK;
 }
 

@@ -1,7 +1,8 @@
 // svgf_scene_pixel.inc.h — the per-pixel body of the scene producer, shared as TEXT by its kernels (as svgf_temporal_pixel.inc.h
-// is by the temporal kernels): k_scene_frame (svgf_scene.hip: every triangle for every pixel) and k_scene_bvh (svgf_scene_bvh.hip:
+// is by the temporal kernels): k_scene_frame (svgf_scene.hip: every triangle for every pixel), k_scene_bvh (svgf_scene_bvh.hip:
 // the resident scene's BVH walk, and in its shadowed form the shadow rays of row f16, which reuse the per-primitive test and the
-// triangle test).  The ray, the primitives loop, the triangle test and everything behind the choice of the nearest
+// triangle test) and k_scene_trace (svgf_scene_trace.hip, the companion library of row f17: the same again for the bounce, and the
+// tail with a shade per channel).  The ray, the primitives loop, the triangle test and everything behind the choice of the nearest
 // triangle (corner weights, texture, shading, noise, the AoS / planar stores) live here, so both kernels compile the same
 // arithmetic; only the loop that offers triangles to scene_tri_test differs.  float32, contraction off in every function.
 // Include inside an anonymous namespace, after svgf.h and hip_runtime.h.
@@ -115,8 +116,8 @@ __device__ __forceinline__ void scene_primitive_test(const SvgfSceneGeom &g, con
     tw = sqrtf((dv0 * dv0 + dv1 * dv1) + dv2 * dv2);                    // t is measured in world space
 }
 
-// nearest hit among the primitives
-__device__ __forceinline__ void scene_primitives(const SceneArgs &a, const float o[3], const float d[3], SceneHit &h)
+// nearest hit among the primitives beyond t_min (the primary ray: 1e-4, scene_primitives below)
+__device__ __forceinline__ void scene_primitives_beyond(const SceneArgs &a, const float o[3], const float d[3], float t_min, SceneHit &h)
 {
 #pragma clang fp contract(off)
     h.t_best = __builtin_huge_valf();
@@ -128,13 +129,18 @@ __device__ __forceinline__ void scene_primitives(const SceneArgs &a, const float
         bool hit;
         float tw, nw[3], pw[3];
         scene_primitive_test(g, o, d, hit, tw, nw, pw);
-        if (hit && (tw > 1e-4f) && (tw < h.t_best)) {
+        if (hit && (tw > t_min) && (tw < h.t_best)) {
             h.t_best = tw; h.gid = a.geom_ids ? a.geom_ids[k] : k;
             h.n[0] = nw[0]; h.n[1] = nw[1]; h.n[2] = nw[2];
             h.ph[0] = pw[0]; h.ph[1] = pw[1]; h.ph[2] = pw[2];
             h.alb[0] = g.albedo[0]; h.alb[1] = g.albedo[1]; h.alb[2] = g.albedo[2]; h.emit = g.emittance;
         }
     }
+}
+
+__device__ __forceinline__ void scene_primitives(const SceneArgs &a, const float o[3], const float d[3], SceneHit &h)
+{
+    scene_primitives_beyond(a, o, d, 1e-4f, h);
 }
 
 // glm::intersectRayTriangle (gtx/intersect.inl:37-74) on triangle T (24 floats): false where the reference's test leaves early,
@@ -162,7 +168,8 @@ __device__ __forceinline__ bool scene_tri_test(const float *T, const float o[3],
 // normal = n0 * b.x + n1 * b.y + n2 * (1 - b.x - b.y) normalised (Triangle::Intersect, src/sceneStructs.h:168-172, sic)
 // It comes in two halves so that svgf_scene_draw_shadowed can cast its shadow rays from `pos` in between: scene_surface settles
 // the hit and the position, scene_shade<SHADOWED> does the rest, with the light's term scaled by `vis` in the shadowed form only
-// (the unshadowed instantiation compiles the statement it always did).
+// (the unshadowed instantiation compiles the statement it always did).  scene_shade is itself scene_direct (the light's term) and
+// scene_store (noise, fireflies, chroma, stores), which the path-traced draw calls with a shade of its own.
 __device__ __forceinline__ void scene_surface(const SceneArgs &a, const float o[3], const float d[3], SceneHit &h, int best, float bt,
                                               float bbx, float bby, float pos[3])
 {
@@ -193,21 +200,26 @@ __device__ __forceinline__ void scene_surface(const SceneArgs &a, const float o[
     for (int c = 0; c < 3; c++) pos[c] = miss ? (o[c] + -1.0f * d[c]) : h.ph[c];    // t = -1 on a miss (src/pathtrace.cu:318)
 }
 
-template <bool SHADOWED>
-__device__ __forceinline__ void scene_shade(const SceneArgs &a, int p, const SceneHit &h, const float pos[3], float vis)
+// the light's term at `pos` with normal n, towards a.light: (30 lam) / (4 + dist2)
+__device__ __forceinline__ float scene_direct(const SceneArgs &a, const float n[3], const float pos[3])
 {
 #pragma clang fp contract(off)
-    const float *n = h.n, *alb = h.alb;
-    const int gid = h.gid;
-    const bool miss = gid < 0;
-
     float tl[3];
     for (int c = 0; c < 3; c++) tl[c] = a.light[c] - pos[c];
     const float dist2 = (tl[0] * tl[0] + tl[1] * tl[1]) + tl[2] * tl[2];
     const float dl = sqrtf(dist2);
     const float lam = fmaxf(((tl[0] / dl) * n[0] + (tl[1] / dl) * n[1]) + (tl[2] / dl) * n[2], 0.0f);
-    float shade = SHADOWED ? 0.15f + vis * ((30.0f * lam) / (4.0f + dist2)) : 0.15f + (30.0f * lam) / (4.0f + dist2);
-    if (h.emit > 0.0f) shade = h.emit;
+    return (30.0f * lam) / (4.0f + dist2);
+}
+
+// noise, fireflies, chroma and the AoS / planar stores of pixel p, whose surface is shaded `shade` per channel
+__device__ __forceinline__ void scene_store(const SceneArgs &a, int p, const SceneHit &h, const float pos[3], float shade_r, float shade_g, float shade_b)
+{
+#pragma clang fp contract(off)
+    const float *n = h.n, *alb = h.alb;
+    const int gid = h.gid;
+    const bool miss = gid < 0;
+    const float shade[3] = { shade_r, shade_g, shade_b };
 
     const unsigned up = (unsigned)p;
     const float u = scene_hash(a.seed, a.frame, up, 0), v = scene_hash(a.seed, a.frame, up, 1);
@@ -216,7 +228,7 @@ __device__ __forceinline__ void scene_shade(const SceneArgs &a, int p, const Sce
     float col[3];
     for (int c = 0; c < 3; c++) {
         const float chroma = 1.0f + a.chroma_amp * (scene_hash(a.seed, a.frame, up, 2 + c) - 0.5f);
-        col[c] = miss ? 0.0f : ((alb[c] * shade) * mult) * chroma;
+        col[c] = miss ? 0.0f : ((alb[c] * shade[c]) * mult) * chroma;
     }
     float *o_rgb = a.out_rgb + 3 * (size_t)p;
     o_rgb[0] = col[0]; o_rgb[1] = col[1]; o_rgb[2] = col[2];
@@ -233,6 +245,16 @@ __device__ __forceinline__ void scene_shade(const SceneArgs &a, int p, const Sce
     g[6] = alb[0]; g[7] = alb[1]; g[8] = alb[2];
     g[9] = 1.0f; g[10] = 1.0f; g[11] = 1.0f;
     reinterpret_cast<int *>(g)[12] = gid;
+}
+
+template <bool SHADOWED>
+__device__ __forceinline__ void scene_shade(const SceneArgs &a, int p, const SceneHit &h, const float pos[3], float vis)
+{
+#pragma clang fp contract(off)
+    const float direct = scene_direct(a, h.n, pos);
+    float shade = SHADOWED ? 0.15f + vis * direct : 0.15f + direct;
+    if (h.emit > 0.0f) shade = h.emit;
+    scene_store(a, p, h, pos, shade, shade, shade);
 }
 
 __device__ __forceinline__ void scene_finish(const SceneArgs &a, int p, const float o[3], const float d[3], SceneHit &h, int best, float bt,

@@ -911,6 +911,30 @@ int svgf_scene_draw_shadowed(const svgf_scene *scene, void *out_rgb_dev, void *o
                              const SvgfPlanarGBuffer *planes /* or NULL */, int width, int height, const SvgfCamera *cam,
                              const SvgfSynthParams *sp, const SvgfSceneLight *light, void *stream);
 
+/* ---- "next" row f17: a read-only view of the resident scene (added after 0.9; probe the symbol) ----
+ * What svgf_scene_draw* read, for renderer-side code that traces its own rays through the same scene: the companion library
+ * libsvgf_trace.so (include/svgf_trace.h: a one-bounce path-traced draw) reaches the scene through this call and nothing else.
+ * Host only, no device work.  On a posed scene (row f15) the pointers are the posed arrays, exactly what svgf_scene_draw reads;
+ * `geom_ids` is NULL where svgf_scene_create got none, `tri_tex` where the scene has no texture.  nodes / tri_boxes are SvgfBvhNode
+ * records (a triangle's padded box: first = i, count = 1).  The view is valid until svgf_scene_destroy or svgf_scene_enable_pose
+ * (which moves the draws to the posed copies); the arrays' CONTENTS change with every svgf_scene_pose, in stream order.
+ * A NULL argument: SVGF_ERR_INVALID_ARG. */
+typedef struct SvgfSceneView {
+    int device, n_geoms, n_tris, n_tex, n_nodes, depth;
+    const SvgfSceneGeom *geoms;
+    const int *geom_ids;
+    const float *tris;              /* 24 floats per triangle */
+    const int *tri_ids;
+    const float *tri_albedo;
+    const int *tri_tex;
+    const int *tex_desc;
+    const unsigned char *tex;
+    const SvgfBvhNode *nodes;
+    const int *order;
+    const SvgfBvhNode *tri_boxes;
+} SvgfSceneView;                    /* 112 bytes */
+int svgf_scene_view(const svgf_scene *scene, SvgfSceneView *out);
+
 #ifdef __cplusplus
 }
 #endif
