@@ -19,6 +19,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libsvgf_hip.so")
 LIB_TRACE_PATH = os.path.join(_HERE, "libsvgf_trace.so")      # the companion library of row f17 (include/svgf_trace.h)
+LIB_SPLIT_PATH = os.path.join(_HERE, "libsvgf_split.so")      # the companion library of row f18 (include/svgf_split.h)
 LIB_EXP_PATH = os.path.join(_HERE, "libsvgf_hip_exp.so")     # -DSVGF_BUILD_EXPERIMENTS: parked variants + tuning table (tests / tools only)
 
 SVGF_OK = 0
@@ -49,6 +50,8 @@ EXPORTS = ["svgf_version", "svgf_params_default", "svgf_create", "svgf_destroy",
            "svgf_scene_draw_shadowed", "svgf_scene_view"]
 # every symbol include/svgf_trace.h declares (libsvgf_trace.so, the companion library of row f17)
 TRACE_EXPORTS = ["svgf_trace_draw", "svgf_trace_version"]
+# libsvgf_split.so (include/svgf_split.h, row f18)
+SPLIT_EXPORTS = ["svgf_trace_draw_split", "svgf_trace_compose"]
 TRACE_MAX_BOUNCE_SAMPLES = 8
 SCENE_MAX_DEPTH = 48
 SCENE_MAX_POSED = 1024
@@ -367,6 +370,27 @@ def load_trace_library():
     lib.svgf_trace_draw.argtypes = [vp, vp, vp, C.POINTER(SvgfPlanarGBuffer), ip, ip, C.POINTER(SvgfCamera), C.POINTER(SvgfSynthParams),
                                     C.POINTER(SvgfSceneLight), C.POINTER(SvgfTraceParams), vp]
     _lib_trace = lib
+    return lib
+
+
+_lib_split = None
+
+
+def load_split_library():
+    """Load libsvgf_split.so (row f18; after the product library it links against) and declare its prototypes.  Fails loudly when
+    it is absent."""
+    global _lib_split
+    if _lib_split is not None:
+        return _lib_split
+    load_library()
+    if not os.path.exists(LIB_SPLIT_PATH):
+        raise SvgfError(f"{LIB_SPLIT_PATH} not found: build it first (python -c 'import __graft_entry__ as g; g.build()').")
+    lib = C.CDLL(LIB_SPLIT_PATH)
+    vp, ip = C.c_void_p, C.c_int
+    lib.svgf_trace_draw_split.argtypes = [vp, vp, vp, vp, vp, C.POINTER(SvgfPlanarGBuffer), ip, ip, C.POINTER(SvgfCamera), C.POINTER(SvgfSynthParams),
+                                          C.POINTER(SvgfSceneLight), C.POINTER(SvgfTraceParams), vp]
+    lib.svgf_trace_compose.argtypes = [ip, vp, vp, vp, C.POINTER(SvgfGuide), ip, ip, vp]
+    _lib_split = lib
     return lib
 
 
@@ -728,6 +752,17 @@ def upsample(out, hi_guide, width_hi: int, height_hi: int, rgb_lo, lo_guide, wid
         raise SvgfError(f"svgf_upsample failed ({rc})")
 
 
+def trace_compose(out, direct, indirect, guide_or_gbuffer, width: int, height: int, device: int = 0, stream=None):
+    """svgf_trace_compose of libsvgf_split.so (row f18): out = albedo * (direct + indirect), the albedo from a SvgfGuide (guide(...):
+    AoS texels, or an albedo plane) or from the AoS texels themselves (a tensor or a raw pointer).  `out` may be `direct` or
+    `indirect`.  One launch on `stream`; never waits."""
+    g = guide_or_gbuffer if isinstance(guide_or_gbuffer, SvgfGuide) else guide(gbuffer=guide_or_gbuffer)
+    rc = load_split_library().svgf_trace_compose(int(device), _ptr(out), _ptr(direct), _ptr(indirect), C.byref(g), int(width), int(height),
+                                                 _stream(stream))
+    if rc != SVGF_OK:
+        raise SvgfError(f"svgf_trace_compose failed ({rc})")
+
+
 # --- SURVEY.md 8(f) row f2: the step after denoise() ----------------------------------------------------------------
 def display_pack(pbo, left, right, width: int, height: int, device: int = 0, stream=None):
     """svgf_display_pack: `left` | `right` (packed rgb float, device) -> (height, 2*width, 4) uint8 in device memory."""
@@ -1066,6 +1101,26 @@ class Scene:
                                                   int(width), int(height), C.byref(cam), C.byref(sp), C.byref(light), C.byref(tp), _stream(stream))
         if rc != SVGF_OK:
             raise SvgfError(f"svgf_trace_draw failed ({rc})")
+
+    def draw_traced_split(self, out_direct, out_indirect, out_gbuffer, width: int, height: int, camera, light, frame: int,
+                          bounce_samples: int = 1, ambient: float = 0.15, shadow_secondary: int = 1, seed: int = 1, noise: float = 0.6,
+                          fireflies: float = 0.02, pixel_length=None, out_rgb=None, stream=None):
+        """svgf_trace_draw_split of libsvgf_split.so (row f18): draw_traced's rays, with the direct and the indirect term written
+        apart and without the albedo; `out_rgb` (optional) receives draw_traced's colour.  One launch on `stream`; never waits."""
+        from . import synth as _synth
+        cam = camera if isinstance(camera, SvgfCamera) else SvgfCamera.from_dict(camera)
+        if pixel_length is None:
+            fovy = camera.get("fovy_deg", 45.0) if isinstance(camera, dict) else 45.0
+            pixel_length = _synth._pixel_length(width, height, fovy)
+        sp = SvgfSynthParams(int(frame), int(seed), float(noise), float(fireflies))
+        sp.pixel_length[0], sp.pixel_length[1] = float(pixel_length[0]), float(pixel_length[1])
+        tp = SvgfTraceParams(int(bounce_samples), float(ambient), int(shadow_secondary))
+        planar = isinstance(out_gbuffer, SvgfPlanarGBuffer)
+        rc = load_split_library().svgf_trace_draw_split(self.h, _ptr(out_direct), _ptr(out_indirect), _ptr(out_rgb), None if planar else _ptr(out_gbuffer),
+                                                        C.byref(out_gbuffer) if planar else None, int(width), int(height), C.byref(cam), C.byref(sp),
+                                                        C.byref(light), C.byref(tp), _stream(stream))
+        if rc != SVGF_OK:
+            raise SvgfError(f"svgf_trace_draw_split failed ({rc})")
 
     def view(self) -> dict:
         """svgf_scene_view (host only): the device index, the counts and the device pointers the draws read, as integers (0 = NULL)."""

@@ -22,6 +22,10 @@ CXX_FLAGS = ["-x", "c++", "-O3", "-std=c++17", "-fPIC", "-Wall", "-ffp-contract=
 # linked against the product library, which stays what it was (tests/test_abi.py caps its size).
 LIB_TRACE = os.path.join(_HERE, "libsvgf_trace.so")
 TRACE_SOURCES = ["svgf_scene_trace.hip"]
+# The companion library of row f18 (include/svgf_split.h: the split draw and the recomposition): a second one, so that libsvgf_trace.so
+# stays the two functions it was; its draw compiles the same kernel text (csrc/svgf_scene_trace.inc.h).
+LIB_SPLIT = os.path.join(_HERE, "libsvgf_split.so")
+SPLIT_SOURCES = ["svgf_scene_split.hip", "svgf_trace_compose.hip"]
 HIP_SOURCES_EXPERIMENTS = ["svgf_experiments.hip", "svgf_atrous_lane_reuse.hip", "svgf_atrous_fused.hip"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unused-function"]
 # Per-file flags.  svgf_atrous_fused.hip: SimplifyCFG's common-code sinking merges the last store of the "bilinear history" branch
@@ -97,6 +101,21 @@ def build_trace(force: bool = False) -> str:
     return LIB_TRACE
 
 
+def build_split(force: bool = False) -> str:
+    """Compile csrc/svgf_scene_split.hip and csrc/svgf_trace_compose.hip for gfx950 into cuda-path-tracer-denoising_amd/libsvgf_split.so,
+    linked against the product library beside it, by build_trace()'s scheme."""
+    build_hip()
+    srcs = [os.path.join(CSRC, s) for s in SPLIT_SOURCES]
+    deps = srcs + [os.path.join(CSRC, h) for h in sorted(os.listdir(CSRC)) if h.endswith(".h")] + \
+        [os.path.join(ROOT, "include", h) for h in ("svgf.h", "svgf_trace.h", "svgf_split.h")] + [LIB]
+    if not force and _newer(LIB_SPLIT, deps):
+        return LIB_SPLIT
+    tmp = LIB_SPLIT + f".tmp{os.getpid()}"
+    _run([hipcc_path()] + HIPCC_FLAGS + srcs + ["-L", _HERE, "-lsvgf_hip", "-Wl,-rpath," + _HERE, "-Wl,-rpath,$ORIGIN", "-Wl,-s", "-o", tmp])
+    os.replace(tmp, LIB_SPLIT)
+    return LIB_SPLIT
+
+
 def build_examples(force: bool = False) -> str:
     """examples/farm.cpp (N contexts on N GPUs from one C++ process), examples/pipeline.cpp (a renderer's frame loop on the frame
     pipeline), examples/cadence.cpp (a fixed-rate loop + the effective shader clock), examples/upsample.cpp (denoise at a reduced
@@ -108,17 +127,20 @@ def build_examples(force: bool = False) -> str:
     each draw) and examples/shadowed_scene.cpp (svgf_scene_draw_shadowed: one shadow ray per pixel, denoised, against 64), through the C ABI -> examples/farm, examples/pipeline, examples/cadence, examples/upsample, examples/dynres,
     examples/hdr_display, examples/quality, examples/resident_scene, examples/animated_scene, examples/shadowed_scene, linked against the product library
     in-tree; and examples/traced_scene.cpp (svgf_trace_draw: one bounce sample and one shadow ray per pixel, denoised three ways,
-    against a converged frame), linked against the companion library too."""
+    against a converged frame) and examples/split_scene.cpp (svgf_trace_draw_split, a context per term, svgf_trace_compose: SVGF's
+    own pipeline beside the one-image one), linked against both companion libraries."""
     build_trace()
+    build_split()
     out = ""
-    for name in ("pipeline", "farm", "cadence", "upsample", "dynres", "hdr_display", "quality", "resident_scene", "animated_scene", "shadowed_scene", "traced_scene"):
+    for name in ("pipeline", "farm", "cadence", "upsample", "dynres", "hdr_display", "quality", "resident_scene", "animated_scene", "shadowed_scene", "traced_scene", "split_scene"):
         src = os.path.join(ROOT, "examples", name + ".cpp")
         out = os.path.join(ROOT, "examples", name)
-        traced = name == "traced_scene"
-        if not force and _newer(out, [src, os.path.join(ROOT, "include", "svgf.h"), LIB] + ([os.path.join(ROOT, "include", "svgf_trace.h"), LIB_TRACE] if traced else [])):
+        traced, split = name in ("traced_scene", "split_scene"), name == "split_scene"
+        if not force and _newer(out, [src, os.path.join(ROOT, "include", "svgf.h"), LIB] + ([os.path.join(ROOT, "include", "svgf_trace.h"), LIB_TRACE] if traced else []) +
+                                ([os.path.join(ROOT, "include", "svgf_split.h"), LIB_SPLIT] if split else [])):
             continue
         tmp = out + f".tmp{os.getpid()}"
-        _run([hipcc_path(), "--offload-arch=gfx950", "-O2", "-I", os.path.join(ROOT, "include"), src, "-L", _HERE] + (["-lsvgf_trace"] if traced else []) + ["-lsvgf_hip",
+        _run([hipcc_path(), "--offload-arch=gfx950", "-O2", "-I", os.path.join(ROOT, "include"), src, "-L", _HERE] + (["-lsvgf_split"] if split else []) + (["-lsvgf_trace"] if traced else []) + ["-lsvgf_hip",
               "-Wl,-rpath," + _HERE, "-Wl,-rpath,$ORIGIN/../cuda-path-tracer-denoising_amd", "-o", tmp])
         os.replace(tmp, out)
     return out
