@@ -20,6 +20,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libsvgf_hip.so")
 LIB_TRACE_PATH = os.path.join(_HERE, "libsvgf_trace.so")      # the companion library of row f17 (include/svgf_trace.h)
 LIB_SPLIT_PATH = os.path.join(_HERE, "libsvgf_split.so")      # the companion library of row f18 (include/svgf_split.h)
+LIB_PATH_PATH = os.path.join(_HERE, "libsvgf_path.so")        # the companion library of row f19 (include/svgf_path.h)
 LIB_EXP_PATH = os.path.join(_HERE, "libsvgf_hip_exp.so")     # -DSVGF_BUILD_EXPERIMENTS: parked variants + tuning table (tests / tools only)
 
 SVGF_OK = 0
@@ -53,6 +54,10 @@ TRACE_EXPORTS = ["svgf_trace_draw", "svgf_trace_version"]
 # libsvgf_split.so (include/svgf_split.h, row f18)
 SPLIT_EXPORTS = ["svgf_trace_draw_split", "svgf_trace_compose"]
 TRACE_MAX_BOUNCE_SAMPLES = 8
+# libsvgf_path.so (include/svgf_path.h, row f19)
+PATH_EXPORTS = ["svgf_path_draw", "svgf_path_draw_split", "svgf_path_version"]
+PATH_MAX_PATHS = 8
+PATH_MAX_DEPTH = 8
 SCENE_MAX_DEPTH = 48
 SCENE_MAX_POSED = 1024
 SCENE_REFIT_CAP = 1024
@@ -176,6 +181,12 @@ class SvgfTraceParams(C.Structure):
     """svgf_trace_draw: directions gathered per pixel (0..TRACE_MAX_BOUNCE_SAMPLES), the constant term, and whether the bounce's hit
     casts a shadow ray of its own."""
     _fields_ = [("bounce_samples", C.c_int), ("ambient", C.c_float), ("shadow_secondary", C.c_int)]
+
+
+class SvgfPathParams(C.Structure):
+    """svgf_path_draw / svgf_path_draw_split: paths per pixel (0..PATH_MAX_PATHS), bounces per path (1..PATH_MAX_DEPTH), the bounce
+    from which Russian roulette acts (0: never), the constant term, and whether the vertices behind the first cast a shadow ray."""
+    _fields_ = [("paths", C.c_int), ("max_depth", C.c_int), ("rr_depth", C.c_int), ("ambient", C.c_float), ("shadow_secondary", C.c_int)]
 
 
 # SvgfBvhNode, 32 bytes: count > 0 a leaf over order[first : first + count], count == 0 an inner node with children first, first + 1
@@ -391,6 +402,31 @@ def load_split_library():
                                           C.POINTER(SvgfSceneLight), C.POINTER(SvgfTraceParams), vp]
     lib.svgf_trace_compose.argtypes = [ip, vp, vp, vp, C.POINTER(SvgfGuide), ip, ip, vp]
     _lib_split = lib
+    return lib
+
+
+_lib_path = None
+
+
+def load_path_library():
+    """Load libsvgf_path.so (row f19; after the product library it links against) and declare its prototypes.  Fails loudly when it
+    is absent, and when it was compiled against another svgf.h than the product library found."""
+    global _lib_path
+    if _lib_path is not None:
+        return _lib_path
+    product = load_library()
+    if not os.path.exists(LIB_PATH_PATH):
+        raise SvgfError(f"{LIB_PATH_PATH} not found: build it first (python -c 'import __graft_entry__ as g; g.build()').")
+    lib = C.CDLL(LIB_PATH_PATH)
+    vp, ip = C.c_void_p, C.c_int
+    lib.svgf_path_version.restype = ip
+    if lib.svgf_path_version() != product.svgf_version():
+        raise SvgfError(f"libsvgf_path.so was built for ABI {lib.svgf_path_version():#x}, libsvgf_hip.so is {product.svgf_version():#x}")
+    lib.svgf_path_draw.argtypes = [vp, vp, vp, C.POINTER(SvgfPlanarGBuffer), ip, ip, C.POINTER(SvgfCamera), C.POINTER(SvgfSynthParams),
+                                   C.POINTER(SvgfSceneLight), C.POINTER(SvgfPathParams), vp]
+    lib.svgf_path_draw_split.argtypes = [vp, vp, vp, vp, vp, C.POINTER(SvgfPlanarGBuffer), ip, ip, C.POINTER(SvgfCamera), C.POINTER(SvgfSynthParams),
+                                         C.POINTER(SvgfSceneLight), C.POINTER(SvgfPathParams), vp]
+    _lib_path = lib
     return lib
 
 
@@ -1121,6 +1157,44 @@ class Scene:
                                                         C.byref(light), C.byref(tp), _stream(stream))
         if rc != SVGF_OK:
             raise SvgfError(f"svgf_trace_draw_split failed ({rc})")
+
+    def _path_call_args(self, width, height, camera, frame, paths, max_depth, rr_depth, ambient, shadow_secondary, seed, noise, fireflies,
+                        pixel_length):
+        from . import synth as _synth
+        cam = camera if isinstance(camera, SvgfCamera) else SvgfCamera.from_dict(camera)
+        if pixel_length is None:
+            fovy = camera.get("fovy_deg", 45.0) if isinstance(camera, dict) else 45.0
+            pixel_length = _synth._pixel_length(width, height, fovy)
+        sp = SvgfSynthParams(int(frame), int(seed), float(noise), float(fireflies))
+        sp.pixel_length[0], sp.pixel_length[1] = float(pixel_length[0]), float(pixel_length[1])
+        return cam, sp, SvgfPathParams(int(paths), int(max_depth), int(rr_depth), float(ambient), int(shadow_secondary))
+
+    def draw_path(self, out_rgb, out_gbuffer, width: int, height: int, camera, light, frame: int, paths: int = 1, max_depth: int = 4,
+                  rr_depth: int = 2, ambient: float = 0.15, shadow_secondary: int = 1, seed: int = 1, noise: float = 0.6,
+                  fireflies: float = 0.02, pixel_length=None, stream=None):
+        """svgf_path_draw of libsvgf_path.so (row f19): draw_traced's frame with `paths` paths of up to `max_depth` diffuse bounces per
+        pixel in the one bounce's place, Russian roulette from bounce `rr_depth` on (0: none).  One launch on `stream`; never waits."""
+        cam, sp, pp = self._path_call_args(width, height, camera, frame, paths, max_depth, rr_depth, ambient, shadow_secondary, seed, noise,
+                                           fireflies, pixel_length)
+        planar = isinstance(out_gbuffer, SvgfPlanarGBuffer)
+        rc = load_path_library().svgf_path_draw(self.h, _ptr(out_rgb), None if planar else _ptr(out_gbuffer), C.byref(out_gbuffer) if planar else None,
+                                                int(width), int(height), C.byref(cam), C.byref(sp), C.byref(light), C.byref(pp), _stream(stream))
+        if rc != SVGF_OK:
+            raise SvgfError(f"svgf_path_draw failed ({rc})")
+
+    def draw_path_split(self, out_direct, out_indirect, out_gbuffer, width: int, height: int, camera, light, frame: int, paths: int = 1,
+                        max_depth: int = 4, rr_depth: int = 2, ambient: float = 0.15, shadow_secondary: int = 1, seed: int = 1,
+                        noise: float = 0.6, fireflies: float = 0.02, pixel_length=None, out_rgb=None, stream=None):
+        """svgf_path_draw_split of libsvgf_path.so (row f19): draw_path's rays, with the direct and the indirect term written apart and
+        without the albedo; `out_rgb` (optional) receives draw_path's colour.  One launch on `stream`; never waits."""
+        cam, sp, pp = self._path_call_args(width, height, camera, frame, paths, max_depth, rr_depth, ambient, shadow_secondary, seed, noise,
+                                           fireflies, pixel_length)
+        planar = isinstance(out_gbuffer, SvgfPlanarGBuffer)
+        rc = load_path_library().svgf_path_draw_split(self.h, _ptr(out_direct), _ptr(out_indirect), _ptr(out_rgb), None if planar else _ptr(out_gbuffer),
+                                                      C.byref(out_gbuffer) if planar else None, int(width), int(height), C.byref(cam), C.byref(sp),
+                                                      C.byref(light), C.byref(pp), _stream(stream))
+        if rc != SVGF_OK:
+            raise SvgfError(f"svgf_path_draw_split failed ({rc})")
 
     def view(self) -> dict:
         """svgf_scene_view (host only): the device index, the counts and the device pointers the draws read, as integers (0 = NULL)."""
