@@ -21,6 +21,7 @@ LIB_PATH = os.path.join(_HERE, "libsvgf_hip.so")
 LIB_TRACE_PATH = os.path.join(_HERE, "libsvgf_trace.so")      # the companion library of row f17 (include/svgf_trace.h)
 LIB_SPLIT_PATH = os.path.join(_HERE, "libsvgf_split.so")      # the companion library of row f18 (include/svgf_split.h)
 LIB_PATH_PATH = os.path.join(_HERE, "libsvgf_path.so")        # the companion library of row f19 (include/svgf_path.h)
+LIB_GLOSS_PATH = os.path.join(_HERE, "libsvgf_gloss.so")      # the companion library of row f20 (include/svgf_gloss.h)
 LIB_EXP_PATH = os.path.join(_HERE, "libsvgf_hip_exp.so")     # -DSVGF_BUILD_EXPERIMENTS: parked variants + tuning table (tests / tools only)
 
 SVGF_OK = 0
@@ -58,6 +59,9 @@ TRACE_MAX_BOUNCE_SAMPLES = 8
 PATH_EXPORTS = ["svgf_path_draw", "svgf_path_draw_split", "svgf_path_version"]
 PATH_MAX_PATHS = 8
 PATH_MAX_DEPTH = 8
+# libsvgf_gloss.so (include/svgf_gloss.h, row f20)
+GLOSS_EXPORTS = ["svgf_gloss_table_create", "svgf_gloss_table_destroy", "svgf_gloss_table_size", "svgf_gloss_draw", "svgf_gloss_draw_split",
+                 "svgf_gloss_version"]
 SCENE_MAX_DEPTH = 48
 SCENE_MAX_POSED = 1024
 SCENE_REFIT_CAP = 1024
@@ -187,6 +191,12 @@ class SvgfPathParams(C.Structure):
     """svgf_path_draw / svgf_path_draw_split: paths per pixel (0..PATH_MAX_PATHS), bounces per path (1..PATH_MAX_DEPTH), the bounce
     from which Russian roulette acts (0: never), the constant term, and whether the vertices behind the first cast a shadow ray."""
     _fields_ = [("paths", C.c_int), ("max_depth", C.c_int), ("rr_depth", C.c_int), ("ambient", C.c_float), ("shadow_secondary", C.c_int)]
+
+
+class SvgfSurface(C.Structure):
+    """One record of a svgf_gloss_table (include/svgf_gloss.h, row f20), 24 bytes: the mirror lobe's probability, > 0 for glass on a
+    cube / sphere, the index of refraction, and the weight of a mirror / Fresnel reflection."""
+    _fields_ = [("reflect", C.c_float), ("refract", C.c_float), ("ior", C.c_float), ("spec", C.c_float * 3)]
 
 
 # SvgfBvhNode, 32 bytes: count > 0 a leaf over order[first : first + count], count == 0 an inner node with children first, first + 1
@@ -428,6 +438,72 @@ def load_path_library():
                                          C.POINTER(SvgfSceneLight), C.POINTER(SvgfPathParams), vp]
     _lib_path = lib
     return lib
+
+
+_lib_gloss = None
+
+
+def load_gloss_library():
+    """Load libsvgf_gloss.so (row f20; after the product library it links against) and declare its prototypes.  Fails loudly when it
+    is absent, and when it was compiled against another svgf.h than the product library found."""
+    global _lib_gloss
+    if _lib_gloss is not None:
+        return _lib_gloss
+    product = load_library()
+    if not os.path.exists(LIB_GLOSS_PATH):
+        raise SvgfError(f"{LIB_GLOSS_PATH} not found: build it first (python -c 'import __graft_entry__ as g; g.build()').")
+    lib = C.CDLL(LIB_GLOSS_PATH)
+    vp, ip = C.c_void_p, C.c_int
+    lib.svgf_gloss_version.restype = ip
+    if lib.svgf_gloss_version() != product.svgf_version():
+        raise SvgfError(f"libsvgf_gloss.so was built for ABI {lib.svgf_gloss_version():#x}, libsvgf_hip.so is {product.svgf_version():#x}")
+    lib.svgf_gloss_table_create.argtypes = [ip, C.POINTER(SvgfSurface), ip, C.POINTER(vp)]
+    lib.svgf_gloss_table_destroy.argtypes = [vp]
+    lib.svgf_gloss_table_destroy.restype = None
+    lib.svgf_gloss_table_size.argtypes = [vp]
+    lib.svgf_gloss_draw.argtypes = [vp, vp, vp, vp, C.POINTER(SvgfPlanarGBuffer), ip, ip, C.POINTER(SvgfCamera), C.POINTER(SvgfSynthParams),
+                                    C.POINTER(SvgfSceneLight), C.POINTER(SvgfPathParams), vp]
+    lib.svgf_gloss_draw_split.argtypes = [vp, vp, vp, vp, vp, vp, C.POINTER(SvgfPlanarGBuffer), ip, ip, C.POINTER(SvgfCamera),
+                                          C.POINTER(SvgfSynthParams), C.POINTER(SvgfSceneLight), C.POINTER(SvgfPathParams), vp]
+    _lib_gloss = lib
+    return lib
+
+
+class GlossTable:
+    """svgf_gloss_table: the surfaces of a scene's objects on one device, one SvgfSurface per object id.  `surfaces` is a numpy array
+    of scene.SURFACE_DTYPE (or anything np.asarray turns into one; None or empty: a table of no records).  Allocates and uploads once;
+    usable as a context manager."""
+
+    def __init__(self, surfaces=None, device: int = 0):
+        from . import scene as _scene
+        self.lib = load_gloss_library()
+        arr = np.zeros(0, _scene.SURFACE_DTYPE) if surfaces is None else np.ascontiguousarray(surfaces, dtype=_scene.SURFACE_DTYPE).reshape(-1)
+        self.h = C.c_void_p()
+        rc = self.lib.svgf_gloss_table_create(int(device), arr.ctypes.data_as(C.POINTER(SvgfSurface)), len(arr), C.byref(self.h))
+        if rc != SVGF_OK:
+            self.h = C.c_void_p()
+            raise SvgfError(f"svgf_gloss_table_create failed ({rc})")
+        self.device = int(device)
+
+    def __len__(self):
+        return int(self.lib.svgf_gloss_table_size(self.h))
+
+    def free(self):
+        if self.h:
+            self.lib.svgf_gloss_table_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.free()
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
 
 
 def _ptr(x):
@@ -1195,6 +1271,35 @@ class Scene:
                                                       C.byref(light), C.byref(pp), _stream(stream))
         if rc != SVGF_OK:
             raise SvgfError(f"svgf_path_draw_split failed ({rc})")
+
+    def draw_gloss(self, out_rgb, out_gbuffer, width: int, height: int, camera, light, frame: int, table=None, paths: int = 1,
+                   max_depth: int = 4, rr_depth: int = 2, ambient: float = 0.15, shadow_secondary: int = 1, seed: int = 1, noise: float = 0.6,
+                   fireflies: float = 0.02, pixel_length=None, stream=None):
+        """svgf_gloss_draw of libsvgf_gloss.so (row f20): draw_path's frame with the mirror and glass surfaces of `table` (a GlossTable,
+        or None: every surface diffuse, draw_path's frame on bits) along the paths.  One launch on `stream`; never waits."""
+        cam, sp, pp = self._path_call_args(width, height, camera, frame, paths, max_depth, rr_depth, ambient, shadow_secondary, seed, noise,
+                                           fireflies, pixel_length)
+        planar = isinstance(out_gbuffer, SvgfPlanarGBuffer)
+        rc = load_gloss_library().svgf_gloss_draw(self.h, table.h if table is not None else None, _ptr(out_rgb), None if planar else _ptr(out_gbuffer),
+                                                  C.byref(out_gbuffer) if planar else None, int(width), int(height), C.byref(cam), C.byref(sp),
+                                                  C.byref(light), C.byref(pp), _stream(stream))
+        if rc != SVGF_OK:
+            raise SvgfError(f"svgf_gloss_draw failed ({rc})")
+
+    def draw_gloss_split(self, out_direct, out_indirect, out_gbuffer, width: int, height: int, camera, light, frame: int, table=None,
+                         paths: int = 1, max_depth: int = 4, rr_depth: int = 2, ambient: float = 0.15, shadow_secondary: int = 1, seed: int = 1,
+                         noise: float = 0.6, fireflies: float = 0.02, pixel_length=None, out_rgb=None, stream=None):
+        """svgf_gloss_draw_split of libsvgf_gloss.so (row f20): draw_gloss's rays, with the direct and the indirect term written apart
+        and without the albedo; `out_rgb` (optional) receives draw_gloss's colour.  One launch on `stream`; never waits."""
+        cam, sp, pp = self._path_call_args(width, height, camera, frame, paths, max_depth, rr_depth, ambient, shadow_secondary, seed, noise,
+                                           fireflies, pixel_length)
+        planar = isinstance(out_gbuffer, SvgfPlanarGBuffer)
+        rc = load_gloss_library().svgf_gloss_draw_split(self.h, table.h if table is not None else None, _ptr(out_direct), _ptr(out_indirect),
+                                                        _ptr(out_rgb), None if planar else _ptr(out_gbuffer),
+                                                        C.byref(out_gbuffer) if planar else None, int(width), int(height), C.byref(cam),
+                                                        C.byref(sp), C.byref(light), C.byref(pp), _stream(stream))
+        if rc != SVGF_OK:
+            raise SvgfError(f"svgf_gloss_draw_split failed ({rc})")
 
     def view(self) -> dict:
         """svgf_scene_view (host only): the device index, the counts and the device pointers the draws read, as integers (0 = NULL)."""

@@ -31,6 +31,9 @@ SCENE_GEOM_DTYPE = np.dtype([("type", "<i4"), ("material", "<i4"), ("albedo", "<
                              ("xf", "<f4", 12), ("inv", "<f4", 12), ("invT", "<f4", 9)])
 assert SCENE_GEOM_DTYPE.itemsize == 156
 CUBE, SPHERE = 0, 1
+# SvgfSurface (include/svgf_gloss.h, row f20): one record per object id
+SURFACE_DTYPE = np.dtype([("reflect", "<f4"), ("refract", "<f4"), ("ior", "<f4"), ("spec", "<f4", 3)])
+assert SURFACE_DTYPE.itemsize == 24
 MAX_GEOMS = 64
 
 
@@ -156,6 +159,25 @@ def geom_array(scene: Scene) -> np.ndarray:
     if len(rec) > MAX_GEOMS:
         raise ValueError(f"{len(rec)} primitives, at most {MAX_GEOMS}")
     return np.array(rec, dtype=SCENE_GEOM_DTYPE)
+
+
+def surface_table(scene: Scene, ids=None) -> np.ndarray:
+    """The svgf_gloss_table records of a parsed scene: SURFACE_DTYPE[len(scene.objects)], record g filled from the material of OBJECT g
+    (the id the G-buffer carries) - REFL, REFR, REFRIOR (1 where the file has none, and where it has a value that is not > 0, as the
+    files' diffuse materials do: svgf_gloss_table_create refuses such an ior, and only a REFR > 0 reads it) and SPECRGB (0 where it has none).  Mesh objects
+    get theirs too; the draw ignores `refract` on triangles.  `ids`: only these object ids get their material, every other record is
+    the diffuse one."""
+    t = np.zeros(len(scene.objects), dtype=SURFACE_DTYPE)
+    t["ior"] = F(1.0)
+    for o in scene.objects:
+        if ids is not None and o["id"] not in ids:
+            continue
+        m = scene.materials[o["material"]]
+        r = t[o["id"]]
+        ior = F(m.get("refrior", 1.0))
+        r["reflect"], r["refract"], r["ior"] = F(m.get("refl", 0.0)), F(m.get("refr", 0.0)), ior if ior > 0 else F(1.0)
+        r["spec"] = np.array(m.get("specrgb", (0.0, 0.0, 0.0)), dtype=F)
+    return t
 
 
 def camera_for_frame(scene: Scene, frame: int, moving: bool):
