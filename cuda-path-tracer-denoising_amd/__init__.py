@@ -21,4 +21,5 @@ from .binding import SvgfSceneView, SvgfTraceParams, load_trace_library  # noqa:
 from .binding import load_split_library, trace_compose  # noqa: F401  (Scene.draw_traced_split is its other half)
 from .binding import SvgfPathParams, load_path_library  # noqa: F401  (Scene.draw_path, Scene.draw_path_split)
 from .binding import GlossTable, SvgfSurface, load_gloss_library  # noqa: F401  (Scene.draw_gloss, Scene.draw_gloss_split)
+from .binding import SvgfVirtualParams, load_virtual_library  # noqa: F401  (Scene.draw_virtual, Scene.draw_virtual_split)
 from .binding import STATE_PREV_NORMAL, STATE_PREV_POSITION, STATE_PREV_GEOM_ID, STATE_OUTPUT_HISTORY  # noqa: F401

@@ -22,6 +22,7 @@ LIB_TRACE_PATH = os.path.join(_HERE, "libsvgf_trace.so")      # the companion li
 LIB_SPLIT_PATH = os.path.join(_HERE, "libsvgf_split.so")      # the companion library of row f18 (include/svgf_split.h)
 LIB_PATH_PATH = os.path.join(_HERE, "libsvgf_path.so")        # the companion library of row f19 (include/svgf_path.h)
 LIB_GLOSS_PATH = os.path.join(_HERE, "libsvgf_gloss.so")      # the companion library of row f20 (include/svgf_gloss.h)
+LIB_VIRTUAL_PATH = os.path.join(_HERE, "libsvgf_virtual.so")  # the companion library of row f21 (include/svgf_virtual.h)
 LIB_EXP_PATH = os.path.join(_HERE, "libsvgf_hip_exp.so")     # -DSVGF_BUILD_EXPERIMENTS: parked variants + tuning table (tests / tools only)
 
 SVGF_OK = 0
@@ -62,6 +63,8 @@ PATH_MAX_DEPTH = 8
 # libsvgf_gloss.so (include/svgf_gloss.h, row f20)
 GLOSS_EXPORTS = ["svgf_gloss_table_create", "svgf_gloss_table_destroy", "svgf_gloss_table_size", "svgf_gloss_draw", "svgf_gloss_draw_split",
                  "svgf_gloss_version"]
+# libsvgf_virtual.so (include/svgf_virtual.h, row f21)
+VIRTUAL_EXPORTS = ["svgf_virtual_draw", "svgf_virtual_draw_split", "svgf_virtual_version"]
 SCENE_MAX_DEPTH = 48
 SCENE_MAX_POSED = 1024
 SCENE_REFIT_CAP = 1024
@@ -197,6 +200,12 @@ class SvgfSurface(C.Structure):
     """One record of a svgf_gloss_table (include/svgf_gloss.h, row f20), 24 bytes: the mirror lobe's probability, > 0 for glass on a
     cube / sphere, the index of refraction, and the weight of a mirror / Fresnel reflection."""
     _fields_ = [("reflect", C.c_float), ("refract", C.c_float), ("ior", C.c_float), ("spec", C.c_float * 3)]
+
+
+class SvgfVirtualParams(C.Structure):
+    """svgf_virtual_draw / svgf_virtual_draw_split (include/svgf_virtual.h, row f21): the most rays the guide chain may trace
+    (1..PATH_MAX_DEPTH) and the offset added to the geomId of a virtual hit (0..1 << 24)."""
+    _fields_ = [("max_chain", C.c_int), ("id_offset", C.c_int)]
 
 
 # SvgfBvhNode, 32 bytes: count > 0 a leaf over order[first : first + count], count == 0 an inner node with children first, first + 1
@@ -466,6 +475,32 @@ def load_gloss_library():
     lib.svgf_gloss_draw_split.argtypes = [vp, vp, vp, vp, vp, vp, C.POINTER(SvgfPlanarGBuffer), ip, ip, C.POINTER(SvgfCamera),
                                           C.POINTER(SvgfSynthParams), C.POINTER(SvgfSceneLight), C.POINTER(SvgfPathParams), vp]
     _lib_gloss = lib
+    return lib
+
+
+_lib_virtual = None
+
+
+def load_virtual_library():
+    """Load libsvgf_virtual.so (row f21; after the product library it links against) and declare its prototypes.  Fails loudly when it
+    is absent, and when it was compiled against another svgf.h than the product library found."""
+    global _lib_virtual
+    if _lib_virtual is not None:
+        return _lib_virtual
+    product = load_library()
+    if not os.path.exists(LIB_VIRTUAL_PATH):
+        raise SvgfError(f"{LIB_VIRTUAL_PATH} not found: build it first (python -c 'import __graft_entry__ as g; g.build()').")
+    lib = C.CDLL(LIB_VIRTUAL_PATH)
+    vp, ip = C.c_void_p, C.c_int
+    lib.svgf_virtual_version.restype = ip
+    if lib.svgf_virtual_version() != product.svgf_version():
+        raise SvgfError(f"libsvgf_virtual.so was built for ABI {lib.svgf_virtual_version():#x}, libsvgf_hip.so is {product.svgf_version():#x}")
+    lib.svgf_virtual_draw.argtypes = [vp, vp, vp, vp, C.POINTER(SvgfPlanarGBuffer), ip, ip, C.POINTER(SvgfCamera), C.POINTER(SvgfSynthParams),
+                                      C.POINTER(SvgfSceneLight), C.POINTER(SvgfPathParams), C.POINTER(SvgfVirtualParams), vp, vp]
+    lib.svgf_virtual_draw_split.argtypes = [vp, vp, vp, vp, vp, vp, C.POINTER(SvgfPlanarGBuffer), ip, ip, C.POINTER(SvgfCamera),
+                                            C.POINTER(SvgfSynthParams), C.POINTER(SvgfSceneLight), C.POINTER(SvgfPathParams),
+                                            C.POINTER(SvgfVirtualParams), vp, vp]
+    _lib_virtual = lib
     return lib
 
 
@@ -1300,6 +1335,41 @@ class Scene:
                                                         C.byref(sp), C.byref(light), C.byref(pp), _stream(stream))
         if rc != SVGF_OK:
             raise SvgfError(f"svgf_gloss_draw_split failed ({rc})")
+
+    def draw_virtual(self, out_rgb, out_gbuffer, width: int, height: int, camera, light, frame: int, table=None, paths: int = 1,
+                     max_depth: int = 4, rr_depth: int = 2, ambient: float = 0.15, shadow_secondary: int = 1, seed: int = 1, noise: float = 0.6,
+                     fireflies: float = 0.02, pixel_length=None, stream=None, max_chain: int = 4, id_offset: int = 0, out_chain=None):
+        """svgf_virtual_draw of libsvgf_virtual.so (row f21): draw_gloss's frame, on bits, with a G-buffer whose normal, position and
+        geomId describe what a full mirror or glass shows (a guide chain of at most `max_chain` rays; `id_offset` is added to a virtual
+        hit's id).  `out_chain` (optional) receives one int32 per pixel.  One launch on `stream`; never waits."""
+        cam, sp, pp = self._path_call_args(width, height, camera, frame, paths, max_depth, rr_depth, ambient, shadow_secondary, seed, noise,
+                                           fireflies, pixel_length)
+        vp = SvgfVirtualParams(int(max_chain), int(id_offset))
+        planar = isinstance(out_gbuffer, SvgfPlanarGBuffer)
+        rc = load_virtual_library().svgf_virtual_draw(self.h, table.h if table is not None else None, _ptr(out_rgb),
+                                                      None if planar else _ptr(out_gbuffer), C.byref(out_gbuffer) if planar else None,
+                                                      int(width), int(height), C.byref(cam), C.byref(sp), C.byref(light), C.byref(pp),
+                                                      C.byref(vp), _ptr(out_chain), _stream(stream))
+        if rc != SVGF_OK:
+            raise SvgfError(f"svgf_virtual_draw failed ({rc})")
+
+    def draw_virtual_split(self, out_direct, out_indirect, out_gbuffer, width: int, height: int, camera, light, frame: int, table=None,
+                           paths: int = 1, max_depth: int = 4, rr_depth: int = 2, ambient: float = 0.15, shadow_secondary: int = 1, seed: int = 1,
+                           noise: float = 0.6, fireflies: float = 0.02, pixel_length=None, out_rgb=None, stream=None, max_chain: int = 4,
+                           id_offset: int = 0, out_chain=None):
+        """svgf_virtual_draw_split of libsvgf_virtual.so (row f21): draw_gloss_split's D, I and colour, on bits, with draw_virtual's
+        G-buffer.  One launch on `stream`; never waits."""
+        cam, sp, pp = self._path_call_args(width, height, camera, frame, paths, max_depth, rr_depth, ambient, shadow_secondary, seed, noise,
+                                           fireflies, pixel_length)
+        vp = SvgfVirtualParams(int(max_chain), int(id_offset))
+        planar = isinstance(out_gbuffer, SvgfPlanarGBuffer)
+        rc = load_virtual_library().svgf_virtual_draw_split(self.h, table.h if table is not None else None, _ptr(out_direct), _ptr(out_indirect),
+                                                            _ptr(out_rgb), None if planar else _ptr(out_gbuffer),
+                                                            C.byref(out_gbuffer) if planar else None, int(width), int(height), C.byref(cam),
+                                                            C.byref(sp), C.byref(light), C.byref(pp), C.byref(vp), _ptr(out_chain),
+                                                            _stream(stream))
+        if rc != SVGF_OK:
+            raise SvgfError(f"svgf_virtual_draw_split failed ({rc})")
 
     def view(self) -> dict:
         """svgf_scene_view (host only): the device index, the counts and the device pointers the draws read, as integers (0 = NULL)."""

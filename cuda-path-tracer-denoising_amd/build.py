@@ -34,6 +34,10 @@ PATH_SOURCES = ["svgf_scene_path.hip"]
 # the other three stay the code objects they were; its kernel compiles the same shared texts unchanged.
 LIB_GLOSS = os.path.join(_HERE, "libsvgf_gloss.so")
 GLOSS_SOURCES = ["svgf_scene_gloss.hip"]
+# The companion library of row f21 (include/svgf_virtual.h: the glossy draws with a virtual-hit G-buffer): a fifth one; its kernel is
+# csrc/svgf_scene_gloss.inc.h's, the text libsvgf_gloss.so compiles, and that library's code object stays what it was.
+LIB_VIRTUAL = os.path.join(_HERE, "libsvgf_virtual.so")
+VIRTUAL_SOURCES = ["svgf_scene_virtual.hip"]
 HIP_SOURCES_EXPERIMENTS = ["svgf_experiments.hip", "svgf_atrous_lane_reuse.hip", "svgf_atrous_fused.hip"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unused-function"]
 # Per-file flags.  svgf_atrous_fused.hip: SimplifyCFG's common-code sinking merges the last store of the "bilinear history" branch
@@ -154,6 +158,22 @@ def build_gloss(force: bool = False) -> str:
     return LIB_GLOSS
 
 
+def build_virtual(force: bool = False) -> str:
+    """Compile csrc/svgf_scene_virtual.hip for gfx950 into cuda-path-tracer-denoising_amd/libsvgf_virtual.so, linked against the product
+    library beside it (and against no other companion: a svgf_gloss_table is read through csrc/svgf_gloss_table.h), by build_trace()'s
+    scheme."""
+    build_hip()
+    srcs = [os.path.join(CSRC, s) for s in VIRTUAL_SOURCES]
+    deps = srcs + [os.path.join(CSRC, h) for h in sorted(os.listdir(CSRC)) if h.endswith(".h")] + \
+        [os.path.join(ROOT, "include", h) for h in ("svgf.h", "svgf_trace.h", "svgf_path.h", "svgf_gloss.h", "svgf_virtual.h")] + [LIB]
+    if not force and _newer(LIB_VIRTUAL, deps):
+        return LIB_VIRTUAL
+    tmp = LIB_VIRTUAL + f".tmp{os.getpid()}"
+    _run([hipcc_path()] + HIPCC_FLAGS + srcs + ["-L", _HERE, "-lsvgf_hip", "-Wl,-rpath," + _HERE, "-Wl,-rpath,$ORIGIN", "-Wl,-s", "-o", tmp])
+    os.replace(tmp, LIB_VIRTUAL)
+    return LIB_VIRTUAL
+
+
 def build_examples(force: bool = False) -> str:
     """examples/farm.cpp (N contexts on N GPUs from one C++ process), examples/pipeline.cpp (a renderer's frame loop on the frame
     pipeline), examples/cadence.cpp (a fixed-rate loop + the effective shader clock), examples/upsample.cpp (denoise at a reduced
@@ -169,24 +189,28 @@ def build_examples(force: bool = False) -> str:
     own pipeline beside the one-image one), linked against both companion libraries; and examples/path_scene.cpp (svgf_path_draw and
     svgf_path_draw_split at depth 1 and 4, each denoised as one image and as two), linked against the path and the split library; and
     examples/gloss_scene.cpp (svgf_gloss_draw_split on a room with a mirror sphere and a glass cube, the two-context pipeline with and
-    without the history clamp, scored inside and outside the mirror), linked against the gloss and the split library."""
+    without the history clamp, scored inside and outside the mirror), linked against the gloss and the split library; and
+    examples/virtual_scene.cpp (the same room through the same pipeline with the first-hit and with the virtual-hit G-buffer of
+    svgf_virtual_draw_split), linked against the virtual, the gloss and the split library."""
     build_trace()
     build_split()
     build_path()
     build_gloss()
+    build_virtual()
     out = ""
-    for name in ("pipeline", "farm", "cadence", "upsample", "dynres", "hdr_display", "quality", "resident_scene", "animated_scene", "shadowed_scene", "traced_scene", "split_scene", "path_scene", "gloss_scene"):
+    for name in ("pipeline", "farm", "cadence", "upsample", "dynres", "hdr_display", "quality", "resident_scene", "animated_scene", "shadowed_scene", "traced_scene", "split_scene", "path_scene", "gloss_scene", "virtual_scene"):
         src = os.path.join(ROOT, "examples", name + ".cpp")
         out = os.path.join(ROOT, "examples", name)
-        traced, split, path = name in ("traced_scene", "split_scene"), name in ("split_scene", "path_scene", "gloss_scene"), name == "path_scene"
-        gloss = name == "gloss_scene"
+        traced, split, path = name in ("traced_scene", "split_scene"), name in ("split_scene", "path_scene", "gloss_scene", "virtual_scene"), name == "path_scene"
+        gloss, virt = name in ("gloss_scene", "virtual_scene"), name == "virtual_scene"
         if not force and _newer(out, [src, os.path.join(ROOT, "include", "svgf.h"), LIB] + ([os.path.join(ROOT, "include", "svgf_trace.h"), LIB_TRACE] if traced else []) +
                                 ([os.path.join(ROOT, "include", "svgf_split.h"), LIB_SPLIT] if split else []) +
                                 ([os.path.join(ROOT, "include", "svgf_path.h"), LIB_PATH] if path else []) +
-                                ([os.path.join(ROOT, "include", "svgf_gloss.h"), os.path.join(ROOT, "include", "svgf_path.h"), LIB_GLOSS] if gloss else [])):
+                                ([os.path.join(ROOT, "include", "svgf_gloss.h"), os.path.join(ROOT, "include", "svgf_path.h"), LIB_GLOSS] if gloss else []) +
+                                ([os.path.join(ROOT, "include", "svgf_virtual.h"), LIB_VIRTUAL] if virt else [])):
             continue
         tmp = out + f".tmp{os.getpid()}"
-        _run([hipcc_path(), "--offload-arch=gfx950", "-O2", "-I", os.path.join(ROOT, "include"), src, "-L", _HERE] + (["-lsvgf_gloss"] if gloss else []) + (["-lsvgf_path"] if path else []) + (["-lsvgf_split"] if split else []) + (["-lsvgf_trace"] if traced else []) + ["-lsvgf_hip",
+        _run([hipcc_path(), "--offload-arch=gfx950", "-O2", "-I", os.path.join(ROOT, "include"), src, "-L", _HERE] + (["-lsvgf_virtual"] if virt else []) + (["-lsvgf_gloss"] if gloss else []) + (["-lsvgf_path"] if path else []) + (["-lsvgf_split"] if split else []) + (["-lsvgf_trace"] if traced else []) + ["-lsvgf_hip",
               "-Wl,-rpath," + _HERE, "-Wl,-rpath,$ORIGIN/../cuda-path-tracer-denoising_amd", "-o", tmp])
         os.replace(tmp, out)
     return out

@@ -2,19 +2,15 @@
 // paths with a mirror and a glass lobe at every vertex, chosen per object from a table of SvgfSurface records (svgf_gloss_table_*).
 // include/svgf_gloss.h states the semantics.  Like the other three companions this one links against libsvgf_hip.so and reaches a scene
 // through svgf_scene_view alone.  Every ray, sampled direction and stored pixel is svgf_scene_trace.inc.h's text (and through it
-// svgf_scene_pixel.inc.h's and svgf_scene_walk.inc.h's).  What is new here is gloss_vertex (the class of a vertex and the direction a
-// specular one sends the path on in) and the loop that strings vertices into a path.
+// svgf_scene_pixel.inc.h's and svgf_scene_walk.inc.h's).  What row f20 added - gloss_vertex (the class of a vertex and the direction a
+// specular one sends the path on in) and the loop that strings vertices into a path - is svgf_scene_gloss.inc.h's text, which
+// libsvgf_virtual.so (row f21) compiles too; this file keeps the table and the two draws.
 //
-// k_scene_gloss: one thread per pixel, 256 per block, every ray of the pixel on the per-lane LDS stack stack[level][lane] (48 x 256 x 4 B;
-// empty between rays).  Paths and vertices are runtime loops around ONE vertex body - classify, gather, throughput, roulette, next ray,
-// nearest hit - so the code object holds one closest-hit walk and one any-hit walk behind the first hit whatever the counts and
-// whatever the classes: the class selects how d', thr and acc are formed, not a second copy of a walk.  A path's state is scalars in
-// registers - thr, acc, the vertex, its normal, albedo and id, the direction that arrived, the inside bit - no runtime-indexed private
-// array, no scratch, no spinning, no traffic between workgroups.
+// k_scene_gloss: one thread per pixel, 256 per block; svgf_scene_gloss.inc.h describes the pixel.
 #include "svgf_kernels.h"
 #include "../../include/svgf_trace.h"
 #include "../../include/svgf_path.h"
-#include "../../include/svgf_gloss.h"
+#include "svgf_gloss_table.h"
 
 #include <hip/hip_runtime.h>
 
@@ -23,224 +19,11 @@
 #include <new>
 #include <type_traits>
 
-struct svgf_gloss_table {
-    int device, n;
-    SvgfSurface *dev;           // n records on `device` (null with n == 0)
-};
-
 namespace {
 
 #include "svgf_scene_trace.inc.h"
 
-// t (and for the split form s.t).bounce_samples carries `paths`
-struct SceneGlossArgs {
-    SceneTraceArgs t;
-    int max_depth, rr_depth;
-    const SvgfSurface *table;
-    int n_table;
-};
-
-struct SceneGlossSplitArgs {
-    SceneSplitArgs s;
-    int max_depth, rr_depth;
-    const SvgfSurface *table;
-    int n_table;
-};
-
-__device__ __forceinline__ const SceneTraceArgs &trace_args(const SceneGlossArgs &a) { return a.t; }
-__device__ __forceinline__ const SceneTraceArgs &trace_args(const SceneGlossSplitArgs &a) { return a.s.t; }
-
-// the surface of object id g: the table's record, or the diffuse one (all fields 0) outside it
-__device__ __forceinline__ SvgfSurface gloss_surface(const SvgfSurface *table, int n_table, int g)
-{
-    SvgfSurface S = { 0.0f, 0.0f, 0.0f, { 0.0f, 0.0f, 0.0f } };
-    if (g >= 0 && g < n_table) S = table[g];
-    return S;
-}
-
-// The class of a vertex with surface S and normal n, reached along d, from the stream value u: false = diffuse (dn, wgt = 1 and
-// `moved` untouched or unused); true = specular, with the direction dn the path goes on in, the weight wgt of the lobe, and, for a
-// transmission, `inside` toggled and `moved` set (the ray starts behind the surface, along -nn).  nn is written for a glass vertex.
-__device__ __forceinline__ bool gloss_vertex(const SvgfSurface &S, bool triangle, const float d[3], const float n[3], float u, bool &inside,
-                                             float dn[3], float wgt[3], float nn[3], bool &moved)
-{
-#pragma clang fp contract(off)
-    moved = false;
-    wgt[0] = 1.0f; wgt[1] = 1.0f; wgt[2] = 1.0f;
-    const bool glass = S.refract > 0.0f && !triangle;
-    const float dotn = (d[0] * n[0] + d[1] * n[1]) + d[2] * n[2];
-    if (glass) {
-        const bool flip = dotn > 0.0f;
-        for (int c = 0; c < 3; c++) nn[c] = flip ? -n[c] : n[c];
-        const float eta = inside ? S.ior : 1.0f / S.ior;
-        const float dnn = (d[0] * nn[0] + d[1] * nn[1]) + d[2] * nn[2];
-        const float cs = -dnn;
-        const float r0 = (1.0f - eta) / (1.0f + eta), R0 = r0 * r0;
-        const float m = 1.0f - cs;
-        const float R = R0 + (1.0f - R0) * (((m * m) * (m * m)) * m);
-        const float k2 = 1.0f - (eta * eta) * (1.0f - cs * cs);
-        if (!(k2 >= 0.0f) || u < R) {
-            const float f = 2.0f * dnn;
-            for (int c = 0; c < 3; c++) { dn[c] = d[c] - f * nn[c]; wgt[c] = S.spec[c]; }
-        } else {
-            const float f = eta * cs - sqrtf(k2);
-            for (int c = 0; c < 3; c++) dn[c] = eta * d[c] + f * nn[c];
-            inside = !inside;
-            moved = true;
-        }
-        normalise3(dn);
-        return true;
-    }
-    if (u < S.reflect) {
-        const float f = 2.0f * dotn;
-        for (int c = 0; c < 3; c++) { dn[c] = d[c] - f * n[c]; wgt[c] = S.spec[c]; }
-        normalise3(dn);
-        return true;
-    }
-    return false;
-}
-
-// Args = SceneGlossArgs: svgf_gloss_draw.  Args = SceneGlossSplitArgs: svgf_gloss_draw_split, the same rays with trace_store_split's tail.
-template <class Args>
-__global__ __launch_bounds__(256) void k_scene_gloss(Args args)
-{
-#pragma clang fp contract(off)
-    constexpr bool SPLIT = std::is_same<Args, SceneGlossSplitArgs>::value;
-    __shared__ int stack[SVGF_SCENE_MAX_DEPTH * 256];
-    const SceneTraceArgs &arg = trace_args(args);
-    const SceneBvhArgs &b = arg.b;
-    const SceneArgs &a = b.s;
-    const int p = blockIdx.x * 256 + threadIdx.x;
-    if (p < a.W * a.H) {
-        int *const stk = stack + threadIdx.x;
-        // the first hit: k_scene_path's statements
-        SceneRay r;
-        scene_ray(a, p % a.W, p / a.W, r.o, r.d);
-        const float d0[3] = { r.d[0], r.d[1], r.d[2] };
-        SceneHit h;
-        scene_primitives(a, r.o, r.d, h);
-        trace_aim(r);
-        int best = -1;
-        float bt = h.t_best, bbx = 0.0f, bby = 0.0f;
-        scene_nearest(b, r, stk, 0.0f, bt, best, bbx, bby);
-        float pos[3];
-        scene_surface(a, r.o, r.d, h, best, bt, bbx, bby, pos);
-
-        float shade[3] = { h.emit, h.emit, h.emit };
-        float first_term = h.emit, ind_term[3] = { 0.0f, 0.0f, 0.0f };
-        bool bounced = false;
-        if (!(h.emit > 0.0f)) {
-            const bool casts = h.gid >= 0;
-            // the diffuse share of the first hit's surface weighs the first term; a share of 0 casts no shadow ray
-            const SvgfSurface S0 = gloss_surface(args.table, args.n_table, h.gid);
-            const float w_d = (S0.refract > 0.0f && best < 0) ? 0.0f : 1.0f - S0.reflect;
-            float first = 0.0f;
-            if (w_d != 0.0f) {
-                int unoccluded = arg.samples;
-                if (casts) {
-                    unoccluded = 0;
-                    for (int c = 0; c < 3; c++) r.o[c] = pos[c];
-                    for (int s = 0; s < arg.samples; s++)
-                        unoccluded += scene_shadow_sample(b, arg.edge_u, arg.edge_v, r, pos, stk, p, 8 + 2 * s, 9 + 2 * s) ? 0 : 1;
-                }
-                const float vis = (float)unoccluded / (float)arg.samples;
-                first = w_d * (arg.ambient + vis * scene_direct(a, h.n, pos));
-            }
-            shade[0] = first; shade[1] = first; shade[2] = first;
-            first_term = first;
-            const int paths = arg.bounce_samples;
-            if (casts && paths > 0) {
-                float ind[3] = { 0.0f, 0.0f, 0.0f };
-                for (int j = 0; j < paths; j++) {
-                    float thr[3] = { 1.0f, 1.0f, 1.0f }, acc[3] = { 0.0f, 0.0f, 0.0f };
-                    float x[3] = { pos[0], pos[1], pos[2] }, n[3] = { h.n[0], h.n[1], h.n[2] }, alb[3] = { h.alb[0], h.alb[1], h.alb[2] };
-                    float d[3] = { d0[0], d0[1], d0[2] };
-                    int gid = h.gid;
-                    bool triangle = best >= 0, inside = false;
-                    // cb: the class stream of vertex v.  Behind the first hit f19's base is cb - 11: the shadow ray of the vertex reads
-                    // cb - 3 and cb - 2, its roulette cb - 1; the direction sampled AT vertex v reads cb + 117 + 0..7 (f19's next base)
-                    unsigned cb = 139u + 16u * (unsigned)j;
-                    for (int v = 0; ; v++, cb += 128u) {
-                        // vertex v: a hit that is no emitter
-                        const SvgfSurface S = gloss_surface(args.table, args.n_table, gid);
-                        float dn[3] = { 0.0f, 0.0f, 0.0f }, wgt[3], nn[3] = { 0.0f, 0.0f, 0.0f };
-                        bool moved;
-                        const bool specular = gloss_vertex(S, triangle, d, n, scene_hash(a.seed, a.frame, (unsigned)p, cb), inside, dn, wgt, nn, moved);
-                        if (v >= 1) {
-                            if (!specular) {
-                                bool occluded = false;
-                                if (arg.shadow_secondary) {
-                                    for (int c = 0; c < 3; c++) r.o[c] = x[c];
-                                    occluded = scene_shadow_sample(b, arg.edge_u, arg.edge_v, r, x, stk, p, cb - 3u, cb - 2u);
-                                }
-                                const float L = arg.ambient + (occluded ? 0.0f : 1.0f) * scene_direct(a, n, x);
-                                for (int c = 0; c < 3; c++) acc[c] = acc[c] + thr[c] * (alb[c] * L);
-                            }
-                            if (v >= args.max_depth) break;
-                            for (int c = 0; c < 3; c++) thr[c] = thr[c] * (alb[c] * wgt[c]);
-                            if (args.rr_depth > 0 && v >= args.rr_depth) {
-                                const float rq = fminf(fmaxf(fmaxf(thr[0], thr[1]), thr[2]), 1.0f);
-                                if (!(rq > 0.0f && scene_hash(a.seed, a.frame, (unsigned)p, cb - 1u) < rq)) break;
-                                for (int c = 0; c < 3; c++) thr[c] = thr[c] / rq;
-                            }
-                        } else {
-                            for (int c = 0; c < 3; c++) thr[c] = wgt[c];        // the store applies the first hit's albedo
-                        }
-                        // the ray that leaves vertex v
-                        const float t_lo = 0x1p-10f * fmaxf(1.0f, fmaxf(fmaxf(fabsf(x[0]), fabsf(x[1])), fabsf(x[2])));
-                        if (specular) {
-                            const float back = -(4.0f * t_lo);
-                            for (int c = 0; c < 3; c++) { r.o[c] = moved ? x[c] + back * nn[c] : x[c]; r.d[c] = dn[c]; }
-                        } else {
-                            const float s = copysignf(1.0f, n[2]), q = -1.0f / (s + n[2]), w = (n[0] * n[1]) * q;
-                            const float T[3] = { 1.0f + ((s * n[0]) * n[0]) * q, s * w, -(s * n[0]) };
-                            const float B[3] = { w, s + (n[1] * n[1]) * q, -n[1] };
-                            for (int c = 0; c < 3; c++) r.o[c] = x[c];
-                            trace_direction(a, p, cb + 117u, n, T, B, r.d);
-                        }
-                        for (int c = 0; c < 3; c++) d[c] = r.d[c];
-                        trace_aim(r);
-                        SceneHit h2;
-                        scene_primitives_beyond(a, r.o, r.d, t_lo, h2);
-                        int best2 = -1;
-                        float bt2 = h2.t_best, bbx2 = 0.0f, bby2 = 0.0f;
-                        scene_nearest(b, r, stk, t_lo, bt2, best2, bbx2, bby2);
-                        scene_surface(a, r.o, r.d, h2, best2, bt2, bbx2, bby2, x);
-                        if (h2.gid < 0) break;                  // a miss
-                        if (h2.emit > 0.0f) {                   // an emitter, before its surface is looked at
-                            for (int c = 0; c < 3; c++) acc[c] = acc[c] + thr[c] * (h2.alb[c] * h2.emit);
-                            break;
-                        }
-                        for (int c = 0; c < 3; c++) { n[c] = h2.n[c]; alb[c] = h2.alb[c]; }
-                        gid = h2.gid;
-                        triangle = best2 >= 0;
-                    }
-                    for (int c = 0; c < 3; c++) ind[c] = ind[c] + acc[c];
-                }
-                for (int c = 0; c < 3; c++) { ind_term[c] = ind[c] / (float)paths; shade[c] = first + ind_term[c]; }
-                bounced = true;
-            }
-        }
-        if constexpr (SPLIT) trace_store_split(args.s, p, h, pos, first_term, ind_term, bounced, shade);
-        else scene_store(a, p, h, pos, shade[0], shade[1], shade[2]);
-    }
-}
-
-// svgf_path_draw's refusals: trace_prepare's with pp in tp's place (paths is checked behind them), then the path parameters
-int gloss_prepare(SceneTraceArgs &t, int &device, const svgf_scene *scene, void *out_rgb_dev, bool rgb_required, void *out_gbuffer_dev,
-                  const SvgfPlanarGBuffer *planes, int width, int height, const SvgfCamera *cam, const SvgfSynthParams *sp,
-                  const SvgfSceneLight *light, const SvgfPathParams *pp)
-{
-    SvgfTraceParams tp = { 0, 0.0f, 0 };
-    if (pp) { tp.ambient = pp->ambient; tp.shadow_secondary = pp->shadow_secondary; }
-    return trace_prepare(t, device, scene, out_rgb_dev, rgb_required, out_gbuffer_dev, planes, width, height, cam, sp, light, pp ? &tp : nullptr);
-}
-
-bool gloss_params_ok(const SvgfPathParams *pp)
-{
-    return pp->paths >= 0 && pp->paths <= SVGF_PATH_MAX_PATHS && pp->max_depth >= 1 && pp->max_depth <= SVGF_PATH_MAX_DEPTH &&
-           pp->rr_depth >= 0 && pp->rr_depth <= SVGF_PATH_MAX_DEPTH;
-}
+#include "svgf_scene_gloss.inc.h"
 
 bool surface_ok(const SvgfSurface &s)
 {
@@ -303,14 +86,10 @@ extern "C" int svgf_gloss_draw(const svgf_scene *scene, const svgf_gloss_table *
 {
     SceneGlossArgs t;
     int device = 0;
-    const int rc = gloss_prepare(t.t, device, scene, out_rgb_dev, true, out_gbuffer_dev, planes, width, height, cam, sp, light, pp);
+    const int rc = gloss_draw_args(t, device, scene, table, out_rgb_dev, out_gbuffer_dev, planes, width, height, cam, sp, light, pp);
     if (rc != SVGF_OK) return rc;
-    if (!gloss_params_ok(pp)) return SVGF_ERR_INVALID_ARG;
-    if (table && table->device != device) return SVGF_ERR_INVALID_ARG;
     SvgfDeviceGuard dev_guard(device);
     if (!dev_guard.ok) return SVGF_ERR_NO_DEVICE;
-    t.t.bounce_samples = pp->paths; t.max_depth = pp->max_depth; t.rr_depth = pp->rr_depth;
-    t.table = table ? table->dev : nullptr; t.n_table = table ? table->n : 0;
     const int n = width * height;
     hipLaunchKernelGGL(k_scene_gloss<SceneGlossArgs>, dim3((n + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), t);
     return hipGetLastError() == hipSuccess ? SVGF_OK : SVGF_ERR_HIP;
@@ -323,16 +102,11 @@ extern "C" int svgf_gloss_draw_split(const svgf_scene *scene, const svgf_gloss_t
 {
     SceneGlossSplitArgs s;
     int device = 0;
-    const int rc = gloss_prepare(s.s.t, device, scene, out_rgb_dev, false, out_gbuffer_dev, planes, width, height, cam, sp, light, pp);
+    const int rc = gloss_draw_split_args(s, device, scene, table, out_direct_dev, out_indirect_dev, out_rgb_dev, out_gbuffer_dev, planes, width,
+                                         height, cam, sp, light, pp);
     if (rc != SVGF_OK) return rc;
-    if (!out_direct_dev || !out_indirect_dev || out_direct_dev == out_indirect_dev) return SVGF_ERR_INVALID_ARG;
-    if (!gloss_params_ok(pp)) return SVGF_ERR_INVALID_ARG;
-    if (table && table->device != device) return SVGF_ERR_INVALID_ARG;
     SvgfDeviceGuard dev_guard(device);
     if (!dev_guard.ok) return SVGF_ERR_NO_DEVICE;
-    s.s.out_direct = static_cast<float *>(out_direct_dev); s.s.out_indirect = static_cast<float *>(out_indirect_dev);
-    s.s.t.bounce_samples = pp->paths; s.max_depth = pp->max_depth; s.rr_depth = pp->rr_depth;
-    s.table = table ? table->dev : nullptr; s.n_table = table ? table->n : 0;
     const int n = width * height;
     hipLaunchKernelGGL(k_scene_gloss<SceneGlossSplitArgs>, dim3((n + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), s);
     return hipGetLastError() == hipSuccess ? SVGF_OK : SVGF_ERR_HIP;

@@ -56,7 +56,7 @@
  *     no ray reaches changes no bit.
  * Limits: a camera inside glass starts with inside = false and so refracts the wrong way; overlapping glass objects share the one
  *   bit; glass meshes are mirrors at most (see above).  The G-buffer is the first hit's: what a mirror or a pane shows moves
- *   independently of it, which a temporal filter sees as ghosting (examples/gloss_scene.cpp; a virtual-hit G-buffer is the follow-up).
+ *   independently of it, which a temporal filter sees as ghosting (examples/gloss_scene.cpp; svgf_virtual.h, row f21, draws a virtual-hit one).
  * INTEGRATION.md 5n has the frame loop and the link line, examples/gloss_scene.cpp runs it. */
 #ifndef SVGF_GLOSS_H_
 #define SVGF_GLOSS_H_
