@@ -22,4 +22,5 @@ from .binding import load_split_library, trace_compose  # noqa: F401  (Scene.dra
 from .binding import SvgfPathParams, load_path_library  # noqa: F401  (Scene.draw_path, Scene.draw_path_split)
 from .binding import GlossTable, SvgfSurface, load_gloss_library  # noqa: F401  (Scene.draw_gloss, Scene.draw_gloss_split)
 from .binding import SvgfVirtualParams, load_virtual_library  # noqa: F401  (Scene.draw_virtual, Scene.draw_virtual_split)
+from .binding import RoughTable, SvgfRoughParams, load_rough_library  # noqa: F401  (Scene.draw_rough, Scene.draw_rough_split)
 from .binding import STATE_PREV_NORMAL, STATE_PREV_POSITION, STATE_PREV_GEOM_ID, STATE_OUTPUT_HISTORY  # noqa: F401

@@ -23,6 +23,7 @@ LIB_SPLIT_PATH = os.path.join(_HERE, "libsvgf_split.so")      # the companion li
 LIB_PATH_PATH = os.path.join(_HERE, "libsvgf_path.so")        # the companion library of row f19 (include/svgf_path.h)
 LIB_GLOSS_PATH = os.path.join(_HERE, "libsvgf_gloss.so")      # the companion library of row f20 (include/svgf_gloss.h)
 LIB_VIRTUAL_PATH = os.path.join(_HERE, "libsvgf_virtual.so")  # the companion library of row f21 (include/svgf_virtual.h)
+LIB_ROUGH_PATH = os.path.join(_HERE, "libsvgf_rough.so")  # the companion library of row f22 (include/svgf_rough.h)
 LIB_EXP_PATH = os.path.join(_HERE, "libsvgf_hip_exp.so")     # -DSVGF_BUILD_EXPERIMENTS: parked variants + tuning table (tests / tools only)
 
 SVGF_OK = 0
@@ -65,6 +66,9 @@ GLOSS_EXPORTS = ["svgf_gloss_table_create", "svgf_gloss_table_destroy", "svgf_gl
                  "svgf_gloss_version"]
 # libsvgf_virtual.so (include/svgf_virtual.h, row f21)
 VIRTUAL_EXPORTS = ["svgf_virtual_draw", "svgf_virtual_draw_split", "svgf_virtual_version"]
+# libsvgf_rough.so (include/svgf_rough.h, row f22)
+ROUGH_EXPORTS = ["svgf_rough_table_create", "svgf_rough_table_destroy", "svgf_rough_table_size", "svgf_rough_draw", "svgf_rough_draw_split",
+                 "svgf_rough_version"]
 SCENE_MAX_DEPTH = 48
 SCENE_MAX_POSED = 1024
 SCENE_REFIT_CAP = 1024
@@ -206,6 +210,12 @@ class SvgfVirtualParams(C.Structure):
     """svgf_virtual_draw / svgf_virtual_draw_split (include/svgf_virtual.h, row f21): the most rays the guide chain may trace
     (1..PATH_MAX_DEPTH) and the offset added to the geomId of a virtual hit (0..1 << 24)."""
     _fields_ = [("max_chain", C.c_int), ("id_offset", C.c_int)]
+
+
+class SvgfRoughParams(C.Structure):
+    """svgf_rough_draw / svgf_rough_draw_split (include/svgf_rough.h, row f22): the guide follows a full mirror whose roughness is at
+    most guide_alpha (>= 0)."""
+    _fields_ = [("guide_alpha", C.c_float)]
 
 
 # SvgfBvhNode, 32 bytes: count > 0 a leaf over order[first : first + count], count == 0 an inner node with children first, first + 1
@@ -502,6 +512,73 @@ def load_virtual_library():
                                             C.POINTER(SvgfVirtualParams), vp, vp]
     _lib_virtual = lib
     return lib
+
+
+_lib_rough = None
+
+
+def load_rough_library():
+    """Load libsvgf_rough.so (row f22; after the product library it links against) and declare its prototypes.  Fails loudly when it
+    is absent, and when it was compiled against another svgf.h than the product library found."""
+    global _lib_rough
+    if _lib_rough is not None:
+        return _lib_rough
+    product = load_library()
+    if not os.path.exists(LIB_ROUGH_PATH):
+        raise SvgfError(f"{LIB_ROUGH_PATH} not found: build it first (python -c 'import __graft_entry__ as g; g.build()').")
+    lib = C.CDLL(LIB_ROUGH_PATH)
+    vp, ip = C.c_void_p, C.c_int
+    lib.svgf_rough_version.restype = ip
+    if lib.svgf_rough_version() != product.svgf_version():
+        raise SvgfError(f"libsvgf_rough.so was built for ABI {lib.svgf_rough_version():#x}, libsvgf_hip.so is {product.svgf_version():#x}")
+    lib.svgf_rough_table_create.argtypes = [ip, C.POINTER(C.c_float), ip, C.POINTER(vp)]
+    lib.svgf_rough_table_destroy.argtypes = [vp]
+    lib.svgf_rough_table_destroy.restype = None
+    lib.svgf_rough_table_size.argtypes = [vp]
+    lib.svgf_rough_draw.argtypes = [vp, vp, vp, vp, C.POINTER(SvgfPlanarGBuffer), ip, ip, C.POINTER(SvgfCamera), C.POINTER(SvgfSynthParams),
+                                    C.POINTER(SvgfSceneLight), C.POINTER(SvgfPathParams), C.POINTER(SvgfVirtualParams), vp, vp, vp,
+                                    C.POINTER(SvgfRoughParams)]
+    lib.svgf_rough_draw_split.argtypes = [vp, vp, vp, vp, vp, vp, C.POINTER(SvgfPlanarGBuffer), ip, ip, C.POINTER(SvgfCamera),
+                                          C.POINTER(SvgfSynthParams), C.POINTER(SvgfSceneLight), C.POINTER(SvgfPathParams),
+                                          C.POINTER(SvgfVirtualParams), vp, vp, vp, C.POINTER(SvgfRoughParams)]
+    _lib_rough = lib
+    return lib
+
+
+class RoughTable:
+    """svgf_rough_table: the GGX roughness of a scene's objects on one device, one float32 per object id, 0 = smooth.  `alpha` is
+    anything np.asarray turns into float32 (None or empty: a table of no entries).  Allocates and uploads once; usable as a context
+    manager."""
+
+    def __init__(self, alpha=None, device: int = 0):
+        self.lib = load_rough_library()
+        arr = np.zeros(0, np.float32) if alpha is None else np.ascontiguousarray(alpha, dtype=np.float32).reshape(-1)
+        self.h = C.c_void_p()
+        rc = self.lib.svgf_rough_table_create(int(device), arr.ctypes.data_as(C.POINTER(C.c_float)), len(arr), C.byref(self.h))
+        if rc != SVGF_OK:
+            self.h = C.c_void_p()
+            raise SvgfError(f"svgf_rough_table_create failed ({rc})")
+        self.device = int(device)
+
+    def __len__(self):
+        return int(self.lib.svgf_rough_table_size(self.h))
+
+    def free(self):
+        if self.h:
+            self.lib.svgf_rough_table_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.free()
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
 
 
 class GlossTable:
@@ -1370,6 +1447,43 @@ class Scene:
                                                             _stream(stream))
         if rc != SVGF_OK:
             raise SvgfError(f"svgf_virtual_draw_split failed ({rc})")
+
+    def draw_rough(self, out_rgb, out_gbuffer, width: int, height: int, camera, light, frame: int, table=None, paths: int = 1,
+                   max_depth: int = 4, rr_depth: int = 2, ambient: float = 0.15, shadow_secondary: int = 1, seed: int = 1, noise: float = 0.6,
+                   fireflies: float = 0.02, pixel_length=None, stream=None, max_chain: int = 4, id_offset: int = 0, out_chain=None, rough=None,
+                   guide_alpha: float = 0.0):
+        """svgf_rough_draw of libsvgf_rough.so (row f22): draw_virtual with a GGX lobe on the mirror vertices of the objects the
+        RoughTable `rough` gives a roughness; the guide follows a full mirror no rougher than `guide_alpha`.  With rough=None it is
+        draw_virtual's frame on bits.  One launch on `stream`; never waits."""
+        cam, sp, pp = self._path_call_args(width, height, camera, frame, paths, max_depth, rr_depth, ambient, shadow_secondary, seed, noise,
+                                           fireflies, pixel_length)
+        vp, rp = SvgfVirtualParams(int(max_chain), int(id_offset)), SvgfRoughParams(float(guide_alpha))
+        planar = isinstance(out_gbuffer, SvgfPlanarGBuffer)
+        rc = load_rough_library().svgf_rough_draw(self.h, table.h if table is not None else None, _ptr(out_rgb),
+                                                  None if planar else _ptr(out_gbuffer), C.byref(out_gbuffer) if planar else None,
+                                                  int(width), int(height), C.byref(cam), C.byref(sp), C.byref(light), C.byref(pp),
+                                                  C.byref(vp), _ptr(out_chain), _stream(stream), rough.h if rough is not None else None,
+                                                  C.byref(rp))
+        if rc != SVGF_OK:
+            raise SvgfError(f"svgf_rough_draw failed ({rc})")
+
+    def draw_rough_split(self, out_direct, out_indirect, out_gbuffer, width: int, height: int, camera, light, frame: int, table=None,
+                         paths: int = 1, max_depth: int = 4, rr_depth: int = 2, ambient: float = 0.15, shadow_secondary: int = 1, seed: int = 1,
+                         noise: float = 0.6, fireflies: float = 0.02, pixel_length=None, out_rgb=None, stream=None, max_chain: int = 4,
+                         id_offset: int = 0, out_chain=None, rough=None, guide_alpha: float = 0.0):
+        """svgf_rough_draw_split of libsvgf_rough.so (row f22): draw_virtual_split with draw_rough's lobe and guide.  One launch on
+        `stream`; never waits."""
+        cam, sp, pp = self._path_call_args(width, height, camera, frame, paths, max_depth, rr_depth, ambient, shadow_secondary, seed, noise,
+                                           fireflies, pixel_length)
+        vp, rp = SvgfVirtualParams(int(max_chain), int(id_offset)), SvgfRoughParams(float(guide_alpha))
+        planar = isinstance(out_gbuffer, SvgfPlanarGBuffer)
+        rc = load_rough_library().svgf_rough_draw_split(self.h, table.h if table is not None else None, _ptr(out_direct), _ptr(out_indirect),
+                                                        _ptr(out_rgb), None if planar else _ptr(out_gbuffer),
+                                                        C.byref(out_gbuffer) if planar else None, int(width), int(height), C.byref(cam),
+                                                        C.byref(sp), C.byref(light), C.byref(pp), C.byref(vp), _ptr(out_chain),
+                                                        _stream(stream), rough.h if rough is not None else None, C.byref(rp))
+        if rc != SVGF_OK:
+            raise SvgfError(f"svgf_rough_draw_split failed ({rc})")
 
     def view(self) -> dict:
         """svgf_scene_view (host only): the device index, the counts and the device pointers the draws read, as integers (0 = NULL)."""

@@ -38,6 +38,10 @@ GLOSS_SOURCES = ["svgf_scene_gloss.hip"]
 # csrc/svgf_scene_gloss.inc.h's, the text libsvgf_gloss.so compiles, and that library's code object stays what it was.
 LIB_VIRTUAL = os.path.join(_HERE, "libsvgf_virtual.so")
 VIRTUAL_SOURCES = ["svgf_scene_virtual.hip"]
+# The companion library of row f22 (include/svgf_rough.h: the virtual-hit draws with a GGX lobe on rough mirrors): a sixth one; its
+# kernel is csrc/svgf_scene_gloss.inc.h's too, and the gloss and the virtual library's code objects stay what they were.
+LIB_ROUGH = os.path.join(_HERE, "libsvgf_rough.so")
+ROUGH_SOURCES = ["svgf_scene_rough.hip"]
 HIP_SOURCES_EXPERIMENTS = ["svgf_experiments.hip", "svgf_atrous_lane_reuse.hip", "svgf_atrous_fused.hip"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unused-function"]
 # Per-file flags.  svgf_atrous_fused.hip: SimplifyCFG's common-code sinking merges the last store of the "bilinear history" branch
@@ -174,6 +178,26 @@ def build_virtual(force: bool = False) -> str:
     return LIB_VIRTUAL
 
 
+def build_rough(force: bool = False) -> str:
+    """Compile csrc/svgf_scene_rough.hip for gfx950 into cuda-path-tracer-denoising_amd/libsvgf_rough.so, linked against the product
+    library beside it (and against no other companion), by build_trace()'s scheme."""
+    build_hip()
+    srcs = [os.path.join(CSRC, s) for s in ROUGH_SOURCES]
+    deps = srcs + [os.path.join(CSRC, h) for h in sorted(os.listdir(CSRC)) if h.endswith(".h")] + \
+        [os.path.join(ROOT, "include", h) for h in ("svgf.h", "svgf_trace.h", "svgf_path.h", "svgf_gloss.h", "svgf_virtual.h", "svgf_rough.h")] + [LIB]
+    if not force and _newer(LIB_ROUGH, deps):
+        return LIB_ROUGH
+    tmp = LIB_ROUGH + f".tmp{os.getpid()}"
+    _run([hipcc_path()] + HIPCC_FLAGS + srcs + ["-L", _HERE, "-lsvgf_hip", "-Wl,-rpath," + _HERE, "-Wl,-rpath,$ORIGIN", "-Wl,-s", "-o", tmp])
+    os.replace(tmp, LIB_ROUGH)
+    return LIB_ROUGH
+
+
+def build_all(force: bool = False) -> list[str]:
+    """The product library and the six companion libraries, in the order they were added."""
+    return [build_hip(force), build_trace(force), build_split(force), build_path(force), build_gloss(force), build_virtual(force), build_rough(force)]
+
+
 def build_examples(force: bool = False) -> str:
     """examples/farm.cpp (N contexts on N GPUs from one C++ process), examples/pipeline.cpp (a renderer's frame loop on the frame
     pipeline), examples/cadence.cpp (a fixed-rate loop + the effective shader clock), examples/upsample.cpp (denoise at a reduced
@@ -191,26 +215,30 @@ def build_examples(force: bool = False) -> str:
     examples/gloss_scene.cpp (svgf_gloss_draw_split on a room with a mirror sphere and a glass cube, the two-context pipeline with and
     without the history clamp, scored inside and outside the mirror), linked against the gloss and the split library; and
     examples/virtual_scene.cpp (the same room through the same pipeline with the first-hit and with the virtual-hit G-buffer of
-    svgf_virtual_draw_split), linked against the virtual, the gloss and the split library."""
+    svgf_virtual_draw_split), linked against the virtual, the gloss and the split library; and examples/rough_scene.cpp (that room with
+    a rough floor through the same pipeline, svgf_rough_draw_split with guide_alpha 0 and 1, with and without the firefly filter and the
+    history clamp), linked against the rough, the gloss and the split library."""
     build_trace()
     build_split()
     build_path()
     build_gloss()
     build_virtual()
+    build_rough()
     out = ""
-    for name in ("pipeline", "farm", "cadence", "upsample", "dynres", "hdr_display", "quality", "resident_scene", "animated_scene", "shadowed_scene", "traced_scene", "split_scene", "path_scene", "gloss_scene", "virtual_scene"):
+    for name in ("pipeline", "farm", "cadence", "upsample", "dynres", "hdr_display", "quality", "resident_scene", "animated_scene", "shadowed_scene", "traced_scene", "split_scene", "path_scene", "gloss_scene", "virtual_scene", "rough_scene"):
         src = os.path.join(ROOT, "examples", name + ".cpp")
         out = os.path.join(ROOT, "examples", name)
-        traced, split, path = name in ("traced_scene", "split_scene"), name in ("split_scene", "path_scene", "gloss_scene", "virtual_scene"), name == "path_scene"
-        gloss, virt = name in ("gloss_scene", "virtual_scene"), name == "virtual_scene"
+        traced, split, path = name in ("traced_scene", "split_scene"), name in ("split_scene", "path_scene", "gloss_scene", "virtual_scene", "rough_scene"), name == "path_scene"
+        gloss, virt, rough = name in ("gloss_scene", "virtual_scene", "rough_scene"), name == "virtual_scene", name == "rough_scene"
         if not force and _newer(out, [src, os.path.join(ROOT, "include", "svgf.h"), LIB] + ([os.path.join(ROOT, "include", "svgf_trace.h"), LIB_TRACE] if traced else []) +
                                 ([os.path.join(ROOT, "include", "svgf_split.h"), LIB_SPLIT] if split else []) +
                                 ([os.path.join(ROOT, "include", "svgf_path.h"), LIB_PATH] if path else []) +
                                 ([os.path.join(ROOT, "include", "svgf_gloss.h"), os.path.join(ROOT, "include", "svgf_path.h"), LIB_GLOSS] if gloss else []) +
-                                ([os.path.join(ROOT, "include", "svgf_virtual.h"), LIB_VIRTUAL] if virt else [])):
+                                ([os.path.join(ROOT, "include", "svgf_virtual.h"), LIB_VIRTUAL] if virt else []) +
+                                ([os.path.join(ROOT, "include", "svgf_rough.h"), os.path.join(ROOT, "include", "svgf_virtual.h"), LIB_ROUGH] if rough else [])):
             continue
         tmp = out + f".tmp{os.getpid()}"
-        _run([hipcc_path(), "--offload-arch=gfx950", "-O2", "-I", os.path.join(ROOT, "include"), src, "-L", _HERE] + (["-lsvgf_virtual"] if virt else []) + (["-lsvgf_gloss"] if gloss else []) + (["-lsvgf_path"] if path else []) + (["-lsvgf_split"] if split else []) + (["-lsvgf_trace"] if traced else []) + ["-lsvgf_hip",
+        _run([hipcc_path(), "--offload-arch=gfx950", "-O2", "-I", os.path.join(ROOT, "include"), src, "-L", _HERE] + (["-lsvgf_rough"] if rough else []) + (["-lsvgf_virtual"] if virt else []) + (["-lsvgf_gloss"] if gloss else []) + (["-lsvgf_path"] if path else []) + (["-lsvgf_split"] if split else []) + (["-lsvgf_trace"] if traced else []) + ["-lsvgf_hip",
               "-Wl,-rpath," + _HERE, "-Wl,-rpath,$ORIGIN/../cuda-path-tracer-denoising_amd", "-o", tmp])
         os.replace(tmp, out)
     return out

@@ -3,7 +3,9 @@
 // row f20) instantiates k_scene_gloss for SceneGlossArgs and SceneGlossSplitArgs, libsvgf_virtual.so (svgf_scene_virtual.hip: svgf_virtual_draw and
 // svgf_virtual_draw_split, row f21) instantiates it for SceneVirtualArgs and SceneVirtualSplitArgs - every ray of every path the same statements, plus the GUIDE
 // chain that replaces the first hit's normal, position and id in the stored texel where the first hit is purely specular
-// (include/svgf_virtual.h).  Include inside an anonymous namespace, behind svgf_scene_trace.inc.h (whose text this one continues: the
+// (include/svgf_virtual.h); libsvgf_rough.so (svgf_scene_rough.hip: svgf_rough_draw and svgf_rough_draw_split, row f22) instantiates it for
+// SceneRoughArgs and SceneRoughSplitArgs - the guide, and a GGX lobe (ROUGH) on the mirror vertices of objects with a roughness
+// (include/svgf_rough.h).  Include inside an anonymous namespace, behind svgf_scene_trace.inc.h (whose text this one continues: the
 // includer names both) and after svgf_path.h and svgf_gloss_table.h.
 //
 // k_scene_gloss: one thread per pixel, 256 per block, every ray of the pixel on the per-lane LDS stack stack[level][lane] (48 x 256 x 4 B;
@@ -47,17 +49,42 @@ struct SceneVirtualSplitArgs {
     SceneGuide v;
 };
 
+// svgf_rough_draw's and svgf_rough_draw_split's: the virtual draw's arguments and the roughness table's
+struct SceneRough {
+    const float *alpha;         // n values on the scene's device (null with n == 0)
+    int n;
+    float guide_alpha;
+};
+
+struct SceneRoughArgs {
+    SceneVirtualArgs v;
+    SceneRough r;
+};
+
+struct SceneRoughSplitArgs {
+    SceneVirtualSplitArgs v;
+    SceneRough r;
+};
+
 __device__ __forceinline__ const SceneTraceArgs &trace_args(const SceneGlossArgs &a) { return a.t; }
 __device__ __forceinline__ const SceneTraceArgs &trace_args(const SceneGlossSplitArgs &a) { return a.s.t; }
 __device__ __forceinline__ const SceneGlossArgs &gloss_args(const SceneGlossArgs &a) { return a; }
 __device__ __forceinline__ const SceneGlossSplitArgs &gloss_args(const SceneGlossSplitArgs &a) { return a; }
 __device__ __forceinline__ const SceneGlossArgs &gloss_args(const SceneVirtualArgs &a) { return a.g; }
 __device__ __forceinline__ const SceneGlossSplitArgs &gloss_args(const SceneVirtualSplitArgs &a) { return a.g; }
+__device__ __forceinline__ const SceneGlossArgs &gloss_args(const SceneRoughArgs &a) { return a.v.g; }
+__device__ __forceinline__ const SceneGlossSplitArgs &gloss_args(const SceneRoughSplitArgs &a) { return a.v.g; }
 // the guide's arguments; a draw without a guide has none, and its kernel reads none
 __device__ __forceinline__ SceneGuide gloss_guide(const SceneGlossArgs &) { return SceneGuide{ 0, 0, nullptr }; }
 __device__ __forceinline__ SceneGuide gloss_guide(const SceneGlossSplitArgs &) { return SceneGuide{ 0, 0, nullptr }; }
 __device__ __forceinline__ SceneGuide gloss_guide(const SceneVirtualArgs &a) { return a.v; }
 __device__ __forceinline__ SceneGuide gloss_guide(const SceneVirtualSplitArgs &a) { return a.v; }
+__device__ __forceinline__ SceneGuide gloss_guide(const SceneRoughArgs &a) { return a.v.v; }
+__device__ __forceinline__ SceneGuide gloss_guide(const SceneRoughSplitArgs &a) { return a.v.v; }
+// the roughness table; only the ROUGH kernels read one
+template <class Args> __device__ __forceinline__ SceneRough gloss_rough(const Args &) { return SceneRough{ nullptr, 0, 0.0f }; }
+__device__ __forceinline__ SceneRough gloss_rough(const SceneRoughArgs &a) { return a.r; }
+__device__ __forceinline__ SceneRough gloss_rough(const SceneRoughSplitArgs &a) { return a.r; }
 
 // the surface of object id g: the table's record, or the diffuse one (all fields 0) outside it
 __device__ __forceinline__ SvgfSurface gloss_surface(const SvgfSurface *table, int n_table, int g)
@@ -109,17 +136,77 @@ __device__ __forceinline__ bool gloss_vertex(const SvgfSurface &S, bool triangle
     return false;
 }
 
+// The GGX lobe of a ROUGH vertex (include/svgf_rough.h states this order of operations): a mirror vertex with roughness alpha > 0 and
+// normal n, reached along d.  False: the vertex is not rough (v.n is not above 0) and dn and wgt stay gloss_vertex's.  True: dn is the
+// direction d reflected about a normal h drawn from the visible normals, by the disc point the diffuse sampler would have drawn here
+// (streams base + 0..7), wgt is wgt times G1(dn.n), and `absorbed` says that dn does not leave the surface.
+__device__ __forceinline__ bool rough_vertex(const SceneArgs &a, int p, unsigned base, float alpha, const float d[3], const float n[3], float dn[3],
+                                             float wgt[3], bool &absorbed)
+{
+#pragma clang fp contract(off)
+    absorbed = false;
+    const float s = copysignf(1.0f, n[2]), q = -1.0f / (s + n[2]), w = (n[0] * n[1]) * q;
+    const float T[3] = { 1.0f + ((s * n[0]) * n[0]) * q, s * w, -(s * n[0]) };
+    const float B[3] = { w, s + (n[1] * n[1]) * q, -n[1] };
+    const float v[3] = { -d[0], -d[1], -d[2] };
+    const float v_t = (v[0] * T[0] + v[1] * T[1]) + v[2] * T[2], v_b = (v[0] * B[0] + v[1] * B[1]) + v[2] * B[2];
+    const float v_n = (v[0] * n[0] + v[1] * n[1]) + v[2] * n[2];
+    if (!(v_n > 0.0f)) return false;
+    // the disc point: trace_direction's bounded rejection
+    float t1 = 0.0f, t2 = 0.0f;
+    bool found = false;
+#pragma unroll
+    for (unsigned k = 0; k < 4; k++) {
+        const float ak = 2.0f * scene_hash(a.seed, a.frame, (unsigned)p, base + 2 * k) - 1.0f;
+        const float bk = 2.0f * scene_hash(a.seed, a.frame, (unsigned)p, base + 2 * k + 1) - 1.0f;
+        const bool take = !found && (ak * ak + bk * bk < 1.0f);
+        t1 = take ? ak : t1; t2 = take ? bk : t2;
+        found = found || take;
+    }
+    float Vh[3] = { alpha * v_t, alpha * v_b, v_n };
+    normalise3(Vh);
+    const float lensq = Vh[0] * Vh[0] + Vh[1] * Vh[1];
+    float T1x = 1.0f, T1y = 0.0f;
+    if (lensq > 0.0f) {
+        const float len = sqrtf(lensq);
+        T1x = -Vh[1] / len; T1y = Vh[0] / len;
+    }
+    const float T2[3] = { -(Vh[2] * T1y), Vh[2] * T1x, Vh[0] * T1y - Vh[1] * T1x };
+    const float sh = 0.5f * (1.0f + Vh[2]);
+    const float one = 1.0f - t1 * t1;
+    const float t2p = (1.0f - sh) * sqrtf(one) + sh * t2;
+    const float cz = sqrtf(fmaxf(0.0f, one - t2p * t2p));
+    const float Nh[3] = { (t1 * T1x + t2p * T2[0]) + cz * Vh[0], (t1 * T1y + t2p * T2[1]) + cz * Vh[1], t2p * T2[2] + cz * Vh[2] };
+    float hl[3] = { alpha * Nh[0], alpha * Nh[1], fmaxf(0.0f, Nh[2]) };
+    normalise3(hl);
+    float h[3];
+    for (int c = 0; c < 3; c++) h[c] = (hl[0] * T[c] + hl[1] * B[c]) + hl[2] * n[c];
+    const float f = 2.0f * ((d[0] * h[0] + d[1] * h[1]) + d[2] * h[2]);
+    for (int c = 0; c < 3; c++) dn[c] = d[c] - f * h[c];
+    normalise3(dn);
+    const float l_n = (dn[0] * n[0] + dn[1] * n[1]) + dn[2] * n[2];
+    if (!(l_n > 0.0f)) { absorbed = true; return true; }
+    const float a2 = alpha * alpha;
+    const float G1 = (2.0f * l_n) / (l_n + sqrtf(a2 + (1.0f - a2) * (l_n * l_n)));
+    for (int c = 0; c < 3; c++) wgt[c] = wgt[c] * G1;
+    return true;
+}
+
 // Args = SceneGlossArgs: svgf_gloss_draw.  Args = SceneGlossSplitArgs: svgf_gloss_draw_split, the same rays with trace_store_split's tail.
 // Args = SceneVirtualArgs, SceneVirtualSplitArgs: svgf_virtual_draw and svgf_virtual_draw_split, either with the guide (GUIDE).
+// Args = SceneRoughArgs, SceneRoughSplitArgs: svgf_rough_draw and svgf_rough_draw_split, the guide and the rough lobe (ROUGH).
 template <class AllArgs>
 __global__ __launch_bounds__(256) void k_scene_gloss(AllArgs all_args)
 {
 #pragma clang fp contract(off)
-    constexpr bool GUIDE = std::is_same<AllArgs, SceneVirtualArgs>::value || std::is_same<AllArgs, SceneVirtualSplitArgs>::value;
-    constexpr bool SPLIT = std::is_same<AllArgs, SceneGlossSplitArgs>::value || std::is_same<AllArgs, SceneVirtualSplitArgs>::value;
+    constexpr bool ROUGH = std::is_same<AllArgs, SceneRoughArgs>::value || std::is_same<AllArgs, SceneRoughSplitArgs>::value;
+    constexpr bool GUIDE = std::is_same<AllArgs, SceneVirtualArgs>::value || std::is_same<AllArgs, SceneVirtualSplitArgs>::value || ROUGH;
+    constexpr bool SPLIT = std::is_same<AllArgs, SceneGlossSplitArgs>::value || std::is_same<AllArgs, SceneVirtualSplitArgs>::value ||
+                           std::is_same<AllArgs, SceneRoughSplitArgs>::value;
     __shared__ int stack[SVGF_SCENE_MAX_DEPTH * 256];
     const auto &args = gloss_args(all_args);
     const SceneGuide gd = gloss_guide(all_args);
+    const SceneRough rg = gloss_rough(all_args);
     const SceneTraceArgs &arg = trace_args(args);
     const SceneBvhArgs &b = arg.b;
     const SceneArgs &a = b.s;
@@ -186,9 +273,23 @@ __global__ __launch_bounds__(256) void k_scene_gloss(AllArgs all_args)
                         float dn[3] = { 0.0f, 0.0f, 0.0f }, wgt[3], nn[3] = { 0.0f, 0.0f, 0.0f };
                         bool moved;
                         // the guide reads no stream: glass transmits (u = 1), a full mirror reflects (u = 0), a partial one does not (u = 1)
-                        const float u = guide ? ((!(S.refract > 0.0f && !triangle) && S.reflect >= 1.0f) ? 0.0f : 1.0f)
-                                              : scene_hash(a.seed, a.frame, (unsigned)p, cb);
+                        float u = guide ? ((!(S.refract > 0.0f && !triangle) && S.reflect >= 1.0f) ? 0.0f : 1.0f)
+                                        : scene_hash(a.seed, a.frame, (unsigned)p, cb);
+                        // the roughness of the vertex; the guide does not follow a mirror rougher than guide_alpha
+                        float alpha = 0.0f;
+                        if constexpr (ROUGH) {
+                            if (gid >= 0 && gid < rg.n) alpha = rg.alpha[gid];
+                            if (guide && alpha > rg.guide_alpha) u = 1.0f;
+                        }
                         const bool specular = gloss_vertex(S, triangle, d, n, u, inside, dn, wgt, nn, moved);
+                        if constexpr (ROUGH) {
+                            // a mirror vertex (not glass) of a rough object: the lobe's direction and weight in the smooth mirror's place
+                            if (!guide && specular && alpha > 0.0f && !(S.refract > 0.0f && !triangle)) {
+                                bool absorbed;
+                                rough_vertex(a, p, cb + 117u, alpha, d, n, dn, wgt, absorbed);
+                                if (absorbed) break;
+                            }
+                        }
                         if (guide) {
                             if (!specular) { chain = v; break; }                    // the virtual hit
                             if (v == gd.max_chain) { chain = -v; break; }           // the cap

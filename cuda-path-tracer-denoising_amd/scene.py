@@ -180,6 +180,21 @@ def surface_table(scene: Scene, ids=None) -> np.ndarray:
     return t
 
 
+def roughness_table(scene: Scene, ids=None) -> np.ndarray:
+    """The svgf_rough_table entries of a parsed scene (include/svgf_rough.h, row f22): float32[len(scene.objects)], entry g the GGX
+    roughness of OBJECT g from its material's SPECEX e: alpha = sqrt(2 / (e + 2)) for e > 0 (the usual mapping of a Phong exponent,
+    computed in float64, rounded to float32, clipped to 1), 0 (smooth) for e <= 0 or a material without one.  `ids` as in
+    surface_table: every other entry is 0."""
+    t = np.zeros(len(scene.objects), dtype=F)
+    for o in scene.objects:
+        if ids is not None and o["id"] not in ids:
+            continue
+        e = float(scene.materials[o["material"]].get("specex", 0.0))
+        if e > 0:
+            t[o["id"]] = min(F(np.sqrt(2.0 / (e + 2.0))), F(1.0))
+    return t
+
+
 def camera_for_frame(scene: Scene, frame: int, moving: bool):
     """The reference's per-frame camera (src/main.cpp:154-190).  Static: the scene's EYE / LOOKAT with the basis runCuda
     builds (view = -normalize(EYE - LOOKAT), right = cross(view, +y) not normalised, up = cross(right, view)).
