@@ -23,4 +23,5 @@ from .binding import SvgfPathParams, load_path_library  # noqa: F401  (Scene.dra
 from .binding import GlossTable, SvgfSurface, load_gloss_library  # noqa: F401  (Scene.draw_gloss, Scene.draw_gloss_split)
 from .binding import SvgfVirtualParams, load_virtual_library  # noqa: F401  (Scene.draw_virtual, Scene.draw_virtual_split)
 from .binding import RoughTable, SvgfRoughParams, load_rough_library  # noqa: F401  (Scene.draw_rough, Scene.draw_rough_split)
+from .binding import SvgfHighlightParams, load_highlight_library  # noqa: F401  (Scene.draw_highlight, Scene.draw_highlight_split)
 from .binding import STATE_PREV_NORMAL, STATE_PREV_POSITION, STATE_PREV_GEOM_ID, STATE_OUTPUT_HISTORY  # noqa: F401

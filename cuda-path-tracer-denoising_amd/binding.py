@@ -24,6 +24,7 @@ LIB_PATH_PATH = os.path.join(_HERE, "libsvgf_path.so")        # the companion li
 LIB_GLOSS_PATH = os.path.join(_HERE, "libsvgf_gloss.so")      # the companion library of row f20 (include/svgf_gloss.h)
 LIB_VIRTUAL_PATH = os.path.join(_HERE, "libsvgf_virtual.so")  # the companion library of row f21 (include/svgf_virtual.h)
 LIB_ROUGH_PATH = os.path.join(_HERE, "libsvgf_rough.so")  # the companion library of row f22 (include/svgf_rough.h)
+LIB_HIGHLIGHT_PATH = os.path.join(_HERE, "libsvgf_highlight.so")  # the companion library of row f23 (include/svgf_highlight.h)
 LIB_EXP_PATH = os.path.join(_HERE, "libsvgf_hip_exp.so")     # -DSVGF_BUILD_EXPERIMENTS: parked variants + tuning table (tests / tools only)
 
 SVGF_OK = 0
@@ -69,6 +70,8 @@ VIRTUAL_EXPORTS = ["svgf_virtual_draw", "svgf_virtual_draw_split", "svgf_virtual
 # libsvgf_rough.so (include/svgf_rough.h, row f22)
 ROUGH_EXPORTS = ["svgf_rough_table_create", "svgf_rough_table_destroy", "svgf_rough_table_size", "svgf_rough_draw", "svgf_rough_draw_split",
                  "svgf_rough_version"]
+# libsvgf_highlight.so (include/svgf_highlight.h, row f23)
+HIGHLIGHT_EXPORTS = ["svgf_highlight_draw", "svgf_highlight_draw_split", "svgf_highlight_version"]
 SCENE_MAX_DEPTH = 48
 SCENE_MAX_POSED = 1024
 SCENE_REFIT_CAP = 1024
@@ -216,6 +219,12 @@ class SvgfRoughParams(C.Structure):
     """svgf_rough_draw / svgf_rough_draw_split (include/svgf_rough.h, row f22): the guide follows a full mirror whose roughness is at
     most guide_alpha (>= 0)."""
     _fields_ = [("guide_alpha", C.c_float)]
+
+
+class SvgfHighlightParams(C.Structure):
+    """svgf_highlight_draw / svgf_highlight_draw_split (include/svgf_highlight.h, row f23): enable 0 (the rough draws) or 1 (the
+    light's GGX term at rough vertices), and the clamp of the scalar highlight factor (0: none)."""
+    _fields_ = [("enable", C.c_int), ("clamp", C.c_float)]
 
 
 # SvgfBvhNode, 32 bytes: count > 0 a leaf over order[first : first + count], count == 0 an inner node with children first, first + 1
@@ -542,6 +551,34 @@ def load_rough_library():
                                           C.POINTER(SvgfSynthParams), C.POINTER(SvgfSceneLight), C.POINTER(SvgfPathParams),
                                           C.POINTER(SvgfVirtualParams), vp, vp, vp, C.POINTER(SvgfRoughParams)]
     _lib_rough = lib
+    return lib
+
+
+_lib_highlight = None
+
+
+def load_highlight_library():
+    """Load libsvgf_highlight.so (row f23; after the product library it links against) and declare its prototypes.  Fails loudly when
+    it is absent, and when it was compiled against another svgf.h than the product library found."""
+    global _lib_highlight
+    if _lib_highlight is not None:
+        return _lib_highlight
+    product = load_library()
+    if not os.path.exists(LIB_HIGHLIGHT_PATH):
+        raise SvgfError(f"{LIB_HIGHLIGHT_PATH} not found: build it first (python -c 'import __graft_entry__ as g; g.build()').")
+    lib = C.CDLL(LIB_HIGHLIGHT_PATH)
+    vp, ip = C.c_void_p, C.c_int
+    lib.svgf_highlight_version.restype = ip
+    if lib.svgf_highlight_version() != product.svgf_version():
+        raise SvgfError(f"libsvgf_highlight.so was built for ABI {lib.svgf_highlight_version():#x}, libsvgf_hip.so is {product.svgf_version():#x}")
+    lib.svgf_highlight_draw.argtypes = [vp, vp, vp, vp, C.POINTER(SvgfPlanarGBuffer), ip, ip, C.POINTER(SvgfCamera), C.POINTER(SvgfSynthParams),
+                                        C.POINTER(SvgfSceneLight), C.POINTER(SvgfPathParams), C.POINTER(SvgfVirtualParams), vp, vp, vp,
+                                        C.POINTER(SvgfRoughParams), C.POINTER(SvgfHighlightParams)]
+    lib.svgf_highlight_draw_split.argtypes = [vp, vp, vp, vp, vp, vp, C.POINTER(SvgfPlanarGBuffer), ip, ip, C.POINTER(SvgfCamera),
+                                              C.POINTER(SvgfSynthParams), C.POINTER(SvgfSceneLight), C.POINTER(SvgfPathParams),
+                                              C.POINTER(SvgfVirtualParams), vp, vp, vp, C.POINTER(SvgfRoughParams),
+                                              C.POINTER(SvgfHighlightParams)]
+    _lib_highlight = lib
     return lib
 
 
@@ -1484,6 +1521,45 @@ class Scene:
                                                         _stream(stream), rough.h if rough is not None else None, C.byref(rp))
         if rc != SVGF_OK:
             raise SvgfError(f"svgf_rough_draw_split failed ({rc})")
+
+    def draw_highlight(self, out_rgb, out_gbuffer, width: int, height: int, camera, light, frame: int, table=None, paths: int = 1,
+                       max_depth: int = 4, rr_depth: int = 2, ambient: float = 0.15, shadow_secondary: int = 1, seed: int = 1, noise: float = 0.6,
+                       fireflies: float = 0.02, pixel_length=None, stream=None, max_chain: int = 4, id_offset: int = 0, out_chain=None, rough=None,
+                       guide_alpha: float = 0.0, enable: int = 1, clamp: float = 0.0):
+        """svgf_highlight_draw of libsvgf_highlight.so (row f23): draw_rough with the analytic light's GGX term at the rough vertices
+        (`enable` 1), its scalar factor clamped to `clamp` where that is above 0.  With enable=0 it is draw_rough's frame on bits.  One
+        launch on `stream`; never waits."""
+        cam, sp, pp = self._path_call_args(width, height, camera, frame, paths, max_depth, rr_depth, ambient, shadow_secondary, seed, noise,
+                                           fireflies, pixel_length)
+        vp, rp, hp = SvgfVirtualParams(int(max_chain), int(id_offset)), SvgfRoughParams(float(guide_alpha)), SvgfHighlightParams(int(enable), float(clamp))
+        planar = isinstance(out_gbuffer, SvgfPlanarGBuffer)
+        rc = load_highlight_library().svgf_highlight_draw(self.h, table.h if table is not None else None, _ptr(out_rgb),
+                                                          None if planar else _ptr(out_gbuffer), C.byref(out_gbuffer) if planar else None,
+                                                          int(width), int(height), C.byref(cam), C.byref(sp), C.byref(light), C.byref(pp),
+                                                          C.byref(vp), _ptr(out_chain), _stream(stream),
+                                                          rough.h if rough is not None else None, C.byref(rp), C.byref(hp))
+        if rc != SVGF_OK:
+            raise SvgfError(f"svgf_highlight_draw failed ({rc})")
+
+    def draw_highlight_split(self, out_direct, out_indirect, out_gbuffer, width: int, height: int, camera, light, frame: int, table=None,
+                             paths: int = 1, max_depth: int = 4, rr_depth: int = 2, ambient: float = 0.15, shadow_secondary: int = 1,
+                             seed: int = 1, noise: float = 0.6, fireflies: float = 0.02, pixel_length=None, out_rgb=None, stream=None,
+                             max_chain: int = 4, id_offset: int = 0, out_chain=None, rough=None, guide_alpha: float = 0.0, enable: int = 1,
+                             clamp: float = 0.0):
+        """svgf_highlight_draw_split of libsvgf_highlight.so (row f23): draw_rough_split with draw_highlight's term; at the first hit
+        it is part of the direct image.  One launch on `stream`; never waits."""
+        cam, sp, pp = self._path_call_args(width, height, camera, frame, paths, max_depth, rr_depth, ambient, shadow_secondary, seed, noise,
+                                           fireflies, pixel_length)
+        vp, rp, hp = SvgfVirtualParams(int(max_chain), int(id_offset)), SvgfRoughParams(float(guide_alpha)), SvgfHighlightParams(int(enable), float(clamp))
+        planar = isinstance(out_gbuffer, SvgfPlanarGBuffer)
+        rc = load_highlight_library().svgf_highlight_draw_split(self.h, table.h if table is not None else None, _ptr(out_direct),
+                                                                _ptr(out_indirect), _ptr(out_rgb), None if planar else _ptr(out_gbuffer),
+                                                                C.byref(out_gbuffer) if planar else None, int(width), int(height),
+                                                                C.byref(cam), C.byref(sp), C.byref(light), C.byref(pp), C.byref(vp),
+                                                                _ptr(out_chain), _stream(stream), rough.h if rough is not None else None,
+                                                                C.byref(rp), C.byref(hp))
+        if rc != SVGF_OK:
+            raise SvgfError(f"svgf_highlight_draw_split failed ({rc})")
 
     def view(self) -> dict:
         """svgf_scene_view (host only): the device index, the counts and the device pointers the draws read, as integers (0 = NULL)."""

@@ -42,6 +42,10 @@ VIRTUAL_SOURCES = ["svgf_scene_virtual.hip"]
 # kernel is csrc/svgf_scene_gloss.inc.h's too, and the gloss and the virtual library's code objects stay what they were.
 LIB_ROUGH = os.path.join(_HERE, "libsvgf_rough.so")
 ROUGH_SOURCES = ["svgf_scene_rough.hip"]
+# The companion library of row f23 (include/svgf_highlight.h: the rough draws with the light's GGX term at rough vertices): a seventh
+# one; its kernel is csrc/svgf_scene_gloss.inc.h's too, and the gloss, virtual and rough libraries' code objects stay what they were.
+LIB_HIGHLIGHT = os.path.join(_HERE, "libsvgf_highlight.so")
+HIGHLIGHT_SOURCES = ["svgf_scene_highlight.hip"]
 HIP_SOURCES_EXPERIMENTS = ["svgf_experiments.hip", "svgf_atrous_lane_reuse.hip", "svgf_atrous_fused.hip"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unused-function"]
 # Per-file flags.  svgf_atrous_fused.hip: SimplifyCFG's common-code sinking merges the last store of the "bilinear history" branch
@@ -193,9 +197,27 @@ def build_rough(force: bool = False) -> str:
     return LIB_ROUGH
 
 
+def build_highlight(force: bool = False) -> str:
+    """Compile csrc/svgf_scene_highlight.hip for gfx950 into cuda-path-tracer-denoising_amd/libsvgf_highlight.so, linked against the
+    product library beside it (and against no other companion: the two tables are read through csrc/svgf_gloss_table.h and
+    csrc/svgf_rough_table.h), by build_trace()'s scheme."""
+    build_hip()
+    srcs = [os.path.join(CSRC, s) for s in HIGHLIGHT_SOURCES]
+    deps = srcs + [os.path.join(CSRC, h) for h in sorted(os.listdir(CSRC)) if h.endswith(".h")] + \
+        [os.path.join(ROOT, "include", h) for h in ("svgf.h", "svgf_trace.h", "svgf_path.h", "svgf_gloss.h", "svgf_virtual.h", "svgf_rough.h",
+                                                    "svgf_highlight.h")] + [LIB]
+    if not force and _newer(LIB_HIGHLIGHT, deps):
+        return LIB_HIGHLIGHT
+    tmp = LIB_HIGHLIGHT + f".tmp{os.getpid()}"
+    _run([hipcc_path()] + HIPCC_FLAGS + srcs + ["-L", _HERE, "-lsvgf_hip", "-Wl,-rpath," + _HERE, "-Wl,-rpath,$ORIGIN", "-Wl,-s", "-o", tmp])
+    os.replace(tmp, LIB_HIGHLIGHT)
+    return LIB_HIGHLIGHT
+
+
 def build_all(force: bool = False) -> list[str]:
-    """The product library and the six companion libraries, in the order they were added."""
-    return [build_hip(force), build_trace(force), build_split(force), build_path(force), build_gloss(force), build_virtual(force), build_rough(force)]
+    """The product library and the seven companion libraries, in the order they were added."""
+    return [build_hip(force), build_trace(force), build_split(force), build_path(force), build_gloss(force), build_virtual(force), build_rough(force),
+            build_highlight(force)]
 
 
 def build_examples(force: bool = False) -> str:
@@ -217,28 +239,33 @@ def build_examples(force: bool = False) -> str:
     examples/virtual_scene.cpp (the same room through the same pipeline with the first-hit and with the virtual-hit G-buffer of
     svgf_virtual_draw_split), linked against the virtual, the gloss and the split library; and examples/rough_scene.cpp (that room with
     a rough floor through the same pipeline, svgf_rough_draw_split with guide_alpha 0 and 1, with and without the firefly filter and the
-    history clamp), linked against the rough, the gloss and the split library."""
+    history clamp), linked against the rough, the gloss and the split library; and examples/highlight_scene.cpp (that room and floor under
+    svgf_highlight_draw_split with the highlight off, on and clamped, both terms with and without the firefly filter and the history clamp),
+    linked against the highlight, the rough, the gloss and the split library."""
     build_trace()
     build_split()
     build_path()
     build_gloss()
     build_virtual()
     build_rough()
+    build_highlight()
     out = ""
-    for name in ("pipeline", "farm", "cadence", "upsample", "dynres", "hdr_display", "quality", "resident_scene", "animated_scene", "shadowed_scene", "traced_scene", "split_scene", "path_scene", "gloss_scene", "virtual_scene", "rough_scene"):
+    for name in ("pipeline", "farm", "cadence", "upsample", "dynres", "hdr_display", "quality", "resident_scene", "animated_scene", "shadowed_scene", "traced_scene", "split_scene", "path_scene", "gloss_scene", "virtual_scene", "rough_scene", "highlight_scene"):
         src = os.path.join(ROOT, "examples", name + ".cpp")
         out = os.path.join(ROOT, "examples", name)
-        traced, split, path = name in ("traced_scene", "split_scene"), name in ("split_scene", "path_scene", "gloss_scene", "virtual_scene", "rough_scene"), name == "path_scene"
-        gloss, virt, rough = name in ("gloss_scene", "virtual_scene", "rough_scene"), name == "virtual_scene", name == "rough_scene"
+        traced, split, path = name in ("traced_scene", "split_scene"), name in ("split_scene", "path_scene", "gloss_scene", "virtual_scene", "rough_scene", "highlight_scene"), name == "path_scene"
+        gloss, virt, rough = name in ("gloss_scene", "virtual_scene", "rough_scene", "highlight_scene"), name == "virtual_scene", name in ("rough_scene", "highlight_scene")
+        shine = name == "highlight_scene"
         if not force and _newer(out, [src, os.path.join(ROOT, "include", "svgf.h"), LIB] + ([os.path.join(ROOT, "include", "svgf_trace.h"), LIB_TRACE] if traced else []) +
                                 ([os.path.join(ROOT, "include", "svgf_split.h"), LIB_SPLIT] if split else []) +
                                 ([os.path.join(ROOT, "include", "svgf_path.h"), LIB_PATH] if path else []) +
                                 ([os.path.join(ROOT, "include", "svgf_gloss.h"), os.path.join(ROOT, "include", "svgf_path.h"), LIB_GLOSS] if gloss else []) +
                                 ([os.path.join(ROOT, "include", "svgf_virtual.h"), LIB_VIRTUAL] if virt else []) +
-                                ([os.path.join(ROOT, "include", "svgf_rough.h"), os.path.join(ROOT, "include", "svgf_virtual.h"), LIB_ROUGH] if rough else [])):
+                                ([os.path.join(ROOT, "include", "svgf_rough.h"), os.path.join(ROOT, "include", "svgf_virtual.h"), LIB_ROUGH] if rough else []) +
+                                ([os.path.join(ROOT, "include", "svgf_highlight.h"), LIB_HIGHLIGHT] if shine else [])):
             continue
         tmp = out + f".tmp{os.getpid()}"
-        _run([hipcc_path(), "--offload-arch=gfx950", "-O2", "-I", os.path.join(ROOT, "include"), src, "-L", _HERE] + (["-lsvgf_rough"] if rough else []) + (["-lsvgf_virtual"] if virt else []) + (["-lsvgf_gloss"] if gloss else []) + (["-lsvgf_path"] if path else []) + (["-lsvgf_split"] if split else []) + (["-lsvgf_trace"] if traced else []) + ["-lsvgf_hip",
+        _run([hipcc_path(), "--offload-arch=gfx950", "-O2", "-I", os.path.join(ROOT, "include"), src, "-L", _HERE] + (["-lsvgf_highlight"] if shine else []) + (["-lsvgf_rough"] if rough else []) + (["-lsvgf_virtual"] if virt else []) + (["-lsvgf_gloss"] if gloss else []) + (["-lsvgf_path"] if path else []) + (["-lsvgf_split"] if split else []) + (["-lsvgf_trace"] if traced else []) + ["-lsvgf_hip",
               "-Wl,-rpath," + _HERE, "-Wl,-rpath,$ORIGIN/../cuda-path-tracer-denoising_amd", "-o", tmp])
         os.replace(tmp, out)
     return out

@@ -5,7 +5,9 @@
 // chain that replaces the first hit's normal, position and id in the stored texel where the first hit is purely specular
 // (include/svgf_virtual.h); libsvgf_rough.so (svgf_scene_rough.hip: svgf_rough_draw and svgf_rough_draw_split, row f22) instantiates it for
 // SceneRoughArgs and SceneRoughSplitArgs - the guide, and a GGX lobe (ROUGH) on the mirror vertices of objects with a roughness
-// (include/svgf_rough.h).  Include inside an anonymous namespace, behind svgf_scene_trace.inc.h (whose text this one continues: the
+// (include/svgf_rough.h); libsvgf_highlight.so (svgf_scene_highlight.hip: svgf_highlight_draw and svgf_highlight_draw_split, row f23)
+// instantiates it for SceneHighlightArgs and SceneHighlightSplitArgs - the guide, the lobe, and the analytic light's GGX term (SHINE) at
+// the rough vertices, through the shadow samples the diffuse vertices use (include/svgf_highlight.h).  Include inside an anonymous namespace, behind svgf_scene_trace.inc.h (whose text this one continues: the
 // includer names both) and after svgf_path.h and svgf_gloss_table.h.
 //
 // k_scene_gloss: one thread per pixel, 256 per block, every ray of the pixel on the per-lane LDS stack stack[level][lane] (48 x 256 x 4 B;
@@ -66,6 +68,22 @@ struct SceneRoughSplitArgs {
     SceneRough r;
 };
 
+// svgf_highlight_draw's and svgf_highlight_draw_split's: the rough draw's arguments and the highlight's two parameters
+struct SceneHighlight {
+    int enable;
+    float clamp;
+};
+
+struct SceneHighlightArgs {
+    SceneRoughArgs r;
+    SceneHighlight h;
+};
+
+struct SceneHighlightSplitArgs {
+    SceneRoughSplitArgs r;
+    SceneHighlight h;
+};
+
 __device__ __forceinline__ const SceneTraceArgs &trace_args(const SceneGlossArgs &a) { return a.t; }
 __device__ __forceinline__ const SceneTraceArgs &trace_args(const SceneGlossSplitArgs &a) { return a.s.t; }
 __device__ __forceinline__ const SceneGlossArgs &gloss_args(const SceneGlossArgs &a) { return a; }
@@ -74,6 +92,8 @@ __device__ __forceinline__ const SceneGlossArgs &gloss_args(const SceneVirtualAr
 __device__ __forceinline__ const SceneGlossSplitArgs &gloss_args(const SceneVirtualSplitArgs &a) { return a.g; }
 __device__ __forceinline__ const SceneGlossArgs &gloss_args(const SceneRoughArgs &a) { return a.v.g; }
 __device__ __forceinline__ const SceneGlossSplitArgs &gloss_args(const SceneRoughSplitArgs &a) { return a.v.g; }
+__device__ __forceinline__ const SceneGlossArgs &gloss_args(const SceneHighlightArgs &a) { return a.r.v.g; }
+__device__ __forceinline__ const SceneGlossSplitArgs &gloss_args(const SceneHighlightSplitArgs &a) { return a.r.v.g; }
 // the guide's arguments; a draw without a guide has none, and its kernel reads none
 __device__ __forceinline__ SceneGuide gloss_guide(const SceneGlossArgs &) { return SceneGuide{ 0, 0, nullptr }; }
 __device__ __forceinline__ SceneGuide gloss_guide(const SceneGlossSplitArgs &) { return SceneGuide{ 0, 0, nullptr }; }
@@ -81,10 +101,18 @@ __device__ __forceinline__ SceneGuide gloss_guide(const SceneVirtualArgs &a) { r
 __device__ __forceinline__ SceneGuide gloss_guide(const SceneVirtualSplitArgs &a) { return a.v; }
 __device__ __forceinline__ SceneGuide gloss_guide(const SceneRoughArgs &a) { return a.v.v; }
 __device__ __forceinline__ SceneGuide gloss_guide(const SceneRoughSplitArgs &a) { return a.v.v; }
+__device__ __forceinline__ SceneGuide gloss_guide(const SceneHighlightArgs &a) { return a.r.v.v; }
+__device__ __forceinline__ SceneGuide gloss_guide(const SceneHighlightSplitArgs &a) { return a.r.v.v; }
 // the roughness table; only the ROUGH kernels read one
 template <class Args> __device__ __forceinline__ SceneRough gloss_rough(const Args &) { return SceneRough{ nullptr, 0, 0.0f }; }
 __device__ __forceinline__ SceneRough gloss_rough(const SceneRoughArgs &a) { return a.r; }
 __device__ __forceinline__ SceneRough gloss_rough(const SceneRoughSplitArgs &a) { return a.r; }
+__device__ __forceinline__ SceneRough gloss_rough(const SceneHighlightArgs &a) { return a.r.r; }
+__device__ __forceinline__ SceneRough gloss_rough(const SceneHighlightSplitArgs &a) { return a.r.r; }
+// the highlight's parameters; only the SHINE kernels read them
+template <class Args> __device__ __forceinline__ SceneHighlight gloss_shine(const Args &) { return SceneHighlight{ 0, 0.0f }; }
+__device__ __forceinline__ SceneHighlight gloss_shine(const SceneHighlightArgs &a) { return a.h; }
+__device__ __forceinline__ SceneHighlight gloss_shine(const SceneHighlightSplitArgs &a) { return a.h; }
 
 // the surface of object id g: the table's record, or the diffuse one (all fields 0) outside it
 __device__ __forceinline__ SvgfSurface gloss_surface(const SvgfSurface *table, int n_table, int g)
@@ -192,21 +220,49 @@ __device__ __forceinline__ bool rough_vertex(const SceneArgs &a, int p, unsigned
     return true;
 }
 
+// The light's factor H at a ROUGH vertex (include/svgf_highlight.h states this order of operations): the point x with normal n and
+// roughness alpha, reached along d, lit from the unit direction l.  E pi D G1(v) G1(l) / (4 v_n) of the GGX lobe rough_vertex samples,
+// E the diffuse term's 30 / (4 + dist2) towards the light's centre; 0 unless l.n > 0; at most `clamp` where that is above 0.
+__device__ __forceinline__ float shine_factor(const SceneArgs &a, float alpha, float clamp, const float d[3], const float n[3], const float x[3],
+                                              const float l[3])
+{
+#pragma clang fp contract(off)
+    const float l_n = (l[0] * n[0] + l[1] * n[1]) + l[2] * n[2];
+    if (!(l_n > 0.0f)) return 0.0f;
+    const float v[3] = { -d[0], -d[1], -d[2] };
+    const float v_n = (v[0] * n[0] + v[1] * n[1]) + v[2] * n[2];
+    float hv[3] = { v[0] + l[0], v[1] + l[1], v[2] + l[2] };
+    normalise3(hv);
+    const float h_n = (hv[0] * n[0] + hv[1] * n[1]) + hv[2] * n[2];
+    const float a2 = alpha * alpha;
+    const float t = (h_n * h_n) * (a2 - 1.0f) + 1.0f;
+    float tl[3];
+    for (int c = 0; c < 3; c++) tl[c] = a.light[c] - x[c];
+    const float E = 30.0f / (4.0f + ((tl[0] * tl[0] + tl[1] * tl[1]) + tl[2] * tl[2]));
+    const float G = (2.0f * l_n) / (l_n + sqrtf(a2 + (1.0f - a2) * (l_n * l_n)));
+    float H = ((E * (a2 / (t * t))) * G) / (2.0f * (v_n + sqrtf(a2 + (1.0f - a2) * (v_n * v_n))));
+    if (clamp > 0.0f) H = fminf(H, clamp);
+    return H;
+}
+
 // Args = SceneGlossArgs: svgf_gloss_draw.  Args = SceneGlossSplitArgs: svgf_gloss_draw_split, the same rays with trace_store_split's tail.
 // Args = SceneVirtualArgs, SceneVirtualSplitArgs: svgf_virtual_draw and svgf_virtual_draw_split, either with the guide (GUIDE).
 // Args = SceneRoughArgs, SceneRoughSplitArgs: svgf_rough_draw and svgf_rough_draw_split, the guide and the rough lobe (ROUGH).
+// Args = SceneHighlightArgs, SceneHighlightSplitArgs: svgf_highlight_draw and svgf_highlight_draw_split, those and the light's term (SHINE).
 template <class AllArgs>
 __global__ __launch_bounds__(256) void k_scene_gloss(AllArgs all_args)
 {
 #pragma clang fp contract(off)
-    constexpr bool ROUGH = std::is_same<AllArgs, SceneRoughArgs>::value || std::is_same<AllArgs, SceneRoughSplitArgs>::value;
+    constexpr bool SHINE = std::is_same<AllArgs, SceneHighlightArgs>::value || std::is_same<AllArgs, SceneHighlightSplitArgs>::value;
+    constexpr bool ROUGH = std::is_same<AllArgs, SceneRoughArgs>::value || std::is_same<AllArgs, SceneRoughSplitArgs>::value || SHINE;
     constexpr bool GUIDE = std::is_same<AllArgs, SceneVirtualArgs>::value || std::is_same<AllArgs, SceneVirtualSplitArgs>::value || ROUGH;
     constexpr bool SPLIT = std::is_same<AllArgs, SceneGlossSplitArgs>::value || std::is_same<AllArgs, SceneVirtualSplitArgs>::value ||
-                           std::is_same<AllArgs, SceneRoughSplitArgs>::value;
+                           std::is_same<AllArgs, SceneRoughSplitArgs>::value || std::is_same<AllArgs, SceneHighlightSplitArgs>::value;
     __shared__ int stack[SVGF_SCENE_MAX_DEPTH * 256];
     const auto &args = gloss_args(all_args);
     const SceneGuide gd = gloss_guide(all_args);
     const SceneRough rg = gloss_rough(all_args);
+    const SceneHighlight sh = gloss_shine(all_args);
     const SceneTraceArgs &arg = trace_args(args);
     const SceneBvhArgs &b = arg.b;
     const SceneArgs &a = b.s;
@@ -228,6 +284,7 @@ __global__ __launch_bounds__(256) void k_scene_gloss(AllArgs all_args)
 
         float shade[3] = { h.emit, h.emit, h.emit };
         float first_term = h.emit, ind_term[3] = { 0.0f, 0.0f, 0.0f };
+        float first3[3] = { h.emit, h.emit, h.emit };       // SHINE only: the first term per channel, the highlight in it
         bool bounced = false;
         // what the guide leaves: chain (0: none ran), and for chain > 0 the virtual hit's normal, id and unfolded position
         int chain = 0, vgid = 0;
@@ -238,19 +295,46 @@ __global__ __launch_bounds__(256) void k_scene_gloss(AllArgs all_args)
             const SvgfSurface S0 = gloss_surface(args.table, args.n_table, h.gid);
             const float w_d = (S0.refract > 0.0f && best < 0) ? 0.0f : 1.0f - S0.reflect;
             float first = 0.0f;
-            if (w_d != 0.0f) {
+            // SHINE: a first hit that is rough for the highlight gathers the light through the very shadow samples of the first term
+            bool lit0 = w_d != 0.0f, shine0 = false;
+            float alpha0 = 0.0f, hsum = 0.0f;
+            if constexpr (SHINE) {
+                if (sh.enable != 0 && casts && !(S0.refract > 0.0f && best < 0) && S0.reflect > 0.0f) {
+                    if (h.gid < rg.n) alpha0 = rg.alpha[h.gid];
+                    const float v_n = (-d0[0] * h.n[0] + -d0[1] * h.n[1]) + -d0[2] * h.n[2];
+                    shine0 = alpha0 > 0.0f && v_n > 0.0f;
+                }
+                lit0 = lit0 || shine0;
+            }
+            if (lit0) {
                 int unoccluded = arg.samples;
                 if (casts) {
                     unoccluded = 0;
                     for (int c = 0; c < 3; c++) r.o[c] = pos[c];
-                    for (int s = 0; s < arg.samples; s++)
-                        unoccluded += scene_shadow_sample(b, arg.edge_u, arg.edge_v, r, pos, stk, p, 8 + 2 * s, 9 + 2 * s) ? 0 : 1;
+                    for (int s = 0; s < arg.samples; s++) {
+                        if constexpr (SHINE) { r.d[0] = 0.0f; r.d[1] = 0.0f; r.d[2] = 0.0f; }      // a sample that forms no ray leaves them
+                        const bool occluded = scene_shadow_sample(b, arg.edge_u, arg.edge_v, r, pos, stk, p, 8 + 2 * s, 9 + 2 * s);
+                        unoccluded += occluded ? 0 : 1;
+                        if constexpr (SHINE) {
+                            if (shine0 && !occluded && (r.d[0] != 0.0f || r.d[1] != 0.0f || r.d[2] != 0.0f))
+                                hsum = hsum + shine_factor(a, alpha0, sh.clamp, d0, h.n, pos, r.d);
+                        }
+                    }
                 }
-                const float vis = (float)unoccluded / (float)arg.samples;
-                first = w_d * (arg.ambient + vis * scene_direct(a, h.n, pos));
+                if (!SHINE || w_d != 0.0f) {
+                    const float vis = (float)unoccluded / (float)arg.samples;
+                    first = w_d * (arg.ambient + vis * scene_direct(a, h.n, pos));
+                }
             }
             shade[0] = first; shade[1] = first; shade[2] = first;
             first_term = first;
+            if constexpr (SHINE) {
+                const float hm = hsum / (float)arg.samples;
+                for (int c = 0; c < 3; c++) {
+                    first3[c] = shine0 ? first + (S0.reflect * S0.spec[c]) * hm : first;
+                    shade[c] = first3[c];
+                }
+            }
             const int paths = arg.bounce_samples;
             // the guide's turn j == paths, where the first hit is a hit whose diffuse share is 0
             const int turns = (GUIDE && casts && w_d == 0.0f) ? paths + 1 : paths;
@@ -282,7 +366,39 @@ __global__ __launch_bounds__(256) void k_scene_gloss(AllArgs all_args)
                             if (guide && alpha > rg.guide_alpha) u = 1.0f;
                         }
                         const bool specular = gloss_vertex(S, triangle, d, n, u, inside, dn, wgt, nn, moved);
-                        if constexpr (ROUGH) {
+                        if constexpr (SHINE) {
+                            // The highlight's kernels: the rough vertex, and the gather of a vertex behind the first hit - a diffuse one
+                            // as below, a ROUGH one the light's GGX term - through ONE shadow sample on the streams of the vertex.
+                            // A block of its own, so that the other kernels compile the text they compiled before it existed.  The gather
+                            // comes AHEAD of the lobe's sample, whose direction and weight it does not need: an absorbed vertex has
+                            // gathered, and dn and wgt are not live across the shadow walk (behind it the plain kernel kept 52 B of scratch).
+                            const bool lobe = !guide && specular && alpha > 0.0f && !(S.refract > 0.0f && !triangle);
+                            bool shines = false;
+                            if (lobe && sh.enable != 0 && v >= 1) shines = ((-d[0] * n[0] + -d[1] * n[1]) + -d[2] * n[2]) > 0.0f;     // rough_vertex's v_n
+                            if (!guide && v >= 1 && (!specular || shines)) {
+                                bool occluded = false, formed = true;
+                                if (arg.shadow_secondary) {
+                                    for (int c = 0; c < 3; c++) { r.o[c] = x[c]; r.d[c] = 0.0f; }      // a sample that forms no ray leaves d
+                                    occluded = scene_shadow_sample(b, arg.edge_u, arg.edge_v, r, x, stk, p, cb - 3u, cb - 2u);
+                                    formed = r.d[0] != 0.0f || r.d[1] != 0.0f || r.d[2] != 0.0f;
+                                } else if (shines) {                    // no ray is cast: the direction of the light's centre
+                                    for (int c = 0; c < 3; c++) r.d[c] = a.light[c] - x[c];
+                                    normalise3(r.d);
+                                }
+                                if (shines) {
+                                    const float Hc = (formed && !occluded) ? shine_factor(a, alpha, sh.clamp, d, n, x, r.d) : 0.0f;
+                                    for (int c = 0; c < 3; c++) acc[c] = acc[c] + thr[c] * (alb[c] * (S.spec[c] * Hc));
+                                } else {
+                                    const float Ld = arg.ambient + (occluded ? 0.0f : 1.0f) * scene_direct(a, n, x);
+                                    for (int c = 0; c < 3; c++) acc[c] = acc[c] + thr[c] * (alb[c] * Ld);
+                                }
+                            }
+                            if (lobe) {
+                                bool absorbed;
+                                rough_vertex(a, p, cb + 117u, alpha, d, n, dn, wgt, absorbed);
+                                if (absorbed) break;
+                            }
+                        } else if constexpr (ROUGH) {
                             // a mirror vertex (not glass) of a rough object: the lobe's direction and weight in the smooth mirror's place
                             if (!guide && specular && alpha > 0.0f && !(S.refract > 0.0f && !triangle)) {
                                 bool absorbed;
@@ -294,14 +410,16 @@ __global__ __launch_bounds__(256) void k_scene_gloss(AllArgs all_args)
                             if (!specular) { chain = v; break; }                    // the virtual hit
                             if (v == gd.max_chain) { chain = -v; break; }           // the cap
                         } else if (v >= 1) {
-                            if (!specular) {
-                                bool occluded = false;
-                                if (arg.shadow_secondary) {
-                                    for (int c = 0; c < 3; c++) r.o[c] = x[c];
-                                    occluded = scene_shadow_sample(b, arg.edge_u, arg.edge_v, r, x, stk, p, cb - 3u, cb - 2u);
+                            if constexpr (!SHINE) {
+                                if (!specular) {
+                                    bool occluded = false;
+                                    if (arg.shadow_secondary) {
+                                        for (int c = 0; c < 3; c++) r.o[c] = x[c];
+                                        occluded = scene_shadow_sample(b, arg.edge_u, arg.edge_v, r, x, stk, p, cb - 3u, cb - 2u);
+                                    }
+                                    const float Ld = arg.ambient + (occluded ? 0.0f : 1.0f) * scene_direct(a, n, x);
+                                    for (int c = 0; c < 3; c++) acc[c] = acc[c] + thr[c] * (alb[c] * Ld);
                                 }
-                                const float Ld = arg.ambient + (occluded ? 0.0f : 1.0f) * scene_direct(a, n, x);
-                                for (int c = 0; c < 3; c++) acc[c] = acc[c] + thr[c] * (alb[c] * Ld);
                             }
                             if (v >= args.max_depth) break;
                             for (int c = 0; c < 3; c++) thr[c] = thr[c] * (alb[c] * wgt[c]);
@@ -361,7 +479,7 @@ __global__ __launch_bounds__(256) void k_scene_gloss(AllArgs all_args)
                     }
                 }
                 if (!GUIDE || paths > 0) {
-                    for (int c = 0; c < 3; c++) { ind_term[c] = ind[c] / (float)paths; shade[c] = first + ind_term[c]; }
+                    for (int c = 0; c < 3; c++) { ind_term[c] = ind[c] / (float)paths; shade[c] = (SHINE ? first3[c] : first) + ind_term[c]; }
                     bounced = true;
                 }
             }
@@ -374,7 +492,8 @@ __global__ __launch_bounds__(256) void k_scene_gloss(AllArgs all_args)
             }
             if (gd.out_chain) gd.out_chain[p] = chain;
         }
-        if constexpr (SPLIT) trace_store_split(args.s, p, h, pos, first_term, ind_term, bounced, shade);
+        if constexpr (SPLIT && SHINE) trace_store_split3(args.s, p, h, pos, first3, ind_term, bounced, shade);
+        else if constexpr (SPLIT) trace_store_split(args.s, p, h, pos, first_term, ind_term, bounced, shade);
         else scene_store(a, p, h, pos, shade[0], shade[1], shade[2]);
     }
 }

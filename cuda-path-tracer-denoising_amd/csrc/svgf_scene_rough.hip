@@ -13,6 +13,7 @@
 #include "../../include/svgf_virtual.h"
 #include "../../include/svgf_rough.h"
 #include "svgf_gloss_table.h"
+#include "svgf_rough_table.h"
 
 #include <hip/hip_runtime.h>
 
@@ -20,11 +21,6 @@
 #include <cstdint>
 #include <new>
 #include <type_traits>
-
-struct svgf_rough_table {
-    int device, n;
-    float *dev;                 // n values on `device` (null with n == 0)
-};
 
 namespace {
 

@@ -63,8 +63,9 @@ __device__ __forceinline__ void trace_direction(const SceneArgs &a, int p, unsig
 // then scene_store's colour, where the caller asked for it, and scene_store's G-buffer stores.  svgf_scene_pixel.inc.h, which the
 // product library compiles, stays as it is; a change to scene_store's tail has to be made here as well (tests/test_split_scene.py
 // holds the colour and the G-buffer of this draw to svgf_trace_draw's on bits).
-__device__ __forceinline__ void trace_store_split(const SceneSplitArgs &s, int p, const SceneHit &h, const float pos[3], float first, const float ind[3],
-                                                  bool bounced, const float shade[3])
+// `first` is per channel: one value three times in every draw but row f23's, whose first term carries a coloured highlight.
+__device__ __forceinline__ void trace_store_split3(const SceneSplitArgs &s, int p, const SceneHit &h, const float pos[3], const float first[3],
+                                                   const float ind[3], bool bounced, const float shade[3])
 {
 #pragma clang fp contract(off)
     const SceneArgs &a = s.t.b.s;
@@ -81,7 +82,7 @@ __device__ __forceinline__ void trace_store_split(const SceneSplitArgs &s, int p
     for (int c = 0; c < 3; c++) {
         const float chroma = 1.0f + a.chroma_amp * (scene_hash(a.seed, a.frame, up, 2 + c) - 0.5f);
         col[c] = miss ? 0.0f : ((alb[c] * shade[c]) * mult) * chroma;
-        o_d[c] = miss ? 0.0f : (first * mult) * chroma;
+        o_d[c] = miss ? 0.0f : (first[c] * mult) * chroma;
         o_i[c] = bounced ? (ind[c] * mult) * chroma : 0.0f;
     }
     if (a.out_rgb) {
@@ -101,6 +102,13 @@ __device__ __forceinline__ void trace_store_split(const SceneSplitArgs &s, int p
     g[6] = alb[0]; g[7] = alb[1]; g[8] = alb[2];
     g[9] = 1.0f; g[10] = 1.0f; g[11] = 1.0f;
     reinterpret_cast<int *>(g)[12] = gid;
+}
+
+__device__ __forceinline__ void trace_store_split(const SceneSplitArgs &s, int p, const SceneHit &h, const float pos[3], float first, const float ind[3],
+                                                  bool bounced, const float shade[3])
+{
+    const float first3[3] = { first, first, first };
+    trace_store_split3(s, p, h, pos, first3, ind, bounced, shade);
 }
 
 // Args = SceneTraceArgs: svgf_trace_draw.  Args = SceneSplitArgs: svgf_trace_draw_split, the same rays with the tail above.

@@ -52,7 +52,8 @@
  *     output, chain included, for any guide_alpha; roughness on an object no ray reaches, on an object with reflect == 0 or on a glass
  *     object changes no bit.
  * Limits: a rough vertex has no next-event estimation and no multiple importance sampling: a small emitter seen in a rough surface is
- *   noisy and the analytic light leaves no highlight, the rule svgf_gloss.h set for mirrors.  Glass is always smooth.  alpha is
+ *   noisy and the analytic light leaves no highlight, the rule svgf_gloss.h set for mirrors (svgf_highlight.h, row f23, adds the
+ *   light's term in draws of its own; these stay as they are).  Glass is always smooth.  alpha is
  *   isotropic.  The guide's virtual hit under a rough surface is the smooth mirror's: between alpha = 0 and guide_alpha that is an
  *   approximation.
  * INTEGRATION.md 5p has the frame loop and the link line. */
