@@ -11,6 +11,7 @@ There is NO CPU fallback: if the HIP library is missing or no GPU is present, co
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import os
 
@@ -18,13 +19,6 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libsvgf_hip.so")
-LIB_TRACE_PATH = os.path.join(_HERE, "libsvgf_trace.so")      # the companion library of row f17 (include/svgf_trace.h)
-LIB_SPLIT_PATH = os.path.join(_HERE, "libsvgf_split.so")      # the companion library of row f18 (include/svgf_split.h)
-LIB_PATH_PATH = os.path.join(_HERE, "libsvgf_path.so")        # the companion library of row f19 (include/svgf_path.h)
-LIB_GLOSS_PATH = os.path.join(_HERE, "libsvgf_gloss.so")      # the companion library of row f20 (include/svgf_gloss.h)
-LIB_VIRTUAL_PATH = os.path.join(_HERE, "libsvgf_virtual.so")  # the companion library of row f21 (include/svgf_virtual.h)
-LIB_ROUGH_PATH = os.path.join(_HERE, "libsvgf_rough.so")  # the companion library of row f22 (include/svgf_rough.h)
-LIB_HIGHLIGHT_PATH = os.path.join(_HERE, "libsvgf_highlight.so")  # the companion library of row f23 (include/svgf_highlight.h)
 LIB_EXP_PATH = os.path.join(_HERE, "libsvgf_hip_exp.so")     # -DSVGF_BUILD_EXPERIMENTS: parked variants + tuning table (tests / tools only)
 
 SVGF_OK = 0
@@ -72,6 +66,22 @@ ROUGH_EXPORTS = ["svgf_rough_table_create", "svgf_rough_table_destroy", "svgf_ro
                  "svgf_rough_version"]
 # libsvgf_highlight.so (include/svgf_highlight.h, row f23)
 HIGHLIGHT_EXPORTS = ["svgf_highlight_draw", "svgf_highlight_draw_split", "svgf_highlight_version"]
+# The companion libraries in the order they were added (build.COMPANIONS is the builder's side of this table): the short name
+# (libsvgf_<name>.so, include/svgf_<name>.h) and every symbol the header declares.
+Companion = collections.namedtuple("Companion", "name exports")
+COMPANIONS = (Companion("trace", TRACE_EXPORTS), Companion("split", SPLIT_EXPORTS), Companion("path", PATH_EXPORTS), Companion("gloss", GLOSS_EXPORTS),
+              Companion("virtual", VIRTUAL_EXPORTS), Companion("rough", ROUGH_EXPORTS), Companion("highlight", HIGHLIGHT_EXPORTS))
+
+
+def companion_path(name: str) -> str:
+    return os.path.join(_HERE, f"libsvgf_{name}.so")
+
+
+def companion_exports(name: str) -> list[str]:
+    return next(c.exports for c in COMPANIONS if c.name == name)
+
+
+LIB_TRACE_PATH, LIB_SPLIT_PATH, LIB_PATH_PATH, LIB_GLOSS_PATH, LIB_VIRTUAL_PATH, LIB_ROUGH_PATH, LIB_HIGHLIGHT_PATH = (companion_path(c.name) for c in COMPANIONS)
 SCENE_MAX_DEPTH = 48
 SCENE_MAX_POSED = 1024
 SCENE_REFIT_CAP = 1024
@@ -399,260 +409,153 @@ def load_library(path: str | None = None, experiments: bool = False):
     return lib
 
 
-_lib_trace = None
+def _draw_argtypes(params, table=False, split=False, virtual=False, rough=False, highlight=False):
+    """The prototype of a companion draw from its parts: the scene, [the surface table], [direct, indirect], rgb, gbuffer, planes, width,
+    height, camera, synth, light, the parameter block, [SvgfVirtualParams, chain], stream, [roughness table, SvgfRoughParams],
+    [SvgfHighlightParams]."""
+    vp, ip, P = C.c_void_p, C.c_int, C.POINTER
+    return ([vp] + [vp] * table + [vp, vp] * split +
+            [vp, vp, P(SvgfPlanarGBuffer), ip, ip, P(SvgfCamera), P(SvgfSynthParams), P(SvgfSceneLight), P(params)] +
+            [P(SvgfVirtualParams), vp] * virtual + [vp] + [vp, P(SvgfRoughParams)] * rough + [P(SvgfHighlightParams)] * highlight)
+
+
+# what the draws of a library take besides the common part (the split library draws with the trace library's)
+_DRAW_PARTS = {"trace": dict(params=SvgfTraceParams), "path": dict(params=SvgfPathParams), "gloss": dict(params=SvgfPathParams, table=True),
+               "virtual": dict(params=SvgfPathParams, table=True, virtual=True),
+               "rough": dict(params=SvgfPathParams, table=True, virtual=True, rough=True),
+               "highlight": dict(params=SvgfPathParams, table=True, virtual=True, rough=True, highlight=True)}
+# the record a device table's create takes (svgf_<name>_table_create / _destroy / _size)
+_TABLE_RECORD = {"gloss": SvgfSurface, "rough": C.c_float}
+_companion_libs = {}
+
+
+def _load_companion(name: str):
+    """Load libsvgf_<name>.so (after the product library it links against), declare its prototypes and keep the handle.  Fails loudly
+    when it is absent, and - for the libraries that export svgf_<name>_version - when it was compiled against another svgf.h than the
+    product library found."""
+    if name in _companion_libs:
+        return _companion_libs[name]
+    product = load_library()
+    path, exports = companion_path(name), companion_exports(name)
+    if not os.path.exists(path):
+        raise SvgfError(f"{path} not found: build it first (python -c 'import __graft_entry__ as g; g.build()').")
+    lib = C.CDLL(path)
+    vp, ip = C.c_void_p, C.c_int
+    if f"svgf_{name}_version" in exports:
+        version = getattr(lib, f"svgf_{name}_version")
+        version.restype = ip
+        if version() != product.svgf_version():
+            raise SvgfError(f"libsvgf_{name}.so was built for ABI {version():#x}, libsvgf_hip.so is {product.svgf_version():#x}")
+    if name in _TABLE_RECORD:
+        getattr(lib, f"svgf_{name}_table_create").argtypes = [ip, C.POINTER(_TABLE_RECORD[name]), ip, C.POINTER(vp)]
+        getattr(lib, f"svgf_{name}_table_destroy").argtypes = [vp]
+        getattr(lib, f"svgf_{name}_table_destroy").restype = None
+        getattr(lib, f"svgf_{name}_table_size").argtypes = [vp]
+    if name == "split":
+        lib.svgf_trace_draw_split.argtypes = _draw_argtypes(split=True, **_DRAW_PARTS["trace"])
+        lib.svgf_trace_compose.argtypes = [ip, vp, vp, vp, C.POINTER(SvgfGuide), ip, ip, vp]
+    else:
+        getattr(lib, f"svgf_{name}_draw").argtypes = _draw_argtypes(**_DRAW_PARTS[name])
+        if name != "trace":
+            getattr(lib, f"svgf_{name}_draw_split").argtypes = _draw_argtypes(split=True, **_DRAW_PARTS[name])
+    _companion_libs[name] = lib
+    return lib
 
 
 def load_trace_library():
-    """Load libsvgf_trace.so (after the product library it links against) and declare its prototypes.  Fails loudly when it is
-    absent, and when it was compiled against another svgf.h than the product library found."""
-    global _lib_trace
-    if _lib_trace is not None:
-        return _lib_trace
-    product = load_library()
-    if not os.path.exists(LIB_TRACE_PATH):
-        raise SvgfError(f"{LIB_TRACE_PATH} not found: build it first (python -c 'import __graft_entry__ as g; g.build()').")
-    lib = C.CDLL(LIB_TRACE_PATH)
-    vp, ip = C.c_void_p, C.c_int
-    lib.svgf_trace_version.restype = ip
-    if lib.svgf_trace_version() != product.svgf_version():
-        raise SvgfError(f"libsvgf_trace.so was built for ABI {lib.svgf_trace_version():#x}, libsvgf_hip.so is {product.svgf_version():#x}")
-    lib.svgf_trace_draw.argtypes = [vp, vp, vp, C.POINTER(SvgfPlanarGBuffer), ip, ip, C.POINTER(SvgfCamera), C.POINTER(SvgfSynthParams),
-                                    C.POINTER(SvgfSceneLight), C.POINTER(SvgfTraceParams), vp]
-    _lib_trace = lib
-    return lib
-
-
-_lib_split = None
+    return _load_companion("trace")
 
 
 def load_split_library():
-    """Load libsvgf_split.so (row f18; after the product library it links against) and declare its prototypes.  Fails loudly when
-    it is absent."""
-    global _lib_split
-    if _lib_split is not None:
-        return _lib_split
-    load_library()
-    if not os.path.exists(LIB_SPLIT_PATH):
-        raise SvgfError(f"{LIB_SPLIT_PATH} not found: build it first (python -c 'import __graft_entry__ as g; g.build()').")
-    lib = C.CDLL(LIB_SPLIT_PATH)
-    vp, ip = C.c_void_p, C.c_int
-    lib.svgf_trace_draw_split.argtypes = [vp, vp, vp, vp, vp, C.POINTER(SvgfPlanarGBuffer), ip, ip, C.POINTER(SvgfCamera), C.POINTER(SvgfSynthParams),
-                                          C.POINTER(SvgfSceneLight), C.POINTER(SvgfTraceParams), vp]
-    lib.svgf_trace_compose.argtypes = [ip, vp, vp, vp, C.POINTER(SvgfGuide), ip, ip, vp]
-    _lib_split = lib
-    return lib
-
-
-_lib_path = None
+    return _load_companion("split")
 
 
 def load_path_library():
-    """Load libsvgf_path.so (row f19; after the product library it links against) and declare its prototypes.  Fails loudly when it
-    is absent, and when it was compiled against another svgf.h than the product library found."""
-    global _lib_path
-    if _lib_path is not None:
-        return _lib_path
-    product = load_library()
-    if not os.path.exists(LIB_PATH_PATH):
-        raise SvgfError(f"{LIB_PATH_PATH} not found: build it first (python -c 'import __graft_entry__ as g; g.build()').")
-    lib = C.CDLL(LIB_PATH_PATH)
-    vp, ip = C.c_void_p, C.c_int
-    lib.svgf_path_version.restype = ip
-    if lib.svgf_path_version() != product.svgf_version():
-        raise SvgfError(f"libsvgf_path.so was built for ABI {lib.svgf_path_version():#x}, libsvgf_hip.so is {product.svgf_version():#x}")
-    lib.svgf_path_draw.argtypes = [vp, vp, vp, C.POINTER(SvgfPlanarGBuffer), ip, ip, C.POINTER(SvgfCamera), C.POINTER(SvgfSynthParams),
-                                   C.POINTER(SvgfSceneLight), C.POINTER(SvgfPathParams), vp]
-    lib.svgf_path_draw_split.argtypes = [vp, vp, vp, vp, vp, C.POINTER(SvgfPlanarGBuffer), ip, ip, C.POINTER(SvgfCamera), C.POINTER(SvgfSynthParams),
-                                         C.POINTER(SvgfSceneLight), C.POINTER(SvgfPathParams), vp]
-    _lib_path = lib
-    return lib
-
-
-_lib_gloss = None
+    return _load_companion("path")
 
 
 def load_gloss_library():
-    """Load libsvgf_gloss.so (row f20; after the product library it links against) and declare its prototypes.  Fails loudly when it
-    is absent, and when it was compiled against another svgf.h than the product library found."""
-    global _lib_gloss
-    if _lib_gloss is not None:
-        return _lib_gloss
-    product = load_library()
-    if not os.path.exists(LIB_GLOSS_PATH):
-        raise SvgfError(f"{LIB_GLOSS_PATH} not found: build it first (python -c 'import __graft_entry__ as g; g.build()').")
-    lib = C.CDLL(LIB_GLOSS_PATH)
-    vp, ip = C.c_void_p, C.c_int
-    lib.svgf_gloss_version.restype = ip
-    if lib.svgf_gloss_version() != product.svgf_version():
-        raise SvgfError(f"libsvgf_gloss.so was built for ABI {lib.svgf_gloss_version():#x}, libsvgf_hip.so is {product.svgf_version():#x}")
-    lib.svgf_gloss_table_create.argtypes = [ip, C.POINTER(SvgfSurface), ip, C.POINTER(vp)]
-    lib.svgf_gloss_table_destroy.argtypes = [vp]
-    lib.svgf_gloss_table_destroy.restype = None
-    lib.svgf_gloss_table_size.argtypes = [vp]
-    lib.svgf_gloss_draw.argtypes = [vp, vp, vp, vp, C.POINTER(SvgfPlanarGBuffer), ip, ip, C.POINTER(SvgfCamera), C.POINTER(SvgfSynthParams),
-                                    C.POINTER(SvgfSceneLight), C.POINTER(SvgfPathParams), vp]
-    lib.svgf_gloss_draw_split.argtypes = [vp, vp, vp, vp, vp, vp, C.POINTER(SvgfPlanarGBuffer), ip, ip, C.POINTER(SvgfCamera),
-                                          C.POINTER(SvgfSynthParams), C.POINTER(SvgfSceneLight), C.POINTER(SvgfPathParams), vp]
-    _lib_gloss = lib
-    return lib
-
-
-_lib_virtual = None
+    return _load_companion("gloss")
 
 
 def load_virtual_library():
-    """Load libsvgf_virtual.so (row f21; after the product library it links against) and declare its prototypes.  Fails loudly when it
-    is absent, and when it was compiled against another svgf.h than the product library found."""
-    global _lib_virtual
-    if _lib_virtual is not None:
-        return _lib_virtual
-    product = load_library()
-    if not os.path.exists(LIB_VIRTUAL_PATH):
-        raise SvgfError(f"{LIB_VIRTUAL_PATH} not found: build it first (python -c 'import __graft_entry__ as g; g.build()').")
-    lib = C.CDLL(LIB_VIRTUAL_PATH)
-    vp, ip = C.c_void_p, C.c_int
-    lib.svgf_virtual_version.restype = ip
-    if lib.svgf_virtual_version() != product.svgf_version():
-        raise SvgfError(f"libsvgf_virtual.so was built for ABI {lib.svgf_virtual_version():#x}, libsvgf_hip.so is {product.svgf_version():#x}")
-    lib.svgf_virtual_draw.argtypes = [vp, vp, vp, vp, C.POINTER(SvgfPlanarGBuffer), ip, ip, C.POINTER(SvgfCamera), C.POINTER(SvgfSynthParams),
-                                      C.POINTER(SvgfSceneLight), C.POINTER(SvgfPathParams), C.POINTER(SvgfVirtualParams), vp, vp]
-    lib.svgf_virtual_draw_split.argtypes = [vp, vp, vp, vp, vp, vp, C.POINTER(SvgfPlanarGBuffer), ip, ip, C.POINTER(SvgfCamera),
-                                            C.POINTER(SvgfSynthParams), C.POINTER(SvgfSceneLight), C.POINTER(SvgfPathParams),
-                                            C.POINTER(SvgfVirtualParams), vp, vp]
-    _lib_virtual = lib
-    return lib
-
-
-_lib_rough = None
+    return _load_companion("virtual")
 
 
 def load_rough_library():
-    """Load libsvgf_rough.so (row f22; after the product library it links against) and declare its prototypes.  Fails loudly when it
-    is absent, and when it was compiled against another svgf.h than the product library found."""
-    global _lib_rough
-    if _lib_rough is not None:
-        return _lib_rough
-    product = load_library()
-    if not os.path.exists(LIB_ROUGH_PATH):
-        raise SvgfError(f"{LIB_ROUGH_PATH} not found: build it first (python -c 'import __graft_entry__ as g; g.build()').")
-    lib = C.CDLL(LIB_ROUGH_PATH)
-    vp, ip = C.c_void_p, C.c_int
-    lib.svgf_rough_version.restype = ip
-    if lib.svgf_rough_version() != product.svgf_version():
-        raise SvgfError(f"libsvgf_rough.so was built for ABI {lib.svgf_rough_version():#x}, libsvgf_hip.so is {product.svgf_version():#x}")
-    lib.svgf_rough_table_create.argtypes = [ip, C.POINTER(C.c_float), ip, C.POINTER(vp)]
-    lib.svgf_rough_table_destroy.argtypes = [vp]
-    lib.svgf_rough_table_destroy.restype = None
-    lib.svgf_rough_table_size.argtypes = [vp]
-    lib.svgf_rough_draw.argtypes = [vp, vp, vp, vp, C.POINTER(SvgfPlanarGBuffer), ip, ip, C.POINTER(SvgfCamera), C.POINTER(SvgfSynthParams),
-                                    C.POINTER(SvgfSceneLight), C.POINTER(SvgfPathParams), C.POINTER(SvgfVirtualParams), vp, vp, vp,
-                                    C.POINTER(SvgfRoughParams)]
-    lib.svgf_rough_draw_split.argtypes = [vp, vp, vp, vp, vp, vp, C.POINTER(SvgfPlanarGBuffer), ip, ip, C.POINTER(SvgfCamera),
-                                          C.POINTER(SvgfSynthParams), C.POINTER(SvgfSceneLight), C.POINTER(SvgfPathParams),
-                                          C.POINTER(SvgfVirtualParams), vp, vp, vp, C.POINTER(SvgfRoughParams)]
-    _lib_rough = lib
-    return lib
-
-
-_lib_highlight = None
+    return _load_companion("rough")
 
 
 def load_highlight_library():
-    """Load libsvgf_highlight.so (row f23; after the product library it links against) and declare its prototypes.  Fails loudly when
-    it is absent, and when it was compiled against another svgf.h than the product library found."""
-    global _lib_highlight
-    if _lib_highlight is not None:
-        return _lib_highlight
-    product = load_library()
-    if not os.path.exists(LIB_HIGHLIGHT_PATH):
-        raise SvgfError(f"{LIB_HIGHLIGHT_PATH} not found: build it first (python -c 'import __graft_entry__ as g; g.build()').")
-    lib = C.CDLL(LIB_HIGHLIGHT_PATH)
-    vp, ip = C.c_void_p, C.c_int
-    lib.svgf_highlight_version.restype = ip
-    if lib.svgf_highlight_version() != product.svgf_version():
-        raise SvgfError(f"libsvgf_highlight.so was built for ABI {lib.svgf_highlight_version():#x}, libsvgf_hip.so is {product.svgf_version():#x}")
-    lib.svgf_highlight_draw.argtypes = [vp, vp, vp, vp, C.POINTER(SvgfPlanarGBuffer), ip, ip, C.POINTER(SvgfCamera), C.POINTER(SvgfSynthParams),
-                                        C.POINTER(SvgfSceneLight), C.POINTER(SvgfPathParams), C.POINTER(SvgfVirtualParams), vp, vp, vp,
-                                        C.POINTER(SvgfRoughParams), C.POINTER(SvgfHighlightParams)]
-    lib.svgf_highlight_draw_split.argtypes = [vp, vp, vp, vp, vp, vp, C.POINTER(SvgfPlanarGBuffer), ip, ip, C.POINTER(SvgfCamera),
-                                              C.POINTER(SvgfSynthParams), C.POINTER(SvgfSceneLight), C.POINTER(SvgfPathParams),
-                                              C.POINTER(SvgfVirtualParams), vp, vp, vp, C.POINTER(SvgfRoughParams),
-                                              C.POINTER(SvgfHighlightParams)]
-    _lib_highlight = lib
-    return lib
+    return _load_companion("highlight")
 
 
-class RoughTable:
+class _DeviceTable:
+    """One record per object id of a scene, on one device: allocated and uploaded once by svgf_<name>_table_create of libsvgf_<name>.so;
+    usable as a context manager.  A subclass names the library and gives the records' numpy dtype and ctypes type."""
+    name = record_dtype = record_ctype = None
+
+    def __init__(self, records=None, device: int = 0):
+        self.lib = _load_companion(self.name)
+        arr = np.zeros(0, self.record_dtype) if records is None else np.ascontiguousarray(records, dtype=self.record_dtype).reshape(-1)
+        self.h = C.c_void_p()
+        rc = getattr(self.lib, f"svgf_{self.name}_table_create")(int(device), arr.ctypes.data_as(C.POINTER(self.record_ctype)), len(arr), C.byref(self.h))
+        if rc != SVGF_OK:
+            self.h = C.c_void_p()
+            raise SvgfError(f"svgf_{self.name}_table_create failed ({rc})")
+        self.device = int(device)
+
+    def __len__(self):
+        return int(getattr(self.lib, f"svgf_{self.name}_table_size")(self.h))
+
+    def free(self):
+        if self.h:
+            getattr(self.lib, f"svgf_{self.name}_table_destroy")(self.h)
+            self.h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.free()
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class RoughTable(_DeviceTable):
     """svgf_rough_table: the GGX roughness of a scene's objects on one device, one float32 per object id, 0 = smooth.  `alpha` is
     anything np.asarray turns into float32 (None or empty: a table of no entries).  Allocates and uploads once; usable as a context
     manager."""
+    name, record_dtype, record_ctype = "rough", np.float32, C.c_float
 
     def __init__(self, alpha=None, device: int = 0):
-        self.lib = load_rough_library()
-        arr = np.zeros(0, np.float32) if alpha is None else np.ascontiguousarray(alpha, dtype=np.float32).reshape(-1)
-        self.h = C.c_void_p()
-        rc = self.lib.svgf_rough_table_create(int(device), arr.ctypes.data_as(C.POINTER(C.c_float)), len(arr), C.byref(self.h))
-        if rc != SVGF_OK:
-            self.h = C.c_void_p()
-            raise SvgfError(f"svgf_rough_table_create failed ({rc})")
-        self.device = int(device)
-
-    def __len__(self):
-        return int(self.lib.svgf_rough_table_size(self.h))
-
-    def free(self):
-        if self.h:
-            self.lib.svgf_rough_table_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.free()
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
+        super().__init__(alpha, device)
 
 
-class GlossTable:
+class GlossTable(_DeviceTable):
     """svgf_gloss_table: the surfaces of a scene's objects on one device, one SvgfSurface per object id.  `surfaces` is a numpy array
     of scene.SURFACE_DTYPE (or anything np.asarray turns into one; None or empty: a table of no records).  Allocates and uploads once;
     usable as a context manager."""
+    name, record_ctype = "gloss", SvgfSurface
 
     def __init__(self, surfaces=None, device: int = 0):
         from . import scene as _scene
-        self.lib = load_gloss_library()
-        arr = np.zeros(0, _scene.SURFACE_DTYPE) if surfaces is None else np.ascontiguousarray(surfaces, dtype=_scene.SURFACE_DTYPE).reshape(-1)
-        self.h = C.c_void_p()
-        rc = self.lib.svgf_gloss_table_create(int(device), arr.ctypes.data_as(C.POINTER(SvgfSurface)), len(arr), C.byref(self.h))
-        if rc != SVGF_OK:
-            self.h = C.c_void_p()
-            raise SvgfError(f"svgf_gloss_table_create failed ({rc})")
-        self.device = int(device)
+        self.record_dtype = _scene.SURFACE_DTYPE
+        super().__init__(surfaces, device)
 
-    def __len__(self):
-        return int(self.lib.svgf_gloss_table_size(self.h))
 
-    def free(self):
-        if self.h:
-            self.lib.svgf_gloss_table_destroy(self.h)
-            self.h = C.c_void_p()
+# int or float per field of the companions' parameter blocks
+_CONVERTERS = {s: tuple(float if t is C.c_float else int for _, t in s._fields_)
+               for s in (SvgfTraceParams, SvgfPathParams, SvgfVirtualParams, SvgfRoughParams, SvgfHighlightParams)}
 
-    def __enter__(self):
-        return self
 
-    def __exit__(self, *exc):
-        self.free()
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
+def _filled(struct, values):
+    """`struct` with its fields set from `values`, each converted to its field's type."""
+    return struct(*[c(v) for c, v in zip(_CONVERTERS[struct], values)])
 
 
 def _ptr(x):
@@ -1344,111 +1247,84 @@ class Scene:
         if rc != SVGF_OK:
             raise SvgfError(f"svgf_scene_draw_shadowed failed ({rc})")
 
-    def draw_traced(self, out_rgb, out_gbuffer, width: int, height: int, camera, light, frame: int, bounce_samples: int = 1,
-                    ambient: float = 0.15, shadow_secondary: int = 1, seed: int = 1, noise: float = 0.6, fireflies: float = 0.02,
-                    pixel_length=None, stream=None):
-        """svgf_trace_draw of libsvgf_trace.so (row f17): draw_shadowed's frame plus one diffuse bounce gathered over
-        `bounce_samples` directions.  One launch on `stream`; never waits."""
+    def _companion_draw(self, name, out, out_gbuffer, width, height, camera, light, frame, params, synth, stream, table=None, guide=None,
+                        lobe=None, shine=None):
+        """One draw of libsvgf_<name>.so, every companion's the same way.  `out` is (out_rgb,) or, for the split form, (out_direct,
+        out_indirect, out_rgb); `params` the values of the library's parameter block, `synth` (seed, noise, fireflies, pixel_length);
+        the libraries that take them read `table` (a GlossTable or None), `guide` (max_chain, id_offset, out_chain), `lobe` (a RoughTable
+        or None, guide_alpha) and `shine` (enable, clamp).  `out_gbuffer` is AoS texels or a SvgfPlanarGBuffer."""
         from . import synth as _synth
+        parts = _DRAW_PARTS["trace" if name == "split" else name]
+        symbol = ("svgf_trace_draw" if name == "split" else f"svgf_{name}_draw") + "_split" * (len(out) == 3)
         cam = camera if isinstance(camera, SvgfCamera) else SvgfCamera.from_dict(camera)
+        seed, noise, fireflies, pixel_length = synth
         if pixel_length is None:
             fovy = camera.get("fovy_deg", 45.0) if isinstance(camera, dict) else 45.0
             pixel_length = _synth._pixel_length(width, height, fovy)
         sp = SvgfSynthParams(int(frame), int(seed), float(noise), float(fireflies))
         sp.pixel_length[0], sp.pixel_length[1] = float(pixel_length[0]), float(pixel_length[1])
-        tp = SvgfTraceParams(int(bounce_samples), float(ambient), int(shadow_secondary))
         planar = isinstance(out_gbuffer, SvgfPlanarGBuffer)
-        rc = load_trace_library().svgf_trace_draw(self.h, _ptr(out_rgb), None if planar else _ptr(out_gbuffer), C.byref(out_gbuffer) if planar else None,
-                                                  int(width), int(height), C.byref(cam), C.byref(sp), C.byref(light), C.byref(tp), _stream(stream))
+        args = [self.h] + ([table.h if table is not None else None] if parts.get("table") else []) + [_ptr(o) for o in out]
+        args += [None if planar else _ptr(out_gbuffer), C.byref(out_gbuffer) if planar else None, int(width), int(height), C.byref(cam),
+                 C.byref(sp), C.byref(light), C.byref(_filled(parts["params"], params))]
+        if parts.get("virtual"):
+            args += [C.byref(_filled(SvgfVirtualParams, guide[:2])), _ptr(guide[2])]
+        args.append(_stream(stream))
+        if parts.get("rough"):
+            args += [lobe[0].h if lobe[0] is not None else None, C.byref(_filled(SvgfRoughParams, lobe[1:]))]
+        if parts.get("highlight"):
+            args.append(C.byref(_filled(SvgfHighlightParams, shine)))
+        rc = getattr(_load_companion(name), symbol)(*args)
         if rc != SVGF_OK:
-            raise SvgfError(f"svgf_trace_draw failed ({rc})")
+            raise SvgfError(f"{symbol} failed ({rc})")
+
+    def draw_traced(self, out_rgb, out_gbuffer, width: int, height: int, camera, light, frame: int, bounce_samples: int = 1,
+                    ambient: float = 0.15, shadow_secondary: int = 1, seed: int = 1, noise: float = 0.6, fireflies: float = 0.02,
+                    pixel_length=None, stream=None):
+        """svgf_trace_draw of libsvgf_trace.so (row f17): draw_shadowed's frame plus one diffuse bounce gathered over
+        `bounce_samples` directions.  One launch on `stream`; never waits."""
+        self._companion_draw("trace", (out_rgb,), out_gbuffer, width, height, camera, light, frame,
+                             (bounce_samples, ambient, shadow_secondary), (seed, noise, fireflies, pixel_length), stream)
 
     def draw_traced_split(self, out_direct, out_indirect, out_gbuffer, width: int, height: int, camera, light, frame: int,
                           bounce_samples: int = 1, ambient: float = 0.15, shadow_secondary: int = 1, seed: int = 1, noise: float = 0.6,
                           fireflies: float = 0.02, pixel_length=None, out_rgb=None, stream=None):
         """svgf_trace_draw_split of libsvgf_split.so (row f18): draw_traced's rays, with the direct and the indirect term written
         apart and without the albedo; `out_rgb` (optional) receives draw_traced's colour.  One launch on `stream`; never waits."""
-        from . import synth as _synth
-        cam = camera if isinstance(camera, SvgfCamera) else SvgfCamera.from_dict(camera)
-        if pixel_length is None:
-            fovy = camera.get("fovy_deg", 45.0) if isinstance(camera, dict) else 45.0
-            pixel_length = _synth._pixel_length(width, height, fovy)
-        sp = SvgfSynthParams(int(frame), int(seed), float(noise), float(fireflies))
-        sp.pixel_length[0], sp.pixel_length[1] = float(pixel_length[0]), float(pixel_length[1])
-        tp = SvgfTraceParams(int(bounce_samples), float(ambient), int(shadow_secondary))
-        planar = isinstance(out_gbuffer, SvgfPlanarGBuffer)
-        rc = load_split_library().svgf_trace_draw_split(self.h, _ptr(out_direct), _ptr(out_indirect), _ptr(out_rgb), None if planar else _ptr(out_gbuffer),
-                                                        C.byref(out_gbuffer) if planar else None, int(width), int(height), C.byref(cam), C.byref(sp),
-                                                        C.byref(light), C.byref(tp), _stream(stream))
-        if rc != SVGF_OK:
-            raise SvgfError(f"svgf_trace_draw_split failed ({rc})")
-
-    def _path_call_args(self, width, height, camera, frame, paths, max_depth, rr_depth, ambient, shadow_secondary, seed, noise, fireflies,
-                        pixel_length):
-        from . import synth as _synth
-        cam = camera if isinstance(camera, SvgfCamera) else SvgfCamera.from_dict(camera)
-        if pixel_length is None:
-            fovy = camera.get("fovy_deg", 45.0) if isinstance(camera, dict) else 45.0
-            pixel_length = _synth._pixel_length(width, height, fovy)
-        sp = SvgfSynthParams(int(frame), int(seed), float(noise), float(fireflies))
-        sp.pixel_length[0], sp.pixel_length[1] = float(pixel_length[0]), float(pixel_length[1])
-        return cam, sp, SvgfPathParams(int(paths), int(max_depth), int(rr_depth), float(ambient), int(shadow_secondary))
+        self._companion_draw("split", (out_direct, out_indirect, out_rgb), out_gbuffer, width, height, camera, light, frame,
+                             (bounce_samples, ambient, shadow_secondary), (seed, noise, fireflies, pixel_length), stream)
 
     def draw_path(self, out_rgb, out_gbuffer, width: int, height: int, camera, light, frame: int, paths: int = 1, max_depth: int = 4,
                   rr_depth: int = 2, ambient: float = 0.15, shadow_secondary: int = 1, seed: int = 1, noise: float = 0.6,
                   fireflies: float = 0.02, pixel_length=None, stream=None):
         """svgf_path_draw of libsvgf_path.so (row f19): draw_traced's frame with `paths` paths of up to `max_depth` diffuse bounces per
         pixel in the one bounce's place, Russian roulette from bounce `rr_depth` on (0: none).  One launch on `stream`; never waits."""
-        cam, sp, pp = self._path_call_args(width, height, camera, frame, paths, max_depth, rr_depth, ambient, shadow_secondary, seed, noise,
-                                           fireflies, pixel_length)
-        planar = isinstance(out_gbuffer, SvgfPlanarGBuffer)
-        rc = load_path_library().svgf_path_draw(self.h, _ptr(out_rgb), None if planar else _ptr(out_gbuffer), C.byref(out_gbuffer) if planar else None,
-                                                int(width), int(height), C.byref(cam), C.byref(sp), C.byref(light), C.byref(pp), _stream(stream))
-        if rc != SVGF_OK:
-            raise SvgfError(f"svgf_path_draw failed ({rc})")
+        self._companion_draw("path", (out_rgb,), out_gbuffer, width, height, camera, light, frame,
+                             (paths, max_depth, rr_depth, ambient, shadow_secondary), (seed, noise, fireflies, pixel_length), stream)
 
     def draw_path_split(self, out_direct, out_indirect, out_gbuffer, width: int, height: int, camera, light, frame: int, paths: int = 1,
                         max_depth: int = 4, rr_depth: int = 2, ambient: float = 0.15, shadow_secondary: int = 1, seed: int = 1,
                         noise: float = 0.6, fireflies: float = 0.02, pixel_length=None, out_rgb=None, stream=None):
         """svgf_path_draw_split of libsvgf_path.so (row f19): draw_path's rays, with the direct and the indirect term written apart and
         without the albedo; `out_rgb` (optional) receives draw_path's colour.  One launch on `stream`; never waits."""
-        cam, sp, pp = self._path_call_args(width, height, camera, frame, paths, max_depth, rr_depth, ambient, shadow_secondary, seed, noise,
-                                           fireflies, pixel_length)
-        planar = isinstance(out_gbuffer, SvgfPlanarGBuffer)
-        rc = load_path_library().svgf_path_draw_split(self.h, _ptr(out_direct), _ptr(out_indirect), _ptr(out_rgb), None if planar else _ptr(out_gbuffer),
-                                                      C.byref(out_gbuffer) if planar else None, int(width), int(height), C.byref(cam), C.byref(sp),
-                                                      C.byref(light), C.byref(pp), _stream(stream))
-        if rc != SVGF_OK:
-            raise SvgfError(f"svgf_path_draw_split failed ({rc})")
+        self._companion_draw("path", (out_direct, out_indirect, out_rgb), out_gbuffer, width, height, camera, light, frame,
+                             (paths, max_depth, rr_depth, ambient, shadow_secondary), (seed, noise, fireflies, pixel_length), stream)
 
     def draw_gloss(self, out_rgb, out_gbuffer, width: int, height: int, camera, light, frame: int, table=None, paths: int = 1,
                    max_depth: int = 4, rr_depth: int = 2, ambient: float = 0.15, shadow_secondary: int = 1, seed: int = 1, noise: float = 0.6,
                    fireflies: float = 0.02, pixel_length=None, stream=None):
         """svgf_gloss_draw of libsvgf_gloss.so (row f20): draw_path's frame with the mirror and glass surfaces of `table` (a GlossTable,
         or None: every surface diffuse, draw_path's frame on bits) along the paths.  One launch on `stream`; never waits."""
-        cam, sp, pp = self._path_call_args(width, height, camera, frame, paths, max_depth, rr_depth, ambient, shadow_secondary, seed, noise,
-                                           fireflies, pixel_length)
-        planar = isinstance(out_gbuffer, SvgfPlanarGBuffer)
-        rc = load_gloss_library().svgf_gloss_draw(self.h, table.h if table is not None else None, _ptr(out_rgb), None if planar else _ptr(out_gbuffer),
-                                                  C.byref(out_gbuffer) if planar else None, int(width), int(height), C.byref(cam), C.byref(sp),
-                                                  C.byref(light), C.byref(pp), _stream(stream))
-        if rc != SVGF_OK:
-            raise SvgfError(f"svgf_gloss_draw failed ({rc})")
+        self._companion_draw("gloss", (out_rgb,), out_gbuffer, width, height, camera, light, frame,
+                             (paths, max_depth, rr_depth, ambient, shadow_secondary), (seed, noise, fireflies, pixel_length), stream, table)
 
     def draw_gloss_split(self, out_direct, out_indirect, out_gbuffer, width: int, height: int, camera, light, frame: int, table=None,
                          paths: int = 1, max_depth: int = 4, rr_depth: int = 2, ambient: float = 0.15, shadow_secondary: int = 1, seed: int = 1,
                          noise: float = 0.6, fireflies: float = 0.02, pixel_length=None, out_rgb=None, stream=None):
         """svgf_gloss_draw_split of libsvgf_gloss.so (row f20): draw_gloss's rays, with the direct and the indirect term written apart
         and without the albedo; `out_rgb` (optional) receives draw_gloss's colour.  One launch on `stream`; never waits."""
-        cam, sp, pp = self._path_call_args(width, height, camera, frame, paths, max_depth, rr_depth, ambient, shadow_secondary, seed, noise,
-                                           fireflies, pixel_length)
-        planar = isinstance(out_gbuffer, SvgfPlanarGBuffer)
-        rc = load_gloss_library().svgf_gloss_draw_split(self.h, table.h if table is not None else None, _ptr(out_direct), _ptr(out_indirect),
-                                                        _ptr(out_rgb), None if planar else _ptr(out_gbuffer),
-                                                        C.byref(out_gbuffer) if planar else None, int(width), int(height), C.byref(cam),
-                                                        C.byref(sp), C.byref(light), C.byref(pp), _stream(stream))
-        if rc != SVGF_OK:
-            raise SvgfError(f"svgf_gloss_draw_split failed ({rc})")
+        self._companion_draw("gloss", (out_direct, out_indirect, out_rgb), out_gbuffer, width, height, camera, light, frame,
+                             (paths, max_depth, rr_depth, ambient, shadow_secondary), (seed, noise, fireflies, pixel_length), stream, table)
 
     def draw_virtual(self, out_rgb, out_gbuffer, width: int, height: int, camera, light, frame: int, table=None, paths: int = 1,
                      max_depth: int = 4, rr_depth: int = 2, ambient: float = 0.15, shadow_secondary: int = 1, seed: int = 1, noise: float = 0.6,
@@ -1456,16 +1332,9 @@ class Scene:
         """svgf_virtual_draw of libsvgf_virtual.so (row f21): draw_gloss's frame, on bits, with a G-buffer whose normal, position and
         geomId describe what a full mirror or glass shows (a guide chain of at most `max_chain` rays; `id_offset` is added to a virtual
         hit's id).  `out_chain` (optional) receives one int32 per pixel.  One launch on `stream`; never waits."""
-        cam, sp, pp = self._path_call_args(width, height, camera, frame, paths, max_depth, rr_depth, ambient, shadow_secondary, seed, noise,
-                                           fireflies, pixel_length)
-        vp = SvgfVirtualParams(int(max_chain), int(id_offset))
-        planar = isinstance(out_gbuffer, SvgfPlanarGBuffer)
-        rc = load_virtual_library().svgf_virtual_draw(self.h, table.h if table is not None else None, _ptr(out_rgb),
-                                                      None if planar else _ptr(out_gbuffer), C.byref(out_gbuffer) if planar else None,
-                                                      int(width), int(height), C.byref(cam), C.byref(sp), C.byref(light), C.byref(pp),
-                                                      C.byref(vp), _ptr(out_chain), _stream(stream))
-        if rc != SVGF_OK:
-            raise SvgfError(f"svgf_virtual_draw failed ({rc})")
+        self._companion_draw("virtual", (out_rgb,), out_gbuffer, width, height, camera, light, frame,
+                             (paths, max_depth, rr_depth, ambient, shadow_secondary), (seed, noise, fireflies, pixel_length), stream, table,
+                             (max_chain, id_offset, out_chain))
 
     def draw_virtual_split(self, out_direct, out_indirect, out_gbuffer, width: int, height: int, camera, light, frame: int, table=None,
                            paths: int = 1, max_depth: int = 4, rr_depth: int = 2, ambient: float = 0.15, shadow_secondary: int = 1, seed: int = 1,
@@ -1473,17 +1342,9 @@ class Scene:
                            id_offset: int = 0, out_chain=None):
         """svgf_virtual_draw_split of libsvgf_virtual.so (row f21): draw_gloss_split's D, I and colour, on bits, with draw_virtual's
         G-buffer.  One launch on `stream`; never waits."""
-        cam, sp, pp = self._path_call_args(width, height, camera, frame, paths, max_depth, rr_depth, ambient, shadow_secondary, seed, noise,
-                                           fireflies, pixel_length)
-        vp = SvgfVirtualParams(int(max_chain), int(id_offset))
-        planar = isinstance(out_gbuffer, SvgfPlanarGBuffer)
-        rc = load_virtual_library().svgf_virtual_draw_split(self.h, table.h if table is not None else None, _ptr(out_direct), _ptr(out_indirect),
-                                                            _ptr(out_rgb), None if planar else _ptr(out_gbuffer),
-                                                            C.byref(out_gbuffer) if planar else None, int(width), int(height), C.byref(cam),
-                                                            C.byref(sp), C.byref(light), C.byref(pp), C.byref(vp), _ptr(out_chain),
-                                                            _stream(stream))
-        if rc != SVGF_OK:
-            raise SvgfError(f"svgf_virtual_draw_split failed ({rc})")
+        self._companion_draw("virtual", (out_direct, out_indirect, out_rgb), out_gbuffer, width, height, camera, light, frame,
+                             (paths, max_depth, rr_depth, ambient, shadow_secondary), (seed, noise, fireflies, pixel_length), stream, table,
+                             (max_chain, id_offset, out_chain))
 
     def draw_rough(self, out_rgb, out_gbuffer, width: int, height: int, camera, light, frame: int, table=None, paths: int = 1,
                    max_depth: int = 4, rr_depth: int = 2, ambient: float = 0.15, shadow_secondary: int = 1, seed: int = 1, noise: float = 0.6,
@@ -1492,17 +1353,9 @@ class Scene:
         """svgf_rough_draw of libsvgf_rough.so (row f22): draw_virtual with a GGX lobe on the mirror vertices of the objects the
         RoughTable `rough` gives a roughness; the guide follows a full mirror no rougher than `guide_alpha`.  With rough=None it is
         draw_virtual's frame on bits.  One launch on `stream`; never waits."""
-        cam, sp, pp = self._path_call_args(width, height, camera, frame, paths, max_depth, rr_depth, ambient, shadow_secondary, seed, noise,
-                                           fireflies, pixel_length)
-        vp, rp = SvgfVirtualParams(int(max_chain), int(id_offset)), SvgfRoughParams(float(guide_alpha))
-        planar = isinstance(out_gbuffer, SvgfPlanarGBuffer)
-        rc = load_rough_library().svgf_rough_draw(self.h, table.h if table is not None else None, _ptr(out_rgb),
-                                                  None if planar else _ptr(out_gbuffer), C.byref(out_gbuffer) if planar else None,
-                                                  int(width), int(height), C.byref(cam), C.byref(sp), C.byref(light), C.byref(pp),
-                                                  C.byref(vp), _ptr(out_chain), _stream(stream), rough.h if rough is not None else None,
-                                                  C.byref(rp))
-        if rc != SVGF_OK:
-            raise SvgfError(f"svgf_rough_draw failed ({rc})")
+        self._companion_draw("rough", (out_rgb,), out_gbuffer, width, height, camera, light, frame,
+                             (paths, max_depth, rr_depth, ambient, shadow_secondary), (seed, noise, fireflies, pixel_length), stream, table,
+                             (max_chain, id_offset, out_chain), (rough, guide_alpha))
 
     def draw_rough_split(self, out_direct, out_indirect, out_gbuffer, width: int, height: int, camera, light, frame: int, table=None,
                          paths: int = 1, max_depth: int = 4, rr_depth: int = 2, ambient: float = 0.15, shadow_secondary: int = 1, seed: int = 1,
@@ -1510,17 +1363,9 @@ class Scene:
                          id_offset: int = 0, out_chain=None, rough=None, guide_alpha: float = 0.0):
         """svgf_rough_draw_split of libsvgf_rough.so (row f22): draw_virtual_split with draw_rough's lobe and guide.  One launch on
         `stream`; never waits."""
-        cam, sp, pp = self._path_call_args(width, height, camera, frame, paths, max_depth, rr_depth, ambient, shadow_secondary, seed, noise,
-                                           fireflies, pixel_length)
-        vp, rp = SvgfVirtualParams(int(max_chain), int(id_offset)), SvgfRoughParams(float(guide_alpha))
-        planar = isinstance(out_gbuffer, SvgfPlanarGBuffer)
-        rc = load_rough_library().svgf_rough_draw_split(self.h, table.h if table is not None else None, _ptr(out_direct), _ptr(out_indirect),
-                                                        _ptr(out_rgb), None if planar else _ptr(out_gbuffer),
-                                                        C.byref(out_gbuffer) if planar else None, int(width), int(height), C.byref(cam),
-                                                        C.byref(sp), C.byref(light), C.byref(pp), C.byref(vp), _ptr(out_chain),
-                                                        _stream(stream), rough.h if rough is not None else None, C.byref(rp))
-        if rc != SVGF_OK:
-            raise SvgfError(f"svgf_rough_draw_split failed ({rc})")
+        self._companion_draw("rough", (out_direct, out_indirect, out_rgb), out_gbuffer, width, height, camera, light, frame,
+                             (paths, max_depth, rr_depth, ambient, shadow_secondary), (seed, noise, fireflies, pixel_length), stream, table,
+                             (max_chain, id_offset, out_chain), (rough, guide_alpha))
 
     def draw_highlight(self, out_rgb, out_gbuffer, width: int, height: int, camera, light, frame: int, table=None, paths: int = 1,
                        max_depth: int = 4, rr_depth: int = 2, ambient: float = 0.15, shadow_secondary: int = 1, seed: int = 1, noise: float = 0.6,
@@ -1529,17 +1374,9 @@ class Scene:
         """svgf_highlight_draw of libsvgf_highlight.so (row f23): draw_rough with the analytic light's GGX term at the rough vertices
         (`enable` 1), its scalar factor clamped to `clamp` where that is above 0.  With enable=0 it is draw_rough's frame on bits.  One
         launch on `stream`; never waits."""
-        cam, sp, pp = self._path_call_args(width, height, camera, frame, paths, max_depth, rr_depth, ambient, shadow_secondary, seed, noise,
-                                           fireflies, pixel_length)
-        vp, rp, hp = SvgfVirtualParams(int(max_chain), int(id_offset)), SvgfRoughParams(float(guide_alpha)), SvgfHighlightParams(int(enable), float(clamp))
-        planar = isinstance(out_gbuffer, SvgfPlanarGBuffer)
-        rc = load_highlight_library().svgf_highlight_draw(self.h, table.h if table is not None else None, _ptr(out_rgb),
-                                                          None if planar else _ptr(out_gbuffer), C.byref(out_gbuffer) if planar else None,
-                                                          int(width), int(height), C.byref(cam), C.byref(sp), C.byref(light), C.byref(pp),
-                                                          C.byref(vp), _ptr(out_chain), _stream(stream),
-                                                          rough.h if rough is not None else None, C.byref(rp), C.byref(hp))
-        if rc != SVGF_OK:
-            raise SvgfError(f"svgf_highlight_draw failed ({rc})")
+        self._companion_draw("highlight", (out_rgb,), out_gbuffer, width, height, camera, light, frame,
+                             (paths, max_depth, rr_depth, ambient, shadow_secondary), (seed, noise, fireflies, pixel_length), stream, table,
+                             (max_chain, id_offset, out_chain), (rough, guide_alpha), (enable, clamp))
 
     def draw_highlight_split(self, out_direct, out_indirect, out_gbuffer, width: int, height: int, camera, light, frame: int, table=None,
                              paths: int = 1, max_depth: int = 4, rr_depth: int = 2, ambient: float = 0.15, shadow_secondary: int = 1,
@@ -1548,18 +1385,9 @@ class Scene:
                              clamp: float = 0.0):
         """svgf_highlight_draw_split of libsvgf_highlight.so (row f23): draw_rough_split with draw_highlight's term; at the first hit
         it is part of the direct image.  One launch on `stream`; never waits."""
-        cam, sp, pp = self._path_call_args(width, height, camera, frame, paths, max_depth, rr_depth, ambient, shadow_secondary, seed, noise,
-                                           fireflies, pixel_length)
-        vp, rp, hp = SvgfVirtualParams(int(max_chain), int(id_offset)), SvgfRoughParams(float(guide_alpha)), SvgfHighlightParams(int(enable), float(clamp))
-        planar = isinstance(out_gbuffer, SvgfPlanarGBuffer)
-        rc = load_highlight_library().svgf_highlight_draw_split(self.h, table.h if table is not None else None, _ptr(out_direct),
-                                                                _ptr(out_indirect), _ptr(out_rgb), None if planar else _ptr(out_gbuffer),
-                                                                C.byref(out_gbuffer) if planar else None, int(width), int(height),
-                                                                C.byref(cam), C.byref(sp), C.byref(light), C.byref(pp), C.byref(vp),
-                                                                _ptr(out_chain), _stream(stream), rough.h if rough is not None else None,
-                                                                C.byref(rp), C.byref(hp))
-        if rc != SVGF_OK:
-            raise SvgfError(f"svgf_highlight_draw_split failed ({rc})")
+        self._companion_draw("highlight", (out_direct, out_indirect, out_rgb), out_gbuffer, width, height, camera, light, frame,
+                             (paths, max_depth, rr_depth, ambient, shadow_secondary), (seed, noise, fireflies, pixel_length), stream, table,
+                             (max_chain, id_offset, out_chain), (rough, guide_alpha), (enable, clamp))
 
     def view(self) -> dict:
         """svgf_scene_view (host only): the device index, the counts and the device pointers the draws read, as integers (0 = NULL)."""

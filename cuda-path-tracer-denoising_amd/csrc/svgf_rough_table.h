@@ -5,6 +5,7 @@
 #define SVGF_ROUGH_TABLE_H_
 
 #include "../../include/svgf_rough.h"
+#include "svgf_device_table.h"
 
 struct svgf_rough_table {
     int device, n;

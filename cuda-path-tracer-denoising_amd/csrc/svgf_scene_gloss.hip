@@ -16,7 +16,6 @@
 
 #include <cmath>
 #include <cstdint>
-#include <new>
 #include <type_traits>
 
 namespace {
@@ -39,46 +38,12 @@ extern "C" int svgf_gloss_version(void) { return (SVGF_VERSION_MAJOR << 16) | SV
 
 extern "C" int svgf_gloss_table_create(int device, const SvgfSurface *host, int n, svgf_gloss_table **out)
 {
-    if (!out) return SVGF_ERR_INVALID_ARG;
-    *out = nullptr;
-    if (n < 0 || n > SVGF_SCENE_MAX_POSED || (n > 0 && !host) || device < 0) return SVGF_ERR_INVALID_ARG;
-    for (int i = 0; i < n; i++)
-        if (!surface_ok(host[i])) return SVGF_ERR_INVALID_ARG;
-    SvgfDeviceGuard dev_guard(device);
-    if (!dev_guard.ok) {
-        (void)hipGetLastError();        // a device that does not exist must not fail the next launch's check
-        return SVGF_ERR_NO_DEVICE;
-    }
-    svgf_gloss_table *t = new (std::nothrow) svgf_gloss_table{ device, n, nullptr };
-    if (!t) return SVGF_ERR_OOM;
-    if (n > 0) {
-        if (hipMalloc(reinterpret_cast<void **>(&t->dev), (size_t)n * sizeof(SvgfSurface)) != hipSuccess) {
-            (void)hipGetLastError();
-            delete t;
-            return SVGF_ERR_OOM;
-        }
-        if (hipMemcpy(t->dev, host, (size_t)n * sizeof(SvgfSurface), hipMemcpyHostToDevice) != hipSuccess) {
-            (void)hipGetLastError();
-            (void)hipFree(t->dev);
-            delete t;
-            return SVGF_ERR_HIP;
-        }
-    }
-    *out = t;
-    return SVGF_OK;
+    return svgf_device_table_create(device, host, n, out, surface_ok);
 }
 
-extern "C" void svgf_gloss_table_destroy(svgf_gloss_table *t)
-{
-    if (!t) return;
-    if (t->dev) {
-        SvgfDeviceGuard dev_guard(t->device);
-        (void)hipFree(t->dev);
-    }
-    delete t;
-}
+extern "C" void svgf_gloss_table_destroy(svgf_gloss_table *t) { svgf_device_table_destroy(t); }
 
-extern "C" int svgf_gloss_table_size(const svgf_gloss_table *t) { return t ? t->n : SVGF_ERR_INVALID_ARG; }
+extern "C" int svgf_gloss_table_size(const svgf_gloss_table *t) { return svgf_device_table_size(t); }
 
 extern "C" int svgf_gloss_draw(const svgf_scene *scene, const svgf_gloss_table *table, void *out_rgb_dev, void *out_gbuffer_dev,
                                const SvgfPlanarGBuffer *planes, int width, int height, const SvgfCamera *cam, const SvgfSynthParams *sp,
@@ -87,12 +52,7 @@ extern "C" int svgf_gloss_draw(const svgf_scene *scene, const svgf_gloss_table *
     SceneGlossArgs t;
     int device = 0;
     const int rc = gloss_draw_args(t, device, scene, table, out_rgb_dev, out_gbuffer_dev, planes, width, height, cam, sp, light, pp);
-    if (rc != SVGF_OK) return rc;
-    SvgfDeviceGuard dev_guard(device);
-    if (!dev_guard.ok) return SVGF_ERR_NO_DEVICE;
-    const int n = width * height;
-    hipLaunchKernelGGL(k_scene_gloss<SceneGlossArgs>, dim3((n + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), t);
-    return hipGetLastError() == hipSuccess ? SVGF_OK : SVGF_ERR_HIP;
+    return gloss_launch(rc, t, device, width, height, stream);
 }
 
 extern "C" int svgf_gloss_draw_split(const svgf_scene *scene, const svgf_gloss_table *table, void *out_direct_dev, void *out_indirect_dev,
@@ -104,10 +64,5 @@ extern "C" int svgf_gloss_draw_split(const svgf_scene *scene, const svgf_gloss_t
     int device = 0;
     const int rc = gloss_draw_split_args(s, device, scene, table, out_direct_dev, out_indirect_dev, out_rgb_dev, out_gbuffer_dev, planes, width,
                                          height, cam, sp, light, pp);
-    if (rc != SVGF_OK) return rc;
-    SvgfDeviceGuard dev_guard(device);
-    if (!dev_guard.ok) return SVGF_ERR_NO_DEVICE;
-    const int n = width * height;
-    hipLaunchKernelGGL(k_scene_gloss<SceneGlossSplitArgs>, dim3((n + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), s);
-    return hipGetLastError() == hipSuccess ? SVGF_OK : SVGF_ERR_HIP;
+    return gloss_launch(rc, s, device, width, height, stream);
 }

@@ -498,30 +498,14 @@ __global__ __launch_bounds__(256) void k_scene_gloss(AllArgs all_args)
     }
 }
 
-// svgf_path_draw's refusals: trace_prepare's with pp in tp's place (paths is checked behind them), then the path parameters
-static inline int gloss_prepare(SceneTraceArgs &t, int &device, const svgf_scene *scene, void *out_rgb_dev, bool rgb_required, void *out_gbuffer_dev,
-                                const SvgfPlanarGBuffer *planes, int width, int height, const SvgfCamera *cam, const SvgfSynthParams *sp,
-                                const SvgfSceneLight *light, const SvgfPathParams *pp)
-{
-    SvgfTraceParams tp = { 0, 0.0f, 0 };
-    if (pp) { tp.ambient = pp->ambient; tp.shadow_secondary = pp->shadow_secondary; }
-    return trace_prepare(t, device, scene, out_rgb_dev, rgb_required, out_gbuffer_dev, planes, width, height, cam, sp, light, pp ? &tp : nullptr);
-}
-
-static inline bool gloss_params_ok(const SvgfPathParams *pp)
-{
-    return pp->paths >= 0 && pp->paths <= SVGF_PATH_MAX_PATHS && pp->max_depth >= 1 && pp->max_depth <= SVGF_PATH_MAX_DEPTH &&
-           pp->rr_depth >= 0 && pp->rr_depth <= SVGF_PATH_MAX_DEPTH;
-}
-
 // Every refusal of svgf_gloss_draw that needs no device, in its order, and the kernel's arguments: what svgf_virtual_draw repeats first
 static inline int gloss_draw_args(SceneGlossArgs &t, int &device, const svgf_scene *scene, const svgf_gloss_table *table, void *out_rgb_dev,
                                   void *out_gbuffer_dev, const SvgfPlanarGBuffer *planes, int width, int height, const SvgfCamera *cam,
                                   const SvgfSynthParams *sp, const SvgfSceneLight *light, const SvgfPathParams *pp)
 {
-    const int rc = gloss_prepare(t.t, device, scene, out_rgb_dev, true, out_gbuffer_dev, planes, width, height, cam, sp, light, pp);
+    const int rc = path_prepare(t.t, device, scene, out_rgb_dev, true, out_gbuffer_dev, planes, width, height, cam, sp, light, pp);
     if (rc != SVGF_OK) return rc;
-    if (!gloss_params_ok(pp)) return SVGF_ERR_INVALID_ARG;
+    if (!path_params_ok(pp)) return SVGF_ERR_INVALID_ARG;
     if (table && table->device != device) return SVGF_ERR_INVALID_ARG;
     t.t.bounce_samples = pp->paths; t.max_depth = pp->max_depth; t.rr_depth = pp->rr_depth;
     t.table = table ? table->dev : nullptr; t.n_table = table ? table->n : 0;
@@ -534,13 +518,55 @@ static inline int gloss_draw_split_args(SceneGlossSplitArgs &s, int &device, con
                                         const SvgfPlanarGBuffer *planes, int width, int height, const SvgfCamera *cam, const SvgfSynthParams *sp,
                                         const SvgfSceneLight *light, const SvgfPathParams *pp)
 {
-    const int rc = gloss_prepare(s.s.t, device, scene, out_rgb_dev, false, out_gbuffer_dev, planes, width, height, cam, sp, light, pp);
+    const int rc = path_prepare(s.s.t, device, scene, out_rgb_dev, false, out_gbuffer_dev, planes, width, height, cam, sp, light, pp);
     if (rc != SVGF_OK) return rc;
     if (!out_direct_dev || !out_indirect_dev || out_direct_dev == out_indirect_dev) return SVGF_ERR_INVALID_ARG;
-    if (!gloss_params_ok(pp)) return SVGF_ERR_INVALID_ARG;
+    if (!path_params_ok(pp)) return SVGF_ERR_INVALID_ARG;
     if (table && table->device != device) return SVGF_ERR_INVALID_ARG;
     s.s.out_direct = static_cast<float *>(out_direct_dev); s.s.out_indirect = static_cast<float *>(out_indirect_dev);
     s.s.t.bounce_samples = pp->paths; s.max_depth = pp->max_depth; s.rr_depth = pp->rr_depth;
     s.table = table ? table->dev : nullptr; s.n_table = table ? table->n : 0;
     return SVGF_OK;
+}
+
+// What the draws behind svgf_gloss_draw add to its refusals, in their order - vp's, then rp's and the roughness table's device, then
+// hp's - each with the kernel arguments it fills; compiled where the includer knows the header that declares the parameters.
+#ifdef SVGF_VIRTUAL_H_
+static inline int guide_args(SceneGuide &v, const SvgfVirtualParams *vp, void *out_chain_dev)
+{
+    if (!vp || vp->max_chain < 1 || vp->max_chain > SVGF_PATH_MAX_DEPTH || vp->id_offset < 0 || vp->id_offset > (1 << 24)) return SVGF_ERR_INVALID_ARG;
+    v = SceneGuide{ vp->max_chain, vp->id_offset, static_cast<int *>(out_chain_dev) };
+    return SVGF_OK;
+}
+#endif
+
+#ifdef SVGF_ROUGH_TABLE_H_
+static inline int rough_args(SceneRough &r, const SvgfRoughParams *rp, const svgf_rough_table *rough, int device)
+{
+    if (!rp || !std::isfinite(rp->guide_alpha) || rp->guide_alpha < 0.0f) return SVGF_ERR_INVALID_ARG;
+    if (rough && rough->device != device) return SVGF_ERR_INVALID_ARG;
+    r = SceneRough{ rough ? rough->dev : nullptr, rough ? rough->n : 0, rp->guide_alpha };
+    return SVGF_OK;
+}
+#endif
+
+#ifdef SVGF_HIGHLIGHT_H_
+static inline int shine_args(SceneHighlight &h, const SvgfHighlightParams *hp)
+{
+    if (!hp || hp->enable < 0 || hp->enable > 1 || !std::isfinite(hp->clamp) || hp->clamp < 0.0f) return SVGF_ERR_INVALID_ARG;
+    h = SceneHighlight{ hp->enable, hp->clamp };
+    return SVGF_OK;
+}
+#endif
+
+// The end of every draw of this text: the refusals' answer `rc`, else the device guard and one launch of k_scene_gloss<Args> on `stream`
+template <class Args>
+static inline int gloss_launch(int rc, const Args &args, int device, int width, int height, void *stream)
+{
+    if (rc != SVGF_OK) return rc;
+    SvgfDeviceGuard dev_guard(device);
+    if (!dev_guard.ok) return SVGF_ERR_NO_DEVICE;
+    const int n = width * height;
+    hipLaunchKernelGGL(k_scene_gloss<Args>, dim3((n + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), args);
+    return hipGetLastError() == hipSuccess ? SVGF_OK : SVGF_ERR_HIP;
 }

@@ -28,24 +28,6 @@ namespace {
 
 #include "svgf_scene_gloss.inc.h"
 
-// what follows the gloss draw's refusals, in svgf_rough_draw's order: vp's, rp's and the roughness table's, then hp's
-bool highlight_params_ok(const SvgfVirtualParams *vp, const SvgfRoughParams *rp, const svgf_rough_table *rough, int device, const SvgfHighlightParams *hp)
-{
-    if (!vp || vp->max_chain < 1 || vp->max_chain > SVGF_PATH_MAX_DEPTH || vp->id_offset < 0 || vp->id_offset > (1 << 24)) return false;
-    if (!rp || !std::isfinite(rp->guide_alpha) || rp->guide_alpha < 0.0f) return false;
-    if (rough && rough->device != device) return false;
-    return hp && hp->enable >= 0 && hp->enable <= 1 && std::isfinite(hp->clamp) && hp->clamp >= 0.0f;
-}
-
-template <class Args>
-void highlight_fill(Args &t, const SvgfVirtualParams *vp, void *out_chain_dev, const svgf_rough_table *rough, const SvgfRoughParams *rp,
-                    const SvgfHighlightParams *hp)
-{
-    t.r.v.v = SceneGuide{ vp->max_chain, vp->id_offset, static_cast<int *>(out_chain_dev) };
-    t.r.r = SceneRough{ rough ? rough->dev : nullptr, rough ? rough->n : 0, rp->guide_alpha };
-    t.h = SceneHighlight{ hp->enable, hp->clamp };
-}
-
 }  // namespace
 
 extern "C" int svgf_highlight_version(void) { return (SVGF_VERSION_MAJOR << 16) | SVGF_VERSION_MINOR; }
@@ -57,15 +39,11 @@ extern "C" int svgf_highlight_draw(const svgf_scene *scene, const svgf_gloss_tab
 {
     SceneHighlightArgs t;
     int device = 0;
-    const int rc = gloss_draw_args(t.r.v.g, device, scene, table, out_rgb_dev, out_gbuffer_dev, planes, width, height, cam, sp, light, pp);
-    if (rc != SVGF_OK) return rc;
-    if (!highlight_params_ok(vp, rp, rough, device, hp)) return SVGF_ERR_INVALID_ARG;
-    SvgfDeviceGuard dev_guard(device);
-    if (!dev_guard.ok) return SVGF_ERR_NO_DEVICE;
-    highlight_fill(t, vp, out_chain_dev, rough, rp, hp);
-    const int n = width * height;
-    hipLaunchKernelGGL(k_scene_gloss<SceneHighlightArgs>, dim3((n + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), t);
-    return hipGetLastError() == hipSuccess ? SVGF_OK : SVGF_ERR_HIP;
+    int rc = gloss_draw_args(t.r.v.g, device, scene, table, out_rgb_dev, out_gbuffer_dev, planes, width, height, cam, sp, light, pp);
+    if (rc == SVGF_OK) rc = guide_args(t.r.v.v, vp, out_chain_dev);
+    if (rc == SVGF_OK) rc = rough_args(t.r.r, rp, rough, device);
+    if (rc == SVGF_OK) rc = shine_args(t.h, hp);
+    return gloss_launch(rc, t, device, width, height, stream);
 }
 
 extern "C" int svgf_highlight_draw_split(const svgf_scene *scene, const svgf_gloss_table *table, void *out_direct_dev, void *out_indirect_dev,
@@ -76,14 +54,10 @@ extern "C" int svgf_highlight_draw_split(const svgf_scene *scene, const svgf_glo
 {
     SceneHighlightSplitArgs s;
     int device = 0;
-    const int rc = gloss_draw_split_args(s.r.v.g, device, scene, table, out_direct_dev, out_indirect_dev, out_rgb_dev, out_gbuffer_dev, planes,
-                                         width, height, cam, sp, light, pp);
-    if (rc != SVGF_OK) return rc;
-    if (!highlight_params_ok(vp, rp, rough, device, hp)) return SVGF_ERR_INVALID_ARG;
-    SvgfDeviceGuard dev_guard(device);
-    if (!dev_guard.ok) return SVGF_ERR_NO_DEVICE;
-    highlight_fill(s, vp, out_chain_dev, rough, rp, hp);
-    const int n = width * height;
-    hipLaunchKernelGGL(k_scene_gloss<SceneHighlightSplitArgs>, dim3((n + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), s);
-    return hipGetLastError() == hipSuccess ? SVGF_OK : SVGF_ERR_HIP;
+    int rc = gloss_draw_split_args(s.r.v.g, device, scene, table, out_direct_dev, out_indirect_dev, out_rgb_dev, out_gbuffer_dev, planes,
+                                   width, height, cam, sp, light, pp);
+    if (rc == SVGF_OK) rc = guide_args(s.r.v.v, vp, out_chain_dev);
+    if (rc == SVGF_OK) rc = rough_args(s.r.r, rp, rough, device);
+    if (rc == SVGF_OK) rc = shine_args(s.h, hp);
+    return gloss_launch(rc, s, device, width, height, stream);
 }

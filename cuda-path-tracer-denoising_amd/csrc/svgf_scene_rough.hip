@@ -19,7 +19,6 @@
 
 #include <cmath>
 #include <cstdint>
-#include <new>
 #include <type_traits>
 
 namespace {
@@ -28,22 +27,7 @@ namespace {
 
 #include "svgf_scene_gloss.inc.h"
 
-bool virtual_params_ok(const SvgfVirtualParams *vp)
-{
-    return vp && vp->max_chain >= 1 && vp->max_chain <= SVGF_PATH_MAX_DEPTH && vp->id_offset >= 0 && vp->id_offset <= (1 << 24);
-}
-
-// what follows the virtual draw's refusals: rp's and the roughness table's
-bool rough_params_ok(const SvgfRoughParams *rp, const svgf_rough_table *rough, int device)
-{
-    if (!rp || !std::isfinite(rp->guide_alpha) || rp->guide_alpha < 0.0f) return false;
-    return !rough || rough->device == device;
-}
-
-SceneRough rough_of(const svgf_rough_table *rough, const SvgfRoughParams *rp)
-{
-    return SceneRough{ rough ? rough->dev : nullptr, rough ? rough->n : 0, rp->guide_alpha };
-}
+bool alpha_ok(const float &alpha) { return std::isfinite(alpha) && alpha >= 0.0f && alpha <= 1.0f; }
 
 }  // namespace
 
@@ -51,46 +35,12 @@ extern "C" int svgf_rough_version(void) { return (SVGF_VERSION_MAJOR << 16) | SV
 
 extern "C" int svgf_rough_table_create(int device, const float *alpha_host, int n, svgf_rough_table **out)
 {
-    if (!out) return SVGF_ERR_INVALID_ARG;
-    *out = nullptr;
-    if (n < 0 || n > SVGF_SCENE_MAX_POSED || (n > 0 && !alpha_host) || device < 0) return SVGF_ERR_INVALID_ARG;
-    for (int i = 0; i < n; i++)
-        if (!std::isfinite(alpha_host[i]) || alpha_host[i] < 0.0f || alpha_host[i] > 1.0f) return SVGF_ERR_INVALID_ARG;
-    SvgfDeviceGuard dev_guard(device);
-    if (!dev_guard.ok) {
-        (void)hipGetLastError();        // a device that does not exist must not fail the next launch's check
-        return SVGF_ERR_NO_DEVICE;
-    }
-    svgf_rough_table *t = new (std::nothrow) svgf_rough_table{ device, n, nullptr };
-    if (!t) return SVGF_ERR_OOM;
-    if (n > 0) {
-        if (hipMalloc(reinterpret_cast<void **>(&t->dev), (size_t)n * sizeof(float)) != hipSuccess) {
-            (void)hipGetLastError();
-            delete t;
-            return SVGF_ERR_OOM;
-        }
-        if (hipMemcpy(t->dev, alpha_host, (size_t)n * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
-            (void)hipGetLastError();
-            (void)hipFree(t->dev);
-            delete t;
-            return SVGF_ERR_HIP;
-        }
-    }
-    *out = t;
-    return SVGF_OK;
+    return svgf_device_table_create(device, alpha_host, n, out, alpha_ok);
 }
 
-extern "C" void svgf_rough_table_destroy(svgf_rough_table *t)
-{
-    if (!t) return;
-    if (t->dev) {
-        SvgfDeviceGuard dev_guard(t->device);
-        (void)hipFree(t->dev);
-    }
-    delete t;
-}
+extern "C" void svgf_rough_table_destroy(svgf_rough_table *t) { svgf_device_table_destroy(t); }
 
-extern "C" int svgf_rough_table_size(const svgf_rough_table *t) { return t ? t->n : SVGF_ERR_INVALID_ARG; }
+extern "C" int svgf_rough_table_size(const svgf_rough_table *t) { return svgf_device_table_size(t); }
 
 extern "C" int svgf_rough_draw(const svgf_scene *scene, const svgf_gloss_table *table, void *out_rgb_dev, void *out_gbuffer_dev,
                                const SvgfPlanarGBuffer *planes, int width, int height, const SvgfCamera *cam, const SvgfSynthParams *sp,
@@ -99,17 +49,10 @@ extern "C" int svgf_rough_draw(const svgf_scene *scene, const svgf_gloss_table *
 {
     SceneRoughArgs t;
     int device = 0;
-    const int rc = gloss_draw_args(t.v.g, device, scene, table, out_rgb_dev, out_gbuffer_dev, planes, width, height, cam, sp, light, pp);
-    if (rc != SVGF_OK) return rc;
-    if (!virtual_params_ok(vp)) return SVGF_ERR_INVALID_ARG;
-    if (!rough_params_ok(rp, rough, device)) return SVGF_ERR_INVALID_ARG;
-    SvgfDeviceGuard dev_guard(device);
-    if (!dev_guard.ok) return SVGF_ERR_NO_DEVICE;
-    t.v.v = SceneGuide{ vp->max_chain, vp->id_offset, static_cast<int *>(out_chain_dev) };
-    t.r = rough_of(rough, rp);
-    const int n = width * height;
-    hipLaunchKernelGGL(k_scene_gloss<SceneRoughArgs>, dim3((n + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), t);
-    return hipGetLastError() == hipSuccess ? SVGF_OK : SVGF_ERR_HIP;
+    int rc = gloss_draw_args(t.v.g, device, scene, table, out_rgb_dev, out_gbuffer_dev, planes, width, height, cam, sp, light, pp);
+    if (rc == SVGF_OK) rc = guide_args(t.v.v, vp, out_chain_dev);
+    if (rc == SVGF_OK) rc = rough_args(t.r, rp, rough, device);
+    return gloss_launch(rc, t, device, width, height, stream);
 }
 
 extern "C" int svgf_rough_draw_split(const svgf_scene *scene, const svgf_gloss_table *table, void *out_direct_dev, void *out_indirect_dev,
@@ -120,16 +63,9 @@ extern "C" int svgf_rough_draw_split(const svgf_scene *scene, const svgf_gloss_t
 {
     SceneRoughSplitArgs s;
     int device = 0;
-    const int rc = gloss_draw_split_args(s.v.g, device, scene, table, out_direct_dev, out_indirect_dev, out_rgb_dev, out_gbuffer_dev, planes,
-                                         width, height, cam, sp, light, pp);
-    if (rc != SVGF_OK) return rc;
-    if (!virtual_params_ok(vp)) return SVGF_ERR_INVALID_ARG;
-    if (!rough_params_ok(rp, rough, device)) return SVGF_ERR_INVALID_ARG;
-    SvgfDeviceGuard dev_guard(device);
-    if (!dev_guard.ok) return SVGF_ERR_NO_DEVICE;
-    s.v.v = SceneGuide{ vp->max_chain, vp->id_offset, static_cast<int *>(out_chain_dev) };
-    s.r = rough_of(rough, rp);
-    const int n = width * height;
-    hipLaunchKernelGGL(k_scene_gloss<SceneRoughSplitArgs>, dim3((n + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), s);
-    return hipGetLastError() == hipSuccess ? SVGF_OK : SVGF_ERR_HIP;
+    int rc = gloss_draw_split_args(s.v.g, device, scene, table, out_direct_dev, out_indirect_dev, out_rgb_dev, out_gbuffer_dev, planes,
+                                   width, height, cam, sp, light, pp);
+    if (rc == SVGF_OK) rc = guide_args(s.v.v, vp, out_chain_dev);
+    if (rc == SVGF_OK) rc = rough_args(s.r, rp, rough, device);
+    return gloss_launch(rc, s, device, width, height, stream);
 }

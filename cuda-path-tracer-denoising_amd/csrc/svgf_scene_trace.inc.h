@@ -229,3 +229,22 @@ static inline int trace_prepare(SceneTraceArgs &t, int &device, const svgf_scene
     t.bounce_samples = tp->bounce_samples; t.ambient = tp->ambient; t.shadow_secondary = tp->shadow_secondary;
     return SVGF_OK;
 }
+
+// The path family's (svgf_path_draw and the draws of svgf_scene_gloss.inc.h): trace_prepare's refusals with pp in tp's place (paths is
+// checked behind them, so a bounce count it would accept goes in), then the path parameters'.  Compiled where the includer knows svgf_path.h.
+#ifdef SVGF_PATH_H_
+static inline int path_prepare(SceneTraceArgs &t, int &device, const svgf_scene *scene, void *out_rgb_dev, bool rgb_required, void *out_gbuffer_dev,
+                               const SvgfPlanarGBuffer *planes, int width, int height, const SvgfCamera *cam, const SvgfSynthParams *sp,
+                               const SvgfSceneLight *light, const SvgfPathParams *pp)
+{
+    SvgfTraceParams tp = { 0, 0.0f, 0 };
+    if (pp) { tp.ambient = pp->ambient; tp.shadow_secondary = pp->shadow_secondary; }
+    return trace_prepare(t, device, scene, out_rgb_dev, rgb_required, out_gbuffer_dev, planes, width, height, cam, sp, light, pp ? &tp : nullptr);
+}
+
+static inline bool path_params_ok(const SvgfPathParams *pp)
+{
+    return pp->paths >= 0 && pp->paths <= SVGF_PATH_MAX_PATHS && pp->max_depth >= 1 && pp->max_depth <= SVGF_PATH_MAX_DEPTH &&
+           pp->rr_depth >= 0 && pp->rr_depth <= SVGF_PATH_MAX_DEPTH;
+}
+#endif

@@ -25,16 +25,6 @@ namespace {
 
 #include "svgf_scene_gloss.inc.h"
 
-bool virtual_params_ok(const SvgfVirtualParams *vp)
-{
-    return vp && vp->max_chain >= 1 && vp->max_chain <= SVGF_PATH_MAX_DEPTH && vp->id_offset >= 0 && vp->id_offset <= (1 << 24);
-}
-
-SceneGuide guide_of(const SvgfVirtualParams *vp, void *out_chain_dev)
-{
-    return SceneGuide{ vp->max_chain, vp->id_offset, static_cast<int *>(out_chain_dev) };
-}
-
 }  // namespace
 
 extern "C" int svgf_virtual_version(void) { return (SVGF_VERSION_MAJOR << 16) | SVGF_VERSION_MINOR; }
@@ -46,15 +36,9 @@ extern "C" int svgf_virtual_draw(const svgf_scene *scene, const svgf_gloss_table
 {
     SceneVirtualArgs t;
     int device = 0;
-    const int rc = gloss_draw_args(t.g, device, scene, table, out_rgb_dev, out_gbuffer_dev, planes, width, height, cam, sp, light, pp);
-    if (rc != SVGF_OK) return rc;
-    if (!virtual_params_ok(vp)) return SVGF_ERR_INVALID_ARG;
-    SvgfDeviceGuard dev_guard(device);
-    if (!dev_guard.ok) return SVGF_ERR_NO_DEVICE;
-    t.v = guide_of(vp, out_chain_dev);
-    const int n = width * height;
-    hipLaunchKernelGGL(k_scene_gloss<SceneVirtualArgs>, dim3((n + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), t);
-    return hipGetLastError() == hipSuccess ? SVGF_OK : SVGF_ERR_HIP;
+    int rc = gloss_draw_args(t.g, device, scene, table, out_rgb_dev, out_gbuffer_dev, planes, width, height, cam, sp, light, pp);
+    if (rc == SVGF_OK) rc = guide_args(t.v, vp, out_chain_dev);
+    return gloss_launch(rc, t, device, width, height, stream);
 }
 
 extern "C" int svgf_virtual_draw_split(const svgf_scene *scene, const svgf_gloss_table *table, void *out_direct_dev, void *out_indirect_dev,
@@ -64,14 +48,8 @@ extern "C" int svgf_virtual_draw_split(const svgf_scene *scene, const svgf_gloss
 {
     SceneVirtualSplitArgs s;
     int device = 0;
-    const int rc = gloss_draw_split_args(s.g, device, scene, table, out_direct_dev, out_indirect_dev, out_rgb_dev, out_gbuffer_dev, planes,
-                                         width, height, cam, sp, light, pp);
-    if (rc != SVGF_OK) return rc;
-    if (!virtual_params_ok(vp)) return SVGF_ERR_INVALID_ARG;
-    SvgfDeviceGuard dev_guard(device);
-    if (!dev_guard.ok) return SVGF_ERR_NO_DEVICE;
-    s.v = guide_of(vp, out_chain_dev);
-    const int n = width * height;
-    hipLaunchKernelGGL(k_scene_gloss<SceneVirtualSplitArgs>, dim3((n + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), s);
-    return hipGetLastError() == hipSuccess ? SVGF_OK : SVGF_ERR_HIP;
+    int rc = gloss_draw_split_args(s.g, device, scene, table, out_direct_dev, out_indirect_dev, out_rgb_dev, out_gbuffer_dev, planes,
+                                   width, height, cam, sp, light, pp);
+    if (rc == SVGF_OK) rc = guide_args(s.v, vp, out_chain_dev);
+    return gloss_launch(rc, s, device, width, height, stream);
 }

@@ -84,7 +84,10 @@ extern "C" int svgf_trace_compose(int device, void *out_rgb_dev, const void *dir
         return SVGF_ERR_INVALID_ARG;
     if ((long long)width * height >= (1LL << 31) / 16) return SVGF_ERR_UNSUPPORTED;
     SvgfDeviceGuard dev_guard(device);
-    if (!dev_guard.ok) return SVGF_ERR_NO_DEVICE;
+    if (!dev_guard.ok) {
+        (void)hipGetLastError();        // a device that does not exist must not fail the next launch's check
+        return SVGF_ERR_NO_DEVICE;
+    }
     const bool aos = guide->gbuffer != nullptr;
     ComposeArgs q;
     q.out = static_cast<float *>(out_rgb_dev);
