@@ -26,16 +26,15 @@ import numpy as np
 import pytest
 
 import resident_scene_model as rm
+import scene_harness as sh
 import scene_model as sm
 import scene_pose_model as pm
-import test_resident_scene as trs
 import test_scene_model as tsm
 from conftest import ROOT
 from test_scene_model import FRAME, SEED, cap, counts
 
 F = np.float32
 CAP = 1024
-BUILDS = trs.BUILDS
 POSES = ("identity", "translate", "turn9", "skew170")
 SET_NAMES = ("one", "copies300", "zero_area257", "huge_over_500", "line4096")
 STATE_INPUTS = ("A", "room", "bunny") + SET_NAMES
@@ -57,10 +56,10 @@ def same_bits(a, b):
 def _input(name):
     """(scene dict, W, H, n_objects).  Triangle sets get ids i % 3, one id of -1 and one beyond the table, under scene A's camera."""
     if name in ("room", "bunny"):
-        s, W, H = trs._recorded(name, 0)
+        s, W, H = sh.recorded(name, 0)
         return s, W, H, min(int(np.max(s["tri_ids"])) + 1, 1024)
     if name in SET_NAMES:
-        tris = trs._tri_set(name)
+        tris = sh.tri_set(name)
         n = len(tris)
         ids = (np.arange(n) % 3).astype(np.int32)
         if n >= 3:
@@ -171,11 +170,11 @@ def _subtree(nodes, k):
     return out
 
 
-@pytest.mark.parametrize("name", [n for n in trs.TRI_SETS if n != "none"])
+@pytest.mark.parametrize("name", [n for n in sh.TRI_SETS if n != "none"])
 def test_plan_invariants_on_builder_trees(pkg, name):
-    tris = trs._tri_set(name)
+    tris = sh.tri_set(name)
     lo, hi = rm.padded_boxes(tris)
-    for ml, sp in BUILDS:
+    for ml, sp in sh.BUILDS:
         nodes, order, _ = pkg.bvh_build_host(tris, ml, sp)
         for cap_ in (CAP, 16) if len(nodes) < 3000 else (CAP,):
             plan = _check_plan(pkg, nodes, order, cap_, lo, hi, f"{name} leaf {ml} split {sp} cap {cap_}")
@@ -294,16 +293,6 @@ def test_refit_plan_native_program_under_sanitizers(tmp_path):
 
 
 # ---- GPU helpers -------------------------------------------------------------------------------------------------------------------------
-def _dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).cuda()
-
-
-def _motion_buffer(n):
-    import torch
-    return torch.full((n, 12), float("nan"), dtype=torch.float32, device="cuda")
-
-
 def _assert_state(pkg, scene, s, table, nodes, order, what, kinds=(0, 1, 2, 3, 5)):
     m = pm.state(s, table, nodes, order)
     n = len(m["tris"])
@@ -326,65 +315,19 @@ def _assert_state(pkg, scene, s, table, nodes, order, what, kinds=(0, 1, 2, 3, 5
         assert same_bits(h["xf"], table["xf"]) and same_bits(h["inv"], table["inv"]), f"{what}: held table"
 
 
-def _graph_api():
-    from temporal_harness import _hip
-    hip = _hip()
-    vp = ctypes.c_void_p
-    hip.hipStreamBeginCapture.argtypes = [vp, ctypes.c_int]
-    hip.hipStreamEndCapture.argtypes = [vp, ctypes.POINTER(vp)]
-    hip.hipGraphInstantiate.argtypes = [ctypes.POINTER(vp), vp, vp, vp, ctypes.c_size_t]
-    hip.hipGraphLaunch.argtypes = [vp, vp]
-    hip.hipGraphExecDestroy.argtypes = [vp]
-    hip.hipGraphDestroy.argtypes = [vp]
-    hip.hipGraphGetNodes.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_size_t)]
-    hip.hipGraphNodeGetType.argtypes = [vp, ctypes.POINTER(ctypes.c_int)]
-    return hip
-
-
-def _node_types(hip, graph):
-    n = ctypes.c_size_t(0)
-    assert hip.hipGraphGetNodes(graph, None, ctypes.byref(n)) == 0
-    arr = (ctypes.c_void_p * max(n.value, 1))()
-    assert hip.hipGraphGetNodes(graph, arr, ctypes.byref(n)) == 0
-    types = []
-    for k in range(n.value):
-        t = ctypes.c_int(-1)
-        assert hip.hipGraphNodeGetType(arr[k], ctypes.byref(t)) == 0
-        types.append(t.value)
-    return types        # hipGraphNodeTypeKernel 0, Memcpy 1, Memset 2
-
-
-def _draw_planar(pkg, scene, den, W, H, s, frame, seed):
-    import torch
-    from temporal_harness import _hip
-    planes = den.planar_gbuffer()
-    rgb = torch.empty((H, W, 3), dtype=torch.float32, device="cuda")
-    scene.draw_planar(rgb, planes, W, H, s["cam"], s["light"], frame, seed=seed)
-    torch.cuda.synchronize()
-    hip = _hip()
-    hip.hipMemcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
-    gb = np.zeros((H, W), dtype=pkg.synth.GBUFFER_DTYPE)
-    for field, ptr in (("normal", planes.normal), ("position", planes.position), ("albedo", planes.albedo), ("geomId", planes.geom_id)):
-        host = np.zeros((H, W, 3) if field != "geomId" else (H, W), F if field != "geomId" else np.int32)
-        assert hip.hipMemcpy(host.ctypes.data, ptr, host.nbytes, 2) == 0
-        gb[field] = host
-    gb["ialbedo"] = F(1.0)
-    return rgb.cpu().numpy(), gb
-
-
 # ---- GPU 6: state on bits ----------------------------------------------------------------------------------------------------------------
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", STATE_INPUTS)
 def test_state_after_a_pose_equals_the_model_on_bits(pkg, name):
     s, W, H, n_obj = _input(name)
-    for ml, sp in BUILDS:
+    for ml, sp in sh.BUILDS:
         nodes, order, _ = pkg.bvh_build_host(s["tris"], ml, sp)
-        scene = trs._create(pkg, s, ml, sp)
+        scene = sh.create(pkg, s, ml, sp)
         scene.enable_pose(n_obj)
         assert np.array_equal(scene.read(4), order), "order"
         for pose in POSES:
             table = _table(name, pose)
-            scene.pose(_dev(table))
+            scene.pose(sh.dev(table))
             _assert_state(pkg, scene, s, table, nodes, order, f"{name} leaf {ml} split {sp} {pose}")
         assert np.array_equal(scene.read(4), order), "order after the poses"
         scene.free()
@@ -401,18 +344,18 @@ def test_state_after_a_pose_equals_the_model_on_bits(pkg, name):
 def test_posed_frame_equals_model_and_mesh_path(pkg, name, pose):
     s, W, H, n_obj = _input(name)
     ps = _posed(name, pose)
-    scene = trs._create(pkg, s)
+    scene = sh.create(pkg, s)
     scene.enable_pose(n_obj)
-    scene.pose(_dev(_table(name, pose)))
-    got = trs._draw(pkg, scene, W, H, s, FRAME, SEED)
+    scene.pose(sh.dev(_table(name, pose)))
+    got = sh.draw_frame(pkg, scene, W, H, s, FRAME, SEED)
     den = pkg.Denoiser(W, H, 0)
-    planar = _draw_planar(pkg, scene, den, W, H, s, FRAME, SEED)
+    planar = sh.pair(sh.draw(pkg, sh.RESIDENT, scene, W, H, s, None, planes=den.planar_gbuffer()))
     den.free(); scene.free()
     mesh = tsm._device(pkg, W, H, ps, FRAME, SEED)
-    trs._same(got, mesh, W, H, f"{name} {pose}: draw vs svgf_scene_render_mesh on the model's arrays")
-    trs._same(planar, got, W, H, f"{name} {pose}: draw_planar vs draw")
+    sh.same_capped(got, mesh, W, H, f"{name} {pose}: draw vs svgf_scene_render_mesh on the model's arrays")
+    sh.same_capped(planar, got, W, H, f"{name} {pose}: draw_planar vs draw")
     if name != "bunny":
-        trs._same(got, _posed_model(name, pose, W, H), W, H, f"{name} {pose}: draw vs model")
+        sh.same_capped(got, _posed_model(name, pose, W, H), W, H, f"{name} {pose}: draw vs model")
     if pose in ("identity", "translate"):
         assert (got[1]["geomId"] >= 0).sum() > cap(W, H), "the frame shows nothing"
 
@@ -422,18 +365,18 @@ def test_posed_frame_equals_model_and_mesh_path(pkg, name, pose):
 def test_every_build_draws_the_same_posed_frame(pkg, name):
     s, W, H, n_obj = _input(name)
     frames = {}
-    for ml, sp in BUILDS:
-        scene = trs._create(pkg, s, ml, sp)
+    for ml, sp in sh.BUILDS:
+        scene = sh.create(pkg, s, ml, sp)
         scene.enable_pose(n_obj)
         for pose in POSES:
-            scene.pose(_dev(_table(name, pose)))
-            frames[(ml, sp, pose)] = trs._draw(pkg, scene, W, H, s, FRAME, SEED)
+            scene.pose(sh.dev(_table(name, pose)))
+            frames[(ml, sp, pose)] = sh.draw_frame(pkg, scene, W, H, s, FRAME, SEED)
         scene.free()
     for pose in POSES:
-        for ml, sp in BUILDS[1:]:
-            c = counts(frames[(ml, sp, pose)], frames[BUILDS[0] + (pose,)])
+        for ml, sp in sh.BUILDS[1:]:
+            c = counts(frames[(ml, sp, pose)], frames[sh.BUILDS[0] + (pose,)])
             assert not any(c.values()), f"{pose}: leaf {ml} split {sp} differs from leaf 1 split 0: {c}"
-    assert any(counts(frames[BUILDS[0] + ("turn9",)], frames[BUILDS[0] + ("identity",)]).values()), "the pose should move the picture"
+    assert any(counts(frames[sh.BUILDS[0] + ("turn9",)], frames[sh.BUILDS[0] + ("identity",)]).values()), "the pose should move the picture"
 
 
 # ---- GPU 8: lifecycle ----------------------------------------------------------------------------------------------------------------------
@@ -444,11 +387,11 @@ def _all_state(scene):
 @pytest.mark.gpu
 def test_lifecycle(pkg):
     s, W, H, n_obj = _input("F_cube")
-    static = trs._create(pkg, s)
-    created = trs._draw(pkg, static, W, H, s, FRAME, SEED)
+    static = sh.create(pkg, s)
+    created = sh.draw_frame(pkg, static, W, H, s, FRAME, SEED)
     static_state = [static.read(k).tobytes() for k in (0, 1, 2, 3, 4)]
     info = static.info()
-    scene = trs._create(pkg, s)
+    scene = sh.create(pkg, s)
     assert scene.info() == info
     scene.enable_pose(n_obj)
     enabled = [scene.read(k).tobytes() for k in (0, 1, 2, 3, 4)]
@@ -457,23 +400,23 @@ def test_lifecycle(pkg):
     scene.enable_pose(n_obj)                                            # twice: a no-op
     assert [scene.read(k).tobytes() for k in (0, 1, 2, 3, 4)] == enabled
     assert scene.lib.svgf_scene_enable_pose(scene.h, n_obj + 1) == -1
-    assert not any(counts(trs._draw(pkg, scene, W, H, s, FRAME, SEED), created).values()), "enable_pose alone changes the frame"
-    a, b = _dev(_table("F_cube", "turn9")), _dev(_table("F_cube", "skew170"))
+    assert not any(counts(sh.draw_frame(pkg, scene, W, H, s, FRAME, SEED), created).values()), "enable_pose alone changes the frame"
+    a, b = sh.dev(_table("F_cube", "turn9")), sh.dev(_table("F_cube", "skew170"))
     scene.pose(a)
     once = _all_state(scene)
     scene.pose(a)
     assert _all_state(scene) == once, "the same table twice leaves other bytes"
     scene.pose(b)
-    fresh = trs._create(pkg, s)
+    fresh = sh.create(pkg, s)
     fresh.enable_pose(n_obj)
     fresh.pose(b)
     assert _all_state(scene) == _all_state(fresh), "pose A then B differs from a fresh scene posed B"
-    assert not any(counts(trs._draw(pkg, scene, W, H, s, FRAME, SEED), trs._draw(pkg, fresh, W, H, s, FRAME, SEED)).values())
-    scene.pose(_dev(_table("F_cube", "identity")))
-    assert not any(counts(trs._draw(pkg, scene, W, H, s, FRAME, SEED), created).values()), "the identity pose does not restore the created frame"
+    assert not any(counts(sh.draw_frame(pkg, scene, W, H, s, FRAME, SEED), sh.draw_frame(pkg, fresh, W, H, s, FRAME, SEED)).values())
+    scene.pose(sh.dev(_table("F_cube", "identity")))
+    assert not any(counts(sh.draw_frame(pkg, scene, W, H, s, FRAME, SEED), created).values()), "the identity pose does not restore the created frame"
     # (the frame, not every byte of the state: the identity goes through the arithmetic, and (1 * -0 + 0 * y) + 0 * z is +0)
     assert [static.read(k).tobytes() for k in (0, 1, 2, 3, 4)] == static_state and static.info() == info, "the static scene moved"
-    assert not any(counts(trs._draw(pkg, static, W, H, s, FRAME, SEED), created).values())
+    assert not any(counts(sh.draw_frame(pkg, static, W, H, s, FRAME, SEED), created).values())
     for sc in (static, scene, fresh):
         sc.free()
 
@@ -484,13 +427,13 @@ def test_motion_table_rows(pkg):
     import torch
     B = pkg.binding
     s, W, H, n_obj = _input("A")
-    scene = trs._create(pkg, s)
+    scene = sh.create(pkg, s)
     scene.enable_pose(n_obj)
     held = B.pose_identity(n_obj)
-    out = _motion_buffer(n_obj + 1)                                     # one row more: the call must not write past n_objects
+    out = sh.motion_buffer(n_obj + 1)                                     # one row more: the call must not write past n_objects
     for f, pose in enumerate(("turn9", "skew170", "translate")):
         table = _table("A", pose)
-        scene.pose(_dev(table), out)
+        scene.pose(sh.dev(table), out)
         torch.cuda.synchronize()
         rows = out.cpu().numpy()
         want = pm.motion_rows(held, table)
@@ -501,7 +444,7 @@ def test_motion_table_rows(pkg):
         held = table
     out.fill_(float("nan"))
     last = _table("A", "turn9")
-    scene.pose(_dev(last), None)                                        # NULL: nothing written, held still follows
+    scene.pose(sh.dev(last), None)                                        # NULL: nothing written, held still follows
     torch.cuda.synchronize()
     assert np.isnan(out.cpu().numpy()).all()
     h = scene.read(5)
@@ -515,26 +458,26 @@ def test_eight_pose_and_draw_pairs_queued_without_host_waits(pkg):
     import torch
     s, W, H, n_obj = _input("A")
     seq = [POSES[f % 4] for f in range(8)]
-    tables = [_dev(_table("A", p)) for p in seq]
-    motions = [_motion_buffer(n_obj) for _ in seq]
-    scene = trs._create(pkg, s)
+    tables = [sh.dev(_table("A", p)) for p in seq]
+    motions = [sh.motion_buffer(n_obj) for _ in seq]
+    scene = sh.create(pkg, s)
     scene.enable_pose(n_obj)
     st = torch.cuda.Stream()
     torch.cuda.synchronize()
-    bufs = [trs._buffers(W, H) for _ in seq]
+    bufs = [sh.buffers(W, H) for _ in seq]
     for f, (rgb, gbt) in enumerate(bufs):
         scene.pose(tables[f], motions[f], stream=st)
         scene.draw(rgb, gbt, W, H, s["cam"], s["light"], f, seed=SEED, stream=st)
     st.synchronize()
-    queued = [(trs._host(pkg, rgb, gbt, W, H), m.cpu().numpy()) for (rgb, gbt), m in zip(bufs, motions)]
+    queued = [(sh.host(pkg, rgb, gbt, W, H), m.cpu().numpy()) for (rgb, gbt), m in zip(bufs, motions)]
     scene.free()
-    scene = trs._create(pkg, s)
+    scene = sh.create(pkg, s)
     scene.enable_pose(n_obj)
     for f, p in enumerate(seq):
-        m = _motion_buffer(n_obj)
+        m = sh.motion_buffer(n_obj)
         scene.pose(tables[f], m)
         torch.cuda.synchronize()
-        alone = trs._draw(pkg, scene, W, H, s, f, SEED)
+        alone = sh.draw_frame(pkg, scene, W, H, s, f, SEED)
         assert not any(counts(queued[f][0], alone).values()), f"frame {f}"
         assert same_bits(queued[f][1], m.cpu().numpy()), f"motion rows, frame {f}"
     scene.free()
@@ -543,36 +486,33 @@ def test_eight_pose_and_draw_pairs_queued_without_host_waits(pkg):
 @pytest.mark.gpu
 def test_a_captured_pose_and_draw_replays_with_the_table_of_the_moment(pkg):
     import torch
-    hip = _graph_api()
     s, W, H, n_obj = _input("A")
-    scene = trs._create(pkg, s)
+    scene = sh.create(pkg, s)
     scene.enable_pose(n_obj)
     st = torch.cuda.Stream()
     t1, t2 = _table("A", "turn9"), _table("A", "skew170")
-    table, motion = _dev(t1), _motion_buffer(n_obj)
-    rgb, gbt = trs._buffers(W, H)
+    table, motion = sh.dev(t1), sh.motion_buffer(n_obj)
+    rgb, gbt = sh.buffers(W, H)
     torch.cuda.synchronize()
-    scene.pose(table, motion, stream=st)                                # eager first: a first launch may set kernel attributes
-    scene.draw(rgb, gbt, W, H, s["cam"], s["light"], FRAME, seed=SEED, stream=st)
-    scene.pose(_dev(pkg.binding.pose_identity(n_obj)), None, stream=st)         # held back to the identity
+
+    def record():
+        scene.pose(table, motion, stream=st)
+        scene.draw(rgb, gbt, W, H, s["cam"], s["light"], FRAME, seed=SEED, stream=st)
+    record()                                                            # eager first: a first launch may set kernel attributes
+    scene.pose(sh.dev(pkg.binding.pose_identity(n_obj)), None, stream=st)         # held back to the identity
     st.synchronize()
-    graph, gexec = ctypes.c_void_p(), ctypes.c_void_p()
-    assert hip.hipStreamBeginCapture(st.cuda_stream, 2) == 0
-    scene.pose(table, motion, stream=st)
-    scene.draw(rgb, gbt, W, H, s["cam"], s["light"], FRAME, seed=SEED, stream=st)
-    assert hip.hipStreamEndCapture(st.cuda_stream, ctypes.byref(graph)) == 0 and graph.value
-    assert hip.hipGraphInstantiate(ctypes.byref(gexec), graph, None, None, 0) == 0
+    graph = sh.Captured(st, record)
     got = []
     for t in (t1, t2):
         with torch.cuda.stream(st):
-            table.copy_(_dev(t)); rgb.zero_(); gbt.zero_()
-        assert hip.hipGraphLaunch(gexec, st.cuda_stream) == 0
+            table.copy_(sh.dev(t)); rgb.zero_(); gbt.zero_()
+        graph.launch()
         st.synchronize()
-        got.append((trs._host(pkg, rgb, gbt, W, H), motion.cpu().numpy()))
-    hip.hipGraphExecDestroy(gexec); hip.hipGraphDestroy(graph)
+        got.append((sh.host(pkg, rgb, gbt, W, H), motion.cpu().numpy()))
+    graph.destroy()
     scene.free()
     for k, pose in enumerate(("turn9", "skew170")):
-        trs._same(got[k][0], _posed_model("A", pose, W, H), W, H, f"replay {k} vs model")
+        sh.same_capped(got[k][0], _posed_model("A", pose, W, H), W, H, f"replay {k} vs model")
     assert same_bits(got[0][1], pm.motion_rows(pkg.binding.pose_identity(n_obj), t1))
     assert same_bits(got[1][1], pm.motion_rows(t1, t2)), "the second replay's motion rows should use the first replay's pose"
 
@@ -581,21 +521,18 @@ def test_a_captured_pose_and_draw_replays_with_the_table_of_the_moment(pkg):
 @pytest.mark.parametrize("name,ml", [("line4096", 1), ("one", 4)])
 def test_a_captured_pose_is_at_most_three_kernel_nodes(pkg, name, ml):
     import torch
-    hip = _graph_api()
     s, W, H, n_obj = _input(name)
-    scene = trs._create(pkg, s, ml, 0)
+    scene = sh.create(pkg, s, ml, 0)
     scene.enable_pose(n_obj)
     st = torch.cuda.Stream()
-    table, motion = _dev(_table(name, "turn9")), _motion_buffer(n_obj)
+    table, motion = sh.dev(_table(name, "turn9")), sh.motion_buffer(n_obj)
     torch.cuda.synchronize()
-    scene.pose(table, motion, stream=st)
+    record = lambda: scene.pose(table, motion, stream=st)      # noqa: E731
+    record()
     st.synchronize()
-    graph = ctypes.c_void_p()
-    assert hip.hipStreamBeginCapture(st.cuda_stream, 2) == 0
-    scene.pose(table, motion, stream=st)
-    assert hip.hipStreamEndCapture(st.cuda_stream, ctypes.byref(graph)) == 0 and graph.value
-    types = _node_types(hip, graph)
-    hip.hipGraphDestroy(graph)
+    graph = sh.Captured(st, record)
+    types = graph.types
+    graph.destroy()
     scene.free()
     print(f"{name}: captured pose = node types {types}")
     assert 1 <= len(types) <= 3 and all(t == 0 for t in types), types
@@ -611,11 +548,11 @@ def test_non_finite_rows(pkg):
     table["xf"][0], table["inv"][0] = np.nan, np.nan
     table["xf"][1], table["inv"][1] = np.inf, np.inf
     nodes, order, _ = pkg.bvh_build_host(s["tris"], 4, 0)
-    scene = trs._create(pkg, s, 4, 0)
+    scene = sh.create(pkg, s, 4, 0)
     scene.enable_pose(n_obj)
-    scene.pose(_dev(table))
+    scene.pose(sh.dev(table))
     _assert_state(pkg, scene, s, table, nodes, order, "non-finite table", kinds=(0, 1, 2))
-    got = trs._draw(pkg, scene, W, H, s, FRAME, SEED)                   # completes
+    got = sh.draw_frame(pkg, scene, W, H, s, FRAME, SEED)                   # completes
     scene.free()
     ps = pm.posed_scene(s, table)
     ref = sm.render(W, H, FRAME, ps["cam"], ps["geoms"], ps["geom_ids"], ps["tris"], ps["tri_ids"], ps["tri_albedo"], None, None, ps["light"], seed=SEED)
@@ -627,33 +564,12 @@ def test_non_finite_rows(pkg):
 
 
 # ---- GPU 12: end to end - the turning, sliding block -----------------------------------------------------------------------------------------
-@functools.lru_cache(maxsize=None)
-def _block_inputs():
-    """box_room as a resident scene of primitives; six frames, the block 9 degrees further about y through its centre and 1.0
-    further in x per frame (test_object_motion.py's motion), as pose tables over the rest state."""
-    import __graft_entry__ as ge
-    from temporal_harness import BLOCK, SCENE
-    pkg = ge.load_package()
-    sc = pkg.scene.parse_scene(open(SCENE).read())
-    cam = pkg.scene.camera_for_frame(sc, 0, False)
-    geoms = pkg.scene.geom_array(sc)
-    centre = tuple(float(v) for v in sc.objects[BLOCK]["trans"])
-    tables = []
-    for f in range(6):
-        t = pkg.binding.pose_identity(len(geoms))
-        t[BLOCK] = pkg.binding.pose_rigid((0, 1, 0), np.deg2rad(9.0 * f), centre, (1.0 * f, 0, 0))
-        tables.append(t)
-    s = dict(cam=cam, geoms=geoms, geom_ids=None, tris=None, tri_ids=None, tri_albedo=None, tri_tex=None, textures=None,
-             light=pkg.scene.light_position(geoms))
-    return s, tables
-
-
 @pytest.mark.gpu
 def test_turning_block_end_to_end(pkg, orc):
     import torch
     import temporal_model as tm
     from temporal_harness import BLOCK, SIDE, assert_frames_equal, read_states, temporal_only
-    s, tables = _block_inputs()
+    s, tables = sh.block_inputs()
     W = H = SIDE
     n = len(s["geoms"])
     held, frames, motion = pkg.binding.pose_identity(n), [], []
@@ -668,19 +584,19 @@ def test_turning_block_end_to_end(pkg, orc):
     p = temporal_only(pkg)
     got = {}
     for with_table in (True, False):
-        scene = trs._create(pkg, s)
+        scene = sh.create(pkg, s)
         scene.enable_pose(n)
         den = pkg.Denoiser(W, H)
         den.set_capture(True)
-        t_x = _motion_buffer(n)
+        t_x = sh.motion_buffer(n)
         if with_table:
             den.set_object_motion(t_x)
-        rgb, gbt = trs._buffers(W, H)
+        rgb, gbt = sh.buffers(W, H)
         out = torch.empty((H, W, 3), dtype=torch.float32, device="cuda")
         got[with_table] = []
         try:
             for f, t in enumerate(tables):
-                scene.pose(_dev(t), t_x)
+                scene.pose(sh.dev(t), t_x)
                 scene.draw(rgb, gbt, W, H, s["cam"], s["light"], f, seed=3)
                 den.denoise(out, rgb, gbt, s["cam"], p)
                 torch.cuda.synchronize()
@@ -708,9 +624,9 @@ def test_turning_block_end_to_end(pkg, orc):
 def test_errors_leave_the_scene_drawing_the_previous_frame(pkg):
     import torch
     s, W, H, n_obj = _input("A")
-    scene = trs._create(pkg, s)
+    scene = sh.create(pkg, s)
     lib = scene.lib
-    table, motion = _dev(_table("A", "turn9")), _motion_buffer(n_obj + 1)
+    table, motion = sh.dev(_table("A", "turn9")), sh.motion_buffer(n_obj + 1)
     assert lib.svgf_scene_enable_pose(scene.h, 0) == -1 and lib.svgf_scene_enable_pose(scene.h, 1025) == -1 and lib.svgf_scene_enable_pose(scene.h, -3) == -1
     assert lib.svgf_scene_pose(scene.h, table.data_ptr(), n_obj, None, None) == -1, "a scene without svgf_scene_enable_pose"
     assert lib.svgf_scene_read(scene.h, 5, None, 0) == -1 and lib.svgf_scene_read(scene.h, 6, None, 0) == -1 and lib.svgf_scene_read(scene.h, -1, None, 0) == -1
@@ -719,8 +635,8 @@ def test_errors_leave_the_scene_drawing_the_previous_frame(pkg):
     assert lib.svgf_scene_read(scene.h, 0, host.ctypes.data, host.nbytes) == 0 and same_bits(host.reshape(-1, 3, 8), np.asarray(s["tris"], F))
     scene.enable_pose(n_obj)
     scene.pose(table, motion)
-    before, state = trs._draw(pkg, scene, W, H, s, FRAME, SEED), _all_state(scene)
-    other = _dev(_table("A", "skew170"))
+    before, state = sh.draw_frame(pkg, scene, W, H, s, FRAME, SEED), _all_state(scene)
+    other = sh.dev(_table("A", "skew170"))
     pad = torch.zeros(24 * n_obj + 4, dtype=torch.float32, device="cuda")
     for what, rc in (("NULL table", lib.svgf_scene_pose(scene.h, None, n_obj, None, None)),
                      ("NULL scene", lib.svgf_scene_pose(None, other.data_ptr(), n_obj, None, None)),
@@ -729,5 +645,5 @@ def test_errors_leave_the_scene_drawing_the_previous_frame(pkg):
                      ("a misaligned motion table", lib.svgf_scene_pose(scene.h, other.data_ptr(), n_obj, motion.data_ptr() + 8, None))):
         assert rc == -1, what
         assert _all_state(scene) == state, what
-        assert not any(counts(trs._draw(pkg, scene, W, H, s, FRAME, SEED), before).values()), what
+        assert not any(counts(sh.draw_frame(pkg, scene, W, H, s, FRAME, SEED), before).values()), what
     scene.free()

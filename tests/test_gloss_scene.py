@@ -11,155 +11,22 @@ the GPU case list, C8 every event of the model occurs at least 32 times over tha
 model.
 """
 import ctypes
-import functools
 import os
 import re
 import subprocess
-import tarfile
 
 import numpy as np
 import pytest
 
 import scene_gloss_model as gm
+import scene_harness as sh
 import scene_path_model as spm
-import scene_pose_model as pm
 import scene_shadow_model as ssm
 import scene_split_model as splm
-import test_animated_scene as tas
-import test_path_scene as tps
-import test_resident_scene as trs
-import test_scene_model as tsm
-import test_shadowed_scene as tss
-import test_split_scene as tsp
-import test_traced_scene as tts
 from conftest import ROOT
 from test_scene_model import FRAME, SEED, differing
 
 F = np.float32
-BUILDS = trs.BUILDS
-SIZES = tss.SIZES
-W0, H0 = 67, 41
-
-
-# ---- inputs ------------------------------------------------------------------------------------------------------------------------------
-def _room(pkg, *extra, block=True):
-    geoms, cam, lk = tss._example_scene()
-    geoms = geoms if block else geoms[:5]
-    if extra:
-        geoms = np.concatenate([geoms, tsm._geoms(pkg, *extra)])
-    s = dict(cam=cam, geoms=geoms, geom_ids=None, tris=None, tri_ids=None, tri_albedo=None, tri_tex=None, textures=None, light=lk["centre"])
-    return s, lk
-
-
-@functools.lru_cache(maxsize=None)
-def _glass_pair():
-    """The f16 room (its block taken out) with a glass sphere (id 5) and a glass cube turned 30 degrees about y (id 6), both of scale
-    3 and ior 1.5, with a spec that is not 1, so that the weight of a Fresnel reflection differs from a transmission's."""
-    import __graft_entry__ as ge
-    pkg = ge.load_package()
-    s, lk = _room(pkg, (1, (-2.2, 1.7, 0.0), (0, 0, 0), (3, 3, 3), (0.95, 0.95, 0.95), 0.0), (0, (2.2, 1.7, 0.0), (0, 30, 0), (3, 3, 3), (0.9, 0.95, 1.0), 0.0),
-                  block=False)
-    return s, lk, gm.table(7, g5=(0.0, 1.0, 1.5, (0.9, 0.8, 0.7)), g6=(0.0, 1.0, 1.5, (0.7, 0.8, 0.9)))
-
-
-@functools.lru_cache(maxsize=None)
-def _mirror_partial():
-    """The f16 room with its block: the floor (id 0) reflects with probability 0.5 and a red spec, the back wall (id 1) always."""
-    import __graft_entry__ as ge
-    s, lk = _room(ge.load_package())
-    return s, lk, gm.table(6, g0=(0.5, 0.0, 1.0, (0.9, 0.3, 0.3)), g1=(1.0, 0.0, 1.0, (0.9, 0.9, 0.9)))
-
-
-@functools.lru_cache(maxsize=None)
-def _mirror_mesh():
-    """f19's textured mesh over a floor primitive: every mesh id gets a mirror lobe of probability 0.6 and, as a scene file would give
-    it, a refract > 0 that the draw has to ignore on triangles; the floor is a full mirror, so that paths reach the mesh again."""
-    s, lk = tts._input("traced", "textured")
-    ids = sorted(set(np.asarray(s["tri_ids"]).tolist()))
-    floor = int(s["geom_ids"][-1]) if s["geom_ids"] is not None else len(s["geoms"]) - 1
-    n = max(ids + [floor]) + 1
-    entries = {f"g{i}": (0.6, 1.0, 1.5, (0.8, 0.9, 1.0)) for i in ids}
-    entries[f"g{floor}"] = (0.7, 0.0, 1.0, (0.9, 0.9, 0.9))
-    return s, lk, gm.table(n, **entries)
-
-
-@functools.lru_cache(maxsize=None)
-def _scene_text(name):
-    with tarfile.open(os.path.join(trs.REF_DIR, "scene_files.tar.gz")) as tar:
-        return tar.extractfile(name + ".txt").read().decode()
-
-
-@functools.lru_cache(maxsize=None)
-def _cornell():
-    """The recorded cornell with the table scene.surface_table makes of its own file."""
-    import __graft_entry__ as ge
-    pkg = ge.load_package()
-    s, lk = tts._input("rec", "cornell")
-    return s, lk, pkg.scene.surface_table(pkg.scene.parse_scene(_scene_text("cornell")))
-
-
-def _f19(kind, name):
-    s, lk = tps._input(kind, name)
-    return s, lk, None
-
-
-INPUTS = {"glass_pair": _glass_pair, "mirror_partial": _mirror_partial, "mirror_mesh": _mirror_mesh, "cornell": _cornell,
-          "F_cube": lambda: _f19("edge", "F_cube"), "stage": lambda: _f19("made", "stage"), "bleed_ceiling": lambda: _f19("path", "bleed_ceiling"),
-          "cornell_plain": lambda: _f19("rec", "cornell")}
-RECORDED = ("cornell", "cornell_plain")
-
-
-@functools.lru_cache(maxsize=None)
-def _first(name, W, H, frame, seed, noise=0.6):
-    import scene_model as sm
-    s = INPUTS[name]()[0]
-    first = sm.render(W, H, frame, *tss._args(s), s["light"], seed=seed, noise=noise, fireflies=0.02 if noise else 0.0)
-    em = ssm.emitter_mask(W, H, s["cam"], s["geoms"], s["geom_ids"], s["tris"], s["tri_ids"])
-    emit = splm.emittance_plane(W, H, s["cam"], s["geoms"], s["geom_ids"], s["tris"], s["tri_ids"])
-    for a in first + (em, emit):
-        a.setflags(write=False)
-    return first, em, emit
-
-
-def _table_of(name, table):
-    """table: "own" (the input's), "empty" (no records), "diffuse" (as many records as the input's, all diffuse), None."""
-    own = INPUTS[name]()[2]
-    if table == "own":
-        return own
-    if table == "diffuse":
-        return gm.table(16 if own is None else len(own))
-    return np.zeros(0, gm.SURFACE_DTYPE) if table == "empty" else None
-
-
-@functools.lru_cache(maxsize=None)
-def _model(name, W, H, J, K, R, sec=1, point=False, alt=None, frame=None, seed=None, table="own", keep_rays=False):
-    """dict(color, gb, D, I, info, lt, frame, seed, tab) of scene_gloss_model.render; a recorded scene at frame 0, seed 1 unless told."""
-    frame = (0 if name in RECORDED else FRAME) if frame is None else frame
-    seed = (1 if name in RECORDED else SEED) if seed is None else seed
-    s, lk, _ = INPUTS[name]()
-    tab = _table_of(name, table)
-    lt = ssm.light(lk["centre"], samples=1) if point else ssm.light(lk["centre"], lk["edge_u"], lk["edge_v"], 1)
-    first, em, emit = _first(name, W, H, frame, seed)
-    col, gb, D, I, info = gm.render(W, H, frame, *tss._args(s), lt, spm.params(J, K, R, 0.15, sec), tab, seed=seed, alt=alt, first=first,      # noqa: E741
-                                    emitters=em, emittance=emit, keep_rays=keep_rays)
-    for a in (col, D, I):
-        a.setflags(write=False)
-    return dict(color=col, gb=gb, D=D, I=I, info=info, lt=lt, frame=frame, seed=seed, tab=tab)
-
-
-# (name, W, H, paths, max_depth, rr_depth, shadow_secondary, point light): what G2 draws
-CASES = [("glass_pair", W0, H0, 4, 4, 2, 1, False), ("mirror_partial", W0, H0, 3, 3, 0, 1, True), ("mirror_mesh", W0, H0, 2, 3, 2, 1, False),
-         ("cornell", 96, 96, 1, 4, 2, 1, False), ("glass_pair", W0, H0, 4, 8, 1, 1, False)]
-QUEUED = ("glass_pair", W0, H0, 2, 3, 2, 1, False)
-
-
-def _case_model(case, **kw):
-    return _model(*case, **kw)
-
-
-def _what(case):
-    name, W, H, J, K, R, sec, point = case
-    return f"{name} {W}x{H}, {J} paths, max_depth {K}, rr_depth {R}, secondary shadow {sec}, {'point' if point else 'area'} light"
 
 
 def _events_row(info):
@@ -232,7 +99,7 @@ def test_gloss_argument_errors_without_a_device(pkg):
             assert call(ctypes.byref(B.SvgfSceneLight.make((0, 1, 0), samples=n)), P) == -1, n
         assert call(L, P, pl=ctypes.byref(planes)) == -1 and call(L, P, gb=None) == -1
         assert call(L, P, w=0) == -1 and call(L, P, h=-3) == -1
-        for bad in tps.BAD_PARAMS:
+        for bad in sh.BAD_PARAMS:
             assert call(L, ctypes.byref(B.SvgfPathParams(*bad))) == -1, bad
     assert plain(L, P, rgb=None) == -1
     assert split(L, P, d=None) == -1 and split(L, P, i=None) == -1 and split(L, P, d=5, i=5) == -1 and split(L, P, rgb=None) == -1
@@ -243,29 +110,29 @@ def test_gloss_argument_errors_without_a_device(pkg):
                                            ("cornell_plain", "rec", "cornell")])
 def test_an_empty_or_all_diffuse_table_is_the_path_model_on_bits(name, kind, f19):
     J, K, R = 3, 4, 1
-    ref = tps._model(kind, f19, W0, H0, J, K, R)
+    ref = sh.path_model(kind, f19, sh.W0, sh.H0, J, K, R)
     for table in (None, "empty", "diffuse"):
-        m = _model(name, W0, H0, J, K, R, table=table)
-        c = tsp._split_counts(m, ref)
+        m = sh.gloss_model(name, sh.W0, sh.H0, J, K, R, table=table)
+        c = sh.split_counts(m, ref)
         print(f"{name}, table {table}: differing pixels {c} (expected and allowed: 0)")
         assert not any(c.values()), (table, c)
         rows = [tuple(d[k] for k in spm.COUNTS[1:]) for d in m["info"]["depth"]]            # `alive` is counted ahead of the roulette here
-        assert rows == [r[1:] for r in tps._counts_row(ref["info"])], table
+        assert rows == [r[1:] for r in sh.counts_row(ref["info"])], table
     assert (ref["I"] > 0).any()
 
 
 def test_a_surface_that_no_ray_reaches_changes_no_bit():
     """Identity 2: glass_pair's table with records for ids the scene does not have (7 .. 15), and the table cut off behind the cube."""
-    case = CASES[0]
-    ref = _case_model(case)
-    s, lk, tab = _glass_pair()
+    case = sh.GLOSS_CASES[0]
+    ref = sh.gloss_model(*case)
+    s, lk, tab = sh.glass_pair()
     wide = gm.table(16, **{f"g{i}": (0.5, 1.0, 1.3, (0.5, 0.5, 0.5)) for i in range(7, 16)})
     wide[:7] = tab
     name, W, H, J, K, R, sec, point = case
-    first, em, emit = _first(name, W, H, ref["frame"], ref["seed"])
-    col, gb, D, I, _ = gm.render(W, H, ref["frame"], *tss._args(s), ref["lt"], spm.params(J, K, R, 0.15, sec), wide, seed=ref["seed"], first=first,     # noqa: E741
+    first, em, emit = sh.gloss_first(name, W, H, ref["frame"], ref["seed"])
+    col, gb, D, I, _ = gm.render(W, H, ref["frame"], *sh.args_of(s), ref["lt"], spm.params(J, K, R, 0.15, sec), wide, seed=ref["seed"], first=first,     # noqa: E741
                                  emitters=em, emittance=emit)
-    assert not any(tsp._split_counts(dict(color=col, gb=gb, D=D, I=I), ref).values())
+    assert not any(sh.split_counts(dict(color=col, gb=gb, D=D, I=I), ref).values())
 
 
 # ---- C4: the optics in float64 ---------------------------------------------------------------------------------------------------------
@@ -274,8 +141,8 @@ def _d64(v):
 
 
 def test_reflected_and_transmitted_directions_obey_the_laws():
-    m = _model("glass_pair", W0, H0, 4, 4, 2, keep_rays=True)
-    mp = _model("mirror_partial", W0, H0, 3, 3, 0, point=True, keep_rays=True)
+    m = sh.gloss_model("glass_pair", sh.W0, sh.H0, 4, 4, 2, keep_rays=True)
+    mp = sh.gloss_model("mirror_partial", sh.W0, sh.H0, 3, 3, 0, point=True, keep_rays=True)
     n_refl = n_trans = 0
     worst = dict(length=0.0, mirror=0.0, snell=0.0)
     for rays in m["info"]["rays"] + mp["info"]["rays"]:
@@ -302,13 +169,13 @@ def test_reflected_and_transmitted_directions_obey_the_laws():
 
 
 def test_ior_one_goes_straight_and_never_reflects():
-    s, lk, tab = _glass_pair()
+    s, lk, tab = sh.glass_pair()
     tab = np.array(tab, copy=True)
     tab["ior"][5:7] = F(1.0)
     tab["spec"][5:7] = F(0.0)
-    first, em, emit = _first("glass_pair", W0, H0, FRAME, SEED)
+    first, em, emit = sh.gloss_first("glass_pair", sh.W0, sh.H0, FRAME, SEED)
     lt = ssm.light(lk["centre"], lk["edge_u"], lk["edge_v"], 1)
-    info = gm.render(W0, H0, FRAME, *tss._args(s), lt, spm.params(4, 4, 0), tab, seed=SEED, first=first, emitters=em, emittance=emit, keep_rays=True)[4]
+    info = gm.render(sh.W0, sh.H0, FRAME, *sh.args_of(s), lt, spm.params(4, 4, 0), tab, seed=SEED, first=first, emitters=em, emittance=emit, keep_rays=True)[4]
     n = fresnel = 0
     for rays in info["rays"]:
         g = rays["glass"]
@@ -333,7 +200,7 @@ def test_surface_table_carries_the_files_numbers(pkg, name, mirror_objects, glas
     objects of cornell and of room; their glass material (REFR 1, REFRIOR 1.33; cornell's and bunny's number 5) by none, so an object
     is pointed at it here.  A REFRIOR that is not > 0 (the files' diffuse materials say 0) becomes 1."""
     import copy
-    sc = pkg.scene.parse_scene(_scene_text(name))
+    sc = pkg.scene.parse_scene(sh.scene_text(name))
     if glass_material is not None:
         sc = copy.deepcopy(sc)
         sc.objects[0]["material"] = glass_material
@@ -365,7 +232,7 @@ def test_the_moved_origin_finds_the_exit():
     shows the rule is needed.  Measured (rr_depth 2): factor 4: 0 of 1083 (0.00 %); origin not moved: 333 of 1072 (31.06 %)."""
     share = {}
     for alt in (None, "origin_not_moved"):
-        info = _model("glass_pair", W0, H0, 4, 4, 2, alt=alt)["info"]
+        info = sh.gloss_model("glass_pair", sh.W0, sh.H0, 4, 4, 2, alt=alt)["info"]
         enter, found = gm.total(info, "enter"), gm.total(info, "exit_found")
         share[alt] = (enter - found) / enter
         print(f"origin factor {float(gm.ORIGIN_FACTOR):g}, alt {alt}: {enter} enter events, {enter - found} without exit_found: {100 * share[alt]:.2f} %")
@@ -378,11 +245,11 @@ def test_the_moved_origin_finds_the_exit():
 def test_each_alt_acts_on_the_gpu_cases():
     for alt in gm.ALTS:
         acted = None
-        for case in CASES:
-            ref, m = _case_model(case), _case_model(case, alt=alt)
-            c = tsp._split_counts(m, ref)
+        for case in sh.GLOSS_CASES:
+            ref, m = sh.gloss_model(*case), sh.gloss_model(*case, alt=alt)
+            c = sh.split_counts(m, ref)
             if any(c.values()):
-                acted = (_what(case), c)
+                acted = (sh.gloss_what(case), c)
                 break
         print(f"`{alt}`: {acted}")
         assert acted is not None, f"`{alt}` changes no output of any GPU case"
@@ -391,9 +258,9 @@ def test_each_alt_acts_on_the_gpu_cases():
 def test_gpu_cases_cover_every_event():
     total = dict.fromkeys(gm.EVENTS, 0)
     deep_exit = tir_on_cube = tir_on_sphere = 0
-    for case in CASES:
-        info = _case_model(case)["info"]
-        print(f"{_what(case)}: {_events_row(info)}")
+    for case in sh.GLOSS_CASES:
+        info = sh.gloss_model(*case)["info"]
+        print(f"{sh.gloss_what(case)}: {_events_row(info)}")
         for e in gm.EVENTS:
             total[e] += gm.total(info, e)
         deep_exit += gm.total(info, "exit", 2)
@@ -403,7 +270,7 @@ def test_gpu_cases_cover_every_event():
     assert deep_exit >= 32
     # an exact sphere never reflects totally (the inner angle of incidence is the angle of refraction; here the moved origin and
     # rounding leave a stray grazing one): the count that matters is the cube's
-    m = _model("glass_pair", W0, H0, 4, 4, 2, keep_rays=True)
+    m = sh.gloss_model("glass_pair", sh.W0, sh.H0, 4, 4, 2, keep_rays=True)
     for rays in m["info"]["rays"]:
         tir_on_cube += int((rays["tir"] & (rays["gid"] == 6)).sum())
         tir_on_sphere += int((rays["tir"] & (rays["gid"] == 5)).sum())
@@ -413,262 +280,118 @@ def test_gpu_cases_cover_every_event():
 
 
 # ---- GPU -------------------------------------------------------------------------------------------------------------------------------
-def _light(pkg, lt):
-    return pkg.binding.SvgfSceneLight.make(lt["centre"], lt["edge_u"], lt["edge_v"], lt["samples"])
-
-
-def _draw(pkg, scene, table, W, H, s, lt, J, K, R, sec=1, frame=FRAME, seed=SEED, stream=None, bufs=None, sync=True):
-    import torch
-    rgb, gbt = bufs or trs._buffers(W, H)
-    scene.draw_gloss(rgb, gbt, W, H, s["cam"], _light(pkg, lt), frame, table=table, paths=J, max_depth=K, rr_depth=R, shadow_secondary=sec, seed=seed,
-                     stream=stream)
-    if not sync:
-        return None
-    torch.cuda.synchronize()
-    return trs._host(pkg, rgb, gbt, W, H)
-
-
-def _draw_split(pkg, scene, table, W, H, s, lt, J, K, R, sec=1, frame=FRAME, seed=SEED, stream=None, bufs=None, rgb=True, sync=True):
-    import torch
-    b = bufs or tsp._split_buffers(W, H, rgb)
-    scene.draw_gloss_split(b["D"], b["I"], b["gb"], W, H, s["cam"], _light(pkg, lt), frame, table=table, paths=J, max_depth=K, rr_depth=R,
-                           shadow_secondary=sec, seed=seed, out_rgb=b["color"], stream=stream)
-    if not sync:
-        return None
-    torch.cuda.synchronize()
-    return tsp._split_host(pkg, b, W, H)
-
-
-def _same(got, m, what):
-    tts._no_difference(got, (m["color"], m["gb"]), what)
-
-
-def _table(pkg, tab):
-    return None if tab is None else pkg.GlossTable(tab)
-
-
-def _draw_case(pkg, case, split=False, rgb=True, **kw):
-    name, W, H, J, K, R, sec, point = case
-    m = _case_model(case, **kw)
-    s = INPUTS[name]()[0]
-    scene = trs._create(pkg, s)
-    table = _table(pkg, m["tab"])
-    try:
-        args = (pkg, scene, table, W, H, s, m["lt"], J, K, R, sec)
-        kw = dict(frame=m["frame"], seed=m["seed"])
-        return (_draw_split(*args, rgb=rgb, **kw) if split else _draw(*args, **kw)), m
-    finally:
-        if table is not None:
-            table.free()
-        scene.free()
+def _draw_case(pkg, case, split=False, rgb=True):
+    m = sh.gloss_model(*case)
+    return sh.draw_case(pkg, sh.GLOSS, sh.gloss_case(case, m), split=split, rgb=rgb), m
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("W,H", SIZES)
+@pytest.mark.parametrize("W,H", sh.SIZES)
 def test_gloss_sizes_and_seams(pkg, W, H):
     case = ("glass_pair", W, H, 2, 3, 2, 1, False)
     got, m = _draw_case(pkg, case)
-    _same(got, m, _what(case))
+    sh.same(got, m, sh.gloss_what(case))
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("case", CASES, ids=lambda c: f"{c[0]}-J{c[3]}-K{c[4]}-R{c[5]}")
+@pytest.mark.parametrize("case", sh.GLOSS_CASES, ids=lambda c: f"{c[0]}-J{c[3]}-K{c[4]}-R{c[5]}")
 def test_gloss_case_equals_the_model(pkg, case):
     got, m = _draw_case(pkg, case)
-    print(f"{_what(case)}: {_events_row(m['info'])}")
-    _same(got, m, _what(case))
+    print(f"{sh.gloss_what(case)}: {_events_row(m['info'])}")
+    sh.same(got, m, sh.gloss_what(case))
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", ["F_cube", "glass_pair"])
 def test_an_empty_table_and_null_are_the_path_library_on_bits(pkg, name):
-    W, H, J, K, R = W0, H0, 3, 4, 2
-    s, lk, _ = INPUTS[name]()
+    W, H, J, K, R = sh.W0, sh.H0, 3, 4, 2
+    s, lk, _ = sh.INPUTS[name]()
     lt = ssm.light(lk["centre"], lk["edge_u"], lk["edge_v"], 1)
-    scene = trs._create(pkg, s)
-    plain = tps._draw(pkg, scene, W, H, s, lt, J, K, R)
-    split = tps._draw_split(pkg, scene, W, H, s, lt, J, K, R)
+    scene = sh.create(pkg, s)
+    plain = sh.draw(pkg, sh.PATH, scene, W, H, s, lt, sh.path_args(J, K, R))
+    split = sh.draw(pkg, sh.PATH, scene, W, H, s, lt, sh.path_args(J, K, R), split=True)
     empty, diffuse = pkg.GlossTable(None), pkg.GlossTable(gm.table(16))
     assert len(empty) == 0 and len(diffuse) == 16
     for what, table in (("NULL", None), ("an empty table", empty), ("an all-diffuse table", diffuse)):
-        tts._no_difference(_draw(pkg, scene, table, W, H, s, lt, J, K, R), plain, f"{name}: {what} vs svgf_path_draw")
-        tsp._no_difference(_draw_split(pkg, scene, table, W, H, s, lt, J, K, R), split, f"{name}: {what} vs svgf_path_draw_split")
+        tb = dict(table=table)
+        sh.same(sh.draw(pkg, sh.GLOSS, scene, W, H, s, lt, sh.path_args(J, K, R), tables=tb), plain, f"{name}: {what} vs svgf_path_draw")
+        sh.same(sh.draw(pkg, sh.GLOSS, scene, W, H, s, lt, sh.path_args(J, K, R), split=True, tables=tb), split, f"{name}: {what} vs svgf_path_draw_split",
+                split=True)
     empty.free(); diffuse.free()
     scene.free()
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("case", [CASES[0], CASES[1], CASES[3]], ids=lambda c: c[0])
+@pytest.mark.parametrize("case", [sh.GLOSS_CASES[0], sh.GLOSS_CASES[1], sh.GLOSS_CASES[3]], ids=lambda c: c[0])
 def test_gloss_split_form_equals_the_model_and_recomposes(pkg, case):
-    import torch
-    name, W, H = case[:3]
+    W, H = case[1:3]
     for rgb in (True, False):
         got, m = _draw_case(pkg, case, split=True, rgb=rgb)
-        tsp._no_difference(got, m, f"{_what(case)}, out_rgb {'given' if rgb else 'NULL'}", rgb=rgb)
+        sh.same(got, m, f"{sh.gloss_what(case)}, out_rgb {'given' if rgb else 'NULL'}", split=True, rgb=rgb)
     assert (m["I"] > 0).any() and (m["info"]["w_d"] == 0).any()
-    d, i = torch.from_numpy(got["D"]).cuda(), torch.from_numpy(got["I"]).cuda()
-    tex = torch.from_numpy(np.ascontiguousarray(got["gb"]).view(np.uint8).reshape(-1).copy()).cuda()
-    out = torch.empty((H, W, 3), dtype=torch.float32, device="cuda")
-    pkg.trace_compose(out, d, i, tex, W, H)
-    torch.cuda.synchronize()
     want = splm.compose((m["gb"]["albedo"] * m["gb"]["ialbedo"]).astype(F), m["D"], m["I"])
-    assert not differing(out.cpu().numpy(), want).any(), "albedo * (D + I) through svgf_trace_compose"
+    assert not differing(sh.compose_on_device(pkg, got, W, H), want).any(), "albedo * (D + I) through svgf_trace_compose"
 
 
 @pytest.mark.gpu
 def test_gloss_planar_target_equals_the_model(pkg):
-    import torch
-    from temporal_harness import _hip
-    case = CASES[0]
-    name, W, H, J, K, R, sec, point = case
-    m = _case_model(case)
-    s = INPUTS[name]()[0]
-    scene = trs._create(pkg, s)
-    table = pkg.GlossTable(m["tab"])
-    den = pkg.Denoiser(W, H, 0)
-    planes = den.planar_gbuffer()
-    rgb = torch.empty((H, W, 3), dtype=torch.float32, device="cuda")
-    scene.draw_gloss(rgb, planes, W, H, s["cam"], _light(pkg, m["lt"]), FRAME, table=table, paths=J, max_depth=K, rr_depth=R, shadow_secondary=sec, seed=SEED)
-    torch.cuda.synchronize()
-    hip = _hip()
-    hip.hipMemcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
-    gb = np.zeros((H, W), dtype=pkg.synth.GBUFFER_DTYPE)
-    for field, ptr in (("normal", planes.normal), ("position", planes.position), ("albedo", planes.albedo), ("geomId", planes.geom_id)):
-        host = np.zeros((H, W, 3) if field != "geomId" else (H, W), F if field != "geomId" else np.int32)
-        assert hip.hipMemcpy(host.ctypes.data, ptr, host.nbytes, 2) == 0
-        gb[field] = host
-    gb["ialbedo"] = F(1.0)
-    got = (rgb.cpu().numpy(), gb)
-    den.free(); table.free(); scene.free()
-    _same(got, m, "glass_pair, planar target")
+    case = sh.GLOSS_CASES[0]
+    m = sh.gloss_model(*case)
+    sh.check_planar_target(pkg, sh.GLOSS, sh.gloss_case(case, m), m, "glass_pair, planar target")
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("case", [CASES[2], CASES[3]], ids=lambda c: c[0])
+@pytest.mark.parametrize("case", [sh.GLOSS_CASES[2], sh.GLOSS_CASES[3]], ids=lambda c: c[0])
 def test_every_tree_draws_the_same_glossy_frame(pkg, case):
-    name, W, H, J, K, R, sec, point = case
-    m = _case_model(case)
-    s = INPUTS[name]()[0]
-    table = pkg.GlossTable(m["tab"])
-    for ml, sp in BUILDS:
-        scene = trs._create(pkg, s, ml, sp)
-        got = _draw(pkg, scene, table, W, H, s, m["lt"], J, K, R, sec, frame=m["frame"], seed=m["seed"])
-        scene.free()
-        _same(got, m, f"{name}, leaf {ml} split {sp}")
-    table.free()
-
-
-BLOCK = (96, 96, 2, 3, 2)                 # the posed block: W, H, paths, max_depth, rr_depth
-
-
-def _block_table():
-    from temporal_harness import BLOCK as B
-    s, _ = tas._block_inputs()
-    return gm.table(len(s["geoms"]), **{f"g{B}": (1.0, 0.0, 1.0, (0.9, 0.9, 0.9))})
-
-
-@functools.lru_cache(maxsize=None)
-def _block_model(f, W, H, J, K, R, posed=True):
-    """Frame f of f15's turning block, the block a mirror, under f16's area light: the model on the posed arrays."""
-    s, tables = tas._block_inputs()
-    ps = pm.posed_scene(s, tables[f]) if posed else s
-    lk = tss._block_light()
-    lt = ssm.light(lk["centre"], lk["edge_u"], lk["edge_v"], 1)
-    col, gb, D, I, info = gm.render(W, H, f, ps["cam"], ps["geoms"], None, None, None, None, None, None, lt, spm.params(J, K, R), _block_table(), seed=3)      # noqa: E741
-    return dict(color=col, gb=gb, D=D, I=I, info=info, lt=lt)
+    m = sh.gloss_model(*case)
+    sh.check_every_tree(pkg, sh.GLOSS, sh.gloss_case(case, m), m, case[0])
 
 
 @pytest.mark.gpu
 def test_the_mirror_follows_the_pose(pkg):
-    W, H, J, K, R = BLOCK
-    s, tables = tas._block_inputs()
-    scene = trs._create(pkg, s)
-    table = pkg.GlossTable(_block_table())
+    W, H, J, K, R = sh.BLOCK
+    s, tables = sh.block_inputs()
+    scene = sh.create(pkg, s)
+    tb = dict(table=pkg.GlossTable(sh.block_table()))
     scene.enable_pose(len(s["geoms"]))
     ind = []
     for f in (0, 2):
-        m = _block_model(f, W, H, J, K, R)
+        m = sh.gloss_block_model(f, W, H, J, K, R)
         assert gm.total(m["info"], "mirror0") > 100
-        scene.pose(tas._dev(tables[f]))
-        _same(_draw(pkg, scene, table, W, H, s, m["lt"], J, K, R, frame=f, seed=3), m, f"mirror block, pose {f}")
-        tsp._no_difference(_draw_split(pkg, scene, table, W, H, s, m["lt"], J, K, R, frame=f, seed=3), m, f"mirror block, pose {f}, split form")
+        scene.pose(sh.dev(tables[f]))
+        for split in (False, True):
+            got = sh.draw(pkg, sh.GLOSS, scene, W, H, s, m["lt"], sh.path_args(J, K, R), split=split, frame=f, seed=3, tables=tb)
+            sh.same(got, m, f"mirror block, pose {f}" + ", split form" * split, split=split)
         ind.append(m["info"]["ind"])
-    table.free(); scene.free()
+    sh.free(*tb.values()); scene.free()
     assert int((ind[0] != ind[1]).any(axis=-1).sum()) > 50
 
 
 @pytest.mark.gpu
 def test_eight_gloss_draws_queued_without_host_waits(pkg):
-    import torch
-    name, W, H, J, K, R, sec, point = QUEUED
-    s = INPUTS[name]()[0]
-    m0 = _case_model(QUEUED)
-    scene = trs._create(pkg, s)
-    table = pkg.GlossTable(m0["tab"])
-    st = tsp._OwnStream()
-    bufs = [trs._buffers(W, H) for _ in range(8)]
-    torch.cuda.synchronize()
-    for f, b in enumerate(bufs):
-        _draw(pkg, scene, table, W, H, s, m0["lt"], J, K, R, sec, frame=f, stream=st, bufs=b, sync=False)
-    st.close()
-    for f, (rgb, gbt) in enumerate(bufs):
-        _same(trs._host(pkg, rgb, gbt, W, H), _case_model(QUEUED, frame=f), f"queued gloss draw, frame {f}")
-    table.free(); scene.free()
+    c = sh.gloss_case(sh.GLOSS_QUEUED, sh.gloss_model(*sh.GLOSS_QUEUED))
+    sh.check_queued(pkg, sh.GLOSS, c, lambda f: sh.gloss_model(*sh.GLOSS_QUEUED, frame=f), "queued gloss draw")
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("split", [False, True])
 def test_a_captured_gloss_draw_is_one_kernel_node_and_replays_the_same_bits(pkg, split):
-    import torch
-    hip = tas._graph_api()
-    name, W, H, J, K, R, sec, point = QUEUED
-    s = INPUTS[name]()[0]
-    m = _case_model(QUEUED)
-    scene = trs._create(pkg, s)
-    table = pkg.GlossTable(m["tab"])
-    st = tsp._OwnStream()
-    b = tsp._split_buffers(W, H) if split else trs._buffers(W, H)
-    torch.cuda.synchronize()
-    draw = (lambda: _draw_split(pkg, scene, table, W, H, s, m["lt"], J, K, R, sec, stream=st, bufs=b, sync=False)) if split else \
-        (lambda: _draw(pkg, scene, table, W, H, s, m["lt"], J, K, R, sec, stream=st, bufs=b, sync=False))
-    draw()                                  # eager first: a first launch may set kernel attributes
-    st.synchronize()
-    graph, gexec = ctypes.c_void_p(), ctypes.c_void_p()
-    assert hip.hipStreamBeginCapture(st.cuda_stream, 2) == 0
-    draw()                                  # recorded, not executed
-    assert hip.hipStreamEndCapture(st.cuda_stream, ctypes.byref(graph)) == 0 and graph.value
-    types = tas._node_types(hip, graph)
-    assert hip.hipGraphInstantiate(ctypes.byref(gexec), graph, None, None, 0) == 0
-    with torch.cuda.stream(st.torch):
-        for t in (b.values() if split else b):
-            t.zero_()
-    assert hip.hipGraphLaunch(gexec, st.cuda_stream) == 0
-    st.synchronize()
-    got = tsp._split_host(pkg, b, W, H) if split else trs._host(pkg, *b, W, H)
-    hip.hipGraphExecDestroy(gexec); hip.hipGraphDestroy(graph)
-    st.close()
-    table.free(); scene.free()
-    print(f"captured gloss draw (split {split}) = node types {types}")
-    assert types == [0], types
-    if split:
-        tsp._no_difference(got, m, "replayed split gloss draw")
-    else:
-        _same(got, m, "replayed gloss draw")
+    m = sh.gloss_model(*sh.GLOSS_QUEUED)
+    sh.check_captured(pkg, sh.GLOSS, sh.gloss_case(sh.GLOSS_QUEUED, m), m, "gloss draw", split=split)
 
 
 @pytest.mark.gpu
 def test_every_error_code_of_the_table_and_both_draws(pkg):
     import torch
     B = pkg.binding
-    s, lk, tab = _glass_pair()
-    scene = trs._create(pkg, s)
+    s, lk, tab = sh.glass_pair()
+    scene = sh.create(pkg, s)
     table = pkg.GlossTable(tab)
     assert len(table) == 7
     lib = pkg.load_gloss_library()
-    cam, sp, planes = B.SvgfCamera(), B.SvgfSynthParams(), B.SvgfPlanarGBuffer()
+    c, p = ctypes.byref(B.SvgfCamera()), ctypes.byref(B.SvgfSynthParams())
     ok = ctypes.byref(B.SvgfSceneLight.make((0, 1, 0), (1, 0, 0), (0, 0, 1), 4))
     pp = ctypes.byref(B.SvgfPathParams(1, 4, 2, 0.15, 1))
-    c, p = ctypes.byref(cam), ctypes.byref(sp)
     guard = torch.full((64,), 7.0, dtype=torch.float32, device="cuda")       # every pointer below is this buffer: a refused call writes nothing
     a = guard.data_ptr()
     plain = lambda h=scene.h, tb=table.h, rgb=a, gb=a, pl=None, w=1, hh=1, cm=c, spp=p, lt=ok, t=pp: lib.svgf_gloss_draw(   # noqa: E731
@@ -678,16 +401,7 @@ def test_every_error_code_of_the_table_and_both_draws(pkg):
     assert plain(rgb=None) == -1
     assert split(d=None) == -1 and split(i=None) == -1 and split(d=a, i=a) == -1
     for f in (plain, split):
-        assert f(h=None) == -1 and f(w=0) == -1 and f(hh=-1) == -1 and f(cm=None) == -1 and f(spp=None) == -1 and f(lt=None) == -1 and f(t=None) == -1
-        assert f(gb=None) == -1 and f(pl=ctypes.byref(planes)) == -1 and f(gb=None, pl=ctypes.byref(planes)) == -1
-        assert f(w=1 << 14, hh=1 << 13) == -5
-        for n in (0, 65):
-            assert f(lt=ctypes.byref(B.SvgfSceneLight.make((0, 1, 0), samples=n))) == -1
-        bad_light = B.SvgfSceneLight.make((0, 1, 0), samples=1)
-        bad_light.edge_v[2] = float("nan")
-        assert f(lt=ctypes.byref(bad_light)) == -1
-        for bad in tps.BAD_PARAMS:
-            assert f(t=ctypes.byref(B.SvgfPathParams(*bad))) == -1, bad
+        sh.check_common_refusals(B, f, (B.SvgfPathParams, sh.BAD_PARAMS))
     # the table's own refusals with a device present, and a device that does not exist
     h = ctypes.c_void_p(7)
     one = (B.SvgfSurface * 1)(B.SvgfSurface(0, 0, 1, (ctypes.c_float * 3)(0, 0, 0)))
@@ -704,9 +418,10 @@ def test_every_error_code_of_the_table_and_both_draws(pkg):
     torch.cuda.synchronize()
     assert (guard.cpu().numpy() == F(7.0)).all()
     case = ("glass_pair", 7, 5, 2, 3, 2, 1, False)
-    m = _case_model(case)
-    _same(_draw(pkg, scene, table, 7, 5, s, m["lt"], 2, 3, 2), m, "after the refused calls")
-    tsp._no_difference(_draw_split(pkg, scene, table, 7, 5, s, m["lt"], 2, 3, 2), m, "after the refused calls, split form")
+    m = sh.gloss_model(*case)
+    tb = dict(table=table)
+    sh.same(sh.draw(pkg, sh.GLOSS, scene, 7, 5, s, m["lt"], sh.path_args(2, 3, 2), tables=tb), m, "after the refused calls")
+    sh.same(sh.draw(pkg, sh.GLOSS, scene, 7, 5, s, m["lt"], sh.path_args(2, 3, 2), split=True, tables=tb), m, "after the refused calls, split form", split=True)
     table.free(); scene.free()
 
 
@@ -719,29 +434,29 @@ def test_pose_gloss_split_draw_two_denoises_compose_sequence(pkg):
     import torch
     from temporal_harness import scales, synth_params
     W, H, J, K, R, N = 128, 72, 1, 3, 2, 4
-    s, tables = tas._block_inputs()
+    s, tables = sh.block_inputs()
     n = len(s["geoms"])
-    lk = tss._block_light()
+    lk = sh.block_light()
     lt = ssm.light(lk["centre"], lk["edge_u"], lk["edge_v"], 1)
     p = synth_params(pkg, W, H, sepcolor=1, addcolor=0)
     assert scales(pkg, W, H)
 
     def run(waits):
-        scene = trs._create(pkg, s)
+        scene = sh.create(pkg, s)
         scene.enable_pose(n)
-        table = pkg.GlossTable(_block_table())
+        table = pkg.GlossTable(sh.block_table())
         dens = {"D": pkg.Denoiser(W, H), "I": pkg.Denoiser(W, H)}
-        t_x = tas._motion_buffer(n)
+        t_x = sh.motion_buffer(n)
         for den in dens.values():
             den.set_object_motion(t_x)
-        b = tsp._split_buffers(W, H, rgb=False)
+        b = sh.split_buffers(W, H, rgb=False)
         outs = {k: torch.empty((H, W, 3), dtype=torch.float32, device="cuda") for k in ("D", "I", "C")}
         frames = []
         wait = torch.cuda.synchronize if waits else (lambda: None)
         try:
             for f in range(N):
-                scene.pose(tas._dev(tables[f]), t_x); wait()
-                _draw_split(pkg, scene, table, W, H, s, lt, J, K, R, frame=f, seed=3, bufs=b, sync=False); wait()
+                scene.pose(sh.dev(tables[f]), t_x); wait()
+                sh.draw(pkg, sh.GLOSS, scene, W, H, s, lt, sh.path_args(J, K, R), split=True, frame=f, seed=3, bufs=b, sync=False, tables=dict(table=table)); wait()
                 for key, den in dens.items():
                     den.denoise(outs[key], b[key], b["gb"], s["cam"], p); wait()
                 pkg.trace_compose(outs["C"], outs["D"], outs["I"], b["gb"], W, H); wait()

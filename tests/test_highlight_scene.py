@@ -20,29 +20,21 @@ import numpy as np
 import pytest
 
 import scene_gloss_model as gm
+import scene_harness as sh
 import scene_highlight_model as hm
 import scene_model as sm
+import scene_path_model as spm
 import scene_pose_model as pm
 import scene_rough_model as rm
+import scene_shadow_model as ssm
 import scene_split_model as splm
 import scene_trace_model as stm
 import scene_virtual_model as vm
-import temporal_model as tm
-import test_animated_scene as tas
-import test_gloss_scene as tgs
-import test_path_scene as tps
-import test_resident_scene as trs
-import test_rough_scene as trr
 import test_scene_model as tsm
-import test_shadowed_scene as tss
-import test_split_scene as tsp
-import test_virtual_scene as tvs
 from conftest import ROOT
 from test_scene_model import FRAME, SEED, differing
 
 F = np.float32
-SIZES = trr.SIZES
-W0, H0 = tgs.W0, tgs.H0
 CLAMP = 2.0                    # the finite clamp of the cases: below the largest H of an alpha-0.1 floor (C5 checks that it is)
 HALL_ROUGH = (0, 0.2, 0, 0, 0, 0.6)
 SPHERE_ROUGH = (0, 0, 0, 0, 0, 0.4, 0.4, 0.2)
@@ -51,16 +43,16 @@ SPHERE_ROUGH = (0, 0, 0, 0, 0, 0.4, 0.4, 0.2)
 # ---- inputs ------------------------------------------------------------------------------------------------------------------------------
 # (name, W, H, paths, max_depth, rr_depth, shadow_secondary, point light), roughness per object id, guide_alpha, max_chain, id_offset,
 # enable, clamp, samples, and the light's centre where it is not the input's own ("floor": on the rough floor, see _centre_of)
-def _hc(name, J, K, R, rough, sec=1, point=False, enable=1, clamp=0.0, samples=1, ga=0.0, mc=4, off=0, W=W0, H=H0, centre=None):
+def _hc(name, J, K, R, rough, sec=1, point=False, enable=1, clamp=0.0, samples=1, ga=0.0, mc=4, off=0, W=sh.W0, H=sh.H0, centre=None):
     return ((name, W, H, J, K, R, sec, point), tuple(rough) if not callable(rough) else rough, ga, mc, off, enable, clamp, samples, centre)
 
 
 HCASES = [_hc("rough_floor", 1, 4, 2, (0.1,)), _hc("rough_floor", 3, 2, 0, (0.4,), samples=3), _hc("rough_floor", 1, 4, 2, (0.1,), clamp=CLAMP, ga=0.3, off=100),
           _hc("rough_floor", 1, 1, 0, (0.4,), sec=0, point=True), _hc("rough_floor", 3, 4, 2, (0.1,), clamp=CLAMP, samples=3),
           _hc("mirror_partial", 3, 4, 2, (0.3, 0.2), point=True), _hc("mirror_partial", 1, 2, 0, (0.3, 0.2), sec=0, samples=3),
-          _hc("mirror_mesh", 3, 4, 2, trr._mesh_rough, ga=1.0), _hc("rough_sphere", 3, 4, 2, SPHERE_ROUGH, ga=0.3, mc=8),
+          _hc("mirror_mesh", 3, 4, 2, sh.mesh_rough, ga=1.0), _hc("rough_sphere", 3, 4, 2, SPHERE_ROUGH, ga=0.3, mc=8),
           _hc("mirror_hall", 3, 2, 0, HALL_ROUGH, samples=3, ga=0.3, mc=8, off=100), _hc("mirror_hall", 1, 4, 2, HALL_ROUGH, sec=0, mc=2),
-          _hc("cornell", 1, 4, 2, trr._cornell_rough, W=96, H=96), _hc("cornell", 1, 4, 2, trr._cornell_rough, clamp=CLAMP, samples=3, ga=1.0, W=96, H=96)]
+          _hc("cornell", 1, 4, 2, sh.cornell_rough, W=96, H=96), _hc("cornell", 1, 4, 2, sh.cornell_rough, clamp=CLAMP, samples=3, ga=1.0, W=96, H=96)]
 # the case made for "no ray formed": a point light ON the rough floor, at the point one pixel sees, 33 samples of that one point
 ON_FLOOR = _hc("rough_floor", 1, 2, 0, (0.4,), point=True, samples=33, W=24, H=16, centre="floor")
 QUEUED = _hc("rough_sphere", 2, 3, 2, SPHERE_ROUGH, ga=0.3, samples=2)
@@ -78,15 +70,15 @@ def _hid(hc):
 
 
 def _what(hc):
-    return (f"{tgs._what(hc[0])}, roughness {[float(a) for a in _rough_of(hc)]}, guide_alpha {hc[2]}, max_chain {hc[3]}, id_offset {hc[4]}, enable {hc[5]}, "
+    return (f"{sh.gloss_what(hc[0])}, roughness {[float(a) for a in _rough_of(hc)]}, guide_alpha {hc[2]}, max_chain {hc[3]}, id_offset {hc[4]}, enable {hc[5]}, "
             f"clamp {hc[6]}, samples {hc[7]}{', light on the floor' if hc[8] else ''}")
 
 
 def _centre_of(name, W, H, frame, seed, centre):
     """The light's centre: the input's own, or ("floor") the point of the rough floor that pixel (3 H / 4, W / 2) sees."""
     if centre is None:
-        return tgs.INPUTS[name]()[1]["centre"]
-    gb = tgs._first(name, W, H, frame, seed)[0][1]
+        return sh.INPUTS[name]()[1]["centre"]
+    gb = sh.gloss_first(name, W, H, frame, seed)[0][1]
     y, x = 3 * H // 4, W // 2
     assert gb["geomId"][y, x] == 0, "the pixel sees the floor"
     return tuple(float(c) for c in gb["position"][y, x])
@@ -98,25 +90,22 @@ def _hmodel(case, rough, ga, mc, off, enable, clamp, samples, centre=None, alt=N
     name, W, H, J, K, R, sec, point = case
     frame = (0 if name in ("cornell",) else FRAME) if frame is None else frame
     seed = 1 if name in ("cornell",) else SEED
-    s, lk, _ = tgs.INPUTS[name]()
-    tab = tgs._table_of(name, table)
+    s, lk, _ = sh.INPUTS[name]()
+    tab = sh.table_of(name, table)
     c = _centre_of(name, W, H, frame, seed, centre)
-    lt = tgs.ssm.light(c, samples=samples) if point else tgs.ssm.light(c, lk["edge_u"], lk["edge_v"], samples)
-    first, em, emit = tgs._first(name, W, H, frame, seed)
+    lt = ssm.light(c, samples=samples) if point else ssm.light(c, lk["edge_u"], lk["edge_v"], samples)
+    first, em, emit = sh.gloss_first(name, W, H, frame, seed)
     if centre is not None:          # the first hits' own colour is lit from the light's centre
-        first = sm.render(W, H, frame, *tss._args(s), c, seed=seed)
+        first = sm.render(W, H, frame, *sh.args_of(s), c, seed=seed)
     r = None if rough is None else np.asarray(rough() if callable(rough) else rough, F)
     hp = hm.params(enable, clamp)
-    col, gb, D, I, chain, info = hm.render(W, H, frame, *tss._args(s), lt, tgs.spm.params(J, K, R, 0.15, sec), tab, vm.params(mc, off), r, ga, hp,     # noqa: E741
+    col, gb, D, I, chain, info = hm.render(W, H, frame, *sh.args_of(s), lt, spm.params(J, K, R, 0.15, sec), tab, vm.params(mc, off), r, ga, hp,     # noqa: E741
                                            seed=seed, alt=alt, first=first, emitters=em, emittance=emit)
     return dict(color=col, gb=gb, D=D, I=I, chain=chain, info=info, lt=lt, frame=frame, seed=seed, tab=tab, rough=r, hp=hp)
 
 
 def _events(m):
     return dict(m["info"]["highlight"])
-
-
-_counts = trr._counts
 
 
 # ---- C1: exports, NEEDED, refusals -----------------------------------------------------------------------------------------------------
@@ -172,11 +161,11 @@ def test_highlight_argument_errors_without_a_device(pkg):
             assert call(ctypes.byref(B.SvgfSceneLight.make((0, 1, 0), samples=n)), P) == -1, n
         assert call(L, P, pl=ctypes.byref(planes)) == -1 and call(L, P, gb=None) == -1
         assert call(L, P, w=0) == -1 and call(L, P, h=-3) == -1
-        for bad in tps.BAD_PARAMS:
+        for bad in sh.BAD_PARAMS:
             assert call(L, ctypes.byref(B.SvgfPathParams(*bad))) == -1, bad
-        for bad in tvs.BAD_VIRTUAL:
+        for bad in sh.BAD_VIRTUAL:
             assert call(L, P, v=ctypes.byref(B.SvgfVirtualParams(*bad))) == -1, bad
-        for bad in trr.BAD_GUIDE_ALPHA:
+        for bad in sh.BAD_GUIDE_ALPHA:
             assert call(L, P, r=ctypes.byref(B.SvgfRoughParams(bad))) == -1, bad
         for bad in BAD_HIGHLIGHT:
             assert call(L, P, hh=ctypes.byref(B.SvgfHighlightParams(*bad))) == -1, bad
@@ -185,27 +174,27 @@ def test_highlight_argument_errors_without_a_device(pkg):
 
 
 # ---- C2: the model's identities --------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("rc", trr.RCASES + [trr.ABOVE], ids=trr._rid)
+@pytest.mark.parametrize("rc", sh.RCASES + [sh.ABOVE], ids=sh.rid)
 def test_enable_0_is_the_rough_model_on_bits(rc):
-    """scene_rough_model.render through test_rough_scene's own cache against this file's model with enable = 0, with and without a
-    clamp, on that file's sixteen cases."""
+    """scene_rough_model.render through the rough suite's cache (scene_harness.rmodel) against this file's model with enable = 0, with
+    and without a clamp, on that suite's sixteen cases."""
     case, rough, ga, mc, off = rc
-    ref = trr._rmodel(*rc)
+    ref = sh.rmodel(*rc)
     m = _hmodel(case, rough, ga, mc, off, 0, CLAMP if case[3] == 1 else 0.0, 1, None)
-    c = _counts(m, ref)
+    c = sh.chain_counts(m, ref)
     assert not any(c.values()), c
     assert not any(_events(m).values())
     assert {e: rm.total(m["info"], e) for e in rm.EVENTS} == {e: rm.total(ref["info"], e) for e in rm.EVENTS}
 
 
-@pytest.mark.parametrize("vc", tvs.VCASES, ids=tvs._vid)
+@pytest.mark.parametrize("vc", sh.VCASES, ids=sh.vid)
 def test_no_table_or_a_zero_table_is_the_virtual_model_for_enable_1(vc):
     case, mc, off = vc
-    ref = tvs._vmodel(*vc)
-    tables = (None, (), (0.0,) * 16) if vc in (tvs.VCASES[1], tvs.VCASES[8]) else (None,)
+    ref = sh.vmodel(*vc)
+    tables = (None, (), (0.0,) * 16) if vc in (sh.VCASES[1], sh.VCASES[8]) else (None,)
     for rough in tables:
         m = _hmodel(case, rough, 1.0, mc, off, 1, CLAMP if rough is None else 0.0, 1, None)
-        c = _counts(m, ref)
+        c = sh.chain_counts(m, ref)
         assert not any(c.values()), (rough, c)
         assert not any(_events(m).values())
 
@@ -215,14 +204,14 @@ def test_roughness_where_it_cannot_act_and_a_clamp_nothing_exceeds_change_no_bit
     (rough_sphere's ids 5 and 6); a clamp above the frame's largest H."""
     hc = HCASES[1]
     ref = _hmodel(*hc)
-    assert not any(_counts(_hmodel(hc[0], (0.4, 0.7, 0.7, 0.7, 0.0, 0.7, 0.9, 0.9, 0.9), *hc[2:]), ref).values())
+    assert not any(sh.chain_counts(_hmodel(hc[0], (0.4, 0.7, 0.7, 0.7, 0.0, 0.7, 0.9, 0.9, 0.9), *hc[2:]), ref).values())
     big = float(np.ceil(ref["info"]["H_max"])) + 1.0
     m = _hmodel(*hc[:6], big, *hc[7:])
-    assert not any(_counts(m, ref).values()) and _events(m)["clamped"] == 0
+    assert not any(sh.chain_counts(m, ref).values()) and _events(m)["clamped"] == 0
     hc = HCASES[8]
     ref = _hmodel(*hc)
-    assert not any(_counts(_hmodel(hc[0], (0, 0, 0, 0, 0, 0.0, 0.0, 0.2), *hc[2:]), ref).values())
-    assert any(_counts(_hmodel(hc[0], (0, 0, 0, 0, 0, 0.4, 0.4, 0.0), *hc[2:]), ref).values())
+    assert not any(sh.chain_counts(_hmodel(hc[0], (0, 0, 0, 0, 0, 0.0, 0.0, 0.2), *hc[2:]), ref).values())
+    assert any(sh.chain_counts(_hmodel(hc[0], (0, 0, 0, 0, 0, 0.4, 0.4, 0.0), *hc[2:]), ref).values())
 
 
 def test_the_highlight_changes_colour_and_D_and_not_the_guide():
@@ -230,7 +219,7 @@ def test_the_highlight_changes_colour_and_D_and_not_the_guide():
     rough, and I differs somewhere (the deeper vertices)."""
     hc = HCASES[4]
     on, off = _hmodel(*hc), _hmodel(*hc[:5], 0, *hc[6:])
-    c = _counts(on, off)
+    c = sh.chain_counts(on, off)
     assert not any(c[k] for k in c if k not in ("color", "direct", "indirect")), c
     assert c["color"] > 0 and c["indirect"] > 0
     changed = np.flatnonzero(differing(on["D"], off["D"]).reshape(-1))
@@ -271,7 +260,7 @@ def test_the_brdf_in_float64(alpha, vn):
     light's term gathers) within 4 standard errors of the sample mean plus the quadrature's own error - next-event estimation and the
     lobe describe the same material."""
     n = np.array([0.36, 0.48, 0.8])
-    d = trr._view(vn, n)
+    d = sh.view_dir(vn, n)
     v = [-x for x in d]
     rng = np.random.default_rng(99)
     # reciprocity on 4096 random pairs of the upper hemisphere
@@ -301,7 +290,7 @@ def test_the_brdf_in_float64(alpha, vn):
     in2 = sum(l2[k] * mirror[k] for k in range(3)) >= cosc
     qerr = abs(float((f2 * dw2)[in2].sum() / np.pi) - nee)
     M = 1 << 16
-    t1, t2 = trr._disc_points(M, rng)
+    t1, t2 = sh.disc_points(M, rng)
     rep = lambda x: np.full(M, x, np.float64)                            # noqa: E731
     Lb = rm.lobe(rep(alpha), [rep(x) for x in d], [rep(x) for x in n], t1, t2, np.float64)
     hit = ~Lb["absorbed"] & (sum(Lb["dn"][k] * mirror[k] for k in range(3)) >= cosc)
@@ -320,12 +309,12 @@ def _made(enable):
     pkg = ge.load_package()
     W, H = 41, 31
     r = float(np.sqrt(0.5))
-    base = tss._example_scene()[1]
+    base = sh.example_scene()[1]
     cam = dict(base, right=np.array([1, 0, 0], F), up=np.array([0, r, -r], F), view=np.array([0, -r, -r], F), position=np.array([0, 3, 3], F))
     geoms = tsm._geoms(pkg, (0, (0.0, -0.1, 0.0), (0, 0, 0), (60, 0.2, 60), (0.8, 0.8, 0.8), 0.0))
-    lt = tgs.ssm.light((0.0, 3.0, -3.0), samples=1)
+    lt = ssm.light((0.0, 3.0, -3.0), samples=1)
     tab = gm.table(1, g0=(0.5, 0.0, 1.0, (0.9, 0.9, 0.9)))
-    out = hm.render(W, H, 0, cam, geoms, None, None, None, None, None, None, lt, tgs.spm.params(1, 1, 0, 0.15, 1), tab, None, np.array([0.2], F), 0.0,
+    out = hm.render(W, H, 0, cam, geoms, None, None, None, None, None, None, lt, spm.params(1, 1, 0, 0.15, 1), tab, None, np.array([0.2], F), 0.0,
                     hm.params(enable), seed=1, noise=0.0, fireflies=0.0)
     return out, W, H, lt
 
@@ -353,7 +342,7 @@ def test_each_highlight_alt_acts_on_the_gpu_cases():
     for alt in hm.ALTS:
         acted = None
         for hc in HCASES[:7]:
-            c = _counts(_hmodel(*hc, alt=alt), _hmodel(*hc))
+            c = sh.chain_counts(_hmodel(*hc, alt=alt), _hmodel(*hc))
             if any(c.values()):
                 acted = (_what(hc), c)
                 break
@@ -378,59 +367,24 @@ def test_gpu_cases_cover_every_highlight_event():
 
 
 # ---- GPU -------------------------------------------------------------------------------------------------------------------------------
-_tables, _free = trr._tables, trr._free
+def _bound(hc, m):
+    return sh.gloss_case(hc[0], m, guide_alpha=hc[2], max_chain=hc[3], id_offset=hc[4], enable=hc[5], clamp=hc[6])
 
 
-def _draw(pkg, scene, table, rough, W, H, s, lt, J, K, R, ga, mc, off, en, cl, sec=1, frame=FRAME, seed=SEED, stream=None, bufs=None, chain=True, sync=True):
-    import torch
-    rgb, gbt, ch = bufs or (trs._buffers(W, H) + (tvs._chain_buffer(W, H) if chain else None,))
-    scene.draw_highlight(rgb, gbt, W, H, s["cam"], tgs._light(pkg, lt), frame, table=table, paths=J, max_depth=K, rr_depth=R, shadow_secondary=sec,
-                         seed=seed, stream=stream, max_chain=mc, id_offset=off, out_chain=ch, rough=rough, guide_alpha=ga, enable=en, clamp=cl)
-    if not sync:
-        return None
-    torch.cuda.synchronize()
-    color, gb = trs._host(pkg, rgb, gbt, W, H)
-    return dict(color=color, gb=gb, chain=None if ch is None else ch.cpu().numpy())
-
-
-def _draw_split(pkg, scene, table, rough, W, H, s, lt, J, K, R, ga, mc, off, en, cl, sec=1, frame=FRAME, seed=SEED, stream=None, bufs=None, rgb=True,
-                chain=True, sync=True):
-    import torch
-    b = bufs or dict(tsp._split_buffers(W, H, rgb), chain=tvs._chain_buffer(W, H) if chain else None)
-    scene.draw_highlight_split(b["D"], b["I"], b["gb"], W, H, s["cam"], tgs._light(pkg, lt), frame, table=table, paths=J, max_depth=K, rr_depth=R,
-                               shadow_secondary=sec, seed=seed, out_rgb=b["color"], stream=stream, max_chain=mc, id_offset=off, out_chain=b["chain"],
-                               rough=rough, guide_alpha=ga, enable=en, clamp=cl)
-    if not sync:
-        return None
-    torch.cuda.synchronize()
-    return dict(tsp._split_host(pkg, b, W, H), chain=None if b["chain"] is None else b["chain"].cpu().numpy())
-
-
-def _draw_case(pkg, hc, split=False, rgb=True, chain=True, builds=None):
-    case, _, ga, mc, off, en, cl, S, ctr = hc
-    name, W, H, J, K, R, sec, point = case
+def _draw_case(pkg, hc, **kw):
     m = _hmodel(*hc)
-    s = tgs.INPUTS[name]()[0]
-    scene = trs._create(pkg, s, *(builds or ()))
-    tb, rt = _tables(pkg, m)
-    try:
-        f = _draw_split if split else _draw
-        kw = dict(rgb=rgb) if split else {}
-        return f(pkg, scene, tb, rt, W, H, s, m["lt"], J, K, R, ga, mc, off, en, cl, sec, frame=m["frame"], seed=m["seed"], chain=chain, **kw), m
-    finally:
-        _free(tb, rt)
-        scene.free()
+    return sh.draw_case(pkg, sh.HIGHLIGHT, _bound(hc, m), **kw), m
 
 
 # G1
 @pytest.mark.gpu
-@pytest.mark.parametrize("W,H", SIZES)
+@pytest.mark.parametrize("W,H", sh.SIZES)
 def test_highlight_sizes_and_seams(pkg, W, H):
     hc = _hc("rough_floor", 2, 3, 2, (0.3,), samples=2, clamp=CLAMP, ga=0.3, off=100, W=W, H=H)
     got, m = _draw_case(pkg, hc)
-    tvs._same(got, m, _what(hc))
+    sh.same(got, m, _what(hc))
     got, m = _draw_case(pkg, hc, split=True)
-    tvs._same(got, m, _what(hc) + ", split form", split=True)
+    sh.same(got, m, _what(hc) + ", split form", split=True)
 
 
 # G2
@@ -439,9 +393,9 @@ def test_highlight_sizes_and_seams(pkg, W, H):
 def test_highlight_case_equals_the_model(pkg, hc):
     got, m = _draw_case(pkg, hc)
     print(f"{_what(hc)}: {_events(m)}")
-    tvs._same(got, m, _what(hc))
+    sh.same(got, m, _what(hc))
     got, m = _draw_case(pkg, hc, split=True)
-    tvs._same(got, m, _what(hc) + ", split form", split=True)
+    sh.same(got, m, _what(hc) + ", split form", split=True)
 
 
 # G3
@@ -450,92 +404,53 @@ def test_highlight_case_equals_the_model(pkg, hc):
 def test_highlight_split_form_with_and_without_rgb_and_chain(pkg, hc):
     for rgb, chain in ((False, True), (True, False), (False, False)):
         got, m = _draw_case(pkg, hc, split=True, rgb=rgb, chain=chain)
-        tvs._same(got, m, f"{_what(hc)}, out_rgb {'given' if rgb else 'NULL'}, out_chain {'given' if chain else 'NULL'}", split=True, rgb=rgb)
+        sh.same(got, m, f"{_what(hc)}, out_rgb {'given' if rgb else 'NULL'}, out_chain {'given' if chain else 'NULL'}", split=True, rgb=rgb)
     got, m = _draw_case(pkg, hc, chain=False)
-    tvs._same(got, m, f"{_what(hc)}, plain form, out_chain NULL")
+    sh.same(got, m, f"{_what(hc)}, plain form, out_chain NULL")
 
 
 @pytest.mark.gpu
 def test_highlight_planar_target_equals_the_model(pkg):
-    import torch
-    from temporal_harness import _hip
     hc = HCASES[4]
-    case, _, ga, mc, off, en, cl, S, _ = hc
-    name, W, H, J, K, R, sec, point = case
     m = _hmodel(*hc)
-    s = tgs.INPUTS[name]()[0]
-    scene = trs._create(pkg, s)
-    table, rough = _tables(pkg, m)
-    den = pkg.Denoiser(W, H, 0)
-    planes = den.planar_gbuffer()
-    hip = _hip()
-    hip.hipMemcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
-
-    def read():
-        gb = np.zeros((H, W), dtype=pkg.synth.GBUFFER_DTYPE)
-        for field, ptr in (("normal", planes.normal), ("position", planes.position), ("albedo", planes.albedo), ("geomId", planes.geom_id)):
-            host = np.zeros((H, W, 3) if field != "geomId" else (H, W), F if field != "geomId" else np.int32)
-            assert hip.hipMemcpy(host.ctypes.data, ptr, host.nbytes, 2) == 0
-            gb[field] = host
-        gb["ialbedo"] = F(1.0)
-        return gb
-
-    kw = dict(table=table, paths=J, max_depth=K, rr_depth=R, shadow_secondary=sec, seed=SEED, max_chain=mc, id_offset=off, rough=rough, guide_alpha=ga,
-              enable=en, clamp=cl)
-    rgb, ch = torch.empty((H, W, 3), dtype=torch.float32, device="cuda"), tvs._chain_buffer(W, H)
-    scene.draw_highlight(rgb, planes, W, H, s["cam"], tgs._light(pkg, m["lt"]), FRAME, out_chain=ch, **kw)
-    torch.cuda.synchronize()
-    tvs._same(dict(color=rgb.cpu().numpy(), gb=read(), chain=ch.cpu().numpy()), m, "rough_floor, planar target")
-    b = dict(tsp._split_buffers(W, H), chain=tvs._chain_buffer(W, H))
-    scene.draw_highlight_split(b["D"], b["I"], planes, W, H, s["cam"], tgs._light(pkg, m["lt"]), FRAME, out_rgb=b["color"], out_chain=b["chain"], **kw)
-    torch.cuda.synchronize()
-    got = dict(D=b["D"].cpu().numpy(), I=b["I"].cpu().numpy(), color=b["color"].cpu().numpy(), gb=read(), chain=b["chain"].cpu().numpy())
-    den.free(); _free(table, rough); scene.free()
-    tvs._same(got, m, "rough_floor, planar target, split form", split=True)
+    sh.check_planar_target(pkg, sh.HIGHLIGHT, _bound(hc, m), m, "rough_floor, planar target", forms=(False, True))
 
 
 # G4
 @pytest.mark.gpu
-@pytest.mark.parametrize("rc", [trr.RCASES[2], trr.RCASES[4], trr.RCASES[7]], ids=trr._rid)
+@pytest.mark.parametrize("rc", [sh.RCASES[2], sh.RCASES[4], sh.RCASES[7]], ids=sh.rid)
 def test_enable_0_is_the_rough_library_on_bits(pkg, rc):
-    case, _, ga, mc, off = rc
-    name, W, H, J, K, R, sec, point = case
-    m = trr._rmodel(*rc)
-    s = tgs.INPUTS[name]()[0]
-    scene = trs._create(pkg, s)
-    tb, rt = _tables(pkg, m)
-    kw = dict(frame=m["frame"], seed=m["seed"])
-    r = trr._draw(pkg, scene, tb, rt, W, H, s, m["lt"], J, K, R, ga, mc, off, sec, **kw)
-    rs = trr._draw_split(pkg, scene, tb, rt, W, H, s, m["lt"], J, K, R, ga, mc, off, sec, **kw)
+    m = sh.rmodel(*rc)
+    c = sh.gloss_case(rc[0], m, guide_alpha=rc[2], max_chain=rc[3], id_offset=rc[4])
+    scene, tb = sh.create(pkg, c["s"]), sh.tables_of(pkg, sh.ROUGH, c)
+    where = (scene, c["W"], c["H"], c["s"], c["lt"])
+    kw = dict(frame=c["frame"], seed=c["seed"], tables=tb)
+    r, rs = (sh.draw(pkg, sh.ROUGH, *where, c["args"], split=split, **kw) for split in (False, True))
     for cl in (0.0, CLAMP):
-        h = _draw(pkg, scene, tb, rt, W, H, s, m["lt"], J, K, R, ga, mc, off, 0, cl, sec, **kw)
-        hs = _draw_split(pkg, scene, tb, rt, W, H, s, m["lt"], J, K, R, ga, mc, off, 0, cl, sec, **kw)
-        tvs._same(h, r, f"{trr._what(rc)}: enable 0, clamp {cl} vs svgf_rough_draw")
-        tvs._same(hs, rs, f"{trr._what(rc)}: enable 0, clamp {cl} vs svgf_rough_draw_split", split=True)
-    _free(tb, rt)
+        h, hs = (sh.draw(pkg, sh.HIGHLIGHT, *where, dict(c["args"], enable=0, clamp=cl), split=split, **kw) for split in (False, True))
+        sh.same(h, r, f"{sh.rough_what(rc)}: enable 0, clamp {cl} vs svgf_rough_draw")
+        sh.same(hs, rs, f"{sh.rough_what(rc)}: enable 0, clamp {cl} vs svgf_rough_draw_split", split=True)
+    sh.free(*tb.values())
     scene.free()
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("vc", [tvs.VCASES[1], tvs.VCASES[8]], ids=tvs._vid)
+@pytest.mark.parametrize("vc", [sh.VCASES[1], sh.VCASES[8]], ids=sh.vid)
 def test_no_table_an_empty_and_a_zero_table_are_the_virtual_library_for_any_hp(pkg, vc):
-    case, mc, off = vc
-    name, W, H, J, K, R, sec, point = case
-    m = tvs._vmodel(*vc)
-    s = tgs.INPUTS[name]()[0]
-    scene = trs._create(pkg, s)
-    tb = tgs._table(pkg, m["tab"])
-    kw = dict(frame=m["frame"], seed=m["seed"])
-    v = tvs._draw(pkg, scene, tb, W, H, s, m["lt"], J, K, R, mc, off, sec, **kw)
-    vs = tvs._draw_split(pkg, scene, tb, W, H, s, m["lt"], J, K, R, mc, off, sec, **kw)
+    m = sh.vmodel(*vc)
+    c = sh.gloss_case(vc[0], m, max_chain=vc[1], id_offset=vc[2])
+    scene, tb = sh.create(pkg, c["s"]), sh.tables_of(pkg, sh.GLOSS, c)
+    where = (scene, c["W"], c["H"], c["s"], c["lt"])
+    kw = dict(frame=c["frame"], seed=c["seed"])
+    v, vs = (sh.draw(pkg, sh.VIRTUAL, *where, c["args"], split=split, tables=tb, **kw) for split in (False, True))
     empty, zero = pkg.RoughTable(None), pkg.RoughTable(np.zeros(16, F))
     for what, rt in (("NULL", None), ("an empty table", empty), ("an all-zero table", zero)):
         for en, cl in ((1, 0.0), (1, CLAMP), (0, 0.0)):
-            r = _draw(pkg, scene, tb, rt, W, H, s, m["lt"], J, K, R, 0.3, mc, off, en, cl, sec, **kw)
-            rs = _draw_split(pkg, scene, tb, rt, W, H, s, m["lt"], J, K, R, 0.3, mc, off, en, cl, sec, **kw)
-            tvs._same(r, v, f"{tvs._what(vc)}: {what}, enable {en}, clamp {cl} vs svgf_virtual_draw")
-            tvs._same(rs, vs, f"{tvs._what(vc)}: {what}, enable {en}, clamp {cl} vs svgf_virtual_draw_split", split=True)
-    _free(empty, zero, tb)
+            args = dict(c["args"], guide_alpha=0.3, enable=en, clamp=cl)
+            r, rs = (sh.draw(pkg, sh.HIGHLIGHT, *where, args, split=split, tables=dict(tb, rough=rt), **kw) for split in (False, True))
+            sh.same(r, v, f"{sh.virtual_what(vc)}: {what}, enable {en}, clamp {cl} vs svgf_virtual_draw")
+            sh.same(rs, vs, f"{sh.virtual_what(vc)}: {what}, enable {en}, clamp {cl} vs svgf_virtual_draw_split", split=True)
+    sh.free(empty, zero, *tb.values())
     scene.free()
 
 
@@ -543,123 +458,68 @@ def test_no_table_an_empty_and_a_zero_table_are_the_virtual_library_for_any_hp(p
 @pytest.mark.gpu
 @pytest.mark.parametrize("hc", [HCASES[2], HCASES[8]], ids=_hid)
 def test_compose_of_the_highlight_split_form_is_the_composed_model(pkg, hc):
-    import torch
     W, H = hc[0][1:3]
     got, m = _draw_case(pkg, hc, split=True)
-    tvs._same(got, m, _what(hc), split=True)
-    d, i = torch.from_numpy(got["D"]).cuda(), torch.from_numpy(got["I"]).cuda()
-    tex = torch.from_numpy(np.ascontiguousarray(got["gb"]).view(np.uint8).reshape(-1).copy()).cuda()
-    out = torch.empty((H, W, 3), dtype=torch.float32, device="cuda")
-    pkg.trace_compose(out, d, i, tex, W, H)
-    torch.cuda.synchronize()
+    sh.same(got, m, _what(hc), split=True)
     want = splm.compose((m["gb"]["albedo"] * m["gb"]["ialbedo"]).astype(F), m["D"], m["I"])
-    assert not differing(out.cpu().numpy(), want).any(), "albedo * (D + I) through svgf_trace_compose"
+    assert not differing(sh.compose_on_device(pkg, got, W, H), want).any(), "albedo * (D + I) through svgf_trace_compose"
 
 
 # G6
 @pytest.mark.gpu
 @pytest.mark.parametrize("hc", [HCASES[7], HCASES[11]], ids=_hid)
 def test_every_tree_draws_the_same_highlight_frame(pkg, hc):
-    for ml, sp in trs.BUILDS:
-        got, m = _draw_case(pkg, hc, builds=(ml, sp))
-        tvs._same(got, m, f"{hc[0][0]}, leaf {ml} split {sp}")
+    m = _hmodel(*hc)
+    sh.check_every_tree(pkg, sh.HIGHLIGHT, _bound(hc, m), m, hc[0][0])
+
+
+BLOCK_ARGS = sh.path_args(*sh.BLOCK[2:], guide_alpha=sh.BLOCK_GA, max_chain=4, id_offset=0, enable=1, clamp=CLAMP)
 
 
 @functools.lru_cache(maxsize=None)
 def _block_hmodel(f, W, H, J, K, R, mc=4, off=0):
     """Frame f of f15's turning block, the block a rough full mirror under the light: the model on the posed arrays."""
-    s, tables = tas._block_inputs()
+    s, tables = sh.block_inputs()
     ps = pm.posed_scene(s, tables[f])
-    lk = tss._block_light()
-    lt = tgs.ssm.light(lk["centre"], lk["edge_u"], lk["edge_v"], 1)
-    col, gb, D, I, chain, info = hm.render(W, H, f, ps["cam"], ps["geoms"], None, None, None, None, None, None, lt, tgs.spm.params(J, K, R), tgs._block_table(),     # noqa: E741
-                                           vm.params(mc, off), trr._block_rough(), trr.BLOCK_GA, hm.params(1, CLAMP), seed=3)
+    lk = sh.block_light()
+    lt = ssm.light(lk["centre"], lk["edge_u"], lk["edge_v"], 1)
+    col, gb, D, I, chain, info = hm.render(W, H, f, ps["cam"], ps["geoms"], None, None, None, None, None, None, lt, spm.params(J, K, R), sh.block_table(),     # noqa: E741
+                                           vm.params(mc, off), sh.block_rough(), sh.BLOCK_GA, hm.params(1, CLAMP), seed=3)
     return dict(color=col, gb=gb, D=D, I=I, chain=chain, info=info, lt=lt)
 
 
 # G7
 @pytest.mark.gpu
 def test_the_highlight_on_the_block_follows_the_pose(pkg):
-    W, H, J, K, R = tgs.BLOCK
-    s, tables = tas._block_inputs()
-    scene = trs._create(pkg, s)
-    table, rough = pkg.GlossTable(tgs._block_table()), pkg.RoughTable(trr._block_rough())
+    W, H, J, K, R = sh.BLOCK
+    s, tables = sh.block_inputs()
+    scene = sh.create(pkg, s)
+    tb = dict(table=pkg.GlossTable(sh.block_table()), rough=pkg.RoughTable(sh.block_rough()))
     scene.enable_pose(len(s["geoms"]))
     first = []
     for f in (0, 2):
         m = _block_hmodel(f, W, H, J, K, R)
         assert _events(m)["first"] > 100
-        scene.pose(tas._dev(tables[f]))
-        tvs._same(_draw(pkg, scene, table, rough, W, H, s, m["lt"], J, K, R, trr.BLOCK_GA, 4, 0, 1, CLAMP, frame=f, seed=3), m, f"rough block, pose {f}")
-        tvs._same(_draw_split(pkg, scene, table, rough, W, H, s, m["lt"], J, K, R, trr.BLOCK_GA, 4, 0, 1, CLAMP, frame=f, seed=3), m,
-                  f"rough block, pose {f}, split form", split=True)
+        scene.pose(sh.dev(tables[f]))
+        for split in (False, True):
+            got = sh.draw(pkg, sh.HIGHLIGHT, scene, W, H, s, m["lt"], BLOCK_ARGS, split=split, frame=f, seed=3, tables=tb)
+            sh.same(got, m, f"rough block, pose {f}" + ", split form" * split, split=split)
         first.append(m["D"])
-    _free(table, rough); scene.free()
+    sh.free(*tb.values()); scene.free()
     assert int((first[0] != first[1]).any(axis=-1).sum()) > 50
 
 
 # G8
 @pytest.mark.gpu
 def test_eight_highlight_draws_queued_without_host_waits(pkg):
-    import torch
-    case, r, ga, mc, off, en, cl, S, _ = QUEUED
-    name, W, H, J, K, R, sec, point = case
-    s = tgs.INPUTS[name]()[0]
-    m0 = _hmodel(*QUEUED)
-    scene = trs._create(pkg, s)
-    table, rough = _tables(pkg, m0)
-    st = tsp._OwnStream()
-    bufs = [trs._buffers(W, H) + (tvs._chain_buffer(W, H),) for _ in range(8)]
-    torch.cuda.synchronize()
-    for f, b in enumerate(bufs):
-        _draw(pkg, scene, table, rough, W, H, s, m0["lt"], J, K, R, ga, mc, off, en, cl, sec, frame=f, stream=st, bufs=b, sync=False)
-    st.close()
-    for f, (rgb, gbt, ch) in enumerate(bufs):
-        color, gb = trs._host(pkg, rgb, gbt, W, H)
-        tvs._same(dict(color=color, gb=gb, chain=ch.cpu().numpy()), _hmodel(*QUEUED, frame=f), f"queued highlight draw, frame {f}")
-    _free(table, rough); scene.free()
+    sh.check_queued(pkg, sh.HIGHLIGHT, _bound(QUEUED, _hmodel(*QUEUED)), lambda f: _hmodel(*QUEUED, frame=f), "queued highlight draw")
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("split", [False, True])
 def test_a_captured_highlight_draw_is_one_kernel_node_and_replays_the_same_bits(pkg, split):
-    import torch
-    hip = tas._graph_api()
-    case, r, ga, mc, off, en, cl, S, _ = QUEUED
-    name, W, H, J, K, R, sec, point = case
-    s = tgs.INPUTS[name]()[0]
     m = _hmodel(*QUEUED)
-    scene = trs._create(pkg, s)
-    table, rough = _tables(pkg, m)
-    st = tsp._OwnStream()
-    b = dict(tsp._split_buffers(W, H), chain=tvs._chain_buffer(W, H)) if split else trs._buffers(W, H) + (tvs._chain_buffer(W, H),)
-    torch.cuda.synchronize()
-    f = _draw_split if split else _draw
-    draw = lambda: f(pkg, scene, table, rough, W, H, s, m["lt"], J, K, R, ga, mc, off, en, cl, sec, stream=st, bufs=b, sync=False)      # noqa: E731
-    draw()                                  # eager first: a first launch may set kernel attributes
-    st.synchronize()
-    graph, gexec = ctypes.c_void_p(), ctypes.c_void_p()
-    assert hip.hipStreamBeginCapture(st.cuda_stream, 2) == 0
-    draw()                                  # recorded, not executed
-    assert hip.hipStreamEndCapture(st.cuda_stream, ctypes.byref(graph)) == 0 and graph.value
-    types = tas._node_types(hip, graph)
-    assert hip.hipGraphInstantiate(ctypes.byref(gexec), graph, None, None, 0) == 0
-    with torch.cuda.stream(st.torch):
-        for t in (b.values() if split else b):
-            t.zero_()
-    assert hip.hipGraphLaunch(gexec, st.cuda_stream) == 0
-    st.synchronize()
-    if split:
-        got = dict(tsp._split_host(pkg, b, W, H), chain=b["chain"].cpu().numpy())
-    else:
-        color, gb = trs._host(pkg, b[0], b[1], W, H)
-        got = dict(color=color, gb=gb, chain=b[2].cpu().numpy())
-    hip.hipGraphExecDestroy(gexec); hip.hipGraphDestroy(graph)
-    st.close()
-    _free(table, rough); scene.free()
-    print(f"captured highlight draw (split {split}) = node types {types}")
-    assert types == [0], types
-    tvs._same(got, m, "replayed highlight draw", split=split)
+    sh.check_captured(pkg, sh.HIGHLIGHT, _bound(QUEUED, m), m, "highlight draw", split=split)
 
 
 # G9
@@ -667,15 +527,14 @@ def test_a_captured_highlight_draw_is_one_kernel_node_and_replays_the_same_bits(
 def test_every_error_code_of_both_highlight_draws(pkg):
     import torch
     B = pkg.binding
-    s, lk, tab = trr._rough_sphere()
-    scene = trs._create(pkg, s)
+    s, lk, tab = sh.rough_sphere()
+    scene = sh.create(pkg, s)
     table, rough = pkg.GlossTable(tab), pkg.RoughTable(list(SPHERE_ROUGH))
     lib = pkg.load_highlight_library()
-    cam, sp, planes = B.SvgfCamera(), B.SvgfSynthParams(), B.SvgfPlanarGBuffer()
+    c, p = ctypes.byref(B.SvgfCamera()), ctypes.byref(B.SvgfSynthParams())
     ok = ctypes.byref(B.SvgfSceneLight.make((0, 1, 0), (1, 0, 0), (0, 0, 1), 4))
     pp, vp, rp = ctypes.byref(B.SvgfPathParams(1, 4, 2, 0.15, 1)), ctypes.byref(B.SvgfVirtualParams(4, 0)), ctypes.byref(B.SvgfRoughParams(0.3))
     hp = ctypes.byref(B.SvgfHighlightParams(1, 0.0))
-    c, p = ctypes.byref(cam), ctypes.byref(sp)
     guard = torch.full((64,), 7.0, dtype=torch.float32, device="cuda")       # every pointer below is this buffer: a refused call writes nothing
     a = guard.data_ptr()
     plain = lambda h=scene.h, tb=table.h, rgb=a, gb=a, pl=None, w=1, hh=1, cm=c, spp=p, lt=ok, t=pp, v=vp, rt=rough.h, r=rp, x=hp: lib.svgf_highlight_draw(   # noqa: E731
@@ -685,20 +544,14 @@ def test_every_error_code_of_both_highlight_draws(pkg):
     assert plain(rgb=None) == -1
     assert split(d=None) == -1 and split(i=None) == -1 and split(d=a, i=a) == -1
     for f in (plain, split):
-        assert f(h=None) == -1 and f(w=0) == -1 and f(hh=-1) == -1 and f(cm=None) == -1 and f(spp=None) == -1 and f(lt=None) == -1 and f(t=None) == -1
-        assert f(gb=None) == -1 and f(pl=ctypes.byref(planes)) == -1 and f(gb=None, pl=ctypes.byref(planes)) == -1
-        assert f(w=1 << 14, hh=1 << 13) == -5
+        sh.check_common_refusals(B, f, (B.SvgfPathParams, sh.BAD_PARAMS))
         # the rough draw's refusals come first: an unsupported size with a bad vp, rp or hp is still SVGF_ERR_UNSUPPORTED
         assert f(w=1 << 14, hh=1 << 13, v=None) == -5 and f(w=1 << 14, hh=1 << 13, r=None) == -5 and f(w=1 << 14, hh=1 << 13, x=None) == -5
-        for n in (0, 65):
-            assert f(lt=ctypes.byref(B.SvgfSceneLight.make((0, 1, 0), samples=n))) == -1
-        for bad in tps.BAD_PARAMS:
-            assert f(t=ctypes.byref(B.SvgfPathParams(*bad))) == -1, bad
         assert f(v=None) == -1
-        for bad in tvs.BAD_VIRTUAL:
+        for bad in sh.BAD_VIRTUAL:
             assert f(v=ctypes.byref(B.SvgfVirtualParams(*bad))) == -1, bad
         assert f(r=None) == -1
-        for bad in trr.BAD_GUIDE_ALPHA:
+        for bad in sh.BAD_GUIDE_ALPHA:
             assert f(r=ctypes.byref(B.SvgfRoughParams(bad))) == -1, bad
         assert f(x=None) == -1
         for bad in BAD_HIGHLIGHT:
@@ -715,9 +568,10 @@ def test_every_error_code_of_both_highlight_draws(pkg):
     for cl in (0.0, 3e38):
         hc = _hc("rough_sphere", 2, 3, 2, SPHERE_ROUGH, clamp=cl, W=7, H=5)
         m = _hmodel(*hc)
-        tvs._same(_draw(pkg, scene, table, rough, 7, 5, s, m["lt"], 2, 3, 2, 0.0, 4, 0, 1, cl), m, f"after the refused calls, clamp {cl}")
-        tvs._same(_draw_split(pkg, scene, table, rough, 7, 5, s, m["lt"], 2, 3, 2, 0.0, 4, 0, 1, cl), m, "after the refused calls, split form", split=True)
-    _free(table, rough); scene.free()
+        tb, args = dict(table=table, rough=rough), sh.path_args(2, 3, 2, guide_alpha=0.0, max_chain=4, id_offset=0, enable=1, clamp=cl)
+        sh.same(sh.draw(pkg, sh.HIGHLIGHT, scene, 7, 5, s, m["lt"], args, tables=tb), m, f"after the refused calls, clamp {cl}")
+        sh.same(sh.draw(pkg, sh.HIGHLIGHT, scene, 7, 5, s, m["lt"], args, split=True, tables=tb), m, "after the refused calls, split form", split=True)
+    sh.free(table, rough); scene.free()
 
 
 # G10
@@ -727,43 +581,6 @@ def test_pose_highlight_split_draw_two_denoises_compose_against_the_temporal_mod
     context of its own (sepcolor 1 / addcolor 0, the temporal pass alone so that temporal_model.py is the whole filter) ->
     svgf_trace_compose.  Every state of both contexts after every frame equals temporal_model.run_sequence fed the model's D (or I) and
     the model's G-buffer, on bits."""
-    import torch
-    from temporal_harness import assert_frames_equal, read_states, scales, synth_params
-    W, H, J, K, R = tgs.BLOCK
-    N = 4
-    s, tables = tas._block_inputs()
-    models = [_block_hmodel(f, W, H, J, K, R) for f in range(N)]
-    lt = models[0]["lt"]
-    p = synth_params(pkg, W, H, sepcolor=1, addcolor=0)
-    sx, sy = scales(pkg, W, H)
-    views = [orc.view_matrix(pkg, s["cam"])] * N
-    scene = trs._create(pkg, s)
-    scene.enable_pose(len(s["geoms"]))
-    table, rough = pkg.GlossTable(tgs._block_table()), pkg.RoughTable(trr._block_rough())
-    dens = {"D": pkg.Denoiser(W, H), "I": pkg.Denoiser(W, H)}
-    for den in dens.values():
-        den.set_capture(True)
-    b = dict(tsp._split_buffers(W, H, rgb=False), chain=tvs._chain_buffer(W, H))
-    outs = {k: torch.empty((H, W, 3), dtype=torch.float32, device="cuda") for k in ("D", "I", "C")}
-    states = {"D": [], "I": []}
-    try:
-        for f in range(N):
-            scene.pose(tas._dev(tables[f]))
-            got = _draw_split(pkg, scene, table, rough, W, H, s, lt, J, K, R, trr.BLOCK_GA, 4, 0, 1, CLAMP, frame=f, seed=3, bufs=b, rgb=False)
-            tvs._same(got, models[f], f"frame {f}", split=True, rgb=False)
-            for key, den in dens.items():
-                den.denoise(outs[key], b[key], b["gb"], s["cam"], p)
-                den.sync()
-                states[key].append(read_states(den))
-            pkg.trace_compose(outs["C"], outs["D"], outs["I"], b["gb"], W, H)
-            torch.cuda.synchronize()
-            alb = (models[f]["gb"]["albedo"] * models[f]["gb"]["ialbedo"]).astype(F)
-            want = splm.compose(alb, outs["D"].cpu().numpy(), outs["I"].cpu().numpy())
-            assert not differing(outs["C"].cpu().numpy(), want).any(), f"frame {f}: composed"
-    finally:
-        for den in dens.values():
-            den.free()
-        _free(table, rough); scene.free()
-    for key in ("D", "I"):
-        ref = tm.run_sequence([(m[key], m["gb"]) for m in models], views=views, scale=(sx, sy))
-        assert_frames_equal(states[key], ref, f"highlight block, term {key}")
+    W, H, J, K, R = sh.BLOCK
+    sh.run_split_denoise_compose(pkg, orc, sh.HIGHLIGHT, [_block_hmodel(f, W, H, J, K, R) for f in range(4)], W, H, BLOCK_ARGS,
+                                 ("highlight block, term D", "highlight block, term I"), tab=sh.block_table(), rough=sh.block_rough())

@@ -25,124 +25,18 @@ import subprocess
 import numpy as np
 import pytest
 
+import scene_harness as sh
 import scene_model as sm
 import scene_path_model as spm
 import scene_pose_model as pm
 import scene_shadow_model as ssm
 import scene_split_model as splm
 import scene_trace_model as stm
-import test_animated_scene as tas
-import test_resident_scene as trs
 import test_scene_model as tsm
-import test_shadowed_scene as tss
-import test_split_scene as tsp
-import test_traced_scene as tts
 from conftest import ROOT
 from test_scene_model import FRAME, SEED, differing
 
 F = np.float32
-BUILDS = trs.BUILDS
-SIZES = tss.SIZES
-
-
-# ---- inputs ------------------------------------------------------------------------------------------------------------------------------
-@functools.lru_cache(maxsize=None)
-def _bleed_ceiling():
-    """f17's `bleed` (a white floor, a red wall, a white back wall) under a white ceiling: light that left the red wall comes back to
-    the floor by way of the ceiling too."""
-    import __graft_entry__ as ge
-    pkg = ge.load_package()
-    s, lk = tts._bleed()
-    s = dict(s)
-    s["geoms"] = np.concatenate([s["geoms"], tsm._geoms(pkg, (0, (0, 6.35, 0), (0, 0, 0), (12, 0.5, 12), (0.9, 0.9, 0.9), 0.0))])
-    return s, lk
-
-
-@functools.lru_cache(maxsize=None)
-def _bleed_nan():
-    """_bleed_ceiling with a two-sided sheet WITHOUT normals floating over the floor: a path that lands on it has a NaN normal at that
-    vertex, its next direction is NaN, and it ends there - behind the first hit, where f17 never looked."""
-    s, lk = _bleed_ceiling()
-    s = dict(s)
-    zero = np.zeros((3, 3), F)
-    p0, p1, p2 = (-4.5, 1.5, -3.0), (4.5, 1.5, -3.0), (0.0, 5.0, 3.0)
-    s["tris"] = np.stack([tsm._tri(p0, p1, p2, nrm=zero), tsm._tri(p0, p2, p1, nrm=zero)])
-    s["tri_ids"], s["tri_albedo"] = np.array([7, 7], np.int32), tsm._colours(2, 3)
-    return s, lk
-
-
-@functools.lru_cache(maxsize=None)
-def _furnace07():
-    """f17's furnace with the two objects at albedo 0.7: closed, and the throughput falls, so the roulette kills."""
-    s, lk = tts._furnace()
-    s = dict(s)
-    g = np.array(s["geoms"], copy=True)
-    g["albedo"][1:] = F(0.7)
-    s["geoms"] = g
-    return s, lk
-
-
-@functools.lru_cache(maxsize=None)
-def _far_sheet():
-    """The scene on which t_lo must be formed from the CURRENT vertex.  A floor around the origin (first hits with |x| of a few units:
-    t_lo about 2^-10 ... 2^-8), a wall whose face stands at z = -30 (a vertex there: t_lo = 30 * 2^-10 = 0.029), and 0.01 in front of
-    that face a one-sided sheet that faces the WALL: the camera's rays and the bounce from the floor cross it from behind, a bounce that
-    leaves the wall meets its front at t = 0.01 / cos - below the wall vertex's t_lo for most directions, above the floor vertex's."""
-    import __graft_entry__ as ge
-    pkg = ge.load_package()
-    z = (0, 0, 0)
-    geoms = tsm._geoms(pkg, (0, (0, -0.5, 0), z, (16, 1, 16), (0.8, 0.8, 0.8), 0.0), (0, (0, 20, -31), z, (120, 60, 2), (0.7, 0.7, 0.9), 0.0))
-    a, b, c, d = (-60, -5, -29.99), (60, -5, -29.99), (60, 50, -29.99), (-60, 50, -29.99)
-    tris = [tsm._tri(a, c, b), tsm._tri(a, d, c, k=1)]                 # e1 x e2 points to -z, towards the wall
-    s = dict(cam=tsm._cam(pkg, (0, 5, 9), (0, 0, 0), 30.0), geoms=geoms, geom_ids=None, tris=np.stack(tris), tri_ids=np.array([5, 5], np.int32),
-             tri_albedo=tsm._colours(2, 4), tri_tex=None, textures=None, light=(0.0, 8.0, 0.0))
-    return s, dict(centre=s["light"], edge_u=(0.5, 0.0, 0.0), edge_v=(0.0, 0.0, 0.5))
-
-
-_OWN = {"bleed_ceiling": _bleed_ceiling, "bleed_nan": _bleed_nan, "furnace07": _furnace07, "far_sheet": _far_sheet}
-
-
-def _input(kind, name):
-    return _OWN[name]() if kind == "path" else tts._input(kind, name)
-
-
-@functools.lru_cache(maxsize=None)
-def _first(kind, name, W, H, frame, seed, noise=0.6):
-    if kind != "path":
-        return tts._first(kind, name, W, H, frame, seed, noise)
-    s = _input(kind, name)[0]
-    first = sm.render(W, H, frame, *tss._args(s), s["light"], seed=seed, noise=noise, fireflies=0.02 if noise else 0.0)
-    em = ssm.emitter_mask(W, H, s["cam"], s["geoms"], s["geom_ids"], s["tris"], s["tri_ids"])
-    for a in first + (em,):
-        a.setflags(write=False)
-    return first, em
-
-
-@functools.lru_cache(maxsize=None)
-def _emittance(kind, name, W, H):
-    s = _input(kind, name)[0]
-    e = splm.emittance_plane(W, H, s["cam"], s["geoms"], s["geom_ids"], s["tris"], s["tri_ids"])
-    e.setflags(write=False)
-    return e
-
-
-@functools.lru_cache(maxsize=None)
-def _model(kind, name, W, H, J, K, R, sec=1, samples=1, point=False, alt=None, frame=None, seed=None, noise=0.6, ambient=0.15):
-    """dict(color, gb, D, I, info, lt) of scene_path_model.render; a recorded scene at frame 0, seed 1 unless told otherwise."""
-    frame = (0 if kind == "rec" else FRAME) if frame is None else frame
-    seed = (1 if kind == "rec" else SEED) if seed is None else seed
-    s, lk = _input(kind, name)
-    lt = ssm.light(lk["centre"], samples=samples) if point else ssm.light(lk["centre"], lk["edge_u"], lk["edge_v"], samples)
-    first, em = _first(kind, name, W, H, frame, seed, noise)
-    col, gb, D, I, info = spm.render(W, H, frame, *tss._args(s), lt, spm.params(J, K, R, ambient, sec), seed=seed, noise=noise,       # noqa: E741
-                                     fireflies=0.02 if noise else 0.0, alt=alt, first=first, emitters=em, emittance=_emittance(kind, name, W, H))
-    for a in (col, D, I):
-        a.setflags(write=False)
-    return dict(color=col, gb=gb, D=D, I=I, info=info, lt=lt, frame=frame, seed=seed)
-
-
-def _counts_row(info):
-    return [tuple(d[k] for k in spm.COUNTS) for d in info["depth"]]
 
 
 # ---- CPU 1: exports, declarations, refusals --------------------------------------------------------------------------------------------
@@ -167,10 +61,6 @@ def test_the_three_symbols_are_declared_listed_and_exported(pkg):
     print(f"libsvgf_hip.so {os.path.getsize(B.LIB_PATH)} bytes, libsvgf_path.so {os.path.getsize(B.LIB_PATH_PATH)} bytes")
 
 
-BAD_PARAMS = [(-1, 4, 2, 0.15, 1), (9, 4, 2, 0.15, 1), (1, 0, 0, 0.15, 1), (1, 9, 0, 0.15, 1), (1, -1, 0, 0.15, 1), (1, 4, -1, 0.15, 1), (1, 4, 9, 0.15, 1),
-              (1, 4, 2, float("nan"), 1), (1, 4, 2, float("inf"), 1), (1, 4, 2, -0.5, 1), (1, 4, 2, 0.15, 2), (1, 4, 2, 0.15, -1)]
-
-
 def test_path_argument_errors_without_a_device(pkg):
     """Every refusal of both calls is answered before any device work: none of these calls needs a device (there is no scene without
     one, so the scene is NULL throughout, which is itself refused; the GPU test repeats the list with a scene)."""
@@ -189,7 +79,7 @@ def test_path_argument_errors_without_a_device(pkg):
             assert call(ctypes.byref(B.SvgfSceneLight.make((0, 1, 0), samples=n)), P) == -1, n
         assert call(L, P, pl=ctypes.byref(planes)) == -1 and call(L, P, gb=None) == -1
         assert call(L, P, w=0) == -1 and call(L, P, h=-3) == -1
-        for bad in BAD_PARAMS:
+        for bad in sh.BAD_PARAMS:
             assert call(L, ctypes.byref(B.SvgfPathParams(*bad))) == -1, bad
     assert plain(L, P, rgb=None) == -1
     assert split(L, P, d=None) == -1 and split(L, P, i=None) == -1 and split(L, P, d=5, i=5) == -1 and split(L, P, rgb=None) == -1
@@ -206,10 +96,10 @@ def test_a_moved_seed_moves_every_stream():
 @pytest.mark.parametrize("kind,name,kw", [("edge", "B", {}), ("edge", "F_cube", {}), ("made", "stage", {}), ("traced", "furnace", dict(noise=0.0, ambient=1.0))])
 def test_depth_one_is_the_traced_and_the_split_model(kind, name, kw):
     W, H, J = 67, 41, 3
-    ref = tsp._split(kind, name, W, H, J, **kw)
+    ref = sh.split_model(kind, name, W, H, J, **kw)
     for R in (0, 1):
-        m = _model(kind, name, W, H, J, 1, R, **kw)
-        c = tsp._split_counts(m, ref)
+        m = sh.path_model(kind, name, W, H, J, 1, R, **kw)
+        c = sh.split_counts(m, ref)
         print(f"{name}, max_depth 1, rr_depth {R}: differing pixels {c} (expected and allowed: 0)")
         assert not any(c.values()), c
     assert (ref["I"] > 0).any()
@@ -222,7 +112,7 @@ def test_the_furnace_by_depth():
     W, H, J = 48, 27, 4
     prev, share = None, {}
     for K in (1, 2, 4, 8):
-        m = _model("traced", "furnace", W, H, J, K, 0, noise=0.0, ambient=0.0)
+        m = sh.path_model("traced", "furnace", W, H, J, K, 0, noise=0.0, ambient=0.0)
         info = m["info"]
         cast, acc = info["cast"], np.stack(info["acc"])            # [3, J, n]
         assert cast.sum() > 200 and ((acc == 0) | (acc == 1)).all() and (acc[0] == acc[1]).all() and (acc[0] == acc[2]).all()
@@ -231,7 +121,7 @@ def test_the_furnace_by_depth():
         assert (whole == np.round(whole)).all() and (whole >= 0).all() and (whole <= J).all()
         assert not differing(m["I"], info["ind"])[cast].any()
         share[K] = float((acc[0] == 0).mean())
-        print(f"furnace, max_depth {K}: {acc[0].size} paths, share returning 0: {share[K]:.5f}; per depth {spm.COUNTS}: {_counts_row(info)}")
+        print(f"furnace, max_depth {K}: {acc[0].size} paths, share returning 0: {share[K]:.5f}; per depth {spm.COUNTS}: {sh.counts_row(info)}")
         assert all(d["misses"] == 0 for d in info["depth"])
         if prev is not None:
             assert (ind >= prev).all()
@@ -246,15 +136,15 @@ def test_roulette_is_unbiased_in_the_model():
     errors added in quadrature; the sides share every stream but the roulette's, so this is generous), and the same roulette WITHOUT the
     division by q must not."""
     W, H, N = 48, 48, 8
-    s, lk = _input("rec", "cornell")
+    s, lk = sh.scene_input("rec", "cornell")
     lt = ssm.light(lk["centre"], lk["edge_u"], lk["edge_v"], 1)
-    first, em = _first("rec", "cornell", W, H, 0, 1, 0.0)
+    first, em = sh.first_hit("rec", "cornell", W, H, 0, 1, 0.0)
     stat = {}
     for tag, R, alt in (("rr_depth 0", 0, None), ("rr_depth 1", 1, None), ("no compensation", 1, "no_roulette_compensation")):
         vals, kills, surv = [], 0, 0
         for f in range(N):
-            info = spm.render(W, H, f, *tss._args(s), lt, spm.params(1, 8, R), seed=1, noise=0.0, fireflies=0.0, alt=alt, first=first, emitters=em,
-                              emittance=_emittance("rec", "cornell", W, H))[4]
+            info = spm.render(W, H, f, *sh.args_of(s), lt, spm.params(1, 8, R), seed=1, noise=0.0, fireflies=0.0, alt=alt, first=first, emitters=em,
+                              emittance=sh.emittance("rec", "cornell", W, H))[4]
             vals.append(info["ind"][info["cast"]].astype(np.float64).mean(axis=-1))
             kills += sum(d["rr_kills"] for d in info["depth"]); surv += sum(d["rr_survivals"] for d in info["depth"])
         v = np.stack(vals)
@@ -272,7 +162,7 @@ def test_colour_is_picked_up_twice():
     W, H, J = 48, 27, 8
     ratio = {}
     for K in (1, 4):
-        m = _model("path", "bleed_ceiling", W, H, J, K, 0, noise=0.0)
+        m = sh.path_model("path", "bleed_ceiling", W, H, J, K, 0, noise=0.0)
         x, I = m["gb"]["position"][..., 0], m["I"].astype(np.float64)      # noqa: E741
         near = (m["gb"]["geomId"] == 0) & (x < -2.0)
         assert near.sum() > 20
@@ -287,14 +177,14 @@ ALT_SCENES = [("edge", "F_cube", 67, 41), ("path", "bleed_ceiling", 67, 41), ("r
 
 def test_each_alt_acts():
     """Pixels on which the frame of the model and of a wrong variant of it differ, per scene, at 3 paths of up to 4 bounces with the
-    roulette from bounce 1 on: every alt changes some scene.  `t_lo_from_first_pos` needs the scene made for it (_far_sheet)."""
+    roulette from bounce 1 on: every alt changes some scene.  `t_lo_from_first_pos` needs the scene made for it (scene_harness._far_sheet)."""
     J, K, R = 3, 4, 1
     total = {a: 0 for a in spm.ALTS}
     for kind, name, W, H in ALT_SCENES:
-        ref = _model(kind, name, W, H, J, K, R)
+        ref = sh.path_model(kind, name, W, H, J, K, R)
         row = {}
         for alt in spm.ALTS:
-            m = _model(kind, name, W, H, J, K, R, alt=alt)
+            m = sh.path_model(kind, name, W, H, J, K, R, alt=alt)
             row[alt] = tsm.any_differs((m["color"], m["gb"]), (ref["color"], ref["gb"]))
             total[alt] += row[alt]
         print(f"scene {name} {W}x{H}: {row}")
@@ -324,13 +214,13 @@ COVERED = PRODUCT + RECORDED + SPECIAL + SPLIT + TREES + [QUEUED]
 
 def _case_model(case, **kw):
     kind, name, W, H, J, K, R, sec, point = case
-    return _model(kind, name, W, H, J, K, R, sec, 1, point, **kw)
+    return sh.path_model(kind, name, W, H, J, K, R, sec, 1, point, **kw)
 
 
 def _covered(what, K, R, info):
     second = info["depth"][1]["hits"]
     kills, surv = (sum(d[k] for d in info["depth"]) for k in ("rr_kills", "rr_survivals"))
-    print(f"{what}: paths with a hit at bounce 2: {second}; roulette kills {kills}, survivals {surv}; per depth {spm.COUNTS}: {_counts_row(info)}")
+    print(f"{what}: paths with a hit at bounce 2: {second}; roulette kills {kills}, survivals {surv}; per depth {spm.COUNTS}: {sh.counts_row(info)}")
     assert second >= 100, what
     if R > 0:
         assert kills >= 100 and surv >= 100, what
@@ -366,7 +256,7 @@ def test_denoised_deep_paths_beat_the_noisy_frame_after_eight_static_frames(pkg,
     import quality_model as qm
     from temporal_harness import scales
     W, H, N = 64, 36, 8
-    geoms, cam, lk = tss._example_scene()
+    geoms, cam, lk = sh.example_scene()
     p = pkg.reference_defaults().set(temporal_enable=1, spatial_enable=1)
     p.reproj_scale[0], p.reproj_scale[1] = scales(pkg, W, H)
     first = sm.render(W, H, 0, cam, geoms, None, None, None, None, None, None, lk["centre"], seed=7, noise=0.0, fireflies=0.0)
@@ -388,74 +278,41 @@ def test_denoised_deep_paths_beat_the_noisy_frame_after_eight_static_frames(pkg,
 
 
 # ---- GPU -------------------------------------------------------------------------------------------------------------------------------
-def _light(pkg, lt):
-    return pkg.binding.SvgfSceneLight.make(lt["centre"], lt["edge_u"], lt["edge_v"], lt["samples"])
-
-
-def _draw(pkg, scene, W, H, s, lt, J, K, R, sec=1, ambient=0.15, frame=FRAME, seed=SEED, noise=0.6, stream=None, bufs=None, sync=True):
-    import torch
-    rgb, gbt = bufs or trs._buffers(W, H)
-    scene.draw_path(rgb, gbt, W, H, s["cam"], _light(pkg, lt), frame, paths=J, max_depth=K, rr_depth=R, ambient=ambient, shadow_secondary=sec, seed=seed,
-                    noise=noise, fireflies=0.02 if noise else 0.0, stream=stream)
-    if not sync:
-        return None
-    torch.cuda.synchronize()
-    return trs._host(pkg, rgb, gbt, W, H)
-
-
-def _draw_split(pkg, scene, W, H, s, lt, J, K, R, sec=1, ambient=0.15, frame=FRAME, seed=SEED, noise=0.6, stream=None, bufs=None, rgb=True, sync=True):
-    import torch
-    b = bufs or tsp._split_buffers(W, H, rgb)
-    scene.draw_path_split(b["D"], b["I"], b["gb"], W, H, s["cam"], _light(pkg, lt), frame, paths=J, max_depth=K, rr_depth=R, ambient=ambient,
-                          shadow_secondary=sec, seed=seed, noise=noise, fireflies=0.02 if noise else 0.0, out_rgb=b["color"], stream=stream)
-    if not sync:
-        return None
-    torch.cuda.synchronize()
-    return tsp._split_host(pkg, b, W, H)
-
-
-def _same(got, m, what):
-    tts._no_difference(got, (m["color"], m["gb"]), what)
-
-
 def _what(case):
     kind, name, W, H, J, K, R, sec, point = case
     return f"{name} {W}x{H}, {J} paths, max_depth {K}, rr_depth {R}, secondary shadow {sec}, {'point' if point else 'area'} light"
 
 
-def _draw_case(pkg, case, split=False, rgb=True, **kw):
+def _bound(case, m, **more):
     kind, name, W, H, J, K, R, sec, point = case
+    return sh.case(sh.scene_input(kind, name)[0], W, H, m["lt"], sh.path_args(J, K, R, sec, **more), m["frame"], m["seed"])
+
+
+def _draw_case(pkg, case, split=False, rgb=True, **kw):
     m = _case_model(case, **kw)
-    s = _input(kind, name)[0]
-    scene = trs._create(pkg, s)
-    try:
-        args = (pkg, scene, W, H, s, m["lt"], J, K, R, sec)
-        kw = dict(frame=m["frame"], seed=m["seed"], ambient=kw.get("ambient", 0.15), noise=kw.get("noise", 0.6))
-        return (_draw_split(*args, rgb=rgb, **kw) if split else _draw(*args, **kw)), m
-    finally:
-        scene.free()
+    return sh.draw_case(pkg, sh.PATH, _bound(case, m, **kw), split=split, rgb=rgb), m
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("W,H", SIZES)
+@pytest.mark.parametrize("W,H", sh.SIZES)
 def test_path_sizes_and_seams(pkg, W, H):
     got, m = _draw_case(pkg, ("edge", "B", W, H, 2, 3, 2, 1, False))
-    _same(got, m, f"scene B {W}x{H}, 2 paths, max_depth 3, rr_depth 2")
+    sh.same(got, m, f"scene B {W}x{H}, 2 paths, max_depth 3, rr_depth 2")
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("case", PRODUCT, ids=lambda c: f"{c[1]}-J{c[4]}-K{c[5]}-R{c[6]}-s{c[7]}-{'point' if c[8] else 'area'}")
 def test_parameter_product_equals_the_model(pkg, case):
     got, m = _draw_case(pkg, case)
-    _same(got, m, _what(case))
+    sh.same(got, m, _what(case))
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("case", RECORDED, ids=lambda c: c[1])
 def test_recorded_scene_equals_the_model(pkg, case):
     got, m = _draw_case(pkg, case)
-    print(f"{case[1]}: per depth {spm.COUNTS}: {_counts_row(m['info'])}")
-    _same(got, m, _what(case))
+    print(f"{case[1]}: per depth {spm.COUNTS}: {sh.counts_row(m['info'])}")
+    sh.same(got, m, _what(case))
 
 
 @pytest.mark.gpu
@@ -463,15 +320,15 @@ def test_recorded_scene_equals_the_model(pkg, case):
 def test_the_furnace_on_the_device(pkg, K):
     W, H, J = 48, 27, 4
     got, m = _draw_case(pkg, ("traced", "furnace", W, H, J, K, 0, 1, False), noise=0.0, ambient=0.0)
-    _same(got, m, f"furnace, max_depth {K}")
+    sh.same(got, m, f"furnace, max_depth {K}")
     cast = m["info"]["cast"]
-    want = (got[1]["albedo"] * m["info"]["ind"]).astype(F)            # ((alb * (0 + ind)) * 1) * 1
-    assert not differing(got[0], want)[cast].any()
+    want = (got["gb"]["albedo"] * m["info"]["ind"]).astype(F)            # ((alb * (0 + ind)) * 1) * 1
+    assert not differing(got["color"], want)[cast].any()
 
 
 @pytest.mark.gpu
 def test_nan_normals_behind_the_first_hit(pkg):
-    """_bleed_nan: pixels whose first hit is the sheet without normals cast paths that end at once, and paths that land on it later
+    """scene_harness._bleed_nan: pixels whose first hit is the sheet without normals cast paths that end at once, and paths that land on it later
     end there; the model counts both."""
     case = SPECIAL[0]
     got, m = _draw_case(pkg, case)
@@ -479,103 +336,72 @@ def test_nan_normals_behind_the_first_hit(pkg):
     on_sheet = sum(int((g == 7).sum()) for g in m["info"]["hit_gid"][:-1])
     print(f"{first} pixels see the sheet without normals; {on_sheet} paths land on it before their last bounce")
     assert first > 50 and on_sheet > 100
-    _same(got, m, _what(case))
+    sh.same(got, m, _what(case))
 
 
 @pytest.mark.gpu
 def test_a_textured_mesh_behind_the_second_hit(pkg):
     case = SPECIAL[1]
     got, m = _draw_case(pkg, case)
-    s = _input("traced", "textured")[0]
+    s = sh.scene_input("traced", "textured")[0]
     tex_ids = list(set(np.asarray(s["tri_ids"])[np.asarray(s["tri_tex"]) >= 0].tolist()))
     on_texture = int(np.isin(m["info"]["hit_gid"][1], tex_ids).sum())
     print(f"{on_texture} of {m['info']['depth'][1]['alive']} second bounces end on a textured triangle")
     assert on_texture > 0
-    _same(got, m, _what(case))
+    sh.same(got, m, _what(case))
 
 
 @pytest.mark.gpu
 def test_planar_target_equals_the_model(pkg):
-    import torch
-    from temporal_harness import _hip
     case = PRODUCT[2]
-    kind, name, W, H, J, K, R, sec, point = case
     m = _case_model(case)
-    s = _input(kind, name)[0]
-    scene = trs._create(pkg, s)
-    den = pkg.Denoiser(W, H, 0)
-    planes = den.planar_gbuffer()
-    rgb = torch.empty((H, W, 3), dtype=torch.float32, device="cuda")
-    scene.draw_path(rgb, planes, W, H, s["cam"], _light(pkg, m["lt"]), FRAME, paths=J, max_depth=K, rr_depth=R, shadow_secondary=sec, seed=SEED)
-    torch.cuda.synchronize()
-    hip = _hip()
-    hip.hipMemcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
-    gb = np.zeros((H, W), dtype=pkg.synth.GBUFFER_DTYPE)
-    for field, ptr in (("normal", planes.normal), ("position", planes.position), ("albedo", planes.albedo), ("geomId", planes.geom_id)):
-        host = np.zeros((H, W, 3) if field != "geomId" else (H, W), F if field != "geomId" else np.int32)
-        assert hip.hipMemcpy(host.ctypes.data, ptr, host.nbytes, 2) == 0
-        gb[field] = host
-    gb["ialbedo"] = F(1.0)
-    got = (rgb.cpu().numpy(), gb)
-    den.free(); scene.free()
-    _same(got, m, "scene F_cube, planar target")
+    sh.check_planar_target(pkg, sh.PATH, _bound(case, m), m, "scene F_cube, planar target")
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("case", SPLIT, ids=lambda c: c[1])
 def test_split_form_equals_the_model_and_recomposes(pkg, case):
-    import torch
-    kind, name, W, H = case[:4]
+    W, H = case[2:4]
     for rgb in (True, False):
         got, m = _draw_case(pkg, case, split=True, rgb=rgb)
-        tsp._no_difference(got, m, f"{_what(case)}, out_rgb {'given' if rgb else 'NULL'}", rgb=rgb)
+        sh.same(got, m, f"{_what(case)}, out_rgb {'given' if rgb else 'NULL'}", split=True, rgb=rgb)
     assert (m["I"] > 0).any()
-    d, i = torch.from_numpy(got["D"]).cuda(), torch.from_numpy(got["I"]).cuda()
-    tex = torch.from_numpy(np.ascontiguousarray(got["gb"]).view(np.uint8).reshape(-1).copy()).cuda()
-    out = torch.empty((H, W, 3), dtype=torch.float32, device="cuda")
-    pkg.trace_compose(out, d, i, tex, W, H)
-    torch.cuda.synchronize()
     want = splm.compose((m["gb"]["albedo"] * m["gb"]["ialbedo"]).astype(F), m["D"], m["I"])
-    assert not differing(out.cpu().numpy(), want).any(), "albedo * (D + I) through svgf_trace_compose"
+    assert not differing(sh.compose_on_device(pkg, got, W, H), want).any(), "albedo * (D + I) through svgf_trace_compose"
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", ["B", "F_cube"])
 def test_depth_one_is_the_other_libraries_on_bits(pkg, name):
     W, H, J = 67, 41, 3
-    s = tss._edge(name)[0]
-    lt = tts._model("edge", name, W, H, J)[2]
-    scene = trs._create(pkg, s)
-    traced = tts._draw(pkg, scene, W, H, s, lt, J)
-    split = tsp._draw_split(pkg, scene, W, H, s, lt, J)
+    s = sh.edge(name)[0]
+    lt = sh.traced_model("edge", name, W, H, J)[2]
+    scene = sh.create(pkg, s)
+    traced = sh.draw(pkg, sh.TRACED, scene, W, H, s, lt, sh.trace_args(J))
+    split = sh.draw(pkg, sh.TRACED, scene, W, H, s, lt, sh.trace_args(J), split=True)
     for R in (0, 2):
-        tts._no_difference(_draw(pkg, scene, W, H, s, lt, J, 1, R), traced, f"scene {name}: max_depth 1, rr_depth {R} vs svgf_trace_draw")
-        tsp._no_difference(_draw_split(pkg, scene, W, H, s, lt, J, 1, R), split, f"scene {name}: max_depth 1, rr_depth {R} vs svgf_trace_draw_split")
-    lt3 = tss._model("edge", name, W, H, 3)[2]
-    shadowed = tss._draw(pkg, scene, W, H, s, lt3)
-    tts._no_difference(_draw(pkg, scene, W, H, s, lt3, 0, 4, 2), shadowed, f"scene {name}: paths 0, ambient 0.15 vs svgf_scene_draw_shadowed")
+        sh.same(sh.draw(pkg, sh.PATH, scene, W, H, s, lt, sh.path_args(J, 1, R)), traced, f"scene {name}: max_depth 1, rr_depth {R} vs svgf_trace_draw")
+        sh.same(sh.draw(pkg, sh.PATH, scene, W, H, s, lt, sh.path_args(J, 1, R), split=True), split, f"scene {name}: max_depth 1, rr_depth {R} vs svgf_trace_draw_split",
+                split=True)
+    lt3 = sh.shadow_model("edge", name, W, H, 3)[2]
+    shadowed = sh.draw(pkg, sh.SHADOWED, scene, W, H, s, lt3)
+    sh.same(sh.draw(pkg, sh.PATH, scene, W, H, s, lt3, sh.path_args(0, 4, 2)), shadowed, f"scene {name}: paths 0, ambient 0.15 vs svgf_scene_draw_shadowed")
     scene.free()
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("case", TREES, ids=lambda c: c[1])
 def test_every_tree_draws_the_same_deep_frame(pkg, case):
-    kind, name, W, H, J, K, R, sec, point = case
     m = _case_model(case)
-    s = _input(kind, name)[0]
-    for ml, sp in BUILDS:
-        scene = trs._create(pkg, s, ml, sp)
-        got = _draw(pkg, scene, W, H, s, m["lt"], J, K, R, sec, frame=m["frame"], seed=m["seed"])
-        scene.free()
-        _same(got, m, f"{name}, leaf {ml} split {sp}")
+    sh.check_every_tree(pkg, sh.PATH, _bound(case, m), m, case[1])
 
 
 @functools.lru_cache(maxsize=None)
 def _block_model(f, W, H, J, K, R, posed=True, noise=0.6):
     """Frame f of f15's turning block under f16's area light: the model on the posed arrays (posed=False: the scene as uploaded)."""
-    s, tables = tas._block_inputs()
+    s, tables = sh.block_inputs()
     ps = pm.posed_scene(s, tables[f]) if posed else s
-    lk = tss._block_light()
+    lk = sh.block_light()
     lt = ssm.light(lk["centre"], lk["edge_u"], lk["edge_v"], 1)
     col, gb, D, I, info = spm.render(W, H, f, ps["cam"], ps["geoms"], None, None, None, None, None, None, lt, spm.params(J, K, R), seed=3,      # noqa: E741
                                      noise=noise, fireflies=0.02 if noise else 0.0)
@@ -585,17 +411,18 @@ def _block_model(f, W, H, J, K, R, posed=True, noise=0.6):
 @pytest.mark.gpu
 def test_the_paths_follow_the_pose(pkg):
     W, H, J, K, R = BLOCK[0]
-    s, tables = tas._block_inputs()
-    scene = trs._create(pkg, s)
+    s, tables = sh.block_inputs()
+    scene = sh.create(pkg, s)
     m = _block_model(0, W, H, J, K, R, posed=False)
-    _same(_draw(pkg, scene, W, H, s, m["lt"], J, K, R, frame=0, seed=3), m, "turning block, before any pose")
+    sh.same(sh.draw(pkg, sh.PATH, scene, W, H, s, m["lt"], sh.path_args(J, K, R), frame=0, seed=3), m, "turning block, before any pose")
     scene.enable_pose(len(s["geoms"]))
     ind = []
     for f in (0, 2):
         m = _block_model(f, W, H, J, K, R)
-        scene.pose(tas._dev(tables[f]))
-        _same(_draw(pkg, scene, W, H, s, m["lt"], J, K, R, frame=f, seed=3), m, f"turning block, pose {f}")
-        tsp._no_difference(_draw_split(pkg, scene, W, H, s, m["lt"], J, K, R, frame=f, seed=3), m, f"turning block, pose {f}, split form")
+        scene.pose(sh.dev(tables[f]))
+        sh.same(sh.draw(pkg, sh.PATH, scene, W, H, s, m["lt"], sh.path_args(J, K, R), frame=f, seed=3), m, f"turning block, pose {f}")
+        sh.same(sh.draw(pkg, sh.PATH, scene, W, H, s, m["lt"], sh.path_args(J, K, R), split=True, frame=f, seed=3), m, f"turning block, pose {f}, split form",
+                split=True)
         ind.append(m["info"]["ind"])
     scene.free()
     assert int((ind[0] != ind[1]).any(axis=-1).sum()) > 50
@@ -603,72 +430,26 @@ def test_the_paths_follow_the_pose(pkg):
 
 @pytest.mark.gpu
 def test_eight_path_draws_queued_without_host_waits(pkg):
-    import torch
-    kind, name, W, H, J, K, R, sec, point = QUEUED
-    s = _input(kind, name)[0]
-    scene = trs._create(pkg, s)
-    st = tsp._OwnStream()
-    bufs = [trs._buffers(W, H) for _ in range(8)]
-    torch.cuda.synchronize()
-    lt = _case_model(QUEUED)["lt"]
-    for f, b in enumerate(bufs):
-        _draw(pkg, scene, W, H, s, lt, J, K, R, sec, frame=f, stream=st, bufs=b, sync=False)
-    st.close()
-    for f, (rgb, gbt) in enumerate(bufs):
-        _same(trs._host(pkg, rgb, gbt, W, H), _case_model(QUEUED, frame=f), f"queued path draw, frame {f}")
-    scene.free()
+    sh.check_queued(pkg, sh.PATH, _bound(QUEUED, _case_model(QUEUED)), lambda f: _case_model(QUEUED, frame=f), "queued path draw")
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("split", [False, True])
 def test_a_captured_path_draw_is_one_kernel_node_and_replays_the_same_bits(pkg, split):
-    import torch
-    hip = tas._graph_api()
-    kind, name, W, H, J, K, R, sec, point = QUEUED
-    s = _input(kind, name)[0]
     m = _case_model(QUEUED)
-    scene = trs._create(pkg, s)
-    st = tsp._OwnStream()
-    b = tsp._split_buffers(W, H) if split else trs._buffers(W, H)
-    torch.cuda.synchronize()
-    draw = (lambda: _draw_split(pkg, scene, W, H, s, m["lt"], J, K, R, sec, stream=st, bufs=b, sync=False)) if split else \
-        (lambda: _draw(pkg, scene, W, H, s, m["lt"], J, K, R, sec, stream=st, bufs=b, sync=False))
-    draw()                                  # eager first: a first launch may set kernel attributes
-    st.synchronize()
-    graph, gexec = ctypes.c_void_p(), ctypes.c_void_p()
-    assert hip.hipStreamBeginCapture(st.cuda_stream, 2) == 0
-    draw()                                  # recorded, not executed
-    assert hip.hipStreamEndCapture(st.cuda_stream, ctypes.byref(graph)) == 0 and graph.value
-    types = tas._node_types(hip, graph)
-    assert hip.hipGraphInstantiate(ctypes.byref(gexec), graph, None, None, 0) == 0
-    with torch.cuda.stream(st.torch):
-        for t in (b.values() if split else b):
-            t.zero_()
-    assert hip.hipGraphLaunch(gexec, st.cuda_stream) == 0
-    st.synchronize()
-    got = tsp._split_host(pkg, b, W, H) if split else trs._host(pkg, *b, W, H)
-    hip.hipGraphExecDestroy(gexec); hip.hipGraphDestroy(graph)
-    st.close()
-    scene.free()
-    print(f"captured path draw (split {split}) = node types {types}")
-    assert types == [0], types
-    if split:
-        tsp._no_difference(got, m, "replayed split path draw")
-    else:
-        _same(got, m, "replayed path draw")
+    sh.check_captured(pkg, sh.PATH, _bound(QUEUED, m), m, "path draw", split=split)
 
 
 @pytest.mark.gpu
 def test_every_error_code_of_both_calls(pkg):
     import torch
     B = pkg.binding
-    s = tss._edge("B")[0]
-    scene = trs._create(pkg, s)
+    s = sh.edge("B")[0]
+    scene = sh.create(pkg, s)
     lib = pkg.load_path_library()
-    cam, sp, planes = B.SvgfCamera(), B.SvgfSynthParams(), B.SvgfPlanarGBuffer()
+    c, p = ctypes.byref(B.SvgfCamera()), ctypes.byref(B.SvgfSynthParams())
     ok = ctypes.byref(B.SvgfSceneLight.make((0, 1, 0), (1, 0, 0), (0, 0, 1), 4))
     pp = ctypes.byref(B.SvgfPathParams(1, 4, 2, 0.15, 1))
-    c, p = ctypes.byref(cam), ctypes.byref(sp)
     guard = torch.full((64,), 7.0, dtype=torch.float32, device="cuda")       # every pointer below is this buffer: a refused call writes nothing
     a = guard.data_ptr()
     plain = lambda h=scene.h, rgb=a, gb=a, pl=None, w=1, hh=1, cm=c, spp=p, lt=ok, t=pp: lib.svgf_path_draw(h, rgb, gb, pl, w, hh, cm, spp, lt, t, None)  # noqa: E731
@@ -677,22 +458,13 @@ def test_every_error_code_of_both_calls(pkg):
     assert plain(rgb=None) == -1
     assert split(d=None) == -1 and split(i=None) == -1 and split(d=a, i=a) == -1
     for f in (plain, split):
-        assert f(h=None) == -1 and f(w=0) == -1 and f(hh=-1) == -1 and f(cm=None) == -1 and f(spp=None) == -1 and f(lt=None) == -1 and f(t=None) == -1
-        assert f(gb=None) == -1 and f(pl=ctypes.byref(planes)) == -1 and f(gb=None, pl=ctypes.byref(planes)) == -1
-        assert f(w=1 << 14, hh=1 << 13) == -5
-        for n in (0, 65):
-            assert f(lt=ctypes.byref(B.SvgfSceneLight.make((0, 1, 0), samples=n))) == -1
-        bad_light = B.SvgfSceneLight.make((0, 1, 0), samples=1)
-        bad_light.edge_v[2] = float("nan")
-        assert f(lt=ctypes.byref(bad_light)) == -1
-        for bad in BAD_PARAMS:
-            assert f(t=ctypes.byref(B.SvgfPathParams(*bad))) == -1, bad
+        sh.check_common_refusals(B, f, (B.SvgfPathParams, sh.BAD_PARAMS))
     torch.cuda.synchronize()
     assert (guard.cpu().numpy() == F(7.0)).all()
     case = ("edge", "B", 7, 5, 2, 3, 2, 1, False)
     m = _case_model(case)
-    _same(_draw(pkg, scene, 7, 5, s, m["lt"], 2, 3, 2), m, "after the refused calls")
-    tsp._no_difference(_draw_split(pkg, scene, 7, 5, s, m["lt"], 2, 3, 2), m, "after the refused calls, split form")
+    sh.same(sh.draw(pkg, sh.PATH, scene, 7, 5, s, m["lt"], sh.path_args(2, 3, 2)), m, "after the refused calls")
+    sh.same(sh.draw(pkg, sh.PATH, scene, 7, 5, s, m["lt"], sh.path_args(2, 3, 2), split=True), m, "after the refused calls, split form", split=True)
     scene.free()
 
 
@@ -703,55 +475,6 @@ def test_pose_split_path_draw_two_denoises_compose_sequence(pkg, orc):
     bounce 2, 1 shadow ray) -> svgf_denoise of each term in a context of its own (temporal pass, sepcolor 1 / addcolor 0, the object
     motion table on; the f8 firefly filter on the indirect context only) -> svgf_trace_compose.  Each context against
     tests/temporal_model.py behind tests/firefly_model.py, the composed image against compose() of the two outputs, all on bits."""
-    import torch
-    import firefly_model as fm
-    import temporal_model as tm
-    from temporal_harness import assert_frames_equal, read_states, scales, synth_params
     (W, H, J, K, R), N = BLOCK[1], 4
-    s, tables = tas._block_inputs()
-    tables = tables[:N]
-    n = len(s["geoms"])
-    held, frames, motion = pkg.binding.pose_identity(n), [], []
-    for f, t in enumerate(tables):
-        frames.append(_block_model(f, W, H, J, K, R))
-        motion.append(pm.motion_rows(held, t))
-        held = t
-    lt = frames[0]["lt"]
-    M = orc.view_matrix(pkg, s["cam"])
-    p = synth_params(pkg, W, H, sepcolor=1, addcolor=0)
-    RANK, SCALE = 2, 1.0
-    want = {}
-    for key, rank in (("D", 0), ("I", RANK)):
-        fed = [(fm.firefly_filter(np.asarray(m[key], F).reshape(H, W, 3), rank, SCALE), m["gb"].reshape(H, W)) for m in frames]
-        want[key] = tm.run_sequence(fed, tables=motion, views=[M] * N, scale=scales(pkg, W, H), radius=0, k=0.0)
-    scene = trs._create(pkg, s)
-    scene.enable_pose(n)
-    dens = {"D": pkg.Denoiser(W, H), "I": pkg.Denoiser(W, H)}
-    t_x = tas._motion_buffer(n)
-    for key, den in dens.items():
-        den.set_capture(True)
-        den.set_object_motion(t_x)
-        den.set_firefly_filter(RANK if key == "I" else 0, SCALE)
-    b = tsp._split_buffers(W, H, rgb=False)
-    outs = {k: torch.empty((H, W, 3), dtype=torch.float32, device="cuda") for k in ("D", "I", "C")}
-    got = {"D": [], "I": []}
-    try:
-        for f, t in enumerate(tables):
-            scene.pose(tas._dev(t), t_x)
-            _draw_split(pkg, scene, W, H, s, lt, J, K, R, frame=f, seed=3, bufs=b, sync=False)
-            for key, den in dens.items():
-                den.denoise(outs[key], b[key], b["gb"], s["cam"], p)
-            pkg.trace_compose(outs["C"], outs["D"], outs["I"], b["gb"], W, H)
-            torch.cuda.synchronize()
-            for key, den in dens.items():
-                got[key].append(read_states(den))
-            h = {k: v.cpu().numpy() for k, v in outs.items()}
-            gb = frames[f]["gb"]
-            comp = splm.compose((gb["albedo"] * gb["ialbedo"]).astype(F), h["D"], h["I"])
-            assert not differing(h["C"], comp).any(), f"frame {f}: the composed image"
-    finally:
-        for den in dens.values():
-            den.free()
-        scene.free()
-    assert_frames_equal(got["D"], want["D"], "direct context")
-    assert_frames_equal(got["I"], want["I"], "indirect context")
+    sh.run_split_denoise_compose(pkg, orc, sh.PATH, [_block_model(f, W, H, J, K, R) for f in range(N)], W, H, sh.path_args(J, K, R),
+                                 ("direct context", "indirect context"), form="filtered")

@@ -13,86 +13,27 @@ evenly early enough, never by a larger leaf.
 """
 import ctypes
 import functools
-import os
 
 import numpy as np
 import pytest
 
 import resident_scene_model as rm
+import scene_harness as sh
 import scene_model as sm
 import test_scene_model as tsm
-from test_scene_model import FRAME, REF_DIR, SEED, cap, counts
+from test_scene_model import FRAME, SEED, cap, counts
 
 F = np.float32
-BUILDS = [(ml, sp) for ml in (1, 4, 8) for sp in (0, 1)]
 EDGE_WITH_TRIS = ("A", "B", "C", "D", "F_cube", "F_sphere")
-RECORDED = {"cornell": "cornell96_static", "room": "room128x72_static_sepcolor", "bunny": "bunny128x72_static"}
-
-
-# ---- inputs ------------------------------------------------------------------------------------------------------------------------------
-@functools.lru_cache(maxsize=None)
-def _recorded(scene, f):
-    """A recorded reference scene at frame f of its recorded cameras, as the dict the edge scenes use, and its frame size."""
-    import __graft_entry__ as ge
-    pkg = ge.load_package()
-    z = np.load(os.path.join(REF_DIR, RECORDED[scene] + ".npz"))
-    pi = np.load(os.path.join(REF_DIR, scene + "_producer_inputs.npz"))
-    textures = [pi[k] for k in sorted(pi.files) if k.startswith("texture") and k != "textured_objects"] if "tri_tex" in pi.files else None
-    s = dict(cam=tsm._recorded_cam(z, f, pi["fovy"]), geoms=pi["geoms"], geom_ids=pi["geom_ids"], tris=pi["tris"], tri_ids=pi["tri_ids"],
-             tri_albedo=pi["tri_albedo"], tri_tex=pi["tri_tex"] if textures else None, textures=textures, light=pkg.scene.light_position(pi["geoms"]))
-    return s, int(z["W"]), int(z["H"])
-
-
-def _tri_rows(p0, p1, p2):
-    t = np.zeros((3, 8), F)
-    t[:, 0:3] = np.array([p0, p1, p2], F)
-    return t
-
-
-@functools.lru_cache(maxsize=None)
-def _tri_set(name):
-    """float32[n, 3, 8]: the recorded meshes, scene A and the adversarial sets of the builder test."""
-    if name in RECORDED:
-        return _recorded(name, 0)[0]["tris"]
-    if name == "A":
-        return tsm._scene("A")["tris"]
-    one = _tri_rows((0, 0, 0), (1, 0, 0), (0, 1, 0.5))
-    rng = np.random.default_rng(14)
-    if name == "one":
-        return one[None]
-    if name == "none":
-        return np.zeros((0, 3, 8), F)
-    if name == "copies300":
-        return np.repeat(one[None], 300, axis=0)
-    if name == "zero_area257":      # every triangle a point; all on one point but the last few, which are points elsewhere
-        pts = np.concatenate([np.zeros((250, 3), F), rng.uniform(-1, 1, (7, 3)).astype(F)])
-        t = np.zeros((257, 3, 8), F)
-        t[:, :, 0:3] = pts[:, None, :]
-        return t
-    if name == "huge_over_500":
-        c = rng.uniform(-1, 1, (500, 1, 3)).astype(F)
-        small = np.zeros((500, 3, 8), F)
-        small[:, :, 0:3] = c + rng.uniform(-0.01, 0.01, (500, 3, 3)).astype(F)
-        return np.concatenate([_tri_rows((-1000, -1000, 0), (1000, -1000, 0), (0, 1000, 0))[None], small])
-    if name == "line4096":
-        t = np.zeros((4096, 3, 8), F)
-        x = np.arange(4096, dtype=F)[:, None]
-        t[:, :, 0] = x + np.array([0, 0.5, 0.25], F)
-        t[:, :, 1] = np.array([0, 0, 0.5], F)
-        return t
-    raise KeyError(name)
-
-
-TRI_SETS = ("room", "bunny", "cornell", "A", "one", "none", "copies300", "zero_area257", "huge_over_500", "line4096")
 
 
 # ---- CPU 1: the builder ----------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name", TRI_SETS)
+@pytest.mark.parametrize("name", sh.TRI_SETS)
 def test_builder_invariants(pkg, name):
-    tris = _tri_set(name)
+    tris = sh.tri_set(name)
     n = len(tris)
     lo, hi = rm.padded_boxes(tris)
-    for ml, sp in BUILDS:
+    for ml, sp in sh.BUILDS:
         nodes, order, depth = pkg.bvh_build_host(tris, ml, sp)
         again = pkg.bvh_build_host(tris, ml, sp)
         assert nodes.tobytes() == again[0].tobytes() and np.array_equal(order, again[1]) and depth == again[2], "two builds differ"
@@ -130,17 +71,17 @@ def test_builder_reorders_scene_A_duplicates(pkg):
     """Scene A stores one triangle twice (indices 5 and 6).  At least one of the six builds places index 6 before 5, so the draw's
     'lowest index wins a tie' (GPU test below) is decided by the draw and not by the builder's order."""
     flipped = []
-    for ml, sp in BUILDS:
-        order = pkg.bvh_build_host(_tri_set("A"), ml, sp)[1].tolist()
+    for ml, sp in sh.BUILDS:
+        order = pkg.bvh_build_host(sh.tri_set("A"), ml, sp)[1].tolist()
         flipped.append(order.index(6) < order.index(5))
-    print("index 6 before 5 per build:", dict(zip(BUILDS, flipped)))
+    print("index 6 before 5 per build:", dict(zip(sh.BUILDS, flipped)))
     assert any(flipped)
 
 
 # ---- CPU 2: the gate precondition of every input the GPU part draws ------------------------------------------------------------------------
 @functools.lru_cache(maxsize=None)
 def _gate(kind, name, f, W, H):
-    s = tsm._scene(name) if kind == "edge" else _recorded(name, f)[0]
+    s = tsm._scene(name) if kind == "edge" else sh.recorded(name, f)[0]
     return rm.gate_report(W, H, s["cam"], s["tris"])
 
 
@@ -171,7 +112,7 @@ def test_axis_parallel_rays_take_the_flat_branch():
 def test_argument_errors(pkg):
     lib = pkg.load_library()
     B = pkg.binding
-    tris = np.ascontiguousarray(_tri_set("A"), F).reshape(-1, 24)
+    tris = np.ascontiguousarray(sh.tri_set("A"), F).reshape(-1, 24)
     n = len(tris)
     ids, alb = np.zeros(n, np.int32), np.zeros((n, 3), F)
     h = ctypes.c_void_p()
@@ -207,43 +148,15 @@ def test_argument_errors(pkg):
 
 
 # ---- GPU -------------------------------------------------------------------------------------------------------------------------------
-def _create(pkg, s, ml=0, sp=0):
-    return pkg.Scene.create(s["geoms"], s["geom_ids"], s["tris"], s["tri_ids"], s["tri_albedo"], s["tri_tex"], s["textures"], ml, sp)
-
-
-def _buffers(W, H):
-    import torch
-    return torch.empty((H, W, 3), dtype=torch.float32, device="cuda"), torch.empty((H * W * 52,), dtype=torch.uint8, device="cuda")
-
-
-def _host(pkg, rgb, gbt, W, H):
-    return rgb.cpu().numpy(), gbt.cpu().numpy().view(pkg.synth.GBUFFER_DTYPE).reshape(H, W)
-
-
-def _draw(pkg, scene, W, H, s, frame, seed):
-    import torch
-    rgb, gbt = _buffers(W, H)
-    scene.draw(rgb, gbt, W, H, s["cam"], s["light"], frame, seed=seed)
-    torch.cuda.synchronize()
-    return _host(pkg, rgb, gbt, W, H)
-
-
-def _same(got, ref, W, H, what):
-    c = counts(got, ref)
-    print(f"{what} {W}x{H}: differing pixels {c} (expected 0, cap {cap(W, H)})")
-    for f, k in c.items():
-        assert k <= cap(W, H), f"{what} {W}x{H}: {f} differs on {k} pixels"
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", EDGE_WITH_TRIS + ("E_plus", "G"))
 def test_draw_equals_model_and_mesh_path_on_edge_scene(pkg, name):
     s = tsm._scene(name)
-    scene = _create(pkg, s)
+    scene = sh.create(pkg, s)
     for W, H in tsm.SIZES:
-        got = _draw(pkg, scene, W, H, s, FRAME, SEED)
-        _same(got, tsm._model(name, W, H), W, H, f"scene {name} vs model")
-        _same(got, tsm._device(pkg, W, H, s, FRAME, SEED), W, H, f"scene {name} vs svgf_scene_render_mesh")
+        got = sh.draw_frame(pkg, scene, W, H, s, FRAME, SEED)
+        sh.same_capped(got, tsm._model(name, W, H), W, H, f"scene {name} vs model")
+        sh.same_capped(got, tsm._device(pkg, W, H, s, FRAME, SEED), W, H, f"scene {name} vs svgf_scene_render_mesh")
     assert scene.info()["n_nodes"] == (0 if s["tris"] is None else 2 * scene.info()["n_leaves"] - 1)
     scene.free()
 
@@ -251,27 +164,13 @@ def test_draw_equals_model_and_mesh_path_on_edge_scene(pkg, name):
 @pytest.mark.gpu
 def test_draw_planar_equals_model_on_textures(pkg):
     """Scene C through svgf_scene_draw_planar into a context's planes."""
-    import torch
-    from temporal_harness import _hip
     W, H = tsm.SIZES[0]
     s = tsm._scene("C")
-    scene = _create(pkg, s)
+    scene = sh.create(pkg, s)
     den = pkg.Denoiser(W, H, 0)
-    planes = den.planar_gbuffer()
-    rgb = torch.empty((H, W, 3), dtype=torch.float32, device="cuda")
-    scene.draw_planar(rgb, planes, W, H, s["cam"], s["light"], FRAME, seed=SEED)
-    torch.cuda.synchronize()
-    hip = _hip()
-    hip.hipMemcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
-    gb = np.zeros((H, W), dtype=pkg.synth.GBUFFER_DTYPE)
-    for field, ptr in (("normal", planes.normal), ("position", planes.position), ("albedo", planes.albedo), ("geomId", planes.geom_id)):
-        host = np.zeros((H, W, 3) if field != "geomId" else (H, W), F if field != "geomId" else np.int32)
-        assert hip.hipMemcpy(host.ctypes.data, ptr, host.nbytes, 2) == 0
-        gb[field] = host
-    gb["ialbedo"] = F(1.0)
-    got = (rgb.cpu().numpy(), gb)
-    _same(got, tsm._model("C", W, H), W, H, "scene C planar vs model")
-    _same(got, tsm._device(pkg, W, H, s, FRAME, SEED, planar=True), W, H, "scene C planar vs svgf_scene_render_mesh_planar")
+    got = sh.pair(sh.draw(pkg, sh.RESIDENT, scene, W, H, s, None, planes=den.planar_gbuffer()))
+    sh.same_capped(got, tsm._model("C", W, H), W, H, "scene C planar vs model")
+    sh.same_capped(got, tsm._device(pkg, W, H, s, FRAME, SEED, planar=True), W, H, "scene C planar vs svgf_scene_render_mesh_planar")
     den.free(); scene.free()
 
 
@@ -280,30 +179,30 @@ def test_draw_planar_equals_model_on_textures(pkg):
 def test_draw_equals_model_and_mesh_path_on_recorded_scene(pkg, scene_name, frames):
     """bunny: against svgf_scene_render_mesh only (the numpy frame over 4 968 triangles is what would make this slow; its gate
     precondition is test_gate_precondition's)."""
-    scene = _create(pkg, _recorded(scene_name, 0)[0])
+    scene = sh.create(pkg, sh.recorded(scene_name, 0)[0])
     for f in frames:
-        s, W, H = _recorded(scene_name, f)
-        got = _draw(pkg, scene, W, H, s, f, 1)
+        s, W, H = sh.recorded(scene_name, f)
+        got = sh.draw_frame(pkg, scene, W, H, s, f, 1)
         if scene_name != "bunny":
-            _same(got, tsm._recorded_model(RECORDED[scene_name], scene_name, f), W, H, f"{scene_name} frame {f} vs model")
+            sh.same_capped(got, tsm._recorded_model(sh.RECORDED[scene_name], scene_name, f), W, H, f"{scene_name} frame {f} vs model")
         ref = tsm._device(pkg, W, H, s, f, 1)
         assert np.isin(ref[1]["geomId"], np.unique(s["tri_ids"])).mean() > 0.01, "the scene's meshes should be in the picture"
-        _same(got, ref, W, H, f"{scene_name} frame {f} vs svgf_scene_render_mesh")
+        sh.same_capped(got, ref, W, H, f"{scene_name} frame {f} vs svgf_scene_render_mesh")
     scene.free()
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", ["room", "A"])
 def test_every_tree_draws_the_same_frame(pkg, name):
-    (s, W, H) = _recorded("room", 0) if name == "room" else (tsm._scene("A"), 67, 41)
+    (s, W, H) = sh.recorded("room", 0) if name == "room" else (tsm._scene("A"), 67, 41)
     frames, infos = [], []
-    for ml, sp in BUILDS:
-        scene = _create(pkg, s, ml, sp)
-        frames.append(_draw(pkg, scene, W, H, s, FRAME, SEED))
+    for ml, sp in sh.BUILDS:
+        scene = sh.create(pkg, s, ml, sp)
+        frames.append(sh.draw_frame(pkg, scene, W, H, s, FRAME, SEED))
         infos.append(scene.info())
         scene.free()
     assert len({(i["n_nodes"], i["depth"]) for i in infos}) >= 4, "the builds should differ in shape"
-    for (ml, sp), fr in zip(BUILDS[1:], frames[1:]):
+    for (ml, sp), fr in zip(sh.BUILDS[1:], frames[1:]):
         c = counts(fr, frames[0])
         assert not any(c.values()), f"leaf {ml} split {sp} differs from leaf 1 split 0: {c}"
 
@@ -316,15 +215,15 @@ def test_ties_lowest_index_and_primitive_win(pkg):
     A, B = tsm._scene("A"), tsm._scene("B")
     want = tsm._model("A", W, H)[1]["geomId"]
     assert (want == 14).sum() > cap(W, H) and not (want == 15).any()
-    for ml, sp in BUILDS:
-        scene = _create(pkg, A, ml, sp)
-        gid = _draw(pkg, scene, W, H, A, FRAME, SEED)[1]["geomId"]
+    for ml, sp in sh.BUILDS:
+        scene = sh.create(pkg, A, ml, sp)
+        gid = sh.draw_frame(pkg, scene, W, H, A, FRAME, SEED)[1]["geomId"]
         scene.free()
         assert np.array_equal(gid, want), f"leaf {ml} split {sp}: {int((gid != want).sum())} pixels, {int((gid == 15).sum())} show the copy"
     ref, le = tsm._model("B", W, H)[1]["geomId"], tsm._model("B", W, H, "tri_le")[1]["geomId"]
     assert ((le == 9) & (ref == 7)).sum() > cap(W, H), "scene B should hold a tie between triangle 2 and the cube"
-    scene = _create(pkg, B)
-    gid = _draw(pkg, scene, W, H, B, FRAME, SEED)[1]["geomId"]
+    scene = sh.create(pkg, B)
+    gid = sh.draw_frame(pkg, scene, W, H, B, FRAME, SEED)[1]["geomId"]
     scene.free()
     assert np.array_equal(gid, ref)
 
@@ -334,51 +233,40 @@ def test_eight_draws_queued_without_host_waits(pkg):
     import torch
     W, H = 67, 41
     s = tsm._scene("A")
-    scene = _create(pkg, s)
+    scene = sh.create(pkg, s)
     st = torch.cuda.Stream()
-    bufs = [_buffers(W, H) for _ in range(8)]
+    bufs = [sh.buffers(W, H) for _ in range(8)]
     for f, (rgb, gbt) in enumerate(bufs):
         scene.draw(rgb, gbt, W, H, s["cam"], s["light"], f, seed=SEED, stream=st)
     st.synchronize()
     for f, (rgb, gbt) in enumerate(bufs):
         ref = sm.render(W, H, f, s["cam"], s["geoms"], s["geom_ids"], s["tris"], s["tri_ids"], s["tri_albedo"], None, None, s["light"], seed=SEED)
-        _same(_host(pkg, rgb, gbt, W, H), ref, W, H, f"queued draw, frame {f}")
+        sh.same_capped(sh.host(pkg, rgb, gbt, W, H), ref, W, H, f"queued draw, frame {f}")
     scene.free()
 
 
 @pytest.mark.gpu
 def test_a_captured_draw_replays_the_same_bits(pkg):
     import torch
-    from temporal_harness import _hip
-    hip = _hip()
     W, H = 67, 41
     s = tsm._scene("B")
-    scene = _create(pkg, s)
+    scene = sh.create(pkg, s)
     st = torch.cuda.Stream()
-    rgb, gbt = _buffers(W, H)
-    scene.draw(rgb, gbt, W, H, s["cam"], s["light"], FRAME, seed=SEED, stream=st)      # eager first: a first launch may set kernel attributes
+    rgb, gbt = sh.buffers(W, H)
+    record = lambda: scene.draw(rgb, gbt, W, H, s["cam"], s["light"], FRAME, seed=SEED, stream=st)      # noqa: E731
+    record()                                # eager first: a first launch may set kernel attributes
     st.synchronize()
-    want = _host(pkg, rgb, gbt, W, H)
-    graph, gexec = ctypes.c_void_p(), ctypes.c_void_p()
-    hip.hipStreamBeginCapture.argtypes = [ctypes.c_void_p, ctypes.c_int]
-    hip.hipStreamEndCapture.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)]
-    hip.hipGraphInstantiate.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]
-    hip.hipGraphLaunch.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
-    hip.hipGraphExecDestroy.argtypes = [ctypes.c_void_p]
-    hip.hipGraphDestroy.argtypes = [ctypes.c_void_p]
-    assert hip.hipStreamBeginCapture(st.cuda_stream, 2) == 0            # hipStreamCaptureModeRelaxed
-    scene.draw(rgb, gbt, W, H, s["cam"], s["light"], FRAME, seed=SEED, stream=st)      # recorded, not executed
-    assert hip.hipStreamEndCapture(st.cuda_stream, ctypes.byref(graph)) == 0 and graph.value
-    assert hip.hipGraphInstantiate(ctypes.byref(gexec), graph, None, None, 0) == 0
+    want = sh.host(pkg, rgb, gbt, W, H)
+    graph = sh.Captured(st, record)         # recorded, not executed
     with torch.cuda.stream(st):
         rgb.zero_(); gbt.zero_()
-    assert hip.hipGraphLaunch(gexec, st.cuda_stream) == 0
+    graph.launch()
     st.synchronize()
-    got = _host(pkg, rgb, gbt, W, H)
-    hip.hipGraphExecDestroy(gexec); hip.hipGraphDestroy(graph)
+    got = sh.host(pkg, rgb, gbt, W, H)
+    graph.destroy()
     scene.free()
     assert (got[1]["geomId"] >= 0).any() and not any(counts(got, want).values())
-    _same(got, tsm._model("B", W, H), W, H, "replayed draw vs model")
+    sh.same_capped(got, tsm._model("B", W, H), W, H, "replayed draw vs model")
 
 
 @pytest.mark.gpu
@@ -390,14 +278,14 @@ def test_draws_feed_a_denoise_sequence_on_one_stream(pkg):
     st = torch.cuda.Stream()
     p = pkg.reference_defaults().set(temporal_enable=1, spatial_enable=1)
     outs = {}
-    scene = _create(pkg, _recorded("cornell", 0)[0])
+    scene = sh.create(pkg, sh.recorded("cornell", 0)[0])
     for path in ("draw", "mesh"):
-        s0, W, H = _recorded("cornell", 0)
+        s0, W, H = sh.recorded("cornell", 0)
         den = pkg.Denoiser(W, H, 0)
-        rgb, gbt = _buffers(W, H)
+        rgb, gbt = sh.buffers(W, H)
         out = [torch.empty((H, W, 3), dtype=torch.float32, device="cuda") for _ in range(N)]
         for f in range(N):
-            s = _recorded("cornell", f)[0]
+            s = sh.recorded("cornell", f)[0]
             if path == "draw":
                 scene.draw(rgb, gbt, W, H, s["cam"], s["light"], f, stream=st)
             else:
@@ -416,9 +304,9 @@ def test_draws_feed_a_denoise_sequence_on_one_stream(pkg):
 @pytest.mark.gpu
 def test_scene_info_and_draw_argument_errors(pkg):
     B = pkg.binding
-    s = _recorded("cornell", 0)[0]
+    s = sh.recorded("cornell", 0)[0]
     for ml, sp in ((0, 0), (1, 1), (8, 0)):
-        scene = _create(pkg, s, ml, sp)
+        scene = sh.create(pkg, s, ml, sp)
         nodes, order, depth = pkg.bvh_build_host(s["tris"], ml, sp)
         i = scene.info()
         print(f"cornell leaf {ml} split {sp}: {i}")
@@ -426,7 +314,7 @@ def test_scene_info_and_draw_argument_errors(pkg):
         assert (i["n_nodes"], i["n_leaves"], i["depth"], i["max_leaf_tris"]) == (len(nodes), int((nodes["count"] > 0).sum()), depth, ml or 4)
         assert i["device_bytes"] >= s["tris"].nbytes + nodes.nbytes + order.nbytes + s["textures"][0].nbytes
         scene.free()
-    scene = _create(pkg, s)
+    scene = sh.create(pkg, s)
     lib = scene.lib
     cam, sp_, light = B.SvgfCamera(), B.SvgfSynthParams(), (ctypes.c_float * 3)()
     args = (ctypes.byref(cam), ctypes.byref(sp_), light, None)

@@ -19,142 +19,22 @@ import subprocess
 import numpy as np
 import pytest
 
-import scene_gloss_model as gm
+import scene_harness as sh
+import scene_path_model as spm
 import scene_pose_model as pm
 import scene_rough_model as rm
+import scene_shadow_model as ssm
 import scene_split_model as splm
 import scene_virtual_model as vm
-import temporal_model as tm
-import test_animated_scene as tas
-import test_gloss_scene as tgs
-import test_path_scene as tps
-import test_resident_scene as trs
-import test_shadowed_scene as tss
-import test_split_scene as tsp
-import test_virtual_scene as tvs
 from conftest import ROOT
-from test_scene_model import FRAME, SEED, differing
+from test_scene_model import differing
 
 F = np.float32
-SIZES = tsp.SIZES
-W0, H0 = tgs.W0, tgs.H0
-GREY = (0.9, 0.9, 0.9)
-
-
-# ---- inputs ------------------------------------------------------------------------------------------------------------------------------
-@functools.lru_cache(maxsize=None)
-def _rough_floor():
-    """The f16 room with its diffuse block; the floor (id 0) is a full mirror (the case's roughness makes it rough)."""
-    import __graft_entry__ as ge
-    s, lk = tgs._room(ge.load_package())
-    return s, lk, gm.table(6, g0=(1.0, 0.0, 1.0, GREY))
-
-
-@functools.lru_cache(maxsize=None)
-def _rough_sphere():
-    """test_gloss_scene's glass pair (ids 5 and 6) with a full-mirror sphere (id 7) between and in front of them."""
-    import __graft_entry__ as ge
-    pkg = ge.load_package()
-    s, lk = tgs._room(pkg, (1, (-2.2, 1.7, 0.0), (0, 0, 0), (3, 3, 3), (0.95, 0.95, 0.95), 0.0), (0, (2.2, 1.7, 0.0), (0, 30, 0), (3, 3, 3), (0.9, 0.95, 1.0), 0.0),
-                     (1, (0.0, 1.2, 2.5), (0, 0, 0), (2, 2, 2), (0.95, 0.95, 0.95), 0.0), block=False)
-    return s, lk, gm.table(8, g5=(0.0, 1.0, 1.5, (0.9, 0.8, 0.7)), g6=(0.0, 1.0, 1.5, (0.7, 0.8, 0.9)), g7=(1.0, 0.0, 1.0, GREY))
-
-
-@functools.lru_cache(maxsize=None)
-def _floor_from_above():
-    """The rough floor seen straight down from (0, 6, 0): the ray of the central pixel of an odd-sized frame is the view direction
-    (0, -1, 0) itself, so that there v is the floor's normal, Vh has no tangential part and T1 is the degenerate tangent's (1, 0, 0)."""
-    s, lk, tab = _rough_floor()
-    cam = dict(s["cam"], right=np.array([1, 0, 0], F), up=np.array([0, 0, -1], F), view=np.array([0, -1, 0], F), position=np.array([0, 6, 0], F))
-    return dict(s, cam=cam), lk, tab
-
-
-@functools.lru_cache(maxsize=None)
-def _cornell_rough():
-    """The recorded cornell with scene.surface_table's and scene.roughness_table's tables of its own file."""
-    import __graft_entry__ as ge
-    pkg = ge.load_package()
-    return tuple(float(a) for a in pkg.scene.roughness_table(pkg.scene.parse_scene(tgs._scene_text("cornell"))))
-
-
-for _name, _f in (("rough_floor", _rough_floor), ("rough_sphere", _rough_sphere), ("floor_from_above", _floor_from_above), ("mirror_hall", tvs._mirror_hall)):
-    tgs.INPUTS.setdefault(_name, _f)          # so that test_gloss_scene._first (and its cache) serves these inputs too
-
-
-def _mesh_rough():
-    tab = tgs._mirror_mesh()[2]
-    return tuple(0.25 if r > 0 else 0.0 for r in tab["reflect"])
-
-
-# (name, W, H, paths, max_depth, rr_depth, shadow_secondary, point light), the roughness per object id, guide_alpha, max_chain, id_offset
-def _rc(name, J, K, R, rough, ga, mc=4, off=0, W=W0, H=H0, point=False):
-    return ((name, W, H, J, K, R, 1, point), tuple(rough) if not callable(rough) else rough, ga, mc, off)
-
-
-RCASES = [_rc("rough_floor", 1, 4, 2, (0.1,), 0.0), _rc("rough_floor", 3, 2, 0, (0.5,), 0.3), _rc("rough_floor", 3, 4, 2, (0.1,), 0.3, 4, 100),
-          _rc("rough_floor", 1, 1, 0, (0.5,), 1.0), _rc("mirror_partial", 3, 4, 2, (0.3, 0.2), 0.3, point=True), _rc("mirror_partial", 1, 2, 0, (0.3, 0.2), 0.0),
-          _rc("mirror_mesh", 3, 4, 2, _mesh_rough, 1.0), _rc("rough_sphere", 3, 4, 2, (0, 0, 0, 0, 0, 0.4, 0.4, 0.2), 0.3, 8),
-          _rc("rough_sphere", 1, 2, 0, (0, 0, 0, 0, 0, 0.4, 0.4, 0.2), 0.0, 8, 100), _rc("mirror_hall", 1, 4, 2, (0, 0.2), 0.0, 8),
-          _rc("mirror_hall", 3, 2, 0, (0, 0.2), 0.3, 8, 100), _rc("mirror_hall", 3, 4, 2, (0, 0.2, 0, 0, 0, 0.6), 0.3, 2),
-          _rc("mirror_hall", 1, 1, 0, (0, 0.2, 0, 0, 0, 0.6), 1.0, 8), _rc("cornell", 1, 4, 2, _cornell_rough, 0.0, 4, 0, 96, 96),
-          _rc("cornell", 1, 4, 2, _cornell_rough, 1.0, 4, 0, 96, 96)]
-# the exception of C5: the degenerate tangent occurs on one pixel of a case made for it
-ABOVE = _rc("floor_from_above", 8, 2, 0, (0.5,), 0.0, W=7, H=5)
-QUEUED = _rc("rough_sphere", 2, 3, 2, (0, 0, 0, 0, 0, 0.4, 0.4, 0.2), 0.3, 4)
-
-
-def _rough_of(rc):
-    r = rc[1]() if callable(rc[1]) else rc[1]
-    return None if r is None else np.asarray(r, F)
-
-
-def _rid(rc):
-    c, r, ga, mc, off = rc
-    return f"{c[0]}-{c[1]}x{c[2]}-J{c[3]}-K{c[4]}-R{c[5]}-ga{ga}-chain{mc}-off{off}-{'fn' if callable(r) else 'a' + '_'.join(str(a) for a in r)}"
-
-
-def _what(rc):
-    r = _rough_of(rc)
-    return f"{tgs._what(rc[0])}, roughness {None if r is None else [float(a) for a in r]}, guide_alpha {rc[2]}, max_chain {rc[3]}, id_offset {rc[4]}"
-
-
-@functools.lru_cache(maxsize=None)
-def _base(case, rough, alt=None, frame=None, table="own"):
-    """What does not depend on the guide: scene_gloss_model.render's results with scene_rough_model.paths, on test_gloss_scene's
-    (shared, unchanged) first hits."""
-    name, W, H, J, K, R, sec, point = case
-    frame = (0 if name in ("cornell",) else FRAME) if frame is None else frame
-    seed = 1 if name in ("cornell",) else SEED
-    s, lk, _ = tgs.INPUTS[name]()
-    tab = tgs._table_of(name, table)
-    lt = tgs.ssm.light(lk["centre"], samples=1) if point else tgs.ssm.light(lk["centre"], lk["edge_u"], lk["edge_v"], 1)
-    first, em, emit = tgs._first(name, W, H, frame, seed)
-    r = None if rough is None else np.asarray(rough() if callable(rough) else rough, F)
-    out = rm.render(W, H, frame, *tss._args(s), lt, tgs.spm.params(J, K, R, 0.15, sec), tab, None, r, 0.0, seed=seed, alt=alt, first=first, emitters=em,
-                    emittance=emit)
-    return dict(base=(out[0], out[5]["first_gb"], out[2], out[3], out[5]), lt=lt, frame=frame, seed=seed, tab=tab, rough=r)
-
-
-@functools.lru_cache(maxsize=None)
-def _rmodel(case, rough, ga, mc, off, alt=None, frame=None, table="own"):
-    """dict(color, gb, D, I, chain, info, lt, frame, seed, tab, rough) of scene_rough_model.render."""
-    b = _base(case, rough, None if alt == "guide_alpha_compared_the_wrong_way" else alt, frame, table)
-    name, W, H = case[:3]
-    s = tgs.INPUTS[name]()[0]
-    info0 = {k: v for k, v in b["base"][4].items() if k not in ("guide", "first_gb", "guide_events")}
-    col, gb, D, I, chain, info = rm.render(W, H, b["frame"], *tss._args(s), b["lt"], None, b["tab"], vm.params(mc, off), b["rough"], ga, seed=b["seed"],      # noqa: E741
-                                           alt=alt, base=b["base"][:4] + (info0,))
-    return dict(b, color=col, gb=gb, D=D, I=I, chain=chain, info=info)
+QUEUED = sh.rc("rough_sphere", 2, 3, 2, (0, 0, 0, 0, 0, 0.4, 0.4, 0.2), 0.3, 4)
 
 
 def _events(m):
     return {e: rm.total(m["info"], e) for e in rm.EVENTS + rm.GUIDE_EVENTS}
-
-
-def _counts(m, ref):
-    c = tsp._split_counts(m, ref)
-    c["chain"] = int((m["chain"] != ref["chain"]).sum())
-    return c
 
 
 # ---- C1: exports, NEEDED, refusals -----------------------------------------------------------------------------------------------------
@@ -188,7 +68,6 @@ def test_the_six_rough_symbols_are_declared_listed_and_exported(pkg):
 
 
 BAD_ALPHA = [-0.25, 1.5, float("nan"), float("inf"), -float("inf")]
-BAD_GUIDE_ALPHA = [-0.5, float("nan"), float("inf"), -float("inf")]
 
 
 def test_rough_argument_errors_without_a_device(pkg):
@@ -228,27 +107,27 @@ def test_rough_argument_errors_without_a_device(pkg):
             assert call(ctypes.byref(B.SvgfSceneLight.make((0, 1, 0), samples=n)), P) == -1, n
         assert call(L, P, pl=ctypes.byref(planes)) == -1 and call(L, P, gb=None) == -1
         assert call(L, P, w=0) == -1 and call(L, P, h=-3) == -1
-        for bad in tps.BAD_PARAMS:
+        for bad in sh.BAD_PARAMS:
             assert call(L, ctypes.byref(B.SvgfPathParams(*bad))) == -1, bad
-        for bad in tvs.BAD_VIRTUAL:
+        for bad in sh.BAD_VIRTUAL:
             assert call(L, P, v=ctypes.byref(B.SvgfVirtualParams(*bad))) == -1, bad
-        for bad in BAD_GUIDE_ALPHA:
+        for bad in sh.BAD_GUIDE_ALPHA:
             assert call(L, P, r=ctypes.byref(B.SvgfRoughParams(bad))) == -1, bad
     assert plain(L, P, rgb=None) == -1
     assert split(L, P, d=None) == -1 and split(L, P, i=None) == -1 and split(L, P, d=5, i=5) == -1 and split(L, P, rgb=None) == -1
 
 
 # ---- C2: the model's identities --------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("vc", tvs.VCASES, ids=tvs._vid)
+@pytest.mark.parametrize("vc", sh.VCASES, ids=sh.vid)
 def test_no_table_or_a_zero_table_is_the_virtual_model_on_bits(vc):
-    """scene_virtual_model.render through test_virtual_scene's own cache against this file's model with no roughness, an empty table
-    and an all-zero table, for two values of guide_alpha."""
+    """scene_virtual_model.render through the virtual suite's cache (scene_harness.vmodel) against this file's model with no roughness, an
+    empty table and an all-zero table, for two values of guide_alpha."""
     case, mc, off = vc
-    ref = tvs._vmodel(*vc)
+    ref = sh.vmodel(*vc)
     for rough in (None, (), (0.0,) * 16):
         for ga in (0.0, 1.0):
-            m = _rmodel(case, rough, ga, mc, off)
-            c = _counts(m, ref)
+            m = sh.rmodel(case, rough, ga, mc, off)
+            c = sh.chain_counts(m, ref)
             assert not any(c.values()), (rough, ga, c)
             assert not any(_events(m).values())
 
@@ -256,22 +135,22 @@ def test_no_table_or_a_zero_table_is_the_virtual_model_on_bits(vc):
 def test_roughness_where_it_cannot_act_changes_no_bit():
     """On objects no ray reaches (ids the scene does not have), on an object with reflect == 0 (rough_floor's walls and block) and on
     glass objects (rough_sphere's ids 5 and 6)."""
-    rc = RCASES[2]
-    ref = _rmodel(*rc)
-    assert not any(_counts(_rmodel(rc[0], (0.1, 0.7, 0.7, 0.7, 0.0, 0.7, 0.9, 0.9, 0.9), *rc[2:]), ref).values())
-    rc = RCASES[7]
-    ref = _rmodel(*rc)
-    assert not any(_counts(_rmodel(rc[0], (0, 0, 0, 0, 0, 0.0, 0.0, 0.2), *rc[2:]), ref).values())
-    assert any(_counts(_rmodel(rc[0], (0, 0, 0, 0, 0, 0.4, 0.4, 0.0), *rc[2:]), ref).values())
+    rc = sh.RCASES[2]
+    ref = sh.rmodel(*rc)
+    assert not any(sh.chain_counts(sh.rmodel(rc[0], (0.1, 0.7, 0.7, 0.7, 0.0, 0.7, 0.9, 0.9, 0.9), *rc[2:]), ref).values())
+    rc = sh.RCASES[7]
+    ref = sh.rmodel(*rc)
+    assert not any(sh.chain_counts(sh.rmodel(rc[0], (0, 0, 0, 0, 0, 0.0, 0.0, 0.2), *rc[2:]), ref).values())
+    assert any(sh.chain_counts(sh.rmodel(rc[0], (0, 0, 0, 0, 0, 0.4, 0.4, 0.0), *rc[2:]), ref).values())
 
 
-@pytest.mark.parametrize("rc", [RCASES[2], RCASES[10]], ids=_rid)
+@pytest.mark.parametrize("rc", [sh.RCASES[2], sh.RCASES[10]], ids=sh.rid)
 def test_colour_does_not_depend_on_the_guide(rc):
     case, rough, ga, mc, off = rc
-    ref = _rmodel(*rc)
+    ref = sh.rmodel(*rc)
     for ga2, mc2, off2 in ((0.0, 1, 0), (1.0, 8, 7)):
-        m = _rmodel(case, rough, ga2, mc2, off2)
-        c = tsp._split_counts(m, ref)
+        m = sh.rmodel(case, rough, ga2, mc2, off2)
+        c = sh.split_counts(m, ref)
         assert not c["color"] and not c["direct"] and not c["indirect"], c
 
 
@@ -279,7 +158,7 @@ def test_colour_does_not_depend_on_the_guide(rc):
 def test_roughness_table_of_the_three_scene_files(pkg):
     seen = 0
     for name in ("cornell", "room", "bunny"):
-        sc = pkg.scene.parse_scene(tgs._scene_text(name))
+        sc = pkg.scene.parse_scene(sh.scene_text(name))
         seen += 1
         t = pkg.scene.roughness_table(sc)
         assert t.dtype == F and t.shape == (len(sc.objects),) and ((t >= 0) & (t <= 1)).all()
@@ -292,30 +171,15 @@ def test_roughness_table_of_the_three_scene_files(pkg):
         assert all(part[i] == (t[i] if i in ids else 0) for i in range(len(t)))
         print(f"{name}: {[float(a) for a in t]}")
     assert seen == 3
-    t = np.asarray(_cornell_rough(), F)
+    t = np.asarray(sh.cornell_rough(), F)
     assert (t > 0).sum() >= 1 and F(np.sqrt(2.0 / 7.0)) in t            # SPECEX 5
     # the mapping's ends: a huge exponent is nearly smooth, a tiny one is clipped to 1
-    sc = pkg.scene.parse_scene(tgs._scene_text("cornell"))
+    sc = pkg.scene.parse_scene(sh.scene_text("cornell"))
     sc.materials[sc.objects[0]["material"]]["specex"] = 1e-3
     assert pkg.scene.roughness_table(sc)[sc.objects[0]["id"]] <= 1.0
 
 
 # ---- C4: the construction in float64 ---------------------------------------------------------------------------------------------------
-def _disc_points(n, rng):
-    p = rng.uniform(-1, 1, (4 * n, 2))
-    p = p[(p * p).sum(1) < 1][:n]
-    assert len(p) == n
-    return p[:, 0].copy(), p[:, 1].copy()
-
-
-def _view(c, n):
-    """A direction d with v.n = c about the normal n, off the frame's axes."""
-    T, B = rm.frame_of([np.array([x]) for x in n], np.float64)
-    s = np.sqrt(1 - c * c)
-    v = [s * (0.6 * T[k][0] + 0.8 * B[k][0]) + c * n[k] for k in range(3)]
-    return [-x for x in v]
-
-
 def _quadrature(alpha, d, n, N=1536):
     """(albedo, mean d') of the lobe by quadrature over the hemisphere of normals h about n: D_v(h) = G1(v) max(0, v.h) D(h) / v.n,
     D the GGX distribution, d' = d - 2 (d.h) h, integrand D_v(h) G1(d'.n) [d'.n > 0]; midpoint rule in (cos theta, phi)."""
@@ -356,8 +220,8 @@ def test_the_lobe_in_float64(alpha, vn):
     N = 1 << 16
     rng = np.random.default_rng(1234)
     n = np.array([0.36, 0.48, 0.8])
-    d = _view(vn, n)
-    t1, t2 = _disc_points(N, rng)
+    d = sh.view_dir(vn, n)
+    t1, t2 = sh.disc_points(N, rng)
     rep = lambda x: np.full(N, x, np.float64)         # noqa: E731
     Lb = rm.lobe(rep(alpha), [rep(x) for x in d], [rep(x) for x in n], t1, t2, np.float64)
     assert Lb["faces"].all()
@@ -392,8 +256,8 @@ def test_a_small_alpha_stays_within_the_constructions_angle_of_the_mirror_direct
     rng = np.random.default_rng(7)
     n = np.array([0.36, 0.48, 0.8])
     for c in (1.0, 0.5, 0.1):
-        d = _view(c, n)
-        t1, t2 = _disc_points(N, rng)
+        d = sh.view_dir(c, n)
+        t1, t2 = sh.disc_points(N, rng)
         rep = lambda x: np.full(N, x, np.float64)         # noqa: E731
         Lb = rm.lobe(rep(alpha), [rep(x) for x in d], [rep(x) for x in n], t1, t2, np.float64)
         dn_ = float(np.dot(d, n))
@@ -412,10 +276,10 @@ def test_a_small_alpha_stays_within_the_constructions_angle_of_the_mirror_direct
 def test_each_rough_alt_acts_on_the_gpu_cases():
     for alt in rm.ALTS:
         acted = None
-        for rc in RCASES[:13]:
-            c = _counts(_rmodel(*rc, alt=alt), _rmodel(*rc))
+        for rc in sh.RCASES[:13]:
+            c = sh.chain_counts(sh.rmodel(*rc, alt=alt), sh.rmodel(*rc))
             if any(c.values()):
-                acted = (_what(rc), c)
+                acted = (sh.rough_what(rc), c)
                 break
         print(f"`{alt}`: {acted}")
         assert acted is not None, f"`{alt}` changes no output of any GPU case"
@@ -423,297 +287,154 @@ def test_each_rough_alt_acts_on_the_gpu_cases():
 
 def test_gpu_cases_cover_every_rough_event():
     total = dict.fromkeys(rm.EVENTS + rm.GUIDE_EVENTS, 0)
-    for rc in RCASES:
-        ev = _events(_rmodel(*rc))
-        print(f"{_what(rc)}: {ev}")
+    for rc in sh.RCASES:
+        ev = _events(sh.rmodel(*rc))
+        print(f"{sh.rough_what(rc)}: {ev}")
         for e in total:
             total[e] += ev[e]
-    above = _events(_rmodel(*ABOVE))
-    print(f"all cases: {total}; the case made for the degenerate tangent ({_what(ABOVE)}): {above}")
+    above = _events(sh.rmodel(*sh.ABOVE))
+    print(f"all cases: {total}; the case made for the degenerate tangent ({sh.rough_what(sh.ABOVE)}): {above}")
     for e, n in total.items():
-        if e != "degenerate_tangent":            # the named exception: an exact alignment, met on one pixel of ABOVE
+        if e != "degenerate_tangent":            # the named exception: an exact alignment, met on one pixel of sh.ABOVE
             assert n >= 32, e
     assert above["degenerate_tangent"] >= 1
 
 
 # ---- GPU -------------------------------------------------------------------------------------------------------------------------------
-def _tables(pkg, m):
-    return tgs._table(pkg, m["tab"]), (None if m["rough"] is None else pkg.RoughTable(m["rough"]))
+def _bound(rc, m):
+    return sh.gloss_case(rc[0], m, guide_alpha=rc[2], max_chain=rc[3], id_offset=rc[4])
 
 
-def _free(*ts):
-    for t in ts:
-        if t is not None:
-            t.free()
-
-
-def _draw(pkg, scene, table, rough, W, H, s, lt, J, K, R, ga, mc, off, sec=1, frame=FRAME, seed=SEED, stream=None, bufs=None, chain=True, sync=True):
-    import torch
-    rgb, gbt, ch = bufs or (trs._buffers(W, H) + (tvs._chain_buffer(W, H) if chain else None,))
-    scene.draw_rough(rgb, gbt, W, H, s["cam"], tgs._light(pkg, lt), frame, table=table, paths=J, max_depth=K, rr_depth=R, shadow_secondary=sec,
-                     seed=seed, stream=stream, max_chain=mc, id_offset=off, out_chain=ch, rough=rough, guide_alpha=ga)
-    if not sync:
-        return None
-    torch.cuda.synchronize()
-    color, gb = trs._host(pkg, rgb, gbt, W, H)
-    return dict(color=color, gb=gb, chain=None if ch is None else ch.cpu().numpy())
-
-
-def _draw_split(pkg, scene, table, rough, W, H, s, lt, J, K, R, ga, mc, off, sec=1, frame=FRAME, seed=SEED, stream=None, bufs=None, rgb=True, chain=True,
-                sync=True):
-    import torch
-    b = bufs or dict(tsp._split_buffers(W, H, rgb), chain=tvs._chain_buffer(W, H) if chain else None)
-    scene.draw_rough_split(b["D"], b["I"], b["gb"], W, H, s["cam"], tgs._light(pkg, lt), frame, table=table, paths=J, max_depth=K, rr_depth=R,
-                           shadow_secondary=sec, seed=seed, out_rgb=b["color"], stream=stream, max_chain=mc, id_offset=off, out_chain=b["chain"],
-                           rough=rough, guide_alpha=ga)
-    if not sync:
-        return None
-    torch.cuda.synchronize()
-    return dict(tsp._split_host(pkg, b, W, H), chain=None if b["chain"] is None else b["chain"].cpu().numpy())
-
-
-def _draw_case(pkg, rc, split=False, rgb=True, chain=True, builds=None):
-    case, _, ga, mc, off = rc
-    name, W, H, J, K, R, sec, point = case
-    m = _rmodel(*rc)
-    s = tgs.INPUTS[name]()[0]
-    scene = trs._create(pkg, s, *(builds or ()))
-    tb, rt = _tables(pkg, m)
-    try:
-        f = _draw_split if split else _draw
-        kw = dict(rgb=rgb) if split else {}
-        return f(pkg, scene, tb, rt, W, H, s, m["lt"], J, K, R, ga, mc, off, sec, frame=m["frame"], seed=m["seed"], chain=chain, **kw), m
-    finally:
-        _free(tb, rt)
-        scene.free()
+def _draw_case(pkg, rc, **kw):
+    m = sh.rmodel(*rc)
+    return sh.draw_case(pkg, sh.ROUGH, _bound(rc, m), **kw), m
 
 
 # G1
 @pytest.mark.gpu
-@pytest.mark.parametrize("W,H", SIZES)
+@pytest.mark.parametrize("W,H", sh.SIZES)
 def test_rough_sizes_and_seams(pkg, W, H):
-    rc = _rc("mirror_hall", 2, 3, 2, (0, 0.2, 0, 0, 0, 0.6), 0.3, 4, 100, W=W, H=H)
+    rc = sh.rc("mirror_hall", 2, 3, 2, (0, 0.2, 0, 0, 0, 0.6), 0.3, 4, 100, W=W, H=H)
     got, m = _draw_case(pkg, rc)
-    tvs._same(got, m, _what(rc))
+    sh.same(got, m, sh.rough_what(rc))
     got, m = _draw_case(pkg, rc, split=True)
-    tvs._same(got, m, _what(rc) + ", split form", split=True)
+    sh.same(got, m, sh.rough_what(rc) + ", split form", split=True)
 
 
 # G2
 @pytest.mark.gpu
-@pytest.mark.parametrize("rc", RCASES + [ABOVE], ids=_rid)
+@pytest.mark.parametrize("rc", sh.RCASES + [sh.ABOVE], ids=sh.rid)
 def test_rough_case_equals_the_model(pkg, rc):
     got, m = _draw_case(pkg, rc)
-    print(f"{_what(rc)}: {_events(m)}")
-    tvs._same(got, m, _what(rc))
+    print(f"{sh.rough_what(rc)}: {_events(m)}")
+    sh.same(got, m, sh.rough_what(rc))
 
 
 # G3
 @pytest.mark.gpu
-@pytest.mark.parametrize("rc", [RCASES[2], RCASES[10]], ids=_rid)
+@pytest.mark.parametrize("rc", [sh.RCASES[2], sh.RCASES[10]], ids=sh.rid)
 def test_rough_split_form_with_and_without_rgb_and_chain(pkg, rc):
     for rgb, chain in ((True, True), (False, True), (True, False), (False, False)):
         got, m = _draw_case(pkg, rc, split=True, rgb=rgb, chain=chain)
-        tvs._same(got, m, f"{_what(rc)}, out_rgb {'given' if rgb else 'NULL'}, out_chain {'given' if chain else 'NULL'}", split=True, rgb=rgb)
+        sh.same(got, m, f"{sh.rough_what(rc)}, out_rgb {'given' if rgb else 'NULL'}, out_chain {'given' if chain else 'NULL'}", split=True, rgb=rgb)
     got, m = _draw_case(pkg, rc, chain=False)
-    tvs._same(got, m, f"{_what(rc)}, plain form, out_chain NULL")
+    sh.same(got, m, f"{sh.rough_what(rc)}, plain form, out_chain NULL")
 
 
 @pytest.mark.gpu
 def test_rough_planar_target_equals_the_model(pkg):
-    import torch
-    from temporal_harness import _hip
-    rc = RCASES[10]
-    case, _, ga, mc, off = rc
-    name, W, H, J, K, R, sec, point = case
-    m = _rmodel(*rc)
-    s = tgs.INPUTS[name]()[0]
-    scene = trs._create(pkg, s)
-    table, rough = _tables(pkg, m)
-    den = pkg.Denoiser(W, H, 0)
-    planes = den.planar_gbuffer()
-    hip = _hip()
-    hip.hipMemcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
-
-    def read():
-        gb = np.zeros((H, W), dtype=pkg.synth.GBUFFER_DTYPE)
-        for field, ptr in (("normal", planes.normal), ("position", planes.position), ("albedo", planes.albedo), ("geomId", planes.geom_id)):
-            host = np.zeros((H, W, 3) if field != "geomId" else (H, W), F if field != "geomId" else np.int32)
-            assert hip.hipMemcpy(host.ctypes.data, ptr, host.nbytes, 2) == 0
-            gb[field] = host
-        gb["ialbedo"] = F(1.0)
-        return gb
-
-    rgb, ch = torch.empty((H, W, 3), dtype=torch.float32, device="cuda"), tvs._chain_buffer(W, H)
-    scene.draw_rough(rgb, planes, W, H, s["cam"], tgs._light(pkg, m["lt"]), FRAME, table=table, paths=J, max_depth=K, rr_depth=R, shadow_secondary=sec,
-                     seed=SEED, max_chain=mc, id_offset=off, out_chain=ch, rough=rough, guide_alpha=ga)
-    torch.cuda.synchronize()
-    tvs._same(dict(color=rgb.cpu().numpy(), gb=read(), chain=ch.cpu().numpy()), m, "mirror_hall, planar target")
-    b = dict(tsp._split_buffers(W, H), chain=tvs._chain_buffer(W, H))
-    scene.draw_rough_split(b["D"], b["I"], planes, W, H, s["cam"], tgs._light(pkg, m["lt"]), FRAME, table=table, paths=J, max_depth=K, rr_depth=R,
-                           shadow_secondary=sec, seed=SEED, out_rgb=b["color"], max_chain=mc, id_offset=off, out_chain=b["chain"], rough=rough, guide_alpha=ga)
-    torch.cuda.synchronize()
-    got = dict(D=b["D"].cpu().numpy(), I=b["I"].cpu().numpy(), color=b["color"].cpu().numpy(), gb=read(), chain=b["chain"].cpu().numpy())
-    den.free(); _free(table, rough); scene.free()
-    tvs._same(got, m, "mirror_hall, planar target, split form", split=True)
+    rc = sh.RCASES[10]
+    m = sh.rmodel(*rc)
+    sh.check_planar_target(pkg, sh.ROUGH, _bound(rc, m), m, "mirror_hall, planar target", forms=(False, True))
 
 
 # G4
 @pytest.mark.gpu
-@pytest.mark.parametrize("vc", [tvs.VCASES[1], tvs.VCASES[4], tvs.VCASES[8]], ids=tvs._vid)
+@pytest.mark.parametrize("vc", [sh.VCASES[1], sh.VCASES[4], sh.VCASES[8]], ids=sh.vid)
 def test_no_table_an_empty_and_a_zero_table_are_the_virtual_library_on_bits(pkg, vc):
-    case, mc, off = vc
-    name, W, H, J, K, R, sec, point = case
-    m = tvs._vmodel(*vc)
-    s = tgs.INPUTS[name]()[0]
-    scene = trs._create(pkg, s)
-    tb = tgs._table(pkg, m["tab"])
-    kw = dict(frame=m["frame"], seed=m["seed"])
-    v = tvs._draw(pkg, scene, tb, W, H, s, m["lt"], J, K, R, mc, off, sec, **kw)
-    vs = tvs._draw_split(pkg, scene, tb, W, H, s, m["lt"], J, K, R, mc, off, sec, **kw)
+    m = sh.vmodel(*vc)
+    c = sh.gloss_case(vc[0], m, max_chain=vc[1], id_offset=vc[2])
+    scene, tb = sh.create(pkg, c["s"]), sh.tables_of(pkg, sh.GLOSS, c)
+    where = (scene, c["W"], c["H"], c["s"], c["lt"])
+    kw = dict(frame=c["frame"], seed=c["seed"])
+    v, vs = (sh.draw(pkg, sh.VIRTUAL, *where, c["args"], split=split, tables=tb, **kw) for split in (False, True))
     empty, zero = pkg.RoughTable(None), pkg.RoughTable(np.zeros(16, F))
     assert len(empty) == 0 and len(zero) == 16
     for what, rt in (("NULL", None), ("an empty table", empty), ("an all-zero table", zero)):
         for ga in (0.0, 0.3, 1.0):
-            r = _draw(pkg, scene, tb, rt, W, H, s, m["lt"], J, K, R, ga, mc, off, sec, **kw)
-            rs = _draw_split(pkg, scene, tb, rt, W, H, s, m["lt"], J, K, R, ga, mc, off, sec, **kw)
-            tvs._same(r, v, f"{tvs._what(vc)}: {what}, guide_alpha {ga} vs svgf_virtual_draw")
-            tvs._same(rs, vs, f"{tvs._what(vc)}: {what}, guide_alpha {ga} vs svgf_virtual_draw_split", split=True)
-    _free(empty, zero, tb)
+            r, rs = (sh.draw(pkg, sh.ROUGH, *where, dict(c["args"], guide_alpha=ga), split=split, tables=dict(tb, rough=rt), **kw) for split in (False, True))
+            sh.same(r, v, f"{sh.virtual_what(vc)}: {what}, guide_alpha {ga} vs svgf_virtual_draw")
+            sh.same(rs, vs, f"{sh.virtual_what(vc)}: {what}, guide_alpha {ga} vs svgf_virtual_draw_split", split=True)
+    sh.free(empty, zero, *tb.values())
     scene.free()
 
 
 # G5
 @pytest.mark.gpu
-@pytest.mark.parametrize("rc", [RCASES[2], RCASES[7]], ids=_rid)
+@pytest.mark.parametrize("rc", [sh.RCASES[2], sh.RCASES[7]], ids=sh.rid)
 def test_compose_of_the_rough_split_form_is_the_composed_model(pkg, rc):
-    import torch
     W, H = rc[0][1:3]
     got, m = _draw_case(pkg, rc, split=True)
-    tvs._same(got, m, _what(rc), split=True)
-    d, i = torch.from_numpy(got["D"]).cuda(), torch.from_numpy(got["I"]).cuda()
-    tex = torch.from_numpy(np.ascontiguousarray(got["gb"]).view(np.uint8).reshape(-1).copy()).cuda()
-    out = torch.empty((H, W, 3), dtype=torch.float32, device="cuda")
-    pkg.trace_compose(out, d, i, tex, W, H)
-    torch.cuda.synchronize()
+    sh.same(got, m, sh.rough_what(rc), split=True)
     want = splm.compose((m["gb"]["albedo"] * m["gb"]["ialbedo"]).astype(F), m["D"], m["I"])
-    assert not differing(out.cpu().numpy(), want).any(), "albedo * (D + I) through svgf_trace_compose"
+    assert not differing(sh.compose_on_device(pkg, got, W, H), want).any(), "albedo * (D + I) through svgf_trace_compose"
 
 
 # G6
 @pytest.mark.gpu
-@pytest.mark.parametrize("rc", [RCASES[6], RCASES[13]], ids=_rid)
+@pytest.mark.parametrize("rc", [sh.RCASES[6], sh.RCASES[13]], ids=sh.rid)
 def test_every_tree_draws_the_same_rough_frame(pkg, rc):
-    for ml, sp in trs.BUILDS:
-        got, m = _draw_case(pkg, rc, builds=(ml, sp))
-        tvs._same(got, m, f"{rc[0][0]}, leaf {ml} split {sp}")
+    m = sh.rmodel(*rc)
+    sh.check_every_tree(pkg, sh.ROUGH, _bound(rc, m), m, rc[0][0])
 
 
-BLOCK_ALPHA, BLOCK_GA = 0.2, 0.3
-
-
-def _block_rough():
-    from temporal_harness import BLOCK as B
-    a = np.zeros(len(tas._block_inputs()[0]["geoms"]), F)
-    a[B] = BLOCK_ALPHA
-    return a
+BLOCK_ARGS = sh.path_args(*sh.BLOCK[2:], guide_alpha=sh.BLOCK_GA, max_chain=4, id_offset=0)
 
 
 @functools.lru_cache(maxsize=None)
 def _block_rmodel(f, W, H, J, K, R, mc=4, off=0):
     """Frame f of f15's turning block, the block a rough full mirror: the model on the posed arrays."""
-    s, tables = tas._block_inputs()
+    s, tables = sh.block_inputs()
     ps = pm.posed_scene(s, tables[f])
-    lk = tss._block_light()
-    lt = tgs.ssm.light(lk["centre"], lk["edge_u"], lk["edge_v"], 1)
-    col, gb, D, I, chain, info = rm.render(W, H, f, ps["cam"], ps["geoms"], None, None, None, None, None, None, lt, tgs.spm.params(J, K, R), tgs._block_table(),     # noqa: E741
-                                           vm.params(mc, off), _block_rough(), BLOCK_GA, seed=3)
+    lk = sh.block_light()
+    lt = ssm.light(lk["centre"], lk["edge_u"], lk["edge_v"], 1)
+    col, gb, D, I, chain, info = rm.render(W, H, f, ps["cam"], ps["geoms"], None, None, None, None, None, None, lt, spm.params(J, K, R), sh.block_table(),     # noqa: E741
+                                           vm.params(mc, off), sh.block_rough(), sh.BLOCK_GA, seed=3)
     return dict(color=col, gb=gb, D=D, I=I, chain=chain, info=info, lt=lt)
 
 
 # G7
 @pytest.mark.gpu
 def test_the_rough_block_follows_the_pose(pkg):
-    W, H, J, K, R = tgs.BLOCK
-    s, tables = tas._block_inputs()
-    scene = trs._create(pkg, s)
-    table, rough = pkg.GlossTable(tgs._block_table()), pkg.RoughTable(_block_rough())
+    W, H, J, K, R = sh.BLOCK
+    s, tables = sh.block_inputs()
+    scene = sh.create(pkg, s)
+    tb = dict(table=pkg.GlossTable(sh.block_table()), rough=pkg.RoughTable(sh.block_rough()))
     scene.enable_pose(len(s["geoms"]))
     cols = []
     for f in (0, 2):
         m = _block_rmodel(f, W, H, J, K, R)
         assert rm.total(m["info"], "rough0") > 100 and int((m["chain"] > 0).sum()) > 100
-        scene.pose(tas._dev(tables[f]))
-        tvs._same(_draw(pkg, scene, table, rough, W, H, s, m["lt"], J, K, R, BLOCK_GA, 4, 0, frame=f, seed=3), m, f"rough block, pose {f}")
-        tvs._same(_draw_split(pkg, scene, table, rough, W, H, s, m["lt"], J, K, R, BLOCK_GA, 4, 0, frame=f, seed=3), m, f"rough block, pose {f}, split form",
-                  split=True)
+        scene.pose(sh.dev(tables[f]))
+        for split in (False, True):
+            got = sh.draw(pkg, sh.ROUGH, scene, W, H, s, m["lt"], BLOCK_ARGS, split=split, frame=f, seed=3, tables=tb)
+            sh.same(got, m, f"rough block, pose {f}" + ", split form" * split, split=split)
         cols.append(m["gb"]["position"])
-    _free(table, rough); scene.free()
+    sh.free(*tb.values()); scene.free()
     assert int((cols[0] != cols[1]).any(axis=-1).sum()) > 50
 
 
 # G8
 @pytest.mark.gpu
 def test_eight_rough_draws_queued_without_host_waits(pkg):
-    import torch
-    case, r, ga, mc, off = QUEUED
-    name, W, H, J, K, R, sec, point = case
-    s = tgs.INPUTS[name]()[0]
-    m0 = _rmodel(*QUEUED)
-    scene = trs._create(pkg, s)
-    table, rough = _tables(pkg, m0)
-    st = tsp._OwnStream()
-    bufs = [trs._buffers(W, H) + (tvs._chain_buffer(W, H),) for _ in range(8)]
-    torch.cuda.synchronize()
-    for f, b in enumerate(bufs):
-        _draw(pkg, scene, table, rough, W, H, s, m0["lt"], J, K, R, ga, mc, off, sec, frame=f, stream=st, bufs=b, sync=False)
-    st.close()
-    for f, (rgb, gbt, ch) in enumerate(bufs):
-        color, gb = trs._host(pkg, rgb, gbt, W, H)
-        tvs._same(dict(color=color, gb=gb, chain=ch.cpu().numpy()), _rmodel(case, r, ga, mc, off, frame=f), f"queued rough draw, frame {f}")
-    _free(table, rough); scene.free()
+    sh.check_queued(pkg, sh.ROUGH, _bound(QUEUED, sh.rmodel(*QUEUED)), lambda f: sh.rmodel(*QUEUED, frame=f), "queued rough draw")
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("split", [False, True])
 def test_a_captured_rough_draw_is_one_kernel_node_and_replays_the_same_bits(pkg, split):
-    import torch
-    hip = tas._graph_api()
-    case, r, ga, mc, off = QUEUED
-    name, W, H, J, K, R, sec, point = case
-    s = tgs.INPUTS[name]()[0]
-    m = _rmodel(*QUEUED)
-    scene = trs._create(pkg, s)
-    table, rough = _tables(pkg, m)
-    st = tsp._OwnStream()
-    b = dict(tsp._split_buffers(W, H), chain=tvs._chain_buffer(W, H)) if split else trs._buffers(W, H) + (tvs._chain_buffer(W, H),)
-    torch.cuda.synchronize()
-    draw = (lambda: _draw_split(pkg, scene, table, rough, W, H, s, m["lt"], J, K, R, ga, mc, off, sec, stream=st, bufs=b, sync=False)) if split else \
-        (lambda: _draw(pkg, scene, table, rough, W, H, s, m["lt"], J, K, R, ga, mc, off, sec, stream=st, bufs=b, sync=False))
-    draw()                                  # eager first: a first launch may set kernel attributes
-    st.synchronize()
-    graph, gexec = ctypes.c_void_p(), ctypes.c_void_p()
-    assert hip.hipStreamBeginCapture(st.cuda_stream, 2) == 0
-    draw()                                  # recorded, not executed
-    assert hip.hipStreamEndCapture(st.cuda_stream, ctypes.byref(graph)) == 0 and graph.value
-    types = tas._node_types(hip, graph)
-    assert hip.hipGraphInstantiate(ctypes.byref(gexec), graph, None, None, 0) == 0
-    with torch.cuda.stream(st.torch):
-        for t in (b.values() if split else b):
-            t.zero_()
-    assert hip.hipGraphLaunch(gexec, st.cuda_stream) == 0
-    st.synchronize()
-    if split:
-        got = dict(tsp._split_host(pkg, b, W, H), chain=b["chain"].cpu().numpy())
-    else:
-        color, gb = trs._host(pkg, b[0], b[1], W, H)
-        got = dict(color=color, gb=gb, chain=b[2].cpu().numpy())
-    hip.hipGraphExecDestroy(gexec); hip.hipGraphDestroy(graph)
-    st.close()
-    _free(table, rough); scene.free()
-    print(f"captured rough draw (split {split}) = node types {types}")
-    assert types == [0], types
-    tvs._same(got, m, "replayed rough draw", split=split)
+    m = sh.rmodel(*QUEUED)
+    sh.check_captured(pkg, sh.ROUGH, _bound(QUEUED, m), m, "rough draw", split=split)
 
 
 # G9
@@ -721,17 +442,16 @@ def test_a_captured_rough_draw_is_one_kernel_node_and_replays_the_same_bits(pkg,
 def test_every_error_code_of_the_table_and_of_both_rough_draws(pkg):
     import torch
     B = pkg.binding
-    s, lk, tab = _rough_sphere()
-    scene = trs._create(pkg, s)
+    s, lk, tab = sh.rough_sphere()
+    scene = sh.create(pkg, s)
     table, rough = pkg.GlossTable(tab), pkg.RoughTable([0, 0, 0, 0, 0, 0.4, 0.4, 0.2])
     assert len(rough) == 8
     lib = pkg.load_rough_library()
     h = ctypes.c_void_p(7)
     assert lib.svgf_rough_table_create(torch.cuda.device_count(), (ctypes.c_float * 1)(0.5), 1, ctypes.byref(h)) == -2 and not h.value       # SVGF_ERR_NO_DEVICE
-    cam, sp, planes = B.SvgfCamera(), B.SvgfSynthParams(), B.SvgfPlanarGBuffer()
+    c, p = ctypes.byref(B.SvgfCamera()), ctypes.byref(B.SvgfSynthParams())
     ok = ctypes.byref(B.SvgfSceneLight.make((0, 1, 0), (1, 0, 0), (0, 0, 1), 4))
     pp, vp, rp = ctypes.byref(B.SvgfPathParams(1, 4, 2, 0.15, 1)), ctypes.byref(B.SvgfVirtualParams(4, 0)), ctypes.byref(B.SvgfRoughParams(0.3))
-    c, p = ctypes.byref(cam), ctypes.byref(sp)
     guard = torch.full((64,), 7.0, dtype=torch.float32, device="cuda")       # every pointer below is this buffer: a refused call writes nothing
     a = guard.data_ptr()
     plain = lambda h=scene.h, tb=table.h, rgb=a, gb=a, pl=None, w=1, hh=1, cm=c, spp=p, lt=ok, t=pp, v=vp, rt=rough.h, r=rp: lib.svgf_rough_draw(   # noqa: E731
@@ -741,20 +461,14 @@ def test_every_error_code_of_the_table_and_of_both_rough_draws(pkg):
     assert plain(rgb=None) == -1
     assert split(d=None) == -1 and split(i=None) == -1 and split(d=a, i=a) == -1
     for f in (plain, split):
-        assert f(h=None) == -1 and f(w=0) == -1 and f(hh=-1) == -1 and f(cm=None) == -1 and f(spp=None) == -1 and f(lt=None) == -1 and f(t=None) == -1
-        assert f(gb=None) == -1 and f(pl=ctypes.byref(planes)) == -1 and f(gb=None, pl=ctypes.byref(planes)) == -1
-        assert f(w=1 << 14, hh=1 << 13) == -5
+        sh.check_common_refusals(B, f, (B.SvgfPathParams, sh.BAD_PARAMS))
         # the virtual draw's refusals come first: an unsupported size with a bad vp or rp is still SVGF_ERR_UNSUPPORTED
         assert f(w=1 << 14, hh=1 << 13, v=None) == -5 and f(w=1 << 14, hh=1 << 13, r=None) == -5
-        for n in (0, 65):
-            assert f(lt=ctypes.byref(B.SvgfSceneLight.make((0, 1, 0), samples=n))) == -1
-        for bad in tps.BAD_PARAMS:
-            assert f(t=ctypes.byref(B.SvgfPathParams(*bad))) == -1, bad
         assert f(v=None) == -1
-        for bad in tvs.BAD_VIRTUAL:
+        for bad in sh.BAD_VIRTUAL:
             assert f(v=ctypes.byref(B.SvgfVirtualParams(*bad))) == -1, bad
         assert f(r=None) == -1
-        for bad in BAD_GUIDE_ALPHA:
+        for bad in sh.BAD_GUIDE_ALPHA:
             assert f(r=ctypes.byref(B.SvgfRoughParams(bad))) == -1, bad
     if torch.cuda.device_count() >= 2:
         other = pkg.RoughTable([0.5], device=1)
@@ -766,11 +480,12 @@ def test_every_error_code_of_the_table_and_of_both_rough_draws(pkg):
     assert (guard.cpu().numpy() == F(7.0)).all()
     # after the refused calls, and the extremes of guide_alpha that are allowed
     for ga in (0.0, 1e30):
-        rc = _rc("rough_sphere", 2, 3, 2, (0, 0, 0, 0, 0, 0.4, 0.4, 0.2), ga, 4, 0, W=7, H=5)
-        m = _rmodel(*rc)
-        tvs._same(_draw(pkg, scene, table, rough, 7, 5, s, m["lt"], 2, 3, 2, ga, 4, 0), m, f"after the refused calls, guide_alpha {ga}")
-        tvs._same(_draw_split(pkg, scene, table, rough, 7, 5, s, m["lt"], 2, 3, 2, ga, 4, 0), m, "after the refused calls, split form", split=True)
-    _free(table, rough); scene.free()
+        rc = sh.rc("rough_sphere", 2, 3, 2, (0, 0, 0, 0, 0, 0.4, 0.4, 0.2), ga, 4, 0, W=7, H=5)
+        m = sh.rmodel(*rc)
+        tb, args = dict(table=table, rough=rough), sh.path_args(2, 3, 2, guide_alpha=ga, max_chain=4, id_offset=0)
+        sh.same(sh.draw(pkg, sh.ROUGH, scene, 7, 5, s, m["lt"], args, tables=tb), m, f"after the refused calls, guide_alpha {ga}")
+        sh.same(sh.draw(pkg, sh.ROUGH, scene, 7, 5, s, m["lt"], args, split=True, tables=tb), m, "after the refused calls, split form", split=True)
+    sh.free(table, rough); scene.free()
 
 
 # G10
@@ -780,43 +495,6 @@ def test_pose_rough_split_draw_two_denoises_compose_against_the_temporal_model(p
     context of its own (sepcolor 1 / addcolor 0, the temporal pass alone so that temporal_model.py is the whole filter) ->
     svgf_trace_compose.  Every state of both contexts after every frame equals temporal_model.run_sequence fed the model's D (or I) and
     the model's G-buffer, on bits."""
-    import torch
-    from temporal_harness import assert_frames_equal, read_states, scales, synth_params
-    W, H, J, K, R = tgs.BLOCK
-    N = 4
-    s, tables = tas._block_inputs()
-    models = [_block_rmodel(f, W, H, J, K, R) for f in range(N)]
-    lt = models[0]["lt"]
-    p = synth_params(pkg, W, H, sepcolor=1, addcolor=0)
-    sx, sy = scales(pkg, W, H)
-    views = [orc.view_matrix(pkg, s["cam"])] * N
-    scene = trs._create(pkg, s)
-    scene.enable_pose(len(s["geoms"]))
-    table, rough = pkg.GlossTable(tgs._block_table()), pkg.RoughTable(_block_rough())
-    dens = {"D": pkg.Denoiser(W, H), "I": pkg.Denoiser(W, H)}
-    for den in dens.values():
-        den.set_capture(True)
-    b = dict(tsp._split_buffers(W, H, rgb=False), chain=tvs._chain_buffer(W, H))
-    outs = {k: torch.empty((H, W, 3), dtype=torch.float32, device="cuda") for k in ("D", "I", "C")}
-    states = {"D": [], "I": []}
-    try:
-        for f in range(N):
-            scene.pose(tas._dev(tables[f]))
-            got = _draw_split(pkg, scene, table, rough, W, H, s, lt, J, K, R, BLOCK_GA, 4, 0, frame=f, seed=3, bufs=b, rgb=False)
-            tvs._same(got, models[f], f"frame {f}", split=True, rgb=False)
-            for key, den in dens.items():
-                den.denoise(outs[key], b[key], b["gb"], s["cam"], p)
-                den.sync()
-                states[key].append(read_states(den))
-            pkg.trace_compose(outs["C"], outs["D"], outs["I"], b["gb"], W, H)
-            torch.cuda.synchronize()
-            alb = (models[f]["gb"]["albedo"] * models[f]["gb"]["ialbedo"]).astype(F)
-            want = splm.compose(alb, outs["D"].cpu().numpy(), outs["I"].cpu().numpy())
-            assert not differing(outs["C"].cpu().numpy(), want).any(), f"frame {f}: composed"
-    finally:
-        for den in dens.values():
-            den.free()
-        _free(table, rough); scene.free()
-    for key in ("D", "I"):
-        ref = tm.run_sequence([(m[key], m["gb"]) for m in models], views=views, scale=(sx, sy))
-        assert_frames_equal(states[key], ref, f"rough block, term {key}")
+    W, H, J, K, R = sh.BLOCK
+    sh.run_split_denoise_compose(pkg, orc, sh.ROUGH, [_block_rmodel(f, W, H, J, K, R) for f in range(4)], W, H, BLOCK_ARGS,
+                                 ("rough block, term D", "rough block, term I"), tab=sh.block_table(), rough=sh.block_rough())

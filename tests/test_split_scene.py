@@ -17,80 +17,16 @@ import subprocess
 import numpy as np
 import pytest
 
+import scene_harness as sh
 import scene_model as sm
 import scene_pose_model as pm
 import scene_shadow_model as ssm
 import scene_split_model as spm
 import scene_trace_model as stm
-import test_animated_scene as tas
-import test_resident_scene as trs
-import test_shadowed_scene as tss
-import test_traced_scene as tts
 from conftest import ROOT
-from test_scene_model import FRAME, SEED, counts, differing
+from test_scene_model import FRAME, SEED, differing
 
 F = np.float32
-EDGE = tss.EDGE
-SIZES = [(1, 1), (7, 5), (65, 4), (257, 3)]         # one pixel; 35 pixels; a wave seam in a row; a block seam (771 pixels, 4 blocks)
-
-
-class _OwnStream:
-    """A non-blocking HIP stream of the test's own, destroyed by close(): the tests here take nothing from torch's pool of streams and
-    leave the process with the streams it had (tests/test_stream_gpu.py's timing test depends on which hardware queue the NEXT two
-    pool streams land on, and with it on every stream a test file in front of it leaves behind)."""
-
-    def __init__(self):
-        import torch
-        from temporal_harness import _hip
-        self.hip = _hip()
-        self.hip.hipStreamCreateWithFlags.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint]
-        self.hip.hipStreamDestroy.argtypes = [ctypes.c_void_p]
-        h = ctypes.c_void_p()
-        assert self.hip.hipStreamCreateWithFlags(ctypes.byref(h), 1) == 0 and h.value
-        self.cuda_stream = h.value
-        self.torch = torch.cuda.ExternalStream(h.value)
-
-    def synchronize(self):
-        self.torch.synchronize()
-
-    def close(self):
-        self.synchronize()
-        assert self.hip.hipStreamDestroy(self.cuda_stream) == 0
-
-
-# ---- the model, computed once per case and shared --------------------------------------------------------------------------------------
-@functools.lru_cache(maxsize=None)
-def _emittance(kind, name, W, H):
-    s = tts._input(kind, name)[0]
-    e = spm.emittance_plane(W, H, s["cam"], s["geoms"], s["geom_ids"], s["tris"], s["tri_ids"])
-    e.setflags(write=False)
-    return e
-
-
-@functools.lru_cache(maxsize=None)
-def _split(kind, name, W, H, J, sec=1, samples=1, point=False, frame=FRAME, seed=SEED, noise=0.6, ambient=0.15):
-    """dict(D, I, color, gb, info, lt): the split model on top of test_traced_scene's cached traced model."""
-    (col, gb), info, lt = tts._model(kind, name, W, H, J, sec, samples, point, None, frame, seed, noise, ambient)
-    s = tts._input(kind, name)[0]
-    D, I, col, gb, info = spm.render(W, H, frame, *tss._args(s), lt, stm.params(J, ambient, sec), seed=seed, noise=noise,     # noqa: E741
-                                     fireflies=0.02 if noise else 0.0, traced=(col, gb, info), emittance=_emittance(kind, name, W, H))
-    D.setflags(write=False); I.setflags(write=False)
-    return dict(D=D, I=I, color=col, gb=gb, info=info, lt=lt)
-
-
-def _split_counts(got, ref, rgb=True):
-    c = counts((got["color"] if rgb else ref["color"], got["gb"]), (ref["color"], ref["gb"]))
-    if not rgb:
-        del c["color"]
-    c["direct"] = int(np.count_nonzero(differing(got["D"], ref["D"])))
-    c["indirect"] = int(np.count_nonzero(differing(got["I"], ref["I"])))
-    return c
-
-
-def _no_difference(got, ref, what, rgb=True):
-    c = _split_counts(got, ref, rgb)
-    print(f"{what}: differing pixels {c} (expected and allowed: 0)")
-    assert not any(c.values()), f"{what}: {c}"
 
 
 # ---- CPU 1: exports and refusals -------------------------------------------------------------------------------------------------------
@@ -150,12 +86,12 @@ def test_compose_argument_errors_without_a_device(pkg):
 
 
 # ---- CPU 2: the model's own properties -------------------------------------------------------------------------------------------------
-SMALL = [("edge", n, 67, 41) for n in EDGE] + [("rec", "cornell", 96, 96)]
+SMALL = [("edge", n, 67, 41) for n in sh.EDGE] + [("rec", "cornell", 96, 96)]
 
 
 def _case(kind, name, W, H, J, **kw):
     rec = kind == "rec"
-    return _split(kind, name, W, H, J, frame=0 if rec else FRAME, seed=1 if rec else SEED, **kw)
+    return sh.split_model(kind, name, W, H, J, frame=0 if rec else FRAME, seed=1 if rec else SEED, **kw)
 
 
 @pytest.mark.parametrize("kind,name,W,H", SMALL)
@@ -178,7 +114,7 @@ def test_without_noise_the_terms_are_the_shade_and_the_bounce(kind, name, W, H):
 
 
 def test_the_stage_has_emitter_pixels_and_they_carry_no_indirect_light():
-    m = _split("made", "stage", 67, 41, 3, noise=0.0)
+    m = sh.split_model("made", "stage", 67, 41, 3, noise=0.0)
     em = m["info"]["emitter"]
     print(f"stage: {int(em.sum())} emitter pixels")
     assert em.sum() >= 10 and (m["I"].view(np.uint32)[em] == 0).all() and (m["D"][em] > 0).all()
@@ -188,14 +124,14 @@ def test_the_stage_has_emitter_pixels_and_they_carry_no_indirect_light():
 @pytest.mark.parametrize("J", [1, 8])
 def test_the_furnace_splits_into_ambient_and_one(J):
     W, H = 48, 27
-    m = _split("traced", "furnace", W, H, J, noise=0.0, ambient=1.0)
+    m = sh.split_model("traced", "furnace", W, H, J, noise=0.0, ambient=1.0)
     cast = m["info"]["cast"]
     assert cast.sum() > 200 and (m["I"][cast] == F(1.0)).all() and (m["D"][cast] == F(1.0)).all()      # D = ambient + vis * 0
     em = m["info"]["emitter"]
     assert em.sum() > 200 and (m["D"][em] == F(2.0)).all() and (m["I"].view(np.uint32)[em] == 0).all()
 
 
-RECOMPOSE = [("edge", n, 67, 41) for n in EDGE] + [("rec", "cornell", 96, 96), ("traced", "furnace", 48, 27), ("made", "stage", 67, 41)]
+RECOMPOSE = [("edge", n, 67, 41) for n in sh.EDGE] + [("rec", "cornell", 96, 96), ("traced", "furnace", 48, 27), ("made", "stage", 67, 41)]
 
 
 @pytest.mark.parametrize("noise", [0.0, 0.6, 1.0])
@@ -233,7 +169,7 @@ def test_two_denoised_terms_recomposed_beat_the_noisy_frame_after_eight_static_f
     import quality_model as qm
     from temporal_harness import scales
     W, H, N = 64, 36, 8
-    geoms, cam, lk = tss._example_scene()
+    geoms, cam, lk = sh.example_scene()
     p1 = pkg.reference_defaults().set(temporal_enable=1, spatial_enable=1)
     p2 = pkg.reference_defaults().set(temporal_enable=1, spatial_enable=1, sepcolor=1, addcolor=0)
     for p in (p1, p2):
@@ -263,61 +199,38 @@ def test_two_denoised_terms_recomposed_beat_the_noisy_frame_after_eight_static_f
 
 
 # ---- GPU: the split draw ---------------------------------------------------------------------------------------------------------------
-def _split_buffers(W, H, rgb=True):
-    import torch
-    img = lambda: torch.full((H, W, 3), float("nan"), dtype=torch.float32, device="cuda")      # noqa: E731
-    return dict(D=img(), I=img(), color=img() if rgb else None, gb=torch.empty((H * W * 52,), dtype=torch.uint8, device="cuda"))
-
-
-def _split_host(pkg, b, W, H):
-    return dict(D=b["D"].cpu().numpy(), I=b["I"].cpu().numpy(), color=None if b["color"] is None else b["color"].cpu().numpy(),
-                gb=b["gb"].cpu().numpy().view(pkg.synth.GBUFFER_DTYPE).reshape(H, W))
-
-
-def _draw_split(pkg, scene, W, H, s, lt, J, sec=1, ambient=0.15, frame=FRAME, seed=SEED, noise=0.6, stream=None, bufs=None, rgb=True, sync=True):
-    import torch
-    b = bufs or _split_buffers(W, H, rgb)
-    light = pkg.binding.SvgfSceneLight.make(lt["centre"], lt["edge_u"], lt["edge_v"], lt["samples"])
-    scene.draw_traced_split(b["D"], b["I"], b["gb"], W, H, s["cam"], light, frame, bounce_samples=J, ambient=ambient, shadow_secondary=sec,
-                            seed=seed, noise=noise, fireflies=0.02 if noise else 0.0, out_rgb=b["color"], stream=stream)
-    if not sync:
-        return None
-    torch.cuda.synchronize()
-    return _split_host(pkg, b, W, H)
-
-
 @pytest.mark.gpu
-@pytest.mark.parametrize("W,H", SIZES)
+@pytest.mark.parametrize("W,H", sh.SIZES)
 def test_split_sizes_and_seams(pkg, W, H):
-    s = tss._edge("B")[0]
-    scene = trs._create(pkg, s)
-    m = _split("edge", "B", W, H, 3, samples=2)
-    got = _draw_split(pkg, scene, W, H, s, m["lt"], 3)
-    traced = tts._draw(pkg, scene, W, H, s, m["lt"], 3)
+    s = sh.edge("B")[0]
+    scene = sh.create(pkg, s)
+    m = sh.split_model("edge", "B", W, H, 3, samples=2)
+    got = sh.draw(pkg, sh.TRACED, scene, W, H, s, m["lt"], sh.trace_args(3), split=True)
+    traced = sh.draw(pkg, sh.TRACED, scene, W, H, s, m["lt"], sh.trace_args(3))
     scene.free()
-    _no_difference(got, m, f"scene B {W}x{H}, 3 bounce samples")
-    tts._no_difference((got["color"], got["gb"]), traced, f"scene B {W}x{H}: split draw vs svgf_trace_draw")
+    sh.same(got, m, f"scene B {W}x{H}, 3 bounce samples", split=True)
+    sh.same((got["color"], got["gb"]), traced, f"scene B {W}x{H}: split draw vs svgf_trace_draw")
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("name", EDGE)
+@pytest.mark.parametrize("name", sh.EDGE)
 def test_split_edge_scene_equals_the_model_and_the_traced_draw(pkg, name):
     W, H = 67, 41
-    s = tss._edge(name)[0]
-    scene = trs._create(pkg, s)
+    s = sh.edge(name)[0]
+    scene = sh.create(pkg, s)
     lit = 0
     for J in (0, 1, 8):
         for sec in (0, 1):
             for point in (True, False):
-                m = _split("edge", name, W, H, J, sec, samples=1, point=point)
+                m = sh.split_model("edge", name, W, H, J, sec, samples=1, point=point)
                 versus = J == 8 and not point
                 rgb = (J + sec) % 2 == 0 or point or versus          # out_rgb NULL on some of them
-                got = _draw_split(pkg, scene, W, H, s, m["lt"], J, sec, rgb=rgb)
-                _no_difference(got, m, f"scene {name}, {J} bounce samples, secondary shadow {sec}, {'point' if point else 'area'} light, "
-                               f"out_rgb {'given' if rgb else 'NULL'}", rgb=rgb)
+                got = sh.draw(pkg, sh.TRACED, scene, W, H, s, m["lt"], sh.trace_args(J, sec), split=True, rgb=rgb)
+                sh.same(got, m, f"scene {name}, {J} bounce samples, secondary shadow {sec}, {'point' if point else 'area'} light, "
+                        f"out_rgb {'given' if rgb else 'NULL'}", split=True, rgb=rgb)
                 lit += int((m["I"] > 0).any(axis=-1).sum())
                 if versus:
-                    tts._no_difference((got["color"], got["gb"]), tts._draw(pkg, scene, W, H, s, m["lt"], J, sec), f"scene {name} vs svgf_trace_draw")
+                    sh.same((got["color"], got["gb"]), sh.draw(pkg, sh.TRACED, scene, W, H, s, m["lt"], sh.trace_args(J, sec)), f"scene {name} vs svgf_trace_draw")
     scene.free()
     assert lit > 0
 
@@ -327,13 +240,13 @@ def test_split_cornell_furnace_and_nan_normals(pkg):
     for kind, name, W, H, J, kw in (("rec", "cornell", 96, 96, 3, {}), ("traced", "furnace", 48, 27, 3, dict(noise=0.0, ambient=1.0)),
                                     ("plain", "D", 67, 41, 3, dict(samples=2)), ("made", "stage", 67, 41, 3, dict(samples=2))):
         rec = kind == "rec"
-        s = tts._input(kind, name)[0]
-        scene = trs._create(pkg, s)
-        m = _split(kind, name, W, H, J, frame=0 if rec else FRAME, seed=1 if rec else SEED, **kw)
-        got = _draw_split(pkg, scene, W, H, s, m["lt"], J, ambient=kw.get("ambient", 0.15), noise=kw.get("noise", 0.6), frame=0 if rec else FRAME,
-                          seed=1 if rec else SEED)
+        s = sh.scene_input(kind, name)[0]
+        scene = sh.create(pkg, s)
+        m = sh.split_model(kind, name, W, H, J, frame=0 if rec else FRAME, seed=1 if rec else SEED, **kw)
+        args = sh.trace_args(J, ambient=kw.get("ambient", 0.15), noise=kw.get("noise", 0.6))
+        got = sh.draw(pkg, sh.TRACED, scene, W, H, s, m["lt"], args, split=True, frame=0 if rec else FRAME, seed=1 if rec else SEED)
         scene.free()
-        _no_difference(got, m, f"{name} {W}x{H}")
+        sh.same(got, m, f"{name} {W}x{H}", split=True)
         if name == "furnace":
             assert (got["I"][m["info"]["cast"]] == F(1.0)).all()
 
@@ -341,38 +254,18 @@ def test_split_cornell_furnace_and_nan_normals(pkg):
 @pytest.mark.gpu
 @pytest.mark.parametrize("rgb", [True, False])
 def test_split_planar_target(pkg, rgb):
-    import torch
-    from temporal_harness import _hip
     W, H = 67, 41
-    s = tss._edge("F_cube")[0]
-    m = _split("edge", "F_cube", W, H, 3, samples=2)
-    scene = trs._create(pkg, s)
-    den = pkg.Denoiser(W, H, 0)
-    planes = den.planar_gbuffer()
-    b = _split_buffers(W, H, rgb)
-    lt = m["lt"]
-    scene.draw_traced_split(b["D"], b["I"], planes, W, H, s["cam"], pkg.binding.SvgfSceneLight.make(lt["centre"], lt["edge_u"], lt["edge_v"], 2), FRAME,
-                            bounce_samples=3, seed=SEED, out_rgb=b["color"])
-    torch.cuda.synchronize()
-    hip = _hip()
-    hip.hipMemcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
-    gb = np.zeros((H, W), dtype=pkg.synth.GBUFFER_DTYPE)
-    for field, ptr in (("normal", planes.normal), ("position", planes.position), ("albedo", planes.albedo), ("geomId", planes.geom_id)):
-        host = np.zeros((H, W, 3) if field != "geomId" else (H, W), F if field != "geomId" else np.int32)
-        assert hip.hipMemcpy(host.ctypes.data, ptr, host.nbytes, 2) == 0
-        gb[field] = host
-    gb["ialbedo"] = F(1.0)
-    got = dict(_split_host(pkg, b, W, H), gb=gb)
-    den.free(); scene.free()
-    _no_difference(got, m, f"scene F_cube, planar target, out_rgb {'given' if rgb else 'NULL'}", rgb=rgb)
+    m = sh.split_model("edge", "F_cube", W, H, 3, samples=2)
+    sh.check_planar_target(pkg, sh.TRACED, sh.case(sh.edge("F_cube")[0], W, H, m["lt"], sh.trace_args(3)), m,
+                           f"scene F_cube, planar target, out_rgb {'given' if rgb else 'NULL'}", forms=(True,), rgb=rgb)
 
 
 @functools.lru_cache(maxsize=None)
 def _block_split(f, W, H, J, noise=0.6):
     """Frame f of f15's turning block under f16's area light: the split model on the posed arrays."""
-    s, tables = tas._block_inputs()
+    s, tables = sh.block_inputs()
     ps = pm.posed_scene(s, tables[f])
-    (col, gb), info, lt = tts._block_frame(f, W, H, J, 1, noise)
+    (col, gb), info, lt = sh.traced_block_frame(f, W, H, J, 1, noise)
     emit = spm.emittance_plane(W, H, ps["cam"], ps["geoms"], None, None, None)
     D, I, col, gb, info = spm.render(W, H, f, ps["cam"], ps["geoms"], None, None, None, None, None, None, lt, stm.params(J), seed=3, noise=noise,   # noqa: E741
                                      fireflies=0.02 if noise else 0.0, traced=(col, gb, info), emittance=emit)
@@ -382,17 +275,18 @@ def _block_split(f, W, H, J, noise=0.6):
 @pytest.mark.gpu
 def test_the_split_follows_the_pose(pkg):
     W, H = 96, 96
-    s, tables = tas._block_inputs()
-    scene = trs._create(pkg, s)
+    s, tables = sh.block_inputs()
+    scene = sh.create(pkg, s)
     lt = _block_split(0, W, H, 2)["lt"]
-    D, I, col, gb, info = spm.render(W, H, 0, *tss._args(s), lt, stm.params(2), seed=3)      # the scene at rest, as uploaded     # noqa: E741
-    _no_difference(_draw_split(pkg, scene, W, H, s, lt, 2, frame=0, seed=3), dict(D=D, I=I, color=col, gb=gb), "turning block, before any pose")
+    D, I, col, gb, info = spm.render(W, H, 0, *sh.args_of(s), lt, stm.params(2), seed=3)      # the scene at rest, as uploaded     # noqa: E741
+    sh.same(sh.draw(pkg, sh.TRACED, scene, W, H, s, lt, sh.trace_args(2), split=True, frame=0, seed=3), dict(D=D, I=I, color=col, gb=gb),
+            "turning block, before any pose", split=True)
     scene.enable_pose(len(s["geoms"]))
     terms = []
     for f in (0, 2):
         m = _block_split(f, W, H, 2)
-        scene.pose(tas._dev(tables[f]))
-        _no_difference(_draw_split(pkg, scene, W, H, s, m["lt"], 2, frame=f, seed=3), m, f"turning block, pose {f}")
+        scene.pose(sh.dev(tables[f]))
+        sh.same(sh.draw(pkg, sh.TRACED, scene, W, H, s, m["lt"], sh.trace_args(2), split=True, frame=f, seed=3), m, f"turning block, pose {f}", split=True)
         terms.append(m)
     scene.free()
     assert int((terms[0]["I"] != terms[1]["I"]).any(axis=-1).sum()) > 50 and int((terms[0]["D"] != terms[1]["D"]).any(axis=-1).sum()) > 50
@@ -400,90 +294,47 @@ def test_the_split_follows_the_pose(pkg):
 
 @pytest.mark.gpu
 def test_eight_split_draws_queued_without_host_waits(pkg):
-    import torch
     W, H = 67, 41
-    s = tss._edge("A")[0]
-    scene = trs._create(pkg, s)
-    st = _OwnStream()
-    bufs = [_split_buffers(W, H) for _ in range(8)]
-    torch.cuda.synchronize()
-    lt = _split("edge", "A", W, H, 2)["lt"]
-    for f, b in enumerate(bufs):
-        _draw_split(pkg, scene, W, H, s, lt, 2, frame=f, stream=st, bufs=b, sync=False)
-    st.close()
-    for f, b in enumerate(bufs):
-        _no_difference(_split_host(pkg, b, W, H), _split("edge", "A", W, H, 2, frame=f), f"queued split draw, frame {f}")
-    scene.free()
+    lt = sh.split_model("edge", "A", W, H, 2)["lt"]
+    sh.check_queued(pkg, sh.TRACED, sh.case(sh.edge("A")[0], W, H, lt, sh.trace_args(2)), lambda f: sh.split_model("edge", "A", W, H, 2, frame=f),
+                    "queued split draw", split=True)
 
 
 @pytest.mark.gpu
 def test_a_captured_split_draw_is_one_kernel_node_and_replays_the_same_bits(pkg):
-    import torch
-    hip = tas._graph_api()
     W, H = 67, 41
-    s = tss._edge("B")[0]
-    m = _split("edge", "B", W, H, 3)
-    scene = trs._create(pkg, s)
-    st = _OwnStream()
-    b = _split_buffers(W, H)
-    torch.cuda.synchronize()
-    _draw_split(pkg, scene, W, H, s, m["lt"], 3, stream=st, bufs=b, sync=False)       # eager first: a first launch may set kernel attributes
-    st.synchronize()
-    graph, gexec = ctypes.c_void_p(), ctypes.c_void_p()
-    assert hip.hipStreamBeginCapture(st.cuda_stream, 2) == 0
-    _draw_split(pkg, scene, W, H, s, m["lt"], 3, stream=st, bufs=b, sync=False)       # recorded, not executed
-    assert hip.hipStreamEndCapture(st.cuda_stream, ctypes.byref(graph)) == 0 and graph.value
-    types = tas._node_types(hip, graph)
-    assert hip.hipGraphInstantiate(ctypes.byref(gexec), graph, None, None, 0) == 0
-    with torch.cuda.stream(st.torch):
-        for k in ("D", "I", "color", "gb"):
-            b[k].zero_()
-    assert hip.hipGraphLaunch(gexec, st.cuda_stream) == 0
-    st.synchronize()
-    got = _split_host(pkg, b, W, H)
-    hip.hipGraphExecDestroy(gexec); hip.hipGraphDestroy(graph)
-    st.close()
-    scene.free()
-    print(f"captured split draw = node types {types}")
-    assert types == [0], types
-    _no_difference(got, m, "replayed split draw")
+    m = sh.split_model("edge", "B", W, H, 3)
+    sh.check_captured(pkg, sh.TRACED, sh.case(sh.edge("B")[0], W, H, m["lt"], sh.trace_args(3)), m, "split draw", split=True)
 
 
 @pytest.mark.gpu
 def test_every_error_code_of_the_split_draw(pkg):
     import torch
     B = pkg.binding
-    s = tss._edge("B")[0]
-    scene = trs._create(pkg, s)
+    s = sh.edge("B")[0]
+    scene = sh.create(pkg, s)
     lib = pkg.load_split_library()
-    cam, sp, planes = B.SvgfCamera(), B.SvgfSynthParams(), B.SvgfPlanarGBuffer()
+    c, p = ctypes.byref(B.SvgfCamera()), ctypes.byref(B.SvgfSynthParams())
     ok = ctypes.byref(B.SvgfSceneLight.make((0, 1, 0), (1, 0, 0), (0, 0, 1), 4))
     tp = ctypes.byref(B.SvgfTraceParams(1, 0.15, 1))
-    c, p = ctypes.byref(cam), ctypes.byref(sp)
     guard = torch.full((64,), 7.0, dtype=torch.float32, device="cuda")       # every pointer below is this buffer: a refused call writes nothing
     a = guard.data_ptr()
     f = lambda h=scene.h, d=a, i=a + 16, rgb=a, gb=a, pl=None, w=1, hh=1, cm=c, spp=p, lt=ok, t=tp: lib.svgf_trace_draw_split(   # noqa: E731
         h, d, i, rgb, gb, pl, w, hh, cm, spp, lt, t, None)
     assert f(d=None) == -1 and f(i=None) == -1 and f(d=a, i=a) == -1
-    assert f(h=None) == -1 and f(w=0) == -1 and f(hh=-1) == -1 and f(cm=None) == -1 and f(spp=None) == -1 and f(lt=None) == -1 and f(t=None) == -1
-    assert f(gb=None) == -1 and f(pl=ctypes.byref(planes)) == -1 and f(gb=None, pl=ctypes.byref(planes)) == -1
-    assert f(w=1 << 14, hh=1 << 13) == -5
-    for n in (0, 65):
-        assert f(lt=ctypes.byref(B.SvgfSceneLight.make((0, 1, 0), samples=n))) == -1
-    for J, amb, sec in ((-1, 0.15, 1), (9, 0.15, 1), (1, float("nan"), 1), (1, float("inf"), 1), (1, -0.5, 1), (1, 0.15, 2), (1, 0.15, -1)):
-        assert f(t=ctypes.byref(B.SvgfTraceParams(J, amb, sec))) == -1, (J, amb, sec)
+    sh.check_common_refusals(B, f, (B.SvgfTraceParams, sh.BAD_TRACE))
     torch.cuda.synchronize()
     assert (guard.cpu().numpy() == F(7.0)).all()
     W, H = 7, 5
-    m = _split("edge", "B", W, H, 3)
-    _no_difference(_draw_split(pkg, scene, W, H, s, m["lt"], 3), m, "after the refused calls")
+    m = sh.split_model("edge", "B", W, H, 3)
+    sh.same(sh.draw(pkg, sh.TRACED, scene, W, H, s, m["lt"], sh.trace_args(3), split=True), m, "after the refused calls", split=True)
     scene.free()
 
 
 # ---- GPU: the recomposition ------------------------------------------------------------------------------------------------------------
 # The grid is not capped (one thread per group of four pixels, at most 2^27 / 4 groups): there is no second grid-stride turn to reach.
-# 67 x 41 = 2747 pixels is 686 groups: three blocks of the 16-byte path; the four SIZES stay inside one.
-COMPOSE_SIZES = SIZES + [(67, 41)]
+# 67 x 41 = 2747 pixels is 686 groups: three blocks of the 16-byte path; the four sh.SIZES stay inside one.
+COMPOSE_SIZES = sh.SIZES + [(67, 41)]
 
 
 @functools.lru_cache(maxsize=None)
@@ -511,20 +362,30 @@ def _gbuffer_dtype():
     return ge.load_package().synth.GBUFFER_DTYPE
 
 
+def _offset_dev(a, offset_floats=0):
+    """The array on the device, `offset_floats` floats behind a 16-byte boundary."""
+    import torch
+    flat = torch.from_numpy(np.ascontiguousarray(a)).reshape(-1)
+    buf = torch.zeros((flat.numel() + 4,), dtype=flat.dtype, device="cuda")
+    view = buf[offset_floats:offset_floats + flat.numel()]
+    view.copy_(flat)
+    assert buf.data_ptr() % 16 == 0 and view.data_ptr() % 16 == 4 * offset_floats
+    return view
+
+
 def _run_compose(pkg, W, H, special=False, layout="aos", off=(0, 0, 0, 0), alias=None, stream=None, twice=False):
     """off: floats behind a 16-byte boundary of (out, direct, indirect, albedo plane); alias: None, "direct" or "indirect"."""
     import torch
-    from test_quality_meter import _dev
     D, I, gb, a, want = _compose_inputs(W, H, special)      # noqa: E741
-    d, i = _dev(np.array(D), off[1]), _dev(np.array(I), off[2])
+    d, i = _offset_dev(np.array(D), off[1]), _offset_dev(np.array(I), off[2])
     out = {"direct": d, "indirect": i}.get(alias)
     if out is None:
-        out = _dev(np.full_like(D, np.nan), off[0])
+        out = _offset_dev(np.full_like(D, np.nan), off[0])
     if layout == "aos":
         keep = torch.from_numpy(np.ascontiguousarray(gb).view(np.uint8).reshape(-1).copy()).cuda()
         g = pkg.binding.guide(gbuffer=keep)
     else:
-        keep = _dev(np.array(a), off[3])
+        keep = _offset_dev(np.array(a), off[3])
         g = pkg.binding.guide(albedo=keep)
     torch.cuda.synchronize()
     for _ in range(2 if twice and alias is None else 1):
@@ -553,7 +414,7 @@ def test_compose_equals_the_model(pkg, W, H, layout):
 def test_compose_twice_and_on_another_stream(pkg):
     import torch
     W, H = 67, 41
-    st = _OwnStream()
+    st = sh.OwnStream()
     for layout in ("aos", "planar"):
         assert _run_compose(pkg, W, H, True, layout, twice=True)[0] == 0
         torch.cuda.synchronize()
@@ -564,29 +425,24 @@ def test_compose_twice_and_on_another_stream(pkg):
 @pytest.mark.gpu
 def test_a_captured_compose_is_one_kernel_node(pkg):
     import torch
-    hip = tas._graph_api()
     W, H = 67, 41
     D, I, gb, a, want = _compose_inputs(W, H, True)      # noqa: E741
-    st = _OwnStream()
+    st = sh.OwnStream()
     d, i, out = torch.from_numpy(np.array(D)).cuda(), torch.from_numpy(np.array(I)).cuda(), torch.zeros((W * H, 3), dtype=torch.float32, device="cuda")
     tex = torch.from_numpy(np.ascontiguousarray(gb).view(np.uint8).reshape(-1).copy()).cuda()
     torch.cuda.synchronize()
-    pkg.trace_compose(out, d, i, tex, W, H, stream=st)
+    record = lambda: pkg.trace_compose(out, d, i, tex, W, H, stream=st)      # noqa: E731
+    record()
     st.synchronize()
-    graph, gexec = ctypes.c_void_p(), ctypes.c_void_p()
-    assert hip.hipStreamBeginCapture(st.cuda_stream, 2) == 0
-    pkg.trace_compose(out, d, i, tex, W, H, stream=st)
-    assert hip.hipStreamEndCapture(st.cuda_stream, ctypes.byref(graph)) == 0 and graph.value
-    types = tas._node_types(hip, graph)
-    assert hip.hipGraphInstantiate(ctypes.byref(gexec), graph, None, None, 0) == 0
+    graph = sh.Captured(st, record)
     with torch.cuda.stream(st.torch):
         out.zero_()
-    assert hip.hipGraphLaunch(gexec, st.cuda_stream) == 0
+    graph.launch()
     st.synchronize()
     got = out.cpu().numpy()
-    hip.hipGraphExecDestroy(gexec); hip.hipGraphDestroy(graph)
+    graph.destroy()
     st.close()
-    assert types == [0], types
+    assert graph.types == [0], graph.types
     assert not differing(got[None], want[None]).any()
 
 
@@ -597,56 +453,6 @@ def test_pose_split_draw_two_denoises_compose_sequence(pkg, orc):
     each term in a context of its own (temporal pass, sepcolor 1 / addcolor 0, the object motion table on; the f8 firefly filter on the
     indirect context only) -> svgf_trace_compose.  Each context against tests/temporal_model.py behind tests/firefly_model.py, the
     composed image against compose() of the two outputs, all on bits."""
-    import torch
-    import firefly_model as fm
-    import temporal_model as tm
-    from temporal_harness import assert_frames_equal, read_states, scales, synth_params
     W, H, N = 128, 72, 4
-    s, tables = tas._block_inputs()
-    tables = tables[:N]
-    n = len(s["geoms"])
-    held, frames, motion = pkg.binding.pose_identity(n), [], []
-    for f, t in enumerate(tables):
-        m = _block_split(f, W, H, 1)
-        frames.append(m)
-        motion.append(pm.motion_rows(held, t))
-        held = t
-    lt = frames[0]["lt"]
-    M = orc.view_matrix(pkg, s["cam"])
-    p = synth_params(pkg, W, H, sepcolor=1, addcolor=0)
-    RANK, SCALE = 2, 1.0
-    want = {}
-    for key, rank in (("D", 0), ("I", RANK)):
-        fed = [(fm.firefly_filter(np.asarray(m[key], F).reshape(H, W, 3), rank, SCALE), m["gb"].reshape(H, W)) for m in frames]
-        want[key] = tm.run_sequence(fed, tables=motion, views=[M] * N, scale=scales(pkg, W, H), radius=0, k=0.0)
-    scene = trs._create(pkg, s)
-    scene.enable_pose(n)
-    dens = {"D": pkg.Denoiser(W, H), "I": pkg.Denoiser(W, H)}
-    t_x = tas._motion_buffer(n)
-    for key, den in dens.items():
-        den.set_capture(True)
-        den.set_object_motion(t_x)
-        den.set_firefly_filter(RANK if key == "I" else 0, SCALE)
-    b = _split_buffers(W, H, rgb=False)
-    outs = {k: torch.empty((H, W, 3), dtype=torch.float32, device="cuda") for k in ("D", "I", "C")}
-    got = {"D": [], "I": []}
-    try:
-        for f, t in enumerate(tables):
-            scene.pose(tas._dev(t), t_x)
-            _draw_split(pkg, scene, W, H, s, lt, 1, frame=f, seed=3, bufs=b, sync=False)
-            for key, den in dens.items():
-                den.denoise(outs[key], b[key], b["gb"], s["cam"], p)
-            pkg.trace_compose(outs["C"], outs["D"], outs["I"], b["gb"], W, H)
-            torch.cuda.synchronize()
-            for key, den in dens.items():
-                got[key].append(read_states(den))
-            h = {k: v.cpu().numpy() for k, v in outs.items()}
-            gb = frames[f]["gb"]
-            comp = spm.compose((gb["albedo"] * gb["ialbedo"]).astype(F), h["D"], h["I"])
-            assert not differing(h["C"], comp).any(), f"frame {f}: the composed image"
-    finally:
-        for den in dens.values():
-            den.free()
-        scene.free()
-    assert_frames_equal(got["D"], want["D"], "direct context")
-    assert_frames_equal(got["I"], want["I"], "indirect context, firefly filter on")
+    sh.run_split_denoise_compose(pkg, orc, sh.TRACED, [_block_split(f, W, H, 1) for f in range(N)], W, H, sh.trace_args(1),
+                                 ("direct context", "indirect context, firefly filter on"), form="filtered")

@@ -19,67 +19,18 @@ import numpy as np
 import pytest
 
 import scene_gloss_model as gm
+import scene_harness as sh
+import scene_path_model as spm
 import scene_pose_model as pm
+import scene_shadow_model as ssm
 import scene_split_model as splm
 import scene_virtual_model as vm
 import temporal_model as tm
-import test_animated_scene as tas
-import test_gloss_scene as tgs
-import test_path_scene as tps
-import test_resident_scene as trs
-import test_shadowed_scene as tss
-import test_split_scene as tsp
-import test_traced_scene as tts
 from conftest import ROOT
-from test_scene_model import FRAME, SEED, differing
+from test_scene_model import SEED, differing
 
 F = np.float32
-SIZES = tss.SIZES
-W0, H0 = tgs.W0, tgs.H0
-
-
-# ---- inputs ------------------------------------------------------------------------------------------------------------------------------
-@functools.lru_cache(maxsize=None)
-def _mirror_hall():
-    """Two full mirrors facing each other - the f16 room's back wall (id 1) and a wall behind the camera (id 5) - with a glass sphere
-    (id 6) and an emitting panel that faces the back wall (id 7) between them, the room's block taken out: the chains reach the cap
-    (mirror to mirror), miss (the room is open at the top and between the floor and the wall behind the camera) and end on the emitter
-    (the panel's reflection in the back wall)."""
-    import __graft_entry__ as ge
-    z = (0, 0, 0)
-    s, lk = tgs._room(ge.load_package(), (0, (0, 5, 12.0), z, (12, 10, 0.2), (0.8, 0.8, 0.7), 0.0), (1, (1.5, 2.0, -1.0), z, (2.5, 2.5, 2.5), (0.95, 0.95, 0.95), 0.0),
-                      (0, (0.0, 9.0, 6.5), z, (12, 4, 0.2), (1, 1, 1), 4.0), block=False)
-    return s, lk, gm.table(8, g1=(1.0, 0.0, 1.0, (0.9, 0.9, 0.9)), g5=(1.0, 0.0, 1.0, (0.9, 0.9, 0.9)), g6=(0.0, 1.0, 1.5, (0.9, 0.8, 0.7)))
-
-
-tgs.INPUTS.setdefault("mirror_hall", _mirror_hall)          # so that test_gloss_scene._model (and its cache) serves this input too
-HALL = ("mirror_hall", W0, H0, 2, 3, 2, 1, False)
-# (the gloss case, max_chain, id_offset): what G2 draws.  tgs.CASES: glass_pair, mirror_partial, mirror_mesh, cornell 96x96, glass_pair deep
-VCASES = [(tgs.CASES[0], 8, 0), (tgs.CASES[0], 2, 100), (tgs.CASES[1], 1, 100), (tgs.CASES[1], 8, 0), (tgs.CASES[2], 2, 0), (tgs.CASES[3], 8, 100),
-          (tgs.CASES[3], 1, 0), (HALL, 1, 0), (HALL, 2, 100), (HALL, 8, 0)]
-QUEUED = (tgs.QUEUED, 4, 0)
-
-
-def _vid(vc):
-    c, mc, off = vc
-    return f"{c[0]}-J{c[3]}-K{c[4]}-chain{mc}-off{off}"
-
-
-def _what(vc):
-    return f"{tgs._what(vc[0])}, max_chain {vc[1]}, id_offset {vc[2]}"
-
-
-@functools.lru_cache(maxsize=None)
-def _vmodel(case, max_chain, id_offset, alt=None, table="own", frame=None):
-    """dict(color, gb, D, I, chain, info, first_gb, lt, frame, seed, tab): scene_virtual_model.render on test_gloss_scene's (shared,
-    unchanged) model of the case."""
-    kw = {k: v for k, v in (("table", table), ("frame", frame)) if v != ("own" if k == "table" else None)}
-    m = tgs._model(*case, **kw)                   # the keywords test_gloss_scene's own calls use, so that its cache is shared
-    name, W, H = case[:3]
-    s = tgs.INPUTS[name]()[0]
-    col, gb, D, I, chain, info = vm.render(W, H, m["frame"], *tss._args(s), m["lt"], None, m["tab"], vm.params(max_chain, id_offset), seed=m["seed"],      # noqa: E741
-                                           alt=alt, base=(m["color"], m["gb"], m["D"], m["I"], m["info"]))
-    return dict(color=col, gb=gb, D=D, I=I, chain=chain, info=info, first_gb=m["gb"], lt=m["lt"], frame=m["frame"], seed=m["seed"], tab=m["tab"])
+QUEUED = (sh.GLOSS_QUEUED, 4, 0)
 
 
 def _events(m):
@@ -114,9 +65,6 @@ def test_the_three_symbols_are_declared_listed_and_exported(pkg):
     print(f"libsvgf_gloss.so {os.path.getsize(B.LIB_GLOSS_PATH)} bytes, libsvgf_virtual.so {os.path.getsize(B.LIB_VIRTUAL_PATH)} bytes")
 
 
-BAD_VIRTUAL = [(0, 0), (-1, 0), (9, 0), (4, -1), (4, (1 << 24) + 1)]
-
-
 def test_virtual_argument_errors_without_a_device(pkg):
     """The gloss draws' refusals, then vp's; all answered before any device work (the scene is NULL throughout, which is itself
     refused, so vp's own refusals are reached only with a scene: the GPU test repeats the list with one)."""
@@ -136,19 +84,19 @@ def test_virtual_argument_errors_without_a_device(pkg):
             assert call(ctypes.byref(B.SvgfSceneLight.make((0, 1, 0), samples=n)), P) == -1, n
         assert call(L, P, pl=ctypes.byref(planes)) == -1 and call(L, P, gb=None) == -1
         assert call(L, P, w=0) == -1 and call(L, P, h=-3) == -1
-        for bad in tps.BAD_PARAMS:
+        for bad in sh.BAD_PARAMS:
             assert call(L, ctypes.byref(B.SvgfPathParams(*bad))) == -1, bad
-        for bad in BAD_VIRTUAL:
+        for bad in sh.BAD_VIRTUAL:
             assert call(L, P, v=ctypes.byref(B.SvgfVirtualParams(*bad))) == -1, bad
     assert plain(L, P, rgb=None) == -1
     assert split(L, P, d=None) == -1 and split(L, P, i=None) == -1 and split(L, P, d=5, i=5) == -1 and split(L, P, rgb=None) == -1
 
 
 # ---- C2: the model's identities --------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("vc", VCASES, ids=_vid)
+@pytest.mark.parametrize("vc", sh.VCASES, ids=sh.vid)
 def test_colour_and_first_hit_fields_are_the_gloss_models_on_bits(vc):
     case, mc, off = vc
-    ref, m = tgs._case_model(case), _vmodel(*vc)
+    ref, m = sh.gloss_model(*case), sh.vmodel(*vc)
     assert not differing(m["color"], ref["color"]).any() and not differing(m["D"], ref["D"]).any() and not differing(m["I"], ref["I"]).any()
     for f in ("albedo", "ialbedo"):
         assert not differing(m["gb"][f], ref["gb"][f]).any(), f
@@ -162,19 +110,19 @@ def test_colour_and_first_hit_fields_are_the_gloss_models_on_bits(vc):
     # the unfolded position lies on the primary ray beyond the first hit
     g = m["info"]["guide"]
     assert (g["length"][virt] > g["t0"][virt]).all()
-    print(f"{_what(vc)}: {int(virt.sum())} virtual texels, {int((m['chain'] < 0).sum())} given up; {_events(m)}")
+    print(f"{sh.virtual_what(vc)}: {int(virt.sum())} virtual texels, {int((m['chain'] < 0).sum())} given up; {_events(m)}")
 
 
 @pytest.mark.parametrize("name", ["glass_pair", "mirror_hall", "cornell"])
 def test_an_empty_or_all_diffuse_table_leaves_the_first_hit_gbuffer(name):
-    case = {"glass_pair": tgs.CASES[0], "mirror_hall": HALL, "cornell": tgs.CASES[3]}[name]
+    case = {"glass_pair": sh.GLOSS_CASES[0], "mirror_hall": sh.HALL, "cornell": sh.GLOSS_CASES[3]}[name]
     for table in (None, "empty", "diffuse"):
-        ref, m = tgs._case_model(case, table=table), _vmodel(case, 8, 100, table=table)
-        c = tsp._split_counts(m, ref)
+        ref, m = sh.gloss_model(*case, table=table), sh.vmodel(case, 8, 100, table=table)
+        c = sh.split_counts(m, ref)
         assert not any(c.values()) and not m["chain"].any(), (table, c)
     # a table none of whose fully specular objects is a first hit: mirror_mesh (partial mirrors only)
-    m = _vmodel(tgs.CASES[2], 8, 100)
-    assert not any(tsp._split_counts(m, tgs._case_model(tgs.CASES[2])).values()) and not m["chain"].any()
+    m = sh.vmodel(sh.GLOSS_CASES[2], 8, 100)
+    assert not any(sh.split_counts(m, sh.gloss_model(*sh.GLOSS_CASES[2])).values()) and not m["chain"].any()
 
 
 # ---- C3: the planar mirror in float64 --------------------------------------------------------------------------------------------------
@@ -188,8 +136,8 @@ def test_the_unfolded_position_is_the_mirror_image_of_the_seen_point():
     (again about 24) and t_1 (6), then L (1) and o + L d0 (2): about 80 roundings, each at most 2^-24 E, and the directions' errors
     are carried over a length < E, which the bound E per rounding already covers.  80 * 2^-24 * 64 = 3.1e-4."""
     tol = 80 * 2.0 ** -24 * 64
-    m = _vmodel(tgs.CASES[1], 8, 0)
-    s = tgs.INPUTS["mirror_partial"]()[0]
+    m = sh.vmodel(sh.GLOSS_CASES[1], 8, 0)
+    s = sh.INPUTS["mirror_partial"]()[0]
     wall = s["geoms"][1]
     xf = np.asarray(wall["xf"], np.float64).reshape(3, 4)
     z_plane = xf[2, 2] * 0.5 + xf[2, 3]
@@ -221,15 +169,15 @@ def test_a_virtual_texel_reprojects_to_the_pixel_that_saw_the_same_point(pkg, or
     vertical-neighbour distances of seen points - because rounding to the nearest pixel is off by at most half a pixel per axis.
     The same median for the first-hit G-buffer (which reprojects the wall, not what it shows) is printed beside it."""
     from temporal_harness import scales
-    W, H = W0, H0
-    case = tgs.CASES[1]
-    s, lk, tab = tgs.INPUTS["mirror_partial"]()
-    lt = tgs._case_model(case)["lt"]
+    W, H = sh.W0, sh.H0
+    case = sh.GLOSS_CASES[1]
+    s, lk, tab = sh.INPUTS["mirror_partial"]()
+    lt = sh.gloss_model(*case)["lt"]
     sx, sy = scales(pkg, W, H)
     out = {}
     for which, cam in (("A", s["cam"]), ("B", _moved_camera(s["cam"], 4.0))):
-        args = (cam,) + tss._args(s)[1:]
-        col, gb, D, I, chain, info = vm.render(W, H, 0, *args, lt, tgs.spm.params(1, 3, 0, 0.15, 1), tab, vm.params(4, 0), seed=SEED, noise=0.0, fireflies=0.0)      # noqa: E741
+        args = (cam,) + sh.args_of(s)[1:]
+        col, gb, D, I, chain, info = vm.render(W, H, 0, *args, lt, spm.params(1, 3, 0, 0.15, 1), tab, vm.params(4, 0), seed=SEED, noise=0.0, fireflies=0.0)      # noqa: E741
         out[which] = dict(gb=gb, chain=chain, seen=info["guide"]["seen"], first=info["first_gb"])
     M = orc.view_matrix(pkg, s["cam"])
     A, B = out["A"], out["B"]
@@ -261,19 +209,13 @@ def test_a_virtual_texel_reprojects_to_the_pixel_that_saw_the_same_point(pkg, or
 
 
 # ---- C5: coverage ----------------------------------------------------------------------------------------------------------------------
-def _counts(m, ref):
-    c = tsp._split_counts(m, ref)
-    c["chain"] = int((m["chain"] != ref["chain"]).sum())
-    return c
-
-
 def test_each_alt_acts_on_the_gpu_cases():
     for alt in vm.ALTS:
         acted = None
-        for vc in VCASES:
-            c = _counts(_vmodel(*vc, alt=alt), _vmodel(*vc))
+        for vc in sh.VCASES:
+            c = sh.chain_counts(sh.vmodel(*vc, alt=alt), sh.vmodel(*vc))
             if any(c.values()):
-                acted = (_what(vc), c)
+                acted = (sh.virtual_what(vc), c)
                 break
         print(f"`{alt}`: {acted}")
         assert acted is not None, f"`{alt}` changes no output of any GPU case"
@@ -282,10 +224,10 @@ def test_each_alt_acts_on_the_gpu_cases():
 def test_gpu_cases_cover_every_guide_event():
     total = dict.fromkeys(vm.EVENTS, 0)
     long_chains = 0
-    for vc in VCASES:
-        m = _vmodel(*vc)
+    for vc in sh.VCASES:
+        m = sh.vmodel(*vc)
         ev = _events(m)
-        print(f"{_what(vc)}: {ev}")
+        print(f"{sh.virtual_what(vc)}: {ev}")
         for e in vm.EVENTS:
             total[e] += ev[e]
         long_chains += int((m["chain"] >= 2).sum())
@@ -296,171 +238,89 @@ def test_gpu_cases_cover_every_guide_event():
 
 
 # ---- GPU -------------------------------------------------------------------------------------------------------------------------------
-def _chain_buffer(W, H):
-    import torch
-    return torch.full((H, W), -77, dtype=torch.int32, device="cuda")
+def _bound(vc, m):
+    return sh.gloss_case(vc[0], m, max_chain=vc[1], id_offset=vc[2])
 
 
-def _draw(pkg, scene, table, W, H, s, lt, J, K, R, mc, off, sec=1, frame=FRAME, seed=SEED, stream=None, bufs=None, chain=True, sync=True):
-    import torch
-    rgb, gbt, ch = bufs or (trs._buffers(W, H) + (_chain_buffer(W, H) if chain else None,))
-    scene.draw_virtual(rgb, gbt, W, H, s["cam"], tgs._light(pkg, lt), frame, table=table, paths=J, max_depth=K, rr_depth=R, shadow_secondary=sec,
-                       seed=seed, stream=stream, max_chain=mc, id_offset=off, out_chain=ch)
-    if not sync:
-        return None
-    torch.cuda.synchronize()
-    color, gb = trs._host(pkg, rgb, gbt, W, H)
-    return dict(color=color, gb=gb, chain=None if ch is None else ch.cpu().numpy())
-
-
-def _draw_split(pkg, scene, table, W, H, s, lt, J, K, R, mc, off, sec=1, frame=FRAME, seed=SEED, stream=None, bufs=None, rgb=True, chain=True, sync=True):
-    import torch
-    b = bufs or dict(tsp._split_buffers(W, H, rgb), chain=_chain_buffer(W, H) if chain else None)
-    scene.draw_virtual_split(b["D"], b["I"], b["gb"], W, H, s["cam"], tgs._light(pkg, lt), frame, table=table, paths=J, max_depth=K, rr_depth=R,
-                             shadow_secondary=sec, seed=seed, out_rgb=b["color"], stream=stream, max_chain=mc, id_offset=off, out_chain=b["chain"])
-    if not sync:
-        return None
-    torch.cuda.synchronize()
-    return dict(tsp._split_host(pkg, b, W, H), chain=None if b["chain"] is None else b["chain"].cpu().numpy())
-
-
-def _same(got, m, what, split=False, rgb=True):
-    if split:
-        tsp._no_difference(got, m, what, rgb=rgb)
-    else:
-        tts._no_difference((got["color"], got["gb"]), (m["color"], m["gb"]), what)
-    if got["chain"] is not None:
-        bad = int((got["chain"] != m["chain"]).sum())
-        print(f"{what}: differing chain counts {bad} (expected and allowed: 0)")
-        assert got["chain"].dtype == np.int32 and bad == 0, what
-
-
-def _draw_case(pkg, vc, split=False, rgb=True, chain=True, table="own"):
-    case, mc, off = vc
-    name, W, H, J, K, R, sec, point = case
-    m = _vmodel(*vc, table=table)
-    s = tgs.INPUTS[name]()[0]
-    scene = trs._create(pkg, s)
-    tb = tgs._table(pkg, m["tab"])
-    try:
-        f = _draw_split if split else _draw
-        kw = dict(rgb=rgb) if split else {}
-        return f(pkg, scene, tb, W, H, s, m["lt"], J, K, R, mc, off, sec, frame=m["frame"], seed=m["seed"], chain=chain, **kw), m
-    finally:
-        if tb is not None:
-            tb.free()
-        scene.free()
+def _draw_case(pkg, vc, **kw):
+    m = sh.vmodel(*vc)
+    return sh.draw_case(pkg, sh.VIRTUAL, _bound(vc, m), **kw), m
 
 
 # G1
 @pytest.mark.gpu
-@pytest.mark.parametrize("W,H", SIZES)
+@pytest.mark.parametrize("W,H", sh.SIZES)
 def test_virtual_sizes_and_seams(pkg, W, H):
     vc = (("mirror_hall", W, H, 2, 3, 2, 1, False), 4, 100)
     got, m = _draw_case(pkg, vc)
-    _same(got, m, _what(vc))
+    sh.same(got, m, sh.virtual_what(vc))
     got, m = _draw_case(pkg, vc, split=True)
-    _same(got, m, _what(vc) + ", split form", split=True)
+    sh.same(got, m, sh.virtual_what(vc) + ", split form", split=True)
 
 
 # G2
 @pytest.mark.gpu
-@pytest.mark.parametrize("vc", VCASES, ids=_vid)
+@pytest.mark.parametrize("vc", sh.VCASES, ids=sh.vid)
 def test_virtual_case_equals_the_model(pkg, vc):
     got, m = _draw_case(pkg, vc)
-    print(f"{_what(vc)}: {_events(m)}")
-    _same(got, m, _what(vc))
+    print(f"{sh.virtual_what(vc)}: {_events(m)}")
+    sh.same(got, m, sh.virtual_what(vc))
 
 
 # G3
 @pytest.mark.gpu
-@pytest.mark.parametrize("vc", [VCASES[1], VCASES[5], VCASES[9]], ids=_vid)
+@pytest.mark.parametrize("vc", [sh.VCASES[1], sh.VCASES[5], sh.VCASES[9]], ids=sh.vid)
 def test_virtual_split_form_with_and_without_rgb_and_chain(pkg, vc):
     for rgb, chain in ((True, True), (False, True), (True, False), (False, False)):
         got, m = _draw_case(pkg, vc, split=True, rgb=rgb, chain=chain)
-        _same(got, m, f"{_what(vc)}, out_rgb {'given' if rgb else 'NULL'}, out_chain {'given' if chain else 'NULL'}", split=True, rgb=rgb)
+        sh.same(got, m, f"{sh.virtual_what(vc)}, out_rgb {'given' if rgb else 'NULL'}, out_chain {'given' if chain else 'NULL'}", split=True, rgb=rgb)
     got, m = _draw_case(pkg, vc, chain=False)
-    _same(got, m, f"{_what(vc)}, plain form, out_chain NULL")
+    sh.same(got, m, f"{sh.virtual_what(vc)}, plain form, out_chain NULL")
     assert (m["chain"] > 0).any()
 
 
 @pytest.mark.gpu
 def test_virtual_planar_target_equals_the_model(pkg):
-    import torch
-    from temporal_harness import _hip
-    vc = VCASES[9]
-    case, mc, off = vc
-    name, W, H, J, K, R, sec, point = case
-    m = _vmodel(*vc)
-    s = tgs.INPUTS[name]()[0]
-    scene = trs._create(pkg, s)
-    table = pkg.GlossTable(m["tab"])
-    den = pkg.Denoiser(W, H, 0)
-    planes = den.planar_gbuffer()
-    hip = _hip()
-    hip.hipMemcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
-
-    def read():
-        gb = np.zeros((H, W), dtype=pkg.synth.GBUFFER_DTYPE)
-        for field, ptr in (("normal", planes.normal), ("position", planes.position), ("albedo", planes.albedo), ("geomId", planes.geom_id)):
-            host = np.zeros((H, W, 3) if field != "geomId" else (H, W), F if field != "geomId" else np.int32)
-            assert hip.hipMemcpy(host.ctypes.data, ptr, host.nbytes, 2) == 0
-            gb[field] = host
-        gb["ialbedo"] = F(1.0)
-        return gb
-
-    rgb, ch = torch.empty((H, W, 3), dtype=torch.float32, device="cuda"), _chain_buffer(W, H)
-    scene.draw_virtual(rgb, planes, W, H, s["cam"], tgs._light(pkg, m["lt"]), FRAME, table=table, paths=J, max_depth=K, rr_depth=R, shadow_secondary=sec,
-                       seed=SEED, max_chain=mc, id_offset=off, out_chain=ch)
-    torch.cuda.synchronize()
-    _same(dict(color=rgb.cpu().numpy(), gb=read(), chain=ch.cpu().numpy()), m, "mirror_hall, planar target")
-    b = dict(tsp._split_buffers(W, H), chain=_chain_buffer(W, H))
-    scene.draw_virtual_split(b["D"], b["I"], planes, W, H, s["cam"], tgs._light(pkg, m["lt"]), FRAME, table=table, paths=J, max_depth=K, rr_depth=R,
-                             shadow_secondary=sec, seed=SEED, out_rgb=b["color"], max_chain=mc, id_offset=off, out_chain=b["chain"])
-    torch.cuda.synchronize()
-    got = dict(D=b["D"].cpu().numpy(), I=b["I"].cpu().numpy(), color=b["color"].cpu().numpy(), gb=read(), chain=b["chain"].cpu().numpy())
-    den.free(); table.free(); scene.free()
-    _same(got, m, "mirror_hall, planar target, split form", split=True)
+    vc = sh.VCASES[9]
+    m = sh.vmodel(*vc)
+    sh.check_planar_target(pkg, sh.VIRTUAL, _bound(vc, m), m, "mirror_hall, planar target", forms=(False, True))
 
 
 # G4
 @pytest.mark.gpu
-@pytest.mark.parametrize("vc", VCASES, ids=_vid)
+@pytest.mark.parametrize("vc", sh.VCASES, ids=sh.vid)
 def test_colour_direct_and_indirect_are_the_gloss_librarys_on_bits(pkg, vc):
-    case, mc, off = vc
-    name, W, H, J, K, R, sec, point = case
-    m = _vmodel(*vc)
-    s = tgs.INPUTS[name]()[0]
-    scene = trs._create(pkg, s)
-    tb = tgs._table(pkg, m["tab"])
-    kw = dict(frame=m["frame"], seed=m["seed"])
-    gl = tgs._draw(pkg, scene, tb, W, H, s, m["lt"], J, K, R, sec, **kw)
-    gls = tgs._draw_split(pkg, scene, tb, W, H, s, m["lt"], J, K, R, sec, **kw)
-    v = _draw(pkg, scene, tb, W, H, s, m["lt"], J, K, R, mc, off, sec, **kw)
-    vs = _draw_split(pkg, scene, tb, W, H, s, m["lt"], J, K, R, mc, off, sec, **kw)
-    tb.free(); scene.free()
-    assert not differing(v["color"], gl[0]).any() and not differing(vs["color"], gls["color"]).any()
+    m = sh.vmodel(*vc)
+    c = _bound(vc, m)
+    scene, tb = sh.create(pkg, c["s"]), sh.tables_of(pkg, sh.GLOSS, c)
+    where = (scene, c["W"], c["H"], c["s"], c["lt"])
+    kw = dict(frame=c["frame"], seed=c["seed"], tables=tb)
+    gl, gls = (sh.draw(pkg, sh.GLOSS, *where, sh.path_args(*vc[0][3:7]), split=split, **kw) for split in (False, True))
+    v, vs = (sh.draw(pkg, sh.VIRTUAL, *where, c["args"], split=split, **kw) for split in (False, True))
+    sh.free(*tb.values()); scene.free()
+    assert not differing(v["color"], gl["color"]).any() and not differing(vs["color"], gls["color"]).any()
     assert not differing(vs["D"], gls["D"]).any() and not differing(vs["I"], gls["I"]).any()
     for f in ("albedo", "ialbedo"):
-        assert not differing(v["gb"][f], gl[1][f]).any() and not differing(vs["gb"][f], gls["gb"][f]).any()
+        assert not differing(v["gb"][f], gl["gb"][f]).any() and not differing(vs["gb"][f], gls["gb"][f]).any()
     keep = v["chain"] <= 0
     for f in ("normal", "position", "geomId"):
-        assert not differing(v["gb"][f], gl[1][f])[keep].any(), f
+        assert not differing(v["gb"][f], gl["gb"][f])[keep].any(), f
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", ["glass_pair", "mirror_hall"])
 def test_null_empty_and_all_diffuse_tables_are_the_gloss_library_on_bits(pkg, name):
-    W, H, J, K, R = W0, H0, 2, 3, 2
-    s, lk, _ = tgs.INPUTS[name]()
-    lt = tgs.ssm.light(lk["centre"], lk["edge_u"], lk["edge_v"], 1)
-    scene = trs._create(pkg, s)
+    W, H, J, K, R = sh.W0, sh.H0, 2, 3, 2
+    s, lk, _ = sh.INPUTS[name]()
+    lt = ssm.light(lk["centre"], lk["edge_u"], lk["edge_v"], 1)
+    scene = sh.create(pkg, s)
     empty, diffuse = pkg.GlossTable(None), pkg.GlossTable(gm.table(16))
     for what, table in (("NULL", None), ("an empty table", empty), ("an all-diffuse table", diffuse)):
-        plain, split = tgs._draw(pkg, scene, table, W, H, s, lt, J, K, R), tgs._draw_split(pkg, scene, table, W, H, s, lt, J, K, R)
-        v, vs = _draw(pkg, scene, table, W, H, s, lt, J, K, R, 8, 100), _draw_split(pkg, scene, table, W, H, s, lt, J, K, R, 8, 100)
-        tts._no_difference((v["color"], v["gb"]), plain, f"{name}: {what} vs svgf_gloss_draw")
-        tsp._no_difference(vs, split, f"{name}: {what} vs svgf_gloss_draw_split")
+        tb, args = dict(table=table), sh.path_args(J, K, R)
+        plain, split = (sh.draw(pkg, sh.GLOSS, scene, W, H, s, lt, args, split=sp, tables=tb) for sp in (False, True))
+        v, vs = (sh.draw(pkg, sh.VIRTUAL, scene, W, H, s, lt, dict(args, max_chain=8, id_offset=100), split=sp, tables=tb) for sp in (False, True))
+        sh.same(sh.pair(v), plain, f"{name}: {what} vs svgf_gloss_draw")
+        sh.same(vs, split, f"{name}: {what} vs svgf_gloss_draw_split", split=True, chain=False)
         assert not v["chain"].any() and not vs["chain"].any()
     empty.free(); diffuse.free()
     scene.free()
@@ -468,132 +328,67 @@ def test_null_empty_and_all_diffuse_tables_are_the_gloss_library_on_bits(pkg, na
 
 # G5
 @pytest.mark.gpu
-@pytest.mark.parametrize("vc", [VCASES[0], VCASES[9]], ids=_vid)
+@pytest.mark.parametrize("vc", [sh.VCASES[0], sh.VCASES[9]], ids=sh.vid)
 def test_compose_from_the_virtual_gbuffer_is_the_composed_gloss_frame(pkg, vc):
-    import torch
     case = vc[0]
     W, H = case[1:3]
     got, m = _draw_case(pkg, vc, split=True)
-    d, i = torch.from_numpy(got["D"]).cuda(), torch.from_numpy(got["I"]).cuda()
-    tex = torch.from_numpy(np.ascontiguousarray(got["gb"]).view(np.uint8).reshape(-1).copy()).cuda()
-    out = torch.empty((H, W, 3), dtype=torch.float32, device="cuda")
-    pkg.trace_compose(out, d, i, tex, W, H)
-    torch.cuda.synchronize()
-    ref = tgs._case_model(case)
+    ref = sh.gloss_model(*case)
     want = splm.compose((ref["gb"]["albedo"] * ref["gb"]["ialbedo"]).astype(F), ref["D"], ref["I"])
     assert (m["chain"] > 0).any()
-    assert not differing(out.cpu().numpy(), want).any(), "albedo * (D + I) through svgf_trace_compose from the virtual G-buffer"
+    assert not differing(sh.compose_on_device(pkg, got, W, H), want).any(), "albedo * (D + I) through svgf_trace_compose from the virtual G-buffer"
 
 
 # G6
 @pytest.mark.gpu
-@pytest.mark.parametrize("vc", [VCASES[4], VCASES[5]], ids=_vid)
+@pytest.mark.parametrize("vc", [sh.VCASES[4], sh.VCASES[5]], ids=sh.vid)
 def test_every_tree_draws_the_same_virtual_frame(pkg, vc):
-    case, mc, off = vc
-    name, W, H, J, K, R, sec, point = case
-    m = _vmodel(*vc)
-    s = tgs.INPUTS[name]()[0]
-    table = pkg.GlossTable(m["tab"])
-    for ml, sp in trs.BUILDS:
-        scene = trs._create(pkg, s, ml, sp)
-        got = _draw(pkg, scene, table, W, H, s, m["lt"], J, K, R, mc, off, sec, frame=m["frame"], seed=m["seed"])
-        scene.free()
-        _same(got, m, f"{name}, leaf {ml} split {sp}")
-    table.free()
+    m = sh.vmodel(*vc)
+    sh.check_every_tree(pkg, sh.VIRTUAL, _bound(vc, m), m, vc[0][0])
 
 
 @functools.lru_cache(maxsize=None)
 def _block_vmodel(f, W, H, J, K, R, mc=4, off=0):
-    """Frame f of f15's turning block, the block a full mirror: the virtual model on the posed arrays (test_gloss_scene._block_model)."""
-    g = tgs._block_model(f, W, H, J, K, R)
-    s, tables = tas._block_inputs()
+    """Frame f of f15's turning block, the block a full mirror: the virtual model on the posed arrays (on scene_harness.gloss_block_model)."""
+    g = sh.gloss_block_model(f, W, H, J, K, R)
+    s, tables = sh.block_inputs()
     ps = pm.posed_scene(s, tables[f])
-    col, gb, D, I, chain, info = vm.render(W, H, f, ps["cam"], ps["geoms"], None, None, None, None, None, None, g["lt"], None, tgs._block_table(),     # noqa: E741
+    col, gb, D, I, chain, info = vm.render(W, H, f, ps["cam"], ps["geoms"], None, None, None, None, None, None, g["lt"], None, sh.block_table(),     # noqa: E741
                                            vm.params(mc, off), seed=3, base=(g["color"], g["gb"], g["D"], g["I"], g["info"]))
     return dict(color=col, gb=gb, D=D, I=I, chain=chain, info=info, lt=g["lt"])
 
 
 @pytest.mark.gpu
 def test_the_virtual_texels_follow_the_pose(pkg):
-    W, H, J, K, R = tgs.BLOCK
-    s, tables = tas._block_inputs()
-    scene = trs._create(pkg, s)
-    table = pkg.GlossTable(tgs._block_table())
+    W, H, J, K, R = sh.BLOCK
+    s, tables = sh.block_inputs()
+    scene = sh.create(pkg, s)
+    tb, args = dict(table=pkg.GlossTable(sh.block_table())), sh.path_args(J, K, R, max_chain=4, id_offset=0)
     scene.enable_pose(len(s["geoms"]))
     pos = []
     for f in (0, 2):
         m = _block_vmodel(f, W, H, J, K, R)
         assert int((m["chain"] > 0).sum()) > 100
-        scene.pose(tas._dev(tables[f]))
-        _same(_draw(pkg, scene, table, W, H, s, m["lt"], J, K, R, 4, 0, frame=f, seed=3), m, f"mirror block, pose {f}")
-        _same(_draw_split(pkg, scene, table, W, H, s, m["lt"], J, K, R, 4, 0, frame=f, seed=3), m, f"mirror block, pose {f}, split form", split=True)
+        scene.pose(sh.dev(tables[f]))
+        for split in (False, True):
+            got = sh.draw(pkg, sh.VIRTUAL, scene, W, H, s, m["lt"], args, split=split, frame=f, seed=3, tables=tb)
+            sh.same(got, m, f"mirror block, pose {f}" + ", split form" * split, split=split)
         pos.append(m["gb"]["position"])
-    table.free(); scene.free()
+    sh.free(*tb.values()); scene.free()
     assert int((pos[0] != pos[1]).any(axis=-1).sum()) > 50
 
 
 # G7
 @pytest.mark.gpu
 def test_eight_virtual_draws_queued_without_host_waits(pkg):
-    import torch
-    case, mc, off = QUEUED
-    name, W, H, J, K, R, sec, point = case
-    s = tgs.INPUTS[name]()[0]
-    m0 = _vmodel(*QUEUED)
-    scene = trs._create(pkg, s)
-    table = pkg.GlossTable(m0["tab"])
-    st = tsp._OwnStream()
-    bufs = [trs._buffers(W, H) + (_chain_buffer(W, H),) for _ in range(8)]
-    torch.cuda.synchronize()
-    for f, b in enumerate(bufs):
-        _draw(pkg, scene, table, W, H, s, m0["lt"], J, K, R, mc, off, sec, frame=f, stream=st, bufs=b, sync=False)
-    st.close()
-    for f, (rgb, gbt, ch) in enumerate(bufs):
-        color, gb = trs._host(pkg, rgb, gbt, W, H)
-        _same(dict(color=color, gb=gb, chain=ch.cpu().numpy()), _vmodel(case, mc, off, frame=f), f"queued virtual draw, frame {f}")
-    table.free(); scene.free()
+    sh.check_queued(pkg, sh.VIRTUAL, _bound(QUEUED, sh.vmodel(*QUEUED)), lambda f: sh.vmodel(*QUEUED, frame=f), "queued virtual draw")
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("split", [False, True])
 def test_a_captured_virtual_draw_is_one_kernel_node_and_replays_the_same_bits(pkg, split):
-    import torch
-    hip = tas._graph_api()
-    case, mc, off = QUEUED
-    name, W, H, J, K, R, sec, point = case
-    s = tgs.INPUTS[name]()[0]
-    m = _vmodel(*QUEUED)
-    scene = trs._create(pkg, s)
-    table = pkg.GlossTable(m["tab"])
-    st = tsp._OwnStream()
-    b = dict(tsp._split_buffers(W, H), chain=_chain_buffer(W, H)) if split else trs._buffers(W, H) + (_chain_buffer(W, H),)
-    torch.cuda.synchronize()
-    draw = (lambda: _draw_split(pkg, scene, table, W, H, s, m["lt"], J, K, R, mc, off, sec, stream=st, bufs=b, sync=False)) if split else \
-        (lambda: _draw(pkg, scene, table, W, H, s, m["lt"], J, K, R, mc, off, sec, stream=st, bufs=b, sync=False))
-    draw()                                  # eager first: a first launch may set kernel attributes
-    st.synchronize()
-    graph, gexec = ctypes.c_void_p(), ctypes.c_void_p()
-    assert hip.hipStreamBeginCapture(st.cuda_stream, 2) == 0
-    draw()                                  # recorded, not executed
-    assert hip.hipStreamEndCapture(st.cuda_stream, ctypes.byref(graph)) == 0 and graph.value
-    types = tas._node_types(hip, graph)
-    assert hip.hipGraphInstantiate(ctypes.byref(gexec), graph, None, None, 0) == 0
-    with torch.cuda.stream(st.torch):
-        for t in (b.values() if split else b):
-            t.zero_()
-    assert hip.hipGraphLaunch(gexec, st.cuda_stream) == 0
-    st.synchronize()
-    if split:
-        got = dict(tsp._split_host(pkg, b, W, H), chain=b["chain"].cpu().numpy())
-    else:
-        color, gb = trs._host(pkg, b[0], b[1], W, H)
-        got = dict(color=color, gb=gb, chain=b[2].cpu().numpy())
-    hip.hipGraphExecDestroy(gexec); hip.hipGraphDestroy(graph)
-    st.close()
-    table.free(); scene.free()
-    print(f"captured virtual draw (split {split}) = node types {types}")
-    assert types == [0], types
-    _same(got, m, "replayed virtual draw", split=split)
+    m = sh.vmodel(*QUEUED)
+    sh.check_captured(pkg, sh.VIRTUAL, _bound(QUEUED, m), m, "virtual draw", split=split)
 
 
 # G8
@@ -601,14 +396,13 @@ def test_a_captured_virtual_draw_is_one_kernel_node_and_replays_the_same_bits(pk
 def test_every_error_code_of_both_virtual_draws(pkg):
     import torch
     B = pkg.binding
-    s, lk, tab = tgs._glass_pair()
-    scene = trs._create(pkg, s)
+    s, lk, tab = sh.glass_pair()
+    scene = sh.create(pkg, s)
     table = pkg.GlossTable(tab)
     lib = pkg.load_virtual_library()
-    cam, sp, planes = B.SvgfCamera(), B.SvgfSynthParams(), B.SvgfPlanarGBuffer()
+    c, p = ctypes.byref(B.SvgfCamera()), ctypes.byref(B.SvgfSynthParams())
     ok = ctypes.byref(B.SvgfSceneLight.make((0, 1, 0), (1, 0, 0), (0, 0, 1), 4))
     pp, vp = ctypes.byref(B.SvgfPathParams(1, 4, 2, 0.15, 1)), ctypes.byref(B.SvgfVirtualParams(4, 0))
-    c, p = ctypes.byref(cam), ctypes.byref(sp)
     guard = torch.full((64,), 7.0, dtype=torch.float32, device="cuda")       # every pointer below is this buffer: a refused call writes nothing
     a = guard.data_ptr()
     plain = lambda h=scene.h, tb=table.h, rgb=a, gb=a, pl=None, w=1, hh=1, cm=c, spp=p, lt=ok, t=pp, v=vp: lib.svgf_virtual_draw(   # noqa: E731
@@ -618,17 +412,11 @@ def test_every_error_code_of_both_virtual_draws(pkg):
     assert plain(rgb=None) == -1
     assert split(d=None) == -1 and split(i=None) == -1 and split(d=a, i=a) == -1
     for f in (plain, split):
-        assert f(h=None) == -1 and f(w=0) == -1 and f(hh=-1) == -1 and f(cm=None) == -1 and f(spp=None) == -1 and f(lt=None) == -1 and f(t=None) == -1
-        assert f(gb=None) == -1 and f(pl=ctypes.byref(planes)) == -1 and f(gb=None, pl=ctypes.byref(planes)) == -1
-        assert f(w=1 << 14, hh=1 << 13) == -5
+        sh.check_common_refusals(B, f, (B.SvgfPathParams, sh.BAD_PARAMS))
         # the gloss draw's refusals come first: an unsupported size with a bad vp is still SVGF_ERR_UNSUPPORTED
         assert f(w=1 << 14, hh=1 << 13, v=None) == -5
-        for n in (0, 65):
-            assert f(lt=ctypes.byref(B.SvgfSceneLight.make((0, 1, 0), samples=n))) == -1
-        for bad in tps.BAD_PARAMS:
-            assert f(t=ctypes.byref(B.SvgfPathParams(*bad))) == -1, bad
         assert f(v=None) == -1
-        for bad in BAD_VIRTUAL:
+        for bad in sh.BAD_VIRTUAL:
             assert f(v=ctypes.byref(B.SvgfVirtualParams(*bad))) == -1, bad
     if torch.cuda.device_count() >= 2:
         other = pkg.GlossTable(tab, device=1)
@@ -641,9 +429,10 @@ def test_every_error_code_of_both_virtual_draws(pkg):
     # the extremes that are allowed
     for mc, off in ((1, 0), (8, 1 << 24)):
         vc = (("glass_pair", 7, 5, 2, 3, 2, 1, False), mc, off)
-        m = _vmodel(*vc)
-        _same(_draw(pkg, scene, table, 7, 5, s, m["lt"], 2, 3, 2, mc, off), m, f"after the refused calls, max_chain {mc}, id_offset {off}")
-        _same(_draw_split(pkg, scene, table, 7, 5, s, m["lt"], 2, 3, 2, mc, off), m, "after the refused calls, split form", split=True)
+        m = sh.vmodel(*vc)
+        tb, args = dict(table=table), sh.path_args(2, 3, 2, max_chain=mc, id_offset=off)
+        sh.same(sh.draw(pkg, sh.VIRTUAL, scene, 7, 5, s, m["lt"], args, tables=tb), m, f"after the refused calls, max_chain {mc}, id_offset {off}")
+        sh.same(sh.draw(pkg, sh.VIRTUAL, scene, 7, 5, s, m["lt"], args, split=True, tables=tb), m, "after the refused calls, split form", split=True)
     table.free(); scene.free()
 
 
@@ -655,49 +444,14 @@ def test_pose_virtual_split_draw_two_denoises_compose_against_the_temporal_model
     svgf_trace_compose.  Every state of both contexts after every frame equals temporal_model.run_sequence fed the model's D (or I) and
     the model's VIRTUAL G-buffer, on bits; the history length kept on the pixels with chain > 0 is printed beside what the first-hit
     G-buffer keeps there in the model."""
-    import torch
-    from temporal_harness import assert_frames_equal, read_states, scales, synth_params
-    W, H, J, K, R = tgs.BLOCK
+    from temporal_harness import scales
+    W, H, J, K, R = sh.BLOCK
     N = 4
-    s, tables = tas._block_inputs()
-    n = len(s["geoms"])
     models = [_block_vmodel(f, W, H, J, K, R) for f in range(N)]
-    lt = models[0]["lt"]
-    p = synth_params(pkg, W, H, sepcolor=1, addcolor=0)
-    sx, sy = scales(pkg, W, H)
-    views = [orc.view_matrix(pkg, s["cam"])] * N
-    scene = trs._create(pkg, s)
-    scene.enable_pose(n)
-    table = pkg.GlossTable(tgs._block_table())
-    dens = {"D": pkg.Denoiser(W, H), "I": pkg.Denoiser(W, H)}
-    for den in dens.values():
-        den.set_capture(True)
-    b = dict(tsp._split_buffers(W, H, rgb=False), chain=_chain_buffer(W, H))
-    outs = {k: torch.empty((H, W, 3), dtype=torch.float32, device="cuda") for k in ("D", "I", "C")}
-    states = {"D": [], "I": []}
-    try:
-        for f in range(N):
-            scene.pose(tas._dev(tables[f]))
-            got = _draw_split(pkg, scene, table, W, H, s, lt, J, K, R, 4, 0, frame=f, seed=3, bufs=b, rgb=False)
-            _same(got, models[f], f"frame {f}", split=True, rgb=False)
-            for key, den in dens.items():
-                den.denoise(outs[key], b[key], b["gb"], s["cam"], p)
-                den.sync()
-                states[key].append(read_states(den))
-            pkg.trace_compose(outs["C"], outs["D"], outs["I"], b["gb"], W, H)
-            torch.cuda.synchronize()
-            alb = (models[f]["gb"]["albedo"] * models[f]["gb"]["ialbedo"]).astype(F)
-            want = splm.compose(alb, outs["D"].cpu().numpy(), outs["I"].cpu().numpy())
-            assert not differing(outs["C"].cpu().numpy(), want).any(), f"frame {f}: composed"
-    finally:
-        for den in dens.values():
-            den.free()
-        table.free(); scene.free()
-    ref = {}
-    for key in ("D", "I"):
-        ref[key] = tm.run_sequence([(m[key], m["gb"]) for m in models], views=views, scale=(sx, sy))
-        assert_frames_equal(states[key], ref[key], f"virtual G-buffer, term {key}")
-    first = tm.run_sequence([(m["I"], m["info"]["first_gb"]) for m in models], views=views, scale=(sx, sy))
+    states, ref = sh.run_split_denoise_compose(pkg, orc, sh.VIRTUAL, models, W, H, sh.path_args(J, K, R, max_chain=4, id_offset=0),
+                                               ("virtual G-buffer, term D", "virtual G-buffer, term I"), tab=sh.block_table())
+    views = [orc.view_matrix(pkg, sh.block_inputs()[0]["cam"])] * N
+    first = tm.run_sequence([(m["I"], m["info"]["first_gb"]) for m in models], views=views, scale=scales(pkg, W, H))
     virt = models[N - 1]["chain"] > 0
     kept_v, kept_f = ref["I"][N - 1]["hlen"][virt], first[N - 1]["hlen"][virt]
     got_v = states["I"][N - 1]["hlen"][virt]
