@@ -8,7 +8,9 @@ same frames ordered on one stream — for every position of the history level, a
 resets, on odd sizes, under a stream capture, on two caller streams used in turn without any promise (inputs_ready = 2), and with
 readers of a reused output buffer enqueued behind earlier calls.
 (tests/test_parity_gpu.py::test_back_to_back_asynchronous_frames_equal_synchronised_frames covers history levels 0 / 1 / 3 / 5 at
-1920x1080 with the state read-back.)"""
+1920x1080 with the state read-back.)
+(These frames run at their natural speed; ordering under LATE producers — each wait of the pipeline held with a gate in front of what
+it waits for — lives in tests/test_pipeline_order_gpu.py.)"""
 import ctypes
 import threading
 
