@@ -24,4 +24,5 @@ from .binding import GlossTable, SvgfSurface, load_gloss_library  # noqa: F401  
 from .binding import SvgfVirtualParams, load_virtual_library  # noqa: F401  (Scene.draw_virtual, Scene.draw_virtual_split)
 from .binding import RoughTable, SvgfRoughParams, load_rough_library  # noqa: F401  (Scene.draw_rough, Scene.draw_rough_split)
 from .binding import SvgfHighlightParams, load_highlight_library  # noqa: F401  (Scene.draw_highlight, Scene.draw_highlight_split)
+from .binding import SceneTree, SvgfLbvhParams, SvgfLbvhInfo, load_lbvh_library, lbvh_build_host  # noqa: F401  (row f24, Scene.adopt_tree)
 from .binding import STATE_PREV_NORMAL, STATE_PREV_POSITION, STATE_PREV_GEOM_ID, STATE_OUTPUT_HISTORY  # noqa: F401

@@ -46,7 +46,7 @@ EXPORTS = ["svgf_version", "svgf_params_default", "svgf_create", "svgf_destroy",
            "svgf_quality_state_bytes", "svgf_quality_windows", "svgf_quality_meter", "svgf_quality_read",
            "svgf_scene_create", "svgf_scene_destroy", "svgf_scene_info", "svgf_scene_draw", "svgf_scene_draw_planar", "svgf_bvh_build_host",
            "svgf_scene_enable_pose", "svgf_scene_pose", "svgf_scene_read", "svgf_pose_rigid", "svgf_bvh_refit_plan_host",
-           "svgf_scene_draw_shadowed", "svgf_scene_view"]
+           "svgf_scene_draw_shadowed", "svgf_scene_view", "svgf_scene_adopt_tree"]
 # every symbol include/svgf_trace.h declares (libsvgf_trace.so, the companion library of row f17)
 TRACE_EXPORTS = ["svgf_trace_draw", "svgf_trace_version"]
 # libsvgf_split.so (include/svgf_split.h, row f18)
@@ -66,6 +66,13 @@ ROUGH_EXPORTS = ["svgf_rough_table_create", "svgf_rough_table_destroy", "svgf_ro
                  "svgf_rough_version"]
 # libsvgf_highlight.so (include/svgf_highlight.h, row f23)
 HIGHLIGHT_EXPORTS = ["svgf_highlight_draw", "svgf_highlight_draw_split", "svgf_highlight_version"]
+# libsvgf_lbvh.so (include/svgf_lbvh.h, row f24): the device BVH builder - built by the companions' recipe (build.BUILDERS) and linked
+# like them, but no companion draw: not a row of COMPANIONS
+LBVH_EXPORTS = ["svgf_lbvh_create", "svgf_lbvh_build", "svgf_lbvh_attach", "svgf_lbvh_info", "svgf_lbvh_read", "svgf_lbvh_destroy",
+                "svgf_lbvh_version", "svgf_lbvh_build_host"]
+LIB_LBVH_PATH = os.path.join(_HERE, "libsvgf_lbvh.so")
+LBVH_READ_NODES, LBVH_READ_ORDER, LBVH_READ_KEYS = 0, 1, 2
+LBVH_TILE = 512
 # The companion libraries in the order they were added (build.COMPANIONS is the builder's side of this table): the short name
 # (libsvgf_<name>.so, include/svgf_<name>.h) and every symbol the header declares.
 Companion = collections.namedtuple("Companion", "name exports")
@@ -402,6 +409,7 @@ def load_library(path: str | None = None, experiments: bool = False):
     lib.svgf_scene_draw_shadowed.argtypes = [vp, vp, vp, C.POINTER(SvgfPlanarGBuffer), ip, ip, C.POINTER(SvgfCamera), C.POINTER(SvgfSynthParams),
                                              C.POINTER(SvgfSceneLight), vp]
     lib.svgf_scene_view.argtypes = [vp, C.POINTER(SvgfSceneView)]
+    lib.svgf_scene_adopt_tree.argtypes = [vp, vp, vp, ip, ip, ip]
     lib.svgf_pose_rigid.argtypes = [C.POINTER(C.c_float), C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float), vp]
     lib.svgf_bvh_refit_plan_host.argtypes = [vp, ip, ip, vp, vp, vp, vp, vp]
     if path == LIB_PATH:
@@ -488,6 +496,59 @@ def load_rough_library():
 
 def load_highlight_library():
     return _load_companion("highlight")
+
+
+class SvgfLbvhParams(C.Structure):
+    _fields_ = [("leaf_tris", C.c_int)]
+
+
+class SvgfLbvhInfo(C.Structure):
+    _fields_ = [(k, C.c_int) for k in ("n_tris", "n_leaves", "n_nodes", "leaf_tris", "idx_bits", "axis_bits", "key_bits", "depth_bound",
+                                       "launches")] + [("device_bytes", C.c_ulonglong)]
+
+
+_lbvh_lib = None
+
+
+def load_lbvh_library():
+    """Load libsvgf_lbvh.so (row f24; after the product library it links against) and declare its prototypes.  Fails loudly when it is
+    absent or was compiled against another svgf.h than the product library."""
+    global _lbvh_lib
+    if _lbvh_lib is not None:
+        return _lbvh_lib
+    product = load_library()
+    if not os.path.exists(LIB_LBVH_PATH):
+        raise SvgfError(f"{LIB_LBVH_PATH} not found: build it first (python -c 'import __graft_entry__ as g; g.build()').")
+    lib = C.CDLL(LIB_LBVH_PATH)
+    vp, ip = C.c_void_p, C.c_int
+    lib.svgf_lbvh_version.restype = ip
+    if lib.svgf_lbvh_version() != product.svgf_version():
+        raise SvgfError(f"libsvgf_lbvh.so was built for ABI {lib.svgf_lbvh_version():#x}, libsvgf_hip.so is {product.svgf_version():#x}")
+    lib.svgf_lbvh_create.argtypes = [vp, C.POINTER(SvgfLbvhParams), C.POINTER(vp)]
+    lib.svgf_lbvh_build.argtypes = [vp, vp]
+    lib.svgf_lbvh_attach.argtypes = [vp, vp]
+    lib.svgf_lbvh_info.argtypes = [vp, C.POINTER(SvgfLbvhInfo)]
+    lib.svgf_lbvh_read.argtypes = [vp, ip, vp, C.c_ulonglong]
+    lib.svgf_lbvh_destroy.argtypes = [vp]
+    lib.svgf_lbvh_destroy.restype = None
+    lib.svgf_lbvh_build_host.argtypes = [vp, ip, C.POINTER(SvgfLbvhParams), vp, vp, vp, C.POINTER(SvgfLbvhInfo)]
+    _lbvh_lib = lib
+    return lib
+
+
+def lbvh_build_host(tri_boxes, leaf_tris: int = 0):
+    """svgf_lbvh_build_host (no device needed): (nodes BVH_NODE_DTYPE[n_nodes], order int32[n_tris], keys uint64[n_tris], info dict) of
+    the padded triangle boxes `tri_boxes` (BVH_NODE_DTYPE[n_tris]; lo and hi are read)."""
+    tb = np.ascontiguousarray(tri_boxes, dtype=BVH_NODE_DTYPE)
+    n = len(tb)
+    L = int(leaf_tris) if 1 <= int(leaf_tris) <= 8 else 4
+    nodes, order, keys = np.zeros(2 * max(-(-n // L), 1), BVH_NODE_DTYPE), np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.uint64)
+    info, p = SvgfLbvhInfo(), SvgfLbvhParams(int(leaf_tris))
+    rc = load_lbvh_library().svgf_lbvh_build_host(tb.ctypes.data if n else None, n, C.byref(p), nodes.ctypes.data, order.ctypes.data,
+                                                  keys.ctypes.data, C.byref(info))
+    if rc != SVGF_OK:
+        raise SvgfError(f"svgf_lbvh_build_host failed ({rc})")
+    return nodes[:info.n_nodes].copy(), order[:n].copy(), keys[:n].copy(), {k: int(getattr(info, k)) for k, _ in SvgfLbvhInfo._fields_}
 
 
 class _DeviceTable:
@@ -1389,6 +1450,13 @@ class Scene:
                              (paths, max_depth, rr_depth, ambient, shadow_secondary), (seed, noise, fireflies, pixel_length), stream, table,
                              (max_chain, id_offset, out_chain), (rough, guide_alpha), (enable, clamp))
 
+    def adopt_tree(self, nodes=None, order=None, n_nodes: int = 0, n_leaves: int = 0, depth_bound: int = 0):
+        """svgf_scene_adopt_tree (row f24; host only): from now on every draw walks the DEVICE arrays `nodes` / `order` (torch tensors
+        or raw pointers) in place of the scene's own tree; nodes=None detaches.  SceneTree.attach() does this with a tree it built."""
+        rc = self.lib.svgf_scene_adopt_tree(self.h, _ptr(nodes), _ptr(order), int(n_nodes), int(n_leaves), int(depth_bound))
+        if rc != SVGF_OK:
+            raise SvgfError(f"svgf_scene_adopt_tree failed ({rc})")
+
     def view(self) -> dict:
         """svgf_scene_view (host only): the device index, the counts and the device pointers the draws read, as integers (0 = NULL)."""
         v = SvgfSceneView()
@@ -1429,6 +1497,62 @@ class Scene:
         if self.h:
             self.lib.svgf_scene_destroy(self.h)
             self.h = None
+
+
+class SceneTree:
+    """A linear BVH over a resident scene's triangles as drawn, built on the device by libsvgf_lbvh.so (row f24): create once (one
+    allocation; not under capture), build(stream) per frame behind the pose - info()["launches"] kernel launches and nothing else, legal
+    under capture - attach() once, detach() before free().  Usable as a context manager."""
+
+    def __init__(self, handle, scene):
+        self.lib, self.h, self.scene = load_lbvh_library(), handle, scene
+
+    @classmethod
+    def create(cls, scene, leaf_tris: int = 0):
+        h, p = C.c_void_p(), SvgfLbvhParams(int(leaf_tris))
+        rc = load_lbvh_library().svgf_lbvh_create(scene.h, C.byref(p), C.byref(h))
+        if rc != SVGF_OK:
+            raise SvgfError(f"svgf_lbvh_create failed ({rc})")
+        return cls(h, scene)
+
+    def _call(self, name, *args):
+        rc = getattr(self.lib, name)(self.h, *args)
+        if rc != SVGF_OK:
+            raise SvgfError(f"{name} failed ({rc})")
+
+    def build(self, stream=None):
+        """svgf_lbvh_build: asynchronous on `stream`; never waits."""
+        self._call("svgf_lbvh_build", _stream(stream))
+
+    def attach(self):
+        self._call("svgf_lbvh_attach", self.scene.h)
+
+    def detach(self):
+        self.scene.adopt_tree(None)
+
+    def info(self) -> dict:
+        i = SvgfLbvhInfo()
+        self._call("svgf_lbvh_info", C.byref(i))
+        return {k: int(getattr(i, k)) for k, _ in SvgfLbvhInfo._fields_}
+
+    def read(self, which: int) -> np.ndarray:
+        """svgf_lbvh_read (blocking): 0 nodes BVH_NODE_DTYPE[n_nodes], 1 order int32[n_tris], 2 the sorted keys uint64[n_tris]."""
+        i = self.info()
+        n, dt = {0: (i["n_nodes"], BVH_NODE_DTYPE), 1: (i["n_tris"], np.int32), 2: (i["n_tris"], np.uint64)}[int(which)]
+        out = np.zeros(n, dt)
+        self._call("svgf_lbvh_read", int(which), out.ctypes.data, out.nbytes)
+        return out
+
+    def free(self):
+        if self.h:
+            self.lib.svgf_lbvh_destroy(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.free()
 
 
 ResidentScene = Scene

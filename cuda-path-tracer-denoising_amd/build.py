@@ -35,6 +35,13 @@ COMPANIONS = (
     Companion("highlight", ["svgf_scene_highlight.hip"],                                                               # f23: the light's GGX term
               ["svgf_trace.h", "svgf_path.h", "svgf_gloss.h", "svgf_virtual.h", "svgf_rough.h", "svgf_highlight.h"]),
 )
+# Libraries built by the companions' recipe that are no companion draw (no Scene.draw_* method, no example, not part of build_all()):
+# the same row, and the flags the row's sources need on top of HIPCC_FLAGS.  Row f24's device BVH builder states its result as
+# float32 arithmetic with one rounding per operation, in kernels and in the host builder alike: -ffp-contract=off.
+Builder = collections.namedtuple("Builder", "name sources headers flags")
+BUILDERS = (
+    Builder("lbvh", ["svgf_lbvh.hip", "svgf_lbvh_host.cpp"], ["svgf_lbvh.h"], ["-ffp-contract=off"]),                  # f24: LBVH on the device
+)
 
 
 def companion_path(name: str) -> str:
@@ -114,11 +121,11 @@ def build_hip(force: bool = False, experiments: bool = False) -> str:
 
 
 def build_companion(name: str, force: bool = False) -> str:
-    """Compile the sources of COMPANIONS' row `name` for gfx950 into cuda-path-tracer-denoising_amd/libsvgf_<name>.so, linked against
+    """Compile the sources of COMPANIONS' (or BUILDERS') row `name` for gfx950 into cuda-path-tracer-denoising_amd/libsvgf_<name>.so, linked against
     the product library beside it and against no other companion (the examples' rpath scheme: the build directory, then $ORIGIN, so the
     pair can be moved together)."""
     build_hip()
-    c = next(c for c in COMPANIONS if c.name == name)
+    c = next(c for c in COMPANIONS + BUILDERS if c.name == name)
     lib = companion_path(name)
     srcs = [os.path.join(CSRC, s) for s in c.sources]
     deps = srcs + [os.path.join(CSRC, h) for h in sorted(os.listdir(CSRC)) if h.endswith(".h")] + \
@@ -126,7 +133,7 @@ def build_companion(name: str, force: bool = False) -> str:
     if not force and _newer(lib, deps):
         return lib
     tmp = lib + f".tmp{os.getpid()}"
-    _run([hipcc_path()] + HIPCC_FLAGS + srcs + ["-L", _HERE, "-lsvgf_hip", "-Wl,-rpath," + _HERE, "-Wl,-rpath,$ORIGIN", "-Wl,-s", "-o", tmp])
+    _run([hipcc_path()] + HIPCC_FLAGS + list(getattr(c, "flags", [])) + srcs + ["-L", _HERE, "-lsvgf_hip", "-Wl,-rpath," + _HERE, "-Wl,-rpath,$ORIGIN", "-Wl,-s", "-o", tmp])
     os.replace(tmp, lib)
     return lib
 
@@ -157,6 +164,11 @@ def build_rough(force: bool = False) -> str:
 
 def build_highlight(force: bool = False) -> str:
     return build_companion("highlight", force)
+
+
+def build_lbvh(force: bool = False) -> str:
+    """libsvgf_lbvh.so (row f24, include/svgf_lbvh.h): BUILDERS' row through the companions' recipe."""
+    return build_companion("lbvh", force)
 
 
 def build_all(force: bool = False) -> list[str]:

@@ -318,7 +318,21 @@ struct svgf_scene {
     int n_objects, n_treelets, n_top;
     ScenePoseArgs pose;
     SceneRefitArgs refit;
+    // row f24, all zero until svgf_scene_adopt_tree: the caller's tree, read by every draw in place of args.nodes / args.order
+    const float4 *ad_nodes;
+    const int *ad_order;
+    int ad_n_nodes, ad_n_leaves, ad_depth;
 };
+
+// what the draws walk: the scene's own tree, or the adopted one
+static inline const float4 *scene_nodes(const svgf_scene *sc) { return sc->ad_nodes ? sc->ad_nodes : sc->args.nodes; }
+static inline const int *scene_order(const svgf_scene *sc) { return sc->ad_nodes ? sc->ad_order : sc->args.order; }
+static inline SvgfSceneInfo scene_info(const svgf_scene *sc)
+{
+    SvgfSceneInfo in = sc->info;
+    if (sc->ad_nodes) { in.n_nodes = sc->ad_n_nodes; in.n_leaves = sc->ad_n_leaves; in.depth = sc->ad_depth; }
+    return in;
+}
 
 extern "C" int svgf_scene_create(int device, const SvgfSceneGeom *geoms, int n_geoms, const int *geom_ids, const float *tris, const int *tri_ids,
                                  const float *tri_albedo, int n_tris, const int *tri_tex, const int *tex_desc, const unsigned char *tex_data,
@@ -404,7 +418,7 @@ extern "C" int svgf_scene_destroy(svgf_scene *scene)
 extern "C" int svgf_scene_info(const svgf_scene *scene, SvgfSceneInfo *out)
 {
     if (!scene || !out) return SVGF_ERR_INVALID_ARG;
-    *out = scene->info;
+    *out = scene_info(scene);
     return SVGF_OK;
 }
 
@@ -413,9 +427,9 @@ extern "C" int svgf_scene_view(const svgf_scene *scene, SvgfSceneView *out)
 {
     if (!scene || !out) return SVGF_ERR_INVALID_ARG;
     const SceneArgs &a = scene->args.s;
-    const SvgfSceneInfo &in = scene->info;
+    const SvgfSceneInfo in = scene_info(scene);
     *out = SvgfSceneView{ scene->device, in.n_geoms, in.n_tris, in.n_tex, in.n_nodes, in.depth, a.geoms, a.geom_ids, a.tris, a.tri_ids, a.tri_albedo,
-                          a.tri_tex, a.tex_desc, a.tex, reinterpret_cast<const SvgfBvhNode *>(scene->args.nodes), scene->args.order,
+                          a.tri_tex, a.tex_desc, a.tex, reinterpret_cast<const SvgfBvhNode *>(scene_nodes(scene)), scene_order(scene),
                           reinterpret_cast<const SvgfBvhNode *>(scene->args.tri_boxes) };
     return SVGF_OK;
 }
@@ -430,6 +444,7 @@ static int scene_draw_impl(const svgf_scene *scene, void *out_rgb_dev, void *out
     SvgfDeviceGuard dev_guard(scene->device);
     if (!dev_guard.ok) return SVGF_ERR_NO_DEVICE;
     SceneBvhArgs b = scene->args;
+    b.nodes = scene_nodes(scene); b.order = scene_order(scene);
     scene_frame_args(b.s, width, height, cam, sp, light);
     b.s.out_rgb = static_cast<float *>(out_rgb_dev);
     b.s.out_gbuf = static_cast<float *>(out_gbuffer_dev);
@@ -551,6 +566,7 @@ extern "C" int svgf_scene_pose(svgf_scene *scene, const SvgfScenePose *pose_dev,
     const int tail = (p.n_geoms > p.n_objects ? p.n_geoms : p.n_objects);
     hipStream_t st = static_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(k_scene_pose, dim3(p.tri_blocks + (tail + 255) / 256), dim3(256), 0, st, p);
+    if (scene->ad_nodes) return hipGetLastError() == hipSuccess ? SVGF_OK : SVGF_ERR_HIP;      // row f24: the caller rebuilds its tree
     if (scene->n_treelets > 0) hipLaunchKernelGGL(k_scene_refit_treelets, dim3(scene->n_treelets), dim3(256), 0, st, scene->refit);
     if (scene->n_top > 0) hipLaunchKernelGGL(k_scene_refit_top, dim3(1), dim3(256), 0, st, scene->refit);
     return hipGetLastError() == hipSuccess ? SVGF_OK : SVGF_ERR_HIP;
@@ -559,8 +575,8 @@ extern "C" int svgf_scene_pose(svgf_scene *scene, const SvgfScenePose *pose_dev,
 extern "C" int svgf_scene_read(const svgf_scene *scene, int which, void *host_dst, unsigned long long host_bytes)
 {
     if (!scene || which < 0 || which > 5 || (which == 5 && !scene->anim)) return SVGF_ERR_INVALID_ARG;
-    const SvgfSceneInfo &in = scene->info;
-    const void *src[6] = { scene->args.s.tris, scene->args.tri_boxes, scene->args.nodes, scene->args.s.geoms, scene->args.order, scene->pose.held };
+    const SvgfSceneInfo in = scene_info(scene);
+    const void *src[6] = { scene->args.s.tris, scene->args.tri_boxes, scene_nodes(scene), scene->args.s.geoms, scene_order(scene), scene->pose.held };
     const unsigned long long size[6] = { 96ull * in.n_tris, 32ull * in.n_tris, 32ull * in.n_nodes, (unsigned long long)sizeof(SvgfSceneGeom) * in.n_geoms,
                                          4ull * in.n_tris, (unsigned long long)sizeof(SvgfScenePose) * scene->n_objects };
     if (host_bytes != size[which] || (host_bytes > 0 && !host_dst)) return SVGF_ERR_INVALID_ARG;
@@ -568,5 +584,17 @@ extern "C" int svgf_scene_read(const svgf_scene *scene, int which, void *host_ds
     SvgfDeviceGuard dev_guard(scene->device);
     if (!dev_guard.ok) return SVGF_ERR_NO_DEVICE;
     if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(host_dst, src[which], (size_t)host_bytes, hipMemcpyDeviceToHost) != hipSuccess) return SVGF_ERR_HIP;
+    return SVGF_OK;
+}
+
+// row f24: draw with the caller's tree (host only; include/svgf.h states the contract)
+extern "C" int svgf_scene_adopt_tree(svgf_scene *scene, const SvgfBvhNode *nodes_dev, const int *order_dev, int n_nodes, int n_leaves, int depth_bound)
+{
+    if (!scene || scene->info.n_tris == 0) return SVGF_ERR_INVALID_ARG;
+    if (!nodes_dev) { scene->ad_nodes = nullptr; scene->ad_order = nullptr; scene->ad_n_nodes = scene->ad_n_leaves = scene->ad_depth = 0; return SVGF_OK; }
+    if (!order_dev || n_leaves < 1 || n_leaves > scene->info.n_tris || n_nodes != 2 * n_leaves - 1 || depth_bound < 0 || depth_bound > SVGF_SCENE_MAX_DEPTH ||
+        (reinterpret_cast<uintptr_t>(nodes_dev) & 15) || (reinterpret_cast<uintptr_t>(order_dev) & 15)) return SVGF_ERR_INVALID_ARG;
+    scene->ad_nodes = reinterpret_cast<const float4 *>(nodes_dev); scene->ad_order = order_dev;
+    scene->ad_n_nodes = n_nodes; scene->ad_n_leaves = n_leaves; scene->ad_depth = depth_bound;
     return SVGF_OK;
 }

@@ -815,7 +815,7 @@ int svgf_bvh_build_host(const float *tris, int n_tris, const SvgfSceneBuildParam
  * host wait, legal under stream capture.  Nothing of row f14's contract moves: the frame is the gated brute force over the POSED
  * triangles, which every tree reproduces, so a refitted tree draws the frame a tree rebuilt at that pose would.
  * What stays static: the topology (nodes' first / count, the triangle order - the tree is refitted, never re-split, however loose its
- * boxes become), the textures, and the set of objects.
+ * boxes become; row f24 below lets a scene adopt a tree rebuilt elsewhere), the textures, and the set of objects.
  * svgf_scene_enable_pose(scene, n_objects): allocates the animation side once - posed copies of the triangles, triangle boxes, nodes
  *   and primitives, the HELD pose table (identity) and the refit plan.  The arrays svgf_scene_create uploaded become the REST state
  *   and are never written again; the posed copies start as bit copies of them and the draws read them from now on.  Allocates and
@@ -934,6 +934,28 @@ typedef struct SvgfSceneView {
     const SvgfBvhNode *tri_boxes;
 } SvgfSceneView;                    /* 112 bytes */
 int svgf_scene_view(const svgf_scene *scene, SvgfSceneView *out);
+
+/* ---- "next" row f24: draw with a tree of the caller's (added after 0.9; probe the symbol) ----
+ * Row f14's frame is a gated brute force that every valid tree reproduces, so a scene can walk any tree over its triangles without
+ * a pixel changing.  svgf_scene_adopt_tree hands it one: from this call on every draw (svgf_scene_draw*, and the companion libraries
+ * through svgf_scene_view) reads nodes_dev / order_dev instead of the scene's own arrays; svgf_scene_view hands them out,
+ * svgf_scene_info reports n_nodes, n_leaves and depth = depth_bound, svgf_scene_read kinds 2 and 4 read them back.  Host only: no
+ * device work, no allocation, no synchronisation - the caller orders whatever builds the arrays ahead of the draws on the stream,
+ * and keeps them alive and valid (a binary tree by the SvgfBvhNode rules over order_dev, a permutation of 0 .. n_tris - 1, no
+ * deeper than depth_bound; exact boxes) while they are adopted.  libsvgf_lbvh.so (include/svgf_lbvh.h) builds such a tree on the
+ * device from the triangle boxes as drawn.
+ * nodes_dev == NULL detaches: the scene is back on its own tree and its own info.
+ * SVGF_ERR_INVALID_ARG, the scene untouched: a NULL scene; a scene with n_tris == 0; n_leaves outside 1..n_tris; n_nodes other than
+ *   2 * n_leaves - 1; depth_bound outside 0..SVGF_SCENE_MAX_DEPTH (the draws' stack); a pointer that is not 16-byte aligned; a NULL
+ *   order_dev with non-NULL nodes.
+ * svgf_scene_pose on a scene with an adopted tree launches the pose kernel only (triangles, padded boxes, primitives, motion table,
+ *   held) and skips both refit launches: THE ADOPTED TREE IS THEN STALE - its boxes no longer bound the posed triangles - until the
+ *   caller rebuilds it, and a draw in between may miss triangles.  The frame loop is pose, build, draw.  The refit plan and the
+ *   scene's own posed nodes stay valid: after a detach the next svgf_scene_pose refits them from the posed boxes as before (until
+ *   that pose they are as stale as the last refit left them).
+ * A scene that never adopts a tree is row f23's on every byte. */
+int svgf_scene_adopt_tree(svgf_scene *scene, const SvgfBvhNode *nodes_dev, const int *order_dev, int n_nodes, int n_leaves,
+                          int depth_bound);
 
 #ifdef __cplusplus
 }
