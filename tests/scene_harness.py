@@ -901,7 +901,7 @@ def rough_what(c):
 
 @functools.lru_cache(maxsize=None)
 def _rough_base(case, rough, alt=None, frame=None, table="own"):
-    """What does not depend on the guide: scene_gloss_model.render's results with scene_rough_model.paths, on the gloss suite's
+    """What does not depend on the guide: scene_gloss_model.render's results with the roughness table, on the gloss suite's
     (shared, unchanged) first hits."""
     name, W, H, J, K, R, sec, point = case
     frame = (0 if name in ("cornell",) else FRAME) if frame is None else frame

@@ -63,7 +63,7 @@ def guide(W, H, frame, cam, geoms, geom_ids, tris, tri_ids, tri_albedo, tri_tex,
     K, off = vp["max_chain"], vp["id_offset"]
     assert 1 <= K <= MAX_CHAIN and 0 <= off <= MAX_ID_OFFSET
     n_pixels = W * H
-    tri_id_set = np.zeros(0, np.int32) if tri_ids is None else np.unique(np.asarray(tri_ids, np.int32))
+    tri_id_set = gm.tri_id_set(tri_ids)
     gid0 = gb["geomId"].reshape(-1)
     runs = (gid0 >= 0) & ~emitter.reshape(-1) & ((w_d.reshape(-1) < 1) if alt == "partial_mirrors_followed" else (w_d.reshape(-1) == 0))
     pix = np.flatnonzero(runs)

@@ -177,7 +177,7 @@ def test_highlight_argument_errors_without_a_device(pkg):
 @pytest.mark.parametrize("rc", sh.RCASES + [sh.ABOVE], ids=sh.rid)
 def test_enable_0_is_the_rough_model_on_bits(rc):
     """scene_rough_model.render through the rough suite's cache (scene_harness.rmodel) against this file's model with enable = 0, with
-    and without a clamp, on that suite's sixteen cases."""
+    and without a clamp, on that suite's sixteen cases.  Both are one vertex loop: this guards its `hp` flag, not two copies' agreement."""
     case, rough, ga, mc, off = rc
     ref = sh.rmodel(*rc)
     m = _hmodel(case, rough, ga, mc, off, 0, CLAMP if case[3] == 1 else 0.0, 1, None)
@@ -189,6 +189,7 @@ def test_enable_0_is_the_rough_model_on_bits(rc):
 
 @pytest.mark.parametrize("vc", sh.VCASES, ids=sh.vid)
 def test_no_table_or_a_zero_table_is_the_virtual_model_for_enable_1(vc):
+    """Both are one vertex loop: this guards its `rough` and `hp` flags, not the agreement of copies."""
     case, mc, off = vc
     ref = sh.vmodel(*vc)
     tables = (None, (), (0.0,) * 16) if vc in (sh.VCASES[1], sh.VCASES[8]) else (None,)

@@ -121,7 +121,8 @@ def test_rough_argument_errors_without_a_device(pkg):
 @pytest.mark.parametrize("vc", sh.VCASES, ids=sh.vid)
 def test_no_table_or_a_zero_table_is_the_virtual_model_on_bits(vc):
     """scene_virtual_model.render through the virtual suite's cache (scene_harness.vmodel) against this file's model with no roughness, an
-    empty table and an all-zero table, for two values of guide_alpha."""
+    empty table and an all-zero table, for two values of guide_alpha.  Both are one vertex loop: this guards its `rough` flag, not two
+    copies' agreement."""
     case, mc, off = vc
     ref = sh.vmodel(*vc)
     for rough in (None, (), (0.0,) * 16):

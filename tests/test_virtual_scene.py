@@ -95,6 +95,7 @@ def test_virtual_argument_errors_without_a_device(pkg):
 # ---- C2: the model's identities --------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("vc", sh.VCASES, ids=sh.vid)
 def test_colour_and_first_hit_fields_are_the_gloss_models_on_bits(vc):
+    """The paths of both are the one vertex loop with no roughness table and no highlight block; this guards what the guide may write."""
     case, mc, off = vc
     ref, m = sh.gloss_model(*case), sh.vmodel(*vc)
     assert not differing(m["color"], ref["color"]).any() and not differing(m["D"], ref["D"]).any() and not differing(m["I"], ref["I"]).any()
