@@ -154,8 +154,17 @@ typedef struct SvgfParams {
                                  is shorter than K frames takes its variance from the luminance moments of its 7x7
                                  neighbourhood instead of from its own (Schied et al. 2017, section 4.2): taps that pass the
                                  reference's own consistency predicate (same geomId, |n_q - n_p| <= 0.1) count with weight 1,
-                                 variance = max(0, mean(m2) - mean(m1)^2) * max(1, 4 / history length).  0 = reference
-                                 (temporal variance, 100 without history).  ABI 0.3 (sizeof(SvgfParams) 72 -> 80). */
+                                 variance = max(0, mean(m2) - mean(m1)^2) * max(1, 4 / history length).
+                                 The pixel itself always counts, whatever its normal; the predicate is evaluated in float32
+                                 on sqrt((dx dx + dy dy) + dz dz), so a distance of exactly 0.1f passes, the next float above
+                                 it does not, and a tap with a NaN in its normal is skipped; ray misses (geomId -1) pass for
+                                 one another; taps outside the image are left out (16 taps in a corner, 28 at the middle of
+                                 an edge); the sums run over the taps in raster order in float32; a NaN moment in the window
+                                 gives a variance of 0 and a second-moment sum that overflows beside a finite squared mean
+                                 gives +inf, never a negative value; a pixel whose updated history has K frames or more
+                                 keeps the temporal pass's variance, so K <= 1 acts on no pixel; K belongs to the call, the
+                                 context keeps nothing of it.
+                                 0 = reference (temporal variance, 100 without history).  ABI 0.3 (sizeof(SvgfParams) 72 -> 80). */
 } SvgfParams;
 
 #define SVGF_MAX_LEVELS 10

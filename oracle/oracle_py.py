@@ -36,6 +36,8 @@ def load(camera_cls, params_cls):
     lib.svgf_oracle_atrous.argtypes = [vp, vp, vp, vp, vp, ip, ip, ip, ip, fp, fp, fp, ip, ip, ip, ip]
     lib.svgf_oracle_backproject.argtypes = [vp] * 11 + [ip, ip, fp, fp, ip]
     lib.svgf_oracle_view_matrix.argtypes = [C.POINTER(camera_cls), vp]
+    lib.svgf_oracle_spatial_variance.argtypes = [vp, vp, vp, vp, ip, ip, ip, ip]
+    lib.svgf_oracle_spatial_variance.restype = None
     _lib = lib
     return lib
 
@@ -91,3 +93,17 @@ def view_matrix(pkg, camera):
     m = np.empty(16, dtype=np.float32)
     lib.svgf_oracle_view_matrix(C.byref(cam), m.ctypes.data)
     return m
+
+
+def spatial_variance(pkg, variance, moments, history_length, gbuffer, K):
+    """svgf_oracle_spatial_variance on host planes: variance float32[H, W], moments float32[H, W, 2] and history_length int32[H, W]
+    as the temporal pass left them, gbuffer texels[H, W].  Returns the variance with the estimate where history_length < K."""
+    lib = load(pkg.SvgfCamera, pkg.SvgfParams)
+    H, W = history_length.shape
+    v = np.array(variance, dtype=np.float32, order="C")
+    m = np.ascontiguousarray(moments, dtype=np.float32)
+    h = np.ascontiguousarray(history_length, dtype=np.int32)
+    g = np.ascontiguousarray(gbuffer)
+    assert v.shape == (H, W) and m.shape == (H, W, 2) and g.nbytes == 52 * W * H
+    lib.svgf_oracle_spatial_variance(v.ctypes.data, m.ctypes.data, h.ctypes.data, g.ctypes.data, W, H, int(K), 1)
+    return v

@@ -1,5 +1,5 @@
 """What the temporal-pass suites share (tests/test_motion_vectors.py, test_history_clamp.py, test_object_motion.py,
-test_firefly_filter.py, test_temporal_matrix.py): how frames are compared with tests/temporal_model.py, the parameter sets, the
+test_firefly_filter.py, test_temporal_matrix.py, test_spatial_variance.py): how frames are compared with tests/temporal_model.py, the parameter sets, the
 input sequences (the synthetic scene as rendered and with mixed texels under a table of object motions, the block of box_room) and
 the loop that runs a sequence through a context and reads its states back.  Test infrastructure only; not part of the package."""
 import ctypes
@@ -159,22 +159,78 @@ def mixed_sequence(pkg, orc, W, H, n=4, finite=False):
     return cache[(W, H, n, finite)]
 
 
-def mixed_model(pkg, orc, W, H, fmt, tol, radius=0, k=0.0, rank=0, scale=1.0, table=True):
+NOISY_FRAMES = 6
+THRESHOLD_STEP = (F(0.1), np.nextafter(F(0.1), F(1)))      # 0.1f: the largest normal distance accepted; 0.10000001f: the next float
+
+
+def noisy_sequence(pkg, orc, W, H, n=NOISY_FRAMES, finite=False, threshold_edits=True):
+    """mixed_sequence made to act on the spatial variance estimate (k_spatial_variance), by seeded edits per frame:
+    - every colour times one factor per pixel from [0.25, 1.75], plus noise per channel from [0, 0.2]: moments that differ from
+      tap to tap (mixed_sequence's walls are flat, and a flat window's estimate is 0);
+    - about 2 % of the normals NaN (such a pixel accepts its own tap alone, and is nobody's tap);
+    - about 2 % of the pixels get a right-hand neighbour of their geomId with their normal + (0.1f, 0, 0), and about 2 % one with
+      their normal + (0, 0.10000001f, 0): pairs at the threshold of the predicate, on either side of it where the pixel's own
+      component is 0 (threshold_edits False leaves both out, nothing else changes: the draws are made either way);
+    - two pixels each of colour 1e20 (its second moment overflows: an estimate of +inf), NaN and inf, and three of 1000.0.
+    finite: on mixed_sequence's finite form (for frames that run the a-trous levels, see there) and without the edits that put a
+    non-finite value into a plane the levels read: the NaN normals, the NaN and inf colours, and the 1e20 colours, which are
+    inf edits by then (the temporal pass squares the luminance: a second moment of +inf, a variance of +inf or, from inf - inf,
+    of 0, and the levels' kernels are held to the oracle on finite planes only).  The 1000.0 pixels stay.
+    Per frame (colour[H, W, 3], texels[H, W], camera, view matrix)."""
+    cache = noisy_sequence.__dict__.setdefault("cache", {})
+    key = (W, H, n, finite, threshold_edits)
+    if key not in cache:
+        seq = []
+        for f, (col, gb, cam, M) in enumerate(mixed_sequence(pkg, orc, W, H, n, finite)):
+            rng = np.random.default_rng(7919 * W + 31 * H + 101 * f + 5)
+            m = W * H
+            col = (col.reshape(m, 3) * rng.uniform(0.25, 1.75, (m, 1)).astype(F) + rng.uniform(0.0, 0.2, (m, 3)).astype(F)).astype(F)
+            gb = gb.copy()
+            flat = gb.reshape(-1)
+            nan_normals = rng.random(m) < 0.02
+            step = rng.random((2, m))
+            if not finite:
+                flat["normal"][nan_normals] = np.nan
+            if threshold_edits:
+                for j, axis in enumerate((0, 1)):
+                    src = np.flatnonzero((step[j] < 0.02) & (np.arange(m) % W != W - 1))
+                    for i in src:      # in raster order: a pair laid down later may rewrite an earlier pair's neighbour
+                        flat["geomId"][i + 1] = flat["geomId"][i]
+                        nq = flat["normal"][i].copy()
+                        nq[axis] = nq[axis] + THRESHOLD_STEP[j]
+                        flat["normal"][i + 1] = nq
+            special = rng.choice(m, min(9, m), replace=False)
+            values = [F(1e20), F(1e20), F(1000.0), F(1000.0), F(1000.0), F(np.nan), F(np.nan), F(np.inf), F(np.inf)]
+            for i, v in zip(special, values):
+                if not finite or v == F(1000.0):
+                    col[i] = v
+            seq.append((col.reshape(H, W, 3), gb, cam, M))
+        cache[key] = seq
+    return cache[key]
+
+
+def mixed_model(pkg, orc, W, H, fmt, tol, radius=0, k=0.0, rank=0, scale=1.0, table=True, svf=0, noisy=None, reset_before=()):
     """The model on mixed_sequence with mixed_table: fmt None = the camera path (the moved position projected through the previous
     frame's camera); otherwise through the plane svgf_motion_reproject(X) writes in that format, converted as the header says.
     rank, scale: the frames' colours go through firefly_model.firefly_filter first (svgf_set_firefly_filter; rank 0 leaves them as
-    they are).  table False: no table at all, and the plane written without X."""
+    they are).  table False: no table at all, and the plane written without X.
+    svf: SvgfParams::spatial_variance_frames, one K or one per frame.  noisy: None = mixed_sequence; otherwise the keyword
+    arguments of noisy_sequence (a dict), whose frames the model then runs.  reset_before: as run_sequence's."""
     cache = mixed_model.__dict__.setdefault("cache", {})
-    key = (W, H, fmt, tol, radius, k, rank, scale if rank else None, table)
+    svf = svf if np.isscalar(svf) else tuple(svf)
+    noisy_key = None if noisy is None else tuple(sorted(noisy.items()))
+    key = (W, H, fmt, tol, radius, k, rank, scale if rank else None, table, svf, noisy_key, tuple(reset_before))
     if key not in cache:
-        seq, X = mixed_sequence(pkg, orc, W, H), mixed_table() if table else None
+        seq = mixed_sequence(pkg, orc, W, H) if noisy is None else noisy_sequence(pkg, orc, W, H, **noisy)
+        X = mixed_table() if table else None
         sx, sy = scales(pkg, W, H)
         views = [seq[max(f - 1, 0)][3] for f in range(len(seq))]
         coords = None
         if fmt is not None:
             coords = [tm.coord_plane(tm.motion_plane(views[f], W, H, seq[f][1], X, fmt, F(sx), F(sy)), fmt, W, H) for f in range(len(seq))]
         cache[key] = tm.run_sequence([(ff.firefly_filter(c, rank, scale), g) for c, g, _, _ in seq], coords=coords,
-                                     tables=[X] * len(seq) if table else None, views=views, scale=(sx, sy), pos_tol=tol, radius=radius, k=k)
+                                     tables=[X] * len(seq) if table else None, views=views, scale=(sx, sy), pos_tol=tol, radius=radius, k=k,
+                                     svf=svf, reset_before=tuple(reset_before))
     return cache[key]
 
 
@@ -196,20 +252,27 @@ def device_table(X):
     return torch.from_numpy(np.ascontiguousarray(X, dtype=F)).cuda()
 
 
-def run_gpu(pkg, den, frames, params, cams, leg="aos", planes=None, fmt=COORD, plane_fmt=None, plane_tables=None):
-    """frames: [(colour, texels)]; cams: per frame.  The context's clamp and table are whatever the caller set.  The history is
+def run_gpu(pkg, den, frames, params, cams, leg="aos", planes=None, fmt=COORD, plane_fmt=None, plane_tables=None, reset_before=(),
+            outputs=None):
+    """frames: [(colour, texels)]; cams: per frame; params: one SvgfParams, or one per frame.  The context's clamp and table are
+    whatever the caller set.  The history is
     looked up through the camera path, or through a motion plane given in one of two ways:
     planes, fmt: per frame a host plane of format `fmt` (the model's), uploaded;
     plane_fmt, plane_tables: the plane svgf_motion_reproject writes on the device in that format for the previous frame's camera,
     params' reproj_scale and plane_tables[f] (None: no table).
+    reset_before: the frames in front of which svgf_reset is called.  outputs: a list that receives each frame's `out` (host).
     Returns per frame the five states.  `leg`: aos | planar."""
     import torch
     assert planes is None or plane_fmt is None
     H, W = frames[0][1].shape
     den.set_capture(True)
     out, res, keep = torch.empty((H, W, 3), dtype=torch.float32, device="cuda"), [], []
-    rs = (params.reproj_scale[0], params.reproj_scale[1])
+    per_frame = list(params) if isinstance(params, (list, tuple)) else [params] * len(frames)
     for f, (col, gb) in enumerate(frames):
+        params = per_frame[f]
+        rs = (params.reproj_scale[0], params.reproj_scale[1])
+        if f in reset_before:
+            den.reset()
         t_c = torch.from_numpy(np.ascontiguousarray(col, dtype=F)).cuda()
         t_g = torch.from_numpy(np.ascontiguousarray(gb).view(np.uint8).reshape(-1).copy()).cuda()
         mv = None if planes is None else torch.from_numpy(np.ascontiguousarray(planes[f])).cuda()
@@ -235,6 +298,8 @@ def run_gpu(pkg, den, frames, params, cams, leg="aos", planes=None, fmt=COORD, p
             den.denoise(out, t_c, t_g, cams[f], params, motion=mv, motion_format=fmt)
         den.sync()
         res.append(read_states(den))
+        if outputs is not None:
+            outputs.append(out.cpu().numpy())
     return res
 
 

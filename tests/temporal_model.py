@@ -2,9 +2,10 @@
 tests/test_motion_vectors.py, test_history_clamp.py, test_object_motion.py and (behind tests/firefly_model.py) test_firefly_filter.py
 and test_temporal_matrix.py.  Test infrastructure only; not part of the package.
 
-One model with three optional parts, each off at its default: the history clamp of svgf_set_history_clamp (`radius`, `k`), the
-position test of SvgfParams::reproj_position_tol (`pos_tol`) and the object motion table of svgf_set_object_motion (`tables`,
-`compare_normal` / `compare_position`).
+One model with four optional parts, each off at its default: the history clamp of svgf_set_history_clamp (`radius`, `k`), the
+position test of SvgfParams::reproj_position_tol (`pos_tol`), the object motion table of svgf_set_object_motion (`tables`,
+`compare_normal` / `compare_position`) and the spatial variance estimate of SvgfParams::spatial_variance_frames (`svf`;
+spatial_variance below, the model of k_spatial_variance in csrc/svgf_kernels.hip), which rewrites the variance alone.
 
 The model looks a pixel's history up at the coordinate a PREV_COORD_F32 plane gives (svgf_denoise_motion); the camera path is
 the same model fed the plane svgf_motion_reproject would write (project_prev below: the camera path's own projection) — with a
@@ -24,7 +25,16 @@ What pins the model, on the CPU (the oracle knows no plane, no clamp and no tabl
   test_object_motion.py::test_model_with_table_is_the_oracle_on_substituted_texels;
 - the clamp (and everything else on the moving block, radius 0 to 3), to the results recorded in
   tests/golden/temporal_model/moving_block.json from the model the clamp's suite was first written against:
-  test_object_motion.py::test_model_without_table_is_the_clamp_model_on_the_moving_block.
+  test_object_motion.py::test_model_without_table_is_the_clamp_model_on_the_moving_block;
+- the spatial variance estimate, in tests/test_spatial_variance.py:
+  - to the oracle's on the bits of every pixel, every frame of noisy_sequence at seven sizes and five K:
+    test_model_is_the_oracle_on_bits;
+  - to a per-pixel float64 restatement written from the header's sentence, which shares no text with either, within the
+    rounding of the float32 sums: test_model_is_the_float64_restatement_within_rounding;
+  - by value, on hand-built 9x9 frames, case by case (the centre under a NaN normal, a NaN neighbour, distance 0.1f and the
+    next float above, another geomId, ray misses, corner and edge windows, the boost at history lengths 1 to 5, NaN, 1e20
+    and bright flat moments, hlen >= K, K <= 1): the test_case_* tests, each through the model and through the oracle;
+  - and it leaves hlen, mom and color as a run without it: test_the_part_changes_the_variance_alone.
 The GPU suites then hold the kernels to the model on the bits of every pixel."""
 import numpy as np
 
@@ -250,20 +260,67 @@ def _temporal_pass(color, normal, position, gid, prev, coord, cmp_n, cmp_p, pos_
     return state, variance
 
 
+SVF_REACH = 3                               # k_spatial_variance: the 7x7 window
+SVF_NORMAL_DISTANCE = F(0.1)                # 1e-1f: a tap counts when its normal lies no further than this from the pixel's
+
+
+def spatial_variance(variance, mom, hlen, normal, gid, K):
+    """SvgfParams::spatial_variance_frames = K (k_spatial_variance, csrc/svgf_kernels.hip), behind the temporal pass of the same
+    frame: variance float32[H, W] as that pass left it, mom float32[H, W, 2] and hlen int32[H, W] the UPDATED moments and history
+    lengths, normal float32[H, W, 3] and gid int32[H, W] this frame's own (never the moved ones).  Returns the variance: the
+    estimate where hlen < K, `variance` elsewhere.  Nothing else of the state changes.
+    Taps in raster order (yy outer, xx inner); s1, s2 and cnt move only where a tap is accepted: inside the image, and — any tap
+    but the centre — of the pixel's geomId with sqrt((dx dx + dy dy) + dz dz) <= 0.1f, which a NaN fails."""
+    variance, mom, normal = np.asarray(variance, F), np.asarray(mom, F), np.asarray(normal, F)
+    hlen, gid = np.asarray(hlen, np.int32), np.asarray(gid, np.int32)
+    H, W = hlen.shape
+    inside = np.ones((H, W), bool)
+    s1, s2, cnt = np.zeros((H, W), F), np.zeros((H, W), F), np.zeros((H, W), F)
+    with np.errstate(all="ignore"):
+        for yy in range(-SVF_REACH, SVF_REACH + 1):
+            for xx in range(-SVF_REACH, SVF_REACH + 1):
+                if abs(yy) >= H or abs(xx) >= W:      # wholly outside an image smaller than the window
+                    continue
+                ok = _shifted(inside, yy, xx, False)
+                if (yy, xx) != (0, 0):
+                    d = normal - _shifted(normal, yy, xx)
+                    s = d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]
+                    s = s + d[..., 2] * d[..., 2]
+                    ok = ok & (_shifted(gid, yy, xx) == gid) & (np.sqrt(s) <= SVF_NORMAL_DISTANCE)
+                m = _shifted(mom, yy, xx)
+                s1 = np.where(ok, s1 + m[..., 0], s1)
+                s2 = np.where(ok, s2 + m[..., 1], s2)
+                cnt = np.where(ok, cnt + F(1), cnt)
+        m1, m2 = s1 / cnt, s2 / cnt
+        v = m2 - m1 * m1
+        v = np.where(v > 0, v, F(0))
+        boost = F(4) / np.maximum(hlen, 1).astype(F)
+        est = v * np.where(boost > F(1), boost, F(1))
+    return np.where(hlen < K, est, variance).astype(F)
+
+
 def run_sequence(frames, coords=None, tables=None, views=None, scale=(0.0, 0.0), pos_tol=0.0, color_alpha=0.2, moment_alpha=0.2,
-                 radius=0, k=0.0):
+                 radius=0, k=0.0, svf=0, reset_before=()):
     """frames: per frame (color[H, W, 3], gb GBUFFER_DTYPE[H, W]); tables: per frame X float32[n, 12] or None (no table);
     coords: per frame the PREV_COORD_F32 plane the history is looked up at, or None: the camera path — the projection of the
     (moved) position through views[f], the PREVIOUS frame's view matrix, with reproj_scale `scale` (frame 0's is not looked at).
+    svf: SvgfParams::spatial_variance_frames, one K or one per frame (a parameter of the call: nothing of it is kept).
+    reset_before: the frames in front of which svgf_reset is called (the state is the fresh context's again).
     Per frame: dict(hlen, mom, color, variance)."""
     H, W = frames[0][1].shape
     st, out = empty_state(W, H), []
+    Ks = [int(svf)] * len(frames) if np.isscalar(svf) else [int(K) for K in svf]
+    assert len(Ks) == len(frames)
     for f, (col, gb) in enumerate(frames):
+        if f in reset_before:
+            st = empty_state(W, H)
         X = None if tables is None else tables[f]
         gid = gb["geomId"]
         q, m = apply_xf(X, gid, gb["position"]), moved_normal(X, gid, gb["normal"])
         co = coords[f] if coords is not None else project_prev(views[f], W, H, F(scale[0]), F(scale[1]), q)
         st, var = temporal_pass(np.asarray(col, F).reshape(H, W, 3), gb["normal"], gb["position"], gid, st, co, m, q, pos_tol,
                                 color_alpha, moment_alpha, radius, k)
+        if Ks[f] > 0:
+            var = spatial_variance(var, st["mom"], st["hlen"], gb["normal"], gid, Ks[f])
         out.append(dict(hlen=st["hlen"], mom=st["mom"], color=st["color"], variance=var))
     return out

@@ -5,6 +5,10 @@ Neither exists in the reference: README.md:39 names a position test that isReprj
 perform, and EstimateVariance (src/denoise.cu:320-329) is a constant with a TODO.  Both are defined here from Schied et
 al. 2017 (sections 4.1, 4.2) and carried by the CPU oracle as well, so the parity bar is the hot path's: integer state
 bit-exact, fp32 temporal state bit-exact, <= 1e-4 relative after the a-trous levels.  0 / 0 must be the reference path.
+
+The oracle's and the kernel's spatial variance estimate were written together; what holds both to an independent yardstick (a
+float32 numpy model, a float64 restatement of the header's sentence, named cases, every launch path on the GPU) is
+tests/test_spatial_variance.py.
 """
 import numpy as np
 import pytest
