@@ -30,23 +30,6 @@ MAX_LEVELS = 10
 # svgf_exp_level_kernels (experiments build): the kernel an a-trous level ran
 LEVEL_KERNEL_NAMES = ("fused", "lane", "lane2y", "strip", "lattice", "gather")
 
-# every symbol include/svgf.h declares
-EXPORTS = ["svgf_version", "svgf_params_default", "svgf_create", "svgf_destroy", "svgf_reset", "svgf_denoise",
-           "svgf_denoise_host", "svgf_sync", "svgf_last_error", "svgf_width", "svgf_height", "svgf_read_state",
-           "svgf_set_capture", "svgf_profile_enable", "svgf_profile_stride", "svgf_profile_frames", "svgf_profile_read",
-           "svgf_synth_camera", "svgf_synth_render", "svgf_scene_render", "svgf_scene_render_mesh", "svgf_display_pack", "svgf_save_png",
-           "svgf_planar_gbuffer", "svgf_denoise_planar", "svgf_synth_render_planar", "svgf_params_sizeof", "svgf_scene_render_mesh_planar",
-           "svgf_sync_stream", "svgf_build_has_experiments", "svgf_is_pipelined", "svgf_create_ex", "svgf_enable_pipeline",
-           "svgf_pipeline_status", "svgf_planar_gbuffer_stream", "svgf_streams_overlap",
-           "svgf_denoise_motion", "svgf_denoise_planar_motion", "svgf_motion_reproject",
-           "svgf_set_history_clamp", "svgf_get_history_clamp", "svgf_set_object_motion", "svgf_get_object_motion",
-           "svgf_set_firefly_filter", "svgf_get_firefly_filter", "svgf_set_output_taa", "svgf_get_output_taa",
-           "svgf_upsample", "svgf_transfer_history",
-           "svgf_exposure_reset", "svgf_exposure_meter", "svgf_display_tonemap", "svgf_tonemap_srgb_table",
-           "svgf_quality_state_bytes", "svgf_quality_windows", "svgf_quality_meter", "svgf_quality_read",
-           "svgf_scene_create", "svgf_scene_destroy", "svgf_scene_info", "svgf_scene_draw", "svgf_scene_draw_planar", "svgf_bvh_build_host",
-           "svgf_scene_enable_pose", "svgf_scene_pose", "svgf_scene_read", "svgf_pose_rigid", "svgf_bvh_refit_plan_host",
-           "svgf_scene_draw_shadowed", "svgf_scene_view", "svgf_scene_adopt_tree"]
 # every symbol include/svgf_trace.h declares (libsvgf_trace.so, the companion library of row f17)
 TRACE_EXPORTS = ["svgf_trace_draw", "svgf_trace_version"]
 # libsvgf_split.so (include/svgf_split.h, row f18)
@@ -67,9 +50,7 @@ ROUGH_EXPORTS = ["svgf_rough_table_create", "svgf_rough_table_destroy", "svgf_ro
 # libsvgf_highlight.so (include/svgf_highlight.h, row f23)
 HIGHLIGHT_EXPORTS = ["svgf_highlight_draw", "svgf_highlight_draw_split", "svgf_highlight_version"]
 # libsvgf_lbvh.so (include/svgf_lbvh.h, row f24): the device BVH builder - built by the companions' recipe (build.BUILDERS) and linked
-# like them, but no companion draw: not a row of COMPANIONS
-LBVH_EXPORTS = ["svgf_lbvh_create", "svgf_lbvh_build", "svgf_lbvh_attach", "svgf_lbvh_info", "svgf_lbvh_read", "svgf_lbvh_destroy",
-                "svgf_lbvh_version", "svgf_lbvh_build_host"]
+# like them, but no companion draw: not a row of COMPANIONS (its symbols: LBVH_EXPORTS, below the structures)
 LIB_LBVH_PATH = os.path.join(_HERE, "libsvgf_lbvh.so")
 LBVH_READ_NODES, LBVH_READ_ORDER, LBVH_READ_KEYS = 0, 1, 2
 LBVH_TILE = 512
@@ -266,6 +247,181 @@ class SvgfError(RuntimeError):
     pass
 
 
+class SvgfLbvhParams(C.Structure):
+    _fields_ = [("leaf_tris", C.c_int)]
+
+
+class SvgfLbvhInfo(C.Structure):
+    _fields_ = [(k, C.c_int) for k in ("n_tris", "n_leaves", "n_nodes", "leaf_tris", "idx_bits", "axis_bits", "key_bits", "depth_bound",
+                                       "launches")] + [("device_bytes", C.c_ulonglong)]
+
+
+def _check(rc, symbol, message=None):
+    """The return-code check of every wrapper outside Denoiser (whose _check adds the context's last error)."""
+    if rc != SVGF_OK:
+        raise SvgfError(message or f"{symbol} failed ({rc})")
+
+
+def _call(lib, symbol, *args):
+    _check(getattr(lib, symbol)(*args), symbol)
+
+
+def _ptr(x):
+    """device pointer of a torch tensor / int / None"""
+    if x is None:
+        return None
+    if isinstance(x, int):
+        return x
+    if hasattr(x, "data_ptr"):
+        if not x.is_contiguous():
+            raise SvgfError("tensor must be contiguous")
+        return x.data_ptr()
+    raise TypeError(type(x))
+
+
+def _stream(stream):
+    """raw handle of a torch stream / int / None"""
+    return None if stream is None else (stream if isinstance(stream, int) else stream.cuda_stream)
+
+
+def _camera(camera):
+    return camera if isinstance(camera, SvgfCamera) else SvgfCamera.from_dict(camera)
+
+
+def _view(camera, width, height, frame, seed, noise, fireflies, pixel_length, camera_fovy):
+    """(SvgfCamera, SvgfSynthParams) of a producer call.  pixel_length defaults to synth._pixel_length(width, height, field of view), so
+    that host and device producers agree; the field of view is a camera dict's "fovy_deg" where `camera_fovy` (the scene entry points),
+    and 45 degrees otherwise: for an SvgfCamera, a dict without the key, and the synth_render pair whatever the camera says."""
+    if pixel_length is None:
+        from . import synth as _synth
+        fovy = camera.get("fovy_deg", 45.0) if camera_fovy and isinstance(camera, dict) else 45.0
+        pixel_length = _synth._pixel_length(width, height, fovy)
+    return _camera(camera), SvgfSynthParams(int(frame), int(seed), float(noise), float(fireflies), (float(pixel_length[0]), float(pixel_length[1])))
+
+
+def _draw_target(out_gbuffer):
+    """(planar?, AoS texels or None, planes by reference or None) of a G-buffer output: device memory or a SvgfPlanarGBuffer."""
+    planar = isinstance(out_gbuffer, SvgfPlanarGBuffer)
+    return planar, None if planar else _ptr(out_gbuffer), C.byref(out_gbuffer) if planar else None
+
+
+def _v3(v):
+    return (C.c_float * 3)(float(v[0]), float(v[1]), float(v[2]))
+
+
+# Every symbol include/svgf.h declares, in the order they were added: (restype, argtypes or None where none is declared).  load_library
+# declares them from here and EXPORTS is this table's keys (tests/test_abi.py holds them against the header, tests/test_binding_surface.py
+# the prototypes against tests/golden/binding_abi.json), so a symbol cannot be exported without its prototype.
+def _prototypes():
+    vp, ip, fl, P = C.c_void_p, C.c_int, C.c_float, C.POINTER
+    fp, cam, synth, planes = P(fl), P(SvgfCamera), P(SvgfSynthParams), P(SvgfPlanarGBuffer)
+    mesh = [vp, ip, vp, vp, vp, vp, ip, vp, vp, vp, ip]      # geoms, n, geom_ids, tris, tri_ids, tri_albedo, n, tri_tex, tex_desc, texels, n
+    product = {
+        "svgf_version": (ip, None),
+        "svgf_params_default": (ip, [P(SvgfParams)]),
+        "svgf_create": (ip, [ip, ip, ip, P(vp)]),
+        "svgf_destroy": (ip, [vp]),
+        "svgf_reset": (ip, [vp]),
+        "svgf_denoise": (ip, [vp, vp, vp, vp, cam, P(SvgfParams), vp]),
+        "svgf_denoise_host": (ip, [vp, vp, vp, vp, cam, P(SvgfParams)]),
+        "svgf_sync": (ip, [vp]),
+        "svgf_last_error": (C.c_char_p, [vp]),
+        "svgf_width": (ip, [vp]),
+        "svgf_height": (ip, [vp]),
+        "svgf_read_state": (ip, [vp, ip, vp, C.c_ulonglong]),
+        "svgf_set_capture": (ip, [vp, ip]),
+        "svgf_profile_enable": (ip, [vp, ip]),
+        "svgf_profile_stride": (ip, [vp, ip]),
+        "svgf_profile_frames": (C.c_longlong, [vp]),
+        "svgf_profile_read": (ip, [vp, ip, ip, P(ip), fp, P(ip)]),
+        "svgf_synth_camera": (ip, [ip, ip, ip, ip, cam, fp]),
+        "svgf_synth_render": (ip, [ip, vp, vp, ip, ip, cam, synth, vp]),
+        "svgf_scene_render": (ip, [ip, vp, vp, ip, ip, cam, synth, vp, ip, fp, vp]),
+        "svgf_scene_render_mesh": (ip, [ip, vp, vp, ip, ip, cam, synth] + mesh + [fp, vp]),
+        "svgf_display_pack": (ip, [ip, vp, vp, vp, ip, ip, vp]),
+        "svgf_save_png": (ip, [C.c_char_p, vp, ip, ip, ip]),
+        "svgf_planar_gbuffer": (ip, [vp, planes]),
+        "svgf_denoise_planar": (ip, [vp, vp, vp, cam, P(SvgfParams), vp]),
+        "svgf_synth_render_planar": (ip, [ip, vp, planes, ip, ip, cam, synth, vp]),
+        "svgf_params_sizeof": (ip, None),
+        "svgf_scene_render_mesh_planar": (ip, [ip, vp, planes, ip, ip, cam, synth] + mesh + [fp, vp]),
+        "svgf_sync_stream": (ip, [vp, vp]),
+        "svgf_build_has_experiments": (ip, None),
+        "svgf_is_pipelined": (ip, [vp]),
+        "svgf_create_ex": (ip, [ip, ip, ip, C.c_uint, P(vp)]),
+        "svgf_enable_pipeline": (ip, [vp]),
+        "svgf_pipeline_status": (ip, [vp]),
+        "svgf_planar_gbuffer_stream": (ip, [vp, planes, vp]),
+        "svgf_streams_overlap": (ip, [ip, vp, vp]),
+        "svgf_denoise_motion": (ip, [vp, vp, vp, vp, vp, ip, cam, P(SvgfParams), vp]),
+        "svgf_denoise_planar_motion": (ip, [vp, vp, vp, vp, ip, cam, P(SvgfParams), vp]),
+        "svgf_motion_reproject": (ip, [ip, vp, ip, vp, vp, vp, ip, ip, cam, fp, vp, ip, vp]),
+        "svgf_set_history_clamp": (ip, [vp, ip, fl]),
+        "svgf_get_history_clamp": (ip, [vp, P(ip), fp]),
+        "svgf_set_object_motion": (ip, [vp, vp, ip]),
+        "svgf_get_object_motion": (ip, [vp, P(vp), P(ip)]),
+        "svgf_set_firefly_filter": (ip, [vp, ip, fl]),
+        "svgf_get_firefly_filter": (ip, [vp, P(ip), fp]),
+        "svgf_set_output_taa": (ip, [vp, fl, fl]),
+        "svgf_get_output_taa": (ip, [vp, fp, fp]),
+        "svgf_upsample": (ip, [ip, vp, P(SvgfGuide), ip, ip, vp, P(SvgfGuide), ip, ip, P(SvgfUpsampleParams), vp]),
+        "svgf_transfer_history": (ip, [vp, vp, vp]),
+        "svgf_exposure_reset": (ip, [ip, vp, vp]),
+        "svgf_exposure_meter": (ip, [ip, vp, vp, ip, ip, P(SvgfExposureParams), vp]),
+        "svgf_display_tonemap": (ip, [ip, vp, vp, vp, ip, ip, P(SvgfTonemapParams), vp, vp]),
+        "svgf_tonemap_srgb_table": (ip, [fp]),
+        "svgf_quality_state_bytes": (C.c_ulonglong, [ip, ip]),
+        "svgf_quality_windows": (ip, [ip, ip, P(ip), P(ip)]),
+        "svgf_quality_meter": (ip, [ip, vp, vp, vp, ip, ip, P(SvgfQualityParams), vp, vp, vp, vp]),
+        "svgf_quality_read": (ip, [ip, vp, P(SvgfQualityResult), vp]),
+        "svgf_scene_create": (ip, [ip] + mesh + [P(SvgfSceneBuildParams), P(vp)]),
+        "svgf_scene_destroy": (ip, [vp]),
+        "svgf_scene_info": (ip, [vp, P(SvgfSceneInfo)]),
+        "svgf_scene_draw": (ip, [vp, vp, vp, ip, ip, cam, synth, fp, vp]),
+        "svgf_scene_draw_planar": (ip, [vp, vp, planes, ip, ip, cam, synth, fp, vp]),
+        "svgf_bvh_build_host": (ip, [vp, ip, P(SvgfSceneBuildParams), vp, P(ip), vp, P(ip)]),
+        "svgf_scene_enable_pose": (ip, [vp, ip]),
+        "svgf_scene_pose": (ip, [vp, vp, ip, vp, vp]),
+        "svgf_scene_read": (ip, [vp, ip, vp, C.c_ulonglong]),
+        "svgf_pose_rigid": (ip, [fp, fl, fp, fp, vp]),
+        "svgf_bvh_refit_plan_host": (ip, [vp, ip, ip, vp, vp, vp, vp, vp]),
+        "svgf_scene_draw_shadowed": (ip, [vp, vp, vp, planes, ip, ip, cam, synth, P(SvgfSceneLight), vp]),
+        "svgf_scene_view": (ip, [vp, P(SvgfSceneView)]),
+        "svgf_scene_adopt_tree": (ip, [vp, vp, vp, ip, ip, ip]),
+    }
+    # what the experiments build (libsvgf_hip_exp.so) exports on top and the binding calls with arguments
+    experiments = {
+        "svgf_exp_set": (ip, [C.c_char_p, ip]),
+        "svgf_exp_level_kernels": (ip, [vp, P(ip), P(ip), P(C.c_double), P(C.c_double), ip]),
+        "svgf_exp_atrous_geometry": (ip, [ip] * 7 + [P(ip), P(C.c_double)]),
+    }
+    # every symbol include/svgf_lbvh.h declares
+    lbvh = {
+        "svgf_lbvh_create": (ip, [vp, P(SvgfLbvhParams), P(vp)]),
+        "svgf_lbvh_build": (ip, [vp, vp]),
+        "svgf_lbvh_attach": (ip, [vp, vp]),
+        "svgf_lbvh_info": (ip, [vp, P(SvgfLbvhInfo)]),
+        "svgf_lbvh_read": (ip, [vp, ip, vp, C.c_ulonglong]),
+        "svgf_lbvh_destroy": (None, [vp]),
+        "svgf_lbvh_version": (ip, None),
+        "svgf_lbvh_build_host": (ip, [vp, ip, P(SvgfLbvhParams), vp, vp, vp, P(SvgfLbvhInfo)]),
+    }
+    return product, experiments, lbvh
+
+
+_PROTOTYPES, _EXP_PROTOTYPES, _LBVH_PROTOTYPES = _prototypes()
+EXPORTS, LBVH_EXPORTS = list(_PROTOTYPES), list(_LBVH_PROTOTYPES)
+
+
+def _declare(lib, prototypes):
+    for symbol, (restype, argtypes) in prototypes.items():
+        f = getattr(lib, symbol)
+        f.restype = restype
+        if argtypes is not None:
+            f.argtypes = argtypes
+    return lib
+
+
 _lib = None
 _lib_exp = None
 _default_experiments = False
@@ -280,9 +436,7 @@ def use_experiments_library(on: bool = True):
 
 def exp_set(name: str, value: int):
     """svgf_exp_set of the experiments build (process-wide; read by svgf_create / the launchers of libsvgf_hip_exp.so)."""
-    lib = load_library(experiments=True)
-    if lib.svgf_exp_set(name.encode(), int(value)) != SVGF_OK:
-        raise SvgfError(f"svgf_exp_set({name!r}, {value}) failed")
+    _check(load_library(experiments=True).svgf_exp_set(name.encode(), int(value)), "svgf_exp_set", f"svgf_exp_set({name!r}, {value}) failed")
 
 
 def exp_clear():
@@ -294,11 +448,9 @@ def atrous_geometry(kernel: str, W: int, H: int, step: int, blur_variance: int =
     LDS bytes], estimate in us or None) of one a-trous level on `kernel` (LEVEL_KERNEL_NAMES; lattice: [supported, log2k, pstride,
     band_rows, n_bands, grid blocks, block threads, LDS bytes]).  Host arithmetic only: works without a device."""
     out, est = (C.c_int * 8)(), C.c_double()
-    f = load_library(experiments=True).svgf_exp_atrous_geometry
-    f.argtypes = [C.c_int] * 7 + [C.POINTER(C.c_int), C.POINTER(C.c_double)]
-    rc = f(LEVEL_KERNEL_NAMES.index(kernel), W, H, step, blur_variance, has_variance_plane, n_cu, out, C.byref(est))
-    if rc != SVGF_OK:
-        raise SvgfError(f"svgf_exp_atrous_geometry({kernel}, {W}x{H}, step {step}, {n_cu} CUs) -> {rc}")
+    rc = load_library(experiments=True).svgf_exp_atrous_geometry(LEVEL_KERNEL_NAMES.index(kernel), W, H, step, blur_variance, has_variance_plane,
+                                                                 n_cu, out, C.byref(est))
+    _check(rc, "svgf_exp_atrous_geometry", f"svgf_exp_atrous_geometry({kernel}, {W}x{H}, step {step}, {n_cu} CUs) -> {rc}")
     return list(out), (None if np.isnan(est.value) else est.value)
 
 
@@ -310,8 +462,7 @@ def load_library(path: str | None = None, experiments: bool = False):
         experiments = True
     if path is None and experiments:
         if _lib_exp is None:
-            _lib_exp = load_library(LIB_EXP_PATH)
-            _lib_exp.svgf_exp_set.argtypes = [C.c_char_p, C.c_int]
+            _lib_exp = _declare(load_library(LIB_EXP_PATH), _EXP_PROTOTYPES)
         return _lib_exp
     if _lib is not None and path is None:
         return _lib
@@ -327,91 +478,9 @@ def load_library(path: str | None = None, experiments: bool = False):
     if not os.path.exists(path):
         raise SvgfError(f"{path} not found: build it first (python -c 'import __graft_entry__ as g; g.build()'). "
                         "There is no CPU fallback.")
-    lib = C.CDLL(path)
-    vp, ip = C.c_void_p, C.c_int
-    lib.svgf_version.restype = ip
-    lib.svgf_params_default.argtypes = [C.POINTER(SvgfParams)]
-    lib.svgf_create.argtypes = [ip, ip, ip, C.POINTER(vp)]
-    lib.svgf_create_ex.argtypes = [ip, ip, ip, C.c_uint, C.POINTER(vp)]
-    lib.svgf_enable_pipeline.argtypes = [vp]
-    lib.svgf_pipeline_status.argtypes = [vp]
-    lib.svgf_pipeline_status.restype = ip
-    lib.svgf_streams_overlap.argtypes = [ip, vp, vp]
-    lib.svgf_streams_overlap.restype = ip
-    lib.svgf_destroy.argtypes = [vp]
-    lib.svgf_reset.argtypes = [vp]
-    lib.svgf_denoise.argtypes = [vp, vp, vp, vp, C.POINTER(SvgfCamera), C.POINTER(SvgfParams), vp]
-    lib.svgf_denoise_motion.argtypes = [vp, vp, vp, vp, vp, ip, C.POINTER(SvgfCamera), C.POINTER(SvgfParams), vp]
-    lib.svgf_denoise_planar_motion.argtypes = [vp, vp, vp, vp, ip, C.POINTER(SvgfCamera), C.POINTER(SvgfParams), vp]
-    lib.svgf_motion_reproject.argtypes = [ip, vp, ip, vp, vp, vp, ip, ip, C.POINTER(SvgfCamera), C.POINTER(C.c_float), vp, ip, vp]
-    lib.svgf_upsample.argtypes = [ip, vp, C.POINTER(SvgfGuide), ip, ip, vp, C.POINTER(SvgfGuide), ip, ip, C.POINTER(SvgfUpsampleParams), vp]
-    lib.svgf_transfer_history.argtypes = [vp, vp, vp]
-    lib.svgf_set_history_clamp.argtypes = [vp, ip, C.c_float]
-    lib.svgf_get_history_clamp.argtypes = [vp, C.POINTER(ip), C.POINTER(C.c_float)]
-    lib.svgf_set_firefly_filter.argtypes = [vp, ip, C.c_float]
-    lib.svgf_get_firefly_filter.argtypes = [vp, C.POINTER(ip), C.POINTER(C.c_float)]
-    lib.svgf_set_output_taa.argtypes = [vp, C.c_float, C.c_float]
-    lib.svgf_get_output_taa.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
-    lib.svgf_set_object_motion.argtypes = [vp, vp, ip]
-    lib.svgf_get_object_motion.argtypes = [vp, C.POINTER(vp), C.POINTER(ip)]
-    lib.svgf_denoise_host.argtypes = [vp, vp, vp, vp, C.POINTER(SvgfCamera), C.POINTER(SvgfParams)]
-    lib.svgf_sync.argtypes = [vp]
-    lib.svgf_sync_stream.argtypes = [vp, vp]
-    lib.svgf_is_pipelined.argtypes = [vp]
-    lib.svgf_is_pipelined.restype = ip
-    lib.svgf_last_error.argtypes = [vp]
-    lib.svgf_last_error.restype = C.c_char_p
-    lib.svgf_width.argtypes = [vp]
-    lib.svgf_height.argtypes = [vp]
-    lib.svgf_read_state.argtypes = [vp, ip, vp, C.c_ulonglong]
-    lib.svgf_set_capture.argtypes = [vp, ip]
-    lib.svgf_profile_enable.argtypes = [vp, ip]
-    lib.svgf_profile_stride.argtypes = [vp, ip]
-    lib.svgf_profile_frames.argtypes = [vp]
-    lib.svgf_profile_frames.restype = C.c_longlong
-    lib.svgf_profile_read.argtypes = [vp, ip, ip, C.POINTER(ip), C.POINTER(C.c_float), C.POINTER(ip)]
-    lib.svgf_synth_camera.argtypes = [ip, ip, ip, ip, C.POINTER(SvgfCamera), C.POINTER(C.c_float)]
-    lib.svgf_synth_render.argtypes = [ip, vp, vp, ip, ip, C.POINTER(SvgfCamera), C.POINTER(SvgfSynthParams), vp]
-    lib.svgf_scene_render.argtypes = [ip, vp, vp, ip, ip, C.POINTER(SvgfCamera), C.POINTER(SvgfSynthParams), vp, ip,
-                                      C.POINTER(C.c_float), vp]
-    lib.svgf_scene_render_mesh.argtypes = [ip, vp, vp, ip, ip, C.POINTER(SvgfCamera), C.POINTER(SvgfSynthParams), vp, ip,
-                                           vp, vp, vp, vp, ip, vp, vp, vp, ip, C.POINTER(C.c_float), vp]
-    lib.svgf_scene_render_mesh_planar.argtypes = [ip, vp, C.POINTER(SvgfPlanarGBuffer), ip, ip, C.POINTER(SvgfCamera), C.POINTER(SvgfSynthParams), vp, ip,
-                                                  vp, vp, vp, vp, ip, vp, vp, vp, ip, C.POINTER(C.c_float), vp]
-    lib.svgf_planar_gbuffer.argtypes = [vp, C.POINTER(SvgfPlanarGBuffer)]
-    lib.svgf_planar_gbuffer_stream.argtypes = [vp, C.POINTER(SvgfPlanarGBuffer), vp]
-    lib.svgf_denoise_planar.argtypes = [vp, vp, vp, C.POINTER(SvgfCamera), C.POINTER(SvgfParams), vp]
-    lib.svgf_synth_render_planar.argtypes = [ip, vp, C.POINTER(SvgfPlanarGBuffer), ip, ip, C.POINTER(SvgfCamera), C.POINTER(SvgfSynthParams), vp]
-    lib.svgf_params_sizeof.restype = ip
+    lib = _declare(C.CDLL(path), _PROTOTYPES)
     if lib.svgf_params_sizeof() != C.sizeof(SvgfParams):     # the struct grows at its tail between ABI versions
         raise SvgfError(f"libsvgf_hip.so was built with sizeof(SvgfParams) = {lib.svgf_params_sizeof()}, this binding has {C.sizeof(SvgfParams)}")
-    lib.svgf_display_pack.argtypes = [ip, vp, vp, vp, ip, ip, vp]
-    lib.svgf_save_png.argtypes = [C.c_char_p, vp, ip, ip, ip]
-    lib.svgf_exposure_reset.argtypes = [ip, vp, vp]
-    lib.svgf_exposure_meter.argtypes = [ip, vp, vp, ip, ip, C.POINTER(SvgfExposureParams), vp]
-    lib.svgf_display_tonemap.argtypes = [ip, vp, vp, vp, ip, ip, C.POINTER(SvgfTonemapParams), vp, vp]
-    lib.svgf_tonemap_srgb_table.argtypes = [C.POINTER(C.c_float)]
-    lib.svgf_quality_state_bytes.argtypes = [ip, ip]
-    lib.svgf_quality_state_bytes.restype = C.c_ulonglong
-    lib.svgf_quality_windows.argtypes = [ip, ip, C.POINTER(ip), C.POINTER(ip)]
-    lib.svgf_quality_meter.argtypes = [ip, vp, vp, vp, ip, ip, C.POINTER(SvgfQualityParams), vp, vp, vp, vp]
-    lib.svgf_quality_read.argtypes = [ip, vp, C.POINTER(SvgfQualityResult), vp]
-    lib.svgf_scene_create.argtypes = [ip, vp, ip, vp, vp, vp, vp, ip, vp, vp, vp, ip, C.POINTER(SvgfSceneBuildParams), C.POINTER(vp)]
-    lib.svgf_scene_destroy.argtypes = [vp]
-    lib.svgf_scene_info.argtypes = [vp, C.POINTER(SvgfSceneInfo)]
-    lib.svgf_scene_draw.argtypes = [vp, vp, vp, ip, ip, C.POINTER(SvgfCamera), C.POINTER(SvgfSynthParams), C.POINTER(C.c_float), vp]
-    lib.svgf_scene_draw_planar.argtypes = [vp, vp, C.POINTER(SvgfPlanarGBuffer), ip, ip, C.POINTER(SvgfCamera), C.POINTER(SvgfSynthParams),
-                                           C.POINTER(C.c_float), vp]
-    lib.svgf_bvh_build_host.argtypes = [vp, ip, C.POINTER(SvgfSceneBuildParams), vp, C.POINTER(ip), vp, C.POINTER(ip)]
-    lib.svgf_scene_enable_pose.argtypes = [vp, ip]
-    lib.svgf_scene_pose.argtypes = [vp, vp, ip, vp, vp]
-    lib.svgf_scene_read.argtypes = [vp, ip, vp, C.c_ulonglong]
-    lib.svgf_scene_draw_shadowed.argtypes = [vp, vp, vp, C.POINTER(SvgfPlanarGBuffer), ip, ip, C.POINTER(SvgfCamera), C.POINTER(SvgfSynthParams),
-                                             C.POINTER(SvgfSceneLight), vp]
-    lib.svgf_scene_view.argtypes = [vp, C.POINTER(SvgfSceneView)]
-    lib.svgf_scene_adopt_tree.argtypes = [vp, vp, vp, ip, ip, ip]
-    lib.svgf_pose_rigid.argtypes = [C.POINTER(C.c_float), C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float), vp]
-    lib.svgf_bvh_refit_plan_host.argtypes = [vp, ip, ip, vp, vp, vp, vp, vp]
     if path == LIB_PATH:
         _lib = lib
     return lib
@@ -434,106 +503,64 @@ _DRAW_PARTS = {"trace": dict(params=SvgfTraceParams), "path": dict(params=SvgfPa
                "highlight": dict(params=SvgfPathParams, table=True, virtual=True, rough=True, highlight=True)}
 # the record a device table's create takes (svgf_<name>_table_create / _destroy / _size)
 _TABLE_RECORD = {"gloss": SvgfSurface, "rough": C.c_float}
-_companion_libs = {}
+
+
+def _companion_prototypes(name):
+    """The prototypes of libsvgf_<name>.so, a row of COMPANIONS, in _PROTOTYPES' form."""
+    vp, ip, P = C.c_void_p, C.c_int, C.POINTER
+    protos = {f"svgf_{name}_version": (ip, None)} if f"svgf_{name}_version" in companion_exports(name) else {}
+    if name in _TABLE_RECORD:
+        protos[f"svgf_{name}_table_create"] = (ip, [ip, P(_TABLE_RECORD[name]), ip, P(vp)])
+        protos[f"svgf_{name}_table_destroy"] = (None, [vp])
+        protos[f"svgf_{name}_table_size"] = (ip, [vp])
+    if name == "split":
+        protos["svgf_trace_draw_split"] = (ip, _draw_argtypes(split=True, **_DRAW_PARTS["trace"]))
+        protos["svgf_trace_compose"] = (ip, [ip, vp, vp, vp, P(SvgfGuide), ip, ip, vp])
+    else:
+        protos[f"svgf_{name}_draw"] = (ip, _draw_argtypes(**_DRAW_PARTS[name]))
+        if name != "trace":
+            protos[f"svgf_{name}_draw_split"] = (ip, _draw_argtypes(split=True, **_DRAW_PARTS[name]))
+    return protos
+
+
+_linked_libs = {}
+
+
+def _load_linked(name: str, prototypes):
+    """Load libsvgf_<name>.so, a library that links against the product library (loaded first), declare prototypes(name) (a table in
+    _PROTOTYPES' form) and keep the handle.  Fails loudly when the file is absent, and - where the table has svgf_<name>_version - when
+    the library was compiled against another svgf.h than the product library found."""
+    if name not in _linked_libs:
+        product, path, table = load_library(), companion_path(name), prototypes(name)
+        if not os.path.exists(path):
+            raise SvgfError(f"{path} not found: build it first (python -c 'import __graft_entry__ as g; g.build()').")
+        lib = _declare(C.CDLL(path), table)
+        if f"svgf_{name}_version" in table:
+            version = getattr(lib, f"svgf_{name}_version")
+            if version() != product.svgf_version():
+                raise SvgfError(f"libsvgf_{name}.so was built for ABI {version():#x}, libsvgf_hip.so is {product.svgf_version():#x}")
+        _linked_libs[name] = lib
+    return _linked_libs[name]
 
 
 def _load_companion(name: str):
-    """Load libsvgf_<name>.so (after the product library it links against), declare its prototypes and keep the handle.  Fails loudly
-    when it is absent, and - for the libraries that export svgf_<name>_version - when it was compiled against another svgf.h than the
-    product library found."""
-    if name in _companion_libs:
-        return _companion_libs[name]
-    product = load_library()
-    path, exports = companion_path(name), companion_exports(name)
-    if not os.path.exists(path):
-        raise SvgfError(f"{path} not found: build it first (python -c 'import __graft_entry__ as g; g.build()').")
-    lib = C.CDLL(path)
-    vp, ip = C.c_void_p, C.c_int
-    if f"svgf_{name}_version" in exports:
-        version = getattr(lib, f"svgf_{name}_version")
-        version.restype = ip
-        if version() != product.svgf_version():
-            raise SvgfError(f"libsvgf_{name}.so was built for ABI {version():#x}, libsvgf_hip.so is {product.svgf_version():#x}")
-    if name in _TABLE_RECORD:
-        getattr(lib, f"svgf_{name}_table_create").argtypes = [ip, C.POINTER(_TABLE_RECORD[name]), ip, C.POINTER(vp)]
-        getattr(lib, f"svgf_{name}_table_destroy").argtypes = [vp]
-        getattr(lib, f"svgf_{name}_table_destroy").restype = None
-        getattr(lib, f"svgf_{name}_table_size").argtypes = [vp]
-    if name == "split":
-        lib.svgf_trace_draw_split.argtypes = _draw_argtypes(split=True, **_DRAW_PARTS["trace"])
-        lib.svgf_trace_compose.argtypes = [ip, vp, vp, vp, C.POINTER(SvgfGuide), ip, ip, vp]
-    else:
-        getattr(lib, f"svgf_{name}_draw").argtypes = _draw_argtypes(**_DRAW_PARTS[name])
-        if name != "trace":
-            getattr(lib, f"svgf_{name}_draw_split").argtypes = _draw_argtypes(split=True, **_DRAW_PARTS[name])
-    _companion_libs[name] = lib
-    return lib
+    return _load_linked(name, _companion_prototypes)
 
 
-def load_trace_library():
-    return _load_companion("trace")
+def _companion_loader(name):
+    def load():
+        return _load_companion(name)
+    load.__name__ = load.__qualname__ = f"load_{name}_library"
+    return load
 
 
-def load_split_library():
-    return _load_companion("split")
-
-
-def load_path_library():
-    return _load_companion("path")
-
-
-def load_gloss_library():
-    return _load_companion("gloss")
-
-
-def load_virtual_library():
-    return _load_companion("virtual")
-
-
-def load_rough_library():
-    return _load_companion("rough")
-
-
-def load_highlight_library():
-    return _load_companion("highlight")
-
-
-class SvgfLbvhParams(C.Structure):
-    _fields_ = [("leaf_tris", C.c_int)]
-
-
-class SvgfLbvhInfo(C.Structure):
-    _fields_ = [(k, C.c_int) for k in ("n_tris", "n_leaves", "n_nodes", "leaf_tris", "idx_bits", "axis_bits", "key_bits", "depth_bound",
-                                       "launches")] + [("device_bytes", C.c_ulonglong)]
-
-
-_lbvh_lib = None
+(load_trace_library, load_split_library, load_path_library, load_gloss_library, load_virtual_library, load_rough_library,
+ load_highlight_library) = (_companion_loader(c.name) for c in COMPANIONS)
 
 
 def load_lbvh_library():
-    """Load libsvgf_lbvh.so (row f24; after the product library it links against) and declare its prototypes.  Fails loudly when it is
-    absent or was compiled against another svgf.h than the product library."""
-    global _lbvh_lib
-    if _lbvh_lib is not None:
-        return _lbvh_lib
-    product = load_library()
-    if not os.path.exists(LIB_LBVH_PATH):
-        raise SvgfError(f"{LIB_LBVH_PATH} not found: build it first (python -c 'import __graft_entry__ as g; g.build()').")
-    lib = C.CDLL(LIB_LBVH_PATH)
-    vp, ip = C.c_void_p, C.c_int
-    lib.svgf_lbvh_version.restype = ip
-    if lib.svgf_lbvh_version() != product.svgf_version():
-        raise SvgfError(f"libsvgf_lbvh.so was built for ABI {lib.svgf_lbvh_version():#x}, libsvgf_hip.so is {product.svgf_version():#x}")
-    lib.svgf_lbvh_create.argtypes = [vp, C.POINTER(SvgfLbvhParams), C.POINTER(vp)]
-    lib.svgf_lbvh_build.argtypes = [vp, vp]
-    lib.svgf_lbvh_attach.argtypes = [vp, vp]
-    lib.svgf_lbvh_info.argtypes = [vp, C.POINTER(SvgfLbvhInfo)]
-    lib.svgf_lbvh_read.argtypes = [vp, ip, vp, C.c_ulonglong]
-    lib.svgf_lbvh_destroy.argtypes = [vp]
-    lib.svgf_lbvh_destroy.restype = None
-    lib.svgf_lbvh_build_host.argtypes = [vp, ip, C.POINTER(SvgfLbvhParams), vp, vp, vp, C.POINTER(SvgfLbvhInfo)]
-    _lbvh_lib = lib
-    return lib
+    """libsvgf_lbvh.so (row f24)."""
+    return _load_linked("lbvh", lambda name: _LBVH_PROTOTYPES)
 
 
 def lbvh_build_host(tri_boxes, leaf_tris: int = 0):
@@ -544,10 +571,8 @@ def lbvh_build_host(tri_boxes, leaf_tris: int = 0):
     L = int(leaf_tris) if 1 <= int(leaf_tris) <= 8 else 4
     nodes, order, keys = np.zeros(2 * max(-(-n // L), 1), BVH_NODE_DTYPE), np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.uint64)
     info, p = SvgfLbvhInfo(), SvgfLbvhParams(int(leaf_tris))
-    rc = load_lbvh_library().svgf_lbvh_build_host(tb.ctypes.data if n else None, n, C.byref(p), nodes.ctypes.data, order.ctypes.data,
-                                                  keys.ctypes.data, C.byref(info))
-    if rc != SVGF_OK:
-        raise SvgfError(f"svgf_lbvh_build_host failed ({rc})")
+    _call(load_lbvh_library(), "svgf_lbvh_build_host", tb.ctypes.data if n else None, n, C.byref(p), nodes.ctypes.data, order.ctypes.data,
+          keys.ctypes.data, C.byref(info))
     return nodes[:info.n_nodes].copy(), order[:n].copy(), keys[:n].copy(), {k: int(getattr(info, k)) for k, _ in SvgfLbvhInfo._fields_}
 
 
@@ -559,12 +584,9 @@ class _DeviceTable:
     def __init__(self, records=None, device: int = 0):
         self.lib = _load_companion(self.name)
         arr = np.zeros(0, self.record_dtype) if records is None else np.ascontiguousarray(records, dtype=self.record_dtype).reshape(-1)
-        self.h = C.c_void_p()
-        rc = getattr(self.lib, f"svgf_{self.name}_table_create")(int(device), arr.ctypes.data_as(C.POINTER(self.record_ctype)), len(arr), C.byref(self.h))
-        if rc != SVGF_OK:
-            self.h = C.c_void_p()
-            raise SvgfError(f"svgf_{self.name}_table_create failed ({rc})")
-        self.device = int(device)
+        self.h, h = C.c_void_p(), C.c_void_p()      # a table whose create failed stays without a handle
+        _call(self.lib, f"svgf_{self.name}_table_create", int(device), arr.ctypes.data_as(C.POINTER(self.record_ctype)), len(arr), C.byref(h))
+        self.h, self.device = h, int(device)
 
     def __len__(self):
         return int(getattr(self.lib, f"svgf_{self.name}_table_size")(self.h))
@@ -619,19 +641,6 @@ def _filled(struct, values):
     return struct(*[c(v) for c, v in zip(_CONVERTERS[struct], values)])
 
 
-def _ptr(x):
-    """device pointer of a torch tensor / int / None"""
-    if x is None:
-        return None
-    if isinstance(x, int):
-        return x
-    if hasattr(x, "data_ptr"):
-        if not x.is_contiguous():
-            raise SvgfError("tensor must be contiguous")
-        return x.data_ptr()
-    raise TypeError(type(x))
-
-
 class Denoiser:
     """One SVGF context on one GPU (denoiseInit .. denoiseFree of the reference, handle-based)."""
 
@@ -644,15 +653,23 @@ class Denoiser:
         self.device = int(device)
         self.ui = SvgfParams()
         self.lib.svgf_params_default(C.byref(self.ui))
-        h = C.c_void_p()
-        rc = self.lib.svgf_create_ex(int(device), self.width, self.height, CREATE_PIPELINED if pipelined else 0, C.byref(h))
-        if rc != SVGF_OK:
-            raise SvgfError(f"svgf_create_ex({device},{width},{height}) -> {rc}: {self.lib.svgf_last_error(None).decode()}")
+        self.h, h = None, C.c_void_p()      # no context yet: a failing create reports the library's own last error
+        self._check(self.lib.svgf_create_ex(int(device), self.width, self.height, CREATE_PIPELINED if pipelined else 0, C.byref(h)),
+                    f"svgf_create_ex({device},{width},{height})")
         self.h = h
 
     def _check(self, rc, what):
         if rc != SVGF_OK:
             raise SvgfError(f"{what} -> {rc}: {self.lib.svgf_last_error(self.h).decode()}")
+
+    def _frame(self, camera, params, stream=None):
+        """What every denoise entry point takes last: the camera and the parameter block (`params` or self.ui) by reference, the stream."""
+        return C.byref(_camera(camera)), C.byref(params if params is not None else self.ui), _stream(stream)
+
+    def _pair(self, symbol, first, second):
+        """A getter with two out-parameters."""
+        self._check(getattr(self.lib, symbol)(self.h, C.byref(first), C.byref(second)), symbol)
+        return first.value, second.value
 
     # --- reference-named lifecycle ---
     def free(self):
@@ -676,15 +693,12 @@ class Denoiser:
         """Device pointers (ints) or contiguous CUDA torch tensors.  Asynchronous on `stream`.
         motion: a device plane of per-pixel previous-frame coordinates in `motion_format` (svgf_denoise_motion); None: the
         history is found through the previous camera (svgf_denoise)."""
-        cam = camera if isinstance(camera, SvgfCamera) else SvgfCamera.from_dict(camera)
-        p = params if params is not None else self.ui
-        s = None if stream is None else (stream if isinstance(stream, int) else stream.cuda_stream)
+        frame = self._frame(camera, params, stream)
         if motion is None:
-            self._check(self.lib.svgf_denoise(self.h, _ptr(out), _ptr(inp), _ptr(gbuffer), C.byref(cam), C.byref(p), s),
-                        "svgf_denoise")
+            self._check(self.lib.svgf_denoise(self.h, _ptr(out), _ptr(inp), _ptr(gbuffer), *frame), "svgf_denoise")
         else:
-            self._check(self.lib.svgf_denoise_motion(self.h, _ptr(out), _ptr(inp), _ptr(gbuffer), _ptr(motion), int(motion_format),
-                                                     C.byref(cam), C.byref(p), s), "svgf_denoise_motion")
+            self._check(self.lib.svgf_denoise_motion(self.h, _ptr(out), _ptr(inp), _ptr(gbuffer), _ptr(motion), int(motion_format), *frame),
+                        "svgf_denoise_motion")
 
     def planar_gbuffer(self, stream=None) -> SvgfPlanarGBuffer:
         """The planes the NEXT denoise_planar() call consumes: a producer fills them in place.
@@ -694,21 +708,18 @@ class Denoiser:
         if stream is None:
             self._check(self.lib.svgf_planar_gbuffer(self.h, C.byref(g)), "svgf_planar_gbuffer")
         else:
-            s = stream if isinstance(stream, int) else stream.cuda_stream
-            self._check(self.lib.svgf_planar_gbuffer_stream(self.h, C.byref(g), s), "svgf_planar_gbuffer_stream")
+            self._check(self.lib.svgf_planar_gbuffer_stream(self.h, C.byref(g), _stream(stream)), "svgf_planar_gbuffer_stream")
         return g
 
     def denoise_planar(self, out, inp, camera, params: SvgfParams | None = None, stream=None, motion=None,
                        motion_format: int = MOTION_PREV_COORD_F32):
         """One frame whose G-buffer was written into planar_gbuffer()'s planes.  Asynchronous on `stream`.  motion: as in denoise()."""
-        cam = camera if isinstance(camera, SvgfCamera) else SvgfCamera.from_dict(camera)
-        p = params if params is not None else self.ui
-        s = None if stream is None else (stream if isinstance(stream, int) else stream.cuda_stream)
+        frame = self._frame(camera, params, stream)
         if motion is None:
-            self._check(self.lib.svgf_denoise_planar(self.h, _ptr(out), _ptr(inp), C.byref(cam), C.byref(p), s), "svgf_denoise_planar")
+            self._check(self.lib.svgf_denoise_planar(self.h, _ptr(out), _ptr(inp), *frame), "svgf_denoise_planar")
         else:
-            self._check(self.lib.svgf_denoise_planar_motion(self.h, _ptr(out), _ptr(inp), _ptr(motion), int(motion_format),
-                                                            C.byref(cam), C.byref(p), s), "svgf_denoise_planar_motion")
+            self._check(self.lib.svgf_denoise_planar_motion(self.h, _ptr(out), _ptr(inp), _ptr(motion), int(motion_format), *frame),
+                        "svgf_denoise_planar_motion")
 
     def denoise_host(self, color: np.ndarray, gbuffer: np.ndarray, camera, params: SvgfParams | None = None, motion=None,
                      motion_format: int = MOTION_PREV_COORD_F32) -> np.ndarray:
@@ -718,11 +729,9 @@ class Denoiser:
         gbuffer = np.ascontiguousarray(gbuffer)
         assert color.size == 3 * self.width * self.height and gbuffer.nbytes == 52 * self.width * self.height
         out = np.empty_like(color)
-        cam = camera if isinstance(camera, SvgfCamera) else SvgfCamera.from_dict(camera)
-        p = params if params is not None else self.ui
         if motion is None:
             self._check(self.lib.svgf_denoise_host(self.h, out.ctypes.data, color.ctypes.data, gbuffer.ctypes.data,
-                                                   C.byref(cam), C.byref(p)), "svgf_denoise_host")
+                                                   *self._frame(camera, params)[:2]), "svgf_denoise_host")
             return out
         import torch
         motion = np.ascontiguousarray(motion, dtype=np.float16 if motion_format == MOTION_DELTA_F16 else np.float32)
@@ -733,7 +742,7 @@ class Denoiser:
         t_m = torch.from_numpy(motion).to(dev)
         t_out = torch.empty(color.shape, dtype=torch.float32, device=dev)
         torch.cuda.synchronize(dev)
-        self.denoise(t_out, t_in, t_g, cam, p, motion=t_m, motion_format=motion_format)
+        self.denoise(t_out, t_in, t_g, camera, params, motion=t_m, motion_format=motion_format)
         self.sync()
         return t_out.cpu().numpy()
 
@@ -757,8 +766,7 @@ class Denoiser:
 
     def sync_stream(self, stream=None):
         """Wait for what has been enqueued on `stream` only (svgf_sync waits for the whole device, as the reference does)."""
-        s = None if stream is None else (stream if isinstance(stream, int) else stream.cuda_stream)
-        self._check(self.lib.svgf_sync_stream(self.h, s), "svgf_sync_stream")
+        self._check(self.lib.svgf_sync_stream(self.h, _stream(stream)), "svgf_sync_stream")
 
     def level_kernels(self) -> list[tuple[str, int, float | None, float | None]]:
         """Experiments build only: per a-trous level of the last frame, (kernel name, step, lane estimate us, strip estimate us);
@@ -767,9 +775,7 @@ class Denoiser:
             raise SvgfError("level_kernels: this context is not in the experiments build (Denoiser(..., experiments=True))")
         kinds, steps = (C.c_int * MAX_LEVELS)(), (C.c_int * MAX_LEVELS)()
         lane, strip = (C.c_double * MAX_LEVELS)(), (C.c_double * MAX_LEVELS)()
-        f = self.lib.svgf_exp_level_kernels
-        f.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int]
-        n = f(self.h, kinds, steps, lane, strip, MAX_LEVELS)
+        n = self.lib.svgf_exp_level_kernels(self.h, kinds, steps, lane, strip, MAX_LEVELS)
         if n < 0:
             raise SvgfError(f"svgf_exp_level_kernels -> {n}")
         est = lambda v: None if np.isnan(v) else float(v)      # noqa: E731
@@ -785,9 +791,7 @@ class Denoiser:
 
     def history_clamp(self) -> tuple[int, float]:
         """(radius, sigma_scale) as set by set_history_clamp(); (0, 0.0) on a fresh context."""
-        r, k = C.c_int(), C.c_float()
-        self._check(self.lib.svgf_get_history_clamp(self.h, C.byref(r), C.byref(k)), "svgf_get_history_clamp")
-        return int(r.value), float(k.value)
+        return self._pair("svgf_get_history_clamp", C.c_int(), C.c_float())
 
     def set_firefly_filter(self, rank: int, scale: float = 1.0):
         """svgf_set_firefly_filter: frames run as if the input colour had been filtered, every pixel brighter than scale times the
@@ -796,9 +800,7 @@ class Denoiser:
 
     def firefly_filter(self) -> tuple[int, float]:
         """(rank, scale) as set by set_firefly_filter(); (0, 0.0) on a fresh context."""
-        r, k = C.c_int(), C.c_float()
-        self._check(self.lib.svgf_get_firefly_filter(self.h, C.byref(r), C.byref(k)), "svgf_get_firefly_filter")
-        return int(r.value), float(k.value)
+        return self._pair("svgf_get_firefly_filter", C.c_int(), C.c_float())
 
     def set_output_taa(self, alpha: float, sigma_scale: float = 1.0):
         """svgf_set_output_taa: blend every frame's image with the previous frame's output, reprojected like the temporal pass's
@@ -809,9 +811,7 @@ class Denoiser:
 
     def output_taa(self) -> tuple[float, float]:
         """(alpha, sigma_scale) as set by set_output_taa(); (0.0, 0.0) on a fresh context."""
-        a, k = C.c_float(), C.c_float()
-        self._check(self.lib.svgf_get_output_taa(self.h, C.byref(a), C.byref(k)), "svgf_get_output_taa")
-        return float(a.value), float(k.value)
+        return self._pair("svgf_get_output_taa", C.c_float(), C.c_float())
 
     def set_object_motion(self, geom_xf, n_geoms: int | None = None):
         """svgf_set_object_motion: geom_xf is a contiguous device float32[n, 12] tensor (or a raw pointer with n_geoms) of 3x4
@@ -825,9 +825,7 @@ class Denoiser:
 
     def object_motion(self) -> tuple[int | None, int]:
         """(device pointer or None, n_geoms) as set by set_object_motion(); (None, 0) on a fresh context."""
-        ptr, n = C.c_void_p(), C.c_int()
-        self._check(self.lib.svgf_get_object_motion(self.h, C.byref(ptr), C.byref(n)), "svgf_get_object_motion")
-        return ptr.value, int(n.value)
+        return self._pair("svgf_get_object_motion", C.c_void_p(), C.c_int())
 
     def transfer_history_from(self, src: "Denoiser", stream=None):
         """svgf_transfer_history: everything this context's next frame reads as history becomes `src`'s, resampled to this
@@ -837,8 +835,7 @@ class Denoiser:
         goes there too."""
         if not isinstance(src, Denoiser) or src.lib is not self.lib:
             raise SvgfError("transfer_history_from: src must be a Denoiser of the same library")
-        s = None if stream is None else (stream if isinstance(stream, int) else stream.cuda_stream)
-        self._check(self.lib.svgf_transfer_history(self.h, src.h, s), "svgf_transfer_history")
+        self._check(self.lib.svgf_transfer_history(self.h, src.h, _stream(stream)), "svgf_transfer_history")
 
     def read_state(self, which: int) -> np.ndarray:
         """Host copy of one state plane (STATE_*); STATE_OUTPUT_HISTORY is float32[H, W, 4] = {r, g, b, geomId bits} and raises
@@ -879,10 +876,7 @@ class Denoiser:
 # --- the denoiser's inputs produced on the device -------------------------------------------
 def streams_overlap(stream_a, stream_b, device: int = 0) -> bool:
     """svgf_streams_overlap: do kernels on the caller's two streams run side by side (what inputs_ready = 2 needs)?"""
-    lib = load_library()
-    sa = stream_a if isinstance(stream_a, int) else stream_a.cuda_stream
-    sb = stream_b if isinstance(stream_b, int) else stream_b.cuda_stream
-    rc = lib.svgf_streams_overlap(int(device), sa, sb)
+    rc = load_library().svgf_streams_overlap(int(device), _stream(stream_a), _stream(stream_b))
     if rc < 0:
         raise SvgfError(f"svgf_streams_overlap failed ({rc})")
     return bool(rc)
@@ -890,12 +884,9 @@ def streams_overlap(stream_a, stream_b, device: int = 0) -> bool:
 
 def synth_camera(frame: int, moving: bool, width: int, height: int):
     """svgf_synth_camera: (SvgfCamera, (plx, ply)) computed by the library (C float math)."""
-    lib = load_library()
     cam = SvgfCamera()
     pl = (C.c_float * 2)()
-    rc = lib.svgf_synth_camera(int(frame), int(bool(moving)), int(width), int(height), C.byref(cam), pl)
-    if rc != SVGF_OK:
-        raise SvgfError(f"svgf_synth_camera failed ({rc})")
+    _call(load_library(), "svgf_synth_camera", int(frame), int(bool(moving)), int(width), int(height), C.byref(cam), pl)
     return cam, (pl[0], pl[1])
 
 
@@ -904,36 +895,17 @@ def synth_render(out_rgb, out_gbuffer, width: int, height: int, camera, frame: i
     """svgf_synth_render: writes packed rgb (H*W*3 float32) and 52-byte texels (H*W*52 bytes) into device memory
     (torch CUDA tensors or raw pointers).  `camera` is an SvgfCamera or a synth.camera_for_frame() dict;
     `pixel_length` defaults to synth._pixel_length(width, height, 45) so that host and device producers agree."""
-    lib = load_library()
-    cam = camera if isinstance(camera, SvgfCamera) else SvgfCamera.from_dict(camera)
-    if pixel_length is None:
-        from . import synth as _synth
-        pixel_length = _synth._pixel_length(width, height, 45.0)
-    sp = SvgfSynthParams(int(frame), int(seed), float(noise), float(fireflies))
-    sp.pixel_length[0] = float(pixel_length[0])
-    sp.pixel_length[1] = float(pixel_length[1])
-    s = None if stream is None else (stream if isinstance(stream, int) else stream.cuda_stream)
-    rc = lib.svgf_synth_render(int(device), _ptr(out_rgb), _ptr(out_gbuffer), int(width), int(height), C.byref(cam),
-                               C.byref(sp), s)
-    if rc != SVGF_OK:
-        raise SvgfError(f"svgf_synth_render failed ({rc})")
+    cam, sp = _view(camera, width, height, frame, seed, noise, fireflies, pixel_length, camera_fovy=False)
+    _call(load_library(), "svgf_synth_render", int(device), _ptr(out_rgb), _ptr(out_gbuffer), int(width), int(height), C.byref(cam), C.byref(sp),
+          _stream(stream))
 
 
 def synth_render_planar(out_rgb, planes: SvgfPlanarGBuffer, width: int, height: int, camera, frame: int, seed: int = 1,
                         noise: float = 0.6, fireflies: float = 0.02, pixel_length=None, device: int = 0, stream=None):
     """svgf_synth_render_planar: the frame of synth_render written into a Denoiser's planar_gbuffer() planes."""
-    lib = load_library()
-    cam = camera if isinstance(camera, SvgfCamera) else SvgfCamera.from_dict(camera)
-    if pixel_length is None:
-        from . import synth as _synth
-        pixel_length = _synth._pixel_length(width, height, 45.0)
-    sp = SvgfSynthParams(int(frame), int(seed), float(noise), float(fireflies))
-    sp.pixel_length[0] = float(pixel_length[0])
-    sp.pixel_length[1] = float(pixel_length[1])
-    s = None if stream is None else (stream if isinstance(stream, int) else stream.cuda_stream)
-    rc = lib.svgf_synth_render_planar(int(device), _ptr(out_rgb), C.byref(planes), int(width), int(height), C.byref(cam), C.byref(sp), s)
-    if rc != SVGF_OK:
-        raise SvgfError(f"svgf_synth_render_planar failed ({rc})")
+    cam, sp = _view(camera, width, height, frame, seed, noise, fireflies, pixel_length, camera_fovy=False)
+    _call(load_library(), "svgf_synth_render_planar", int(device), _ptr(out_rgb), C.byref(planes), int(width), int(height), C.byref(cam),
+          C.byref(sp), _stream(stream))
 
 
 # --- per-pixel motion vectors: the plane svgf_denoise_motion reads, for rigid motion --------------------------------------
@@ -944,16 +916,11 @@ def motion_reproject(motion_out, width: int, height: int, prev_camera, gbuffer=N
     `geom_id` planes — tensors, raw pointers or a SvgfPlanarGBuffer's fields), mapped by geom_xf[geomId] (device float32[n, 12], 3x4
     row-major, this frame's world -> the previous frame's) and projected through `prev_camera` exactly as the temporal pass does.
     `motion_out`: device memory of width * height * 2 float32 (float16 for MOTION_DELTA_F16)."""
-    lib = load_library()
-    cam = prev_camera if isinstance(prev_camera, SvgfCamera) else SvgfCamera.from_dict(prev_camera)
     rs = (C.c_float * 2)(float(reproj_scale[0]), float(reproj_scale[1]))
     if geom_xf is not None and n_geoms is None:
         n_geoms = int(geom_xf.numel()) // 12
-    s = None if stream is None else (stream if isinstance(stream, int) else stream.cuda_stream)
-    rc = lib.svgf_motion_reproject(int(device), _ptr(motion_out), int(motion_format), _ptr(gbuffer), _ptr(position), _ptr(geom_id),
-                                   int(width), int(height), C.byref(cam), rs, _ptr(geom_xf), int(n_geoms or 0), s)
-    if rc != SVGF_OK:
-        raise SvgfError(f"svgf_motion_reproject failed ({rc})")
+    _call(load_library(), "svgf_motion_reproject", int(device), _ptr(motion_out), int(motion_format), _ptr(gbuffer), _ptr(position), _ptr(geom_id),
+          int(width), int(height), C.byref(_camera(prev_camera)), rs, _ptr(geom_xf), int(n_geoms or 0), _stream(stream))
 
 
 # --- guided upsampling: the full-size image from a reduced-size denoise ----------------------------------------------------
@@ -967,14 +934,10 @@ def upsample(out, hi_guide, width_hi: int, height_hi: int, rgb_lo, lo_guide, wid
     """svgf_upsample: `out` (device, height_hi * width_hi * 3 float32) from `rgb_lo`, the output of a denoise at width_lo x height_lo
     run with sepcolor = 1 and addcolor = 0, guided by the two G-buffers.  A guide is a SvgfGuide (guide(...)) or the AoS texels
     themselves (a tensor or a raw pointer).  sigma_x is in the scene's world units; 0 turns a term off."""
-    lib = load_library()
     hi, lo = (g if isinstance(g, SvgfGuide) else guide(gbuffer=g) for g in (hi_guide, lo_guide))
     up = SvgfUpsampleParams(float(sigma_n), float(sigma_x), int(modulate))
-    s = None if stream is None else (stream if isinstance(stream, int) else stream.cuda_stream)
-    rc = lib.svgf_upsample(int(device), _ptr(out), C.byref(hi), int(width_hi), int(height_hi), _ptr(rgb_lo), C.byref(lo),
-                           int(width_lo), int(height_lo), C.byref(up), s)
-    if rc != SVGF_OK:
-        raise SvgfError(f"svgf_upsample failed ({rc})")
+    _call(load_library(), "svgf_upsample", int(device), _ptr(out), C.byref(hi), int(width_hi), int(height_hi), _ptr(rgb_lo), C.byref(lo),
+          int(width_lo), int(height_lo), C.byref(up), _stream(stream))
 
 
 def trace_compose(out, direct, indirect, guide_or_gbuffer, width: int, height: int, device: int = 0, stream=None):
@@ -982,32 +945,20 @@ def trace_compose(out, direct, indirect, guide_or_gbuffer, width: int, height: i
     AoS texels, or an albedo plane) or from the AoS texels themselves (a tensor or a raw pointer).  `out` may be `direct` or
     `indirect`.  One launch on `stream`; never waits."""
     g = guide_or_gbuffer if isinstance(guide_or_gbuffer, SvgfGuide) else guide(gbuffer=guide_or_gbuffer)
-    rc = load_split_library().svgf_trace_compose(int(device), _ptr(out), _ptr(direct), _ptr(indirect), C.byref(g), int(width), int(height),
-                                                 _stream(stream))
-    if rc != SVGF_OK:
-        raise SvgfError(f"svgf_trace_compose failed ({rc})")
+    _call(load_split_library(), "svgf_trace_compose", int(device), _ptr(out), _ptr(direct), _ptr(indirect), C.byref(g), int(width), int(height),
+          _stream(stream))
 
 
 # --- SURVEY.md 8(f) row f2: the step after denoise() ----------------------------------------------------------------
 def display_pack(pbo, left, right, width: int, height: int, device: int = 0, stream=None):
     """svgf_display_pack: `left` | `right` (packed rgb float, device) -> (height, 2*width, 4) uint8 in device memory."""
-    lib = load_library()
-    s = None if stream is None else (stream if isinstance(stream, int) else stream.cuda_stream)
-    rc = lib.svgf_display_pack(int(device), _ptr(pbo), _ptr(left), _ptr(right), int(width), int(height), s)
-    if rc != SVGF_OK:
-        raise SvgfError(f"svgf_display_pack failed ({rc})")
+    _call(load_library(), "svgf_display_pack", int(device), _ptr(pbo), _ptr(left), _ptr(right), int(width), int(height), _stream(stream))
 
 
 # --- row f12: HDR display (luminance histogram, auto-exposure, tone-mapped pack) ---------------------------------------------------
-def _stream(stream):
-    return None if stream is None else (stream if isinstance(stream, int) else stream.cuda_stream)
-
-
 def exposure_reset(state, device: int = 0, stream=None):
     """svgf_exposure_reset: `state` (device, EXPOSURE_STATE_WORDS int32) back to "no metering yet", exposure 1."""
-    rc = load_library().svgf_exposure_reset(int(device), _ptr(state), _stream(stream))
-    if rc != SVGF_OK:
-        raise SvgfError(f"svgf_exposure_reset failed ({rc})")
+    _call(load_library(), "svgf_exposure_reset", int(device), _ptr(state), _stream(stream))
 
 
 def exposure_state(device: int = 0):
@@ -1023,9 +974,7 @@ def exposure_meter(state, rgb, width: int, height: int, key: float = 0.18, trim_
                    min_exposure: float = 1.0 / 64.0, max_exposure: float = 64.0, adapt: float = 1.0, device: int = 0, stream=None):
     """svgf_exposure_meter: the luminance histogram of `rgb` (packed rgb float, device) and the exposure step, into `state`."""
     ep = SvgfExposureParams(float(key), int(trim_low_1024), int(trim_high_1024), float(min_exposure), float(max_exposure), float(adapt))
-    rc = load_library().svgf_exposure_meter(int(device), _ptr(state), _ptr(rgb), int(width), int(height), C.byref(ep), _stream(stream))
-    if rc != SVGF_OK:
-        raise SvgfError(f"svgf_exposure_meter failed ({rc})")
+    _call(load_library(), "svgf_exposure_meter", int(device), _ptr(state), _ptr(rgb), int(width), int(height), C.byref(ep), _stream(stream))
 
 
 def display_tonemap(pbo, left, right, width: int, height: int, op: int = TONEMAP_ACES, transfer: int = TRANSFER_SRGB,
@@ -1033,18 +982,14 @@ def display_tonemap(pbo, left, right, width: int, height: int, op: int = TONEMAP
     """svgf_display_tonemap: `left` | `right` (or `right` alone when `left` is None) through exposure (exposure_bias x the metered
     exposure of `state`, or exposure_bias alone), tone curve and display transfer -> (height, 2*width or width, 4) uint8 on the device."""
     tp = SvgfTonemapParams(int(op), int(transfer), float(exposure_bias), float(white))
-    rc = load_library().svgf_display_tonemap(int(device), _ptr(pbo), _ptr(left), _ptr(right), int(width), int(height), C.byref(tp),
-                                             _ptr(state), _stream(stream))
-    if rc != SVGF_OK:
-        raise SvgfError(f"svgf_display_tonemap failed ({rc})")
+    _call(load_library(), "svgf_display_tonemap", int(device), _ptr(pbo), _ptr(left), _ptr(right), int(width), int(height), C.byref(tp),
+          _ptr(state), _stream(stream))
 
 
 def srgb_table() -> np.ndarray:
     """svgf_tonemap_srgb_table: the 256 float32 thresholds transfer 2 searches."""
     t = np.empty(256, dtype=np.float32)
-    rc = load_library().svgf_tonemap_srgb_table(t.ctypes.data_as(C.POINTER(C.c_float)))
-    if rc != SVGF_OK:
-        raise SvgfError(f"svgf_tonemap_srgb_table failed ({rc})")
+    _call(load_library(), "svgf_tonemap_srgb_table", t.ctypes.data_as(C.POINTER(C.c_float)))
     return t
 
 
@@ -1052,9 +997,7 @@ def srgb_table() -> np.ndarray:
 def quality_windows(width: int, height: int):
     """svgf_quality_windows: (nwx, nwy), the 8 x 8 windows at stride 4 that fit; (0, 0) below 8 pixels either way."""
     nwx, nwy = C.c_int(), C.c_int()
-    rc = load_library().svgf_quality_windows(int(width), int(height), C.byref(nwx), C.byref(nwy))
-    if rc != SVGF_OK:
-        raise SvgfError(f"svgf_quality_windows failed ({rc})")
+    _call(load_library(), "svgf_quality_windows", int(width), int(height), C.byref(nwx), C.byref(nwy))
     return nwx.value, nwy.value
 
 
@@ -1074,107 +1017,25 @@ def quality_meter(state, a, b, width: int, height: int, peak: float = 1.0, scale
     (quality_state); `exposure_state` is f12's state (the effective scale is scale x its exposure); the maps are optional device
     float32 outputs of height x width and quality_windows' nwy x nwx elements."""
     qp = SvgfQualityParams(float(peak), float(scale), int(clamp))
-    rc = load_library().svgf_quality_meter(int(device), _ptr(state), _ptr(a), _ptr(b), int(width), int(height), C.byref(qp),
-                                           _ptr(exposure_state), _ptr(se_map), _ptr(ssim_map), _stream(stream))
-    if rc != SVGF_OK:
-        raise SvgfError(f"svgf_quality_meter failed ({rc})")
+    _call(load_library(), "svgf_quality_meter", int(device), _ptr(state), _ptr(a), _ptr(b), int(width), int(height), C.byref(qp),
+          _ptr(exposure_state), _ptr(se_map), _ptr(ssim_map), _stream(stream))
 
 
 def quality_read(state, device: int = 0, stream=None) -> dict:
     """svgf_quality_read: waits for `stream` and returns the result block and mse / psnr_db / mean_ssim as a dict."""
     r = SvgfQualityResult()
-    rc = load_library().svgf_quality_read(int(device), _ptr(state), C.byref(r), _stream(stream))
-    if rc != SVGF_OK:
-        raise SvgfError(f"svgf_quality_read failed ({rc})")
+    _call(load_library(), "svgf_quality_read", int(device), _ptr(state), C.byref(r), _stream(stream))
     return {n: getattr(r, n) for n, _ in SvgfQualityResult._fields_}
 
 
 def save_png(path: str, rgb: np.ndarray, mirror_x: bool = True):
     """svgf_save_png: host float32 (H, W, 3) -> 8-bit RGB PNG, with the reference's x mirror by default."""
-    lib = load_library()
     rgb = np.ascontiguousarray(rgb, dtype=np.float32)
     h, w = rgb.shape[0], rgb.shape[1]
-    rc = lib.svgf_save_png(os.fsencode(path), rgb.ctypes.data, int(w), int(h), int(bool(mirror_x)))
-    if rc != SVGF_OK:
-        raise SvgfError(f"svgf_save_png failed ({rc})")
+    _call(load_library(), "svgf_save_png", os.fsencode(path), rgb.ctypes.data, int(w), int(h), int(bool(mirror_x)))
 
 
 # --- SURVEY.md 8(f) row f3: scene-driven producer -------------------------------------------------------------------
-def scene_render(out_rgb, out_gbuffer, width: int, height: int, camera, geoms: np.ndarray, frame: int, seed: int = 1,
-                 noise: float = 0.6, fireflies: float = 0.02, pixel_length=None, light=None, device: int = 0, stream=None):
-    """svgf_scene_render: `geoms` is a scene.SCENE_GEOM_DTYPE array (scene.geom_array(scene.parse_scene(text)))."""
-    from . import scene as _scene
-    from . import synth as _synth
-    lib = load_library()
-    cam = camera if isinstance(camera, SvgfCamera) else SvgfCamera.from_dict(camera)
-    if pixel_length is None:
-        fovy = camera.get("fovy_deg", 45.0) if isinstance(camera, dict) else 45.0
-        pixel_length = _synth._pixel_length(width, height, fovy)
-    sp = SvgfSynthParams(int(frame), int(seed), float(noise), float(fireflies))
-    sp.pixel_length[0] = float(pixel_length[0])
-    sp.pixel_length[1] = float(pixel_length[1])
-    geoms = np.ascontiguousarray(geoms, dtype=_scene.SCENE_GEOM_DTYPE)
-    lp = _scene.light_position(geoms) if light is None else np.asarray(light, dtype=np.float32)
-    larr = (C.c_float * 3)(float(lp[0]), float(lp[1]), float(lp[2]))
-    s = None if stream is None else (stream if isinstance(stream, int) else stream.cuda_stream)
-    rc = lib.svgf_scene_render(int(device), _ptr(out_rgb), _ptr(out_gbuffer), int(width), int(height), C.byref(cam), C.byref(sp),
-                               geoms.ctypes.data, int(len(geoms)), larr, s)
-    if rc != SVGF_OK:
-        raise SvgfError(f"svgf_scene_render failed ({rc})")
-
-
-def scene_render_mesh(out_rgb, out_gbuffer, width: int, height: int, camera, geoms: np.ndarray, geom_ids, tris, tri_ids, tri_albedo,
-                      frame: int, tri_tex=None, textures=None, seed: int = 1, noise: float = 0.6, fireflies: float = 0.02, pixel_length=None, light=None,
-                      device: int = 0, stream=None):
-    """svgf_scene_render_mesh: primitives (`geoms`, geomId = geom_ids[k]) + world-space triangles (`tris` float32[n,3,8] =
-    pos, normal, uv per corner; geomId = tri_ids[i]; albedo = tri_albedo[i]).  The library has read the host arrays completely
-    when it returns (it waits for its uploads); the kernel itself stays asynchronous on `stream`.
-    `out_gbuffer` may be a SvgfPlanarGBuffer (Denoiser.planar_gbuffer()): svgf_scene_render_mesh_planar writes the planes."""
-    from . import scene as _scene
-    from . import synth as _synth
-    lib = load_library()
-    cam = camera if isinstance(camera, SvgfCamera) else SvgfCamera.from_dict(camera)
-    if pixel_length is None:
-        fovy = camera.get("fovy_deg", 45.0) if isinstance(camera, dict) else 45.0
-        pixel_length = _synth._pixel_length(width, height, fovy)
-    sp = SvgfSynthParams(int(frame), int(seed), float(noise), float(fireflies))
-    sp.pixel_length[0] = float(pixel_length[0])
-    sp.pixel_length[1] = float(pixel_length[1])
-    geoms = np.ascontiguousarray(geoms, dtype=_scene.SCENE_GEOM_DTYPE)
-    gi = np.ascontiguousarray(geom_ids, dtype=np.int32)
-    tr = np.ascontiguousarray(tris, dtype=np.float32).reshape(-1, 24)
-    ti = np.ascontiguousarray(tri_ids, dtype=np.int32)
-    ta = np.ascontiguousarray(tri_albedo, dtype=np.float32).reshape(-1, 3)
-    # textures: list of uint8[h, w, 3]; tri_tex: index into that list per triangle, -1 = none
-    n_tex, tt, td, tx = 0, None, None, None
-    if textures is not None and len(textures) and tri_tex is not None:
-        n_tex = len(textures)
-        tt = np.ascontiguousarray(tri_tex, dtype=np.int32)
-        offs, blobs, o = [], [], 0
-        for t in textures:
-            t = np.ascontiguousarray(t, dtype=np.uint8)
-            offs += [o, t.shape[1], t.shape[0]]
-            blobs.append(t.reshape(-1))
-            o += t.size
-        td = np.array(offs, dtype=np.int32)
-        tx = np.concatenate(blobs)
-    lp = _scene.light_position(geoms) if light is None else np.asarray(light, dtype=np.float32)
-    larr = (C.c_float * 3)(float(lp[0]), float(lp[1]), float(lp[2]))
-    s = None if stream is None else (stream if isinstance(stream, int) else stream.cuda_stream)
-    planar = isinstance(out_gbuffer, SvgfPlanarGBuffer)
-    fn = lib.svgf_scene_render_mesh_planar if planar else lib.svgf_scene_render_mesh
-    rc = fn(int(device), _ptr(out_rgb), C.byref(out_gbuffer) if planar else _ptr(out_gbuffer), int(width), int(height), C.byref(cam), C.byref(sp),
-            geoms.ctypes.data if len(geoms) else None, int(len(geoms)), gi.ctypes.data if len(gi) else None,
-            tr.ctypes.data if len(tr) else None, ti.ctypes.data if len(ti) else None, ta.ctypes.data if len(ta) else None, int(len(tr)),
-            tt.ctypes.data if n_tex else None, td.ctypes.data if n_tex else None, tx.ctypes.data if n_tex else None, int(n_tex), larr, s)
-    if rc != SVGF_OK:
-        raise SvgfError(f"svgf_scene_render_mesh failed ({rc})")
-    if stream is None:
-        import torch
-        torch.cuda.synchronize(int(device))
-
-
-# --- row f14: resident scene (upload once, BVH over the triangles, one launch per frame) ------------------------------------------
 def _scene_arrays(geoms, geom_ids, tris, tri_ids, tri_albedo, tri_tex, textures):
     """The host arrays svgf_scene_render_mesh / svgf_scene_create take, as (arrays to keep alive, ctypes arguments)."""
     from . import scene as _scene
@@ -1196,6 +1057,41 @@ def _scene_arrays(geoms, geom_ids, tris, tri_ids, tri_albedo, tri_tex, textures)
     return (geoms, gi, tr, ti, ta, tt, td, tx), args
 
 
+def _light_of(geoms, light):
+    from . import scene as _scene
+    return _v3(_scene.light_position(geoms) if light is None else np.asarray(light, dtype=np.float32))
+
+
+def scene_render(out_rgb, out_gbuffer, width: int, height: int, camera, geoms: np.ndarray, frame: int, seed: int = 1,
+                 noise: float = 0.6, fireflies: float = 0.02, pixel_length=None, light=None, device: int = 0, stream=None):
+    """svgf_scene_render: `geoms` is a scene.SCENE_GEOM_DTYPE array (scene.geom_array(scene.parse_scene(text)))."""
+    from . import scene as _scene
+    cam, sp = _view(camera, width, height, frame, seed, noise, fireflies, pixel_length, camera_fovy=True)
+    geoms = np.ascontiguousarray(geoms, dtype=_scene.SCENE_GEOM_DTYPE)
+    _call(load_library(), "svgf_scene_render", int(device), _ptr(out_rgb), _ptr(out_gbuffer), int(width), int(height), C.byref(cam), C.byref(sp),
+          geoms.ctypes.data, int(len(geoms)), _light_of(geoms, light), _stream(stream))
+
+
+def scene_render_mesh(out_rgb, out_gbuffer, width: int, height: int, camera, geoms: np.ndarray, geom_ids, tris, tri_ids, tri_albedo,
+                      frame: int, tri_tex=None, textures=None, seed: int = 1, noise: float = 0.6, fireflies: float = 0.02, pixel_length=None, light=None,
+                      device: int = 0, stream=None):
+    """svgf_scene_render_mesh: primitives (`geoms`, geomId = geom_ids[k]) + world-space triangles (`tris` float32[n,3,8] =
+    pos, normal, uv per corner; geomId = tri_ids[i]; albedo = tri_albedo[i]).  The library has read the host arrays completely
+    when it returns (it waits for its uploads); the kernel itself stays asynchronous on `stream`.
+    `out_gbuffer` may be a SvgfPlanarGBuffer (Denoiser.planar_gbuffer()): svgf_scene_render_mesh_planar writes the planes."""
+    cam, sp = _view(camera, width, height, frame, seed, noise, fireflies, pixel_length, camera_fovy=True)
+    keep, args = _scene_arrays(geoms, geom_ids, tris, tri_ids, tri_albedo, tri_tex, textures)
+    planar, texels, planes = _draw_target(out_gbuffer)
+    rc = getattr(load_library(), "svgf_scene_render_mesh_planar" if planar else "svgf_scene_render_mesh")(
+        int(device), _ptr(out_rgb), planes if planar else texels, int(width), int(height), C.byref(cam), C.byref(sp), *args,
+        _light_of(keep[0], light), _stream(stream))
+    _check(rc, "svgf_scene_render_mesh")
+    if stream is None:
+        import torch
+        torch.cuda.synchronize(int(device))
+
+
+# --- row f14: resident scene (upload once, BVH over the triangles, one launch per frame) ------------------------------------------
 def bvh_build_host(tris, max_leaf_tris: int = 0, split: int = 0):
     """svgf_bvh_build_host (no device needed): (nodes BVH_NODE_DTYPE[n_nodes], order int32[n_tris], depth) of `tris`
     (float32[n, 3, 8] or [n, 24])."""
@@ -1204,10 +1100,8 @@ def bvh_build_host(tris, max_leaf_tris: int = 0, split: int = 0):
     nodes, order = np.zeros(2 * max(n, 1), BVH_NODE_DTYPE), np.zeros(max(n, 1), np.int32)
     n_nodes, depth = C.c_int(-1), C.c_int(-1)
     bp = SvgfSceneBuildParams(int(max_leaf_tris), int(split))
-    rc = load_library().svgf_bvh_build_host(tr.ctypes.data if n else None, n, C.byref(bp), nodes.ctypes.data, C.byref(n_nodes),
-                                            order.ctypes.data, C.byref(depth))
-    if rc != SVGF_OK:
-        raise SvgfError(f"svgf_bvh_build_host failed ({rc})")
+    _call(load_library(), "svgf_bvh_build_host", tr.ctypes.data if n else None, n, C.byref(bp), nodes.ctypes.data, C.byref(n_nodes),
+          order.ctypes.data, C.byref(depth))
     return nodes[:n_nodes.value].copy(), order[:n].copy(), depth.value
 
 
@@ -1215,10 +1109,7 @@ def pose_rigid(axis, angle_rad: float, pivot=(0.0, 0.0, 0.0), translate=(0.0, 0.
     """svgf_pose_rigid (host only): one SCENE_POSE_DTYPE record - the rotation by angle_rad about `axis` through `pivot`, then
     `translate`, and its analytic inverse."""
     out = np.zeros(1, SCENE_POSE_DTYPE)
-    v3 = lambda v: (C.c_float * 3)(*[float(x) for x in v])      # noqa: E731
-    rc = load_library().svgf_pose_rigid(v3(axis), float(angle_rad), v3(pivot), v3(translate), out.ctypes.data)
-    if rc != SVGF_OK:
-        raise SvgfError(f"svgf_pose_rigid failed ({rc})")
+    _call(load_library(), "svgf_pose_rigid", _v3(axis), float(angle_rad), _v3(pivot), _v3(translate), out.ctypes.data)
     return out[0]
 
 
@@ -1237,10 +1128,8 @@ def bvh_refit_plan_host(nodes, cap: int = SCENE_REFIT_CAP) -> dict:
     n = len(nd)
     treelets, level, top = np.zeros(max(n, 1), REFIT_TREELET_DTYPE), np.zeros(max(n, 1), np.uint8), np.zeros(max(n, 1), np.int32)
     seg, info = np.zeros(SCENE_MAX_DEPTH + 2, np.int32), np.zeros(4, np.int32)
-    rc = load_library().svgf_bvh_refit_plan_host(nd.ctypes.data if n else None, n, int(cap), treelets.ctypes.data, level.ctypes.data,
-                                                 top.ctypes.data, seg.ctypes.data, info.ctypes.data)
-    if rc != SVGF_OK:
-        raise SvgfError(f"svgf_bvh_refit_plan_host failed ({rc})")
+    _call(load_library(), "svgf_bvh_refit_plan_host", nd.ctypes.data if n else None, n, int(cap), treelets.ctypes.data, level.ctypes.data,
+          top.ctypes.data, seg.ctypes.data, info.ctypes.data)
     return dict(treelets=treelets[:info[0]].copy(), level=level[:n].copy(), top=top[:info[1]].copy(), top_seg=seg[:info[2] + 1].copy())
 
 
@@ -1258,36 +1147,26 @@ class Scene:
         _keep, args = _scene_arrays(geoms, geom_ids, tris, tri_ids, tri_albedo, tri_tex, textures)
         h = C.c_void_p()
         bp = SvgfSceneBuildParams(int(max_leaf_tris), int(split))
-        rc = load_library().svgf_scene_create(int(device), *args, C.byref(bp), C.byref(h))
-        if rc != SVGF_OK:
-            raise SvgfError(f"svgf_scene_create failed ({rc})")
+        _call(load_library(), "svgf_scene_create", int(device), *args, C.byref(bp), C.byref(h))
         return cls(h, device)
+
+    def _call(self, symbol, *args):
+        _call(self.lib, symbol, self.h, *args)
 
     def info(self) -> dict:
         i = SvgfSceneInfo()
-        rc = self.lib.svgf_scene_info(self.h, C.byref(i))
-        if rc != SVGF_OK:
-            raise SvgfError(f"svgf_scene_info failed ({rc})")
+        self._call("svgf_scene_info", C.byref(i))
         return {k: int(getattr(i, k)) for k, _ in SvgfSceneInfo._fields_}
 
     def draw(self, out_rgb, out_gbuffer, width: int, height: int, camera, light, frame: int, seed: int = 1, noise: float = 0.6,
              fireflies: float = 0.02, pixel_length=None, stream=None):
         """svgf_scene_draw, or svgf_scene_draw_planar when `out_gbuffer` is a SvgfPlanarGBuffer.  Asynchronous on `stream` (a torch
         stream, a raw handle or None = the default stream); never waits."""
-        from . import synth as _synth
-        cam = camera if isinstance(camera, SvgfCamera) else SvgfCamera.from_dict(camera)
-        if pixel_length is None:
-            fovy = camera.get("fovy_deg", 45.0) if isinstance(camera, dict) else 45.0
-            pixel_length = _synth._pixel_length(width, height, fovy)
-        sp = SvgfSynthParams(int(frame), int(seed), float(noise), float(fireflies))
-        sp.pixel_length[0], sp.pixel_length[1] = float(pixel_length[0]), float(pixel_length[1])
-        larr = (C.c_float * 3)(float(light[0]), float(light[1]), float(light[2]))
-        planar = isinstance(out_gbuffer, SvgfPlanarGBuffer)
+        cam, sp = _view(camera, width, height, frame, seed, noise, fireflies, pixel_length, camera_fovy=True)
+        planar, texels, planes = _draw_target(out_gbuffer)
         fn = self.lib.svgf_scene_draw_planar if planar else self.lib.svgf_scene_draw
-        rc = fn(self.h, _ptr(out_rgb), C.byref(out_gbuffer) if planar else _ptr(out_gbuffer), int(width), int(height), C.byref(cam),
-                C.byref(sp), larr, _stream(stream))
-        if rc != SVGF_OK:
-            raise SvgfError(f"svgf_scene_draw failed ({rc})")
+        _check(fn(self.h, _ptr(out_rgb), planes if planar else texels, int(width), int(height), C.byref(cam), C.byref(sp), _v3(light),
+                  _stream(stream)), "svgf_scene_draw")      # one name for both in the message
 
     draw_planar = draw
 
@@ -1295,18 +1174,9 @@ class Scene:
                       fireflies: float = 0.02, pixel_length=None, stream=None):
         """svgf_scene_draw_shadowed (row f16): `light` is a SvgfSceneLight (SvgfSceneLight.make(centre, edge_u, edge_v, samples));
         `out_gbuffer` AoS texels or a SvgfPlanarGBuffer.  One launch on `stream`; never waits."""
-        from . import synth as _synth
-        cam = camera if isinstance(camera, SvgfCamera) else SvgfCamera.from_dict(camera)
-        if pixel_length is None:
-            fovy = camera.get("fovy_deg", 45.0) if isinstance(camera, dict) else 45.0
-            pixel_length = _synth._pixel_length(width, height, fovy)
-        sp = SvgfSynthParams(int(frame), int(seed), float(noise), float(fireflies))
-        sp.pixel_length[0], sp.pixel_length[1] = float(pixel_length[0]), float(pixel_length[1])
-        planar = isinstance(out_gbuffer, SvgfPlanarGBuffer)
-        rc = self.lib.svgf_scene_draw_shadowed(self.h, _ptr(out_rgb), None if planar else _ptr(out_gbuffer), C.byref(out_gbuffer) if planar else None,
-                                               int(width), int(height), C.byref(cam), C.byref(sp), C.byref(light), _stream(stream))
-        if rc != SVGF_OK:
-            raise SvgfError(f"svgf_scene_draw_shadowed failed ({rc})")
+        cam, sp = _view(camera, width, height, frame, seed, noise, fireflies, pixel_length, camera_fovy=True)
+        self._call("svgf_scene_draw_shadowed", _ptr(out_rgb), *_draw_target(out_gbuffer)[1:], int(width), int(height), C.byref(cam), C.byref(sp),
+                   C.byref(light), _stream(stream))
 
     def _companion_draw(self, name, out, out_gbuffer, width, height, camera, light, frame, params, synth, stream, table=None, guide=None,
                         lobe=None, shine=None):
@@ -1314,20 +1184,12 @@ class Scene:
         out_indirect, out_rgb); `params` the values of the library's parameter block, `synth` (seed, noise, fireflies, pixel_length);
         the libraries that take them read `table` (a GlossTable or None), `guide` (max_chain, id_offset, out_chain), `lobe` (a RoughTable
         or None, guide_alpha) and `shine` (enable, clamp).  `out_gbuffer` is AoS texels or a SvgfPlanarGBuffer."""
-        from . import synth as _synth
         parts = _DRAW_PARTS["trace" if name == "split" else name]
         symbol = ("svgf_trace_draw" if name == "split" else f"svgf_{name}_draw") + "_split" * (len(out) == 3)
-        cam = camera if isinstance(camera, SvgfCamera) else SvgfCamera.from_dict(camera)
-        seed, noise, fireflies, pixel_length = synth
-        if pixel_length is None:
-            fovy = camera.get("fovy_deg", 45.0) if isinstance(camera, dict) else 45.0
-            pixel_length = _synth._pixel_length(width, height, fovy)
-        sp = SvgfSynthParams(int(frame), int(seed), float(noise), float(fireflies))
-        sp.pixel_length[0], sp.pixel_length[1] = float(pixel_length[0]), float(pixel_length[1])
-        planar = isinstance(out_gbuffer, SvgfPlanarGBuffer)
+        cam, sp = _view(camera, width, height, frame, *synth, camera_fovy=True)
         args = [self.h] + ([table.h if table is not None else None] if parts.get("table") else []) + [_ptr(o) for o in out]
-        args += [None if planar else _ptr(out_gbuffer), C.byref(out_gbuffer) if planar else None, int(width), int(height), C.byref(cam),
-                 C.byref(sp), C.byref(light), C.byref(_filled(parts["params"], params))]
+        args += [*_draw_target(out_gbuffer)[1:], int(width), int(height), C.byref(cam), C.byref(sp), C.byref(light),
+                 C.byref(_filled(parts["params"], params))]
         if parts.get("virtual"):
             args += [C.byref(_filled(SvgfVirtualParams, guide[:2])), _ptr(guide[2])]
         args.append(_stream(stream))
@@ -1335,9 +1197,7 @@ class Scene:
             args += [lobe[0].h if lobe[0] is not None else None, C.byref(_filled(SvgfRoughParams, lobe[1:]))]
         if parts.get("highlight"):
             args.append(C.byref(_filled(SvgfHighlightParams, shine)))
-        rc = getattr(_load_companion(name), symbol)(*args)
-        if rc != SVGF_OK:
-            raise SvgfError(f"{symbol} failed ({rc})")
+        _call(_load_companion(name), symbol, *args)
 
     def draw_traced(self, out_rgb, out_gbuffer, width: int, height: int, camera, light, frame: int, bounce_samples: int = 1,
                     ambient: float = 0.15, shadow_secondary: int = 1, seed: int = 1, noise: float = 0.6, fireflies: float = 0.02,
@@ -1453,32 +1313,24 @@ class Scene:
     def adopt_tree(self, nodes=None, order=None, n_nodes: int = 0, n_leaves: int = 0, depth_bound: int = 0):
         """svgf_scene_adopt_tree (row f24; host only): from now on every draw walks the DEVICE arrays `nodes` / `order` (torch tensors
         or raw pointers) in place of the scene's own tree; nodes=None detaches.  SceneTree.attach() does this with a tree it built."""
-        rc = self.lib.svgf_scene_adopt_tree(self.h, _ptr(nodes), _ptr(order), int(n_nodes), int(n_leaves), int(depth_bound))
-        if rc != SVGF_OK:
-            raise SvgfError(f"svgf_scene_adopt_tree failed ({rc})")
+        self._call("svgf_scene_adopt_tree", _ptr(nodes), _ptr(order), int(n_nodes), int(n_leaves), int(depth_bound))
 
     def view(self) -> dict:
         """svgf_scene_view (host only): the device index, the counts and the device pointers the draws read, as integers (0 = NULL)."""
         v = SvgfSceneView()
-        rc = self.lib.svgf_scene_view(self.h, C.byref(v))
-        if rc != SVGF_OK:
-            raise SvgfError(f"svgf_scene_view failed ({rc})")
+        self._call("svgf_scene_view", C.byref(v))
         return {k: int(getattr(v, k) or 0) for k, _ in SvgfSceneView._fields_}
 
     def enable_pose(self, n_objects: int):
         """svgf_scene_enable_pose: allocates the animation side (allocates and synchronises; not under capture)."""
-        rc = self.lib.svgf_scene_enable_pose(self.h, int(n_objects))
-        if rc != SVGF_OK:
-            raise SvgfError(f"svgf_scene_enable_pose failed ({rc})")
+        self._call("svgf_scene_enable_pose", int(n_objects))
         self.n_objects = int(n_objects)
 
     def pose(self, table, motion_out=None, stream=None):
         """svgf_scene_pose: `table` is DEVICE memory of n_objects SCENE_POSE_DTYPE records (a torch tensor of 24 * n_objects float32
         or a raw pointer), read when the kernels run; `motion_out` device memory of 12 * n_objects float32 or None.  Asynchronous on
         `stream`; never waits."""
-        rc = self.lib.svgf_scene_pose(self.h, _ptr(table), int(getattr(self, "n_objects", 0)), _ptr(motion_out), _stream(stream))
-        if rc != SVGF_OK:
-            raise SvgfError(f"svgf_scene_pose failed ({rc})")
+        self._call("svgf_scene_pose", _ptr(table), int(getattr(self, "n_objects", 0)), _ptr(motion_out), _stream(stream))
 
     def read(self, which: int) -> np.ndarray:
         """svgf_scene_read (blocking): 0 float32[n_tris, 3, 8], 1 / 2 BVH_NODE_DTYPE, 3 scene.SCENE_GEOM_DTYPE, 4 int32, 5 SCENE_POSE_DTYPE."""
@@ -1488,9 +1340,7 @@ class Scene:
                  3: (i["n_geoms"], _scene.SCENE_GEOM_DTYPE), 4: (i["n_tris"], np.int32),
                  5: (getattr(self, "n_objects", 0), SCENE_POSE_DTYPE)}[int(which)]
         out = np.zeros(n, dt)
-        rc = self.lib.svgf_scene_read(self.h, int(which), out.ctypes.data if n else None, out.nbytes)
-        if rc != SVGF_OK:
-            raise SvgfError(f"svgf_scene_read failed ({rc})")
+        self._call("svgf_scene_read", int(which), out.ctypes.data if n else None, out.nbytes)
         return out.reshape(-1, 3, 8) if int(which) == 0 else out
 
     def free(self):
@@ -1510,15 +1360,11 @@ class SceneTree:
     @classmethod
     def create(cls, scene, leaf_tris: int = 0):
         h, p = C.c_void_p(), SvgfLbvhParams(int(leaf_tris))
-        rc = load_lbvh_library().svgf_lbvh_create(scene.h, C.byref(p), C.byref(h))
-        if rc != SVGF_OK:
-            raise SvgfError(f"svgf_lbvh_create failed ({rc})")
+        _call(load_lbvh_library(), "svgf_lbvh_create", scene.h, C.byref(p), C.byref(h))
         return cls(h, scene)
 
-    def _call(self, name, *args):
-        rc = getattr(self.lib, name)(self.h, *args)
-        if rc != SVGF_OK:
-            raise SvgfError(f"{name} failed ({rc})")
+    def _call(self, symbol, *args):
+        _call(self.lib, symbol, self.h, *args)
 
     def build(self, stream=None):
         """svgf_lbvh_build: asynchronous on `stream`; never waits."""
