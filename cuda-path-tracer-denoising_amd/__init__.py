@@ -5,11 +5,12 @@ Directory layout:
   binding.py           ctypes binding + `Denoiser`, the host-side mirror of denoiseInit/denoise/denoiseFree
   farm.py              sequence sharding + timing reduction for the 1/2/4/8-GPU runs (no collectives on the data path)
   synth.py             seeded synthetic 1-spp colour + G-buffer frames (test / bench inputs)
+  sah.py               ctypes binding of libsvgf_sah.so (row f25): `SahTree`, the device SAH build of a resident scene's tree
   build.py             hipcc / gcc recipes used by __graft_entry__.build()
 The directory name contains '-', so it is loaded through `__graft_entry__.load_package()` under the module
 name `cuda_path_tracer_denoising_amd`.
 """
-from . import binding, build, farm, scene, synth  # noqa: F401
+from . import binding, build, farm, sah, scene, synth  # noqa: F401
 from .binding import Denoiser, SvgfCamera, SvgfParams, SvgfError, load_library, reference_defaults  # noqa: F401
 from .binding import SvgfGuide, SvgfUpsampleParams, upsample  # noqa: F401
 from .binding import SvgfExposureParams, SvgfTonemapParams, exposure_state, exposure_reset, exposure_meter, display_tonemap, srgb_table  # noqa: F401
@@ -25,4 +26,5 @@ from .binding import SvgfVirtualParams, load_virtual_library  # noqa: F401  (Sce
 from .binding import RoughTable, SvgfRoughParams, load_rough_library  # noqa: F401  (Scene.draw_rough, Scene.draw_rough_split)
 from .binding import SvgfHighlightParams, load_highlight_library  # noqa: F401  (Scene.draw_highlight, Scene.draw_highlight_split)
 from .binding import SceneTree, SvgfLbvhParams, SvgfLbvhInfo, load_lbvh_library, lbvh_build_host  # noqa: F401  (row f24, Scene.adopt_tree)
+from .sah import SahTree, SvgfSahParams, SvgfSahInfo, SAH_EXPORTS, load_sah_library  # noqa: F401  (row f25)
 from .binding import STATE_PREV_NORMAL, STATE_PREV_POSITION, STATE_PREV_GEOM_ID, STATE_OUTPUT_HISTORY  # noqa: F401

@@ -42,6 +42,11 @@ Builder = collections.namedtuple("Builder", "name sources headers flags")
 BUILDERS = (
     Builder("lbvh", ["svgf_lbvh.hip", "svgf_lbvh_host.cpp"], ["svgf_lbvh.h"], ["-ffp-contract=off"]),                  # f24: LBVH on the device
 )
+# Tree builders added after BUILDERS was pinned to row f24's: the same row type, the same recipe.  Row f25 restates svgf_bvh_build_host's
+# float32 / double arithmetic on the device, one rounding per operation: -ffp-contract=off.
+TREE_BUILDERS = (
+    Builder("sah", ["svgf_sah.hip"], ["svgf_sah.h"], ["-ffp-contract=off"]),                                           # f25: binned SAH on the device
+)
 
 
 def companion_path(name: str) -> str:
@@ -121,11 +126,11 @@ def build_hip(force: bool = False, experiments: bool = False) -> str:
 
 
 def build_companion(name: str, force: bool = False) -> str:
-    """Compile the sources of COMPANIONS' (or BUILDERS') row `name` for gfx950 into cuda-path-tracer-denoising_amd/libsvgf_<name>.so, linked against
+    """Compile the sources of COMPANIONS' (or BUILDERS' / TREE_BUILDERS') row `name` for gfx950 into cuda-path-tracer-denoising_amd/libsvgf_<name>.so, linked against
     the product library beside it and against no other companion (the examples' rpath scheme: the build directory, then $ORIGIN, so the
     pair can be moved together)."""
     build_hip()
-    c = next(c for c in COMPANIONS + BUILDERS if c.name == name)
+    c = next(c for c in COMPANIONS + BUILDERS + TREE_BUILDERS if c.name == name)
     lib = companion_path(name)
     srcs = [os.path.join(CSRC, s) for s in c.sources]
     deps = srcs + [os.path.join(CSRC, h) for h in sorted(os.listdir(CSRC)) if h.endswith(".h")] + \
@@ -169,6 +174,11 @@ def build_highlight(force: bool = False) -> str:
 def build_lbvh(force: bool = False) -> str:
     """libsvgf_lbvh.so (row f24, include/svgf_lbvh.h): BUILDERS' row through the companions' recipe."""
     return build_companion("lbvh", force)
+
+
+def build_sah(force: bool = False) -> str:
+    """libsvgf_sah.so (row f25, include/svgf_sah.h): TREE_BUILDERS' row through the companions' recipe."""
+    return build_companion("sah", force)
 
 
 def build_all(force: bool = False) -> list[str]:
