@@ -6,11 +6,12 @@ Directory layout:
   farm.py              sequence sharding + timing reduction for the 1/2/4/8-GPU runs (no collectives on the data path)
   synth.py             seeded synthetic 1-spp colour + G-buffer frames (test / bench inputs)
   sah.py               ctypes binding of libsvgf_sah.so (row f25): `SahTree`, the device SAH build of a resident scene's tree
+  deform.py            ctypes binding of libsvgf_deform.so (row f26): `DeformRig`, skinned triangles; scene_refit / drawn_arrays of the product
   build.py             hipcc / gcc recipes used by __graft_entry__.build()
 The directory name contains '-', so it is loaded through `__graft_entry__.load_package()` under the module
 name `cuda_path_tracer_denoising_amd`.
 """
-from . import binding, build, farm, sah, scene, synth  # noqa: F401
+from . import binding, build, deform, farm, sah, scene, synth  # noqa: F401
 from .binding import Denoiser, SvgfCamera, SvgfParams, SvgfError, load_library, reference_defaults  # noqa: F401
 from .binding import SvgfGuide, SvgfUpsampleParams, upsample  # noqa: F401
 from .binding import SvgfExposureParams, SvgfTonemapParams, exposure_state, exposure_reset, exposure_meter, display_tonemap, srgb_table  # noqa: F401
@@ -27,4 +28,5 @@ from .binding import RoughTable, SvgfRoughParams, load_rough_library  # noqa: F4
 from .binding import SvgfHighlightParams, load_highlight_library  # noqa: F401  (Scene.draw_highlight, Scene.draw_highlight_split)
 from .binding import SceneTree, SvgfLbvhParams, SvgfLbvhInfo, load_lbvh_library, lbvh_build_host  # noqa: F401  (row f24, Scene.adopt_tree)
 from .sah import SahTree, SvgfSahParams, SvgfSahInfo, SAH_EXPORTS, load_sah_library  # noqa: F401  (row f25)
+from .deform import DeformRig, SvgfDeformInfo, DEFORM_EXPORTS, SCENE_WRITE_EXPORTS, load_deform_library, scene_refit, drawn_arrays  # noqa: F401  (row f26)
 from .binding import STATE_PREV_NORMAL, STATE_PREV_POSITION, STATE_PREV_GEOM_ID, STATE_OUTPUT_HISTORY  # noqa: F401

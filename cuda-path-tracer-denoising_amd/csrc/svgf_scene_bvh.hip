@@ -13,6 +13,7 @@
 // level above its current node.  Row f17's companion library (svgf_scene_trace.hip) compiles the same walks.
 #include "svgf_kernels.h"
 #include "../../include/svgf.h"
+#include "../../include/svgf_scene_write.h"
 
 #include <hip/hip_runtime.h>
 
@@ -597,4 +598,25 @@ extern "C" int svgf_scene_adopt_tree(svgf_scene *scene, const SvgfBvhNode *nodes
     scene->ad_nodes = reinterpret_cast<const float4 *>(nodes_dev); scene->ad_order = order_dev;
     scene->ad_n_nodes = n_nodes; scene->ad_n_leaves = n_leaves; scene->ad_depth = depth_bound;
     return SVGF_OK;
+}
+
+// row f26: the posed copies, writable, for renderer-side code that deforms them (libsvgf_deform.so); host only
+extern "C" int svgf_scene_drawn_arrays(svgf_scene *scene, float **tris_dev, SvgfBvhNode **tri_boxes_dev)
+{
+    if (!scene || !tris_dev || !tri_boxes_dev || !scene->anim) return SVGF_ERR_INVALID_ARG;
+    *tris_dev = reinterpret_cast<float *>(scene->pose.tris);
+    *tri_boxes_dev = reinterpret_cast<SvgfBvhNode *>(scene->pose.tri_boxes);
+    return SVGF_OK;
+}
+
+// row f26: svgf_scene_pose's two refit launches on the scene's own nodes, from the boxes as drawn, and nothing else
+extern "C" int svgf_scene_refit(svgf_scene *scene, void *stream)
+{
+    if (!scene || !scene->anim) return SVGF_ERR_INVALID_ARG;
+    SvgfDeviceGuard dev_guard(scene->device);
+    if (!dev_guard.ok) return SVGF_ERR_NO_DEVICE;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (scene->n_treelets > 0) hipLaunchKernelGGL(k_scene_refit_treelets, dim3(scene->n_treelets), dim3(256), 0, st, scene->refit);
+    if (scene->n_top > 0) hipLaunchKernelGGL(k_scene_refit_top, dim3(1), dim3(256), 0, st, scene->refit);
+    return hipGetLastError() == hipSuccess ? SVGF_OK : SVGF_ERR_HIP;
 }

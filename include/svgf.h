@@ -824,7 +824,8 @@ int svgf_bvh_build_host(const float *tris, int n_tris, const SvgfSceneBuildParam
  * host wait, legal under stream capture.  Nothing of row f14's contract moves: the frame is the gated brute force over the POSED
  * triangles, which every tree reproduces, so a refitted tree draws the frame a tree rebuilt at that pose would.
  * What stays static: the topology (nodes' first / count, the triangle order - the tree is refitted, never re-split, however loose its
- * boxes become; row f24 below lets a scene adopt a tree rebuilt elsewhere), the textures, and the set of objects.
+ * boxes become; row f24 below lets a scene adopt a tree rebuilt elsewhere), the textures, and the set of objects.  Row f26 below
+ * lets renderer-side code move vertices independently of each other (include/svgf_deform.h).
  * svgf_scene_enable_pose(scene, n_objects): allocates the animation side once - posed copies of the triangles, triangle boxes, nodes
  *   and primitives, the HELD pose table (identity) and the refit plan.  The arrays svgf_scene_create uploaded become the REST state
  *   and are never written again; the posed copies start as bit copies of them and the draws read them from now on.  Allocates and
@@ -965,6 +966,28 @@ int svgf_scene_view(const svgf_scene *scene, SvgfSceneView *out);
  * A scene that never adopts a tree is row f23's on every byte. */
 int svgf_scene_adopt_tree(svgf_scene *scene, const SvgfBvhNode *nodes_dev, const int *order_dev, int n_nodes, int n_leaves,
                           int depth_bound);
+
+/* ---- "next" row f26: write the triangles as drawn, refit on request (added after 0.9; probe the symbol) ----
+ * Rows f15 and f24 let svgf_scene_pose alone change the triangles as drawn: one rigid map per object.  These two host-side entry
+ * points let renderer-side code move vertices independently of each other - libsvgf_deform.so (include/svgf_deform.h) skins triangles
+ * with them - while the frame stays row f14's gated brute force over the triangles as they stand.
+ * svgf_scene_drawn_arrays(scene, tris_dev, tri_boxes_dev): WRITABLE device pointers to the posed copies, 96 bytes per triangle and 32
+ *   bytes per padded box (SvgfBvhNode: first = i, count = 1) - the arrays the draws and svgf_scene_view read.  Host only: no device
+ *   work, no allocation, no synchronisation; the pointers hold until svgf_scene_destroy.  SVGF_ERR_INVALID_ARG, nothing written: a
+ *   NULL argument; a scene without svgf_scene_enable_pose - its arrays are the REST state and are never written.
+ *   A WRITER OWES THE SCENE row f14's padded box for every triangle it writes, computed by that one formula (the literals and nesting
+ *   of svgf_bvh_tri_box), in stream order ahead of the tree and the draw; uv, albedo, texture index and id are not the writer's.
+ *   svgf_scene_pose rewrites every triangle and box from the rest state: a writer runs behind it, on triangles whose id stands
+ *   outside the pose table.
+ * svgf_scene_refit(scene, stream): exactly the two refit launches of svgf_scene_pose (treelets, then the top) on the scene's OWN nodes,
+ *   from the padded boxes as drawn, and nothing else - no pose, no motion table, held untouched.  No allocation, no host wait; legal
+ *   under stream capture.  Allowed while a tree is adopted: the adopted tree is not touched, and the scene's own tree is valid again
+ *   after a detach.  The topology stays what svgf_scene_create built: a refitted tree is exact and as loose as the deformation makes
+ *   it; re-splitting is rows f24 and f25.  SVGF_ERR_INVALID_ARG for a NULL scene or one without svgf_scene_enable_pose.
+ * A scene that never calls either is row f25's on every byte; no kernel changed.
+ * THE TWO PROTOTYPES stand in include/svgf_scene_write.h, which includes this header: the functions this header declares are the set
+ * the Python binding's EXPORTS table is pinned to (tests/test_abi.py, tests/test_binding_surface.py), and these two are bound by
+ * deform.py beside the library that uses them. */
 
 #ifdef __cplusplus
 }
