@@ -8,11 +8,12 @@ Directory layout:
   sah.py               ctypes binding of libsvgf_sah.so (row f25): `SahTree`, the device SAH build of a resident scene's tree
   deform.py            ctypes binding of libsvgf_deform.so (row f26): `DeformRig`, skinned triangles; scene_refit / drawn_arrays of the product
   restir.py            ctypes binding of libsvgf_restir.so (row f27): `LightTable`, `Restir`, many-light direct lighting by reservoir resampling
+  restir_gi.py         ctypes binding of libsvgf_restir_gi.so (row f28): `RestirGI`, the one-bounce indirect term by reservoir resampling
   build.py             hipcc / gcc recipes used by __graft_entry__.build()
 The directory name contains '-', so it is loaded through `__graft_entry__.load_package()` under the module
 name `cuda_path_tracer_denoising_amd`.
 """
-from . import binding, build, deform, farm, restir, sah, scene, synth  # noqa: F401
+from . import binding, build, deform, farm, restir, restir_gi, sah, scene, synth  # noqa: F401
 from .binding import Denoiser, SvgfCamera, SvgfParams, SvgfError, load_library, reference_defaults  # noqa: F401
 from .binding import SvgfGuide, SvgfUpsampleParams, upsample  # noqa: F401
 from .binding import SvgfExposureParams, SvgfTonemapParams, exposure_state, exposure_reset, exposure_meter, display_tonemap, srgb_table  # noqa: F401
@@ -31,4 +32,5 @@ from .binding import SceneTree, SvgfLbvhParams, SvgfLbvhInfo, load_lbvh_library,
 from .sah import SahTree, SvgfSahParams, SvgfSahInfo, SAH_EXPORTS, load_sah_library  # noqa: F401  (row f25)
 from .deform import DeformRig, SvgfDeformInfo, DEFORM_EXPORTS, SCENE_WRITE_EXPORTS, load_deform_library, scene_refit, drawn_arrays  # noqa: F401  (row f26)
 from .restir import LightTable, Restir, SvgfLight, SvgfRestirParams, SvgfRestirInfo, RESTIR_EXPORTS, load_restir_library  # noqa: F401  (row f27)
+from .restir_gi import RestirGI, SvgfRestirGIParams, SvgfRestirGIInfo, RESTIR_GI_EXPORTS, RESERVOIR_GI_DTYPE, gi_params, load_restir_gi_library  # noqa: F401  (row f28)
 from .binding import STATE_PREV_NORMAL, STATE_PREV_POSITION, STATE_PREV_GEOM_ID, STATE_OUTPUT_HISTORY  # noqa: F401

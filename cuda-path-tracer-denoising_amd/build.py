@@ -57,6 +57,11 @@ SCENE_WRITERS = (
 LIGHT_SAMPLERS = (
     Builder("restir", ["svgf_restir.hip"], ["svgf_restir.h"], ["-ffp-contract=off"]),                                  # f27: ReSTIR DI
 )
+# Libraries that resample the paths behind a G-buffer of the resident scene, added after LIGHT_SAMPLERS was pinned to row f27's: the same
+# row type, the same recipe.  Row f28 states its reservoirs as float32 arithmetic with one rounding per operation: -ffp-contract=off.
+PATH_RESAMPLERS = (
+    Builder("restir_gi", ["svgf_restir_gi.hip"], ["svgf_restir_gi.h", "svgf_trace.h"], ["-ffp-contract=off"]),         # f28: ReSTIR GI
+)
 
 
 def companion_path(name: str) -> str:
@@ -65,13 +70,14 @@ def companion_path(name: str) -> str:
 
 LIB_TRACE, LIB_SPLIT, LIB_PATH, LIB_GLOSS, LIB_VIRTUAL, LIB_ROUGH, LIB_HIGHLIGHT = (companion_path(c.name) for c in COMPANIONS)
 TRACE_SOURCES, SPLIT_SOURCES, PATH_SOURCES, GLOSS_SOURCES, VIRTUAL_SOURCES, ROUGH_SOURCES, HIGHLIGHT_SOURCES = (c.sources for c in COMPANIONS)
-# examples/<name>.cpp -> the companions it links, in link order (every example links the product library behind them).  Row f26's and row f27's
+# examples/<name>.cpp -> the companions it links, in link order (every example links the product library behind them).  Row f26's, row f27's and row f28's
 # stand in directories of their own: the list of examples/*.cpp is pinned (tests/golden/companion_abi.json).
 EXAMPLES = {"pipeline": (), "farm": (), "cadence": (), "upsample": (), "dynres": (), "hdr_display": (), "quality": (), "resident_scene": (),
             "animated_scene": (), "shadowed_scene": (), "traced_scene": ("trace",), "split_scene": ("split", "trace"),
             "path_scene": ("path", "split"), "gloss_scene": ("gloss", "split"), "virtual_scene": ("virtual", "gloss", "split"),
             "rough_scene": ("rough", "gloss", "split"), "highlight_scene": ("highlight", "rough", "gloss", "split"),
-            "deform/deform_scene": ("deform", "sah"), "restir/restir_scene": ("restir", "split")}
+            "deform/deform_scene": ("deform", "sah"), "restir/restir_scene": ("restir", "split"),
+            "restir_gi/restir_gi_scene": ("restir_gi", "restir", "split")}
 HIP_SOURCES_EXPERIMENTS = ["svgf_experiments.hip", "svgf_atrous_lane_reuse.hip", "svgf_atrous_fused.hip"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unused-function"]
 # Per-file flags.  svgf_atrous_fused.hip: SimplifyCFG's common-code sinking merges the last store of the "bilinear history" branch
@@ -138,11 +144,11 @@ def build_hip(force: bool = False, experiments: bool = False) -> str:
 
 
 def build_companion(name: str, force: bool = False) -> str:
-    """Compile the sources of COMPANIONS' (or BUILDERS' / TREE_BUILDERS' / SCENE_WRITERS' / LIGHT_SAMPLERS') row `name` for gfx950 into cuda-path-tracer-denoising_amd/libsvgf_<name>.so, linked against
+    """Compile the sources of COMPANIONS' (or BUILDERS' / TREE_BUILDERS' / SCENE_WRITERS' / LIGHT_SAMPLERS' / PATH_RESAMPLERS') row `name` for gfx950 into cuda-path-tracer-denoising_amd/libsvgf_<name>.so, linked against
     the product library beside it and against no other companion (the examples' rpath scheme: the build directory, then $ORIGIN, so the
     pair can be moved together)."""
     build_hip()
-    c = next(c for c in COMPANIONS + BUILDERS + TREE_BUILDERS + SCENE_WRITERS + LIGHT_SAMPLERS if c.name == name)
+    c = next(c for c in COMPANIONS + BUILDERS + TREE_BUILDERS + SCENE_WRITERS + LIGHT_SAMPLERS + PATH_RESAMPLERS if c.name == name)
     lib = companion_path(name)
     srcs = [os.path.join(CSRC, s) for s in c.sources]
     deps = srcs + [os.path.join(CSRC, h) for h in sorted(os.listdir(CSRC)) if h.endswith(".h")] + \
@@ -203,6 +209,11 @@ def build_restir(force: bool = False) -> str:
     return build_companion("restir", force)
 
 
+def build_restir_gi(force: bool = False) -> str:
+    """libsvgf_restir_gi.so (row f28, include/svgf_restir_gi.h): PATH_RESAMPLERS' row through the companions' recipe."""
+    return build_companion("restir_gi", force)
+
+
 def build_all(force: bool = False) -> list[str]:
     """The product library and the seven companion libraries, in the order they were added."""
     return [build_hip(force)] + [build_companion(c.name, force) for c in COMPANIONS]
@@ -213,7 +224,7 @@ def build_examples(force: bool = False) -> str:
     names and the product library (each example's header comment says what it shows).  Returns the last one's path."""
     for c in COMPANIONS:
         build_companion(c.name)
-    rows = COMPANIONS + BUILDERS + TREE_BUILDERS + SCENE_WRITERS + LIGHT_SAMPLERS
+    rows = COMPANIONS + BUILDERS + TREE_BUILDERS + SCENE_WRITERS + LIGHT_SAMPLERS + PATH_RESAMPLERS
     for name in sorted({n for links in EXAMPLES.values() for n in links} - {c.name for c in COMPANIONS}):
         build_companion(name)
     out = ""
