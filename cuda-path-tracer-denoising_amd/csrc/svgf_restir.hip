@@ -10,6 +10,8 @@
 // the product's own text, on its per-lane stack in LDS (48 KB per block).  A thread writes only its own pixel's records: launch 1
 // reads H and the previous planes and writes T, launch 2 reads T and writes H and the previous planes, so no thread reads what
 // another writes in the same launch, nothing passes between workgroups and there are no atomics.  Reservoirs move as two 16-byte words.
+// What the pass is apart from its payload - the tile's pixel, the G-buffer reads, the history tap's address, update()'s sums, the state
+// behind the handle with its create / read / info / destroy, scene_args - is svgf_reservoir.inc.h, shared with svgf_restir_gi.hip.
 // float32, contraction off (build.LIGHT_SAMPLERS' row adds -ffp-contract=off; the pragmas say it again where the arithmetic is normative).
 #include "svgf_kernels.h"
 #include "svgf_temporal.h"      // svgf_lum_strict
@@ -34,6 +36,8 @@ namespace {
 #include "svgf_scene_pixel.inc.h"
 
 #include "svgf_scene_walk.inc.h"
+
+#include "svgf_reservoir.inc.h"
 
 struct RestirArgs {
     SceneBvhArgs b;             // the scene's arrays, width, height, seed, frame; nothing else of SceneArgs is read
@@ -99,12 +103,7 @@ __device__ __forceinline__ float light_phat(const RestirArgs &a, int j, const fl
 
 __device__ __forceinline__ void reservoir_update(Reservoir &r, int j, float u, float v, float phat, float w, float M_s, float xi)
 {
-#pragma clang fp contract(off)
-    w = w > 0.0f ? w : 0.0f;
-    const float before = r.w_sum;
-    r.w_sum = r.w_sum + w;
-    r.M = r.M + M_s;
-    if (w > 0.0f && (before == 0.0f || xi * r.w_sum < w)) { r.j = j; r.u = u; r.v = v; r.phat = phat; }
+    if (reservoir_add(r.w_sum, r.M, w, M_s, xi)) { r.j = j; r.u = u; r.v = v; r.phat = phat; }
 }
 
 __device__ __forceinline__ void reservoir_finish(Reservoir &r)
@@ -147,39 +146,6 @@ __device__ __forceinline__ bool light_occluded(const SceneBvhArgs &b, const Ligh
     return occluded;
 }
 
-// the pixel of this thread on the 64 x 4 tile, or -1 outside the frame
-__device__ __forceinline__ int tile_pixel(const SceneArgs &a, int &x, int &y)
-{
-    x = 64 * (int)blockIdx.x + ((int)threadIdx.x & 63);
-    y = 4 * (int)blockIdx.y + ((int)threadIdx.x >> 6);
-    return (x < a.W && y < a.H) ? y * a.W + x : -1;
-}
-
-__device__ __forceinline__ int read_surface(const RestirArgs &a, int p, float n[3], float pos[3])
-{
-    if (a.gbuf) {
-        const float *g = a.gbuf + 13 * (size_t)p;
-        for (int c = 0; c < 3; c++) { n[c] = g[c]; pos[c] = g[3 + c]; }
-        return reinterpret_cast<const int *>(g)[12];
-    }
-    for (int c = 0; c < 3; c++) { n[c] = a.pl_nrm[3 * (size_t)p + c]; pos[c] = a.pl_pos[3 * (size_t)p + c]; }
-    return a.pl_gid[p];
-}
-
-__device__ __forceinline__ void read_normal(const RestirArgs &a, int p, float n[3], int &gid)
-{
-    if (a.gbuf) {
-        const float *g = a.gbuf + 13 * (size_t)p;
-        for (int c = 0; c < 3; c++) n[c] = g[c];
-        gid = reinterpret_cast<const int *>(g)[12];
-        return;
-    }
-    for (int c = 0; c < 3; c++) n[c] = a.pl_nrm[3 * (size_t)p + c];
-    gid = a.pl_gid[p];
-}
-
-__device__ __forceinline__ float id_emittance(const RestirArgs &a, int gid) { return (gid >= 0 && gid < a.n_ids) ? a.emit[gid] : 0.0f; }
-
 __global__ __launch_bounds__(256) void k_restir_reset(RestirArgs arg)
 {
     int x, y;
@@ -216,16 +182,10 @@ __global__ __launch_bounds__(256) void k_restir_initial(RestirArgs arg)
         if (r.j >= 0 && r.W > 0.0f && light_occluded(arg.b, load_light(arg, r.j), pos, stk, r.u, r.v)) r.W = 0.0f;
         reservoir_take(s, r, 0.0f);
         if (arg.temporal && arg.motion) {
-            const float fx = floorf(arg.motion[2 * (size_t)p] + 0.5f), fy = floorf(arg.motion[2 * (size_t)p + 1] + 0.5f);
-            if (fx >= 0.0f && fx < (float)a.W && fy >= 0.0f && fy < (float)a.H) {
-                const int q = (int)fy * a.W + (int)fx;
-                if (arg.prev_gid[q] == gid) {
-                    const float *m = arg.prev_n + 3 * (size_t)q;
-                    if ((n[0] * m[0] + n[1] * m[1]) + n[2] * m[2] >= arg.min_dot) {
-                        const Reservoir h = load_reservoir(arg.H, q);
-                        reservoir_take_at(arg, s, h, fminf(h.M, arg.m_cap * r.M), scene_hash(a.seed, a.frame, up, 4160), n, pos);
-                    }
-                }
+            int q;
+            if (history_tap(arg, a, p, gid, n, q)) {
+                const Reservoir h = load_reservoir(arg.H, q);
+                reservoir_take_at(arg, s, h, fminf(h.M, arg.m_cap * r.M), scene_hash(a.seed, a.frame, up, 4160), n, pos);
             }
         }
         reservoir_finish(s);
@@ -326,25 +286,6 @@ __global__ __launch_bounds__(256) void k_lights_draw_all(RestirArgs arg)
     o[0] = D[0]; o[1] = D[1]; o[2] = D[2];
 }
 
-constexpr size_t align16(size_t n) { return (n + 15) & ~(size_t)15; }
-
-dim3 tile_grid(int width, int height) { return dim3((unsigned)((width + 63) / 64), (unsigned)((height + 3) / 4)); }
-
-// the scene's part of the kernel arguments, from the view of the moment
-int scene_args(RestirArgs &t, const svgf_scene *scene, int &device)
-{
-    SvgfSceneView v;
-    if (!scene || svgf_scene_view(scene, &v) != SVGF_OK) return SVGF_ERR_INVALID_ARG;
-    if (v.depth > SVGF_SCENE_MAX_DEPTH) return SVGF_ERR_UNSUPPORTED;        // the kernels' stack; svgf_scene_adopt_tree never lets it
-    device = v.device;
-    SceneArgs &a = t.b.s;
-    a.n_geoms = v.n_geoms; a.geoms = v.geoms; a.geom_ids = v.geom_ids;
-    a.n_tris = v.n_tris; a.tris = v.tris; a.tri_ids = v.tri_ids; a.tri_albedo = v.tri_albedo;
-    a.tri_tex = v.tri_tex; a.tex_desc = v.tex_desc; a.tex = v.tex;
-    t.b.nodes = reinterpret_cast<const float4 *>(v.nodes); t.b.order = v.order; t.b.tri_boxes = reinterpret_cast<const float4 *>(v.tri_boxes);
-    return SVGF_OK;
-}
-
 // the G-buffer, the synth parameters and the ambient term of a frame or a draw_all: refusals, then the arguments
 int surface_args(RestirArgs &t, const void *gbuffer_dev, const SvgfPlanarGBuffer *planes, int width, int height, const SvgfSynthParams *sp,
                  float ambient, void *out_D_dev)
@@ -370,16 +311,8 @@ bool light_ok(const SvgfLight &l)
 
 }  // namespace
 
-struct svgf_restir {
-    const svgf_scene *scene;
-    int device, width, height, n_ids;
-    char *dev;                  // the one allocation
-    unsigned long long bytes;
-    float4 *H, *T;
-    float *prev_n;
-    int *prev_gid;
-    float *emit;
-};
+struct svgf_restir : ReservoirState {};
+static_assert(SVGF_RESTIR_MAX_ID == RESERVOIR_MAX_ID, "the shared create's bound on ids");
 
 extern "C" int svgf_restir_version(void) { return (SVGF_VERSION_MAJOR << 16) | SVGF_VERSION_MINOR; }
 
@@ -419,61 +352,7 @@ extern "C" int svgf_lights_size(const svgf_lights *table) { return svgf_device_t
 
 extern "C" int svgf_restir_create(const svgf_scene *scene, int width, int height, svgf_restir **out)
 {
-    if (!out) return SVGF_ERR_INVALID_ARG;
-    *out = nullptr;
-    if (!scene || width <= 0 || height <= 0) return SVGF_ERR_INVALID_ARG;
-    if ((long long)width * height >= (1LL << 31) / 16) return SVGF_ERR_UNSUPPORTED;
-    SvgfSceneView v;
-    if (svgf_scene_view(scene, &v) != SVGF_OK) return SVGF_ERR_INVALID_ARG;
-    SvgfDeviceGuard dev_guard(v.device);
-    if (!dev_guard.ok) return SVGF_ERR_NO_DEVICE;
-    // the table from geomId to emittance, from the view's own arrays
-    std::vector<SvgfSceneGeom> geoms((size_t)v.n_geoms);
-    std::vector<int> geom_ids(v.geom_ids ? (size_t)v.n_geoms : 0), tri_ids((size_t)v.n_tris);
-    if (hipDeviceSynchronize() != hipSuccess) return SVGF_ERR_HIP;
-    if (v.n_geoms > 0 && hipMemcpy(geoms.data(), v.geoms, geoms.size() * sizeof(SvgfSceneGeom), hipMemcpyDeviceToHost) != hipSuccess) return SVGF_ERR_HIP;
-    if (!geom_ids.empty() && hipMemcpy(geom_ids.data(), v.geom_ids, geom_ids.size() * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return SVGF_ERR_HIP;
-    if (v.n_tris > 0 && hipMemcpy(tri_ids.data(), v.tri_ids, tri_ids.size() * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return SVGF_ERR_HIP;
-    int max_id = -1;
-    for (int k = 0; k < v.n_geoms; k++) {
-        const int id = geom_ids.empty() ? k : geom_ids[k];
-        if (id < 0 || id > SVGF_RESTIR_MAX_ID) return SVGF_ERR_INVALID_ARG;
-        max_id = id > max_id ? id : max_id;
-    }
-    for (int i = 0; i < v.n_tris; i++) {
-        if (tri_ids[i] < 0 || tri_ids[i] > SVGF_RESTIR_MAX_ID) return SVGF_ERR_INVALID_ARG;
-        max_id = tri_ids[i] > max_id ? tri_ids[i] : max_id;
-    }
-    const int n_ids = max_id + 1;
-    std::vector<float> emit((size_t)(n_ids > 0 ? n_ids : 1), 0.0f);
-    std::vector<char> seen(emit.size(), 0);
-    for (int k = 0; k < v.n_geoms; k++) {
-        const int id = geom_ids.empty() ? k : geom_ids[k];
-        const float e = geoms[k].emittance > 0.0f ? geoms[k].emittance : 0.0f;
-        if (seen[id] && emit[id] != e) return SVGF_ERR_INVALID_ARG;
-        seen[id] = 1; emit[id] = e;
-    }
-    for (int i = 0; i < v.n_tris; i++) {
-        if (seen[tri_ids[i]] && emit[tri_ids[i]] != 0.0f) return SVGF_ERR_INVALID_ARG;
-        seen[tri_ids[i]] = 1;
-    }
-    // one allocation: [H | T | previous normals | previous ids | emittance], 16-byte aligned parts
-    const size_t np = (size_t)width * height;
-    const size_t o_h = 0, o_t = o_h + 32 * np, o_n = o_t + 32 * np, o_g = o_n + align16(12 * np), o_e = o_g + align16(4 * np);
-    const size_t bytes = o_e + align16(4 * emit.size());
-    svgf_restir *st = new (std::nothrow) svgf_restir();
-    if (!st) return SVGF_ERR_OOM;
-    char *m = nullptr;
-    if (hipMalloc(reinterpret_cast<void **>(&m), bytes) != hipSuccess) { (void)hipGetLastError(); delete st; return SVGF_ERR_OOM; }
-    st->scene = scene; st->device = v.device; st->width = width; st->height = height; st->n_ids = n_ids;
-    st->dev = m; st->bytes = (unsigned long long)bytes;
-    st->H = reinterpret_cast<float4 *>(m + o_h); st->T = reinterpret_cast<float4 *>(m + o_t);
-    st->prev_n = reinterpret_cast<float *>(m + o_n); st->prev_gid = reinterpret_cast<int *>(m + o_g); st->emit = reinterpret_cast<float *>(m + o_e);
-    bool ok = hipMemset(m, 0, bytes) == hipSuccess && hipMemcpy(st->emit, emit.data(), 4 * emit.size(), hipMemcpyHostToDevice) == hipSuccess;
-    ok = ok && svgf_restir_reset(st, nullptr) == SVGF_OK && hipDeviceSynchronize() == hipSuccess;
-    if (!ok) { (void)hipGetLastError(); (void)hipFree(m); delete st; return SVGF_ERR_HIP; }
-    *out = st;
-    return SVGF_OK;
+    return reservoir_state_create(scene, width, height, 32, svgf_restir_reset, out);
 }
 
 extern "C" int svgf_restir_reset(svgf_restir *st, void *stream)
@@ -502,7 +381,7 @@ extern "C" int svgf_restir_frame(svgf_restir *st, const svgf_lights *table, cons
     if (!std::isfinite(rp->m_cap) || rp->m_cap < 1.0f || rp->neighbours < 0 || rp->neighbours > SVGF_RESTIR_MAX_NEIGHBOURS) return SVGF_ERR_INVALID_ARG;
     if (!std::isfinite(rp->radius) || rp->radius < 1.0f || rp->radius > 65536.0f || !std::isfinite(rp->normal_min_dot)) return SVGF_ERR_INVALID_ARG;
     int device = 0;
-    rc = scene_args(t, st->scene, device);
+    rc = scene_args(t.b, st->scene, device);
     if (rc != SVGF_OK) return rc;
     if (table->device != device || st->device != device) return SVGF_ERR_INVALID_ARG;
     SvgfDeviceGuard dev_guard(device);
@@ -528,7 +407,7 @@ extern "C" int svgf_lights_draw_all(const svgf_scene *scene, const svgf_lights *
     int rc = surface_args(t, gbuffer_dev, planes, width, height, sp, ambient, out_D_dev);
     if (rc != SVGF_OK) return rc;
     int device = 0;
-    rc = scene_args(t, scene, device);
+    rc = scene_args(t.b, scene, device);
     if (rc != SVGF_OK) return rc;
     if (table->device != device) return SVGF_ERR_INVALID_ARG;
     SvgfDeviceGuard dev_guard(device);
@@ -539,30 +418,11 @@ extern "C" int svgf_lights_draw_all(const svgf_scene *scene, const svgf_lights *
     return hipGetLastError() == hipSuccess ? SVGF_OK : SVGF_ERR_HIP;
 }
 
-extern "C" int svgf_restir_info(const svgf_restir *st, SvgfRestirInfo *out)
-{
-    if (!st || !out) return SVGF_ERR_INVALID_ARG;
-    *out = SvgfRestirInfo{ st->width, st->height, st->n_ids, 2, st->bytes };
-    return SVGF_OK;
-}
+extern "C" int svgf_restir_info(const svgf_restir *st, SvgfRestirInfo *out) { return reservoir_state_info(st, out); }
 
 extern "C" int svgf_restir_read(const svgf_restir *st, int which, void *host_dst, unsigned long long host_bytes)
 {
-    if (!st || which < 0 || which > 3 || !host_dst) return SVGF_ERR_INVALID_ARG;
-    const unsigned long long np = (unsigned long long)st->width * st->height;
-    const void *src[4] = { st->H, st->T, st->prev_n, st->prev_gid };
-    const unsigned long long size[4] = { 32ull * np, 32ull * np, 12ull * np, 4ull * np };
-    if (host_bytes != size[which]) return SVGF_ERR_INVALID_ARG;
-    SvgfDeviceGuard dev_guard(st->device);
-    if (!dev_guard.ok) return SVGF_ERR_NO_DEVICE;
-    if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(host_dst, src[which], (size_t)host_bytes, hipMemcpyDeviceToHost) != hipSuccess) return SVGF_ERR_HIP;
-    return SVGF_OK;
+    return reservoir_state_read(st, which, host_dst, host_bytes);
 }
 
-extern "C" void svgf_restir_destroy(svgf_restir *st)
-{
-    if (!st) return;
-    SvgfDeviceGuard dev_guard(st->device);
-    if (dev_guard.ok) { (void)hipDeviceSynchronize(); (void)hipFree(st->dev); }
-    delete st;
-}
+extern "C" void svgf_restir_destroy(svgf_restir *st) { reservoir_state_destroy(st); }

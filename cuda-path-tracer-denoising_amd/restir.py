@@ -115,19 +115,55 @@ class LightTable:
         self.free()
 
 
-class Restir:
-    """svgf_restir: the reservoir state of one frame size over one resident scene (create once: one allocation, not under capture).
-    frame(...) per frame behind the draw that wrote the G-buffer - two launches, legal under capture - writes D for svgf_denoise /
-    svgf_trace_compose; reset(stream) forgets the history in one launch.  free() before the scene's.  Usable as a context manager."""
+class ReservoirState:
+    """What Restir and restir_gi.RestirGI are apart from frame(): the reservoir state of one frame size over one resident scene (create
+    once: one allocation, not under capture), reset(stream) that forgets the history in one launch, info(), read(), free() before the
+    scene's, and the context manager.  A subclass names its library's symbol prefix, loader, reservoir dtype and info struct; a later
+    resampler subclasses this."""
+    PREFIX, LOAD, DTYPE, INFO = None, None, None, None
+    _target, _synth_params = staticmethod(_target), staticmethod(_synth_params)
 
     def __init__(self, scene, width: int, height: int):
-        self.lib, self.scene, self.h, self.width, self.height = load_restir_library(), scene, None, int(width), int(height)
+        self.lib, self.scene, self.h, self.width, self.height = self.LOAD(), scene, None, int(width), int(height)
         h = C.c_void_p()
-        _b._call(self.lib, "svgf_restir_create", scene.h, self.width, self.height, C.byref(h))
+        _b._call(self.lib, self.PREFIX + "_create", scene.h, self.width, self.height, C.byref(h))
         self.h = h
 
     def _call(self, symbol, *args):
         _b._call(self.lib, symbol, self.h, *args)
+
+    def reset(self, stream=None):
+        self._call(self.PREFIX + "_reset", _b._stream(stream))
+
+    def info(self) -> dict:
+        i = self.INFO()
+        self._call(self.PREFIX + "_info", C.byref(i))
+        return {k: int(getattr(i, k)) for k, _ in self.INFO._fields_}
+
+    def read(self, which: int) -> np.ndarray:
+        """<prefix>_read (blocking): 0 H, 1 T as DTYPE[height, width]; 2 the previous normals float32[height, width, 3]; 3 the previous
+        ids int32[height, width]."""
+        shape = (self.height, self.width)
+        out = np.zeros(shape, self.DTYPE) if int(which) < 2 else np.zeros(shape + (3,), np.float32) if int(which) == 2 else np.zeros(shape, np.int32)
+        self._call(self.PREFIX + "_read", int(which), out.ctypes.data, out.nbytes)
+        return out
+
+    def free(self):
+        if self.h:
+            getattr(self.lib, self.PREFIX + "_destroy")(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.free()
+
+
+class Restir(ReservoirState):
+    """svgf_restir: ReservoirState of RESERVOIR_DTYPE records.  frame(...) per frame behind the draw that wrote the G-buffer - two
+    launches, legal under capture - writes D for svgf_denoise / svgf_trace_compose.  Usable as a context manager."""
+    PREFIX, LOAD, DTYPE, INFO = "svgf_restir", staticmethod(load_restir_library), RESERVOIR_DTYPE, SvgfRestirInfo
 
     def frame(self, table: LightTable, gbuffer, out_D, frame: int, seed: int = 1, motion=None, rp: SvgfRestirParams | None = None,
               ambient: float = 0.15, stream=None):
@@ -136,30 +172,3 @@ class Restir:
         sp, rp = _synth_params(frame, seed), rp if rp is not None else params()
         self._call("svgf_restir_frame", table.h, *_target(gbuffer), _b._ptr(motion), C.byref(rp), C.byref(sp), float(ambient), _b._ptr(out_D),
                    _b._stream(stream))
-
-    def reset(self, stream=None):
-        self._call("svgf_restir_reset", _b._stream(stream))
-
-    def info(self) -> dict:
-        i = SvgfRestirInfo()
-        self._call("svgf_restir_info", C.byref(i))
-        return {k: int(getattr(i, k)) for k, _ in SvgfRestirInfo._fields_}
-
-    def read(self, which: int) -> np.ndarray:
-        """svgf_restir_read (blocking): 0 H, 1 T as RESERVOIR_DTYPE[height, width]; 2 the previous normals float32[height, width, 3];
-        3 the previous ids int32[height, width]."""
-        shape = (self.height, self.width)
-        out = np.zeros(shape, RESERVOIR_DTYPE) if int(which) < 2 else np.zeros(shape + (3,), np.float32) if int(which) == 2 else np.zeros(shape, np.int32)
-        self._call("svgf_restir_read", int(which), out.ctypes.data, out.nbytes)
-        return out
-
-    def free(self):
-        if self.h:
-            self.lib.svgf_restir_destroy(self.h)
-            self.h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.free()

@@ -1,7 +1,7 @@
 """libsvgf_restir_gi.so (include/svgf_restir_gi.h, row f28): the one-bounce indirect term of a resident scene's G-buffer by reservoir
 resampling of row f17's bounce samples - a per-size state of two reservoir planes, two launches per frame that write the demodulated
 indirect term I.  Built by the companions' recipe (build.PATH_RESAMPLERS), loaded like them (binding._load_linked), no companion
-draw; binding.py's pinned tables stay as they are.  The wrapper mirrors restir.Restir and shares its helpers."""
+draw; binding.py's pinned tables stay as they are.  The wrapper is restir.ReservoirState with this library's frame()."""
 from __future__ import annotations
 
 import ctypes as C
@@ -9,7 +9,7 @@ import ctypes as C
 import numpy as np
 
 from . import binding as _b
-from .restir import _synth_params, _target
+from .restir import ReservoirState
 
 RESTIR_GI_READ_H, RESTIR_GI_READ_T, RESTIR_GI_READ_PREV_NORMAL, RESTIR_GI_READ_PREV_ID = 0, 1, 2, 3
 RESTIR_GI_MAX_CANDIDATES, RESTIR_GI_MAX_NEIGHBOURS = 8, 8
@@ -51,51 +51,15 @@ def gi_params(candidates: int = 1, temporal: int = 1, m_cap: float = 20.0, neigh
                               float(jacobian_max), float(ambient), int(shadow_secondary))
 
 
-class RestirGI:
-    """svgf_restir_gi: the reservoir state of one frame size over one resident scene (create once: one allocation, not under capture).
-    frame(...) per frame behind the draw that wrote the G-buffer - two launches, legal under capture - writes I for svgf_denoise /
-    svgf_trace_compose; reset(stream) forgets the history in one launch.  free() before the scene's.  Usable as a context manager."""
-
-    def __init__(self, scene, width: int, height: int):
-        self.lib, self.scene, self.h, self.width, self.height = load_restir_gi_library(), scene, None, int(width), int(height)
-        h = C.c_void_p()
-        _b._call(self.lib, "svgf_restir_gi_create", scene.h, self.width, self.height, C.byref(h))
-        self.h = h
-
-    def _call(self, symbol, *args):
-        _b._call(self.lib, symbol, self.h, *args)
+class RestirGI(ReservoirState):
+    """svgf_restir_gi: ReservoirState of RESERVOIR_GI_DTYPE records.  frame(...) per frame behind the draw that wrote the G-buffer - two
+    launches, legal under capture - writes I for svgf_denoise / svgf_trace_compose.  Usable as a context manager."""
+    PREFIX, LOAD, DTYPE, INFO = "svgf_restir_gi", staticmethod(load_restir_gi_library), RESERVOIR_GI_DTYPE, SvgfRestirGIInfo
 
     def frame(self, light, gbuffer, out_I, frame: int, seed: int = 1, motion=None, gp: SvgfRestirGIParams | None = None, stream=None):
         """svgf_restir_gi_frame: `light` a SvgfSceneLight (centre and edges are read), `gbuffer` AoS texels or a SvgfPlanarGBuffer of
         the state's size, `motion` a SVGF_MOTION_PREV_COORD_F32 plane or None (no temporal reuse this frame), `gp` from gi_params().
         Asynchronous on `stream`; never waits."""
-        sp, gp = _synth_params(frame, seed), gp if gp is not None else gi_params()
-        self._call("svgf_restir_gi_frame", C.byref(light), *_target(gbuffer), _b._ptr(motion), C.byref(gp), C.byref(sp), _b._ptr(out_I),
+        sp, gp = self._synth_params(frame, seed), gp if gp is not None else gi_params()
+        self._call("svgf_restir_gi_frame", C.byref(light), *self._target(gbuffer), _b._ptr(motion), C.byref(gp), C.byref(sp), _b._ptr(out_I),
                    _b._stream(stream))
-
-    def reset(self, stream=None):
-        self._call("svgf_restir_gi_reset", _b._stream(stream))
-
-    def info(self) -> dict:
-        i = SvgfRestirGIInfo()
-        self._call("svgf_restir_gi_info", C.byref(i))
-        return {k: int(getattr(i, k)) for k, _ in SvgfRestirGIInfo._fields_}
-
-    def read(self, which: int) -> np.ndarray:
-        """svgf_restir_gi_read (blocking): 0 H, 1 T as RESERVOIR_GI_DTYPE[height, width]; 2 the previous normals float32[height, width, 3];
-        3 the previous ids int32[height, width]."""
-        shape = (self.height, self.width)
-        out = np.zeros(shape, RESERVOIR_GI_DTYPE) if int(which) < 2 else np.zeros(shape + (3,), np.float32) if int(which) == 2 else np.zeros(shape, np.int32)
-        self._call("svgf_restir_gi_read", int(which), out.ctypes.data, out.nbytes)
-        return out
-
-    def free(self):
-        if self.h:
-            self.lib.svgf_restir_gi_destroy(self.h)
-            self.h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.free()

@@ -13,7 +13,7 @@ import resident_scene_model as rm
 import restir_model as rsm
 import scene_shadow_model as ssm
 import scene_trace_model as stm
-from restir_model import lum
+from restir_model import _planes, history_tap, lum, neighbour_tap
 from scene_model import F, _dot, _sel, synth
 
 ALTS = ("no_inverse_M", "no_jacobian", "no_jacobian_bounds", "g_as_stored", "refused_adds_M", "candidate_target_needs_g", "no_m_cap",
@@ -193,11 +193,6 @@ def _take_at(s, mask, r, Mq, xi, nrm, pos, gp, cnt, alt):
         return _update(s, ok, r.xs, r.ns, r.L, r.g if alt == "g_as_stored" else g, phat, w, Mq, xi)
 
 
-def _planes(gb):
-    nrm, pos = ([np.ascontiguousarray(gb[f][..., c]).reshape(-1) for c in range(3)] for f in ("normal", "position"))
-    return nrm, pos, np.ascontiguousarray(gb["geomId"]).reshape(-1)
-
-
 class State:
     """svgf_restir_gi's planes for one frame size: H and T (RESERVOIR_GI_DTYPE[H, W]), the previous normals and ids.  reset() is
     svgf_restir_gi_reset; frame() both launches of svgf_restir_gi_frame."""
@@ -242,19 +237,10 @@ class State:
             s = r
             foreign1 = np.zeros(n, bool)
             if gp["temporal"] and motion is not None:
-                mv = np.ascontiguousarray(motion, dtype=F).reshape(-1, 2)
-                half = F(0.0) if alt == "tap_rounds_down" else F(0.5)
-                fx, fy = np.floor((mv[:, 0] + half).astype(F)), np.floor((mv[:, 1] + half).astype(F))
-                on = (fx >= 0) & (fx < F(W)) & (fy >= 0) & (fy < F(H))
-                q = np.where(on, np.where(on, fy, 0).astype(np.int64) * W + np.where(on, fx, 0).astype(np.int64), 0)
-                id_ok = self.prev_gid.reshape(-1)[q] == gid
-                pn = self.prev_n.reshape(-1, 3)[q]
-                n_ok = _dot(nrm, [pn[:, c] for c in range(3)]) >= gp["normal_min_dot"]
-                on &= surf
+                q, on, id_ok, n_ok, acc = history_tap(self.prev_gid, self.prev_n, motion, W, H, gid, nrm, surf, gp["normal_min_dot"], alt)
                 cnt["tap_off_screen"] = int((surf & ~on).sum())
                 cnt["tap_refused_id"] += int((on & ~id_ok).sum())
                 cnt["tap_refused_normal"] += int((on & id_ok & ~n_ok).sum())
-                acc = on & (id_ok | (alt == "temporal_no_id_test")) & (n_ok | (alt == "temporal_no_normal_test"))
                 h = _Res.stored(self.H.reshape(-1)[q])
                 cap = (gp["m_cap"] * s.M).astype(F)
                 cnt["m_capped"] = int((acc & h.valid & (h.M > cap)).sum())
@@ -266,21 +252,11 @@ class State:
             s = _Res.stored(self.T.reshape(-1))
             _restart(s, surf)
             foreign = np.zeros(n, bool)
-            x, y = np.tile(np.arange(W), H), np.repeat(np.arange(H), W)
             for k in range(gp["neighbours"]):
                 base = 8256 + 4 * k
-                ox = np.floor(((((F(2.0) * hu(base)).astype(F) - F(1.0)).astype(F) * gp["radius"]).astype(F) + F(0.5)).astype(F)).astype(np.int64)
-                oy = np.floor(((((F(2.0) * hu(base + 1)).astype(F) - F(1.0)).astype(F) * gp["radius"]).astype(F) + F(0.5)).astype(F)).astype(np.int64)
-                qx, qy = x + ox, y + oy
-                on = surf & (qx >= 0) & (qx < W) & (qy >= 0) & (qy < H)
-                if alt != "neighbour_may_be_self":
-                    on &= ~((ox == 0) & (oy == 0))
-                q = np.where(on, qy * W + qx, 0)
-                id_ok = gid[q] == gid
-                n_ok = _dot(nrm, [nrm[c][q] for c in range(3)]) >= gp["normal_min_dot"]
+                q, on, id_ok, n_ok, acc = neighbour_tap(hu(base), hu(base + 1), gp["radius"], W, H, gid, nrm, surf, gp["normal_min_dot"], alt)
                 cnt["tap_refused_id"] += int((on & ~id_ok).sum())
                 cnt["tap_refused_normal"] += int((on & id_ok & ~n_ok).sum())
-                acc = on & (id_ok | (alt == "spatial_no_id_test")) & (n_ok | (alt == "spatial_no_normal_test"))
                 tq = _Res.stored(self.T.reshape(-1)[q])
                 foreign |= _take_at(s, acc, tq, tq.M, hu(base + 2), nrm, pos, gp, cnt, alt)
             _finish(s, alt)

@@ -182,6 +182,40 @@ def _planes(gb):
     return nrm, pos, np.ascontiguousarray(gb["geomId"]).reshape(-1)
 
 
+def history_tap(prev_gid, prev_n, motion, W, H, gid, nrm, surf, min_dot, alt=None):
+    """The history tap of every pixel, as both libraries' first launch takes it: (q, on, id_ok, n_ok, acc) - the previous pixel the
+    motion vector rounds to (0 where it is off the frame), and the masks a caller counts its events from: on a surface and on the frame,
+    the id as before, the normal within min_dot, accepted.  alt: tap_rounds_down, temporal_no_id_test, temporal_no_normal_test."""
+    with np.errstate(all="ignore"):
+        mv = np.ascontiguousarray(motion, dtype=F).reshape(-1, 2)
+        half = F(0.0) if alt == "tap_rounds_down" else F(0.5)
+        fx, fy = np.floor((mv[:, 0] + half).astype(F)), np.floor((mv[:, 1] + half).astype(F))
+        on = (fx >= 0) & (fx < F(W)) & (fy >= 0) & (fy < F(H))
+        q = np.where(on, np.where(on, fy, 0).astype(np.int64) * W + np.where(on, fx, 0).astype(np.int64), 0)
+        id_ok = prev_gid.reshape(-1)[q] == gid
+        pn = prev_n.reshape(-1, 3)[q]
+        n_ok = _dot(nrm, [pn[:, c] for c in range(3)]) >= min_dot
+    on = on & surf
+    return q, on, id_ok, n_ok, on & (id_ok | (alt == "temporal_no_id_test")) & (n_ok | (alt == "temporal_no_normal_test"))
+
+
+def neighbour_tap(u_x, u_y, radius, W, H, gid, nrm, surf, min_dot, alt=None):
+    """The neighbour every pixel picks from the uniforms (u_x, u_y), as both libraries' second launch does: (q, on, id_ok, n_ok, acc) -
+    its index (0 where there is none) and the masks a caller counts its events from: on a surface, on the frame and not the pixel
+    itself, the same id, the normal within min_dot, accepted.  alt: neighbour_may_be_self, spatial_no_id_test, spatial_no_normal_test."""
+    x, y = np.tile(np.arange(W), H), np.repeat(np.arange(H), W)
+    with np.errstate(all="ignore"):
+        ox, oy = (np.floor(((((F(2.0) * u).astype(F) - F(1.0)).astype(F) * radius).astype(F) + F(0.5)).astype(F)).astype(np.int64) for u in (u_x, u_y))
+        qx, qy = x + ox, y + oy
+        on = surf & (qx >= 0) & (qx < W) & (qy >= 0) & (qy < H)
+        if alt != "neighbour_may_be_self":
+            on &= ~((ox == 0) & (oy == 0))
+        q = np.where(on, qy * W + qx, 0)
+        id_ok = gid[q] == gid
+        n_ok = _dot(nrm, [nrm[c][q] for c in range(3)]) >= min_dot
+    return q, on, id_ok, n_ok, on & (id_ok | (alt == "spatial_no_id_test")) & (n_ok | (alt == "spatial_no_normal_test"))
+
+
 class State:
     """svgf_restir's planes for one frame size: H and T (RESERVOIR_DTYPE[H, W]), the previous normals and ids.  reset() is
     svgf_restir_reset; frame() both launches of svgf_restir_frame."""
@@ -234,19 +268,10 @@ class State:
             _take(s, surf, r)
             from_history = np.zeros(n, bool)
             if rp["temporal"] and motion is not None:
-                mv = np.ascontiguousarray(motion, dtype=F).reshape(-1, 2)
-                half = F(0.0) if alt == "tap_rounds_down" else F(0.5)
-                fx, fy = np.floor((mv[:, 0] + half).astype(F)), np.floor((mv[:, 1] + half).astype(F))
-                on = (fx >= 0) & (fx < F(W)) & (fy >= 0) & (fy < F(H))
-                q = np.where(on, np.where(on, fy, 0).astype(np.int64) * W + np.where(on, fx, 0).astype(np.int64), 0)
-                id_ok = self.prev_gid.reshape(-1)[q] == gid
-                pn = self.prev_n.reshape(-1, 3)[q]
-                n_ok = _dot(nrm, [pn[:, c] for c in range(3)]) >= rp["normal_min_dot"]
-                on &= surf
+                q, on, id_ok, n_ok, acc = history_tap(self.prev_gid, self.prev_n, motion, W, H, gid, nrm, surf, rp["normal_min_dot"], alt)
                 cnt["tap_off_screen"] = int((surf & ~on).sum())
                 cnt["tap_refused_id"] = int((on & ~id_ok).sum())
                 cnt["tap_refused_normal"] = int((on & id_ok & ~n_ok).sum())
-                acc = on & (id_ok | (alt == "temporal_no_id_test")) & (n_ok | (alt == "temporal_no_normal_test"))
                 cnt["tap_accepted"] = int(acc.sum())
                 h = _Res.stored(self.H.reshape(-1)[q])
                 cap = (rp["m_cap"] * r.M).astype(F)
@@ -263,21 +288,11 @@ class State:
             s = _Res(n)
             _take(s, surf, t)
             reused = from_history & (t.j >= 0)
-            x, y = np.tile(np.arange(W), H), np.repeat(np.arange(H), W)
             for k in range(rp["neighbours"]):
                 base = 4192 + 4 * k
-                ox = np.floor(((((F(2.0) * hu(base)).astype(F) - F(1.0)).astype(F) * rp["radius"]).astype(F) + F(0.5)).astype(F)).astype(np.int64)
-                oy = np.floor(((((F(2.0) * hu(base + 1)).astype(F) - F(1.0)).astype(F) * rp["radius"]).astype(F) + F(0.5)).astype(F)).astype(np.int64)
-                qx, qy = x + ox, y + oy
-                on = surf & (qx >= 0) & (qx < W) & (qy >= 0) & (qy < H)
-                if alt != "neighbour_may_be_self":
-                    on &= ~((ox == 0) & (oy == 0))
-                q = np.where(on, qy * W + qx, 0)
-                id_ok = gid[q] == gid
-                n_ok = _dot(nrm, [nrm[c][q] for c in range(3)]) >= rp["normal_min_dot"]
+                q, on, id_ok, n_ok, acc = neighbour_tap(hu(base), hu(base + 1), rp["radius"], W, H, gid, nrm, surf, rp["normal_min_dot"], alt)
                 cnt["neighbour_refused_id"] += int((on & ~id_ok).sum())
                 cnt["neighbour_refused_normal"] += int((on & id_ok & ~n_ok).sum())
-                acc = on & (id_ok | (alt == "spatial_no_id_test")) & (n_ok | (alt == "spatial_no_normal_test"))
                 cnt["neighbour_accepted"] += int(acc.sum())
                 tq = _Res.stored(self.T.reshape(-1)[q])
                 had = s.w_sum > 0

@@ -31,38 +31,17 @@ import scene_split_model as splm
 import temporal_model as tm
 import test_scene_model as tsm
 from conftest import ROOT
+from reservoir_harness import (AMBIENT, TUBE_ID, PIVOT, assert_frame, device_rp as _device_rp, differing_records, lamps as _lamps, motion as _motion, nm as _nm,
+                               out as _out, planes_of as _planes_of, read as _read, same_bytes, tube_scene as _tube_scene)
 from test_scene_model import FRAME, SEED
 
 F = np.float32
 ERR, UNSUPPORTED = -1, -5
 W0, H0 = 67, 41
 SIZES = [(1, 1), (64, 4), (67, 41), (257, 9)]
-AMBIENT = 0.15
-
-
-def same_bytes(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
-
-
-def differing_records(a, b):
-    return int((np.ascontiguousarray(a).view(np.uint8).reshape(a.size, -1) != np.ascontiguousarray(b).view(np.uint8).reshape(b.size, -1)).any(axis=1).sum())
 
 
 # ---- inputs ------------------------------------------------------------------------------------------------------------------------------
-@functools.lru_cache(maxsize=None)
-def _lamps(n, kind, seed=27):
-    """n lights over the made stage: centres in a slab above the floor, `area` lights with half-edges of up to 0.4, powers per channel
-    such that the sum over the lights stays near one light of 30."""
-    rng = np.random.default_rng(seed + n)
-    c = np.stack([rng.uniform(-5, 5, n), rng.uniform(1.5, 7.0, n), rng.uniform(-5, 5, n)], -1)
-    eu = rng.uniform(-0.4, 0.4, (n, 3)) if kind == "area" else np.zeros((n, 3))
-    ev = rng.uniform(-0.4, 0.4, (n, 3)) if kind == "area" else np.zeros((n, 3))
-    lt = rsm.lights(c, eu, ev, rng.uniform(10.0, 50.0, (n, 3)) / min(n, 64) ** 0.5)
-    lt.setflags(write=False)
-    return lt
-
-
 @functools.lru_cache(maxsize=None)
 def _stage_gb(W, H, nan_normals=False):
     """The made stage's first hit (floor, occluding cube, two emitters, two triangles, misses): scene_model.render's G-buffer."""
@@ -71,22 +50,6 @@ def _stage_gb(W, H, nan_normals=False):
         gb = gb.copy()
         gb["normal"][::3, ::2] = np.nan
     return gb
-
-
-TUBE = dict(segments=8, sides=8, length=6.0, radius=0.5, base=(1.5, 0.1, 6.0))      # tests/test_deform_scene.py's tube in row f15's room
-PIVOT, TUBE_ID = (1.5, 3.1, 6.0), 40
-
-
-@functools.lru_cache(maxsize=None)
-def _tube_scene():
-    import __graft_entry__ as ge
-    pkg = ge.load_package()
-    geoms, cam, lt = sh.example_scene()
-    tris, bone, weight = pkg.deform.tube_rig(**TUBE)
-    n = len(tris)
-    s = dict(cam=cam, geoms=geoms, geom_ids=None, tris=tris, tri_ids=np.full(n, TUBE_ID, np.int32), tri_albedo=tsm._colours(n, 26), tri_tex=None,
-             textures=None, light=lt["centre"])
-    return s, (np.arange(n, dtype=np.int32), bone, weight)
 
 
 @functools.lru_cache(maxsize=None)
@@ -99,19 +62,6 @@ def _room_gb(W, H, nan_normals=False):
         gb["normal"][::3, ::2] = np.nan
     gb.setflags(write=False)
     return gb
-
-
-def _motion(W, H, f):
-    """A SVGF_MOTION_PREV_COORD_F32 plane made for the taps: a shift that differs per frame and crosses object and face edges, and
-    rows of pixels with NaN, +-inf and far off-screen values."""
-    x, y = np.meshgrid(np.arange(W, dtype=F), np.arange(H, dtype=F))
-    sign = F(-1.0 if f == 2 else 1.0)                                       # the second plane looks back the other way
-    mv = np.stack([x + sign * F(1.3 + 2.1 * f), y - sign * F(0.6 + 0.9 * f)], -1).astype(F)
-    flat = mv.reshape(-1, 2)
-    n = W * H
-    for k, bad in enumerate((np.nan, np.inf, -np.inf, -5.0, 1e9, -0.5001, W - 0.5)):
-        flat[(7 * k + 3) % n::53, k % 2] = bad
-    return mv
 
 
 # (W, H, lights, kind, candidates, neighbours, radius, m_cap, planar, normal_min_dot): every value the row lists, across the four sizes; the last
@@ -144,11 +94,6 @@ def _matrix_model(c, alt=None, nan_normals=False):
 
 
 # ---- CPU 1: the libraries' surfaces -----------------------------------------------------------------------------------------------------------
-def _nm(path, flag):
-    out = subprocess.run(["nm", "-D", flag, path], stdout=subprocess.PIPE, text=True, check=True).stdout
-    return sorted(ln.split()[-1] for ln in out.splitlines() if ln.split() and ln.split()[-1].startswith("svgf_")), out
-
-
 def test_exports_and_links(pkg):
     bld, B, R = pkg.build, pkg.binding, pkg.restir
     path = bld.build_restir()
@@ -344,42 +289,6 @@ def test_every_event_occurs_and_every_alt_acts_on_the_gpu_cases():
         assert acts > 0, f"alt {alt} changes nothing on the GPU cases"
 
 
-# ---- GPU helpers ---------------------------------------------------------------------------------------------------------------------------
-def _planes_of(pkg, gb):
-    """A G-buffer's normal, position and geomId as device planes: (SvgfPlanarGBuffer, the tensors that keep them alive)."""
-    import torch
-    t = [torch.from_numpy(np.ascontiguousarray(gb[f])).cuda() for f in ("normal", "position", "geomId")]
-    return pkg.binding.SvgfPlanarGBuffer(t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr(), None), t
-
-
-def _out(W, H):
-    import torch
-    return torch.full((H, W, 3), float("nan"), dtype=torch.float32, device="cuda")
-
-
-def _read(st):
-    return dict(H=st.read(0), T=st.read(1), prev_n=st.read(2), prev_gid=st.read(3))
-
-
-def _assert_frame(st, D, want, what):
-    """T and H as read back BEFORE D; expected and allowed differences: 0."""
-    import torch
-    torch.cuda.synchronize()
-    got = _read(st)
-    bad = {k: differing_records(got[k], want[k]) for k in ("T", "H")}
-    bad["prev_n"] = int(tsm.differing(got["prev_n"], want["prev_n"]).sum())
-    bad["prev_gid"] = int((got["prev_gid"] != want["prev_gid"]).sum())
-    print(f"{what}: differing records {bad} (expected and allowed: 0)")
-    assert not any(bad.values()), f"{what}: {bad}"
-    d = int(tsm.differing(D.cpu().numpy(), want["D"]).sum())
-    print(f"{what}: D differs on {d} pixels (expected and allowed: 0)")
-    assert d == 0, f"{what}: D differs on {d} pixels"
-
-
-def _device_rp(pkg, rp):
-    return pkg.restir.params(rp["candidates"], rp["temporal"], float(rp["m_cap"]), rp["neighbours"], float(rp["radius"]), float(rp["normal_min_dot"]))
-
-
 # ---- GPU 1: the matrix ---------------------------------------------------------------------------------------------------------------------
 @pytest.mark.gpu
 @pytest.mark.parametrize("c", MATRIX, ids=_mid)
@@ -397,13 +306,13 @@ def test_three_successive_frames_equal_the_model_on_bits(pkg, c):
         for f in range(3):
             mv = None if f == 0 else sh.dev(_motion(W, H, f))
             st.frame(table, target, D, FRAME + f, SEED, motion=mv, rp=_device_rp(pkg, _rp(c)), ambient=AMBIENT)
-            _assert_frame(st, D, want[f], f"{_mid(c)} frame {f}")
+            assert_frame(st, D, want[f], "D", f"{_mid(c)} frame {f}")
         st.reset()                                                        # a frame after reset is a first frame
         st.frame(table, target, D, FRAME, SEED, motion=sh.dev(_motion(W, H, 1)), rp=_device_rp(pkg, _rp(c)), ambient=AMBIENT)
         first = rsm.State(rsm.Scene(s), W, H)
         Dm, _ = first.frame(gb, _lamps(n, kind), _rp(c), FRAME, SEED, AMBIENT, motion=_motion(W, H, 1))
         assert same_bytes(first.H, want[0]["H"]) and not tsm.differing(Dm, want[0]["D"]).any(), "the model: a reset state finds no history"
-        _assert_frame(st, D, want[0], f"{_mid(c)} after reset")
+        assert_frame(st, D, want[0], "D", f"{_mid(c)} after reset")
     finally:
         sh.free(st, table, scene)
 
@@ -423,7 +332,7 @@ def test_nan_normals_and_the_same_sequence_twice(pkg):
             st.reset()
             for f in range(3):
                 st.frame(table, tex, D, FRAME + f, SEED, motion=None if f == 0 else sh.dev(_motion(W, H, f)), rp=_device_rp(pkg, _rp(c)), ambient=AMBIENT)
-                _assert_frame(st, D, want[f], f"NaN normals, frame {f}")
+                assert_frame(st, D, want[f], "D", f"NaN normals, frame {f}")
             runs.append((_read(st), D.cpu().numpy().copy()))
         assert all(same_bytes(runs[0][0][k], runs[1][0][k]) for k in runs[0][0]) and same_bytes(runs[0][1], runs[1][1]), "the same calls from the same history"
     finally:
@@ -495,7 +404,7 @@ def test_the_posed_block_with_the_plane_of_motion_reproject(pkg):
             model.sc = rsm.Scene(s, geoms=pm.posed_scene(s, tables[f])["geoms"])
             Dm, cnt = model.frame(gb, lt, rp, f, 3, AMBIENT, motion=mv.cpu().numpy())
             kept += cnt["tap_accepted"] if f else 0
-            _assert_frame(st, D, dict(T=model.T, H=model.H, D=Dm, prev_n=model.prev_n, prev_gid=model.prev_gid), f"posed block, frame {f}")
+            assert_frame(st, D, dict(T=model.T, H=model.H, D=Dm, prev_n=model.prev_n, prev_gid=model.prev_gid), "D", f"posed block, frame {f}")
         assert kept > 1000, "the plane should keep history"
     finally:
         sh.free(st, table, scene)
@@ -535,7 +444,7 @@ def test_the_bending_tube_with_the_plane_of_deform_prev_positions(pkg):
             before = model.prev_gid.copy()
             Dm, cnt = model.frame(gb, lt, rp, f, 3, AMBIENT, motion=mv.cpu().numpy())
             tube_kept += int(((gb["geomId"] == TUBE_ID) & (model.T["M"] > rp["candidates"])).sum()) if f else 0
-            _assert_frame(st, D, dict(T=model.T, H=model.H, D=Dm, prev_n=model.prev_n, prev_gid=model.prev_gid), f"bending tube, frame {f}")
+            assert_frame(st, D, dict(T=model.T, H=model.H, D=Dm, prev_n=model.prev_n, prev_gid=model.prev_gid), "D", f"bending tube, frame {f}")
             assert f == 0 or (before >= 0).any()
         print(f"tube pixels that combined a history reservoir over frames 1 and 2: {tube_kept}")
         assert tube_kept > 0, "the plane should keep history on the tube"
@@ -570,7 +479,7 @@ def test_a_captured_frame_is_two_kernel_nodes_and_replays_with_the_history_of_th
             graph.launch()
             stream.synchronize()
             Dm, _ = model.frame(gb, lt, rp, FRAME, SEED, AMBIENT, motion=mvh)
-            _assert_frame(st, D, dict(T=model.T, H=model.H, D=Dm, prev_n=model.prev_n, prev_gid=model.prev_gid), f"replay {k}")
+            assert_frame(st, D, dict(T=model.T, H=model.H, D=Dm, prev_n=model.prev_n, prev_gid=model.prev_gid), "D", f"replay {k}")
         graph.destroy(); reset.destroy()
     finally:
         stream.close()

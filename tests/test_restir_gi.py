@@ -31,29 +31,15 @@ import scene_shadow_model as ssm
 import scene_split_model as splm
 import scene_trace_model as stm
 import temporal_model as tm
-import test_restir as tr
 import test_scene_model as tsm
 from conftest import ROOT
+from reservoir_harness import (AMBIENT, PIVOT, TUBE_ID, assert_frame, device_rp as _device_rp, differing_records, lamps as _lamps, motion as _motion,
+                               nm as _nm, out as _out, planes_of as _planes_of, read as _read, same_bytes, tube_scene as _tube_scene)
 from test_scene_model import FRAME, SEED
 
 F = np.float32
 ERR, UNSUPPORTED = -1, -5
 SIZES = [(1, 1), (64, 4), (67, 41), (257, 9)]
-
-
-def differing_records(a, b):
-    """The records of two reservoir planes that differ in bits; NaNs in the same place are equal."""
-    a, b = np.ascontiguousarray(a).reshape(-1), np.ascontiguousarray(b).reshape(-1)
-    assert a.dtype == b.dtype and a.shape == b.shape
-    bad = np.zeros(len(a), bool)
-    for k in a.dtype.names:
-        x, y = a[k].reshape(len(a), -1), b[k].reshape(len(b), -1)
-        if x.dtype.kind == "f":
-            nx, ny = np.isnan(x), np.isnan(y)
-            bad |= ((nx != ny) | (~nx & ~ny & (x.view(np.uint32) != y.view(np.uint32)))).any(axis=1)
-        else:
-            bad |= (x != y).any(axis=1)
-    return int(bad.sum())
 
 
 # ---- inputs ------------------------------------------------------------------------------------------------------------------------------
@@ -106,7 +92,7 @@ def _matrix_model(c, alt=None, nan_normals=False):
     st = gm.State(gm.Scene(s), W, H)
     gb, lt, out = _gb(kind, name, W, H, nan_normals), _light(kind, name, c[4]), []
     for f in range(3):
-        I, cnt = st.frame(gb, lt, _gp(c), FRAME + f, SEED, motion=None if f == 0 else tr._motion(W, H, f), alt=alt)      # noqa: E741
+        I, cnt = st.frame(gb, lt, _gp(c), FRAME + f, SEED, motion=None if f == 0 else _motion(W, H, f), alt=alt)      # noqa: E741
         out.append(dict(T=st.T.copy(), H=st.H.copy(), I=I, cnt=cnt, prev_n=st.prev_n.copy(), prev_gid=st.prev_gid.copy()))
     return out
 
@@ -118,11 +104,11 @@ def test_exports_and_links(pkg):
     assert os.path.basename(path) == "libsvgf_restir_gi.so" and path == B.companion_path("restir_gi")
     header = open(os.path.join(ROOT, "include", "svgf_restir_gi.h")).read()
     declared = sorted(set(re.findall(r"^\s*(?:int|void)\s+(svgf_restir_gi_\w+)\(", header, re.M)))
-    assert declared == sorted(G.RESTIR_GI_EXPORTS) == tr._nm(path, "--defined-only")[0]
+    assert declared == sorted(G.RESTIR_GI_EXPORTS) == _nm(path, "--defined-only")[0]
     out = subprocess.run(["readelf", "-d", path], stdout=subprocess.PIPE, text=True, check=True).stdout
     needed = sorted(ln.split("[")[1].split("]")[0] for ln in out.splitlines() if "(NEEDED)" in ln and "[libsvgf_" in ln)
     assert needed == ["libsvgf_hip.so"], needed
-    wanted, undefined = tr._nm(path, "--undefined-only")
+    wanted, undefined = _nm(path, "--undefined-only")
     assert "getenv" not in undefined
     assert wanted == ["svgf_scene_view"], wanted
     assert [b.name for b in bld.PATH_RESAMPLERS] == ["restir_gi"] and "-ffp-contract=off" in bld.PATH_RESAMPLERS[0].flags and path not in bld.build_all()
@@ -140,8 +126,8 @@ def test_the_other_libraries_export_what_they_did_and_build_all_is_as_it_was(pkg
     others.update(lbvh=B.LBVH_EXPORTS, sah=pkg.sah.SAH_EXPORTS, deform=pkg.deform.DEFORM_EXPORTS, restir=pkg.restir.RESTIR_EXPORTS)
     assert len(others) == 11
     for name, exports in others.items():
-        assert tr._nm(bld.build_companion(name), "--defined-only")[0] == sorted(exports), name
-    assert tr._nm(bld.build_hip(), "--defined-only")[0] == sorted(B.EXPORTS + pkg.deform.SCENE_WRITE_EXPORTS)
+        assert _nm(bld.build_companion(name), "--defined-only")[0] == sorted(exports), name
+    assert _nm(bld.build_hip(), "--defined-only")[0] == sorted(B.EXPORTS + pkg.deform.SCENE_WRITE_EXPORTS)
     assert bld.build_all() == [bld.LIB] + [B.companion_path(c.name) for c in bld.COMPANIONS] and len(bld.build_all()) == 8
     assert [b.name for b in bld.BUILDERS + bld.TREE_BUILDERS + bld.SCENE_WRITERS + bld.LIGHT_SAMPLERS] == ["lbvh", "sah", "deform", "restir"]
 
@@ -392,25 +378,6 @@ def test_every_event_occurs_and_every_alt_acts_on_the_gpu_cases():
 
 
 # ---- GPU helpers ---------------------------------------------------------------------------------------------------------------------------
-def _read(st):
-    return dict(H=st.read(0), T=st.read(1), prev_n=st.read(2), prev_gid=st.read(3))
-
-
-def _assert_frame(st, I, want, what):      # noqa: E741
-    """T and H as read back BEFORE I; expected and allowed differences: 0."""
-    import torch
-    torch.cuda.synchronize()
-    got = _read(st)
-    bad = {k: differing_records(got[k], want[k]) for k in ("T", "H")}
-    bad["prev_n"] = int(tsm.differing(got["prev_n"], want["prev_n"]).sum())
-    bad["prev_gid"] = int((got["prev_gid"] != want["prev_gid"]).sum())
-    print(f"{what}: differing records {bad} (expected and allowed: 0)")
-    assert not any(bad.values()), f"{what}: {bad}"
-    d = int(tsm.differing(I.cpu().numpy(), want["I"]).sum())
-    print(f"{what}: I differs on {d} pixels (expected and allowed: 0)")
-    assert d == 0, f"{what}: I differs on {d} pixels"
-
-
 def _device_gp(pkg, gp):
     return pkg.gi_params(gp["candidates"], gp["temporal"], float(gp["m_cap"]), gp["neighbours"], float(gp["radius"]), float(gp["normal_min_dot"]),
                          float(gp["jacobian_max"]), float(gp["ambient"]), gp["shadow_secondary"])
@@ -436,16 +403,16 @@ def _three_frames(pkg, c, nan_normals=False, attach_sah=False):
         assert (info["width"], info["height"], info["launches"]) == (W, H, 2) and info["device_bytes"] >= 144 * W * H
         lt = sh.light(pkg, _light(kind, name, c[4]))
         gb = _gb(kind, name, W, H, nan_normals)
-        target, keep = tr._planes_of(pkg, gb) if c[11] else (sh.dev(gb), None)
-        I = tr._out(W, H)      # noqa: E741
+        target, keep = _planes_of(pkg, gb) if c[11] else (sh.dev(gb), None)
+        I = _out(W, H)      # noqa: E741
         for f in range(3):
-            mv = None if f == 0 else sh.dev(tr._motion(W, H, f))
+            mv = None if f == 0 else sh.dev(_motion(W, H, f))
             st.frame(lt, target, I, FRAME + f, SEED, motion=mv, gp=_device_gp(pkg, _gp(c)))
-            _assert_frame(st, I, want[f], f"{_mid(c)} frame {f}")
+            assert_frame(st, I, want[f], "I", f"{_mid(c)} frame {f}")
         last = _read(st), I.cpu().numpy().copy()
         st.reset()                                                        # a frame after reset is a first frame
-        st.frame(lt, target, I, FRAME, SEED, motion=sh.dev(tr._motion(W, H, 1)), gp=_device_gp(pkg, _gp(c)))
-        _assert_frame(st, I, want[0], f"{_mid(c)} after reset")
+        st.frame(lt, target, I, FRAME, SEED, motion=sh.dev(_motion(W, H, 1)), gp=_device_gp(pkg, _gp(c)))
+        assert_frame(st, I, want[0], "I", f"{_mid(c)} after reset")
         return last
     finally:
         sh.free(st, tree, scene)
@@ -465,9 +432,9 @@ def test_nan_normals_the_same_sequence_twice_and_an_attached_tree(pkg):
     c = MATRIX[10]
     a = _three_frames(pkg, c, nan_normals=True)
     b = _three_frames(pkg, c, nan_normals=True)
-    assert all(tr.same_bytes(a[0][k], b[0][k]) for k in a[0]) and tr.same_bytes(a[1], b[1]), "the same calls from the same history"
+    assert all(same_bytes(a[0][k], b[0][k]) for k in a[0]) and same_bytes(a[1], b[1]), "the same calls from the same history"
     plain, tree = _three_frames(pkg, MATRIX[9]), _three_frames(pkg, MATRIX[9], attach_sah=True)
-    assert all(tr.same_bytes(plain[0][k], tree[0][k]) for k in plain[0]) and tr.same_bytes(plain[1], tree[1]), "an attached tree leaves every byte"
+    assert all(same_bytes(plain[0][k], tree[0][k]) for k in plain[0]) and same_bytes(plain[1], tree[1]), "an attached tree leaves every byte"
 
 
 @pytest.mark.gpu
@@ -481,14 +448,14 @@ def test_a_state_left_by_other_frames_and_reset_gives_the_same_bytes(pkg):
     scene = sh.create(pkg, s)
     st = pkg.RestirGI(scene, W, H)
     try:
-        lt, tex, I = sh.light(pkg, _light(kind, name, c[4])), sh.dev(_gb(kind, name, W, H)), tr._out(W, H)      # noqa: E741
+        lt, tex, I = sh.light(pkg, _light(kind, name, c[4])), sh.dev(_gb(kind, name, W, H)), _out(W, H)      # noqa: E741
         still = sh.dev(np.stack(np.meshgrid(np.arange(W, dtype=F), np.arange(H, dtype=F)), -1))
         for f in range(4):
             st.frame(lt, tex, I, 900 + f, SEED + 5, motion=still, gp=_device_gp(pkg, _gp(c)))
         st.reset()
         for f in range(3):
-            st.frame(lt, tex, I, FRAME + f, SEED, motion=None if f == 0 else sh.dev(tr._motion(W, H, f)), gp=_device_gp(pkg, _gp(c)))
-            _assert_frame(st, I, want[f], f"after a used state's reset, frame {f}")
+            st.frame(lt, tex, I, FRAME + f, SEED, motion=None if f == 0 else sh.dev(_motion(W, H, f)), gp=_device_gp(pkg, _gp(c)))
+            assert_frame(st, I, want[f], "I", f"after a used state's reset, frame {f}")
     finally:
         sh.free(st, scene)
 
@@ -505,7 +472,7 @@ def test_one_candidate_equals_the_split_draw(pkg, W, H):
     st = pkg.RestirGI(scene, W, H)
     try:
         split = sh.draw(pkg, sh.TRACED, scene, W, H, s, lt, sh.trace_args(1, noise=0.0), split=True)
-        tex, I = sh.dev(split["gb"]), tr._out(W, H)      # noqa: E741
+        tex, I = sh.dev(split["gb"]), _out(W, H)      # noqa: E741
         st.frame(sh.light(pkg, lt), tex, I, FRAME, SEED, gp=pkg.gi_params(1, 0, 20.0, 0))
         torch.cuda.synchronize()
         H_ = st.read(0)
@@ -531,7 +498,7 @@ def test_the_posed_block_with_the_plane_of_motion_reproject(pkg):
     scene.enable_pose(n)
     st = pkg.RestirGI(scene, W, H)
     model = gm.State(gm.Scene(s), W, H)
-    t_x, mv, I = sh.motion_buffer(n), torch.empty((H, W, 2), dtype=torch.float32, device="cuda"), tr._out(W, H)      # noqa: E741
+    t_x, mv, I = sh.motion_buffer(n), torch.empty((H, W, 2), dtype=torch.float32, device="cuda"), _out(W, H)      # noqa: E741
     rgb, gbt = sh.buffers(W, H)
     kept = 0
     try:
@@ -545,7 +512,7 @@ def test_the_posed_block_with_the_plane_of_motion_reproject(pkg):
             model.sc = gm.Scene(s, geoms=pm.posed_scene(s, tables[f])["geoms"])
             Im, cnt = model.frame(gb, lt, gp, f, 3, motion=mv.cpu().numpy())
             kept += cnt["tap_accepted"] if f else 0
-            _assert_frame(st, I, dict(_state_of(model), I=Im), f"posed block, frame {f}")
+            assert_frame(st, I, dict(_state_of(model), I=Im), "I", f"posed block, frame {f}")
         assert kept > 1000, "the plane should keep history"
     finally:
         sh.free(st, scene)
@@ -556,7 +523,7 @@ def test_the_bending_tube_with_the_plane_of_deform_prev_positions(pkg):
     import torch
     from temporal_harness import scales
     W, H = 96, 54
-    s, (ti, bone, weight) = tr._tube_scene()
+    s, (ti, bone, weight) = _tube_scene()
     lt = ssm.light((0.0, 9.5, 0.0), (1.5, 0.0, 0.0), (0.0, 0.0, 1.5), 1)
     gp = gm.params(2, 1, 20.0, 3, 12.0)
     scene = sh.create(pkg, s)
@@ -567,13 +534,13 @@ def test_the_bending_tube_with_the_plane_of_deform_prev_positions(pkg):
     model = gm.State(gm.Scene(s), W, H)
     pose = sh.dev(pkg.binding.pose_identity(6))
     pos, gid = torch.empty((H, W, 3), dtype=torch.float32, device="cuda"), torch.empty((H, W), dtype=torch.int32, device="cuda")
-    mv, I = torch.empty((H, W, 2), dtype=torch.float32, device="cuda"), tr._out(W, H)      # noqa: E741
+    mv, I = torch.empty((H, W, 2), dtype=torch.float32, device="cuda"), _out(W, H)      # noqa: E741
     rgb, gbt = sh.buffers(W, H)
     tube_kept = 0
     try:
         for f, deg in enumerate((0.0, 4.5, 9.0)):
             scene.pose(pose)
-            rig.apply(sh.dev(pkg.deform.bend_bones(np.deg2rad(deg), tr.PIVOT)))
+            rig.apply(sh.dev(pkg.deform.bend_bones(np.deg2rad(deg), PIVOT)))
             pkg.scene_refit(scene)
             scene.draw(rgb, gbt, W, H, s["cam"], s["light"], f, seed=3)
             rig.prev_positions(pos, gid, W, H, s["cam"])
@@ -581,10 +548,10 @@ def test_the_bending_tube_with_the_plane_of_deform_prev_positions(pkg):
             st.frame(sh.light(pkg, lt), gbt, I, f, 3, motion=mv, gp=_device_gp(pkg, gp))
             torch.cuda.synchronize()
             gb = sh.host(pkg, rgb, gbt, W, H)[1]
-            model.sc = gm.Scene(s, tris=skin.apply(pkg.deform.bend_bones(np.deg2rad(deg), tr.PIVOT)["xf"], s["tris"]))
+            model.sc = gm.Scene(s, tris=skin.apply(pkg.deform.bend_bones(np.deg2rad(deg), PIVOT)["xf"], s["tris"]))
             Im, cnt = model.frame(gb, lt, gp, f, 3, motion=mv.cpu().numpy())
-            tube_kept += int(((gb["geomId"] == tr.TUBE_ID) & (model.T["M"] > gp["candidates"])).sum()) if f else 0
-            _assert_frame(st, I, dict(_state_of(model), I=Im), f"bending tube, frame {f}")
+            tube_kept += int(((gb["geomId"] == TUBE_ID) & (model.T["M"] > gp["candidates"])).sum()) if f else 0
+            assert_frame(st, I, dict(_state_of(model), I=Im), "I", f"bending tube, frame {f}")
         print(f"tube pixels that combined a history reservoir over frames 1 and 2: {tube_kept}")
         assert tube_kept > 0, "the plane should keep history on the tube"
     finally:
@@ -598,12 +565,12 @@ def test_a_captured_frame_is_two_kernel_nodes_and_replays_with_the_history_of_th
     c = MATRIX[2]
     W, H, kind, name = c[:4]
     s = sh.scene_input(kind, name)[0]
-    gb, lt, gp, mvh = _gb(kind, name, W, H), _light(kind, name, c[4]), _gp(c), tr._motion(W, H, 1)
+    gb, lt, gp, mvh = _gb(kind, name, W, H), _light(kind, name, c[4]), _gp(c), _motion(W, H, 1)
     scene = sh.create(pkg, s)
     st = pkg.RestirGI(scene, W, H)
     stream = sh.open_stream(True)
     try:
-        tex, mv, I, dl = sh.dev(gb), sh.dev(mvh), tr._out(W, H), sh.light(pkg, lt)      # noqa: E741
+        tex, mv, I, dl = sh.dev(gb), sh.dev(mvh), _out(W, H), sh.light(pkg, lt)      # noqa: E741
         torch.cuda.synchronize()
         record = lambda: st.frame(dl, tex, I, FRAME, SEED, motion=mv, gp=_device_gp(pkg, gp), stream=stream.cuda_stream)   # noqa: E731
         record()                                                          # once eagerly: a first launch may set kernel attributes
@@ -618,7 +585,7 @@ def test_a_captured_frame_is_two_kernel_nodes_and_replays_with_the_history_of_th
             graph.launch()
             stream.synchronize()
             Im, _ = model.frame(gb, lt, gp, FRAME, SEED, motion=mvh)
-            _assert_frame(st, I, dict(_state_of(model), I=Im), f"replay {k}")
+            assert_frame(st, I, dict(_state_of(model), I=Im), "I", f"replay {k}")
         graph.destroy(); reset.destroy()
     finally:
         stream.close()
@@ -636,7 +603,7 @@ def test_pose_both_resamplers_two_denoisers_compose_over_four_frames(pkg, orc):
     W, H = 96, 54
     s, tables = sh.block_inputs()
     n = len(s["geoms"])
-    lamps, rp = tr._lamps(64, "area"), rsm.params(8, 1, 20.0, 3, 12.0)
+    lamps, rp = _lamps(64, "area"), rsm.params(8, 1, 20.0, 3, 12.0)
     lt, gp = ssm.light(**sh.block_light()), gm.params(2, 1, 20.0, 3, 12.0)
     scene = sh.create(pkg, s)
     scene.enable_pose(n)
@@ -644,7 +611,7 @@ def test_pose_both_resamplers_two_denoisers_compose_over_four_frames(pkg, orc):
     den_d.set_capture(True); den_i.set_capture(True)
     model_d, model_i = rsm.State(rsm.Scene(s), W, H), gm.State(gm.Scene(s), W, H)
     t_x, mv = sh.motion_buffer(n), torch.empty((H, W, 2), dtype=torch.float32, device="cuda")
-    D, I, out_d, out_i, comp = (tr._out(W, H) for _ in range(5))      # noqa: E741
+    D, I, out_d, out_i, comp = (_out(W, H) for _ in range(5))      # noqa: E741
     rgb, gbt = sh.buffers(W, H)
     p = synth_params(pkg, W, H, sepcolor=1, addcolor=0)
     fed_d, fed_i, states_d, states_i = [], [], [], []
@@ -653,7 +620,7 @@ def test_pose_both_resamplers_two_denoisers_compose_over_four_frames(pkg, orc):
             scene.pose(sh.dev(tables[f]), t_x)
             scene.draw(rgb, gbt, W, H, s["cam"], s["light"], f, seed=3)
             pkg.binding.motion_reproject(mv, W, H, s["cam"], gbuffer=gbt, geom_xf=t_x, n_geoms=n, reproj_scale=scales(pkg, W, H))
-            di.frame(table, gbt, D, f, 3, motion=mv, rp=tr._device_rp(pkg, rp), ambient=tr.AMBIENT)
+            di.frame(table, gbt, D, f, 3, motion=mv, rp=_device_rp(pkg, rp), ambient=AMBIENT)
             gi.frame(sh.light(pkg, lt), gbt, I, f, 3, motion=mv, gp=_device_gp(pkg, gp))
             den_d.denoise(out_d, D, gbt, s["cam"], p)
             den_i.denoise(out_i, I, gbt, s["cam"], p)
@@ -662,7 +629,7 @@ def test_pose_both_resamplers_two_denoisers_compose_over_four_frames(pkg, orc):
             gb = sh.host(pkg, rgb, gbt, W, H)[1]
             posed = pm.posed_scene(s, tables[f])["geoms"]
             model_d.sc, model_i.sc = rsm.Scene(s, geoms=posed), gm.Scene(s, geoms=posed)
-            Dm, _ = model_d.frame(gb, lamps, rp, f, 3, tr.AMBIENT, motion=mv.cpu().numpy())
+            Dm, _ = model_d.frame(gb, lamps, rp, f, 3, AMBIENT, motion=mv.cpu().numpy())
             Im, _ = model_i.frame(gb, lt, gp, f, 3, motion=mv.cpu().numpy())
             assert not tsm.differing(D.cpu().numpy(), Dm).any() and not tsm.differing(I.cpu().numpy(), Im).any(), f"frame {f}: D and I"
             fed_d.append((Dm, gb)); fed_i.append((Im, gb))
@@ -693,8 +660,8 @@ def test_errors_with_a_device(pkg):
         assert lib.svgf_restir_gi_create(scene.h, 0, H, ctypes.byref(h)) == ERR and lib.svgf_restir_gi_create(scene.h, W, -1, ctypes.byref(h)) == ERR
         assert lib.svgf_restir_gi_create(scene.h, 1 << 13, 1 << 13, ctypes.byref(h)) == UNSUPPORTED and lib.svgf_restir_gi_create(scene.h, W, H, None) == ERR
         gb = _gb("made", "stage", W, H)
-        tex, I = sh.dev(gb), tr._out(W, H)      # noqa: E741
-        planes, keep = tr._planes_of(pkg, gb)
+        tex, I = sh.dev(gb), _out(W, H)      # noqa: E741
+        planes, keep = _planes_of(pkg, gb)
         sp = B.SvgfSynthParams(FRAME, SEED, 0.0, 0.0, (0.0, 0.0))
         lt = sh.light(pkg, _light("made", "stage"))
         st.frame(lt, tex, I, FRAME, SEED, gp=G.gi_params(4, 1, 20.0, 2))
@@ -731,6 +698,6 @@ def test_errors_with_a_device(pkg):
         st.frame(lt, tex, I, FRAME, SEED, gp=G.gi_params(4, 1, 20.0, 2))
         torch.cuda.synchronize()
         after = _read(st)
-        assert all(tr.same_bytes(before[k], after[k]) for k in before) and tr.same_bytes(I0, I.cpu().numpy()), "after a reset the same frame leaves the same bytes"
+        assert all(same_bytes(before[k], after[k]) for k in before) and same_bytes(I0, I.cpu().numpy()), "after a reset the same frame leaves the same bytes"
     finally:
         sh.free(st, small, scene, scene_clash)
